@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: residue x diffusion-steps / s of the sampler hot loop (BASELINE.json metric).
 
-    python bench.py --gpus 1 [--steps K] [--warmup W] [--config c4|c2|c3|c5] [--precision fp16|fp32]
+    python bench.py --gpus 1 [--steps K] [--warmup W] [--config c4|c2|c3|c5] [--precision fp16|fp32] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -19,8 +19,16 @@ caller always passes it, experiments/inference.py:218,331): score-network forwar
 reverse step + atom37 frame of x_{t-1}, trajectory writes.  By default K = T: W warm-up steps on a scratch trajectory, then
 the WHOLE trajectory is timed (self-conditioning priming forward + T steps, t = 1 -> min_t, the last step takes the x_0
 branch); with K < T a window of K consecutive steps in the middle of the schedule is timed (priming untimed), issued exactly as
-inference_fn issues them (chunked graph replays).  Inputs, weights and the noise tape are resident in HBM before the timed region; value = B*N*K*n_gpus / max-over-ranks.
-Every sample draws x_T and its noise tape from its own stream (seed + global sample index, framedipt_amd/sharding.py).
+inference_fn issues them (chunked graph replays); with K > T consecutive whole trajectories of the same batch are timed, each from
+x_T with its own priming forward, the last one cut after K mod T steps.  Inputs, weights and the noise tape are resident in HBM
+before the timed region; value = B*N*K*n_gpus / max-over-ranks; ms_per_step = timed region / K.
+Every sample draws x_T and its noise tape from its own stream (seed + global sample index, framedipt_amd/sharding.py): the same
+arguments give the same inputs on every run.
+
+--dump-outputs DIR: after the timed region, what its last step handed to the caller — the rows of that step in the arrays
+ReverseLoop.results() returns (prot_traj, rigid_traj: x_{t-1}, trans_traj, rigid_0_traj, psi_pred), batch on axis 0, float32 — as
+DIR/<name>.npy (rank r > 0 of a multi-GPU run: DIR/<name>_rank<r>.npy), so that two builds can be compared output for output.
+Above DUMP_BYTES in all, a fixed seeded sample of the batch rows is written instead.
 
 Also on the JSON line:
   loop         : how the timed steps were issued — the default product path (inference.ReverseLoop: cursor-addressed launches replayed
@@ -59,6 +67,7 @@ NOMINAL_GHZ = 2.4  # engine clock of PEAK_TFLOPS (MI355X_MICROARCH.md)
 ET4_EXEC_FLOPS_PER_PAIR = (504 + 24) * 32 * 32 * 16 * 2 / 32.0
 FUSED_FLOPS_PER_PAIR = 2.0 * 128 * (8 + 32)  # linear_b (ipa_pytorch.py:247) + down_z (:158,318) of the next block, reference formulation
 PEAK_TFLOPS = {"fp16": 2500.0, "bf16": 2500.0, "fp32": 157.3}  # dense MFMA peaks, MI355X_MICROARCH.md
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: all files of all ranks together
 
 CONFIGS = {
     "c2": dict(n=128, b=8, t=500, prec="fp16", inpaint=False),
@@ -95,6 +104,19 @@ def flops_per_forward(n: int, inpainting: bool = False) -> float:
     """SURVEY.md 8d / BASELINE.md section 3: reference-formulation FLOPs of one score-network forward."""
     c2 = 2248960.0 + (107008.0 - 96256.0 if inpainting else 0.0)
     return c2 * n * n + 32.4e6 * n
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0, world: int = 1):
+    """--dump-outputs: `arrays` (name -> float array, batch on axis 0) as out_dir/<name>.npy (rank r > 0: <name>_rank<r>.npy); above
+    DUMP_BYTES / world, the batch rows of a fixed seeded sample only (the same rows on every run)."""
+    B = next(iter(arrays.values())).shape[0]
+    keep = max(1, int(DUMP_BYTES // world // (sum(v.nbytes for v in arrays.values()) / B)))
+    if keep < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy" if rank == 0 else f"{k}_rank{rank}.npy"), v)
 
 
 def synthetic_complex(chain_lens, windows, seed=0):
@@ -177,7 +199,8 @@ def cpu_baseline(n: int, conf, seed: int, steps: int = 10):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: the whole schedule of the config)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: the whole schedule of the config; more than num_t: "
+                    "consecutive whole trajectories)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--n-res", type=int, default=None)
@@ -191,6 +214,7 @@ def main():
     ap.add_argument("--no-reference-precision", action="store_true", help="skip the fp32 (reference precision) sub-record")
     ap.add_argument("--reference-steps", type=int, default=6, help="timed steps of the fp32 sub-record")
     ap.add_argument("--seed", type=int, default=123)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="weak (default): --samples-per-gpu samples on EVERY GPU; strong: the "
                     "config's whole sample set (c4: BASELINE configs[3]'s 64 samples) split over the GPUs, so that value(N) / value(1) is the "
                     "speed-up of a fixed job")
@@ -221,8 +245,8 @@ def main():
         prec = "bf16"
         os.environ["FDIPT_LIB"] = os.path.join(ROOT, "framedipt_amd", "lib", "libfdipt_hip_bf16.so")  # (read when the package loads the library)
     K = a.steps if a.steps is not None else T
-    if K > T or K < 1:
-        raise SystemExit("--steps must lie in [1, num_t]")
+    if K < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -317,10 +341,11 @@ def main():
     nb = conf.model.ipa.num_blocks
     n_ev = nb - 1
 
-    def timed_region(net, prec, K, warmup, streams, feats=feats, tape=tape, B=B):
-        """W warm-up steps on a scratch trajectory, then K timed steps (the whole trajectory incl. the priming forward when K == T)
-        of the batch (`feats`, `tape`: the rank's batch unless given) with `net`; returns (seconds, D2H seconds, D2H bytes,
-        EdgeTransition launch ms list, clock counters, B_ev)."""
+    def timed_region(net, prec, K, warmup, streams, feats=feats, tape=tape, B=B, outputs=None):
+        """W warm-up steps on a scratch trajectory, then K timed steps (the whole trajectory incl. the priming forward when K == T,
+        whole trajectories one after the other when K > T) of the batch (`feats`, `tape`: the rank's batch unless given) with `net`;
+        returns (seconds, D2H seconds, D2H bytes, EdgeTransition launch ms list, clock counters, B_ev).  `outputs` (a dict): receives
+        the rows the last timed step wrote (--dump-outputs)."""
         def new_loop():
             if streams > 1:
                 return inference.StreamedLoops(net, diff, feats, streams, T, 0.01, noise_tape=tape, reserve_cus=a.reserve_cus, aux_traj=True,
@@ -331,13 +356,14 @@ def main():
             return lp
         # timed steps: the whole schedule, or a window of K CONSECUTIVE steps in the middle of it (the loop's steady state: chunked graph
         # replays exactly as inference_fn issues them; the window starts from x_T's frames copied into its first row, so every timed step
-        # works on a valid state and hands it to the next one)
-        k0 = 0 if K == T else max(0, (T - 1 - K) // 2)
-        steps = list(range(k0, k0 + K))
-        # HIP events around every EdgeTransition launch of a few of the timed steps (recorded on the launch stream by the library):
-        # up to 16 of a whole trajectory, at most 4 when K <= 32
-        n_samp = min(K, 16 if K > 32 else 4)
-        sampled = sorted({steps[int(round(i * (K - 1) / max(n_samp - 1, 1)))] for i in range(n_samp)})
+        # works on a valid state and hands it to the next one); K > T: passes over the whole schedule, the last one cut short
+        k0 = 0 if K >= T else max(0, (T - 1 - K) // 2)
+        passes = [(k0, k0 + K)] if K <= T else [(0, T)] * (K // T) + ([(0, K % T)] if K % T else [])
+        steps = list(range(*passes[0]))
+        # HIP events around every EdgeTransition launch of a few of the timed steps of the first pass (recorded on the launch stream by
+        # the library): up to 16 of a whole trajectory, at most 4 when K <= 32
+        n_samp = min(len(steps), 16 if K > 32 else 4)
+        sampled = sorted({steps[int(round(i * (len(steps) - 1) / max(n_samp - 1, 1)))] for i in range(n_samp)})
         events = {}
         for k in sampled:
             ev_s, ev_e = (C.c_void_p * nb)(), (C.c_void_p * nb)()
@@ -356,6 +382,10 @@ def main():
         t_setup = time.perf_counter()
         loop = new_loop()
         st = loop.st
+        lps = loop.loops if streams > 1 else [loop]
+        # every pass after the first starts a new trajectory: self-conditioning from the sampler's sc_ca_t again, on each loop's stream
+        sc0 = [lp.sc_ca.clone() for lp in lps] if len(passes) > 1 else None
+        lp_streams = loop.streams if streams > 1 else [torch.cuda.current_stream()]
         # in-kernel shader-clock probe of the EdgeTransition launches: opt-in, into a caller-owned buffer (FdiptForwardArgs.clock_out),
         # only on the sampled steps the HIP events bracket
         clk_dev = torch.zeros(3, dtype=torch.int64, device=dev)
@@ -374,28 +404,39 @@ def main():
             st.clock_out = clk_dev if k in events else None
         if K < T:
             loop.prime()
-            for lp in (loop.loops if streams > 1 else [loop]):
+            for lp in lps:
                 lp.rigid_traj[k0].copy_(lp.rigid_traj[0])
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        if streams == 1:
-            if K == T:
+        for p, (kb, ke) in enumerate(passes):
+            if p:
+                bracket(None)
+                for lp, s, sc in zip(lps, lp_streams, sc0):
+                    with torch.cuda.stream(s):
+                        lp.sc_ca.copy_(sc)
+            if K >= T:
                 loop.prime()
-            loop.run_steps(k0, k0 + K, eager_steps=sampled, before_step=bracket)
-        else:
-            if K == T:
-                loop.prime()
-            for k in steps:
-                bracket(k)
-                loop.step(k)
+            if streams == 1:
+                loop.run_steps(kb, ke, eager_steps=sampled if p == 0 else (), before_step=bracket)
+            else:
+                for k in range(kb, ke):
+                    if p == 0:
+                        bracket(k)
+                    loop.step(k)
         host_s = time.perf_counter() - t0  # host time to enqueue the region (the GPU runs behind it)
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         st.ev_start = st.ev_stop = st.clock_out = None
         clk = [int(v) for v in clk_dev.cpu()]
+        if outputs is not None:  # rows of the last timed step k, in the loop's own (unflipped) trajectory order
+            k = passes[-1][1] - 1
+            for name, row in (("prot_traj", lambda lp: lp.prot_traj[k]), ("rigid_traj", lambda lp: lp.rigid_traj[k + 1]),
+                              ("trans_traj", lambda lp: lp.trans_traj[k]), ("rigid_0_traj", lambda lp: lp.bb0_traj[k]),
+                              ("psi_pred", lambda lp: lp.st.psi)):
+                outputs[name] = torch.cat([row(lp) for lp in lps]).float().cpu().numpy()
         d2h = d2h_bytes = None
         if K == T:  # D2H of the whole trajectories, as inference_fn returns them (never part of `value`; only meaningful for a whole run)
             t1 = time.perf_counter()
@@ -431,7 +472,7 @@ def main():
         et_flops = ET_FLOPS_PER_PAIR * B_ev * N * N
         peak = PEAK_TFLOPS[prec]
         achieved = et_flops / et / 1e12
-        fwd_per_step = (T + 1) / T if K == T else 1.0
+        fwd_per_step = (K + (-(-K // T) if K >= T else 0)) / K  # + the priming forward of each (begun) whole trajectory
         fwd_tflops = fwd_flops_per_step * K / el / world * fwd_per_step / 1e12  # whole-forward view, per GPU (real residues only)
         et4 = prec in ("fp16", "bf16") and N % 4 == 0 and not (kernel_flags & 1)  # (FDIPT_KF_ET3 forces the fallback kernel)
         ghz = clk[0] / clk[1] / 10 if clk[1] else None
@@ -459,7 +500,10 @@ def main():
                          "backbone RMSD vs the reference 1.7e-3 A worst / 4e-4 A median (teacher-forced, N=64, T=20: "
                          "tests/test_gpu_round4.py::test_bf16_build_per_step_numbers): outside the 1e-3 A parity bar, a comparison line only",
                  "fp32": "fp32 (v_mfma_f32_32x32x2_f32): the reference's arithmetic"}
-    el, d2h, d2h_bytes, et_ms, clk, B_ev, loop_rec = timed_region(net, prec, K, a.warmup, a.streams)
+    last = {} if a.dump_outputs else None
+    el, d2h, d2h_bytes, et_ms, clk, B_ev, loop_rec = timed_region(net, prec, K, a.warmup, a.streams, outputs=last)
+    if last:
+        dump_outputs(a.dump_outputs, last, rank, world)
     all_rec = None
     if (world == 1 and a.config == "c4" and prec != "fp32" and a.scaling == "weak" and not a.no_all_samples and a.streams == 1
             and a.n_res is None and a.total_samples > B):
@@ -504,7 +548,7 @@ def main():
             "config": {"workload": f"{a.config}: {'inpainting' if inp else 'de novo'} backbone sampler, "
                                    + (f"{B} different complexes/GPU of N={min(all_len)}..{max(all_len)} (mean {np.mean(all_len):.0f}) padded to {N}, "
                                       if mixed else f"N={N}, {B} samples/GPU ") +
-                                   f"batched, {'whole trajectory (priming forward + all steps)' if K == T else f'{K} consecutive steps from the middle of the schedule'}"
+                                   f"batched, {'whole trajectory (priming forward + all steps)' if K == T else f'{K} consecutive steps from the middle of the schedule' if K < T else f'{K} steps of consecutive whole trajectories (a priming forward each)'}"
                                    f" of T={T}, aux_traj=True, noise_scale 0.1, 17.4M-param synthetic weights, per-sample seeds",
                        "n_res": N, "samples_per_gpu": B, "total_samples": n_total, "num_t": T, "parallelism": f"sample-sharded x{world}, no collective" + (f", {a.streams} sub-batch streams per GPU" if a.streams > 1 else ""),
                        "precision_mode": PREC_MODE[prec], "kernel_flags": a.kernel_flags},

@@ -298,6 +298,32 @@ def test_bench_line_of_the_driver_command_shape():
     assert abs(d["value"] - 8 * 128 * 12 / (d["ms_per_step"] * 12e-3)) / d["value"] < 1e-6
 
 
+def test_bench_steps_beyond_the_schedule_and_dumped_outputs(tmp_path):
+    """bench.py --steps K > num_t times K steps of consecutive whole trajectories of the same batch, so that 2T steps end on the same x_0
+    step as T steps: the --dump-outputs files (the rows of the last timed step, float32, batch on axis 0) agree bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = {}
+    for k in (8, 16):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "c2", "--num-t", "8", "--steps", str(k), "--warmup", "2",
+               "--no-cpu-baseline", "--no-reference-precision", "--dump-outputs", str(tmp_path / f"k{k}")]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == k and d["ms_per_step"] > 0
+        dumps[k] = {p.name: np.load(p) for p in (tmp_path / f"k{k}").iterdir()}
+    assert sorted(dumps[8]) == ["prot_traj.npy", "psi_pred.npy", "rigid_0_traj.npy", "rigid_traj.npy", "trans_traj.npy"]
+    assert dumps[8]["prot_traj.npy"].shape == (8, 128, 37, 3) and dumps[8]["rigid_traj.npy"].shape == (8, 128, 7)
+    for name, v in dumps[8].items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), name
+        assert v.tobytes() == dumps[16][name].tobytes(), name
+
+
 def test_batch_of_64_n300_keeps_a_samples_bits():
     """bench.py's all_samples_one_gpu batch (64 samples at N = 300, fp16 mode): samples 0, 31 and 63 of the batch are torch.equal to their B = 1
     runs, sample 0 is the reference golden — the 64-sample sub-record times the kernels the parity suite pins."""

@@ -534,3 +534,23 @@ def test_kernel_flag_constants_match_the_header():
     for k in names:
         assert getattr(_lib, "KF_" + k) == macros[k], k
     assert macros["ALL"] == sum(macros[k] for k in names)
+
+
+def test_bench_dump_outputs_names_and_size_cap(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every array as <name>.npy (rank r > 0: <name>_rank<r>.npy); above DUMP_BYTES / world, the
+    same seeded sample of batch rows on every call, under the cap."""
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"prot_traj": rng.standard_normal((64, 1000, 37, 3)).astype(np.float32), "psi_pred": rng.standard_normal((64, 1000, 2)).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, v in arrays.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "all" / f"{k}.npy"), v)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, rank=3, world=4)
+        assert sorted(os.listdir(tmp_path / run)) == ["prot_traj_rank3.npy", "psi_pred_rank3.npy"]
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= bench.DUMP_BYTES / 4
+    a, b = (np.load(tmp_path / r / "prot_traj_rank3.npy") for r in ("a", "b"))
+    assert 1 <= a.shape[0] < 64 and a.tobytes() == b.tobytes()
+    rows = [int(np.flatnonzero((arrays["prot_traj"] == x).all(axis=(1, 2, 3)))[0]) for x in a]
+    assert rows == sorted(set(rows))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "psi_pred_rank3.npy"), arrays["psi_pred"][rows])
