@@ -55,6 +55,278 @@ __device__ __forceinline__ hx8 p2_frag(unsigned off) { return __builtin_bit_cast
 #define P2S_HALF 32768                      // one part (hi or lo) of a half column block: 2 tiles x 16 k-steps x 1 KB
 #define P2S_STAGE (2 * P2S_HALF)            // hi | lo
 #define P2S_BIAS_OFF (2 * P2S_STAGE)        // fp32 bias of every column (zero-padded to whole column blocks)
+// ---- point epilogue (ProjArgs.pts_img; fd_ipa_proj2_points_supported: H = 8, C = 256, Pq = 8, Pv = 12, split operands)
+// The 672 point columns of the merged projection are regrouped (fd_ipa_proj2_points_image) into 6 column blocks of whole point groups
+// (x, y, z of a point side by side, the 8 or 12 points of one head together): blocks 0..3 = [v_pts of heads 2c, 2c + 1 (36 columns
+// each) | k_pts of heads 2c, 2c + 1 (24 each) | 8 zero], blocks 4, 5 = [q_pts of heads 4 (c - 4) .. 4 (c - 4) + 3 (24 each) | 32 zero].
+// Regrouped point column n -> column of the [q_pts | kv_pts] planes (-1: zero column)
+__host__ __device__ __forceinline__ int p2p_src_col(int n) {
+  const int c = n >> 7, col = n & 127;
+  if (c < 4) {
+    if (col < 72) { const int vh = col / 36, r = col % 36; return 192 + (r % 3) * 160 + (2 * c + vh) * 20 + 8 + r / 3; }
+    if (col < 120) { const int r = col - 72, kh = r / 24, q = r % 24; return 192 + (q % 3) * 160 + (2 * c + kh) * 20 + q / 3; }
+    return -1;
+  }
+  if (c > 5 || col >= 96) return -1;
+  const int hq = col / 24, r = col % 24;
+  return (r % 3) * 64 + (4 * (c - 4) + hq) * 8 + r / 3;
+}
+#define P2P_COLS 768  // regrouped point columns (6 blocks)
+typedef __attribute__((address_space(3))) f32x4* p2_lds_f32x4w;
+typedef __attribute__((address_space(3))) u16x8* p2_lds_u16x8w;
+typedef const __attribute__((address_space(3))) unsigned* p2_lds_u32;
+
+// the 8 fragment units of one (key, head) of the key-point image (kernels.hpp: fd_kpf layout), as points16_kernel forms them
+__device__ __forceinline__ void p2_kpf_units(const ProjArgs& a, const float (&kv)[24], bool lv, int b, int h, int key, int ntl) {
+#pragma unroll
+  for (int un = 0; un < 8; ++un) {
+    const int f = un >> 1, hf = un & 1;
+    unsigned short o[8];
+    if (f == 3 && hf == 1) {
+      float kn = 0.f;
+      if (lv)
+#pragma unroll
+        for (int c = 0; c < 24; ++c) kn = fmaf(kv[c], kv[c], kn);
+      const float m = lv ? a.res_mask[(long)b * a.N + key] : 0.f;
+      const float t0 = fmaxf(-0.5f * a.gamma[h] * kn, -65000.f);
+      const unsigned short p0 = f2f16(t0);
+      const float t1 = t0 - f162f(p0);
+      const unsigned short p1 = f2f16(t1);
+      const unsigned short p2 = f2f16(t1 - f162f(p1));
+      o[0] = f2f16(2.f * m); o[1] = f2f16(m); o[2] = f2f16(lv ? 0.f : -60000.f); o[3] = p0; o[4] = p1; o[5] = p2; o[6] = o[7] = 0;
+    } else {
+      const int c0 = f < 2 ? 8 * hf : 16;
+      const bool lo = f == 1 || (f == 2 && hf == 1);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float x = lv ? kv[c0 + e] : 0.f;
+        const unsigned short xh = f2f16(x);
+        o[e] = lo ? f2f16(x - f162f(xh)) : xh;
+      }
+    }
+    const p2_u32x4 val = {o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16), o[4] | ((unsigned)o[5] << 16), o[6] | ((unsigned)o[7] << 16)};
+    *(p2_u32x4*)(a.kpf + ((((((long)b * a.H + h) * ntl + (key >> 5)) * FD_KPF_FRAGS + f) * 64 + hf * 32 + (key & 31)) << 3)) = val;
+  }
+}
+
+// A point walker: per column block, both halves' products (no epilogue under them: the block's results are wanted all at once),
+// then the 256 x 128 fp32 results + bias go to the freed weight stages as a column-major tile (16 B row groups XOR-swizzled by the
+// column: conflict-free b128 writes of a lane's 4-runs of rows and b32 / b128 reads along the rows) and the 512 threads do the
+// per-residue work of points16_kernel from it: global frame R p + t, qp rows, the kpf units (gamma, mask, the padded keys of a
+// sample that ends in this row block), the v_pts hi / lo image in 8 B pieces (4-runs of keys: N % 4 == 0).
+// fr: LDS address of R (9) and t (3) of the block's rows, [12][256] fp32.
+template <class RQ>
+__device__ __forceinline__ void p2_points_walk(const ProjArgs& a, const hx8 (&Af)[P2_KS], const hx8 (&Al)[P2_KS], int n_class, int nq, int walker,
+                                               int n_walkers, unsigned lds0, unsigned fr, RQ& request_half) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, hi = lane >> 5;
+  const int M = a.B * a.N, m0 = blockIdx.x * 256, H = a.H, ntl = a.Np >> 5, ks = a.Np >> 4;
+  auto tile_at = [&](int col, int rg) { return lds0 + (unsigned)(col * 1024 + ((rg ^ (col & 63)) << 4)); };  // rows 4 rg .. 4 rg + 3
+  auto rotate = [&](int row, float px, float py, float pz, float* g3) {
+    float R[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) R[i] = *(p2_lds_f32)(unsigned long)(fr + 4 * (i * 256 + row));
+    g3[0] = R[0] * px + R[1] * py + R[2] * pz + R[9];
+    g3[1] = R[3] * px + R[4] * py + R[5] * pz + R[10];
+    g3[2] = R[6] * px + R[7] * py + R[8] * pz + R[11];
+  };
+  for (int k = walker; k < n_class; k += n_walkers) {
+    const int c = nq + k;
+    const bool frames = k == walker && tid < 256;  // first column block: the frames of the rows ride with its weight requests
+    f32x4 fq = {0.f, 0.f, 0.f, 0.f};
+    float ft[3] = {0.f, 0.f, 0.f};
+    if (frames) {
+      const int gr = m0 + tid < M ? m0 + tid : M - 1;
+      fq = *(const f32x4*)(a.quat + (long)gr * 4);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) ft[d] = a.trans[(long)gr * 3 + d];
+    }
+    __syncthreads();  // the tile of the previous column block is consumed: both stages are free
+    request_half(c, 0, 0);
+    request_half(c, 1, 1);
+    // half h of the column block (weights in stage h) -> columns 64 h .. 64 h + 63 of the tile = bytes of stage h: written as soon as
+    // every wave is done with that stage (the other half's requests still landing in the other stage)
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half) {
+      if (half == 0) __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8): the frames and this thread's share of half 0 have landed
+      else __builtin_amdgcn_s_waitcnt(0x0F70);
+      if (half == 0 && frames) {  // R (quat_to_rot, openfold/utils/rigid_utils.py:173-205, no normalisation) and t -> LDS [12][256]
+        const float w = fq[0], x = fq[1], y = fq[2], z = fq[3];
+        float R[9];
+        R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * x * y - 2 * w * z; R[2] = 2 * x * z + 2 * w * y;
+        R[3] = 2 * x * y + 2 * w * z; R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * y * z - 2 * w * x;
+        R[6] = 2 * x * z - 2 * w * y; R[7] = 2 * y * z + 2 * w * x; R[8] = w * w - x * x - y * y + z * z;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) *(__attribute__((address_space(3))) float*)(unsigned long)(fr + 4 * (i * 256 + tid)) = i < 9 ? R[i] : ft[i - 9];
+        if (walker == 0 && m0 + tid < M)  // (one point walker per row block writes the rotations: attention3's o_pt reads them)
+#pragma unroll
+          for (int i = 0; i < 9; ++i) a.rot[(long)(m0 + tid) * 9 + i] = R[i];
+      }
+      __syncthreads();
+      f32x16 acc[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+        const unsigned wbh = lds0 + half * P2S_STAGE + j * (P2_KS * 1024) + lane * 16, wbl = wbh + P2S_HALF;
+        // fragments two k-steps ahead of their products, pinned (as in the other walkers)
+        constexpr int DEPTH = 3;
+        hx8 wh[DEPTH], wl[DEPTH];
+#pragma unroll
+        for (int s = 0; s < DEPTH - 1; ++s) { wh[s] = p2_frag(wbh + s * 1024); wl[s] = p2_frag(wbl + s * 1024); }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s = 0; s < P2_KS; ++s) {  // (the order of the three products of the other point epilogue: same sums)
+          if (s + DEPTH - 1 < P2_KS) {
+            wh[(s + DEPTH - 1) % DEPTH] = p2_frag(wbh + (s + DEPTH - 1) * 1024);
+            wl[(s + DEPTH - 1) % DEPTH] = p2_frag(wbl + (s + DEPTH - 1) * 1024);
+          }
+          const hx8 h = wh[s % DEPTH], l = wl[s % DEPTH];
+          acc[j] = fd_mfma32(Af[s], l, acc[j]);
+          acc[j] = fd_mfma32(Al[s], h, acc[j]);
+          acc[j] = fd_mfma32(Af[s], h, acc[j]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      float bv[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bv[j] = *(p2_lds_f32)(unsigned long)(lds0 + P2S_BIAS_OFF + 4 * (c * 128 + 64 * half + 32 * j + li));
+      __syncthreads();  // every wave is done with stage `half`: it becomes these columns of the tile
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {  // register 4 g + q = row 8 g + 4 hi + q of the wave's 32 (32 x 32 MFMA layout), column li
+          const f32x4 v = {acc[j][4 * g] + bv[j], acc[j][4 * g + 1] + bv[j], acc[j][4 * g + 2] + bv[j], acc[j][4 * g + 3] + bv[j]};
+          *(p2_lds_f32x4w)(unsigned long)tile_at(64 * half + 32 * j + li, 8 * wave + 2 * g + hi) = v;
+        }
+    }
+    __syncthreads();
+    auto tv = [&](int row, int col) { return *(p2_lds_f32)(unsigned long)(tile_at(col, row >> 2) + 4 * (row & 3)); };
+    // (the thread index as an opaque value per column block: else the compiler hoists every LDS address of the tasks below out of
+    //  the walk and spills them)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    if (k < 4) {
+      {  // key points of heads 2 k + kh: one thread per (row, kh)
+        const int row = tid & 255, kh = tid >> 8, m = m0 + row;
+        if (m < M) {
+          const int b = m / a.N, key = m - b * a.N;
+          float kv[24];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int col = 72 + 24 * kh + 3 * e;
+            rotate(row, tv(row, col), tv(row, col + 1), tv(row, col + 2), kv + 3 * e);
+          }
+          p2_kpf_units(a, kv, true, b, 2 * k + kh, key, ntl);
+        }
+        // padded keys [N, Np) of the samples that end in this row block
+        const int npad = a.Np - a.N;
+        if (npad > 0)
+          for (int bs = m0 / a.N; bs < a.B && bs * a.N < m0 + 256; ++bs) {
+            const int end = bs * a.N + a.N - 1;
+            if (end < m0 || end >= m0 + 256) continue;
+            float z[24];
+#pragma unroll
+            for (int q = 0; q < 24; ++q) z[q] = 0.f;
+#pragma unroll 1
+            for (int u = tid; u < 2 * npad; u += 512) p2_kpf_units(a, z, false, bs, 2 * k + (u & 1), a.N + (u >> 1), ntl);
+          }
+      }
+      // value points of heads 2 k + vh: one thread per (4-run of rows, vh, point e): 8 B pieces of the hi / lo rows of the image
+#pragma unroll 1
+      for (int t = tid; t < 64 * 24; t += 512) {
+        const int k4 = t & 63, rest = t >> 6, vh = rest / 12, e = rest - 12 * vh, mg = m0 + 4 * k4;
+        if (mg >= M) continue;  // (M % 4 == 0: the 4-run is whole)
+        const int b = mg / a.N, key = mg - b * a.N, pp = (key & ~15) + p2_perm16(key & 15), h = 2 * k + vh;
+        f32x4 pc[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) pc[d] = *(p2_lds_f32x4)(unsigned long)tile_at(36 * vh + 3 * e + d, k4);
+        unsigned short vhs[3][4], vls[3][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float g3[3];
+          rotate(4 * k4 + q, pc[0][q], pc[1][q], pc[2][q], g3);
+#pragma unroll
+          for (int d = 0; d < 3; ++d) {
+            const unsigned short vh16 = f2h(g3[d]);
+            vhs[d][q] = vh16;
+            vls[d][q] = f2h(g3[d] - h2f(vh16));
+          }
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const int rw = 3 * e + d, rl = 36 + rw;
+          const long bh3 = ((long)b * H + h) * 3;
+          const long oh = ((((bh3 + (rw >> 5)) * ks + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (rw & 31)) << 3) + (pp & 7);
+          const long ol = ((((bh3 + (rl >> 5)) * ks + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (rl & 31)) << 3) + (pp & 7);
+          *(p2_u32x2*)(a.vpt + oh) = p2_u32x2{vhs[d][0] | ((unsigned)vhs[d][1] << 16), vhs[d][2] | ((unsigned)vhs[d][3] << 16)};
+          *(p2_u32x2*)(a.vpt + ol) = p2_u32x2{vls[d][0] | ((unsigned)vls[d][1] << 16), vls[d][2] | ((unsigned)vls[d][3] << 16)};
+        }
+      }
+    } else {
+      // query points of heads 4 (k - 4) + hq: one thread per (row, hq), the head's 8 points = 24 consecutive floats of qp
+#pragma unroll 1
+      for (int t = tid; t < 1024; t += 512) {
+        const int row = t & 255, hq = t >> 8, m = m0 + row;
+        if (m >= M) continue;
+        float g[24];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int col = 24 * hq + 3 * e;
+          rotate(row, tv(row, col), tv(row, col + 1), tv(row, col + 2), g + 3 * e);
+        }
+        float* dst = a.qp + ((long)m * H * 8 + (4 * (k - 4) + hq) * 8) * 3;
+#pragma unroll
+        for (int v = 0; v < 6; ++v) *(f32x4*)(dst + 4 * v) = f32x4{g[4 * v], g[4 * v + 1], g[4 * v + 2], g[4 * v + 3]};
+      }
+    }
+  }
+}
+
+// Node-row images of the merged projection (the work of fd_node_images, padded keys excepted) from a Q walker's activation fragments:
+// Af / Al of lane (li, hi), k-step s = the hi / lo parts of row li of the wave's 32, channels 16 s + 8 hi .. + 7 — exactly the units
+// of Kb (hi parts) and the values of Vt / Vt_lo (same conversions as fd_node_images).  Part 0 (Kb): straight from the registers;
+// parts 1, 2 (Vt, Vt_lo): transposed through the wave's 16 KB of the freed weight stages (rows of 512 B, 16 B chunks XOR-swizzled
+// by the row as in the staging), a lane forming the 8 B pieces (4 keys) of two adjacent channels.  Walker p % n_walkers does part p.
+__device__ __forceinline__ void p2_node_rows(const ProjArgs& a, const hx8 (&Af)[P2_KS], const hx8 (&Al)[P2_KS], int walker, int n_walkers,
+                                             unsigned lds0) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, hi = lane >> 5;
+  const int M = a.B * a.N, mw = blockIdx.x * 256 + wave * 32, ntl = a.Np >> 5;
+  for (int p = walker; p < 3; p += n_walkers) {
+    if (p == 0) {
+      const int m = mw + li;
+      if (m < M) {
+        const int b = m / a.N, r = m - b * a.N;
+        half_t* dst = a.Kb + ((((long)b * ntl + (r >> 5)) * 16) * 64 + hi * 32 + (r & 31)) * 8;
+#pragma unroll
+        for (int s = 0; s < P2_KS; ++s) *(hx8*)(dst + s * 64 * 8) = Af[s];
+      }
+      continue;
+    }
+    __syncthreads();  // every wave is done with the weight stages (p depends on the block only)
+    const unsigned xl = lds0 + wave * (32 * P2_XROW);
+#pragma unroll
+    for (int s = 0; s < P2_KS; ++s)
+      *(p2_lds_u16x8w)(unsigned long)(xl + li * P2_XROW + (((2 * s + hi) ^ (li & 15)) << 4)) = __builtin_bit_cast(u16x8, p == 1 ? Af[s] : Al[s]);
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the wave's own rows have landed (wave-private region)
+    half_t* img = p == 1 ? a.Vt : a.Vt_lo;
+#pragma unroll 4
+    for (int t = 0; t < 16; ++t) {
+      const int task = t * 64 + lane, cc = 2 * (task & 127), k4 = task >> 7, mg = mw + 4 * k4;
+      unsigned w[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int rr = 4 * k4 + q;
+        w[q] = *(p2_lds_u32)(unsigned long)(xl + rr * P2_XROW + (((cc >> 3) ^ (rr & 15)) << 4) + (cc & 7) * 2);
+      }
+      if (mg >= M) continue;
+      const int b = mg / a.N, key = mg - b * a.N, pp = (key & ~15) + p2_perm16(key & 15);
+      const long u0 = ((((long)b * 8 + (cc >> 5)) * (2 * ntl) + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (cc & 31)) * 8 + (pp & 7);
+      *(p2_u32x2*)(img + u0) = p2_u32x2{(w[0] & 0xffffu) | (w[1] << 16), (w[2] & 0xffffu) | (w[3] << 16)};
+      *(p2_u32x2*)(img + u0 + 8) = p2_u32x2{(w[0] >> 16) | (w[1] & 0xffff0000u), (w[2] >> 16) | (w[3] & 0xffff0000u)};
+    }
+  }
+}
+
 template <bool QK, bool SPLIT>
 __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, int walker, int n_walkers, char* smem) {
   const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem;
@@ -168,6 +440,12 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the fragments are in registers before the buffer is overwritten
   }
   FD_STAMP(1);
+  if constexpr (SPLIT && !QK) {
+    if (a.pts_img) {
+      p2_points_walk(a, Af[0], Al[0], n_class, nq, kb, n_walkers, lds0, lds0 + P2S_BIAS_OFF + n_cblk * 512, request_half);
+      return;
+    }
+  }
   // ---- store addressing, split into a part that depends on the row(s) of a register group (computed once) and a part that
   // depends on the column block (once per block): an epilogue unit adds the two and a compile-time constant
   //   Q / K images (lane = row): element ((((b H + h) ntl + (r >> 5)) (C >> 4) + (cc >> 4)) 64 + ((cc >> 3) & 1) 32 + (r & 31)) 8 + (cc & 7)
@@ -329,6 +607,8 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
 #pragma unroll
       for (int g = 0; g < 4; ++g) epi_unit(acc, bq, cur.cp, cur.kind, 0, 1, g);
     }
+    if constexpr (QK)
+      if (a.pts_img) p2_node_rows(a, Af[0], Al[0], walker, n_walkers, lds0);
     FD_STAMP(15);
     return;
   }
@@ -524,6 +804,37 @@ int fd_node_images(int B, int N, int Np, const float* node, int ld, half_t* Kb, 
   return FDIPT_OK;
 }
 
+// regrouped image of the point epilogue: one thread per 16 B unit ([tile][k-step][lane]: lane & 31 = column of the tile)
+__global__ void p2_points_image_kernel(const u16x8* __restrict__ src, const float* __restrict__ sbias, u16x8* __restrict__ dst,
+                                       float* __restrict__ dbias, int HC, int ks) {
+  const long n_units = (long)(HC + P2P_COLS) / 32 * ks * 64;
+  for (long u = blockIdx.x * (long)blockDim.x + threadIdx.x; u < n_units; u += (long)gridDim.x * blockDim.x) {
+    const int lane = (int)(u & 63), s = (int)((u >> 6) % ks), t = (int)(u / (64L * ks));
+    int n = 32 * t + (lane & 31);  // column of the new image
+    if (n >= HC) {
+      const int o = p2p_src_col(n - HC);
+      n = o < 0 ? -1 : HC + o;
+    }
+    dst[u] = n < 0 ? u16x8{0, 0, 0, 0, 0, 0, 0, 0} : src[((long)(n >> 5) * ks + s) * 64 + (n & 31) + 32 * (lane >> 5)];
+    if (s == 0 && lane < 32) {
+      const int j = 32 * t + lane;
+      dbias[j] = n < 0 ? 0.f : sbias[n];
+    }
+  }
+}
+int fd_ipa_proj2_points_cols(int H, int C) { return H * C + P2P_COLS; }
+int fd_ipa_proj2_points_image(const void* src_img, const float* src_bias, void* img, float* bias, int H, int C, int K, hipStream_t st) {
+  if (H != 8 || C != 256 || (K & 15)) return FDIPT_EINVAL;
+  const long units = (long)fd_ipa_proj2_points_cols(H, C) / 32 * (K / 16) * 64;
+  hipLaunchKernelGGL(p2_points_image_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, st, (const u16x8*)src_img, src_bias,
+                     (u16x8*)img, bias, H * C, K / 16);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+int fd_ipa_proj2_points_supported(const ProjArgs& a, int Pq, int Pv) {
+  return a.merged && a.W_img && a.W_img_lo && a.H == 8 && a.C == 256 && a.K == 256 && Pq == 8 && Pv == 12 &&
+         a.PT == 3 * a.H * (2 * Pq + Pv) && (a.N & 3) == 0 && (a.Np & 31) == 0 && a.Np >= a.N && (a.lda & 3) == 0;
+}
 int fd_ipa_proj2_supported(const ProjArgs& a) {
   const int HC = a.H * a.C;
   return a.K == P2_K && a.W_img && (a.N & 3) == 0 && (a.C % 128) == 0 && (HC % 128) == 0 && (a.lda & 3) == 0 && (a.Np & 31) == 0 && (a.PT & 3) == 0;
@@ -533,7 +844,10 @@ int fd_ipa_proj2(const ProjArgs& a, hipStream_t st) {
   const bool split = a.W_img_lo != nullptr;
   const int M = a.B * a.N, NOUT = (a.merged ? 1 : 3) * a.H * a.C + a.PT;
   const int n_cblk = cdiv(NOUT, 128), n_rblk = cdiv(M, split ? 256 : 128);
-  const int lds = split ? P2S_BIAS_OFF + n_cblk * 128 * 4 : P2_LDS;
+  if (a.pts_img && (!split || !a.merged || a.PT != P2P_COLS || a.H != 8 || a.C != 256 || !a.quat || !a.trans || !a.rot || !a.qp || !a.kpf ||
+                    !a.vpt || !a.gamma || !a.res_mask || !a.Kb || !a.Vt || !a.Vt_lo))
+    return FDIPT_EINVAL;
+  const int lds = split ? P2S_BIAS_OFF + n_cblk * 128 * 4 + (a.pts_img ? 12 * 256 * 4 : 0) : P2_LDS;  // (+ the frames of the rows)
   if (lds > 160 * 1024 || (split && n_cblk * 128 > 8192)) return FDIPT_ESIZE;
   // (the attribute is per device: set on every launch — a host-side table lookup — rather than cached per process)
   if (hipFuncSetAttribute(split ? (const void*)ipa_proj2_kernel<true> : (const void*)ipa_proj2_kernel<false>,

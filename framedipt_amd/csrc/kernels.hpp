@@ -197,11 +197,29 @@ struct ProjArgs {
   // q' = W_k^T (W_q s + b_q) (a per-(query, head) constant drops out of the softmax), the values are the node rows themselves with
   // W_v folded into the output projection (model.hip: merged weights).  Kb / Vt are then not written (fd_node_images writes them)
   int merged = 0;
+  // merged layout with the point columns regrouped per point group (fd_ipa_proj2_points_image; fd_ipa_proj2_points_supported): the
+  // point walkers rotate the points in their epilogue and write the attention's point images (the work of points16_kernel: qp, kpf,
+  // vpt, rot; pts is not written), and three Q walkers write the node-row images Kb / Vt / Vt_lo from their activation fragments
+  // (the work of fd_node_images; the padded keys of Kb / Vt / Vt_lo are zeroed once per forward by the caller, like the value-point pads)
+  int pts_img = 0;
+  const float* quat = nullptr;      // [B N, 4]
+  const float* trans = nullptr;     // [B N, 3]
+  const float* gamma = nullptr;     // [H] (kpf)
+  const float* res_mask = nullptr;  // [B N] (kpf)
+  float *rot = nullptr, *qp = nullptr;          // [B N, 9], [B N, H, 8, 3]
+  unsigned short *kpf = nullptr, *vpt = nullptr;  // layouts: PointsArgs
 };
 // the node rows as attention operand images shared by all heads of a sample (merged projection): Kb [B][Np/32][16][64][8] (key rows,
 // 256 channels), Vt / Vt_lo [B][8][Np/16][64][8] (channel rows, keys permuted inside every 16-group), padded keys zero
 int fd_node_images(int B, int N, int Np, const float* node, int ld, half_t* Kb, half_t* Vt, half_t* Vt_lo, hipStream_t st);
 int fd_ipa_proj2_permute_image_q(void* img, int H, int C, int K, hipStream_t st);  // ... of the q' tiles only (merged layout)
+// the merged projection with the point epilogue: H = 8, C = c_s = 256, Pq = 8, Pv = 12, split operands (W_img_lo), N % 4 == 0.
+// The ONE predicate of that path: the forward asks it for the projection it launches and for the point launch it then drops
+int fd_ipa_proj2_points_supported(const ProjArgs& a, int Pq, int Pv);
+// weight image / bias of that path from the merged ones ([q' | q_pts | kv_pts], q' tiles permuted): the q' tiles copied, the 672 point
+// columns regrouped into 6 column blocks of whole point groups (ipa_proj2.hip), zero-padded; img: fd_ipa_proj2_points_cols() columns
+int fd_ipa_proj2_points_cols(int H, int C);
+int fd_ipa_proj2_points_image(const void* src_img, const float* src_bias, void* img, float* bias, int H, int C, int K, hipStream_t st);
 int fd_ipa_proj(const ProjArgs& a, hipStream_t st);
 int fd_ipa_proj_zero_pads(const ProjArgs& a, void* extra, size_t extra_bytes, hipStream_t st);  // (Kb, Vt and Vt_lo when set)
 int fd_ipa_proj2_supported(const ProjArgs& a);

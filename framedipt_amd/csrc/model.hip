@@ -29,6 +29,7 @@ struct Switches {
        et4_rows_unfused = false, no_pz = false;
   bool no_split = false;        // node-path products on plain half-precision operands instead of split (hi + lo) ones
   bool no_merge = false;        // IPA projections in the reference's formulation (k, v explicit) instead of the merged one
+  bool points_launch = false;   // merged projection: points and node-row images by points16_kernel instead of the projection's epilogue
 };
 // shapes of tfmr_tail16_kernel: d_model 320, c_s 256 (the reference widths)
 template <class IV> static bool tail16_shapes(const FdiptDims* d, const IV& iv) { return iv.d_t == 320 && d->c_s == 256; }
@@ -43,6 +44,7 @@ static Switches switches_of(const FdiptDims* d) {
   if (f & FDIPT_KF_NO_MERGE) s.no_merge = true;
   if (f & FDIPT_KF_ROWS32) s.no_tail16 = true;
   if (f & FDIPT_KF_PASS_Z) s.no_pz = true;
+  if (f & FDIPT_KF_POINTS_LAUNCH) s.points_launch = true;
   if (f & FDIPT_KF_UNFOLDED)
     s.no_et_bias = s.no_ee_bias = s.feats_unfused = s.torf_unfused = s.init_unfused = s.skip_per_block = s.post_unfused =
         s.et4_rows_unfused = true;
@@ -140,7 +142,7 @@ struct DChain {  // weight images of the fused node-path chains (chain.hip) of o
   size_t skip, inp[FD_MAX_TL], outp[FD_MAX_TL], l1[FD_MAX_TL], l2[FD_MAX_TL], l2n[FD_MAX_TL], post, t1, t2, t3, t2n, t3n, et_init, a1, af, a1af, b1f, r4w, r4b;
   // l2: k-permuted (register chaining in chain.hip); l2n: natural k order (rowblock.hip, hidden rows go through LDS)
 };
-struct DBlock { size_t wq_m, wproj2_img, wproj2_img_lo, bproj2, wout_m, bout_m, wout_img, wout_img_lo, wproj, wproj_img, wproj_img_lo, bproj, gamma, wb, bb, wb_img3, wb_img4, et3, et4, wdz_t, wdz_img, wdz_img_lo, wdz_imgp, wdz_imgp_lo; DChain ch; DSplit lo; };
+struct DBlock { size_t wq_m, wproj2_img, wproj2_img_lo, bproj2, wproj2p_img, wproj2p_img_lo, bproj2p, wout_m, bout_m, wout_img, wout_img_lo, wproj, wproj_img, wproj_img_lo, bproj, gamma, wb, bb, wb_img3, wb_img4, et3, et4, wdz_t, wdz_img, wdz_img_lo, wdz_imgp, wdz_imgp_lo; DChain ch; DSplit lo; };
 struct DLayout {
   size_t h16_base;   // bf16 image of the whole fp32 blob (bf16 mode): element offset == fp32 element offset
   size_t ne0_pad;     // [cs, kn_pad] operand precision
@@ -199,6 +201,12 @@ static void build_layout(const FdiptDims* d, const Inventory& iv, DLayout& L) {
       L.blk[b].wproj2_img = o; if (L.esz == 2 && d->c_s == 256) o = al256(o + (size_t)((n2 + 127) / 128) * 65536);
       L.blk[b].wproj2_img_lo = o; if (L.esz == 2 && d->c_s == 256) o = al256(o + (size_t)((n2 + 127) / 128) * 65536);
       L.blk[b].bproj2 = o; o = al256(o + (size_t)n2 * 4);
+      // ... the same with the point columns regrouped for the projection's point epilogue (ipa_proj2.hip: fd_ipa_proj2_points_image)
+      const bool pimg = L.esz == 2 && d->c_s == 256 && d->c_hidden == 256 && d->no_heads == 8;
+      const size_t pcols = pimg ? (size_t)fd_ipa_proj2_points_cols(d->no_heads, d->c_hidden) : 0;
+      L.blk[b].wproj2p_img = o; o = al256(o + pcols / 128 * 65536);
+      L.blk[b].wproj2p_img_lo = o; o = al256(o + pcols / 128 * 65536);
+      L.blk[b].bproj2p = o; o = al256(o + pcols * 4);
       L.blk[b].wout_m = o; o = al256(o + (size_t)d->c_s * iv.feat_dim * 4);
       L.blk[b].bout_m = o; o = al256(o + (size_t)d->c_s * 4);
       // ... and the merged linear_out as hi / lo fragment images (gemm.hip: outproj_split_kernel)
@@ -461,6 +469,10 @@ int fdipt_model_prepare(const FdiptDims* d, const float* P, void* derived, fdipt
           r0 += rows[p3];
         }
         if ((rc = fd_ipa_proj2_permute_image_q(D + db.wproj2_img, H, C, cs, st)) || (rc = fd_ipa_proj2_permute_image_q(D + db.wproj2_img_lo, H, C, cs, st)))
+          return rc;
+        if (H == 8 && C == 256 && cs == 256 && d->no_qk_points == 8 && d->no_v_points == 12 &&
+            ((rc = fd_ipa_proj2_points_image(D + db.wproj2_img, (const float*)(D + db.bproj2), D + db.wproj2p_img, (float*)(D + db.bproj2p), H, C, cs, st)) ||
+             (rc = fd_ipa_proj2_points_image(D + db.wproj2_img_lo, (const float*)(D + db.bproj2), D + db.wproj2p_img_lo, (float*)(D + db.bproj2p), H, C, cs, st))))
           return rc;
       }
     }
@@ -968,28 +980,39 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
         pj.merged = 1; pj.W_img = D + db.wproj2_img; pj.W_img_lo = D + db.wproj2_img_lo; pj.bias = (const float*)(D + db.bproj2);
         a3.kv_per_sample = 1;
         if (split) a3.Vt_lo = (const half_t*)(W + w.vt_lo);
-      } else if (pj.W_img_lo && split && fd_ipa_proj2_supported(pj)) {  // P V on split operands needs V_lo, which only the split second-generation projection writes
+      }
+      // point epilogue (ipa_proj2.hip: p2_points_walk / p2_node_rows): the merged projection also writes the rotated points (qp, kpf, vpt,
+      // rot) and the node-row images; no point launch, no fp32 point columns.  This flag decides the projection's image, the pads and
+      // the launches dropped below
+      const bool proj_pts = merged && !sw.points_launch && pa.vpt && pa.kpf && fd_ipa_proj2_points_supported(pj, Pq, Pv);
+      if (proj_pts) {
+        pj.pts_img = 1; pj.W_img = D + db.wproj2p_img; pj.W_img_lo = D + db.wproj2p_img_lo; pj.bias = (const float*)(D + db.bproj2p);
+        pj.PT = fd_ipa_proj2_points_cols(H, C) - H * C; pj.Vt_lo = (half_t*)(W + w.vt_lo);
+        pj.quat = pa.quat; pj.trans = pa.trans; pj.gamma = pa.gamma; pj.res_mask = pa.res_mask; pj.rot = pa.rot; pj.qp = pa.qp;
+        pj.kpf = pa.kpf; pj.vpt = pa.vpt;
+      }
+      if (!merged && pj.W_img_lo && split && fd_ipa_proj2_supported(pj)) {  // P V on split operands needs V_lo, which only the split second-generation projection writes
         pj.Vt_lo = (half_t*)(W + w.vt_lo); a3.Vt_lo = pj.Vt_lo;
       }
       // second generation (activation fragments in registers, weights by LDS-DMA) where it applies, else the tiled GEMM
       if (fd_ipa_proj2_supported(pj)) {
         if (pj.zero_pads && seq_fused && !seq_img_ready && (C & 31) == 0 && (vpt_bytes & 15) == 0 && !sw.init_unfused) {
           // every once-per-forward fill of the trunk in one launch: sequence-attention images, value-point image, key pads
-          // (merged: fd_node_images writes the padded keys of its images itself)
-          SeqInitExtra sx = {vpt_zero ? W + w.vpt : nullptr, vpt_zero ? (long)(vpt_bytes >> 4) : 0L, (Np > N && !merged) ? (void*)pj.Kb : nullptr,
+          // (merged without the point epilogue: fd_node_images writes the padded keys of its images itself)
+          SeqInitExtra sx = {vpt_zero ? W + w.vpt : nullptr, vpt_zero ? (long)(vpt_bytes >> 4) : 0L, (Np > N && (!merged || proj_pts)) ? (void*)pj.Kb : nullptr,
                              (void*)pj.Vt, (long)B * H, C, (void*)pj.Vt_lo};
           RC(fd_seq_images_init(B, N, d->tfmr_heads, res_mask, W + w.seqimg, sx, st));
           seq_img_ready = true;
           vpt_zero = false;
-        } else if (pj.zero_pads && ((Np > N && !merged) || vpt_zero)) {
+        } else if (pj.zero_pads && ((Np > N && (!merged || proj_pts)) || vpt_zero)) {
           ProjArgs pz = pj; pz.W_img = nullptr;
-          if (merged) pz.Np = pz.N;  // (no key pads to zero)
+          if (merged && !proj_pts) pz.Np = pz.N;  // (no key pads to zero)
           RC(fd_ipa_proj_zero_pads(pz, vpt_zero ? W + w.vpt : nullptr, vpt_zero ? vpt_bytes : 0, st));
           vpt_zero = false;
         }
         RC(fd_ipa_proj2(pj, st));
         // (the node-row images ride on the point launch when that is the 16-keys-per-block kernel; else their own launch)
-        if (merged) {
+        if (merged && !proj_pts) {
           if (pa.vpt && Pv == 12 && (H & 1) == 0 && cs == 256) {
             pa.node = node_cur; pa.ld_node = cs; pa.nKb = pj.Kb; pa.nVt = pj.Vt; pa.nVt_lo = split ? (half_t*)(W + w.vt_lo) : nullptr;
           } else RC(fd_node_images(B, N, Np, node_cur, cs, pj.Kb, pj.Vt, split ? (half_t*)(W + w.vt_lo) : nullptr, st));
@@ -997,7 +1020,7 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
       } else RC(fd_ipa_proj(pj, st));
       if (vpt_zero && hipMemsetAsync(W + w.vpt, 0, vpt_bytes, st) != hipSuccess) return FDIPT_ELAUNCH;
       pa.proj = F(w.pts); pa.ld = PT; pa.q_off = 0; pa.kv_off = 3 * H * Pq;
-      RC(fd_points(pa, st));
+      if (!proj_pts) RC(fd_points(pa, st));
       if (op.kind == OP_POINTS) return FD_STOP;
       if (!bias_ready)  // blocks >= 1: already emitted by the previous block's EdgeTransition epilogue
         RC(fd_pair_bias2(B, N, H, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), 1, st));

@@ -58,7 +58,9 @@ extern "C" {
                                     node embedder, torsion head) for every N                                                  */
 #define FDIPT_KF_PASS_Z 256      /* o_pair as its own pass over the 128 channels of z (round 5's path: sum_j a z, then down_z) instead of the
                                     pair_z image emitted by the producers of z (round 6); the last EdgeTransition then keeps its z' store */
-#define FDIPT_KF_ALL 511
+#define FDIPT_KF_POINTS_LAUNCH 512 /* merged IPA projection: the rotated points and the node-row images by their own launch (points16_kernel)
+                                    instead of the projection's epilogue                                                       */
+#define FDIPT_KF_ALL 1023
 
 typedef void* fdipt_stream_t; /* hipStream_t */
 
