@@ -215,14 +215,14 @@ int fd_node_images(int B, int N, int Np, const float* node, int ld, half_t* Kb, 
 int fd_ipa_proj2_permute_image_q(void* img, int H, int C, int K, hipStream_t st);  // ... of the q' tiles only (merged layout)
 // the merged projection with the point epilogue: H = 8, C = c_s = 256, Pq = 8, Pv = 12, split operands (W_img_lo), N % 4 == 0.
 // The ONE predicate of that path: the forward asks it for the projection it launches and for the point launch it then drops
-int fd_ipa_proj2_points_supported(const ProjArgs& a, int Pq, int Pv);
+int fd_ipa_proj2_points_supported(const ProjArgs& a, int Pq, int Pv);  // keep to scalars and null tests: plan_forward (model.hip) asks it with placeholder pointers
 // weight image / bias of that path from the merged ones ([q' | q_pts | kv_pts], q' tiles permuted): the q' tiles copied, the 672 point
 // columns regrouped into 6 column blocks of whole point groups (ipa_proj2.hip), zero-padded; img: fd_ipa_proj2_points_cols() columns
 int fd_ipa_proj2_points_cols(int H, int C);
 int fd_ipa_proj2_points_image(const void* src_img, const float* src_bias, void* img, float* bias, int H, int C, int K, hipStream_t st);
 int fd_ipa_proj(const ProjArgs& a, hipStream_t st);
 int fd_ipa_proj_zero_pads(const ProjArgs& a, void* extra, size_t extra_bytes, hipStream_t st);  // (Kb, Vt and Vt_lo when set)
-int fd_ipa_proj2_supported(const ProjArgs& a);
+int fd_ipa_proj2_supported(const ProjArgs& a);  // keep to scalars and null tests: plan_forward (model.hip) asks it with placeholder pointers
 // after the fragment image of the fused projection weight is built: permute the rows of its Q / K tiles (16 B epilogue stores)
 int fd_ipa_proj2_permute_image(void* img, int H, int C, int K, hipStream_t st);
 int fd_ipa_proj2(const ProjArgs& a, hipStream_t st);  // second generation (ipa_proj2.hip): same outputs
@@ -246,7 +246,7 @@ struct Attn3Args {
   long out_ld;
   int pt_off;
 };
-int fd_attention3_supported(const Attn3Args& a);
+int fd_attention3_supported(const Attn3Args& a);  // keep to scalars and null tests: plan_forward (model.hip) asks it with placeholder pointers
 int fd_attention3(const Attn3Args& a, hipStream_t st);
 
 
@@ -276,28 +276,28 @@ int fd_seq_attention_f32(int B, int N, int H, const float* qkv, int ld, float sc
 // row-complete fused per-residue MLPs (rowblock.hip): 32 rows x all output columns per block, up to 3 Linear layers
 // (+ReLU) + residual + LayerNorm + row mask; weights as fd_chain_build_image(.., permuted = 0) fragment images
 struct RowBlockArgs {
-  int M;
-  const float* in;
-  int ld_in;
-  const void *w0, *w1, *w2;
+  int M = 0;
+  const float* in = nullptr;
+  int ld_in = 0;
+  const void *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
   const void *w0l = nullptr, *w1l = nullptr, *w2l = nullptr;  // *_SPLIT kinds: images of W - half(W) (fd_chain_build_image_lo)
-  const float *b0, *b1, *b2;
-  const float* residual;        // or NULL
-  int ld_res;
-  const float *gamma, *beta;    // LayerNorm kinds
-  const float* rowmask_post;    // final * mask, or NULL
-  float* out;
-  int ld_out;
-  float* out2;                  // optional: output columns >= split go to out2 (column - split), or NULL
-  int ld_out2, split;
-  unsigned short* hid_h16;     // optional bf16 copy of the first hidden layer's rows [M, N1], or NULL
+  const float *b0 = nullptr, *b1 = nullptr, *b2 = nullptr;
+  const float* residual = nullptr;  // or NULL
+  int ld_res = 0;
+  const float *gamma = nullptr, *beta = nullptr;  // LayerNorm kinds
+  const float* rowmask_post = nullptr;  // final * mask, or NULL
+  float* out = nullptr;
+  int ld_out = 0;
+  float* out2 = nullptr;        // optional: output columns >= split go to out2 (column - split), or NULL
+  int ld_out2 = 0, split = 0;
+  unsigned short* hid_h16 = nullptr;  // optional bf16 copy of the first hidden layer's rows [M, N1], or NULL
   // FD_RB_ET4_IMAGES: the 1024 output columns [A1 | Af | B1 | Bf] leave as edge_transition4's fold-fragment images (bf16)
-  void *img_a, *img_b;          // fd_et4_row_images layouts
-  int img_B, img_N;
+  void *img_a = nullptr, *img_b = nullptr;  // fd_et4_row_images layouts
+  int img_B = 0, img_N = 0;
   // FD_RB_TRANSITION_BB: BackboneUpdate (Linear c_s -> 6, fp32) on the output rows + compose_q_update_vec, in place
-  const float *bb_w, *bb_b;     // [6, c_s], [6]
-  const float* upd_mask;        // [M] or NULL
-  float *quat, *trans;          // [M,4], [M,3]
+  const float *bb_w = nullptr, *bb_b = nullptr;  // [6, c_s], [6]
+  const float* upd_mask = nullptr;  // [M] or NULL
+  float *quat = nullptr, *trans = nullptr;  // [M,4], [M,3]
   L2Warm warm = {};             // weights of the kernel launched next (common.hpp: L2 warm-up hand-over)
   // fd_node_embed16 only: one more Linear (256 -> 256, split operands, fd_chain_build_image16 images) on the output rows -> out2 [M, ld_out2]
   // (skip_embed of all trunk blocks stacked)
@@ -339,19 +339,19 @@ int fd_tfmr_tail(const TfmrTailArgs& a, hipStream_t st);
 int fd_chain_build_image16(const float* w, int N, int K, int Kpad, int ldw, int lo, void* img, hipStream_t st);
 
 struct ChainArgs {
-  int M;
-  const float* in;          // [M, ld_in] fp32 input rows
-  int ld_in;
-  const void* w[3];         // weight images (fd_chain_build_image) of the layers actually present
-  const float* b[3];
-  const float* residual;    // added to the output layer (fp32) or NULL
-  int ld_res;
-  const float *gamma, *beta;     // LayerNorm parameters (kinds with LN)
-  unsigned short* out_h16;      // optional bf16 copy of the output rows, [M, NOUT] (kinds without LayerNorm), or NULL
-  const float* rowmask_pre;      // (W x + b) * mask before the residual, or NULL
-  const float* rowmask_post;     // final * mask, or NULL
-  float* out;
-  int ld_out;
+  int M = 0;
+  const float* in = nullptr;  // [M, ld_in] fp32 input rows
+  int ld_in = 0;
+  const void* w[3] = {};    // weight images (fd_chain_build_image) of the layers actually present
+  const float* b[3] = {};
+  const float* residual = nullptr;  // added to the output layer (fp32) or NULL
+  int ld_res = 0;
+  const float *gamma = nullptr, *beta = nullptr;  // LayerNorm parameters (kinds with LN)
+  unsigned short* out_h16 = nullptr;  // optional bf16 copy of the output rows, [M, NOUT] (kinds without LayerNorm), or NULL
+  const float* rowmask_pre = nullptr;   // (W x + b) * mask before the residual, or NULL
+  const float* rowmask_post = nullptr;  // final * mask, or NULL
+  float* out = nullptr;
+  int ld_out = 0;
   L2Warm warm = {};  // weights of the kernel launched next (common.hpp: L2 warm-up hand-over)
 };
 // the chain kinds the forward runs where the row-block kernels (rowblock.hip) do not take the layers (FDIPT_KF_UNFOLDED, generic pair path)
@@ -393,7 +393,7 @@ int fd_attention(int precision, int ipa, const AttnArgs& a, hipStream_t st);
 int fd_ipa_attention_f32_supported(const AttnArgs& a);
 int fd_ipa_attention_f32(const AttnArgs& a, hipStream_t st);
 int fd_opair(int precision, const OPairArgs& a, hipStream_t st);
-int fd_opair_mfma_eligible(int precision, const OPairArgs& a);  // the MFMA kernel will run (it can take probs_h16)
+int fd_opair_mfma_eligible(int precision, const OPairArgs& a);  // the MFMA kernel will run (it can take probs_h16); keep to scalars and null tests: plan_forward (model.hip) asks it with placeholder pointers
 int fd_opair_pz(const OPairArgs& a, hipStream_t st);  // o_pair from the producer-emitted pair_z image (OPairArgs.pz, probs_h16)
 int fd_pair_bias2(int B, int N, int H, const void* z, const void* wb, const float* bb, float* out, int frag, hipStream_t st);
 // fp32 mode: out[p, h] = z[p, :] . Wb[h, :] + bb[h] over the fp32 pair representation (H = 8, c_z = 128), one streaming pass

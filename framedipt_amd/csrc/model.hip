@@ -12,45 +12,8 @@
 #include "common.hpp"
 #include "kernels.hpp"
 
-// ------------------------------------------------------------------ kernel-selection switches
-// The library reads no environment.  FdiptDims.kernel_flags (include/fdipt.h: FDIPT_KF_*) selects the fallback paths that other
-// shapes use anyway, so that parity tests can run them at the golden sizes.  The weight images built by fdipt_model_prepare and the
-// forward of the same FdiptDims see the same switches.
-struct Switches {
-  bool generic_pair = false;    // LDS-chain EdgeTransition / edge embedder (any width) instead of the register kernels
-  bool et3 = false;             // 16-pair EdgeTransition kernel (the N % 4 != 0 path) for every N
-  bool generic_attn = false;    // LDS-score attention kernels (the N > 512 path) for every N
-  bool no_rowblock = false;     // node path as GEMM + LayerNorm launches (the non-reference-width path)
-  bool no_chain = false;
-  bool no_splitk = false;
-  bool no_tail16 = false;       // 32-row node-path kernels instead of the 16-row ones (tfmr_tail16_kernel, mlp16_kernel, ...)
-  bool no_et_bias = false, no_ee_bias = false;  // pair bias as its own pass over z
-  bool feats_unfused = false, torf_unfused = false, init_unfused = false, skip_per_block = false, post_unfused = false,
-       et4_rows_unfused = false, no_pz = false;
-  bool no_split = false;        // node-path products on plain half-precision operands instead of split (hi + lo) ones
-  bool no_merge = false;        // IPA projections in the reference's formulation (k, v explicit) instead of the merged one
-  bool points_launch = false;   // merged projection: points and node-row images by points16_kernel instead of the projection's epilogue
-};
 // shapes of tfmr_tail16_kernel: d_model 320, c_s 256 (the reference widths)
 template <class IV> static bool tail16_shapes(const FdiptDims* d, const IV& iv) { return iv.d_t == 320 && d->c_s == 256; }
-static Switches switches_of(const FdiptDims* d) {
-  Switches s;
-  const unsigned f = (unsigned)d->kernel_flags;
-  if (f & FDIPT_KF_GENERIC_PAIR) s.generic_pair = true;
-  if (f & FDIPT_KF_ET3) s.et3 = true;
-  if (f & FDIPT_KF_GENERIC_ATTN) s.generic_attn = true;
-  if (f & FDIPT_KF_UNFUSED_NODE) s.no_rowblock = s.no_chain = s.no_splitk = true;
-  if (f & FDIPT_KF_NO_SPLIT) s.no_split = true;
-  if (f & FDIPT_KF_NO_MERGE) s.no_merge = true;
-  if (f & FDIPT_KF_ROWS32) s.no_tail16 = true;
-  if (f & FDIPT_KF_PASS_Z) s.no_pz = true;
-  if (f & FDIPT_KF_POINTS_LAUNCH) s.points_launch = true;
-  if (f & FDIPT_KF_UNFOLDED)
-    s.no_et_bias = s.no_ee_bias = s.feats_unfused = s.torf_unfused = s.init_unfused = s.skip_per_block = s.post_unfused =
-        s.et4_rows_unfused = true;
-  return s;
-}
-
 // ------------------------------------------------------------------ inventory (== framedipt_amd/weights.py)
 struct LinW { long w, b; int out, in; };
 struct LNW { long g, b; int d; };
@@ -162,12 +125,12 @@ struct DLayout {
 
 // the register-resident half-precision pair kernels (edge_transition3/4.hip, edge_embed2) are compiled for the reference widths only
 static bool use_regpair(const FdiptDims* d) {
-  return d->precision == FDIPT_PREC_HALF && d->c_z == 128 && d->c_s == 256 && !switches_of(d).generic_pair;
+  return d->precision == FDIPT_PREC_HALF && d->c_z == 128 && d->c_s == 256 && !(d->kernel_flags & FDIPT_KF_GENERIC_PAIR);
 }
 
 // fused node-path chains (chain.hip) are compiled for the reference widths only
 static bool use_chain(const FdiptDims* d) {
-  return d->precision == FDIPT_PREC_HALF && d->c_s == 256 && d->c_skip == 64 && d->c_z == 128 && !switches_of(d).no_chain;
+  return d->precision == FDIPT_PREC_HALF && d->c_s == 256 && d->c_skip == 64 && d->c_z == 128 && !(d->kernel_flags & FDIPT_KF_UNFUSED_NODE);
 }
 
 static void build_layout(const FdiptDims* d, const Inventory& iv, DLayout& L) {
@@ -193,7 +156,7 @@ static void build_layout(const FdiptDims* d, const Inventory& iv, DLayout& L) {
     L.blk[b].wproj_img_lo = o;  // ... and of W - half(W) (split operands)
     if (L.esz == 2 && d->c_s == 256) o = al256(o + (size_t)((iv.proj_out + 127) / 128) * 65536);
     L.blk[b].bproj = o; o = al256(o + (size_t)iv.proj_out * 4);
-    // merged IPA projections (forward_impl: `merged`): q' = W_k^T (W_q s + b_q) per head as [H C, c_s] fp32 (+ its bias), the fragment
+    // merged IPA projections (ForwardPlan::merged): q' = W_k^T (W_q s + b_q) per head as [H C, c_s] fp32 (+ its bias), the fragment
     // images of [q' | q_pts | kv_pts] (hi, lo), their biases, and linear_out with W_v folded into its o columns
     {
       const int HCm = d->no_heads * d->c_hidden, n2 = iv.proj_out - 2 * HCm;
@@ -691,7 +654,6 @@ size_t fdipt_forward_workspace_bytes(const FdiptDims* dims, int B, int N) {
 // One sub-module of the forward on caller-provided inputs (the per-op entries of include/fdipt.h): the same launch schedule
 // as the full forward, cut at the sub-module's boundary.
 enum { OP_ALL, OP_EMBED, OP_POINTS, OP_IPA, OP_ET };
-#define FD_STOP 1  // (internal) the selected sub-module is done
 struct OpSel {
   int kind = OP_ALL, block = 0;
   const float* node_in = nullptr;   // [B,N,c_s]                      (POINTS, IPA, ET)
@@ -702,15 +664,631 @@ struct OpSel {
   float *qp = nullptr, *kp = nullptr, *vp = nullptr;  // global-frame points (POINTS)
 };
 
-// The IPA path of a block: attention3, and behind it the MFMA o_pair kernel fed with the attention weights as half-precision rows.  A
-// function of the dims, the switches and the shape only (the fields of a3 / oa read here are the same for every block).  That o_pair is
-// the one consumer of a pair_z image (fd_opair_pz): the producers of z emit pair_z only when probs_h16 holds.
-struct IpaPath { bool a3, probs_h16; };
-static IpaPath ipa_path(const FdiptDims* d, const Switches& sw, const Attn3Args& a3, const OPairArgs& oa) {
-  const bool a3_ok = d->precision == FDIPT_PREC_HALF && d->c_z == 128 && d->c_hidden == 256 && d->no_qk_points == 8 &&
-                     d->no_v_points == 12 && !sw.generic_attn && fd_attention3_supported(a3);
-  return {a3_ok, a3_ok && fd_opair_mfma_eligible(d->precision, oa) && 2 * a3.Np <= 4 * a3.N};
+// ------------------------------------------------------------------ kernel selection of one forward
+// The library reads no environment.  FdiptDims.kernel_flags (include/fdipt.h: FDIPT_KF_*) selects the fallback paths that other
+// shapes use anyway, so that parity tests can run them at the golden sizes.  Every choice below is a function of the dims, the
+// flags, the shape and the op kind only: the same for every block, made once per forward.
+enum NodeForm { NF_GEMM, NF_ROWBLOCK, NF_ROWS16 };  // node-path MLPs: GEMM + LayerNorm launches, 32-row row-block kernel, 16-row kernel
+enum SkipAt { SKIP_PER_BLOCK, SKIP_EMBED16, SKIP_SPLITK, SKIP_GEMM };  // skip_embed(init_node): per block, or once for all blocks
+enum OutProj { OUT_GEMM, OUT_DEDICATED, OUT_SPLITK_SPLIT, OUT_SPLITK_A16, OUT_SPLITK };  // IPA linear_out
+enum NodeRows { NR_PROJ, NR_POINTS, NR_LAUNCH };  // merged projection: who writes the node-row images (Kb / Vt / Vt_lo)
+enum SeqAttn { SEQ_FUSED, SEQ_BF16, SEQ_F32, SEQ_GENERIC };  // sequence-transformer attention: in_proj writes the images / bf16 / fp32 / LDS kernel
+enum PostAt { POST_TAIL, POST_CHAIN, POST_GEMM };
+enum EtKind { ET_GEMM, ET_CHAIN, ET_ET3, ET_ET4 };
+enum EtRows { ETR_IMAGES, ETR_ROWS, ETR_FOLDED };  // edge_transition4's per-residue rows: row-block images, rows + image pass, transition launch
+struct ForwardPlan {
+  int op;
+  bool bf, chain, rbk, split;  // half-precision mode; fused chains (chain.hip); row-complete MLPs (rowblock.hip); split (hi + lo) operands
+  NodeForm embed, tail, transition, torsion;
+  SkipAt skip;
+  OutProj outproj;
+  int slices;   // split-K slices of the output projection
+  bool feats_fused, ee_bias, et_bias, pz;
+  bool a3, probs_h16;                  // IPA path: attention3, and the MFMA o_pair fed with bf16 attention weights
+  bool vpt, proj2, merged, proj_pts, vt_lo, init_fused, feats_h16;
+  NodeRows node_rows;
+  SeqAttn seq;
+  PostAt post;
+  bool et_widths;                      // reference widths of the EdgeTransition rows (cb 128, hidden 384, c_z 128)
+  EtKind et;
+  EtRows et_rows;
+  bool torf_fused, bb_fold;
+  bool regpair;                        // register-resident pair kernels (edge_embed2, edge_transition3/4)
+  bool ipa_bias_f32, ipa_attn_f32;     // fp32 mode: the one-pass pair bias, the register-score IPA attention (where it takes the call)
+};
+static const char kImage = 0;  // stands for an operand image in the probe arguments below (the predicates test only that it is set)
+
+static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const DLayout& L, int B, int N, int op) {
+  const unsigned f = (unsigned)d->kernel_flags;
+  const bool generic_attn = f & FDIPT_KF_GENERIC_ATTN, unfolded = f & FDIPT_KF_UNFOLDED;
+  const int cs = d->c_s, cz = d->c_z, H = d->no_heads, C = d->c_hidden, Pq = d->no_qk_points, Pv = d->no_v_points;
+  const int Np = (N + 31) / 32 * 32;
+  ForwardPlan p = {};
+  p.op = op;
+  p.bf = d->precision == FDIPT_PREC_HALF;
+  // fused chains (chain.hip) where they beat the GEMM + LayerNorm launches they replace at B*N ~ 2400 rows on MI355X
+  // (profiles/r01_chain_vs_gemm.md): post_tfmr and EdgeTransition.initial_embed when the row-block kernels do not take them
+  p.chain = use_chain(d);
+  // row-complete fused MLPs (rowblock.hip) take the multi-layer kinds and the 320-wide transformer layers (FDIPT_KF_UNFUSED_NODE
+  // clears use_chain)
+  p.rbk = p.chain && cs == 256 && iv.d_t == 320;
+  // split operands (hi + lo half-precision parts, 3 MFMAs per k-step) for the dense layers of the node path, whose operand
+  // rounding dominates the error of the predicted frames and psi (tests/err_budget.py): node embedder, IPA projection and output
+  // projection, attention P V, o_pair down-projection, sequence transformer (in_proj, out_proj, feed-forward), post_tfmr, transition,
+  // EdgeTransition per-residue rows, skip_embed, torsion head
+  p.split = p.rbk && !(f & FDIPT_KF_NO_SPLIT);
+  // 16-row node-path blocks pay off while they are about one round of the chip (B N <= ~4000 rows: twice the blocks of the 32-row kernels, each
+  // streaming all weights, half the matrix work per block); with every CU busy anyway the 32-row kernels move half the weight bytes (measured: c4
+  // with 64 samples per GPU 1.277 -> 1.246 M).  The choice goes by N alone — a sample's result must not depend on the batch it rides in.
+  const bool rows16 = p.split && !(f & FDIPT_KF_ROWS32) && N <= 512;
+  const bool ends16 = rows16 && cs == 256 && iv.node_in <= 96;  // node embedder and torsion head (rowblock.hip: mlp16_kernel)
+  const bool mid16 = rows16 && tail16_shapes(d, iv);            // transformer tails and transition
+  p.embed = p.rbk && (L.kn_pad == 72 || L.kn_pad == 88) ? (ends16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
+  p.torsion = p.rbk ? (ends16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
+  p.tail = p.transition = p.rbk ? (mid16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
+  // the IPA output projection as split-K slices that its LayerNorm sums; skip_embed(init_node) of every block depends on the
+  // embedder output only: one launch for all blocks, copied behind the LayerNorm output by that LayerNorm (FDIPT_KF_UNFOLDED: per block)
+  const bool splitk = p.bf && iv.feat_dim >= 1024 && !(f & FDIPT_KF_UNFUSED_NODE);
+  if (!splitk || unfolded || op != OP_ALL) p.skip = SKIP_PER_BLOCK;
+  else if (p.embed == NF_ROWS16 && d->num_blocks * d->c_skip == 256) p.skip = SKIP_EMBED16;  // a fourth layer of the embedder launch
+  else p.skip = p.split && (cs & 7) == 0 ? SKIP_SPLITK : SKIP_GEMM;
+  // the split of x_t (ipa_pytorch.py:516-524) and the per-residue halves of the first edge-embedder layer in the feature launch
+  // (FDIPT_KF_UNFOLDED: three GEMM / element-wise launches more)
+  p.feats_fused = L.d1_pad <= 128 && (L.d1_pad & 3) == 0 && !unfolded && op == OP_ALL;
+  // The IPA path: attention3, and behind it the MFMA o_pair kernel fed with the attention weights as half-precision rows
+  Attn3Args a3 = {};
+  a3.B = B; a3.N = N; a3.H = H; a3.Np = Np; a3.vpt = (const half_t*)&kImage;
+  OPairArgs oa = {};
+  oa.B = B; oa.N = N; oa.H = H; oa.CZ = cz; oa.CD = cz / 4; oa.wdz_img = p.bf && cz == 128 ? &kImage : nullptr;
+  const bool opair_mfma = fd_opair_mfma_eligible(d->precision, oa);
+  p.a3 = p.bf && cz == 128 && C == 256 && Pq == 8 && Pv == 12 && !generic_attn && fd_attention3_supported(a3);
+  p.probs_h16 = p.a3 && opair_mfma && 2 * Np <= 4 * N;
+  // the next block's pair bias linear_b(z)/sqrt(3) from the LayerNorm epilogue of the producer of z (saves a pass over z): the
+  // embedder for block 0 (register kernel only), the EdgeTransition of block b for block b + 1
+  const bool bias_rule = cz == 128 && C == 256 && Pq == 8 && Pv == 12 && H <= 8 && N <= 1024 && !generic_attn && !unfolded;
+  p.regpair = use_regpair(d);
+  p.ee_bias = bias_rule && p.regpair;
+  p.et_bias = bias_rule;
+  // EdgeTransition: register-resident pair kernels at the reference widths, edge_transition4 (8 x 4-pair patches, N % 4 == 0) or
+  // edge_transition3 (16-pair waves: any N >= 43); anything else (N < 43 with N % 4 != 0, other widths) runs the LDS-chain kernel of
+  // pair_mlp.hip.  edge_transition4's rows come from the transition launch where that is the 16-row kernel (FDIPT_KF_UNFOLDED: a row
+  // launch and an image pass)
+  p.et_widths = iv.cb == 128 && iv.hid == 384 && cz == 128;
+  const bool reg_ok = p.rbk && p.et_widths && p.regpair;
+  if (reg_ok && !(f & FDIPT_KF_ET3) && fd_edge_transition4_supported(N)) p.et = ET_ET4;
+  else if (reg_ok && fd_edge_transition3_supported(N)) p.et = ET_ET3;
+  else p.et = p.chain ? ET_CHAIN : ET_GEMM;
+  p.et_rows = unfolded ? ETR_ROWS : p.et == ET_ET4 && p.transition == NF_ROWS16 && op == OP_ALL ? ETR_FOLDED : ETR_IMAGES;
+  // Round 6: o_pair reads pair_z = down_z(z) + b (32 channels) emitted by the producers of the pair bias above (edge_transition4 only)
+  // instead of streaming the 128 channels of z once more per block (opair_pz_kernel).  FDIPT_KF_UNFOLDED / FDIPT_KF_PASS_Z keep the pass
+  // over z.  The consumer: the IPA path that reads probs_h16.
+  p.pz = op == OP_ALL && p.probs_h16 && p.et == ET_ET4 && bias_rule && !(f & FDIPT_KF_PASS_Z);
+  // IPA projection (attention3 path): fused projection written directly as attention operand images (Qb, Kb, Vt) + raw point columns
+  p.vpt = p.a3 && Pv == 12;
+  ProjArgs pj = {};
+  pj.B = B; pj.N = N; pj.H = H; pj.C = C; pj.K = cs; pj.PT = iv.proj_out - 3 * H * C; pj.Np = Np; pj.lda = cs;
+  pj.W_img = cs == 256 ? &kImage : nullptr;
+  pj.W_img_lo = pj.W_img && p.split ? &kImage : nullptr;
+  // Merged projections (the default of the split mode at the reference widths): no k, no v — the node rows are keys and values of
+  // every head (fd_node_images), q' = W_k^T (W_q s + b_q), W_v sits in the output projection (prepare: merge_qk / merge_vo).  40 % of
+  // the projection's columns, and K / V images an eighth of the size.  Exact algebra (softmax shift invariance, linearity); the
+  // per-op entries and FDIPT_KF_NO_MERGE keep the reference's formulation.
+  p.merged = p.a3 && pj.W_img_lo && cs == C && !(f & FDIPT_KF_NO_MERGE) && op == OP_ALL && fd_ipa_proj2_supported(pj);
+  pj.merged = p.merged;
+  // point epilogue (ipa_proj2.hip: p2_points_walk / p2_node_rows): the merged projection also writes the rotated points (qp, kpf, vpt,
+  // rot) and the node-row images; no point launch, no fp32 point columns.  This flag decides the projection's image, the pads and
+  // the launches dropped
+  p.proj_pts = p.merged && !(f & FDIPT_KF_POINTS_LAUNCH) && p.vpt && fd_ipa_proj2_points_supported(pj, Pq, Pv);
+  if (p.proj_pts) pj.PT = fd_ipa_proj2_points_cols(H, C) - H * C;
+  // second generation (activation fragments in registers, weights by LDS-DMA) where it applies, else the tiled GEMM
+  p.proj2 = p.a3 && fd_ipa_proj2_supported(pj);
+  // P V on split operands needs V_lo, which only the split second-generation projection (or the node-row images) writes
+  p.vt_lo = p.merged || (p.proj2 && pj.W_img_lo);
+  // (the node-row images ride on the point launch when that is the 16-keys-per-block kernel; else their own launch)
+  p.node_rows = !p.merged || p.proj_pts ? NR_PROJ : p.vpt && (H & 1) == 0 && cs == 256 ? NR_POINTS : NR_LAUNCH;
+  const int th = d->tfmr_heads, hd = iv.d_t / th;
+  if (p.rbk && !generic_attn && fd_seq_attention_supported(N, th, hd) && fd_seq_qkv_supported(N, th, iv.d_t)) p.seq = SEQ_FUSED;
+  else if (p.bf && !generic_attn && fd_seq_attention_supported(N, th, hd)) p.seq = SEQ_BF16;
+  else if (!p.bf && !generic_attn && fd_seq_attention_f32_supported(N, th, hd, 3 * iv.d_t)) p.seq = SEQ_F32;  // scores in registers (round 5)
+  else p.seq = SEQ_GENERIC;
+  p.ipa_bias_f32 = !p.bf && H == 8 && cz == 128;
+  p.ipa_attn_f32 = !p.bf && !generic_attn;
+  // every once-per-forward fill of the trunk in one launch: sequence-attention images, value-point image, key pads
+  p.init_fused = p.proj2 && p.seq == SEQ_FUSED && !unfolded;  // (proj2: C % 128 == 0; the value-point image: whole 16 B units)
+  // the attention weights go to the MFMA o_pair kernel as bf16 rows [b, i, h, Np] (half the bytes, no conversion pass;
+  // the fp32 buffer is reused: B N H Np bf16 <= B H N N fp32)
+  // ... and both kernels write the attention features as bf16 rows when the output projection is the bf16 split-K GEMM
+  // (the values it would round them to anyway: identical results, half the bytes, no conversion in its staging)
+  p.feats_h16 = p.a3 && opair_mfma && splitk && (iv.feat_dim & 7) == 0 && !p.split && op == OP_ALL;  // (split: the projection splits the features itself)
+  // K = 2688 in slices: 4x the blocks, a quarter of the dependent k-iterations (7 slices: slower).  Split operands: 3 slices
+  // (70 KB of LDS per block = two blocks per CU: at B N = 2400 rows 456 blocks run in one round of the 256 CUs, 30 us;
+  // 4 slices = 608 blocks need two rounds, 41 us).  The slice count must not depend on the batch size: the order of the
+  // partial sums is part of a sample's result (sub-batches and sharded runs reproduce the whole-batch result bit for bit)
+  if (!splitk) p.outproj = OUT_GEMM;
+  else if (p.split && p.merged && fd_outproj_split_supported(cs, iv.feat_dim)) p.outproj = OUT_DEDICATED;
+  else p.outproj = p.split ? OUT_SPLITK_SPLIT : p.feats_h16 ? OUT_SPLITK_A16 : OUT_SPLITK;
+  p.slices = p.outproj == OUT_DEDICATED ? fd_outproj_split_slices() : p.split ? 3 : 4;
+  // the last layer's tail also applies post_tfmr + the node residual (FDIPT_KF_UNFOLDED: its own launch)
+  p.post = p.rbk && !unfolded ? POST_TAIL : p.chain ? POST_CHAIN : POST_GEMM;
+  // the last torsion layer (Linear(c_s, 2), fp32) and the backbone atoms ride on the score launch (FDIPT_KF_UNFOLDED: own launches)
+  p.torf_fused = (cs & 3) == 0 && !unfolded;
+  p.bb_fold = !unfolded;
+  return p;
 }
+
+// ------------------------------------------------------------------ the forward's stages
+// L2 warm-up hand-over (common.hpp): the weight images of the launch that follows, which the current launch touches once its own first
+// loads are out.  (round 3: the lo images are touched as well — a cold image is one exposed memory round trip per weight tile of the consumer)
+enum WarmOf { WARM_QKV, WARM_TAIL, WARM_POST, WARM_TRANSITION, WARM_TRANSITION32, WARM_ET_ROWS, WARM_ET_FOLDED, WARM_TORSION };
+// One call of the forward: its inputs and plan, and one const member function per stage (the stages share no mutable state)
+struct Fwd {
+  const FdiptDims* d;
+  const Inventory& iv;
+  const DLayout& L;
+  const WS& w;
+  const ForwardPlan& p;
+  const float* P;
+  const char* D;
+  char* W;
+  const void* setup;
+  const FdiptForwardArgs* a;
+  hipStream_t st;
+  int B, N, R, Np;
+  size_t NN;
+  const float* res_mask = a->res_mask;
+  float* F(size_t off) const { return (float*)(W + off); }
+  // operand-precision view of a weight matrix of the fp32 blob
+  const void* WM(const LinW& l) const { return p.bf ? (const void*)((const half_t*)(D + L.h16_base) + l.w) : (const void*)(P + l.w); }
+  int lin(const LinW& l, const float* A, int lda, const float* res, int ldr, const float* rm, int relu, float* out, int ldo) const {
+    return fd_linear(d->precision, R, l.out, l.in, A, lda, WM(l), l.in, P + l.b, res, ldr, rm, relu, out, ldo, st);
+  }
+  int lin32(const LinW& l, const float* A, int lda, float* out, int ldo) const {
+    return fd_linear(FDIPT_PREC_F32, R, l.out, l.in, A, lda, P + l.w, l.in, P + l.b, nullptr, 0, nullptr, 0, out, ldo, st);
+  }
+  int d2d(void* dst, const void* src, size_t bytes) const {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess ? FDIPT_OK : FDIPT_ELAUNCH;
+  }
+  // inner traces (parity tests): rows of width `cols` (leading dimension ld) -> slot of block b
+  int inner(int b, int slot, const float* src, int ld, int cols) const {
+    if (!a->trace_inner) return FDIPT_OK;
+    float* dst = a->trace_inner + ((size_t)(b * 4 + slot) * R) * iv.d_t;
+    return hipMemcpy2DAsync(dst, (size_t)iv.d_t * 4, src, (size_t)ld * 4, (size_t)cols * 4, R, hipMemcpyDeviceToDevice, st) == hipSuccess
+               ? FDIPT_OK : FDIPT_ELAUNCH;
+  }
+  bool first_block(int b) const { return b == 0 || p.op != OP_ALL; }  // its buffers' pads are unknown (per-op: the caller's workspace)
+  // the pair bias of block b's attention was written (tiled order) by the producer of its z
+  bool bias_ready(int b) const { return p.op == OP_ALL && (b == 0 ? p.ee_bias : (p.et == ET_ET3 || p.et == ET_ET4) && p.et_bias); }
+  bool fold_et_rows(int b) const { return p.et_rows == ETR_FOLDED && b < d->num_blocks - 1; }
+  L2Warm warm_of(int b, WarmOf next, int l = 0) const {
+    const DBlock& db = L.blk[b];
+    const int cs = d->c_s, dt = iv.d_t;
+    const unsigned tb = (unsigned)fd_chain_image_bytes(cs, cs);
+    switch (next) {
+      case WARM_QKV: {  // layer l's in_proj (fd_seq_qkv)
+        const unsigned n = (unsigned)fd_chain_image_bytes(3 * dt, dt);
+        return L2Warm{{D + db.ch.inp[l], p.split ? D + db.lo.inp[l] : nullptr, nullptr}, {n, p.split ? n : 0u, 0}};
+      }
+      case WARM_TAIL: {  // layer l's tail (fd_tfmr_tail)
+        const unsigned wimg = (unsigned)fd_chain_image_bytes(dt, dt);
+        if (p.tail == NF_ROWS16) {  // its three hi images and its three lo images (each run contiguous; the last layer's run ends with post_tfmr)
+          const unsigned run = 3 * wimg + (l + 1 == d->tfmr_layers ? (unsigned)fd_chain_image_bytes(cs, dt) : 0u);
+          return L2Warm{{D + db.lo.o16[l][0], D + db.lo.o16[l][1], nullptr}, {run, run, 0}};
+        }
+        return L2Warm{{D + db.ch.outp[l], D + db.ch.l1[l], D + db.ch.l2n[l]}, {wimg, wimg, wimg}};
+      }
+      case WARM_POST: return L2Warm{{D + db.ch.post, nullptr, nullptr}, {(unsigned)fd_chain_image_bytes(cs, dt), 0, 0}};
+      case WARM_TRANSITION:
+        if (p.transition == NF_ROWS16) return L2Warm{{D + db.lo.tr16[0][0], D + db.lo.tr16[0][1], nullptr}, {3 * tb, 3 * tb, 0}};  // (hi run, lo run)
+        if (p.split) return L2Warm{{D + db.ch.t1, D + db.ch.t2n, D + db.lo.t1}, {tb, 2 * tb, 3 * tb}};  // (t2n | t3n and lo t1 | t2 | t3 are contiguous)
+        [[fallthrough]];
+      case WARM_TRANSITION32:  // (the post_tfmr chain hands over the 32-row hi images whatever the transition form)
+        return L2Warm{{D + db.ch.t1, D + db.ch.t2n, D + db.ch.t3n}, {tb, tb, tb}};
+      case WARM_ET_ROWS: {  // the EdgeTransition row launch (lo et_init | r4w are contiguous)
+        const unsigned ei = (unsigned)fd_chain_image_bytes(iv.cb, cs), r4 = (unsigned)fd_chain_image_bytes(2 * (iv.hid + d->c_z), iv.cb);
+        return L2Warm{{D + db.ch.et_init, D + db.ch.r4w, p.split ? D + db.lo.et_init : nullptr}, {ei, r4, p.split ? ei + r4 : 0u}};
+      }
+      case WARM_ET_FOLDED: {  // the transition launch's own later-stage images (hi run, lo run)
+        const unsigned run = (unsigned)(fd_chain_image_bytes(iv.cb, cs) + fd_chain_image_bytes(2 * (iv.hid + d->c_z), iv.cb));
+        return L2Warm{{D + db.lo.ei16[0], D + db.lo.ei16[1], nullptr}, {run, run, 0}};
+      }
+      case WARM_TORSION:
+        if (p.torsion == NF_ROWS16) return L2Warm{{D + L.tor16[0][0], D + L.tor16[0][1], nullptr}, {2 * tb, 2 * tb, 0}};  // (hi run, lo run)
+        return L2Warm{{D + L.ch_tor1, D + L.ch_tor2n, p.split ? D + L.lo_tor1 : nullptr}, {tb, tb, p.split ? 2 * tb : 0u}};  // (lo tor1 | tor2 are contiguous)
+    }
+    return L2Warm{};
+  }
+  // ---- Embedder (score_network.py:129-197)
+  int embed_stage() const {
+    const int cs = d->c_s, cz = d->c_z;
+    RC(fd_build_feats(B, N, d->use_aatype, d->index_embed, a->aatype, a->t_emb, a->t_emb_eps, a->fixed_mask, a->idx_emb, F(w.node_feat),
+                      L.kn_pad, F(w.pte), L.d1_pad, p.feats_fused ? a->rigids_t : nullptr, a->res_mask, d->coordinate_scaling, F(w.quat),
+                      F(w.trans), F(w.dmask), (const float*)(D + L.w1i), (const float*)(D + L.w1j), (const float*)(D + L.b1), cz,
+                      p.feats_fused ? F(w.pi) : nullptr, F(w.pj), a->step_cursor, st));
+    if (p.embed == NF_GEMM) {
+      RC(fd_linear(d->precision, R, cs, L.kn_pad, F(w.node_feat), L.kn_pad, D + L.ne0_pad, L.kn_pad, P + iv.ne0.b, nullptr, 0, nullptr, 1,
+                   F(w.h_a), cs, st));
+      RC(lin(iv.ne2, F(w.h_a), cs, nullptr, 0, nullptr, 1, F(w.h_b), cs));
+      RC(lin(iv.ne4, F(w.h_b), cs, nullptr, 0, nullptr, 0, F(w.h_a), cs));
+      RC(fd_layernorm(R, cs, F(w.h_a), cs, nullptr, 0, P + iv.neln.g, P + iv.neln.b, a->res_mask, F(w.node0), cs, st));
+    } else {
+      const bool r16 = p.embed == NF_ROWS16;
+      RowBlockArgs r;
+      r.M = R; r.in = F(w.node_feat); r.ld_in = L.kn_pad;
+      r.w0 = D + (r16 ? L.ne16[0][0] : L.ch_ne0); r.w1 = D + (r16 ? L.ne16[1][0] : L.ch_ne2n); r.w2 = D + (r16 ? L.ne16[2][0] : L.ch_ne4n);
+      if (p.split) {
+        r.w0l = D + (r16 ? L.ne16[0][1] : L.lo_ne0); r.w1l = D + (r16 ? L.ne16[1][1] : L.lo_ne2); r.w2l = D + (r16 ? L.ne16[2][1] : L.lo_ne4);
+      }
+      r.b0 = P + iv.ne0.b; r.b1 = P + iv.ne2.b; r.b2 = P + iv.ne4.b;
+      r.gamma = P + iv.neln.g; r.beta = P + iv.neln.b; r.rowmask_post = a->res_mask; r.out = F(w.node0); r.ld_out = cs;
+      if (p.skip == SKIP_EMBED16) {  // skip_embed(init_node) of all blocks as a fourth layer of the same launch
+        r.w3 = D + L.skip16[0]; r.w3l = D + L.skip16[1]; r.b3 = (const float*)(D + L.skip_b);
+        r.out2 = F(w.skip_all); r.ld_out2 = d->num_blocks * d->c_skip;
+        // (the kernel touches its own last stage's images while it starts: they were last read a whole step ago)
+        // ... and so were its own hi / lo runs (ne16: three images each; skip16 hi | lo are contiguous)
+        const unsigned run = (unsigned)(fd_chain_image_bytes(256, 96) + 2 * fd_chain_image_bytes(256, 256));
+        r.warm = L2Warm{{r.w0, r.w0l, r.w3}, {run, run, 2 * (unsigned)fd_chain_image_bytes(256, 256)}};
+      }
+      if (r16) RC(fd_node_embed16(r, L.kn_pad, st));
+      else if (p.split) RC(fd_rowblock(L.kn_pad == 72 ? FD_RB_NODE_EMBED_72_SPLIT : FD_RB_NODE_EMBED_88_SPLIT, r, st));
+      else RC(fd_rowblock(L.kn_pad == 72 ? FD_RB_NODE_EMBED_72 : FD_RB_NODE_EMBED_88, r, st));
+    }
+    if (!p.feats_fused) {
+      RC(fd_linear(FDIPT_PREC_F32, R, cz, L.d1_pad, F(w.pte), L.d1_pad, D + L.w1i, L.d1_pad, (const float*)(D + L.b1), nullptr, 0,
+                   nullptr, 0, F(w.pi), cz, st));
+      RC(fd_linear(FDIPT_PREC_F32, R, cz, L.d1_pad, F(w.pte), L.d1_pad, D + L.w1j, L.d1_pad, nullptr, nullptr, 0, nullptr, 0,
+                   F(w.pj), cz, st));
+    }
+    EdgeEmbedArgs ea;
+    ea.B = B; ea.N = N; ea.n_rel = a->n_rel; ea.rel_off = a->rel_off; ea.num_bins = d->num_bins;
+    ea.pi = F(w.pi); ea.pj = F(w.pj); ea.rtab = (const float*)setup; ea.dtab = (const float*)(D + L.dtab);
+    ea.edges = (const float*)(D + L.edges); ea.seq_idx = a->seq_idx; ea.sc_ca = a->sc_ca_t;
+    ea.w2 = WM(iv.ee2); ea.w3 = WM(iv.ee4); ea.b2 = P + iv.ee2.b; ea.b3 = P + iv.ee4.b;
+    ea.gamma = P + iv.eeln.g; ea.beta = P + iv.eeln.b; ea.res_mask = a->res_mask; ea.z_out = W + w.z;
+    ea.trace = a->trace_edge; ea.reserve_cus = a->reserve_cus;
+    ea.wb_img = p.ee_bias ? D + L.blk[0].wb_img4 : nullptr; ea.bb = (const float*)(D + L.blk[0].bb); ea.bias_out = F(w.bias); ea.H = d->no_heads;
+    if (p.pz) {
+      ea.wdz_img = D + L.blk[0].wdz_imgp; ea.wdz_img_lo = D + L.blk[0].wdz_imgp_lo; ea.bdz = P + iv.blk[0].dz.b; ea.pz_out = (half_t*)(W + w.pz);
+    }
+    if (p.regpair) RC(fd_edge_embed2(ea, D + L.ee2, st));
+    else RC(fd_edge_embed(d->precision, cz, ea, st));
+    return FDIPT_OK;
+  }
+  // ---- IPA (ipa_pytorch.py:244-330), part 1: the fused q | kv | q_pts | kv_pts projection and the global-frame points
+  int ipa_project(int b, const float* node) const {
+    const DBlock& db = L.blk[b];
+    const int cs = d->c_s, H = d->no_heads, C = d->c_hidden, Pq = d->no_qk_points, Pv = d->no_v_points, PT = iv.proj_out - 3 * H * C;
+    PointsArgs pa;
+    pa.B = B; pa.N = N; pa.H = H; pa.Pq = Pq; pa.Pv = Pv; pa.quat = F(w.quat); pa.trans = F(w.trans);
+    pa.qp = F(w.qp); pa.kp = F(w.kp); pa.vp = F(w.vp); pa.rot = F(w.rot);
+    pa.vpt = p.vpt ? (unsigned short*)(W + w.vpt) : nullptr; pa.Np = Np;
+    if (!p.a3) {  // fp32 activations for the LDS / register attention kernels
+      RC(fd_linear(d->precision, R, iv.proj_out, cs, node, cs, D + db.wproj, cs, (const float*)(D + db.bproj), nullptr, 0,
+                   nullptr, 0, F(w.proj), iv.proj_out, st));
+      pa.proj = F(w.proj); pa.ld = iv.proj_out; pa.q_off = 3 * H * C; pa.kv_off = 3 * H * C + 3 * H * Pq;
+      return fd_points(pa, st);
+    }
+    pa.kpf = (unsigned short*)(W + w.kpf); pa.gamma = (const float*)(D + db.gamma); pa.res_mask = a->res_mask;
+    ProjArgs pj;
+    pj.B = B; pj.N = N; pj.H = H; pj.C = C; pj.K = cs; pj.PT = PT; pj.Np = Np; pj.A = node; pj.lda = cs;
+    pj.W = D + db.wproj; pj.bias = (const float*)(D + db.bproj); pj.qscale = sqrtf(1.0f / (3.0f * (float)C));
+    pj.Qb = (half_t*)(W + w.qb); pj.Kb = (half_t*)(W + w.kb); pj.Vt = (half_t*)(W + w.vt); pj.pts = F(w.pts);
+    pj.zero_pads = first_block(b);
+    pj.W_img = cs == 256 ? D + db.wproj_img : nullptr;
+    pj.W_img_lo = pj.W_img && p.split ? D + db.wproj_img_lo : nullptr;
+    if (p.merged) { pj.merged = 1; pj.W_img = D + db.wproj2_img; pj.W_img_lo = D + db.wproj2_img_lo; pj.bias = (const float*)(D + db.bproj2); }
+    if (p.proj_pts) {
+      pj.pts_img = 1; pj.W_img = D + db.wproj2p_img; pj.W_img_lo = D + db.wproj2p_img_lo; pj.bias = (const float*)(D + db.bproj2p);
+      pj.PT = fd_ipa_proj2_points_cols(H, C) - H * C;
+      pj.quat = pa.quat; pj.trans = pa.trans; pj.gamma = pa.gamma; pj.res_mask = pa.res_mask; pj.rot = pa.rot; pj.qp = pa.qp;
+      pj.kpf = pa.kpf; pj.vpt = pa.vpt;
+    }
+    if (p.vt_lo && p.node_rows == NR_PROJ) pj.Vt_lo = (half_t*)(W + w.vt_lo);
+    // padded keys and rows 72..95 of the value-point image are never written: zero once per forward (on the launch that zeroes
+    // the padded keys of Kb / Vt when the second-generation projection runs)
+    const size_t vpt_bytes = (size_t)B * H * 96 * Np * 2;
+    bool vpt_zero = pa.vpt && first_block(b);
+    if (p.proj2) {
+      const bool key_pads = Np > N && p.node_rows == NR_PROJ;  // (fd_node_images writes the padded keys of its images itself)
+      if (pj.zero_pads && p.init_fused) {
+        SeqInitExtra sx = {vpt_zero ? W + w.vpt : nullptr, vpt_zero ? (long)(vpt_bytes >> 4) : 0L, key_pads ? (void*)pj.Kb : nullptr,
+                           (void*)pj.Vt, (long)B * H, C, (void*)pj.Vt_lo};
+        RC(fd_seq_images_init(B, N, d->tfmr_heads, a->res_mask, W + w.seqimg, sx, st));
+        vpt_zero = false;
+      } else if (pj.zero_pads && (key_pads || vpt_zero)) {
+        ProjArgs pz = pj; pz.W_img = nullptr;
+        if (p.node_rows != NR_PROJ) pz.Np = pz.N;  // (no key pads to zero)
+        RC(fd_ipa_proj_zero_pads(pz, vpt_zero ? W + w.vpt : nullptr, vpt_zero ? vpt_bytes : 0, st));
+        vpt_zero = false;
+      }
+      RC(fd_ipa_proj2(pj, st));
+      half_t* vt_lo = p.split ? (half_t*)(W + w.vt_lo) : nullptr;
+      if (p.node_rows == NR_POINTS) { pa.node = node; pa.ld_node = cs; pa.nKb = pj.Kb; pa.nVt = pj.Vt; pa.nVt_lo = vt_lo; }
+      if (p.node_rows == NR_LAUNCH) RC(fd_node_images(B, N, Np, node, cs, pj.Kb, pj.Vt, vt_lo, st));
+    } else RC(fd_ipa_proj(pj, st));
+    if (vpt_zero && hipMemsetAsync(W + w.vpt, 0, vpt_bytes, st) != hipSuccess) return FDIPT_ELAUNCH;
+    pa.proj = F(w.pts); pa.ld = PT; pa.q_off = 0; pa.kv_off = 3 * H * Pq;
+    if (!p.proj_pts) RC(fd_points(pa, st));
+    return FDIPT_OK;
+  }
+  // ---- IPA, part 2: pair bias, attention (features o and the point features) and o_pair (from z, or from the pair_z image)
+  int ipa_attend(int b) const {
+    const DBlock& db = L.blk[b];
+    const int cz = d->c_z, H = d->no_heads, C = d->c_hidden, Pv = d->no_v_points, feat = iv.feat_dim;
+    OPairArgs oa;
+    oa.B = B; oa.N = N; oa.H = H; oa.CZ = cz; oa.CD = cz / 4; oa.z = W + w.z; oa.probs = F(w.probs); oa.probs_h16 = nullptr;
+    oa.probs_np = 0; oa.out_h16 = nullptr; oa.wdz = (const float*)(D + db.wdz_t); oa.wdz_img = p.bf && cz == 128 ? D + db.wdz_img : nullptr;
+    oa.wdz_img_lo = oa.wdz_img && p.split ? D + db.wdz_img_lo : nullptr; oa.bdz = P + iv.blk[b].dz.b;
+    oa.out = F(w.feats); oa.out_ld = feat; oa.off = H * C + 4 * H * Pv;
+    if (p.a3) {
+      Attn3Args a3;
+      a3.B = B; a3.N = N; a3.H = H; a3.Np = Np; a3.Qb = (const half_t*)(W + w.qb); a3.Kb = (const half_t*)(W + w.kb);
+      a3.Vt = (const half_t*)(W + w.vt); a3.Vt_lo = p.vt_lo ? (const half_t*)(W + w.vt_lo) : nullptr; a3.kv_per_sample = p.merged;
+      a3.bias = F(w.bias); a3.res_mask = res_mask; a3.qp = F(w.qp); a3.kp = F(w.kp); a3.vp = F(w.vp); a3.vpt = (const half_t*)(W + w.vpt);
+      a3.kpf = (const half_t*)(W + w.kpf); a3.gamma = (const float*)(D + db.gamma); a3.rot = F(w.rot); a3.trans = F(w.trans);
+      a3.probs = F(w.probs); a3.probs_h16 = nullptr; a3.out_h16 = nullptr; a3.out = F(w.feats); a3.out_ld = feat; a3.pt_off = H * C;
+      if (!bias_ready(b))
+        RC(fd_pair_bias2(B, N, H, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), 1, st));
+      if (p.feats_h16) { a3.out_h16 = (half_t*)(W + w.feats); oa.out_h16 = a3.out_h16; }
+      if (p.probs_h16) { a3.probs_h16 = (half_t*)(W + w.probs); oa.probs_h16 = a3.probs_h16; oa.probs_np = Np; }
+      RC(fd_attention3(a3, st));
+    } else {
+      const long ld = iv.proj_out;
+      AttnArgs aa;
+      aa.B = B; aa.N = N; aa.H = H;
+      aa.q = F(w.proj); aa.q_ld = ld; aa.q_hs = C;
+      aa.k = F(w.proj) + H * C; aa.k_ld = ld; aa.k_hs = 2 * C;
+      aa.v = F(w.proj) + H * C + C; aa.v_ld = ld; aa.v_hs = 2 * C;
+      aa.C = C; aa.Dv = C; aa.scale = sqrtf(1.0f / (3.0f * (float)C));
+      aa.bias = F(w.bias); aa.res_mask = res_mask; aa.qp = F(w.qp); aa.kp = F(w.kp); aa.vp = F(w.vp); aa.Pq = d->no_qk_points; aa.Pv = Pv;
+      aa.gamma = (const float*)(D + db.gamma); aa.rot = F(w.rot); aa.trans = F(w.trans); aa.probs = F(w.probs);
+      aa.out = F(w.feats); aa.out_ld = feat; aa.pt_off = H * C; aa.lds_s = 0;
+      if (p.ipa_bias_f32)
+        RC(fd_pair_bias_f32((long)NN, H, cz, F(w.z), (const float*)(D + db.wb), (const float*)(D + db.bb), F(w.bias), st));  // [B,N,N,H]
+      else
+        RC(fd_linear_z(d->precision, (long)NN, H, cz, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), st));  // [B,N,N,H]
+      if (p.ipa_attn_f32 && fd_ipa_attention_f32_supported(aa)) RC(fd_ipa_attention_f32(aa, st));  // scores in registers (round 5)
+      else RC(fd_attention(d->precision, 1, aa, st));
+    }
+    if (p.pz) {  // (z itself may not have been stored)
+      if (!oa.probs_h16) return FDIPT_EINVAL;
+      oa.pz = (const half_t*)(W + w.pz);
+      return fd_opair_pz(oa, st);
+    }
+    return fd_opair(d->precision, oa, st);
+  }
+  // ---- IPA, part 3: node = LN(node + linear_out(features)) in tf_in[:, :cs]; tf_in[:, cs:] = skip_embed(init_node)   (ipa:531-535)
+  int ipa_out(int b, const float* node) const {
+    const BlockW& k = iv.blk[b];
+    const DBlock& db = L.blk[b];
+    const int cs = d->c_s, dt = iv.d_t, feat = iv.feat_dim;
+    const float* wout = p.merged ? (const float*)(D + db.wout_m) : P + k.out.w;
+    const float* bout = p.merged ? (const float*)(D + db.bout_m) : P + k.out.b;
+    if (p.outproj == OUT_GEMM) {  // (skip_embed per block: the batched launches need the split-K LayerNorm)
+      RC(lin(k.out, F(w.feats), feat, nullptr, 0, res_mask, 0, F(w.ipa_out), cs));
+      RC(fd_layernorm(R, cs, node, cs, F(w.ipa_out), cs, P + k.ipa_ln.g, P + k.ipa_ln.b, nullptr, F(w.tf_in), dt, st));
+      RC(inner(b, 0, F(w.ipa_out), cs, cs));
+      RC(inner(b, 1, F(w.tf_in), dt, cs));
+      return lin(k.skip, F(w.node0), cs, nullptr, 0, nullptr, 0, F(w.tf_in) + cs, dt);
+    }
+    if (p.outproj == OUT_DEDICATED)
+      RC(fd_outproj_split(R, cs, feat, F(w.feats), feat, D + db.wout_img, D + db.wout_img_lo, bout, res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
+    else if (p.outproj == OUT_SPLITK_SPLIT)
+      RC(fd_linear_splitk_split(R, cs, feat, p.slices, F(w.feats), feat, wout, feat, bout, res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
+    else if (p.outproj == OUT_SPLITK_A16)
+      RC(fd_linear_splitk_a16(R, cs, feat, p.slices, (const half_t*)(W + w.feats), feat, WM(k.out), feat, P + k.out.b, res_mask,
+                              F(w.ipa_parts), (long)R * cs, cs, st));
+    else
+      RC(fd_linear_splitk(R, cs, feat, p.slices, F(w.feats), feat, WM(k.out), feat, P + k.out.b, res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
+    // the slices summed in the LayerNorm, which also copies skip_embed(init_node) of this block behind its output when that ran batched
+    const bool skip_batched = p.skip != SKIP_PER_BLOCK;
+    const L2Warm warm = warm_of(b, WARM_QKV, 0);
+    RC(fd_layernorm_parts(R, cs, node, cs, F(w.ipa_parts), cs, p.slices, (long)R * cs, P + k.ipa_ln.g, P + k.ipa_ln.b, nullptr,
+                          F(w.tf_in), dt, skip_batched ? F(w.skip_all) + (size_t)b * d->c_skip : nullptr,
+                          d->num_blocks * d->c_skip, d->c_skip, p.seq == SEQ_FUSED ? &warm : nullptr, st));
+    if (!skip_batched) RC(lin(k.skip, F(w.node0), cs, nullptr, 0, nullptr, 0, F(w.tf_in) + cs, dt));
+    return FDIPT_OK;
+  }
+  // ---- nn.TransformerEncoder, post-norm (ipa:433-443,536-538) on tf_in -> *x_out (not written when post_tfmr rides on the last tail:
+  // that tail writes node + post_tfmr(x) to h_a)
+  int seq_stage(int b, const float** x_out) const {
+    const BlockW& k = iv.blk[b];
+    const DBlock& db = L.blk[b];
+    const int dt = iv.d_t, cs = d->c_s, th = d->tfmr_heads, hd = dt / th;
+    const float* x = F(w.tf_in);
+    for (int l = 0; l < d->tfmr_layers; ++l) {
+      const TfLayer& t = k.tf[l];
+      const bool last = l + 1 == d->tfmr_layers;
+      if (p.seq == SEQ_FUSED) {  // default bf16 path: in_proj writes the attention operand images directly (attention_seq.hip)
+        if (b == 0 && l == 0 && !p.init_fused) RC(fd_seq_images_init(B, N, th, res_mask, W + w.seqimg, SeqInitExtra{}, st));
+        RC(fd_seq_qkv(B, N, th, x, dt, D + db.ch.inp[l], p.split ? D + db.lo.inp[l] : nullptr, P + t.inp.b, 1.0f / sqrtf((float)hd),
+                      W + w.seqimg, st));
+        const L2Warm wt = warm_of(b, WARM_TAIL, l);  // ... and the attention touches the weights of the layer's tail kernel, launched next
+        RC(fd_seq_attention_run(B, N, th, W + w.seqimg, F(w.att), dt, &wt, st));
+      } else {
+        RC(lin(t.inp, x, dt, nullptr, 0, nullptr, 0, F(w.qkv), 3 * dt));
+        AttnArgs ta = {};
+        ta.B = B; ta.N = N; ta.H = th;
+        ta.q = F(w.qkv); ta.k = F(w.qkv) + dt; ta.v = F(w.qkv) + 2 * dt;
+        ta.q_ld = ta.k_ld = ta.v_ld = 3 * dt; ta.q_hs = ta.k_hs = ta.v_hs = hd;
+        ta.C = hd; ta.Dv = hd; ta.scale = 1.0f / sqrtf((float)hd); ta.res_mask = res_mask; ta.out = F(w.att); ta.out_ld = dt;
+        if (p.seq == SEQ_BF16) RC(fd_seq_attention(B, N, th, F(w.qkv), 3 * dt, ta.scale, res_mask, W + w.seqimg, F(w.att), dt, st));
+        else if (p.seq == SEQ_F32) RC(fd_seq_attention_f32(B, N, th, F(w.qkv), 3 * dt, ta.scale, res_mask, F(w.att), dt, st));
+        else RC(fd_attention(d->precision, 0, ta, st));
+      }
+      // x_a = norm1(x + out_proj(att)); x_b = norm2(x_a + linear2(relu(linear1(x_a))))
+      if (p.tail == NF_GEMM) {
+        RC(lin(t.outp, F(w.att), dt, nullptr, 0, nullptr, 0, F(w.ff), dt));
+        RC(fd_layernorm(R, dt, x, dt, F(w.ff), dt, P + t.n1.g, P + t.n1.b, nullptr, F(w.x_a), dt, st));
+        RC(lin(t.l1, F(w.x_a), dt, nullptr, 0, nullptr, 1, F(w.ff), dt));
+        RC(lin(t.l2, F(w.ff), dt, nullptr, 0, nullptr, 0, F(w.att), dt));
+        RC(fd_layernorm(R, dt, F(w.x_a), dt, F(w.att), dt, P + t.n2.g, P + t.n2.b, nullptr, F(w.x_b), dt, st));
+        x = F(w.x_b);  // next layer: norm1 reads x_b -> x_a, norm2 reads x_a/att -> x_b (no aliasing)
+        continue;
+      }
+      const bool r16 = p.tail == NF_ROWS16;  // 16-row blocks (150 blocks at 2400 rows)
+      TfmrTailArgs tt;
+      tt.M = R; tt.ld = dt; tt.att = F(w.att); tt.x = x;
+      tt.wo = D + (r16 ? db.lo.o16[l][0] : db.ch.outp[l]); tt.w1 = D + (r16 ? db.lo.f16[l][0] : db.ch.l1[l]); tt.w2 = D + (r16 ? db.lo.g16[l][0] : db.ch.l2n[l]);
+      if (p.split) { tt.wol = D + (r16 ? db.lo.o16[l][1] : db.lo.outp[l]); tt.w1l = D + (r16 ? db.lo.f16[l][1] : db.lo.l1[l]); tt.w2l = D + (r16 ? db.lo.g16[l][1] : db.lo.l2[l]); }
+      tt.bo = P + t.outp.b; tt.g1 = P + t.n1.g; tt.be1 = P + t.n1.b; tt.b1 = P + t.l1.b; tt.b2 = P + t.l2.b; tt.g2 = P + t.n2.g;
+      tt.be2 = P + t.n2.b; tt.out = x == F(w.x_b) ? F(w.x_a) : F(w.x_b);
+      tt.rows16 = r16;
+      const bool post_here = last && p.post == POST_TAIL;
+      if (post_here) {
+        tt.wp = D + (r16 ? db.lo.p16[0] : db.ch.post); tt.wpl = r16 ? D + db.lo.p16[1] : p.split ? D + db.lo.post : nullptr;
+        tt.bp = P + k.post.b; tt.pres = F(w.tf_in); tt.ld_pres = dt; tt.pout = F(w.h_a); tt.ld_pout = cs;
+      }
+      // next launch: the following layer's in_proj, or the transition / post_tfmr
+      if (!last) tt.warm = p.seq == SEQ_FUSED ? warm_of(b, WARM_QKV, l + 1) : L2Warm{};
+      else tt.warm = warm_of(b, post_here ? WARM_TRANSITION : WARM_POST);
+      RC(fd_tfmr_tail(tt, st));
+      x = tt.out;
+    }
+    *x_out = x;
+    return FDIPT_OK;
+  }
+  // ---- node = node + post_tfmr(x); StructureModuleTransition; mask (ipa:539-541, 36-58); BackboneUpdate + compose_q_update_vec
+  // (ipa:542-547): the new node rows in w.node
+  int transition_stage(int b, const float* x) const {
+    const BlockW& k = iv.blk[b];
+    const DBlock& db = L.blk[b];
+    const int cs = d->c_s, dt = iv.d_t;
+    if (p.post == POST_CHAIN) {
+      ChainArgs c;
+      c.M = R; c.in = x; c.ld_in = dt; c.w[0] = D + db.ch.post; c.b[0] = P + k.post.b; c.residual = F(w.tf_in); c.ld_res = dt;
+      c.out = F(w.h_a); c.ld_out = cs;
+      if (p.rbk) c.warm = warm_of(b, WARM_TRANSITION32);
+      RC(fd_chain(FD_CHAIN_POST, c, st));
+    } else if (p.post == POST_GEMM) RC(lin(k.post, x, dt, F(w.tf_in), dt, nullptr, 0, F(w.h_a), cs));
+    if (p.transition == NF_GEMM) {
+      RC(lin(k.t1, F(w.h_a), cs, nullptr, 0, nullptr, 1, F(w.h_b), cs));
+      RC(lin(k.t2, F(w.h_b), cs, nullptr, 0, nullptr, 1, F(w.ipa_out), cs));
+      RC(lin(k.t3, F(w.ipa_out), cs, F(w.h_a), cs, nullptr, 0, F(w.h_b), cs));
+      RC(fd_layernorm(R, cs, F(w.h_b), cs, nullptr, 0, P + k.tln.g, P + k.tln.b, a->res_mask, F(w.node), cs, st));
+      // bb_update(node*diffuse_mask) differs from bb_update(node) only on rows whose update is masked out below, so the input mask is
+      // not materialised
+      RC(lin32(k.bb, F(w.node), cs, F(w.upd), 8));
+      RC(inner(b, 3, F(w.upd), 8, 6));
+      return fd_compose_q_update(R, F(w.quat), F(w.trans), F(w.upd), 8, F(w.dmask), st);
+    }
+    // ... with BackboneUpdate + compose_q_update_vec fused in (the fp32 Linear c_s -> 6 is a per-row dot product)
+    const bool r16 = p.transition == NF_ROWS16;  // 16-row blocks (rowblock.hip: transition16_kernel)
+    RowBlockArgs r;
+    r.M = R; r.in = F(w.h_a); r.ld_in = cs;
+    r.w0 = D + (r16 ? db.lo.tr16[0][0] : db.ch.t1); r.w1 = D + (r16 ? db.lo.tr16[1][0] : db.ch.t2n); r.w2 = D + (r16 ? db.lo.tr16[2][0] : db.ch.t3n);
+    if (p.split) { r.w0l = D + (r16 ? db.lo.tr16[0][1] : db.lo.t1); r.w1l = D + (r16 ? db.lo.tr16[1][1] : db.lo.t2); r.w2l = D + (r16 ? db.lo.tr16[2][1] : db.lo.t3); }
+    r.b0 = P + k.t1.b; r.b1 = P + k.t2.b; r.b2 = P + k.t3.b; r.residual = F(w.h_a); r.ld_res = cs; r.gamma = P + k.tln.g; r.beta = P + k.tln.b;
+    r.rowmask_post = a->res_mask; r.out = F(w.node); r.ld_out = cs; r.bb_w = P + k.bb.w; r.bb_b = P + k.bb.b;
+    r.upd_mask = F(w.dmask); r.quat = F(w.quat); r.trans = F(w.trans);
+    // next launch: the EdgeTransition row launch, or the torsion head
+    if (b < d->num_blocks - 1 && p.et_widths) r.warm = warm_of(b, WARM_ET_ROWS);
+    else if (b == d->num_blocks - 1) r.warm = warm_of(b, WARM_TORSION);
+    if (fold_et_rows(b)) {
+      // EdgeTransition's row launch (e = initial_embed(node), fold columns -> edge_transition4's images) folded into this launch: the
+      // rows it needs are this launch's output rows
+      r.we0 = D + db.lo.ei16[0]; r.we0l = D + db.lo.ei16[1]; r.we1 = D + db.lo.r416[0]; r.we1l = D + db.lo.r416[1];
+      r.be0 = P + k.et_init.b; r.be1 = (const float*)(D + db.ch.r4b);
+      r.img_a = W + w.a1img; r.img_b = W + w.b1img; r.img_B = B; r.img_N = N;
+      r.warm = warm_of(b, WARM_ET_FOLDED);
+    }
+    if (r16) return fd_transition16(r, st);
+    return fd_rowblock(p.split ? FD_RB_TRANSITION_BB_SPLIT : FD_RB_TRANSITION_BB, r, st);
+  }
+  // ---- EdgeTransition of block b (ipa:565-572 / 60-96): z <- EdgeTransition(node, z)
+  int edge_transition_stage(int b, const float* node) const {
+    const BlockW& k = iv.blk[b];
+    const DBlock& db = L.blk[b];
+    const int cs = d->c_s, cz = d->c_z;
+    // the per-residue rows: e = initial_embed(node) and the e_i / e_j parts of the concat-free layers in ONE row-block launch
+    RowBlockArgs r;
+    r.M = R; r.in = node; r.ld_in = cs; r.w0 = D + db.ch.et_init; r.b0 = P + k.et_init.b;
+    if (p.et == ET_ET4 && !fold_et_rows(b)) {  // [A1 | Af | B1 | Bf] as edge_transition4's fold-fragment images
+      r.w1 = D + db.ch.r4w; r.b1 = (const float*)(D + db.ch.r4b); r.out = F(w.r4); r.ld_out = 1024;
+      r.img_a = W + w.a1img; r.img_b = W + w.b1img; r.img_B = B; r.img_N = N;
+      if (p.et_rows == ETR_ROWS) {
+        RC(fd_rowblock(FD_RB_ET4_ROWS, r, st));
+        RC(fd_et4_row_images(F(w.r4), B, N, W + w.a1img, W + w.b1img, st));
+      } else {  // the row-block epilogue writes the fold-fragment images itself
+        if (p.split) { r.w0l = D + db.lo.et_init; r.w1l = D + db.lo.r4w; }
+        RC(fd_rowblock(FD_RB_ET4_IMAGES, r, st));
+      }
+    } else if (p.et == ET_ET3) {  // A1 | Af rows and e in half precision
+      r.w1 = D + db.ch.a1af; r.b1 = (const float*)(D + db.ch.b1f); r.out = F(w.a1); r.ld_out = iv.hid; r.out2 = F(w.af); r.ld_out2 = cz;
+      r.split = iv.hid; r.hid_h16 = (unsigned short*)(W + w.e_bf);
+      RC(fd_rowblock(FD_RB_ET_ROWS, r, st));
+    } else if (p.et == ET_CHAIN) {
+      ChainArgs c;
+      c.M = R; c.in = node; c.ld_in = cs; c.w[0] = D + db.ch.et_init; c.b[0] = P + k.et_init.b; c.out_h16 = (unsigned short*)(W + w.e_bf);
+      c.out = F(w.e); c.ld_out = iv.cb;
+      RC(fd_chain(FD_CHAIN_ETINIT, c, st));
+    } else if (p.et == ET_GEMM) {
+      RC(lin(k.et_init, node, cs, nullptr, 0, nullptr, 0, F(w.e), iv.cb));
+      if (p.bf) RC(fd_f32_to_half((long)R * iv.cb, F(w.e), (half_t*)(W + w.e_bf), st));
+    }
+    float* tr_ptr = a->trace_edge ? a->trace_edge + (size_t)(b + 1) * NN * cz : nullptr;
+    if (a->ev_start && a->ev_start[b]) hipEventRecord((hipEvent_t)a->ev_start[b], st);
+    if (p.et == ET_ET4 || p.et == ET_ET3) {
+      ET2Args t2;
+      t2.B = B; t2.N = N; t2.z_in = (const half_t*)(W + w.z); t2.z_out = (half_t*)(W + w.z); t2.e = F(w.e);
+      t2.e_h16 = (const half_t*)(W + w.e_bf);
+      t2.a1 = F(w.a1); t2.af = F(w.af); t2.stream = D + (p.et == ET_ET4 ? db.et4 : db.et3); t2.b2 = P + k.et2.b; t2.gamma = P + k.et_ln.g;
+      t2.beta = P + k.et_ln.b; t2.res_mask = a->res_mask; t2.trace = tr_ptr;
+      // the next block's attention consumes linear_b(z') in fragment order when it runs attention3
+      // (end to end +0.8 % at N = 300: the launch grows by about as much as the pair_bias2 launch it replaces, the gain
+      //  is the z re-read that disappears; FDIPT_KF_UNFOLDED restores the separate pass)
+      const DBlock& next = L.blk[b + 1];
+      t2.wb_img = p.et_bias ? D + (p.et == ET_ET4 ? next.wb_img4 : next.wb_img3) : nullptr;
+      t2.a1_img = W + w.a1img; t2.b1_img = W + w.b1img;
+      t2.bb = (const float*)(D + next.bb); t2.bias_out = F(w.bias); t2.H = d->no_heads; t2.reserve_cus = a->reserve_cus;
+      if (p.pz) {
+        t2.bdz = P + iv.blk[b + 1].dz.b; t2.pz_out = (half_t*)(W + w.pz);  // (down_z itself: the last chunk of the weight stream)
+        // the last EdgeTransition of the trunk: block b + 1 takes bias and pair_z from this epilogue and no launch reads z' itself
+        if (b + 1 == d->num_blocks - 1 && !tr_ptr) t2.z_out = nullptr;
+      }
+      t2.clock = a->clock_out;
+      if (p.et == ET_ET4) RC(fd_edge_transition4(t2, st));
+      else RC(fd_edge_transition3(t2, st));
+    } else {
+      EdgeTransArgs ta;
+      ta.B = B; ta.N = N; ta.z_in = W + w.z; ta.z_out = W + w.z; ta.e = F(w.e);
+      ta.w1 = WM(k.et1); ta.w2 = WM(k.et2); ta.wf = WM(k.etf); ta.b1 = P + k.et1.b; ta.b2 = P + k.et2.b; ta.bf = P + k.etf.b;
+      ta.gamma = P + k.et_ln.g; ta.beta = P + k.et_ln.b; ta.res_mask = a->res_mask; ta.trace = tr_ptr; ta.clock = a->clock_out;
+      RC(fd_edge_transition(d->precision, cz, iv.cb, ta, st));
+    }
+    if (a->ev_stop && a->ev_stop[b]) hipEventRecord((hipEvent_t)a->ev_stop[b], st);
+    return FDIPT_OK;
+  }
+  // ---- heads: torsion (ipa:332-363), tensor_7, scores (ipa:552-564), backbone (sn:269-273)
+  int heads_stage(const float* node) const {
+    const int cs = d->c_s;
+    if (p.torsion == NF_GEMM) {
+      RC(lin(iv.tor1, node, cs, nullptr, 0, nullptr, 1, F(w.h_a), cs));
+      RC(lin(iv.tor2, F(w.h_a), cs, node, cs, nullptr, 0, F(w.h_b), cs));
+    } else {
+      const bool r16 = p.torsion == NF_ROWS16;
+      RowBlockArgs r;
+      r.M = R; r.in = node; r.ld_in = cs; r.w0 = D + (r16 ? L.tor16[0][0] : L.ch_tor1); r.w1 = D + (r16 ? L.tor16[1][0] : L.ch_tor2n);
+      if (p.split) { r.w0l = D + (r16 ? L.tor16[0][1] : L.lo_tor1); r.w1l = D + (r16 ? L.tor16[1][1] : L.lo_tor2); }
+      r.b0 = P + iv.tor1.b; r.b1 = P + iv.tor2.b; r.residual = node; r.ld_res = cs; r.out = F(w.h_b); r.ld_out = cs;
+      if (r16) RC(fd_torsion16(r, st));
+      else RC(fd_rowblock(p.split ? FD_RB_TORSION_SPLIT : FD_RB_TORSION, r, st));
+    }
+    if (!p.torf_fused) RC(lin32(iv.torf, F(w.h_b), cs, F(w.psi_un), 8));
+    // tensor_7 / psi epilogue, R^3 score and IGSO(3) score in one launch (frames.hip); the backbone atoms of the finished frames ride on it
+    // (one atom per lane of a residue's 16) unless the launch folds are off
+    const bool atoms = a->atom37 || a->atom14;
+    if (atoms && !a->bb_tables) return FDIPT_EINVAL;
+    const bool bb_fold = atoms && p.bb_fold;
+    RC(fd_score_tail(B, N, a->rigids_t, F(w.quat), F(w.trans), d->coordinate_scaling, F(w.psi_un), 8, a->gt_psi, a->fixed_mask,
+                     a->res_mask, a->so3_sigma, a->t, d->r3_min_b, d->r3_max_b, a->rigids, a->psi, a->rot_score, a->trans_score,
+                     a->ca_out, p.torf_fused ? F(w.h_b) : nullptr, cs, cs, P + iv.torf.w, P + iv.torf.b, a->so3_score_table,
+                     a->so3_omega_edges, a->so3_num_omega, a->aatype, bb_fold ? a->bb_tables : nullptr, bb_fold ? a->atom37 : nullptr,
+                     bb_fold ? a->atom14 : nullptr, a->step_cursor, st));
+    if (atoms && !bb_fold)
+      RC(fd_backbone(R, a->rigids, nullptr, nullptr, 0, a->psi, a->aatype, a->bb_tables, a->atom37, a->atom14, st, a->step_cursor));
+    return FDIPT_OK;
+  }
+};
 
 static int forward_impl(const FdiptDims* d, const float* P, const void* derived, const void* setup,
                         const FdiptForwardArgs* a, void* workspace, size_t workspace_bytes, fdipt_stream_t stream, const OpSel& op) {
@@ -725,7 +1303,6 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
     return FDIPT_EINVAL;
   if ((op.kind == OP_POINTS || op.kind == OP_IPA) && !a->rigids_t) return FDIPT_EINVAL;
   if (op.kind != OP_ALL && op.kind != OP_EMBED && (op.block < 0 || op.block >= d->num_blocks - (op.kind == OP_ET ? 1 : 0))) return FDIPT_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
   Inventory iv;
   DLayout L;
   WS w;
@@ -735,647 +1312,68 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
   build_ws(d, iv, L, B, N, w);
   if (workspace_bytes < w.total) return FDIPT_ESIZE;
   if ((long)B * N * N > 2000000000L / 1) return FDIPT_ESIZE;
-  char* W = (char*)workspace;
-  const char* D = (const char*)derived;
-  const int prec = d->precision, cs = d->c_s, cz = d->c_z, H = d->no_heads, C = d->c_hidden, Pq = d->no_qk_points,
-            Pv = d->no_v_points, E = d->index_embed, dt = iv.d_t;
-  const bool bf = prec == FDIPT_PREC_HALF;
-  const half_t* PB = (const half_t*)(D + L.h16_base);
-  // operand-precision view of a weight matrix of the fp32 blob
-  auto WM = [&](const LinW& l) -> const void* { return bf ? (const void*)(PB + l.w) : (const void*)(P + l.w); };
-  auto F = [&](size_t off) { return (float*)(W + off); };
-  auto lin = [&](int M, const LinW& l, const float* A, int lda, const float* res, int ldr, const float* rm, int relu,
-                 float* out, int ldo) {
-    return fd_linear(prec, M, l.out, l.in, A, lda, WM(l), l.in, P + l.b, res, ldr, rm, relu, out, ldo, st);
-  };
-  auto lin32 = [&](int M, const LinW& l, const float* A, int lda, float* out, int ldo) {
-    return fd_linear(FDIPT_PREC_F32, M, l.out, l.in, A, lda, P + l.w, l.in, P + l.b, nullptr, 0, nullptr, 0, out, ldo, st);
-  };
-  const float* res_mask = a->res_mask;
-  // fused chains (chain.hip) where they beat the GEMM + LayerNorm launches they replace at B*N ~ 2400 rows on MI355X
-  // (profiles/r01_chain_vs_gemm.md): post_tfmr and EdgeTransition.initial_embed when the row-block kernels below do not take them;
-  // the 320-wide transformer layers (FFN, out_proj, in_proj) and skip_embed stay on the tiled GEMM, which spreads over 10x more CUs.
-  const bool chn_all = use_chain(d);
-  Switches sw_ = switches_of(d);
-  // 16-row node-path blocks pay off while they are about one round of the chip (B N <= ~4000 rows: twice the blocks of the 32-row kernels, each
-  // streaming all weights, half the matrix work per block); with every CU busy anyway the 32-row kernels move half the weight bytes (measured: c4
-  // with 64 samples per GPU 1.277 -> 1.246 M).  The choice goes by N alone — a sample's result must not depend on the batch it rides in.
-  if (N > 512) sw_.no_tail16 = true;
-  const Switches sw = sw_;
-  // row-complete fused MLPs (rowblock.hip) take the multi-layer kinds and the 320-wide transformer layers (use_chain implies the
-  // widths, and FDIPT_KF_UNFUSED_NODE clears both: rbk == chn_all)
-  const bool rbk = chn_all && cs == 256 && iv.d_t == 320 && !sw.no_rowblock;
-  // split operands (hi + lo half-precision parts, 3 MFMAs per k-step) for the dense layers of the node path, whose operand
-  // rounding dominates the error of the predicted frames and psi (tests/err_budget.py): node embedder, IPA projection and output
-  // projection, attention P V, o_pair down-projection, sequence transformer (in_proj, out_proj, feed-forward), post_tfmr, transition,
-  // EdgeTransition per-residue rows, skip_embed, torsion head
-  const bool split = rbk && !sw.no_split;
-  const void *rb_l0 = nullptr, *rb_l1 = nullptr, *rb_l2 = nullptr;  // one-shot: lo images for the next rblock() call
-  const void *rb_w3 = nullptr, *rb_w3l = nullptr; const float* rb_b3 = nullptr; float* rb_out2 = nullptr; int rb_ld2 = 0;  // one-shot: fused skip layer (fd_node_embed16)
-  bool skip_fused = false;
-  int rb16 = 0;  // one-shot: the next rblock() call runs on 16-row blocks (1: node embedder, 2: torsion head; its w0 .. / lo pointers are 16-row images)
-  auto rblock = [&](int kind, const float* in, int ld_in, const void* w0, const float* b0, const void* w1, const float* b1,
-                    const void* w2, const float* b2, const float* resid, int ld_res, const LNW* lnw, const float* post,
-                    float* out, int ld_out) {
-    RowBlockArgs r;
-    r.w0l = rb_l0; r.w1l = rb_l1; r.w2l = rb_l2; rb_l0 = rb_l1 = rb_l2 = nullptr;
-    r.M = R; r.in = in; r.ld_in = ld_in; r.w0 = w0; r.w1 = w1; r.w2 = w2; r.b0 = b0; r.b1 = b1; r.b2 = b2; r.residual = resid;
-    r.ld_res = ld_res; r.gamma = lnw ? P + lnw->g : nullptr; r.beta = lnw ? P + lnw->b : nullptr; r.rowmask_post = post;
-    r.out = out; r.ld_out = ld_out; r.bb_w = r.bb_b = r.upd_mask = nullptr; r.quat = r.trans = nullptr;
-    r.out2 = nullptr; r.ld_out2 = r.split = 0; r.hid_h16 = nullptr;
-    const int k16 = rb16;
-    rb16 = 0;
-    if (k16 == 1 && rb_w3) {
-      r.w3 = rb_w3; r.w3l = rb_w3l; r.b3 = rb_b3; r.out2 = rb_out2; r.ld_out2 = rb_ld2; rb_w3 = rb_w3l = nullptr;
-      // (the kernel touches its own last stage's images while it starts: they were last read a whole step ago)
-      // ... and so were its own hi / lo runs (ne16: three images each; skip16 hi | lo are contiguous)
-      const unsigned run = (unsigned)(fd_chain_image_bytes(256, 96) + 2 * fd_chain_image_bytes(256, 256));
-      r.warm = L2Warm{{w0, r.w0l, r.w3}, {run, run, 2 * (unsigned)fd_chain_image_bytes(256, 256)}};
-    }
-    if (k16 == 1) return fd_node_embed16(r, ld_in, st);
-    if (k16 == 2) return fd_torsion16(r, st);
-    return fd_rowblock(kind, r, st);
-  };
-  unsigned short* chain_h16 = nullptr;  // one-shot: the next chain() call also writes a bf16 copy of its output rows
-  L2Warm chain_warm = {};                // one-shot: the next chain() call touches these weights (L2 warm-up hand-over)
-  auto chain = [&](int kind, const float* in, int ld_in, const void* w0, const float* b0, const void* w1, const float* b1,
-                   const void* w2, const float* b2, const float* resid, int ld_res, const LNW* lnw, const float* pre,
-                   const float* post, float* out, int ld_out) {
-    ChainArgs c;
-    c.M = R; c.in = in; c.ld_in = ld_in; c.w[0] = w0; c.w[1] = w1; c.w[2] = w2; c.b[0] = b0; c.b[1] = b1; c.b[2] = b2;
-    c.residual = resid; c.ld_res = ld_res; c.gamma = lnw ? P + lnw->g : nullptr; c.beta = lnw ? P + lnw->b : nullptr;
-    c.rowmask_pre = pre; c.rowmask_post = post; c.out = out; c.ld_out = ld_out; c.out_h16 = chain_h16; chain_h16 = nullptr;
-    c.warm = chain_warm; chain_warm = L2Warm{};
-    return fd_chain(kind, c, st);
-  };
-
-  // inner traces (parity tests): rows of width `cols` (leading dimension ld) -> slot of block b
-  auto inner = [&](int b, int slot, const float* src, int ld, int cols) -> int {
-    if (!a->trace_inner) return FDIPT_OK;
-    float* dst = a->trace_inner + ((size_t)(b * 4 + slot) * R) * dt;
-    return hipMemcpy2DAsync(dst, (size_t)dt * 4, src, (size_t)ld * 4, (size_t)cols * 4, R, hipMemcpyDeviceToDevice, st) == hipSuccess
-               ? FDIPT_OK : FDIPT_ELAUNCH;
-  };
-  if (a->trace_inner && (rbk || (bf && iv.feat_dim >= 1024 && !sw.no_splitk))) return FDIPT_EINVAL;  // fused node path: the tensors never exist
-  bool ee_bias_done = false;
-  // the IPA's attention3 / o_pair arguments that are the same for every block (the trunk adds the block's weights)
-  const int Np = (N + 31) / 32 * 32;
-  Attn3Args a3_all;
-  a3_all.B = B; a3_all.N = N; a3_all.H = H; a3_all.Np = Np; a3_all.Qb = (const half_t*)(W + w.qb); a3_all.Kb = (const half_t*)(W + w.kb);
-  a3_all.Vt = (const half_t*)(W + w.vt); a3_all.Vt_lo = nullptr; a3_all.bias = F(w.bias); a3_all.res_mask = res_mask; a3_all.qp = F(w.qp);
-  a3_all.kp = F(w.kp); a3_all.vp = F(w.vp); a3_all.vpt = (const half_t*)(W + w.vpt); a3_all.kpf = (const half_t*)(W + w.kpf); a3_all.gamma = nullptr;
-  a3_all.rot = F(w.rot); a3_all.trans = F(w.trans); a3_all.probs = F(w.probs); a3_all.probs_h16 = nullptr; a3_all.out_h16 = nullptr;
-  a3_all.out = F(w.feats); a3_all.out_ld = iv.feat_dim; a3_all.pt_off = H * C;
-  OPairArgs oa_all;
-  oa_all.B = B; oa_all.N = N; oa_all.H = H; oa_all.CZ = cz; oa_all.CD = cz / 4; oa_all.z = W + w.z; oa_all.probs = F(w.probs); oa_all.probs_h16 = nullptr;
-  oa_all.probs_np = 0; oa_all.out_h16 = nullptr; oa_all.wdz = (const float*)(D + L.blk[0].wdz_t); oa_all.wdz_img = (bf && cz == 128) ? D + L.blk[0].wdz_img : nullptr;
-  oa_all.wdz_img_lo = nullptr; oa_all.bdz = nullptr; oa_all.out = F(w.feats); oa_all.out_ld = iv.feat_dim; oa_all.off = H * C + 4 * H * Pv;
-  const IpaPath ipa = ipa_path(d, sw, a3_all, oa_all);
-  // Round 6: o_pair reads pair_z = down_z(z) + b (32 channels) emitted by the producer of z — the edge embedder's epilogue for block 0, the
-  // EdgeTransition epilogue of block b for block b + 1 — instead of streaming the 128 channels of z once more per block (opair_pz_kernel).
-  // The producers: the pair-bias emission of those epilogues, edge_transition4 only (N % 4 == 0); FDIPT_KF_UNFOLDED / FDIPT_KF_PASS_Z
-  // keep the pass over z.  The consumer: the IPA path that reads pair_z (ipa_path).
-  const bool pz_path = op.kind == OP_ALL && ipa.probs_h16 && use_regpair(d) && rbk && iv.cb == 128 && iv.hid == 384 && !sw.no_et_bias &&
-                       !sw.no_ee_bias && !sw.et3 && !sw.no_pz && fd_edge_transition4_supported(N);
-  bool pz_ready = false;  // the pair_z image of the coming block's IPA is in the workspace
-  // ---- Embedder (score_network.py:129-197)
-  // ... with the split of x_t (ipa_pytorch.py:516-524) and the per-residue halves of the first edge-embedder layer in the same
-  // launch (FDIPT_KF_UNFOLDED: three GEMM / element-wise launches more)
-  const bool feats_fused = L.d1_pad <= 128 && (L.d1_pad & 3) == 0 && !sw.feats_unfused && (op.kind == OP_ALL);
-  const bool run_embed = op.kind == OP_ALL || op.kind == OP_EMBED;
-  const size_t NN = (size_t)R * N;
-  auto embed = [&]() -> int {
-  RC(fd_build_feats(B, N, d->use_aatype, E, a->aatype, a->t_emb, a->t_emb_eps, a->fixed_mask, a->idx_emb, F(w.node_feat),
-                    L.kn_pad, F(w.pte), L.d1_pad, feats_fused ? a->rigids_t : nullptr, res_mask, d->coordinate_scaling, F(w.quat),
-                    F(w.trans), F(w.dmask), (const float*)(D + L.w1i), (const float*)(D + L.w1j), (const float*)(D + L.b1), cz,
-                    feats_fused ? F(w.pi) : nullptr, F(w.pj), a->step_cursor, st));
-  if (rbk && (L.kn_pad == 72 || L.kn_pad == 88)) {
-    if (split) { rb_l0 = D + L.lo_ne0; rb_l1 = D + L.lo_ne2; rb_l2 = D + L.lo_ne4; }
-    const bool ne16 = split && cs == 256 && iv.node_in <= 96 && !sw.no_tail16;  // 16-row blocks (rowblock.hip: mlp16_kernel)
-    if (ne16) { rb16 = 1; rb_l0 = D + L.ne16[0][1]; rb_l1 = D + L.ne16[1][1]; rb_l2 = D + L.ne16[2][1]; }
-    // skip_embed(init_node) of all blocks as a fourth layer of the same launch (the GEMM below is then skipped)
-    if (ne16 && d->num_blocks * d->c_skip == 256 && bf && iv.feat_dim >= 1024 && !sw.no_splitk && !sw.skip_per_block &&
-        op.kind == OP_ALL) {
-      rb_w3 = D + L.skip16[0]; rb_w3l = D + L.skip16[1]; rb_b3 = (const float*)(D + L.skip_b); rb_out2 = F(w.skip_all); rb_ld2 = d->num_blocks * d->c_skip;
-      skip_fused = true;
-    }
-    RC(rblock(split ? (L.kn_pad == 72 ? FD_RB_NODE_EMBED_72_SPLIT : FD_RB_NODE_EMBED_88_SPLIT)
-                    : (L.kn_pad == 72 ? FD_RB_NODE_EMBED_72 : FD_RB_NODE_EMBED_88), F(w.node_feat), L.kn_pad, ne16 ? D + L.ne16[0][0] : D + L.ch_ne0, P + iv.ne0.b,
-              ne16 ? D + L.ne16[1][0] : D + L.ch_ne2n, P + iv.ne2.b, ne16 ? D + L.ne16[2][0] : D + L.ch_ne4n, P + iv.ne4.b, nullptr, 0, &iv.neln, res_mask, F(w.node0), cs));
-  } else {
-    RC(fd_linear(prec, R, cs, L.kn_pad, F(w.node_feat), L.kn_pad, D + L.ne0_pad, L.kn_pad, P + iv.ne0.b, nullptr, 0, nullptr, 1,
-                 F(w.h_a), cs, st));
-    RC(lin(R, iv.ne2, F(w.h_a), cs, nullptr, 0, nullptr, 1, F(w.h_b), cs));
-    RC(lin(R, iv.ne4, F(w.h_b), cs, nullptr, 0, nullptr, 0, F(w.h_a), cs));
-    RC(fd_layernorm(R, cs, F(w.h_a), cs, nullptr, 0, P + iv.neln.g, P + iv.neln.b, res_mask, F(w.node0), cs, st));
-  }
-  if (!feats_fused) {
-    RC(fd_linear(FDIPT_PREC_F32, R, cz, L.d1_pad, F(w.pte), L.d1_pad, D + L.w1i, L.d1_pad, (const float*)(D + L.b1), nullptr, 0,
-                 nullptr, 0, F(w.pi), cz, st));
-    RC(fd_linear(FDIPT_PREC_F32, R, cz, L.d1_pad, F(w.pte), L.d1_pad, D + L.w1j, L.d1_pad, nullptr, nullptr, 0, nullptr, 0,
-                 F(w.pj), cz, st));
-  }
-  {
-    EdgeEmbedArgs ea;
-    ea.B = B; ea.N = N; ea.n_rel = a->n_rel; ea.rel_off = a->rel_off; ea.num_bins = d->num_bins;
-    ea.pi = F(w.pi); ea.pj = F(w.pj); ea.rtab = (const float*)setup; ea.dtab = (const float*)(D + L.dtab);
-    ea.edges = (const float*)(D + L.edges); ea.seq_idx = a->seq_idx; ea.sc_ca = a->sc_ca_t;
-    ea.w2 = WM(iv.ee2); ea.w3 = WM(iv.ee4); ea.b2 = P + iv.ee2.b; ea.b3 = P + iv.ee4.b;
-    ea.gamma = P + iv.eeln.g; ea.beta = P + iv.eeln.b; ea.res_mask = res_mask; ea.z_out = W + w.z;
-    ea.trace = a->trace_edge; ea.reserve_cus = a->reserve_cus;
-    // the first block's pair bias linear_b(z)/sqrt(3) from the embedder's LayerNorm epilogue (saves a pass over z)
-    const bool ee_bias = use_regpair(d) && bf && cz == 128 && C == 256 && Pq == 8 && Pv == 12 && H <= 8 && N <= 1024 &&
-                         !sw.generic_attn && !sw.no_et_bias && !sw.no_ee_bias;
-    ea.wb_img = ee_bias ? D + L.blk[0].wb_img4 : nullptr; ea.bb = (const float*)(D + L.blk[0].bb); ea.bias_out = F(w.bias); ea.H = H;
-    ee_bias_done = ee_bias;
-    if (ee_bias && pz_path) {
-      ea.wdz_img = D + L.blk[0].wdz_imgp; ea.wdz_img_lo = D + L.blk[0].wdz_imgp_lo; ea.bdz = P + iv.blk[0].dz.b; ea.pz_out = (half_t*)(W + w.pz);
-      pz_ready = true;
-    }
-    if (use_regpair(d)) RC(fd_edge_embed2(ea, D + L.ee2, st));
-    else RC(fd_edge_embed(prec, cz, ea, st));
-  }
-  return FDIPT_OK;
-  };
-  auto d2d = [&](void* dst, const void* src, size_t bytes) {
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess ? FDIPT_OK : FDIPT_ELAUNCH;
-  };
-  if (run_embed) RC(embed());
+  const ForwardPlan p = plan_forward(d, iv, L, B, N, op.kind);
+  const Fwd f = {d, iv, L, w, p, P, (const char*)derived, (char*)workspace, setup, a, (hipStream_t)stream, B, N, R, (N + 31) / 32 * 32, (size_t)R * N};
+  if (a->trace_inner && (p.rbk || p.outproj != OUT_GEMM)) return FDIPT_EINVAL;  // fused node path: the tensors never exist
+  const size_t node_bytes = (size_t)R * d->c_s * 4, z_bytes = f.NN * d->c_z * L.esz;
+  if (op.kind == OP_ALL || op.kind == OP_EMBED) RC(f.embed_stage());
   if (op.kind == OP_EMBED) {
-    if (op.node_out) RC(d2d(op.node_out, F(w.node0), (size_t)R * cs * 4));
-    if (op.z_out) RC(d2d(op.z_out, W + w.z, NN * cz * L.esz));
+    if (op.node_out) RC(f.d2d(op.node_out, f.F(w.node0), node_bytes));
+    if (op.z_out) RC(f.d2d(op.z_out, f.W + w.z, z_bytes));
     return FDIPT_OK;
   }
-  if (a->trace_node && run_embed)
-    if (hipMemcpyAsync(a->trace_node, F(w.node0), (size_t)R * cs * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return FDIPT_ELAUNCH;
-
-  // ---- IpaScore trunk (ipa_pytorch.py:509-551)
-  if (!feats_fused && a->rigids_t)
-    RC(fd_split_rigids(R, a->rigids_t, d->coordinate_scaling, res_mask, a->fixed_mask ? a->fixed_mask : res_mask, F(w.quat),
-                       F(w.trans), F(w.dmask), a->step_cursor, st));
-  const float* node_cur = F(w.node0);
-  if (op.kind != OP_ALL) {  // per-op entry: the sub-module's inputs come from the caller
+  if (a->trace_node && op.kind == OP_ALL) RC(f.d2d(a->trace_node, f.F(w.node0), node_bytes));
+  if (!p.feats_fused && a->rigids_t)
+    RC(fd_split_rigids(R, a->rigids_t, d->coordinate_scaling, a->res_mask, a->fixed_mask ? a->fixed_mask : a->res_mask, f.F(w.quat),
+                       f.F(w.trans), f.F(w.dmask), a->step_cursor, f.st));
+  if (op.kind != OP_ALL) {  // per-op entry: the sub-module's inputs come from the caller; one block, cut at the sub-module's boundary
     if (!op.node_in) return FDIPT_EINVAL;
-    RC(d2d(F(w.node), op.node_in, (size_t)R * cs * 4));
-    node_cur = F(w.node);
+    RC(f.d2d(f.F(w.node), op.node_in, node_bytes));
     if (op.kind != OP_POINTS) {
       if (!op.z_in) return FDIPT_EINVAL;
-      RC(d2d(W + w.z, op.z_in, NN * cz * L.esz));
+      RC(f.d2d(f.W + w.z, op.z_in, z_bytes));
     }
-  }
-  // skip_embed(init_node) of every block depends on the embedder output only: one GEMM launch for all blocks, copied behind the
-  // LayerNorm output by the LayerNorm kernel (FDIPT_KF_UNFOLDED: one launch per block)
-  const bool skip_batched = bf && iv.feat_dim >= 1024 && !sw.no_splitk && !sw.skip_per_block && op.kind == OP_ALL;
-  if (skip_batched && skip_fused) {
-  } else if (skip_batched && split && (cs & 7) == 0)
-    RC(fd_linear_splitk_split(R, d->num_blocks * d->c_skip, cs, 1, F(w.node0), cs, (const float*)(D + L.skip_w32), cs, (const float*)(D + L.skip_b),
-                              nullptr, F(w.skip_all), 0, d->num_blocks * d->c_skip, st));
-  else if (skip_batched)
-    RC(fd_linear(prec, R, d->num_blocks * d->c_skip, cs, F(w.node0), cs, D + L.skip_w, cs, (const float*)(D + L.skip_b), nullptr, 0,
-                 nullptr, 0, F(w.skip_all), d->num_blocks * d->c_skip, st));
-  bool seq_img_ready = false;  // layer-independent part of the sequence-attention images written (once per forward)
-  const bool seq_fused = rbk && !sw.generic_attn &&
-                         fd_seq_attention_supported(N, d->tfmr_heads, iv.d_t / d->tfmr_heads) &&
-                         fd_seq_qkv_supported(N, d->tfmr_heads, iv.d_t);
-  bool bias_ready = ee_bias_done;  // pair bias of this block's attention already written (tiled order) by the embedder / EdgeTransition
-  for (int b = 0; b < d->num_blocks; ++b) {
-    if (op.kind != OP_ALL && b != op.block) continue;
-    const BlockW& k = iv.blk[b];
-    const DBlock& db = L.blk[b];
-    const int PT = iv.proj_out - 3 * H * C;
-    bool etr_done = false;  // EdgeTransition's row launch folded into the transition launch of this block
-    // IPA + node path of the block (everything up to the frame update)
-    auto trunk = [&]() -> int {
-    Attn3Args a3 = a3_all;
-    a3.gamma = (const float*)(D + db.gamma);
-    OPairArgs oa = oa_all;
-    oa.wdz = (const float*)(D + db.wdz_t); oa.wdz_img = (bf && cz == 128) ? D + db.wdz_img : nullptr; oa.wdz_img_lo = (oa.wdz_img && split) ? D + db.wdz_img_lo : nullptr; oa.bdz = P + k.dz.b;
-    bool feats_h16 = false, skip_done = false, merged = false;
-    const bool use_a3 = ipa.a3;
-    PointsArgs pa;
-    pa.B = B; pa.N = N; pa.H = H; pa.Pq = Pq; pa.Pv = Pv; pa.quat = F(w.quat); pa.trans = F(w.trans);
-    pa.qp = F(w.qp); pa.kp = F(w.kp); pa.vp = F(w.vp); pa.rot = F(w.rot);
-    pa.vpt = (use_a3 && Pv == 12) ? (unsigned short*)(W + w.vpt) : nullptr; pa.Np = Np;
-    if (use_a3) { pa.kpf = (unsigned short*)(W + w.kpf); pa.gamma = (const float*)(D + db.gamma); pa.res_mask = res_mask; }
-    // padded keys and rows 72..95 of the value-point image are never written: zero once per forward (on the launch that zeroes
-    // the padded keys of Kb / Vt when the second-generation projection runs)
-    const size_t vpt_bytes = (size_t)B * H * 96 * Np * 2;
-    bool vpt_zero = pa.vpt && (b == 0 || op.kind != OP_ALL);
-    if (use_a3) {
-      // fused projection written directly as attention operand images (Qb, Kb, Vt) + raw point columns
-      ProjArgs pj;
-      pj.B = B; pj.N = N; pj.H = H; pj.C = C; pj.K = cs; pj.PT = PT; pj.Np = Np; pj.A = node_cur; pj.lda = cs;
-      pj.W = D + db.wproj; pj.bias = (const float*)(D + db.bproj); pj.qscale = sqrtf(1.0f / (3.0f * (float)C));
-      pj.Qb = (half_t*)(W + w.qb); pj.Kb = (half_t*)(W + w.kb); pj.Vt = (half_t*)(W + w.vt); pj.pts = F(w.pts);
-      pj.zero_pads = b == 0 || op.kind != OP_ALL;  // (per-op entry: the workspace is the caller's, pads unknown)
-      pj.W_img = cs == 256 ? D + db.wproj_img : nullptr;
-      pj.W_img_lo = (pj.W_img && split) ? D + db.wproj_img_lo : nullptr;
-      // Merged projections (the default of the split mode at the reference widths): no k, no v — the node rows are keys and values of
-      // every head (fd_node_images), q' = W_k^T (W_q s + b_q), W_v sits in the output projection (prepare: merge_qk / merge_vo).  40 % of
-      // the projection's columns, and K / V images an eighth of the size.  Exact algebra (softmax shift invariance, linearity); the
-      // per-op entries and FDIPT_KF_NO_MERGE keep the reference's formulation.
-      merged = pj.W_img_lo && split && cs == C && !sw.no_merge && op.kind == OP_ALL && fd_ipa_proj2_supported(pj);
-      if (merged) {
-        pj.merged = 1; pj.W_img = D + db.wproj2_img; pj.W_img_lo = D + db.wproj2_img_lo; pj.bias = (const float*)(D + db.bproj2);
-        a3.kv_per_sample = 1;
-        if (split) a3.Vt_lo = (const half_t*)(W + w.vt_lo);
-      }
-      // point epilogue (ipa_proj2.hip: p2_points_walk / p2_node_rows): the merged projection also writes the rotated points (qp, kpf, vpt,
-      // rot) and the node-row images; no point launch, no fp32 point columns.  This flag decides the projection's image, the pads and
-      // the launches dropped below
-      const bool proj_pts = merged && !sw.points_launch && pa.vpt && pa.kpf && fd_ipa_proj2_points_supported(pj, Pq, Pv);
-      if (proj_pts) {
-        pj.pts_img = 1; pj.W_img = D + db.wproj2p_img; pj.W_img_lo = D + db.wproj2p_img_lo; pj.bias = (const float*)(D + db.bproj2p);
-        pj.PT = fd_ipa_proj2_points_cols(H, C) - H * C; pj.Vt_lo = (half_t*)(W + w.vt_lo);
-        pj.quat = pa.quat; pj.trans = pa.trans; pj.gamma = pa.gamma; pj.res_mask = pa.res_mask; pj.rot = pa.rot; pj.qp = pa.qp;
-        pj.kpf = pa.kpf; pj.vpt = pa.vpt;
-      }
-      if (!merged && pj.W_img_lo && split && fd_ipa_proj2_supported(pj)) {  // P V on split operands needs V_lo, which only the split second-generation projection writes
-        pj.Vt_lo = (half_t*)(W + w.vt_lo); a3.Vt_lo = pj.Vt_lo;
-      }
-      // second generation (activation fragments in registers, weights by LDS-DMA) where it applies, else the tiled GEMM
-      if (fd_ipa_proj2_supported(pj)) {
-        if (pj.zero_pads && seq_fused && !seq_img_ready && (C & 31) == 0 && (vpt_bytes & 15) == 0 && !sw.init_unfused) {
-          // every once-per-forward fill of the trunk in one launch: sequence-attention images, value-point image, key pads
-          // (merged without the point epilogue: fd_node_images writes the padded keys of its images itself)
-          SeqInitExtra sx = {vpt_zero ? W + w.vpt : nullptr, vpt_zero ? (long)(vpt_bytes >> 4) : 0L, (Np > N && (!merged || proj_pts)) ? (void*)pj.Kb : nullptr,
-                             (void*)pj.Vt, (long)B * H, C, (void*)pj.Vt_lo};
-          RC(fd_seq_images_init(B, N, d->tfmr_heads, res_mask, W + w.seqimg, sx, st));
-          seq_img_ready = true;
-          vpt_zero = false;
-        } else if (pj.zero_pads && ((Np > N && (!merged || proj_pts)) || vpt_zero)) {
-          ProjArgs pz = pj; pz.W_img = nullptr;
-          if (merged && !proj_pts) pz.Np = pz.N;  // (no key pads to zero)
-          RC(fd_ipa_proj_zero_pads(pz, vpt_zero ? W + w.vpt : nullptr, vpt_zero ? vpt_bytes : 0, st));
-          vpt_zero = false;
-        }
-        RC(fd_ipa_proj2(pj, st));
-        // (the node-row images ride on the point launch when that is the 16-keys-per-block kernel; else their own launch)
-        if (merged && !proj_pts) {
-          if (pa.vpt && Pv == 12 && (H & 1) == 0 && cs == 256) {
-            pa.node = node_cur; pa.ld_node = cs; pa.nKb = pj.Kb; pa.nVt = pj.Vt; pa.nVt_lo = split ? (half_t*)(W + w.vt_lo) : nullptr;
-          } else RC(fd_node_images(B, N, Np, node_cur, cs, pj.Kb, pj.Vt, split ? (half_t*)(W + w.vt_lo) : nullptr, st));
-        }
-      } else RC(fd_ipa_proj(pj, st));
-      if (vpt_zero && hipMemsetAsync(W + w.vpt, 0, vpt_bytes, st) != hipSuccess) return FDIPT_ELAUNCH;
-      pa.proj = F(w.pts); pa.ld = PT; pa.q_off = 0; pa.kv_off = 3 * H * Pq;
-      if (!proj_pts) RC(fd_points(pa, st));
-      if (op.kind == OP_POINTS) return FD_STOP;
-      if (!bias_ready)  // blocks >= 1: already emitted by the previous block's EdgeTransition epilogue
-        RC(fd_pair_bias2(B, N, H, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), 1, st));
-      // the attention weights go to the MFMA o_pair kernel as bf16 rows [b, i, h, Np] (half the bytes, no conversion pass;
-      // the fp32 buffer is reused: B N H Np bf16 <= B H N N fp32)
-      // ... and both kernels write the attention features as bf16 rows when the output projection is the bf16 split-K GEMM
-      // (the values it would round them to anyway: identical results, half the bytes, no conversion in its staging)
-      feats_h16 = fd_opair_mfma_eligible(prec, oa) && iv.feat_dim >= 1024 && (iv.feat_dim & 7) == 0 && !sw.no_splitk &&
-                   !split && op.kind == OP_ALL;  // (split operands: the projection splits the fp32 features itself)
-      if (feats_h16) { a3.out_h16 = (half_t*)(W + w.feats); oa.out_h16 = a3.out_h16; }
-      if (ipa.probs_h16) {
-        a3.probs_h16 = (half_t*)(W + w.probs); oa.probs_h16 = a3.probs_h16; oa.probs_np = Np;
-      }
-      RC(fd_attention3(a3, st));
-    } else {
-      // fused q | kv | q_pts | kv_pts projection (fp32 activations), then the LDS / register attention kernels
-      RC(fd_linear(prec, R, iv.proj_out, cs, node_cur, cs, D + db.wproj, cs, (const float*)(D + db.bproj), nullptr, 0,
-                   nullptr, 0, F(w.proj), iv.proj_out, st));
-      pa.proj = F(w.proj); pa.ld = iv.proj_out; pa.q_off = 3 * H * C; pa.kv_off = 3 * H * C + 3 * H * Pq;
-      RC(fd_points(pa, st));
-      if (op.kind == OP_POINTS) return FD_STOP;
-      AttnArgs aa;
-      aa.B = B; aa.N = N; aa.H = H;
-      aa.q = F(w.proj); aa.q_ld = iv.proj_out; aa.q_hs = C;
-      aa.k = F(w.proj) + H * C; aa.k_ld = iv.proj_out; aa.k_hs = 2 * C;
-      aa.v = F(w.proj) + H * C + C; aa.v_ld = iv.proj_out; aa.v_hs = 2 * C;
-      aa.C = C; aa.Dv = C; aa.scale = sqrtf(1.0f / (3.0f * (float)C));
-      aa.bias = F(w.bias); aa.res_mask = res_mask; aa.qp = F(w.qp); aa.kp = F(w.kp); aa.vp = F(w.vp); aa.Pq = Pq; aa.Pv = Pv;
-      aa.gamma = (const float*)(D + db.gamma); aa.rot = F(w.rot); aa.trans = F(w.trans); aa.probs = F(w.probs);
-      aa.out = F(w.feats); aa.out_ld = iv.feat_dim; aa.pt_off = H * C; aa.lds_s = 0;
-      if (prec == FDIPT_PREC_F32 && H == 8 && cz == 128)
-        RC(fd_pair_bias_f32((long)NN, H, cz, F(w.z), (const float*)(D + db.wb), (const float*)(D + db.bb), F(w.bias), st));  // [B,N,N,H]
-      else
-        RC(fd_linear_z(prec, (long)NN, H, cz, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), st));  // [B,N,N,H]
-      if (prec == FDIPT_PREC_F32 && !sw.generic_attn && fd_ipa_attention_f32_supported(aa)) RC(fd_ipa_attention_f32(aa, st));  // scores in registers (round 5)
-      else RC(fd_attention(prec, 1, aa, st));
-    }
-    if (pz_ready) {  // (emitted only for this path: pz_path; z itself may not have been stored)
-      if (!oa.probs_h16) return FDIPT_EINVAL;
-      oa.pz = (const half_t*)(W + w.pz);
-      RC(fd_opair_pz(oa, st));
-    } else RC(fd_opair(prec, oa, st));
-    // node = LN(node + ipa) lives in tf_in[:, :cs]; tf_in[:, cs:] = skip_embed(init_node)   (ipa:531-535)
-    if (op.kind == OP_IPA) {  // per-op entry: linear_out(features) * mask as one GEMM (the forward sums split-K slices in its LayerNorm)
-      RC(lin(R, k.out, F(w.feats), iv.feat_dim, nullptr, 0, res_mask, 0, F(w.ipa_out), cs));
-      return FD_STOP;
-    }
-    if (bf && iv.feat_dim >= 1024 && !sw.no_splitk) {
-      // K = 2688 in slices: 4x the blocks, a quarter of the dependent k-iterations (7 slices: slower).  Split operands: 3 slices
-      // (70 KB of LDS per block = two blocks per CU: at B N = 2400 rows 456 blocks run in one round of the 256 CUs, 30 us;
-      // 4 slices = 608 blocks need two rounds, 41 us).  The slice count must not depend on the batch size: the order of the
-      // partial sums is part of a sample's result (sub-batches and sharded runs reproduce the whole-batch result bit for bit)
-      const bool op_ded = split && merged && fd_outproj_split_supported(cs, iv.feat_dim);
-      const int NS = op_ded ? fd_outproj_split_slices() : split ? 3 : 4;
-      if (op_ded)
-        RC(fd_outproj_split(R, cs, iv.feat_dim, F(w.feats), iv.feat_dim, D + db.wout_img, D + db.wout_img_lo, (const float*)(D + db.bout_m),
-                                         res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
-      else if (split)
-        RC(fd_linear_splitk_split(R, cs, iv.feat_dim, NS, F(w.feats), iv.feat_dim, merged ? (const float*)(D + db.wout_m) : P + k.out.w,
-                                               iv.feat_dim, merged ? (const float*)(D + db.bout_m) : P + k.out.b, res_mask, F(w.ipa_parts),
-                                               (long)R * cs, cs, st));
-      else if (feats_h16)
-        RC(fd_linear_splitk_a16(R, cs, iv.feat_dim, NS, (const half_t*)(W + w.feats), iv.feat_dim, WM(k.out), iv.feat_dim, P + k.out.b,
-                                res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
-      else
-        RC(fd_linear_splitk(R, cs, iv.feat_dim, NS, F(w.feats), iv.feat_dim, WM(k.out), iv.feat_dim, P + k.out.b, res_mask,
-                            F(w.ipa_parts), (long)R * cs, cs, st));
-      // (round 3: the lo images are touched as well — a cold image is one exposed memory round trip per weight tile of the consumer)
-      const L2Warm warm_qkv0 = {{D + db.ch.inp[0], split ? D + db.lo.inp[0] : nullptr, nullptr},
-                                {(unsigned)fd_chain_image_bytes(3 * dt, dt), split ? (unsigned)fd_chain_image_bytes(3 * dt, dt) : 0u, 0}};
-      RC(fd_layernorm_parts(R, cs, node_cur, cs, F(w.ipa_parts), cs, NS, (long)R * cs, P + k.ipa_ln.g, P + k.ipa_ln.b, nullptr,
-                            F(w.tf_in), dt, skip_batched ? F(w.skip_all) + (size_t)b * d->c_skip : nullptr,
-                            d->num_blocks * d->c_skip, d->c_skip, seq_fused ? &warm_qkv0 : nullptr, st));
-      skip_done = skip_batched;
-    } else {
-      RC(lin(R, k.out, F(w.feats), iv.feat_dim, nullptr, 0, res_mask, 0, F(w.ipa_out), cs));
-      RC(fd_layernorm(R, cs, node_cur, cs, F(w.ipa_out), cs, P + k.ipa_ln.g, P + k.ipa_ln.b, nullptr, F(w.tf_in), dt, st));
-      RC(inner(b, 0, F(w.ipa_out), cs, cs));
-      RC(inner(b, 1, F(w.tf_in), dt, cs));
-    }
-    if (skip_done) {
-    } else RC(lin(R, k.skip, F(w.node0), cs, nullptr, 0, nullptr, 0, F(w.tf_in) + cs, dt));
-    // nn.TransformerEncoder, post-norm (ipa:433-443,536-538)
-    const float* x = F(w.tf_in);
-    bool post_done = false;
-    for (int l = 0; l < d->tfmr_layers; ++l) {
-      const TfLayer& t = k.tf[l];
-      const int hd0 = dt / d->tfmr_heads;
-      // default bf16 path: in_proj writes the attention operand images directly (attention_seq.hip)
-      const bool qkv_fused = seq_fused;
-      if (qkv_fused) {
-        if (!seq_img_ready) {
-          RC(fd_seq_images_init(B, N, d->tfmr_heads, res_mask, W + w.seqimg, SeqInitExtra{}, st));
-          seq_img_ready = true;
-        }
-        RC(fd_seq_qkv(B, N, d->tfmr_heads, x, dt, D + db.ch.inp[l], split ? D + db.lo.inp[l] : nullptr, P + t.inp.b, 1.0f / sqrtf((float)hd0), W + w.seqimg, st));
-        // ... and touches the weights of the layer's tail kernel, launched next (common.hpp: L2 warm-up hand-over)
-        const unsigned wimg = (unsigned)fd_chain_image_bytes(dt, dt);
-        L2Warm wt = {{D + db.ch.outp[l], D + db.ch.l1[l], D + db.ch.l2n[l]}, {wimg, wimg, wimg}};
-        if (split && tail16_shapes(d, iv) && !sw.no_tail16)  // 16-row tail: its three hi images and its three lo images (each run contiguous)
-        {
-          const unsigned run = 3 * wimg + (l + 1 == d->tfmr_layers ? (unsigned)fd_chain_image_bytes(cs, dt) : 0u);  // (the last layer's run ends with post_tfmr)
-          wt = L2Warm{{D + db.lo.o16[l][0], D + db.lo.o16[l][1], nullptr}, {run, run, 0}};
-        }
-        RC(fd_seq_attention_run(B, N, d->tfmr_heads, W + w.seqimg, F(w.att), dt, &wt, st));
-      } else {
-      RC(lin(R, t.inp, x, dt, nullptr, 0, nullptr, 0, F(w.qkv), 3 * dt));
-      AttnArgs ta;
-      const int hd = dt / d->tfmr_heads;
-      ta.B = B; ta.N = N; ta.H = d->tfmr_heads;
-      ta.q = F(w.qkv); ta.k = F(w.qkv) + dt; ta.v = F(w.qkv) + 2 * dt;
-      ta.q_ld = ta.k_ld = ta.v_ld = 3 * dt; ta.q_hs = ta.k_hs = ta.v_hs = hd;
-      ta.C = hd; ta.Dv = hd; ta.scale = 1.0f / sqrtf((float)hd); ta.bias = nullptr; ta.res_mask = res_mask;
-      ta.qp = ta.kp = ta.vp = nullptr; ta.Pq = ta.Pv = 0; ta.gamma = nullptr; ta.rot = ta.trans = nullptr; ta.probs = nullptr;
-      ta.out = F(w.att); ta.out_ld = dt; ta.pt_off = 0; ta.lds_s = 0;
-      if (bf && !sw.generic_attn && fd_seq_attention_supported(N, d->tfmr_heads, hd))
-        RC(fd_seq_attention(B, N, d->tfmr_heads, F(w.qkv), 3 * dt, ta.scale, res_mask, W + w.seqimg, F(w.att), dt, st));
-      else if (prec == FDIPT_PREC_F32 && !sw.generic_attn && fd_seq_attention_f32_supported(N, d->tfmr_heads, hd, 3 * dt))
-        RC(fd_seq_attention_f32(B, N, d->tfmr_heads, F(w.qkv), 3 * dt, ta.scale, res_mask, F(w.att), dt, st));  // fp32 mode: scores in registers (round 5)
-      else RC(fd_attention(prec, 0, ta, st));
-      }
-      // x_a = norm1(x + out_proj(att)); x_b = norm2(x_a + linear2(relu(linear1(x_a))))
-      if (rbk) {
-        TfmrTailArgs tt;
-        tt.M = R; tt.ld = dt; tt.att = F(w.att); tt.x = x; tt.wo = D + db.ch.outp[l]; tt.w1 = D + db.ch.l1[l]; tt.w2 = D + db.ch.l2n[l];
-        tt.bo = P + t.outp.b; tt.g1 = P + t.n1.g; tt.be1 = P + t.n1.b; tt.b1 = P + t.l1.b; tt.b2 = P + t.l2.b; tt.g2 = P + t.n2.g;
-        tt.be2 = P + t.n2.b; tt.out = x == F(w.x_b) ? F(w.x_a) : F(w.x_b);
-        if (split) { tt.wol = D + db.lo.outp[l]; tt.w1l = D + db.lo.l1[l]; tt.w2l = D + db.lo.l2[l]; }
-        const bool t16 = split && tail16_shapes(d, iv) && !sw.no_tail16;  // 16-row blocks (150 blocks at 2400 rows)
-        if (t16) { tt.rows16 = 1; tt.wo = D + db.lo.o16[l][0]; tt.wol = D + db.lo.o16[l][1]; tt.w1 = D + db.lo.f16[l][0]; tt.w1l = D + db.lo.f16[l][1]; tt.w2 = D + db.lo.g16[l][0]; tt.w2l = D + db.lo.g16[l][1]; }
-        tt.warm = L2Warm{};  // next launch: the following layer's in_proj, or post_tfmr / the transition
-        // the last layer also applies post_tfmr + the node residual (FDIPT_KF_UNFOLDED: its own launch)
-        const bool post_here = l + 1 == d->tfmr_layers && cs == 256 && !sw.post_unfused;
-        if (post_here) {
-          tt.wp = t16 ? D + db.lo.p16[0] : D + db.ch.post; tt.wpl = t16 ? D + db.lo.p16[1] : split ? D + db.lo.post : nullptr; tt.bp = P + k.post.b; tt.pres = F(w.tf_in); tt.ld_pres = dt; tt.pout = F(w.h_a); tt.ld_pout = cs;
-          post_done = true;
-        }
-        const unsigned tb = (unsigned)fd_chain_image_bytes(cs, cs);
-        if (l + 1 < d->tfmr_layers && seq_fused) {
-          tt.warm.p[0] = D + db.ch.inp[l + 1]; tt.warm.bytes[0] = (unsigned)fd_chain_image_bytes(3 * dt, dt);
-          if (split) { tt.warm.p[1] = D + db.lo.inp[l + 1]; tt.warm.bytes[1] = tt.warm.bytes[0]; }
-        } else if (post_here && split && tail16_shapes(d, iv) && !sw.no_tail16)
-          tt.warm = L2Warm{{D + db.lo.tr16[0][0], D + db.lo.tr16[0][1], nullptr}, {3 * tb, 3 * tb, 0}};  // (the 16-row images: hi run, lo run)
-        else if (post_here && split) tt.warm = L2Warm{{D + db.ch.t1, D + db.ch.t2n, D + db.lo.t1}, {tb, 2 * tb, 3 * tb}};  // (t2n | t3n and lo t1 | t2 | t3 are contiguous)
-        else if (post_here) tt.warm = L2Warm{{D + db.ch.t1, D + db.ch.t2n, D + db.ch.t3n}, {tb, tb, tb}};
-        else if (l + 1 == d->tfmr_layers) { tt.warm.p[0] = D + db.ch.post; tt.warm.bytes[0] = (unsigned)fd_chain_image_bytes(cs, dt); }
-        RC(fd_tfmr_tail(tt, st));
-        x = tt.out;
-        continue;
-      }
-      RC(lin(R, t.outp, F(w.att), dt, nullptr, 0, nullptr, 0, F(w.ff), dt));
-      RC(fd_layernorm(R, dt, x, dt, F(w.ff), dt, P + t.n1.g, P + t.n1.b, nullptr, F(w.x_a), dt, st));
-      RC(lin(R, t.l1, F(w.x_a), dt, nullptr, 0, nullptr, 1, F(w.ff), dt));
-      RC(lin(R, t.l2, F(w.ff), dt, nullptr, 0, nullptr, 0, F(w.att), dt));
-      RC(fd_layernorm(R, dt, F(w.x_a), dt, F(w.att), dt, P + t.n2.g, P + t.n2.b, nullptr, F(w.x_b), dt, st));
-      x = F(w.x_b);  // next layer: norm1 reads x_b -> x_a, norm2 reads x_a/att -> x_b (no aliasing)
-    }
-    RC(inner(b, 2, x, dt, dt));
-    // node = node + post_tfmr(x); StructureModuleTransition; mask   (ipa:539-541, 36-58)
-    if (post_done) {
-    } else if (chn_all) {
-      const unsigned tb = (unsigned)fd_chain_image_bytes(cs, cs);
-      if (rbk) chain_warm = L2Warm{{D + db.ch.t1, D + db.ch.t2n, D + db.ch.t3n}, {tb, tb, tb}};
-      RC(chain(FD_CHAIN_POST, x, dt, D + db.ch.post, P + k.post.b, nullptr, nullptr, nullptr, nullptr, F(w.tf_in), dt, nullptr,
-               nullptr, nullptr, F(w.h_a), cs));
-    } else {
-      RC(lin(R, k.post, x, dt, F(w.tf_in), dt, nullptr, 0, F(w.h_a), cs));
-    }
-    bool bb_done = false;
-    if (rbk) {
-      // ... with BackboneUpdate + compose_q_update_vec fused in (the fp32 Linear c_s -> 6 is a per-row dot product)
-      RowBlockArgs r;
-      r.M = R; r.in = F(w.h_a); r.ld_in = cs; r.w0 = D + db.ch.t1; r.w1 = D + db.ch.t2n; r.w2 = D + db.ch.t3n; r.b0 = P + k.t1.b;
-      r.b1 = P + k.t2.b; r.b2 = P + k.t3.b; r.residual = F(w.h_a); r.ld_res = cs; r.gamma = P + k.tln.g; r.beta = P + k.tln.b;
-      r.rowmask_post = res_mask; r.out = F(w.node); r.ld_out = cs; r.bb_w = P + k.bb.w; r.bb_b = P + k.bb.b;
-      r.upd_mask = F(w.dmask); r.quat = F(w.quat); r.trans = F(w.trans); r.out2 = nullptr; r.ld_out2 = r.split = 0;
-      r.hid_h16 = nullptr;
-      if (b < d->num_blocks - 1 && iv.cb == 128 && iv.hid == 384 && cz == 128)  // next: the EdgeTransition row launch
-        r.warm = L2Warm{{D + db.ch.et_init, D + db.ch.r4w, split ? D + db.lo.et_init : nullptr},  // (lo et_init | r4w are contiguous)
-                        {(unsigned)fd_chain_image_bytes(iv.cb, cs), (unsigned)fd_chain_image_bytes(2 * (iv.hid + cz), iv.cb),
-                         split ? (unsigned)(fd_chain_image_bytes(iv.cb, cs) + fd_chain_image_bytes(2 * (iv.hid + cz), iv.cb)) : 0u}};
-      else if (b == d->num_blocks - 1)  // ... or the torsion head
-        r.warm = split && cs == 256 && iv.node_in <= 96 && !sw.no_tail16
-            ? L2Warm{{D + L.tor16[0][0], D + L.tor16[0][1], nullptr}, {2 * (unsigned)fd_chain_image_bytes(cs, cs), 2 * (unsigned)fd_chain_image_bytes(cs, cs), 0}}  // (hi run, lo run)
-            : L2Warm{{D + L.ch_tor1, D + L.ch_tor2n, split ? D + L.lo_tor1 : nullptr},  // (lo tor1 | tor2 are contiguous)
-                        {(unsigned)fd_chain_image_bytes(cs, cs), (unsigned)fd_chain_image_bytes(cs, cs), split ? 2 * (unsigned)fd_chain_image_bytes(cs, cs) : 0u}};
-      if (split) { r.w0l = D + db.lo.t1; r.w1l = D + db.lo.t2; r.w2l = D + db.lo.t3; }
-      if (split && tail16_shapes(d, iv) && !sw.no_tail16) {  // 16-row blocks (rowblock.hip: transition16_kernel)
-        r.w0 = D + db.lo.tr16[0][0]; r.w1 = D + db.lo.tr16[1][0]; r.w2 = D + db.lo.tr16[2][0];
-        r.w0l = D + db.lo.tr16[0][1]; r.w1l = D + db.lo.tr16[1][1]; r.w2l = D + db.lo.tr16[2][1];
-        // EdgeTransition's row launch (e = initial_embed(node), fold columns -> edge_transition4's images) folded into this launch: the
-        // rows it needs are this launch's output rows (same conditions as the `use_et4` row launch below, which is then skipped)
-        if (op.kind == OP_ALL && b < d->num_blocks - 1 && iv.cb == 128 && iv.hid == 384 && cz == 128 && use_regpair(d) && !sw.et3 &&
-            fd_edge_transition4_supported(N) && split && !sw.et4_rows_unfused) {
-          r.we0 = D + db.lo.ei16[0]; r.we0l = D + db.lo.ei16[1]; r.we1 = D + db.lo.r416[0]; r.we1l = D + db.lo.r416[1];
-          r.be0 = P + k.et_init.b; r.be1 = (const float*)(D + db.ch.r4b);
-          r.img_a = W + w.a1img; r.img_b = W + w.b1img; r.img_B = B; r.img_N = N;
-          // its own later-stage images (hi run, lo run) instead of the row launch's
-          const unsigned run = (unsigned)(fd_chain_image_bytes(iv.cb, cs) + fd_chain_image_bytes(2 * (iv.hid + cz), iv.cb));
-          r.warm = L2Warm{{D + db.lo.ei16[0], D + db.lo.ei16[1], nullptr}, {run, run, 0}};
-          etr_done = true;
-        }
-        RC(fd_transition16(r, st));
-      } else
-      RC(fd_rowblock(split ? FD_RB_TRANSITION_BB_SPLIT : FD_RB_TRANSITION_BB, r, st));
-      bb_done = true;
-    } else {
-      RC(lin(R, k.t1, F(w.h_a), cs, nullptr, 0, nullptr, 1, F(w.h_b), cs));
-      RC(lin(R, k.t2, F(w.h_b), cs, nullptr, 0, nullptr, 1, F(w.ipa_out), cs));
-      RC(lin(R, k.t3, F(w.ipa_out), cs, F(w.h_a), cs, nullptr, 0, F(w.h_b), cs));
-      RC(fd_layernorm(R, cs, F(w.h_b), cs, nullptr, 0, P + k.tln.g, P + k.tln.b, res_mask, F(w.node), cs, st));
-    }
-    node_cur = F(w.node);
-    // BackboneUpdate + compose_q_update_vec (ipa:542-547).  bb_update(node*diffuse_mask) differs from bb_update(node)
-    // only on rows whose update is masked out below, so the input mask is not materialised.
-    if (!bb_done) {
-      RC(lin32(R, k.bb, node_cur, cs, F(w.upd), 8));
-      RC(inner(b, 3, F(w.upd), 8, 6));
-      RC(fd_compose_q_update(R, F(w.quat), F(w.trans), F(w.upd), 8, F(w.dmask), st));
-    }
-    return FDIPT_OK;
-    };  // trunk
-    if (op.kind != OP_ET) {
-      const int rc_t = trunk();
-      if (rc_t == FD_STOP) {
-        if (op.kind == OP_POINTS) {
-          if (!op.qp || !op.kp || !op.vp) return FDIPT_EINVAL;
-          RC(d2d(op.qp, F(w.qp), (size_t)R * H * Pq * 3 * 4));
-          RC(d2d(op.kp, F(w.kp), (size_t)R * H * Pq * 3 * 4));
-          RC(d2d(op.vp, F(w.vp), (size_t)R * H * Pv * 3 * 4));
-        } else {
-          if (!op.out) return FDIPT_EINVAL;
-          RC(d2d(op.out, F(w.ipa_out), (size_t)R * cs * 4));
-        }
-        return FDIPT_OK;
-      }
-      if (rc_t) return rc_t;
-    }
-    if (b < d->num_blocks - 1) {
-      // register-resident pair kernels (reference widths): e = initial_embed(node) and the per-residue rows of the concat-free
-      // layers come out of ONE row-block launch.  edge_transition4 (8 x 4-pair patches, N % 4 == 0) gets [A1 | Af | B1 | Bf] as
-      // its fold-fragment images; edge_transition3 (16-pair waves: any N >= 43) gets A1 | Af rows and e in half precision.
-      // Anything else (N < 43 with N % 4 != 0, other widths) runs the LDS-chain kernel of pair_mlp.hip.
-      const bool reg_ok = rbk && iv.cb == 128 && iv.hid == 384 && cz == 128 && use_regpair(d);
-      const bool use_et4 = reg_ok && !sw.et3 && fd_edge_transition4_supported(N);
-      const bool use_et3 = reg_ok && !use_et4 && fd_edge_transition3_supported(N);
-      if (use_et4 && etr_done) {
-        // (the fold-fragment images were written by the transition launch)
-      } else if (use_et4) {
-        RowBlockArgs r;
-        r.M = R; r.in = node_cur; r.ld_in = cs; r.w0 = D + db.ch.et_init; r.b0 = P + k.et_init.b; r.w1 = D + db.ch.r4w;
-        r.b1 = (const float*)(D + db.ch.r4b); r.w2 = nullptr; r.b2 = nullptr; r.residual = nullptr; r.ld_res = 0; r.gamma = r.beta = nullptr;
-        r.rowmask_post = nullptr; r.out = F(w.r4); r.ld_out = 1024; r.out2 = nullptr; r.ld_out2 = 0; r.split = 0;
-        r.hid_h16 = nullptr; r.bb_w = r.bb_b = r.upd_mask = nullptr; r.quat = r.trans = nullptr;
-        r.img_a = W + w.a1img; r.img_b = W + w.b1img; r.img_B = B; r.img_N = N;
-        if (split && !sw.et4_rows_unfused) { r.w0l = D + db.lo.et_init; r.w1l = D + db.lo.r4w; }
-        if (!sw.et4_rows_unfused) {  // the row-block epilogue writes the fold-fragment images itself
-          RC(fd_rowblock(FD_RB_ET4_IMAGES, r, st));
-        } else {
-          RC(fd_rowblock(FD_RB_ET4_ROWS, r, st));
-          RC(fd_et4_row_images(F(w.r4), B, N, W + w.a1img, W + w.b1img, st));
-        }
-      } else if (use_et3) {
-        RowBlockArgs r;
-        r.M = R; r.in = node_cur; r.ld_in = cs; r.w0 = D + db.ch.et_init; r.b0 = P + k.et_init.b; r.w1 = D + db.ch.a1af;
-        r.b1 = (const float*)(D + db.ch.b1f); r.w2 = nullptr; r.b2 = nullptr; r.residual = nullptr; r.ld_res = 0; r.gamma = r.beta = nullptr;
-        r.rowmask_post = nullptr; r.out = F(w.a1); r.ld_out = iv.hid; r.out2 = F(w.af); r.ld_out2 = cz; r.split = iv.hid;
-        r.hid_h16 = (unsigned short*)(W + w.e_bf); r.bb_w = r.bb_b = r.upd_mask = nullptr; r.quat = r.trans = nullptr;
-        RC(fd_rowblock(FD_RB_ET_ROWS, r, st));
-      } else if (chn_all) {
-        chain_h16 = (unsigned short*)(W + w.e_bf);
-        RC(chain(FD_CHAIN_ETINIT, node_cur, cs, D + db.ch.et_init, P + k.et_init.b, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                 nullptr, nullptr, nullptr, F(w.e), iv.cb));
-      } else {
-        RC(lin(R, k.et_init, node_cur, cs, nullptr, 0, nullptr, 0, F(w.e), iv.cb));
-        if (bf) RC(fd_f32_to_half((long)R * iv.cb, F(w.e), (half_t*)(W + w.e_bf), st));
-      }
-      float* tr_ptr = a->trace_edge ? a->trace_edge + (size_t)(b + 1) * NN * cz : nullptr;
-      bias_ready = false;
-      pz_ready = false;
-      if (use_et4 || use_et3) {
-        ET2Args t2;
-        t2.B = B; t2.N = N; t2.z_in = (const half_t*)(W + w.z); t2.z_out = (half_t*)(W + w.z); t2.e = F(w.e);
-        t2.e_h16 = (const half_t*)(W + w.e_bf);
-        t2.a1 = F(w.a1); t2.af = F(w.af); t2.stream = use_et4 ? D + db.et4 : D + db.et3; t2.b2 = P + k.et2.b; t2.gamma = P + k.et_ln.g;
-        t2.beta = P + k.et_ln.b; t2.res_mask = res_mask; t2.trace = tr_ptr;
-        // the next block's attention consumes linear_b(z') in fragment order when it runs attention3
-        // (end to end +0.8 % at N = 300: the launch grows by about as much as the pair_bias2 launch it replaces, the gain
-        //  is the z re-read that disappears; FDIPT_KF_UNFOLDED restores the separate pass)
-        const bool emit_bias = cz == 128 && C == 256 && Pq == 8 && Pv == 12 && H <= 8 && !sw.generic_attn && !sw.no_et_bias && N <= 1024;
-        t2.wb_img = emit_bias ? D + (use_et4 ? L.blk[b + 1].wb_img4 : L.blk[b + 1].wb_img3) : nullptr;
-        t2.a1_img = W + w.a1img; t2.b1_img = W + w.b1img;
-        t2.bb = (const float*)(D + L.blk[b + 1].bb); t2.bias_out = F(w.bias); t2.H = H; t2.reserve_cus = a->reserve_cus;
-        bias_ready = emit_bias;
-        pz_ready = false;
-        if (use_et4 && emit_bias && pz_path) {
-          t2.bdz = P + iv.blk[b + 1].dz.b; t2.pz_out = (half_t*)(W + w.pz);  // (down_z itself: the last chunk of the weight stream)
-          pz_ready = true;
-          // the last EdgeTransition of the trunk: block b + 1 takes bias and pair_z from this epilogue and no launch reads z' itself
-          if (b + 1 == d->num_blocks - 1 && !tr_ptr) t2.z_out = nullptr;
-        }
-        t2.clock = a->clock_out;
-        if (a->ev_start && a->ev_start[b]) hipEventRecord((hipEvent_t)a->ev_start[b], st);
-        if (use_et4) RC(fd_edge_transition4(t2, st));
-        else RC(fd_edge_transition3(t2, st));
-        if (a->ev_stop && a->ev_stop[b]) hipEventRecord((hipEvent_t)a->ev_stop[b], st);
-      } else {
-      EdgeTransArgs ta;
-      ta.B = B; ta.N = N; ta.z_in = W + w.z; ta.z_out = W + w.z; ta.e = F(w.e);
-      ta.w1 = WM(k.et1); ta.w2 = WM(k.et2); ta.wf = WM(k.etf); ta.b1 = P + k.et1.b; ta.b2 = P + k.et2.b; ta.bf = P + k.etf.b;
-      ta.gamma = P + k.et_ln.g; ta.beta = P + k.et_ln.b; ta.res_mask = res_mask;
-      ta.trace = tr_ptr;
-      ta.clock = a->clock_out;
-      if (a->ev_start && a->ev_start[b]) hipEventRecord((hipEvent_t)a->ev_start[b], st);
-      RC(fd_edge_transition(prec, cz, iv.cb, ta, st));
-      if (a->ev_stop && a->ev_stop[b]) hipEventRecord((hipEvent_t)a->ev_stop[b], st);
-      }
-    }
+    const int b = op.block;
     if (op.kind == OP_ET) {
+      RC(f.edge_transition_stage(b, f.F(w.node)));
       if (!op.z_out) return FDIPT_EINVAL;
-      RC(d2d(op.z_out, W + w.z, NN * cz * L.esz));
-      return FDIPT_OK;
+      return f.d2d(op.z_out, f.W + w.z, z_bytes);
     }
-    if (a->trace_node)
-      if (hipMemcpyAsync(a->trace_node + (size_t)(b + 1) * R * cs, node_cur, (size_t)R * cs * 4, hipMemcpyDeviceToDevice,
-                         st) != hipSuccess)
-        return FDIPT_ELAUNCH;
+    RC(f.ipa_project(b, f.F(w.node)));
+    if (op.kind == OP_POINTS) {
+      if (!op.qp || !op.kp || !op.vp) return FDIPT_EINVAL;
+      const size_t qk = (size_t)R * d->no_heads * d->no_qk_points * 3 * 4;
+      RC(f.d2d(op.qp, f.F(w.qp), qk));
+      RC(f.d2d(op.kp, f.F(w.kp), qk));
+      return f.d2d(op.vp, f.F(w.vp), (size_t)R * d->no_heads * d->no_v_points * 3 * 4);
+    }
+    RC(f.ipa_attend(b));
+    // linear_out(features) * mask as one GEMM (the forward sums split-K slices in its LayerNorm)
+    RC(f.lin(iv.blk[b].out, f.F(w.feats), iv.feat_dim, nullptr, 0, a->res_mask, 0, f.F(w.ipa_out), d->c_s));
+    if (!op.out) return FDIPT_EINVAL;
+    return f.d2d(op.out, f.F(w.ipa_out), node_bytes);
   }
-  if (op.kind != OP_ALL) return FDIPT_EINVAL;  // (unreachable: every per-op selection returns inside the loop)
-  // ---- heads: torsion (ipa:332-363), tensor_7, scores (ipa:552-564), backbone (sn:269-273)
-  if (rbk) {
-    if (split) { rb_l0 = D + L.lo_tor1; rb_l1 = D + L.lo_tor2; }
-    const bool tor16 = split && cs == 256 && iv.node_in <= 96 && !sw.no_tail16;
-    if (tor16) { rb16 = 2; rb_l0 = D + L.tor16[0][1]; rb_l1 = D + L.tor16[1][1]; }
-    RC(rblock(split ? FD_RB_TORSION_SPLIT : FD_RB_TORSION, node_cur, cs, tor16 ? D + L.tor16[0][0] : D + L.ch_tor1, P + iv.tor1.b, tor16 ? D + L.tor16[1][0] : D + L.ch_tor2n, P + iv.tor2.b, nullptr, nullptr, node_cur,
-              cs, nullptr, nullptr, F(w.h_b), cs));
-  } else {
-    RC(lin(R, iv.tor1, node_cur, cs, nullptr, 0, nullptr, 1, F(w.h_a), cs));
-    RC(lin(R, iv.tor2, F(w.h_a), cs, node_cur, cs, nullptr, 0, F(w.h_b), cs));
+  const int cs = d->c_s, nsk = d->num_blocks * d->c_skip;
+  if (p.skip == SKIP_SPLITK)
+    RC(fd_linear_splitk_split(R, nsk, cs, 1, f.F(w.node0), cs, (const float*)(f.D + L.skip_w32), cs, (const float*)(f.D + L.skip_b),
+                              nullptr, f.F(w.skip_all), 0, nsk, f.st));
+  else if (p.skip == SKIP_GEMM)
+    RC(fd_linear(d->precision, R, nsk, cs, f.F(w.node0), cs, f.D + L.skip_w, cs, (const float*)(f.D + L.skip_b), nullptr, 0,
+                 nullptr, 0, f.F(w.skip_all), nsk, f.st));
+  const float* node = f.F(w.node0);
+  for (int b = 0; b < d->num_blocks; ++b) {
+    const float* x;
+    RC(f.ipa_project(b, node));
+    RC(f.ipa_attend(b));
+    RC(f.ipa_out(b, node));
+    RC(f.seq_stage(b, &x));
+    RC(f.inner(b, 2, x, iv.d_t, iv.d_t));
+    RC(f.transition_stage(b, x));
+    node = f.F(w.node);
+    if (b < d->num_blocks - 1) RC(f.edge_transition_stage(b, node));
+    if (a->trace_node) RC(f.d2d(a->trace_node + (size_t)(b + 1) * R * cs, node, node_bytes));
   }
-  // the last torsion layer (Linear(c_s, 2), fp32) rides on the score launch (FDIPT_KF_UNFOLDED: its own GEMM launch)
-  const bool torf_fused = (cs & 3) == 0 && !sw.torf_unfused;
-  if (!torf_fused) RC(lin32(R, iv.torf, F(w.h_b), cs, F(w.psi_un), 8));
-  // tensor_7 / psi epilogue, R^3 score and IGSO(3) score in one launch (frames.hip); the backbone atoms of the finished frames ride on it
-  // (one atom per lane of a residue's 16) unless the launch folds are off
-  if ((a->atom37 || a->atom14) && !a->bb_tables) return FDIPT_EINVAL;
-  const bool bb_fold = (a->atom37 || a->atom14) && !sw.torf_unfused;
-  RC(fd_score_tail(B, N, a->rigids_t, F(w.quat), F(w.trans), d->coordinate_scaling, F(w.psi_un), 8, a->gt_psi, a->fixed_mask,
-                   res_mask, a->so3_sigma, a->t, d->r3_min_b, d->r3_max_b, a->rigids, a->psi, a->rot_score, a->trans_score,
-                   a->ca_out, torf_fused ? F(w.h_b) : nullptr, cs, cs, P + iv.torf.w, P + iv.torf.b, a->so3_score_table,
-                   a->so3_omega_edges, a->so3_num_omega, a->aatype, bb_fold ? a->bb_tables : nullptr, bb_fold ? a->atom37 : nullptr,
-                   bb_fold ? a->atom14 : nullptr, a->step_cursor, st));
-  if ((a->atom37 || a->atom14) && !bb_fold)
-    RC(fd_backbone(R, a->rigids, nullptr, nullptr, 0, a->psi, a->aatype, a->bb_tables, a->atom37, a->atom14, st, a->step_cursor));
-  return FDIPT_OK;
+  return f.heads_stage(node);
 }
 
 extern "C" {
