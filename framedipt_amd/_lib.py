@@ -16,8 +16,9 @@ PREC_F32, PREC_BF16, PREC_F16 = 0, 1, 2
 # FdiptDims.kernel_flags (include/fdipt.h): fallback paths of the half-precision mode, for parity tests
 KF_ET3, KF_GENERIC_PAIR, KF_GENERIC_ATTN, KF_UNFUSED_NODE, KF_UNFOLDED, KF_NO_SPLIT, KF_NO_MERGE, KF_ROWS32, KF_PASS_Z = 1, 2, 4, 8, 16, 32, 64, 128, 256
 KF_POINTS_LAUNCH = 512
+KF_STREAM_ATTN = 1024
 _ERR = {-1: "FDIPT_EINVAL (bad argument)", -2: "FDIPT_ELAUNCH (HIP launch error)",
-        -3: "FDIPT_ESIZE (workspace too small or N beyond the compiled tiling)"}
+        -3: "FDIPT_ESIZE (workspace too small or N beyond the compiled tiling: N <= 1024, N <= 2048 with KF_STREAM_ATTN in the fp16 mode)"}
 
 
 class FdiptError(RuntimeError):

@@ -636,12 +636,12 @@ static int launch_opair(const OPairArgs& a, hipStream_t st) {
   return FDIPT_OK;
 }
 
-int fd_opair_mfma_eligible(int precision, const OPairArgs& a) {
-  return precision != FDIPT_PREC_F32 && a.CZ == 128 && a.H == 8 && a.CD == 32 && a.wdz_img && a.N <= 1024;
+int fd_opair_mfma_eligible(int precision, const OPairArgs& a, int long_keys) {
+  return precision != FDIPT_PREC_F32 && a.CZ == 128 && a.H == 8 && a.CD == 32 && a.wdz_img && a.N <= (long_keys ? 2048 : 1024);
 }
-int fd_opair(int precision, const OPairArgs& a, hipStream_t st) {
+int fd_opair(int precision, const OPairArgs& a, hipStream_t st, int long_keys) {
   if (a.H > 8) return FDIPT_ESIZE;
-  if (fd_opair_mfma_eligible(precision, a)) {
+  if (fd_opair_mfma_eligible(precision, a, long_keys)) {
     if (a.probs_h16 && (a.probs_np & 3)) return FDIPT_EINVAL;
     const int Np = (a.N + OM_JC - 1) / OM_JC * OM_JC;
     // the four-blocks-per-CU form (SB), in one to four passes of 320 keys (N <= 1024: fd_opair_mfma_eligible).  Round 4, third session:
@@ -650,7 +650,11 @@ int fd_opair(int precision, const OPairArgs& a, hipStream_t st) {
     if (a.N <= 320) hipLaunchKernelGGL((opair_mfma_kernel<20, 4, 1, true>), dim3(a.N, a.B), dim3(FD_THREADS), smem, st, a, Np);
     else if (a.N <= 640) hipLaunchKernelGGL((opair_mfma_kernel<20, 4, 2, true>), dim3(a.N, a.B), dim3(FD_THREADS), smem, st, a, Np);
     else if (a.N <= 960) hipLaunchKernelGGL((opair_mfma_kernel<20, 4, 3, true>), dim3(a.N, a.B), dim3(FD_THREADS), smem, st, a, Np);
-    else hipLaunchKernelGGL((opair_mfma_kernel<20, 4, 4, true>), dim3(a.N, a.B), dim3(FD_THREADS), smem, st, a, Np);
+    else if (a.N <= 1280) hipLaunchKernelGGL((opair_mfma_kernel<20, 4, 4, true>), dim3(a.N, a.B), dim3(FD_THREADS), smem, st, a, Np);
+    // long_keys only (1024 < N <= 2048: the per-op entries of the key-streaming attention, which have no pair_z image); 51 KB of LDS at 2048
+    else if (a.N <= 1600) hipLaunchKernelGGL((opair_mfma_kernel<20, 4, 5, true>), dim3(a.N, a.B), dim3(FD_THREADS), smem, st, a, Np);
+    else if (a.N <= 1920) hipLaunchKernelGGL((opair_mfma_kernel<20, 4, 6, true>), dim3(a.N, a.B), dim3(FD_THREADS), smem, st, a, Np);
+    else hipLaunchKernelGGL((opair_mfma_kernel<20, 4, 7, true>), dim3(a.N, a.B), dim3(FD_THREADS), smem, st, a, Np);
     FD_CHECK_LAUNCH();
     return FDIPT_OK;
   }

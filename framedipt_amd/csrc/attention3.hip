@@ -413,3 +413,297 @@ int fd_attention3(const Attn3Args& a, hipStream_t st) {
   if (a.N <= 6 * 4 * 32) return a3_launch<6, 2, false>(a, grid, with(true), st);
   return a3_launch<8, 1, false>(a, grid, with(false), st);
 }
+
+// ------------------------------------------------------------------ key-streaming form (FDIPT_KF_STREAM_ATTN): N <= 2048
+// The same inputs, outputs and block structure as ipa_attn3_kernel, but no register or LDS array grows with N.  Keys are taken in
+// chunks of A3S_CT tiles per wave (A3S_CT * 4 * 32 = 128 keys, 8 k-steps), counted from key 0, and every query tile makes two sweeps:
+//   sweep 1  the logits of every chunk (the register kernel's code); each lane keeps only its running max and sum of exp
+//            (m, l; a rescale of l where the max grows), merged over lane^32 and the 4 waves once at the end
+//   sweep 2  the same logits again (bit-identical), P = exp(s - M) / L final: the weights go to HBM and the P hi / lo fragments of the
+//            chunk to LDS; after a barrier wave w adds the chunk's V_hi P_hi + V_hi P_lo + V_lo P_hi of d tiles {2w, 2w+1} (and waves
+//            0..2 the value-point tile) into accumulators that live across the chunks
+// No online rescale of the output accumulators; the weights written for o_pair carry the final normalisation.  Padded and masked keys
+// add exact zeros (to l: exp underflows; to the P V sums: zero weights) in the same chunk, wave and order wherever the keys end, so a
+// sample's result does not depend on how far its keys are padded.
+#define A3S_CT 1                   // key tiles per wave per chunk (2: 254 registers and 120 of them spilled)
+#define A3S_KC (2 * 4 * A3S_CT)    // k-steps (16 keys) per chunk
+#define A3S_N_MAX 2048
+
+template <bool SPLIT>
+__global__ __launch_bounds__(FD_THREADS, 2) void ipa_attn3_stream_kernel(Attn3Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int N = a.N, H = a.H, nt = (N + 31) / 32, ks = 2 * nt;
+  float* mxs = (float*)smem;                                 // [4][32]
+  float* sms = mxs + 128;                                    // [4][32]
+  u16x8* Qs = (u16x8*)(sms + 128);                           // [16][64] Q fragments of the query tile (16 KB)
+  u16x8* Pfs = Qs + 16 * 64;                                 // [A3S_KC][64] P_hi fragments of one chunk (8 KB)
+  u16x8* Pls = Pfs + A3S_KC * 64;                            // [A3S_KC][64] P_lo fragments (SPLIT)
+  float* opr = (float*)Pfs;                                  // [32][96] o_pt tile, overlays the P fragments after the last chunk
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, li = lane & 31;
+  const int BH = a.B * H;
+  int bhq, qt;
+  {  // XCD-aware block -> (sample, head, query tile), as ipa_attn3_kernel
+    const int id = blockIdx.x, xcd = id & 7, local = id >> 3;
+    const int per = (BH + 7) >> 3;
+    bhq = xcd * per + local / nt;
+    qt = local % nt;
+    if (local >= per * nt || bhq >= BH) return;
+  }
+  const int h = bhq % H, b = bhq / H;
+  const long rb = (long)b * N, bh = bhq;
+  const long kvh = a.kv_per_sample ? b : bh;
+  const int i_raw = qt * 32 + li;
+  const bool valid = i_raw < N;
+  const int i = valid ? i_raw : N - 1;
+
+  {
+    const half_t* qr = a.Qb + ((bh * nt + qt) * 16 * 64 + lane) * 8;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) Qs[(4 * s + wave) * 64 + lane] = *(const u16x8*)(qr + (4 * s + wave) * 512);
+  }
+  const float mi = a.res_mask[rb + i];
+  const float gam = a.gamma[h];
+  f16x8 Bq01h, Bq01l, Bq2h, Bq2x, Bm;  // (ipa_attn3_kernel)
+  {
+    const float* qpr = a.qp + ((rb + i) * H + h) * 24;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float v = gam * qpr[8 * hi + e], v2 = gam * qpr[16 + e];
+      const _Float16 vh = (_Float16)v, v2h = (_Float16)v2;
+      Bq01h[e] = vh;
+      Bq01l[e] = (_Float16)(v - (float)vh);
+      Bq2h[e] = v2h;
+      Bq2x[e] = hi ? (_Float16)((e >= 3 && e < 6) ? 1.f : 0.f) : (_Float16)(v2 - (float)v2h);
+      Bm[e] = (_Float16)0.f;
+    }
+    if (hi) { Bm[0] = (_Float16)(32768.f * mi); Bm[1] = (_Float16)(34464.f * mi); Bm[2] = (_Float16)60000.f; }
+  }
+  __syncthreads();  // Q fragments in LDS
+  // logits S^T[key, query] of key tile t: mask, point and scalar terms in ipa_attn3_kernel's order, then the pair bias
+  auto logits = [&](int t) {
+    hx8 k[16];
+    f16x8 kf[FD_KPF_FRAGS];
+    f32x4 bv[4];
+    const half_t* kr = a.Kb + ((kvh * nt + t) * 16 * 64 + lane) * 8;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) k[s] = a3_ld(kr + s * 512);
+    const half_t* pr = a.kpf + ((bh * nt + t) * (FD_KPF_FRAGS * 64) + lane) * 8;
+#pragma unroll
+    for (int f = 0; f < FD_KPF_FRAGS; ++f) kf[f] = __builtin_bit_cast(f16x8, *(const u16x8*)(pr + f * 512));
+    const float* bt = a.bias + (((bh * nt + qt) * nt + t) * 32 + li) * 32 + 4 * hi;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int j0 = 32 * t + 8 * g + 4 * hi;
+      bv[g] = *(const f32x4*)(bt + 8 * g);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (j0 + q >= N) bv[g][q] = 0.f;
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = -1e5f;
+    acc = fd_mfma32_f16(kf[3], Bm, acc);
+    acc = fd_mfma32_f16(kf[0], Bq01h, acc);
+    acc = fd_mfma32_f16(kf[1], Bq01h, acc);
+    acc = fd_mfma32_f16(kf[0], Bq01l, acc);
+    acc = fd_mfma32_f16(kf[2], Bq2h, acc);
+    acc = fd_mfma32_f16(kf[3], Bq2x, acc);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) acc = fd_mfma32(k[s], __builtin_bit_cast(hx8, Qs[s * 64 + lane]), acc);
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[4 * g + q] += bv[g][q];
+    return acc;
+  };
+  constexpr float L2E = 1.4426950408889634f;
+  const int nch = (nt + 4 * A3S_CT - 1) / (4 * A3S_CT);
+  // ---- sweep 1: running max and sum of exp per lane, then over lane^32 and the 4 waves
+  float m = -3.0e38f, l = 0.f;
+  for (int c = 0; c < nch; ++c) {
+#pragma unroll
+    for (int u = 0; u < A3S_CT; ++u) {
+      const int t = 4 * A3S_CT * c + wave + 4 * u;
+      if (t < nt) {
+        const f32x16 S = logits(t);
+        float tm = S[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) tm = fmaxf(tm, S[r]);
+        const float mn = fmaxf(m, tm);
+        float e = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) e += __builtin_amdgcn_exp2f((S[r] - mn) * L2E);
+        l = l * __builtin_amdgcn_exp2f((m - mn) * L2E) + e;
+        m = mn;
+      }
+    }
+  }
+  {
+    const float m2 = __shfl_xor(m, 32, 64), l2 = __shfl_xor(l, 32, 64), mn = fmaxf(m, m2);
+    const float lo = hi ? l2 : l, lh = hi ? l : l2, mo = hi ? m2 : m, mh = hi ? m : m2;  // the same order in both halves
+    l = lo * __builtin_amdgcn_exp2f((mo - mn) * L2E) + lh * __builtin_amdgcn_exp2f((mh - mn) * L2E);
+    m = mn;
+  }
+  if (hi == 0) { mxs[wave * 32 + li] = m; sms[wave * 32 + li] = l; }
+  __syncthreads();
+  const float M = fmaxf(fmaxf(mxs[li], mxs[32 + li]), fmaxf(mxs[64 + li], mxs[96 + li]));
+  float L = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) L += sms[32 * w + li] * __builtin_amdgcn_exp2f((mxs[32 * w + li] - M) * L2E);
+  const float inv = 1.0f / L;
+  // ---- sweep 2: final weights -> HBM and LDS, P V into the accumulators
+  float* prow = a.probs + (bh * N + i) * N;
+  const long bq = bh / a.H;
+  half_t* prow16 = a.probs_h16 ? a.probs_h16 + ((bq * N + i) * a.H + (bh - bq * a.H)) * (long)a.Np : nullptr;
+  f32x16 acc0, acc1, accp;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = accp[r] = 0.f;
+  for (int c = 0; c < nch; ++c) {
+#pragma unroll
+    for (int u = 0; u < A3S_CT; ++u) {
+      const int tl = wave + 4 * u, t = 4 * A3S_CT * c + tl;
+      if (t < nt) {
+        const f32x16 S = logits(t);
+        float v[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = __builtin_amdgcn_exp2f((S[r] - M) * L2E) * inv;
+        if (valid && prow16) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const u16x4 o = {f2h(v[4 * g]), f2h(v[4 * g + 1]), f2h(v[4 * g + 2]), f2h(v[4 * g + 3])};
+            *(u16x4*)(prow16 + 32 * t + 8 * g + 4 * hi) = o;
+          }
+        } else if (valid) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int j0 = 32 * t + 8 * g + 4 * hi;
+            if (j0 + 3 < N && (N & 3) == 0) {
+              f32x4 o = {v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
+              *(f32x4*)(prow + j0) = o;
+            } else {
+#pragma unroll
+              for (int q = 0; q < 4; ++q)
+                if (j0 + q < N) prow[j0 + q] = v[4 * g + q];
+            }
+          }
+        }
+        const hx8 p0 = a3_pack8(v), p1 = a3_pack8(v + 8);
+        Pfs[(2 * tl) * 64 + lane] = __builtin_bit_cast(u16x8, p0);
+        Pfs[(2 * tl + 1) * 64 + lane] = __builtin_bit_cast(u16x8, p1);
+        if constexpr (SPLIT) {
+          float w[16];
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            w[r] = v[r] - (float)p0[r];
+            w[8 + r] = v[8 + r] - (float)p1[r];
+          }
+          Pls[(2 * tl) * 64 + lane] = __builtin_bit_cast(u16x8, a3_pack8(w));
+          Pls[(2 * tl + 1) * 64 + lane] = __builtin_bit_cast(u16x8, a3_pack8(w + 8));
+        }
+      }
+    }
+    __syncthreads();  // the chunk's P fragments are complete
+    const int s0 = A3S_KC * c, kc = ks - s0 < A3S_KC ? ks - s0 : A3S_KC;
+    hx8 Va[A3S_KC];
+    auto v_load = [&](const half_t* img, long tile) {  // the chunk's k-steps of one 32-row tile of a V / value-point image
+      const half_t* base = img + (tile * ks + s0) * 512 + lane * 8;
+#pragma unroll
+      for (int s = 0; s < A3S_KC; ++s)
+        if (s < kc) Va[s] = a3_ld(base + s * 512);
+    };
+    auto v_mma = [&](f32x16& acc, const u16x8* P) {
+#pragma unroll
+      for (int s = 0; s < A3S_KC; ++s)
+        if (s < kc) acc = fd_mfma32(Va[s], __builtin_bit_cast(hx8, P[s * 64 + lane]), acc);
+    };
+#pragma unroll
+    for (int dd = 0; dd < 2; ++dd) {
+      f32x16& acc = dd ? acc1 : acc0;
+      const long tile = kvh * (A3_C / 32) + 2 * wave + dd;
+      v_load(a.Vt, tile);
+      v_mma(acc, Pfs);                   // V_hi P_hi
+      if constexpr (SPLIT) {
+        v_mma(acc, Pls);                 // V_hi P_lo
+        v_load(a.Vt_lo, tile);
+        v_mma(acc, Pfs);                 // V_lo P_hi
+      }
+    }
+    if (wave < 3) {
+      v_load(a.vpt, bh * 3 + wave);
+      v_mma(accp, Pfs);
+      if constexpr (SPLIT)
+        if (wave < 2) v_mma(accp, Pls);  // (tile 2 holds low parts only)
+    }
+    __syncthreads();  // every wave has read the chunk's P fragments (and, after the last chunk, the o_pt tile may overlay them)
+  }
+#pragma unroll
+  for (int dd = 0; dd < 2; ++dd) {
+    const f32x16& acc = dd ? acc1 : acc0;
+    const int dt = 2 * wave + dd;
+    if (valid && a.out_h16) {
+      half_t* orow = a.out_h16 + (rb + i) * a.out_ld + (long)h * A3_C + 32 * dt + 4 * hi;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const u16x4 o = {f2h(acc[4 * g]), f2h(acc[4 * g + 1]), f2h(acc[4 * g + 2]), f2h(acc[4 * g + 3])};
+        *(u16x4*)(orow + 8 * g) = o;
+      }
+    } else if (valid) {
+      float* orow = a.out + (rb + i) * a.out_ld + (long)h * A3_C + 32 * dt + 4 * hi;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 o = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+        *(f32x4*)(orow + 8 * g) = o;
+      }
+    }
+  }
+  if (wave < 3) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      f32x4 o = {accp[4 * g], accp[4 * g + 1], accp[4 * g + 2], accp[4 * g + 3]};
+      *(f32x4*)(opr + li * 96 + 32 * wave + 8 * g + 4 * hi) = o;
+    }
+  }
+  __syncthreads();
+  // ---- o_pt = R_i^T (sum - t_i) and its norm, as ipa_attn3_kernel
+  for (int it = tid; it < 32 * 12; it += FD_THREADS) {
+    const int q = it / 12, pt = it % 12, iq = qt * 32 + q;
+    if (iq < N) {
+      const float* o = opr + q * 96 + pt * 3;
+      const float sx = o[0] + o[36], sy = o[1] + o[37], sz = o[2] + o[38];
+      const float* R = a.rot + (rb + iq) * 9;
+      const float* T = a.trans + (rb + iq) * 3;
+      const float x = sx - T[0], y = sy - T[1], z = sz - T[2];
+      const float ox = R[0] * x + R[3] * y + R[6] * z;
+      const float oy = R[1] * x + R[4] * y + R[7] * z;
+      const float oz = R[2] * x + R[5] * y + R[8] * z;
+      const int HP = H * 12;
+      const float on = sqrtf(ox * ox + oy * oy + oz * oz + 1e-8f);
+      if (a.out_h16) {
+        half_t* oo = a.out_h16 + (rb + iq) * a.out_ld + a.pt_off + h * 12 + pt;
+        oo[0] = f2h(ox); oo[HP] = f2h(oy); oo[2 * HP] = f2h(oz); oo[3 * HP] = f2h(on);
+      } else {
+        float* oo = a.out + (rb + iq) * a.out_ld + a.pt_off + h * 12 + pt;
+        oo[0] = ox; oo[HP] = oy; oo[2 * HP] = oz;
+        oo[3 * HP] = on;
+      }
+    }
+  }
+}
+
+int fd_attention3_stream_supported(const Attn3Args& a) {
+  return a.N >= 1 && a.N <= A3S_N_MAX && a.H <= 8 && (a.H & 1) == 0 && a.Np == ((a.N + 31) / 32) * 32 && a.vpt != nullptr;
+}
+
+int fd_attention3_stream(const Attn3Args& a, hipStream_t st) {
+  if (!fd_attention3_stream_supported(a)) return FDIPT_ESIZE;
+  if (!a.kpf) return FDIPT_EINVAL;
+  const int nt = (a.N + 31) / 32, per = (a.B * a.H + 7) / 8;
+  const dim3 grid(8 * per * nt);
+  // reduction buffers 1 KB, Q fragments 16 KB, P_hi / P_lo fragments of one chunk 8 KB each (together >= the 12 KB o_pt tile): 33 KB, any N
+  const size_t smem = 2 * 128 * 4 + 16 * 64 * 16 + (size_t)2 * A3S_KC * 64 * 16;
+  if (a.Vt_lo) hipLaunchKernelGGL((ipa_attn3_stream_kernel<true>), grid, dim3(FD_THREADS), smem, st, a);
+  else hipLaunchKernelGGL((ipa_attn3_stream_kernel<false>), grid, dim3(FD_THREADS), smem, st, a);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}

@@ -25,6 +25,9 @@
 #define SA_DT 3         // 32-channel output tiles (80 -> 96, padded rows are zero)
 #define SA_NTW_MAX 8    // key tiles per wave -> N <= 8 * 4 * 32 = 1024
 
+// the key-streaming form (FDIPT_KF_STREAM_ATTN, below): its launch
+static int seq_attention_stream_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm& wm, hipStream_t st);
+
 __host__ __device__ __forceinline__ int sa_perm16(int pos) {  // involution
   const int hi = pos >> 3, e = pos & 7;
   return 4 * hi + (e & 3) + 8 * (e >> 2);
@@ -429,8 +432,9 @@ size_t fd_seq_attention_image_bytes(int B, int N, int H) {
 int fd_seq_attention_supported(int N, int H, int hd) { return hd == SA_HD && N >= 1 && N <= 4 * SA_NTW_MAX * 32 && H >= 1; }
 
 int fd_seq_attention(int B, int N, int H, const float* qkv, int ld, float scale, const float* res_mask, void* images,
-                     float* out, int out_ld, hipStream_t st) {
-  if (!fd_seq_attention_supported(N, H, SA_HD) || (ld & 3) || (out_ld & 3)) return FDIPT_EINVAL;
+                     float* out, int out_ld, hipStream_t st, int stream) {
+  if (!(stream ? fd_seq_attention_stream_supported(N, H, SA_HD) : fd_seq_attention_supported(N, H, SA_HD)) || (ld & 3) || (out_ld & 3))
+    return FDIPT_EINVAL;
   const int Np = (N + 31) / 32 * 32, nt = Np / 32;
   half_t* Qi = (half_t*)images;
   half_t* Ki = Qi + (size_t)B * H * Np * SA_KS * 16;
@@ -439,13 +443,13 @@ int fd_seq_attention(int B, int N, int H, const float* qkv, int ld, float scale,
   hipLaunchKernelGGL(seq_images_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, st, B, N, Np, H, qkv, ld, scale,
                      res_mask, Qi, Ki, Vi);
   FD_CHECK_LAUNCH();
-  return fd_seq_attention_run(B, N, H, images, out, out_ld, nullptr, st);
+  return fd_seq_attention_run(B, N, H, images, out, out_ld, nullptr, st, stream);
 }
 
 // Fused path: fd_seq_images_init once per forward, then per layer fd_seq_qkv (in_proj + images) and fd_seq_attention_run.
-int fd_seq_images_init(int B, int N, int H, const float* res_mask, void* images, const SeqInitExtra& x, hipStream_t st) {
+int fd_seq_images_init(int B, int N, int H, const float* res_mask, void* images, const SeqInitExtra& x, hipStream_t st, int stream) {
   if (x.Kb && (((N + 31) / 32 * 32) == N || (x.C & 31))) return FDIPT_EINVAL;
-  if (!fd_seq_attention_supported(N, H, SA_HD)) return FDIPT_EINVAL;
+  if (!(stream ? fd_seq_attention_stream_supported(N, H, SA_HD) : fd_seq_attention_supported(N, H, SA_HD))) return FDIPT_EINVAL;
   const int Np = (N + 31) / 32 * 32, nt = Np / 32;
   half_t* Qi = (half_t*)images;
   half_t* Ki = Qi + (size_t)B * H * Np * SA_KS * 16;
@@ -473,8 +477,12 @@ int fd_seq_qkv(int B, int N, int H, const float* x, int ld_x, const void* wimg, 
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
-int fd_seq_attention_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm* warm, hipStream_t st) {
+int fd_seq_attention_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm* warm, hipStream_t st, int stream) {
   const L2Warm wm = warm ? *warm : L2Warm{};
+  if (stream) {
+    if (!fd_seq_attention_stream_supported(N, H, SA_HD) || (out_ld & 3)) return FDIPT_EINVAL;
+    return seq_attention_stream_run(B, N, H, images, out, out_ld, wm, st);
+  }
   if (!fd_seq_attention_supported(N, H, SA_HD) || (out_ld & 3)) return FDIPT_EINVAL;
   const int Np = (N + 31) / 32 * 32, nt = Np / 32;
   const half_t* Qi = (const half_t*)images;
@@ -493,6 +501,144 @@ int fd_seq_attention_run(int B, int N, int H, const void* images, float* out, in
   else if (N <= 4 * 4 * 32) hipLaunchKernelGGL((seq_attn_kernel<4, 1>), grid, block, smem, st, B, N, Np, H, Qi, Ki, Vi, out, out_ld, wm);
   else if (N <= 6 * 4 * 32) hipLaunchKernelGGL((seq_attn_kernel<6, 1>), grid, block, smem, st, B, N, Np, H, Qi, Ki, Vi, out, out_ld, wm);
   else hipLaunchKernelGGL((seq_attn_kernel<8, 1>), grid, block, smem, st, B, N, Np, H, Qi, Ki, Vi, out, out_ld, wm);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+
+// ------------------------------------------------------------------ key-streaming form (FDIPT_KF_STREAM_ATTN): N <= 2048
+// seq_attn_kernel's inputs and block structure with O(1) registers and LDS in N (the scheme of ipa_attn3_stream_kernel, attention3.hip):
+// keys in chunks of SAS_CT tiles per wave (256 keys), counted from key 0; sweep 1 keeps each lane's running max and sum of exp, sweep 2
+// recomputes the same scores, writes the final P fragments of the chunk to LDS and waves 0..2 add V P of their channel tile into
+// accumulators that live across the chunks.  17 KB of LDS at every N (seq_attn_kernel<8, 1> needs 65 KB at N = 1024).
+#define SAS_CT 2                  // key tiles per wave per chunk
+#define SAS_KC (2 * 4 * SAS_CT)   // k-steps (16 keys) per chunk
+#define SAS_N_MAX 2048
+
+__global__ __launch_bounds__(FD_THREADS, 2) void seq_attn_stream_kernel(int B, int N, int Np, int H, const half_t* __restrict__ Qi,
+                                                                       const half_t* __restrict__ Ki, const half_t* __restrict__ Vi,
+                                                                       float* __restrict__ out, int out_ld, L2Warm warm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nt = Np >> 5, ks = 2 * nt;
+  unsigned warm_tok = 0;
+  float* mxs = (float*)smem;              // [4][32]
+  float* sms = mxs + 128;                 // [4][32]
+  u16x8* Pfs = (u16x8*)(sms + 128);       // [SAS_KC][64]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, li = lane & 31;
+  const int BH = B * H;
+  int bhq, qt;
+  {  // XCD-aware, as seq_attn_kernel
+    const int id = blockIdx.x, xcd = id & 7, local = id >> 3;
+    const int per = (BH + 7) >> 3;
+    bhq = xcd * per + local / nt;
+    qt = local % nt;
+    if (local >= per * nt || bhq >= BH) return;
+  }
+  const int h = bhq % H, b = bhq / H;
+  const long bh = bhq, rb = (long)b * N;
+  const int i = 32 * qt + li;
+  hx8 Qf[SA_KS];
+#pragma unroll
+  for (int s = 0; s < SA_KS; ++s) Qf[s] = sa_ld(Qi + (((bh * nt + qt) * SA_KS + s) * 64 + lane) * 8);
+  auto scores = [&](int t) {  // S^T[key, query] of key tile t (mask included: channel 80)
+    hx8 Kf[SA_KS];
+#pragma unroll
+    for (int s = 0; s < SA_KS; ++s) Kf[s] = sa_ld(Ki + (((bh * nt + t) * SA_KS + s) * 64 + lane) * 8);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < SA_KS; ++s) acc = fd_mfma32(Kf[s], Qf[s], acc);
+    return acc;
+  };
+  constexpr float L2E = 1.4426950408889634f;
+  const int nch = (nt + 4 * SAS_CT - 1) / (4 * SAS_CT);
+  // ---- sweep 1: running max and sum of exp per lane, then over lane^32 and the 4 waves
+  float m = -3.0e38f, l = 0.f;
+  for (int c = 0; c < nch; ++c) {
+#pragma unroll
+    for (int u = 0; u < SAS_CT; ++u) {
+      const int t = 4 * SAS_CT * c + wave + 4 * u;
+      if (t < nt) {
+        const f32x16 S = scores(t);
+        float tm = S[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) tm = fmaxf(tm, S[r]);
+        const float mn = fmaxf(m, tm);
+        float e = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) e += __builtin_amdgcn_exp2f((S[r] - mn) * L2E);
+        l = l * __builtin_amdgcn_exp2f((m - mn) * L2E) + e;
+        m = mn;
+      }
+    }
+  }
+  if (wave == 3) warm_tok = fd_l2_warm(warm, blockIdx.x, gridDim.x, lane, 64);  // (wave 3 owns no channel tile)
+  {
+    const float m2 = __shfl_xor(m, 32, 64), l2 = __shfl_xor(l, 32, 64), mn = fmaxf(m, m2);
+    const float lo = hi ? l2 : l, lh = hi ? l : l2, mo = hi ? m2 : m, mh = hi ? m : m2;  // the same order in both halves
+    l = lo * __builtin_amdgcn_exp2f((mo - mn) * L2E) + lh * __builtin_amdgcn_exp2f((mh - mn) * L2E);
+    m = mn;
+  }
+  if (hi == 0) { mxs[wave * 32 + li] = m; sms[wave * 32 + li] = l; }
+  __syncthreads();
+  const float M = fmaxf(fmaxf(mxs[li], mxs[32 + li]), fmaxf(mxs[64 + li], mxs[96 + li]));
+  float L = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) L += sms[32 * w + li] * __builtin_amdgcn_exp2f((mxs[32 * w + li] - M) * L2E);
+  const float inv = 1.0f / L;
+  // ---- sweep 2
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  for (int c = 0; c < nch; ++c) {
+#pragma unroll
+    for (int u = 0; u < SAS_CT; ++u) {
+      const int tl = wave + 4 * u, t = 4 * SAS_CT * c + tl;
+      if (t < nt) {
+        const f32x16 S = scores(t);
+        float v[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = __builtin_amdgcn_exp2f((S[r] - M) * L2E) * inv;
+        Pfs[(2 * tl) * 64 + lane] = __builtin_bit_cast(u16x8, sa_pack8(v));
+        Pfs[(2 * tl + 1) * 64 + lane] = __builtin_bit_cast(u16x8, sa_pack8(v + 8));
+      }
+    }
+    __syncthreads();  // the chunk's P fragments are complete
+    if (wave < SA_DT) {
+      const int s0 = SAS_KC * c, kc = ks - s0 < SAS_KC ? ks - s0 : SAS_KC;
+      const half_t* vr = Vi + (((bh * SA_DT + wave) * ks + s0) * 64 + lane) * 8;
+      hx8 Va[SAS_KC];
+#pragma unroll
+      for (int s = 0; s < SAS_KC; ++s)
+        if (s < kc) Va[s] = sa_ld(vr + s * 512);
+#pragma unroll
+      for (int s = 0; s < SAS_KC; ++s)
+        if (s < kc) acc = fd_mfma32(Va[s], __builtin_bit_cast(hx8, Pfs[s * 64 + lane]), acc);
+    }
+    __syncthreads();  // every wave has read the chunk's P fragments
+  }
+  if (wave < SA_DT && i < N) {
+    float* orow = out + (rb + i) * out_ld + (long)h * SA_HD + 32 * wave + 4 * hi;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      if (32 * wave + 8 * g + 4 * hi < SA_HD) {
+        f32x4 o = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+        *(f32x4*)(orow + 8 * g) = o;
+      }
+  }
+  fd_l2_warm_done(warm_tok);
+}
+
+int fd_seq_attention_stream_supported(int N, int H, int hd) { return hd == SA_HD && N >= 1 && N <= SAS_N_MAX && H >= 1; }
+
+static int seq_attention_stream_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm& wm, hipStream_t st) {
+  const int Np = (N + 31) / 32 * 32, nt = Np / 32;
+  const half_t* Qi = (const half_t*)images;
+  const half_t* Ki = Qi + (size_t)B * H * Np * SA_KS * 16;
+  const half_t* Vi = Ki + (size_t)B * H * Np * SA_KS * 16;
+  const int per = (B * H + 7) / 8;
+  const size_t smem = 2 * 128 * 4 + (size_t)SAS_KC * 64 * 16;
+  hipLaunchKernelGGL(seq_attn_stream_kernel, dim3(8 * per * nt), dim3(FD_THREADS), smem, st, B, N, Np, H, Qi, Ki, Vi, out, out_ld, wm);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }

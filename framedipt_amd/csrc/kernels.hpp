@@ -248,13 +248,18 @@ struct Attn3Args {
 };
 int fd_attention3_supported(const Attn3Args& a);  // keep to scalars and null tests: plan_forward (model.hip) asks it with placeholder pointers
 int fd_attention3(const Attn3Args& a, hipStream_t st);
+// key-streaming form (FDIPT_KF_STREAM_ATTN): the same arguments, 1 <= N <= 2048, LDS and registers independent of N
+int fd_attention3_stream_supported(const Attn3Args& a);  // (scalars and null tests, as fd_attention3_supported)
+int fd_attention3_stream(const Attn3Args& a, hipStream_t st);
 
 
 // sequence-transformer self-attention (attention_seq.hip): bf16, head_dim 80, N <= 512
 size_t fd_seq_attention_image_bytes(int B, int N, int H);
 int fd_seq_attention_supported(int N, int H, int hd);
+// stream != 0: the key-streaming kernel (FDIPT_KF_STREAM_ATTN), N <= 2048, for this call and fd_seq_attention_run
+int fd_seq_attention_stream_supported(int N, int H, int hd);
 int fd_seq_attention(int B, int N, int H, const float* qkv, int ld, float scale, const float* res_mask, void* images,
-                     float* out, int out_ld, hipStream_t st);
+                     float* out, int out_ld, hipStream_t st, int stream = 0);
 
 // fused form: images initialised once per forward, in_proj writes them directly (seq_qkv), then the attention kernel
 struct SeqInitExtra {  // once-per-forward fills folded into the sequence-image init launch (all optional)
@@ -262,12 +267,14 @@ struct SeqInitExtra {  // once-per-forward fills folded into the sequence-image 
   void* Kb; void* Vt; long BH; int C;  // padded keys of attention3's key / value images (N, Np as the sequence images: Np = ceil32(N))
   void* Vt2 = nullptr;                 // optional second value image (V_lo) with the same pads
 };
-int fd_seq_images_init(int B, int N, int H, const float* res_mask, void* images, const SeqInitExtra& x, hipStream_t st);
+// stream != 0: the images are read by the key-streaming kernel (N <= 2048), as fd_seq_attention_run(.., stream)
+int fd_seq_images_init(int B, int N, int H, const float* res_mask, void* images, const SeqInitExtra& x, hipStream_t st, int stream = 0);
 int fd_seq_qkv_supported(int N, int H, int d_model);
 // wimg_lo != NULL: split operands (image of W - half(W), fd_chain_build_image_lo)
 int fd_seq_qkv(int B, int N, int H, const float* x, int ld_x, const void* wimg, const void* wimg_lo, const float* bias, float scale,
                void* images, hipStream_t st);
-int fd_seq_attention_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm* warm, hipStream_t st);
+int fd_seq_attention_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm* warm, hipStream_t st,
+                         int stream = 0);
 // fp32 mode: the same block structure on fp32 MFMAs, operands straight from the fp32 in_proj rows qkv [B N, ld] = (q | k | v)
 int fd_seq_attention_f32_supported(int N, int H, int hd, int ld);
 int fd_seq_attention_f32(int B, int N, int H, const float* qkv, int ld, float scale, const float* res_mask, float* out, int out_ld,
@@ -392,8 +399,9 @@ int fd_attention(int precision, int ipa, const AttnArgs& a, hipStream_t st);
 // fp32 mode, reference widths: the IPA attention with the scores in registers (attention.hip: ipa_attn_f32_kernel)
 int fd_ipa_attention_f32_supported(const AttnArgs& a);
 int fd_ipa_attention_f32(const AttnArgs& a, hipStream_t st);
-int fd_opair(int precision, const OPairArgs& a, hipStream_t st);
-int fd_opair_mfma_eligible(int precision, const OPairArgs& a);  // the MFMA kernel will run (it can take probs_h16); keep to scalars and null tests: plan_forward (model.hip) asks it with placeholder pointers
+// long_keys != 0 (FDIPT_KF_STREAM_ATTN): the MFMA kernel takes N <= 2048 (up to 7 passes of 320 keys) instead of N <= 1024
+int fd_opair(int precision, const OPairArgs& a, hipStream_t st, int long_keys = 0);
+int fd_opair_mfma_eligible(int precision, const OPairArgs& a, int long_keys = 0);  // the MFMA kernel will run (it can take probs_h16); keep to scalars and null tests: plan_forward (model.hip) asks it with placeholder pointers
 int fd_opair_pz(const OPairArgs& a, hipStream_t st);  // o_pair from the producer-emitted pair_z image (OPairArgs.pz, probs_h16)
 int fd_pair_bias2(int B, int N, int H, const void* z, const void* wb, const float* bb, float* out, int frag, hipStream_t st);
 // fp32 mode: out[p, h] = z[p, :] . Wb[h, :] + bb[h] over the fp32 pair representation (H = 8, c_z = 128), one streaming pass

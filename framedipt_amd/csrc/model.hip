@@ -684,6 +684,7 @@ struct ForwardPlan {
   OutProj outproj;
   int slices;   // split-K slices of the output projection
   bool feats_fused, ee_bias, et_bias, pz;
+  bool stream;                         // FDIPT_KF_STREAM_ATTN in the half-precision mode, N <= 2048: the key-streaming attention kernels
   bool a3, probs_h16;                  // IPA path: attention3, and the MFMA o_pair fed with bf16 attention weights
   bool vpt, proj2, merged, proj_pts, vt_lo, init_fused, feats_h16;
   NodeRows node_rows;
@@ -740,12 +741,17 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   a3.B = B; a3.N = N; a3.H = H; a3.Np = Np; a3.vpt = (const half_t*)&kImage;
   OPairArgs oa = {};
   oa.B = B; oa.N = N; oa.H = H; oa.CZ = cz; oa.CD = cz / 4; oa.wdz_img = p.bf && cz == 128 ? &kImage : nullptr;
-  const bool opair_mfma = fd_opair_mfma_eligible(d->precision, oa);
-  p.a3 = p.bf && cz == 128 && C == 256 && Pq == 8 && Pv == 12 && !generic_attn && fd_attention3_supported(a3);
+  // key-streaming attention (attention3.hip / attention_seq.hip: two sweeps over key chunks) for every N <= 2048; it lifts the register
+  // kernels' N <= 1024 wherever this plan tests a length (IPA attention, o_pair, pair bias producers, sequence attention)
+  p.stream = (f & FDIPT_KF_STREAM_ATTN) && p.bf && !generic_attn && N <= 2048;
+  const int n_attn = p.stream ? 2048 : 1024;  // the attention kernels' bound on N
+  const bool opair_mfma = fd_opair_mfma_eligible(d->precision, oa, p.stream);
+  p.a3 = p.bf && cz == 128 && C == 256 && Pq == 8 && Pv == 12 && !generic_attn &&
+         (p.stream ? fd_attention3_stream_supported(a3) : fd_attention3_supported(a3));
   p.probs_h16 = p.a3 && opair_mfma && 2 * Np <= 4 * N;
   // the next block's pair bias linear_b(z)/sqrt(3) from the LayerNorm epilogue of the producer of z (saves a pass over z): the
   // embedder for block 0 (register kernel only), the EdgeTransition of block b for block b + 1
-  const bool bias_rule = cz == 128 && C == 256 && Pq == 8 && Pv == 12 && H <= 8 && N <= 1024 && !generic_attn && !unfolded;
+  const bool bias_rule = cz == 128 && C == 256 && Pq == 8 && Pv == 12 && H <= 8 && N <= n_attn && !generic_attn && !unfolded;
   p.regpair = use_regpair(d);
   p.ee_bias = bias_rule && p.regpair;
   p.et_bias = bias_rule;
@@ -787,8 +793,9 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   // (the node-row images ride on the point launch when that is the 16-keys-per-block kernel; else their own launch)
   p.node_rows = !p.merged || p.proj_pts ? NR_PROJ : p.vpt && (H & 1) == 0 && cs == 256 ? NR_POINTS : NR_LAUNCH;
   const int th = d->tfmr_heads, hd = iv.d_t / th;
-  if (p.rbk && !generic_attn && fd_seq_attention_supported(N, th, hd) && fd_seq_qkv_supported(N, th, iv.d_t)) p.seq = SEQ_FUSED;
-  else if (p.bf && !generic_attn && fd_seq_attention_supported(N, th, hd)) p.seq = SEQ_BF16;
+  const bool seq_ok = p.stream ? fd_seq_attention_stream_supported(N, th, hd) : fd_seq_attention_supported(N, th, hd);
+  if (p.rbk && !generic_attn && seq_ok && fd_seq_qkv_supported(N, th, iv.d_t)) p.seq = SEQ_FUSED;
+  else if (p.bf && !generic_attn && seq_ok) p.seq = SEQ_BF16;
   else if (!p.bf && !generic_attn && fd_seq_attention_f32_supported(N, th, hd, 3 * iv.d_t)) p.seq = SEQ_F32;  // scores in registers (round 5)
   else p.seq = SEQ_GENERIC;
   p.ipa_bias_f32 = !p.bf && H == 8 && cz == 128;
@@ -992,7 +999,7 @@ struct Fwd {
       if (pj.zero_pads && p.init_fused) {
         SeqInitExtra sx = {vpt_zero ? W + w.vpt : nullptr, vpt_zero ? (long)(vpt_bytes >> 4) : 0L, key_pads ? (void*)pj.Kb : nullptr,
                            (void*)pj.Vt, (long)B * H, C, (void*)pj.Vt_lo};
-        RC(fd_seq_images_init(B, N, d->tfmr_heads, a->res_mask, W + w.seqimg, sx, st));
+        RC(fd_seq_images_init(B, N, d->tfmr_heads, a->res_mask, W + w.seqimg, sx, st, p.stream));
         vpt_zero = false;
       } else if (pj.zero_pads && (key_pads || vpt_zero)) {
         ProjArgs pz = pj; pz.W_img = nullptr;
@@ -1030,7 +1037,7 @@ struct Fwd {
         RC(fd_pair_bias2(B, N, H, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), 1, st));
       if (p.feats_h16) { a3.out_h16 = (half_t*)(W + w.feats); oa.out_h16 = a3.out_h16; }
       if (p.probs_h16) { a3.probs_h16 = (half_t*)(W + w.probs); oa.probs_h16 = a3.probs_h16; oa.probs_np = Np; }
-      RC(fd_attention3(a3, st));
+      RC(p.stream ? fd_attention3_stream(a3, st) : fd_attention3(a3, st));
     } else {
       const long ld = iv.proj_out;
       AttnArgs aa;
@@ -1054,7 +1061,7 @@ struct Fwd {
       oa.pz = (const half_t*)(W + w.pz);
       return fd_opair_pz(oa, st);
     }
-    return fd_opair(d->precision, oa, st);
+    return fd_opair(d->precision, oa, st, p.stream);
   }
   // ---- IPA, part 3: node = LN(node + linear_out(features)) in tf_in[:, :cs]; tf_in[:, cs:] = skip_embed(init_node)   (ipa:531-535)
   int ipa_out(int b, const float* node) const {
@@ -1099,11 +1106,11 @@ struct Fwd {
       const TfLayer& t = k.tf[l];
       const bool last = l + 1 == d->tfmr_layers;
       if (p.seq == SEQ_FUSED) {  // default bf16 path: in_proj writes the attention operand images directly (attention_seq.hip)
-        if (b == 0 && l == 0 && !p.init_fused) RC(fd_seq_images_init(B, N, th, res_mask, W + w.seqimg, SeqInitExtra{}, st));
+        if (b == 0 && l == 0 && !p.init_fused) RC(fd_seq_images_init(B, N, th, res_mask, W + w.seqimg, SeqInitExtra{}, st, p.stream));
         RC(fd_seq_qkv(B, N, th, x, dt, D + db.ch.inp[l], p.split ? D + db.lo.inp[l] : nullptr, P + t.inp.b, 1.0f / sqrtf((float)hd),
                       W + w.seqimg, st));
         const L2Warm wt = warm_of(b, WARM_TAIL, l);  // ... and the attention touches the weights of the layer's tail kernel, launched next
-        RC(fd_seq_attention_run(B, N, th, W + w.seqimg, F(w.att), dt, &wt, st));
+        RC(fd_seq_attention_run(B, N, th, W + w.seqimg, F(w.att), dt, &wt, st, p.stream));
       } else {
         RC(lin(t.inp, x, dt, nullptr, 0, nullptr, 0, F(w.qkv), 3 * dt));
         AttnArgs ta = {};
@@ -1111,7 +1118,7 @@ struct Fwd {
         ta.q = F(w.qkv); ta.k = F(w.qkv) + dt; ta.v = F(w.qkv) + 2 * dt;
         ta.q_ld = ta.k_ld = ta.v_ld = 3 * dt; ta.q_hs = ta.k_hs = ta.v_hs = hd;
         ta.C = hd; ta.Dv = hd; ta.scale = 1.0f / sqrtf((float)hd); ta.res_mask = res_mask; ta.out = F(w.att); ta.out_ld = dt;
-        if (p.seq == SEQ_BF16) RC(fd_seq_attention(B, N, th, F(w.qkv), 3 * dt, ta.scale, res_mask, W + w.seqimg, F(w.att), dt, st));
+        if (p.seq == SEQ_BF16) RC(fd_seq_attention(B, N, th, F(w.qkv), 3 * dt, ta.scale, res_mask, W + w.seqimg, F(w.att), dt, st, p.stream));
         else if (p.seq == SEQ_F32) RC(fd_seq_attention_f32(B, N, th, F(w.qkv), 3 * dt, ta.scale, res_mask, F(w.att), dt, st));
         else RC(fd_attention(d->precision, 0, ta, st));
       }

@@ -196,6 +196,7 @@ def main():
     ap.add_argument("--noise-scale", type=float, default=0.1)
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--precision", default="fp16", choices=["fp16", "fp32"])
+    ap.add_argument("--kernel-flags", type=int, default=0, help="FdiptDims.kernel_flags (_lib.KF_*); 1024 = KF_STREAM_ATTN: fp16 chains up to 2048")
     ap.add_argument("--seed", type=int, default=123)
     ap.add_argument("--weights-seed", type=int, default=7, help="synthetic weights (no checkpoint is available offline)")
     ap.add_argument("--full-trajectory", action="store_true", help="store every step of prot_traj instead of the final sample")
@@ -243,7 +244,7 @@ def main():
     inp = a.download_dir is not None
     conf = config.base_config(inpainting=inp)
     diff = SE3Diffuser(conf.diffuser, device=dev)
-    net = ScoreNetwork(conf.model, diff, inpainting=inp, precision=a.precision).load_synthetic(a.weights_seed).to(dev)
+    net = ScoreNetwork(conf.model, diff, inpainting=inp, precision=a.precision, kernel_flags=a.kernel_flags).load_synthetic(a.weights_seed).to(dev)
     write_item, keep = None, ("prot_traj",)
     if inp:
         from .sampler import ConditionalSampler, TCRSampler

@@ -60,7 +60,11 @@ extern "C" {
                                     pair_z image emitted by the producers of z (round 6); the last EdgeTransition then keeps its z' store */
 #define FDIPT_KF_POINTS_LAUNCH 512 /* merged IPA projection: the rotated points and the node-row images by their own launch (points16_kernel)
                                     instead of the projection's epilogue                                                       */
-#define FDIPT_KF_ALL 1023
+#define FDIPT_KF_STREAM_ATTN 1024 /* half-precision mode: the IPA and sequence-transformer attentions on the key-streaming kernels (two sweeps
+                                    over key chunks, LDS and registers independent of N) for every N, and the forward accepts N <= 2048
+                                    instead of 1024.  No effect in the fp32 mode or with FDIPT_KF_GENERIC_ATTN (which takes precedence):
+                                    there N > 1024 stays FDIPT_ESIZE.  N > 2048 is FDIPT_ESIZE with or without the flag          */
+#define FDIPT_KF_ALL 2047
 
 typedef void* fdipt_stream_t; /* hipStream_t */
 
