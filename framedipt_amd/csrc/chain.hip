@@ -35,19 +35,7 @@ __global__ void chain_image_kernel(const float* __restrict__ w, int N, int K, in
   }
 }
 size_t fd_chain_image_bytes(int N, int K) { return (size_t)((N + 31) / 32) * ((K + 15) / 16) * 1024; }
-int fd_chain_build_image_scaled(const float* w, int N, int K, int ldw, int permuted, float scale, void* img, hipStream_t st) {
-  const int NT = (N + 31) / 32, KS = (K + 15) / 16;
-  hipLaunchKernelGGL(chain_image_kernel, dim3(64), dim3(256), 0, st, w, N, K, ldw, permuted, NT, KS, scale, 0, (half_t*)img);
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
-}
-int fd_chain_build_image_lo(const float* w, int N, int K, int ldw, void* img, hipStream_t st) {
-  const int NT = (N + 31) / 32, KS = (K + 15) / 16;
-  hipLaunchKernelGGL(chain_image_kernel, dim3(64), dim3(256), 0, st, w, N, K, ldw, 0, NT, KS, 1.0f, 1, (half_t*)img);
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
-}
-int fd_chain_build_image_ex(const float* w, int N, int K, int ldw, int permuted, int lo, void* img, hipStream_t st) {
+int fd_chain_build_image(const float* w, int N, int K, int ldw, int permuted, int lo, void* img, hipStream_t st) {
   const int NT = (N + 31) / 32, KS = (K + 15) / 16;
   hipLaunchKernelGGL(chain_image_kernel, dim3(64), dim3(256), 0, st, w, N, K, ldw, permuted, NT, KS, 1.0f, lo, (half_t*)img);
   FD_CHECK_LAUNCH();
@@ -72,9 +60,6 @@ int fd_chain_build_image16(const float* w, int N, int K, int Kpad, int ldw, int 
   hipLaunchKernelGGL(chain_image16_kernel, dim3(64), dim3(256), 0, st, w, K, ldw, N / 16, Kpad / 32, lo, (half_t*)img);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
-}
-int fd_chain_build_image(const float* w, int N, int K, int ldw, int permuted, void* img, hipStream_t st) {
-  return fd_chain_build_image_scaled(w, N, K, ldw, permuted, 1.0f, img, st);
 }
 
 // ------------------------------------------------------------------ device pieces

@@ -112,7 +112,7 @@ int fd_et4_build_stream(const float* w1, const float* w2, const float* wf, void*
   return FDIPT_OK;
 }
 size_t fd_et4_stream_bytes() { return E4_STREAM_BYTES; }
-// down_z of the NEXT block's IPA into the stream's last chunk: img_hi / img_lo = fd_chain_build_image_ex(Wdz, 32, 128, permuted = 1, lo = 0 / 1), 8 KB each
+// down_z of the NEXT block's IPA into the stream's last chunk: img_hi / img_lo = fd_chain_build_image(Wdz, 32, 128, 128, permuted = 1, lo = 0 / 1), 8 KB each
 int fd_et4_set_dz(void* stream, const void* img_hi, const void* img_lo, hipStream_t st) {
   char* dst = (char*)stream + (size_t)E4_DZ_FR0 * 1024;
   if (hipMemcpyAsync(dst, img_hi, 8192, hipMemcpyDeviceToDevice, st) != hipSuccess || hipMemcpyAsync(dst + 8192, img_lo, 8192, hipMemcpyDeviceToDevice, st) != hipSuccess)

@@ -562,8 +562,8 @@ int fd_linear_splitk_split(int M, int N, int K, int nsplit, const float* A, int 
 // matrix in each of its 38 row blocks and runs 14 dependent load -> split -> LDS -> barrier -> MFMA rounds per block (29 us, MFMA 11 %).
 // Here: a block = 64 rows x ALL 256 columns x one K slice of KSL k-steps (2688 = 6 x 28 x 16: 38 x 6 = 228 blocks, one round of the 256
 // CUs); the block's activation slice is read once (coalesced fp32 rows), split, and parked in LDS as hi rows | lo rows (row stride
-// 2 KW + 16 B: the 16 lanes of a b128 read hit 16 distinct slots); the weights are fragment images prepared once (fd_chain_build_image /
-// _lo of the [256, K] matrix) and go STRAIGHT from L2 into registers — wave w owns column tile w, one linear 1 KB load per fragment,
+// 2 KW + 16 B: the 16 lanes of a b128 read hit 16 distinct slots); the weights are fragment images prepared once (fd_chain_build_image,
+// hi and lo, of the [256, K] matrix) and go STRAIGHT from L2 into registers — wave w owns column tile w, one linear 1 KB load per fragment,
 // OP_DEPTH k-steps ahead, no LDS, no barrier after the staging one.  Per k-step and wave: 2 KB of weights, 4 LDS reads, 6 MFMAs on two
 // independent accumulators (the two 32-row tiles).  The slice count is a constant of the kernel (the order of the partial sums is part
 // of a row's result: any batch composition gives the same bits); the LayerNorm that follows sums the slices.
@@ -677,7 +677,7 @@ __global__ __launch_bounds__(512, 1) void outproj_split_kernel(int M, const floa
 #define OP_NS 6
 int fd_outproj_split_supported(int N, int K) { return N == 256 && K == OP_KSL * OP_NS * 16; }
 int fd_outproj_split_slices() { return OP_NS; }
-// parts[z][M, ldo], z < fd_outproj_split_slices(): w_hi / w_lo = fd_chain_build_image / _lo of the [256, K] weight matrix
+// parts[z][M, ldo], z < fd_outproj_split_slices(): w_hi / w_lo = fd_chain_build_image(.., lo = 0 / 1) of the [256, K] weight matrix
 int fd_outproj_split(int M, int N, int K, const float* A, int lda, const void* w_hi, const void* w_lo, const float* bias, const float* rowmask,
                      float* parts, long part_stride, int ldo, hipStream_t st) {
   if (M <= 0 || !fd_outproj_split_supported(N, K) || (lda & 3) || (ldo & 3) || (part_stride & 3) || !w_hi || !w_lo) return FDIPT_EINVAL;

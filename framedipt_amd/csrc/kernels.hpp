@@ -140,7 +140,7 @@ struct ET2Args {
   const float *b2, *gamma, *beta, *res_mask;
   float* trace;         // optional [B,N,N,128] f32
   // optional: pair bias of the NEXT block's attention, linear_b(z') / sqrt(3), emitted from the LayerNorm epilogue
-  const void* wb_img;   // fd_chain_build_image_scaled(Wb, H, 128, permuted) of the next block (8 KB), or NULL
+  const void* wb_img;   // linear_b of the next block (fd_et3_build_bias_image / fd_et4_build_bias_image), or NULL
   const float* bb;      // [H] pre-scaled bias of linear_b
   float* bias_out;      // fragment order (fd_bias_frag_off)
   int H;
@@ -151,7 +151,7 @@ struct ET2Args {
   unsigned long long* clock = nullptr;  // optional shader-clock probe (FdiptForwardArgs.clock_out)
   // optional (edge_transition4 with wb_img set; round 6): pair_z = down_z(z') + b of the NEXT block's IPA (ipa_pytorch.py:158,318) from the
   // same epilogue, as the image opair_pz_kernel reads (fd_pz_bytes): 64 B per pair instead of a second pass over the 256 B of z'
-  const void* wdz_img = nullptr;     // (edge_embed2 only) down_z [32, 128] as a fragment image, k in hand-off order (fd_chain_build_image_ex(.., permuted = 1, lo = 0));
+  const void* wdz_img = nullptr;     // (edge_embed2 only) down_z [32, 128] as a fragment image, k in hand-off order (fd_chain_build_image(.., permuted = 1, lo = 0));
   const void* wdz_img_lo = nullptr;  // ... of Wdz - half(Wdz) (lo = 1).  edge_transition4 finds both in the last chunk of its weight stream (fd_et4_set_dz)
   const float* bdz = nullptr;        // [32]
   half_t* pz_out = nullptr;          // [B*N][N/4][32][4]
@@ -270,7 +270,7 @@ struct SeqInitExtra {  // once-per-forward fills folded into the sequence-image 
 // stream != 0: the images are read by the key-streaming kernel (N <= 2048), as fd_seq_attention_run(.., stream)
 int fd_seq_images_init(int B, int N, int H, const float* res_mask, void* images, const SeqInitExtra& x, hipStream_t st, int stream = 0);
 int fd_seq_qkv_supported(int N, int H, int d_model);
-// wimg_lo != NULL: split operands (image of W - half(W), fd_chain_build_image_lo)
+// wimg_lo != NULL: split operands (image of W - half(W), fd_chain_build_image(.., lo = 1))
 int fd_seq_qkv(int B, int N, int H, const float* x, int ld_x, const void* wimg, const void* wimg_lo, const float* bias, float scale,
                void* images, hipStream_t st);
 int fd_seq_attention_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm* warm, hipStream_t st,
@@ -287,7 +287,7 @@ struct RowBlockArgs {
   const float* in = nullptr;
   int ld_in = 0;
   const void *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
-  const void *w0l = nullptr, *w1l = nullptr, *w2l = nullptr;  // *_SPLIT kinds: images of W - half(W) (fd_chain_build_image_lo)
+  const void *w0l = nullptr, *w1l = nullptr, *w2l = nullptr;  // *_SPLIT kinds: images of W - half(W) (fd_chain_build_image(.., lo = 1))
   const float *b0 = nullptr, *b1 = nullptr, *b2 = nullptr;
   const float* residual = nullptr;  // or NULL
   int ld_res = 0;
@@ -328,8 +328,8 @@ int fd_torsion16(const RowBlockArgs& a, hipStream_t st);             // FD_RB_TO
 struct TfmrTailArgs {
   int M, ld;                      // rows; common row stride of att / x / out (d_model = 320)
   const float *att, *x;           // attention output rows, layer input rows (residual)
-  const void *wo, *w1, *w2;       // fragment images, natural k order (fd_chain_build_image(.., 0))
-  const void *wol = nullptr, *w1l = nullptr, *w2l = nullptr, *wpl = nullptr;  // split operands: lo images (fd_chain_build_image_lo); wol selects the split kernel
+  const void *wo, *w1, *w2;       // fragment images, natural k order (fd_chain_build_image(.., permuted = 0, ..))
+  const void *wol = nullptr, *w1l = nullptr, *w2l = nullptr, *wpl = nullptr;  // split operands: lo images (fd_chain_build_image(.., lo = 1)); wol selects the split kernel
   const float *bo, *g1, *be1, *b1, *b2, *g2, *be2;
   float* out;                     // must not alias x
   // optional (last layer of the stack): post_tfmr (Linear 320 -> 256, fragment image wp, bias bp) + residual rows pres on the
@@ -364,11 +364,8 @@ struct ChainArgs {
 // the chain kinds the forward runs where the row-block kernels (rowblock.hip) do not take the layers (FDIPT_KF_UNFOLDED, generic pair path)
 enum { FD_CHAIN_POST, FD_CHAIN_ETINIT };
 size_t fd_chain_image_bytes(int N, int K);
-int fd_chain_build_image(const float* w, int N, int K, int ldw, int permuted, void* img, hipStream_t st);
-// the same for W - half(W): the lo part of a weight matrix used as split operands (hi image + lo image = 22 significant bits)
-int fd_chain_build_image_lo(const float* w, int N, int K, int ldw, void* img, hipStream_t st);
-int fd_chain_build_image_scaled(const float* w, int N, int K, int ldw, int permuted, float scale, void* img, hipStream_t st);
-int fd_chain_build_image_ex(const float* w, int N, int K, int ldw, int permuted, int lo, void* img, hipStream_t st);  // any (k order, part)
+// lo = 1: the image of W - half(W), the lo part of a weight matrix used as split operands (hi image + lo image = 22 significant bits)
+int fd_chain_build_image(const float* w, int N, int K, int ldw, int permuted, int lo, void* img, hipStream_t st);
 int fd_chain(int kind, const ChainArgs& a, hipStream_t st);
 
 int fd_linear(int precision, int M, int N, int K, const float* A, int lda, const void* W, int ldw, const float* bias,

@@ -12,8 +12,6 @@
 #include "common.hpp"
 #include "kernels.hpp"
 
-// shapes of tfmr_tail16_kernel: d_model 320, c_s 256 (the reference widths)
-template <class IV> static bool tail16_shapes(const FdiptDims* d, const IV& iv) { return iv.d_t == 320 && d->c_s == 256; }
 // ------------------------------------------------------------------ inventory (== framedipt_amd/weights.py)
 struct LinW { long w, b; int out, in; };
 struct LNW { long g, b; int d; };
@@ -94,16 +92,20 @@ static void build_inventory(const FdiptDims* d, Inventory& iv) {
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int rup8(int x) { return (x + 7) & ~7; }
 
+// A run: images reserved back to back, which an L2 warm-up touches as one range from its first member; *_run is its length in bytes
 struct DSplit {  // lo images (W - half(W)) of the node-path layers that run on split operands (rowblock.hip, attention_seq.hip)
   size_t inp[FD_MAX_TL], outp[FD_MAX_TL], l1[FD_MAX_TL], l2[FD_MAX_TL], post, t1, t2, t3, et_init, r4w;
   // 16-row images (fd_chain_build_image16) of the tail's matrices, hi then lo: out_proj, FFN 1, FFN 2 per layer, post_tfmr
   size_t o16[FD_MAX_TL][2], f16[FD_MAX_TL][2], g16[FD_MAX_TL][2], p16[2];
-  size_t tr16[3][2];  // ... of the transition's three matrices (transition16_kernel): hi run t1 | t2 | t3, then the lo run
-  size_t ei16[2], r416[2];  // ... of EdgeTransition's initial_embed and fold-row matrix r4w (rows folded into the transition launch): hi run, lo run
+  size_t tr16[3][2];  // ... of the transition's three matrices (transition16_kernel)
+  size_t ei16[2], r416[2];  // ... of EdgeTransition's initial_embed and fold-row matrix r4w (rows folded into the transition launch)
+  // runs, hi and lo alike: o16 | f16 | g16 of layer l (the last layer's ends with p16); tr16 t1 | t2 | t3; ei16 | r416; lo t1 | t2 | t3;
+  // lo et_init | r4w
+  unsigned tail16_run[FD_MAX_TL], tr16_run, et16_run, t_run, et_run;
 };
-struct DChain {  // weight images of the fused node-path chains (chain.hip) of one trunk block
-  size_t skip, inp[FD_MAX_TL], outp[FD_MAX_TL], l1[FD_MAX_TL], l2[FD_MAX_TL], l2n[FD_MAX_TL], post, t1, t2, t3, t2n, t3n, et_init, a1, af, a1af, b1f, r4w, r4b;
-  // l2: k-permuted (register chaining in chain.hip); l2n: natural k order (rowblock.hip, hidden rows go through LDS)
+struct DChain {  // weight images of the fused node-path chains (chain.hip, rowblock.hip: natural k order) of one trunk block
+  size_t inp[FD_MAX_TL], outp[FD_MAX_TL], l1[FD_MAX_TL], l2[FD_MAX_TL], post, t1, t2, t3, et_init, a1af, b1f, r4w, r4b;
+  unsigned t23_run;  // run t2 | t3
 };
 struct DBlock { size_t wq_m, wproj2_img, wproj2_img_lo, bproj2, wproj2p_img, wproj2p_img_lo, bproj2p, wout_m, bout_m, wout_img, wout_img_lo, wproj, wproj_img, wproj_img_lo, bproj, gamma, wb, bb, wb_img3, wb_img4, et3, et4, wdz_t, wdz_img, wdz_img_lo, wdz_imgp, wdz_imgp_lo; DChain ch; DSplit lo; };
 struct DLayout {
@@ -112,10 +114,10 @@ struct DLayout {
   size_t w1i, w1j, w1r, dtab, edges, b1;  // fp32 pieces of the concat-free first edge-embedder layer
   size_t ee2;         // LDS images of edge-embedder layers 2/3 (register-resident bf16 kernel)
   size_t ch_ne0, ch_ne2, ch_ne4, ch_tor1, ch_tor2;  // chain images: node embedder, torsion head
-  size_t ch_ne2n, ch_ne4n, ch_tor2n;                // ... natural k order (rowblock.hip)
   size_t lo_ne0, lo_ne2, lo_ne4, lo_tor1, lo_tor2;  // lo images: node embedder, torsion head
   size_t skip16[2];                                 // ... of the stacked skip_embed matrices [num_blocks * c_skip = 256, c_s] (fused into the node embedder)
   size_t ne16[3][2], tor16[2][2];                   // 16-row images (fd_chain_build_image16; the embedder's first one zero-padded to K = 96), hi / lo
+  unsigned lo_tor_run, ne16_run, tor16_run, skip16_run;  // runs: lo tor1 | tor2; ne16 hi or lo; tor16 hi or lo; skip16 hi | lo
   size_t skip_w32;                                  // ... in fp32 (split operands: the GEMM splits both operands while it stages them)
   size_t skip_w, skip_b;                            // skip_embed of ALL blocks stacked: [num_blocks * c_skip, c_s] operand precision, bias f32
   DBlock blk[FD_MAX_BLOCKS];
@@ -123,116 +125,39 @@ struct DLayout {
   int kn_pad, d1_pad, esz;
 };
 
-// the register-resident half-precision pair kernels (edge_transition3/4.hip, edge_embed2) are compiled for the reference widths only
+// Conditional groups of derived images.  Each predicate decides both that blob_walk builds the group and that a path of
+// plan_forward may read it.
+// the register-resident half-precision pair kernels (edge_transition3/4.hip, edge_embed2) are compiled for the reference widths only:
+// the edge embedder's LDS images, the EdgeTransition weight streams
 static bool use_regpair(const FdiptDims* d) {
   return d->precision == FDIPT_PREC_HALF && d->c_z == 128 && d->c_s == 256 && !(d->kernel_flags & FDIPT_KF_GENERIC_PAIR);
 }
-
-// fused node-path chains (chain.hip) are compiled for the reference widths only
+// fused node-path kernels (chain.hip, rowblock.hip) are compiled for the reference widths only: their 32-row images, the lo images of
+// split operands and the 16-row images.  (c_s 256, c_skip 64, c_z 128 fix d_t 320, cb 128, hid 384: the shapes of the 16-row kernels)
 static bool use_chain(const FdiptDims* d) {
   return d->precision == FDIPT_PREC_HALF && d->c_s == 256 && d->c_skip == 64 && d->c_z == 128 && !(d->kernel_flags & FDIPT_KF_UNFUSED_NODE);
 }
-
-static void build_layout(const FdiptDims* d, const Inventory& iv, DLayout& L) {
-  size_t o = 0;
-  L.esz = d->precision == FDIPT_PREC_HALF ? 2 : 4;
-  L.kn_pad = rup8(iv.node_in);
-  L.d1_pad = rup8(iv.d1);
-  L.h16_base = o;
-  if (d->precision == FDIPT_PREC_HALF) o = al256(o + (size_t)iv.offsets.back() * 2);
-  L.ne0_pad = o; o = al256(o + (size_t)d->c_s * L.kn_pad * L.esz);
-  L.w1i = o; o = al256(o + (size_t)d->c_z * L.d1_pad * 4);
-  L.w1j = o; o = al256(o + (size_t)d->c_z * L.d1_pad * 4);
-  L.w1r = o; o = al256(o + (size_t)d->c_z * d->index_embed * 4);
-  L.dtab = o; o = al256(o + (size_t)(d->num_bins + 1) * d->c_z * 4);
-  L.edges = o; o = al256(o + (size_t)d->num_bins * 4);
-  L.b1 = o; o = al256(o + (size_t)d->c_z * 4);
-  L.ee2 = o;
-  if (use_regpair(d)) o = al256(o + fd_ee2_image_bytes());
-  for (int b = 0; b < d->num_blocks; ++b) {
-    L.blk[b].wproj = o; o = al256(o + (size_t)iv.proj_out * d->c_s * L.esz);
-    L.blk[b].wproj_img = o;  // the same matrix as a fragment image, zero-padded to whole 128-column blocks (ipa_proj2.hip)
-    if (L.esz == 2 && d->c_s == 256) o = al256(o + (size_t)((iv.proj_out + 127) / 128) * 65536);
-    L.blk[b].wproj_img_lo = o;  // ... and of W - half(W) (split operands)
-    if (L.esz == 2 && d->c_s == 256) o = al256(o + (size_t)((iv.proj_out + 127) / 128) * 65536);
-    L.blk[b].bproj = o; o = al256(o + (size_t)iv.proj_out * 4);
-    // merged IPA projections (ForwardPlan::merged): q' = W_k^T (W_q s + b_q) per head as [H C, c_s] fp32 (+ its bias), the fragment
-    // images of [q' | q_pts | kv_pts] (hi, lo), their biases, and linear_out with W_v folded into its o columns
-    {
-      const int HCm = d->no_heads * d->c_hidden, n2 = iv.proj_out - 2 * HCm;
-      L.blk[b].wq_m = o; o = al256(o + (size_t)HCm * d->c_s * 4);
-      L.blk[b].wproj2_img = o; if (L.esz == 2 && d->c_s == 256) o = al256(o + (size_t)((n2 + 127) / 128) * 65536);
-      L.blk[b].wproj2_img_lo = o; if (L.esz == 2 && d->c_s == 256) o = al256(o + (size_t)((n2 + 127) / 128) * 65536);
-      L.blk[b].bproj2 = o; o = al256(o + (size_t)n2 * 4);
-      // ... the same with the point columns regrouped for the projection's point epilogue (ipa_proj2.hip: fd_ipa_proj2_points_image)
-      const bool pimg = L.esz == 2 && d->c_s == 256 && d->c_hidden == 256 && d->no_heads == 8;
-      const size_t pcols = pimg ? (size_t)fd_ipa_proj2_points_cols(d->no_heads, d->c_hidden) : 0;
-      L.blk[b].wproj2p_img = o; o = al256(o + pcols / 128 * 65536);
-      L.blk[b].wproj2p_img_lo = o; o = al256(o + pcols / 128 * 65536);
-      L.blk[b].bproj2p = o; o = al256(o + pcols * 4);
-      L.blk[b].wout_m = o; o = al256(o + (size_t)d->c_s * iv.feat_dim * 4);
-      L.blk[b].bout_m = o; o = al256(o + (size_t)d->c_s * 4);
-      // ... and the merged linear_out as hi / lo fragment images (gemm.hip: outproj_split_kernel)
-      L.blk[b].wout_img = o; if (fd_outproj_split_supported(d->c_s, iv.feat_dim)) o = al256(o + fd_chain_image_bytes(d->c_s, iv.feat_dim));
-      L.blk[b].wout_img_lo = o; if (fd_outproj_split_supported(d->c_s, iv.feat_dim)) o = al256(o + fd_chain_image_bytes(d->c_s, iv.feat_dim));
-    }
-    L.blk[b].gamma = o; o = al256(o + (size_t)d->no_heads * 4);
-    L.blk[b].wb = o; o = al256(o + (size_t)d->no_heads * d->c_z * L.esz);
-    L.blk[b].bb = o; o = al256(o + (size_t)d->no_heads * 4);
-    L.blk[b].wb_img3 = o; o = al256(o + 4096);  // ... as 16 x 128 (edge_transition3 epilogue)
-    L.blk[b].wb_img4 = o; o = al256(o + 8192);  // ... compact (8 head rows: 2 KB) in the hand-off order of edge_transition4 / edge_embed2
-    L.blk[b].wdz_img = o; o = al256(o + 8192);  // down_z [c_z/4, c_z] as a bf16 fragment image (MFMA o_pair kernel)
-    L.blk[b].wdz_img_lo = o; o = al256(o + 8192);  // ... and of Wdz - half(Wdz)
-    L.blk[b].wdz_imgp = o; o = al256(o + 8192);     // ... both with k in the hand-off order of the LayerNorm epilogues that emit pair_z (round 6)
-    L.blk[b].wdz_imgp_lo = o; o = al256(o + 8192);
-    L.blk[b].wdz_t = o; o = al256(o + (size_t)d->c_z * (d->c_z / 4) * 4);
-    L.blk[b].et3 = o;
-    if (use_regpair(d) && b < d->num_blocks - 1) o = al256(o + fd_et3_stream_bytes());
-    L.blk[b].et4 = o;
-    if (use_regpair(d) && b < d->num_blocks - 1) o = al256(o + fd_et4_stream_bytes());
-    if (use_chain(d)) {
-      DChain& c = L.blk[b].ch;
-      auto img = [&](int n, int k) { size_t r = o; o = al256(o + fd_chain_image_bytes(n, k)); return r; };
-      const int cs = d->c_s, dt = iv.d_t;
-      c.skip = img(d->c_skip, cs);
-      for (int l = 0; l < d->tfmr_layers; ++l) { c.inp[l] = img(3 * dt, dt); c.outp[l] = img(dt, dt); c.l1[l] = img(dt, dt); c.l2[l] = img(dt, dt); c.l2n[l] = img(dt, dt); }
-      c.post = img(cs, dt); c.t1 = img(cs, cs); c.t2 = img(cs, cs); c.t3 = img(cs, cs); c.t2n = img(cs, cs); c.t3n = img(cs, cs);
-      c.et_init = img(iv.cb, cs); c.a1 = img(iv.hid, iv.cb); c.af = img(d->c_z, iv.cb);
-      c.a1af = img(iv.hid + d->c_z, iv.cb);                     // [W1[:, e_i]; Wf[:, e_i]] as one 512-row image (rowblock.hip)
-      c.b1f = o; o = al256(o + (size_t)(iv.hid + d->c_z) * 4);  // [b1; bf]
-      c.r4w = img(2 * (iv.hid + d->c_z), iv.cb);                // [W1[:, e_i]; Wf[:, e_i]; W1[:, e_j]; Wf[:, e_j]] (edge_transition4 rows)
-      c.r4b = o; o = al256(o + (size_t)2 * (iv.hid + d->c_z) * 4);  // [b1; bf; 0; 0]
-    }
-  }
-  if (use_chain(d)) {
-    auto img = [&](int n, int k) { size_t r = o; o = al256(o + fd_chain_image_bytes(n, k)); return r; };
-    const int cs = d->c_s, dt = iv.d_t;
-    for (int b = 0; b < d->num_blocks; ++b) {
-      DSplit& c = L.blk[b].lo;
-      for (int l = 0; l < d->tfmr_layers; ++l) { c.inp[l] = img(3 * dt, dt); c.outp[l] = img(dt, dt); c.l1[l] = img(dt, dt); c.l2[l] = img(dt, dt); }
-      c.post = img(cs, dt); c.t1 = img(cs, cs); c.t2 = img(cs, cs); c.t3 = img(cs, cs);
-      c.et_init = img(iv.cb, cs); c.r4w = img(2 * (iv.hid + d->c_z), iv.cb);
-      for (int h = 0; h < 2; ++h) {
-        for (int l = 0; l < d->tfmr_layers; ++l) { c.o16[l][h] = img(dt, dt); c.f16[l][h] = img(dt, dt); c.g16[l][h] = img(dt, dt); }
-        c.p16[h] = img(cs, dt);
-      }
-      for (int h = 0; h < 2; ++h)
-        for (int i = 0; i < 3; ++i) c.tr16[i][h] = img(cs, cs);
-      for (int h = 0; h < 2; ++h) { c.ei16[h] = img(iv.cb, cs); c.r416[h] = img(2 * (iv.hid + d->c_z), iv.cb); }
-    }
-    L.lo_ne0 = img(cs, L.kn_pad); L.lo_ne2 = img(cs, cs); L.lo_ne4 = img(cs, cs); L.lo_tor1 = img(cs, cs); L.lo_tor2 = img(cs, cs);
-    for (int h = 0; h < 2; ++h) { L.ne16[0][h] = img(cs, 96); L.ne16[1][h] = img(cs, cs); L.ne16[2][h] = img(cs, cs); }
-    for (int h = 0; h < 2; ++h) { L.tor16[0][h] = img(cs, cs); L.tor16[1][h] = img(cs, cs); }
-    for (int h = 0; h < 2; ++h) L.skip16[h] = img(cs, cs);
-    L.ch_ne0 = img(d->c_s, L.kn_pad); L.ch_ne2 = img(d->c_s, d->c_s); L.ch_ne4 = img(d->c_s, d->c_s);
-    L.ch_tor1 = img(d->c_s, d->c_s); L.ch_tor2 = img(d->c_s, d->c_s);
-    L.ch_ne2n = img(d->c_s, d->c_s); L.ch_ne4n = img(d->c_s, d->c_s); L.ch_tor2n = img(d->c_s, d->c_s);
-  }
-  L.skip_w = o; o = al256(o + (size_t)d->num_blocks * d->c_skip * d->c_s * L.esz);
-  L.skip_b = o; o = al256(o + (size_t)d->num_blocks * d->c_skip * 4);
-  L.skip_w32 = o; o = al256(o + (size_t)d->num_blocks * d->c_skip * d->c_s * 4);
-  L.total = o;
+// the stacked skip_embed matrices as 16-row images: a fourth layer of the 16-row node embedder, 256 rows
+static bool skip16_image(const FdiptDims* d) { return use_chain(d) && d->num_blocks * d->c_skip == 256; }
+// the fused IPA projection as fragment images, zero-padded to whole 128-column blocks (ipa_proj2.hip: K = c_s = 256)
+static bool proj_image(const FdiptDims* d) { return d->precision == FDIPT_PREC_HALF && d->c_s == 256; }
+// merged IPA projections (ForwardPlan::merged; the o columns of linear_out keep their width: H c_s = H C): q', its bias and the
+// merged linear_out
+static bool merged_weights(const FdiptDims* d) { return d->c_s == d->c_hidden; }
+// ... the merged projection as fragment images in fd_ipa_proj2's column order
+static bool merged_image(const FdiptDims* d) {
+  return proj_image(d) && merged_weights(d) && d->c_hidden % 128 == 0 && (d->no_heads * d->c_hidden) % 128 == 0;
 }
+// ... with the point columns regrouped for the projection's point epilogue (ipa_proj2.hip: fd_ipa_proj2_points_image)
+static bool points_image(const FdiptDims* d) {
+  return merged_image(d) && d->no_heads == 8 && d->c_hidden == 256 && d->no_qk_points == 8 && d->no_v_points == 12;
+}
+// ... the merged linear_out as hi / lo fragment images (gemm.hip: outproj_split_kernel)
+static bool outproj_image(const FdiptDims* d, const Inventory& iv) { return merged_weights(d) && fd_outproj_split_supported(d->c_s, iv.feat_dim); }
+// linear_b in the fragment order of the epilogues that emit the next block's pair bias (edge_transition3/4, edge_embed2)
+static bool bias_images(const FdiptDims* d) { return d->c_z == 128 && d->no_heads <= 8; }
+// down_z as fragment images (MFMA o_pair kernel; the epilogues that emit pair_z)
+static bool dz_images(const FdiptDims* d) { return d->c_z == 128; }
 
 // ------------------------------------------------------------------ prepare kernels
 // dst[r, c] (ld_dst, operand precision) = scale * src[r, col0 + c] for c < ncols else 0
@@ -324,6 +249,270 @@ __global__ void merge_vo_kernel(int H, int C, int cs, int feat, const float* __r
   }
 }
 
+#define RC(x)                   \
+  do {                          \
+    int rc__ = (x);             \
+    if (rc__) return rc__;      \
+  } while (0)
+
+// ------------------------------------------------------------------ the derived blob, declared once
+// One walk over the blob declares every image once: the condition under which it exists, its size and its build step.  Without a
+// blob (fdipt_derived_bytes, fdipt_sample_setup, the forward) it only sizes the layout; fdipt_model_prepare runs the same walk and
+// launches each build step on the stream as its image is declared, so an image may be built from images declared before it.
+struct Blob {
+  const float* P;
+  char* D;  // nullptr: size only, nothing is launched
+  hipStream_t st;
+  size_t o = 0;
+  int rc = FDIPT_OK;  // the first failed build step (the later ones are skipped)
+  template <class F> void step(bool on, F&& build) {
+    if (on && D && rc == FDIPT_OK) rc = build();
+  }
+  // an image of `bytes` that exists when `on`; returns its offset
+  template <class F> size_t img(bool on, size_t bytes, F&& build) {
+    const size_t at = o;
+    if (on) o = al256(o + bytes);
+    step(on, [&] { return build(D + at); });
+    return at;
+  }
+  size_t img(bool on, size_t bytes) { return img(on, bytes, [](char*) { return FDIPT_OK; }); }  // (written by a later build step)
+  // a run: the images that `members` declares, back to back; returns its length
+  template <class F> unsigned run(F&& members) {
+    const size_t at = o;
+    members();
+    return (unsigned)(o - at);
+  }
+};
+
+static int blob_walk(const FdiptDims* d, const Inventory& iv, DLayout& L, const float* P = nullptr, char* D = nullptr, hipStream_t st = nullptr) {
+  Blob w{P, D, st};
+  L = DLayout{};
+  L.esz = d->precision == FDIPT_PREC_HALF ? 2 : 4;
+  L.kn_pad = rup8(iv.node_in);
+  L.d1_pad = rup8(iv.d1);
+  const int esz = L.esz, cs = d->c_s, cz = d->c_z, E = d->index_embed, H = d->no_heads, C = d->c_hidden, cb = iv.cb, hid = iv.hid;
+  const int nsk = d->num_blocks * d->c_skip;
+  const float s3 = sqrtf(1.0f / 3.0f);
+  auto vec = [&](long src, int n, char* at) { return copy_cols(4, 1, n, n, P + src, n, 0, 1.f, at, st); };  // fp32 vector of P
+  // fragment images of a whole matrix: 32-row (hi or lo) and 16-row (hi or lo)
+  auto chain = [&](const LinW& l, int lo) {
+    return w.img(true, fd_chain_image_bytes(l.out, l.in), [&](char* at) { return fd_chain_build_image(P + l.w, l.out, l.in, l.in, 0, lo, at, st); });
+  };
+  auto chain16 = [&](const LinW& l, int lo) {
+    return w.img(true, fd_chain_image_bytes(l.out, l.in), [&](char* at) { return fd_chain_build_image16(P + l.w, l.out, l.in, l.in, l.in, lo, at, st); });
+  };
+  L.h16_base = w.img(d->precision == FDIPT_PREC_HALF, (size_t)iv.offsets.back() * 2,
+                     [&](char* at) { return fd_f32_to_half(iv.offsets.back(), P, (half_t*)at, st); });
+  // the node embedder's first layer [c_s, kn_pad] in operand precision; fp32 pieces of the concat-free first edge-embedder layer: the e_i,
+  // e_j and relative-position columns, the distogram table [num_bins + 1, c_z] with the bin edges (one launch writes both), the bias
+  L.ne0_pad = w.img(true, (size_t)cs * L.kn_pad * esz,
+                    [&](char* at) { return copy_cols(esz, cs, iv.node_in, L.kn_pad, P + iv.ne0.w, iv.node_in, 0, 1.f, at, st); });
+  L.w1i = w.img(true, (size_t)cz * L.d1_pad * 4, [&](char* at) { return copy_cols(4, cz, iv.d1, L.d1_pad, P + iv.ee0.w, iv.edge_in, 0, 1.f, at, st); });
+  L.w1j = w.img(true, (size_t)cz * L.d1_pad * 4, [&](char* at) { return copy_cols(4, cz, iv.d1, L.d1_pad, P + iv.ee0.w, iv.edge_in, iv.d1, 1.f, at, st); });
+  L.w1r = w.img(true, (size_t)cz * E * 4, [&](char* at) { return copy_cols(4, cz, E, E, P + iv.ee0.w, iv.edge_in, 2 * iv.d1, 1.f, at, st); });
+  L.dtab = w.img(true, (size_t)(d->num_bins + 1) * cz * 4);
+  L.edges = w.img(true, (size_t)d->num_bins * 4, [&](char* at) {
+    hipLaunchKernelGGL(misc_prepare_kernel, dim3(16), dim3(256), 0, st, cz, d->num_bins, iv.edge_in, 2 * iv.d1 + E, P + iv.ee0.w, d->min_bin,
+                       d->max_bin, (float*)(D + L.dtab), (float*)at);
+    FD_CHECK_LAUNCH();
+    return FDIPT_OK;
+  });
+  L.b1 = w.img(true, (size_t)cz * 4, [&](char* at) { return vec(iv.ee0.b, cz, at); });
+  L.ee2 = w.img(use_regpair(d), fd_ee2_image_bytes(), [&](char* at) { return fd_ee2_build_images(P + iv.ee2.w, P + iv.ee4.w, at, st); });
+  for (int b = 0; b < d->num_blocks; ++b) {
+    const BlockW& k = iv.blk[b];
+    DBlock& db = L.blk[b];
+    const bool trunk = b < d->num_blocks - 1;  // an EdgeTransition follows
+    // fused projection [q | kv | q_pts | kv_pts] rows (ipa_pytorch.py:202-239), its bias, and the same matrix as hi / lo fragment
+    // images (tile-major images: stacking row blocks of 32 = concatenation), permuted where fd_ipa_proj2 takes the shapes
+    const LinW* parts[4] = {&k.q, &k.kv, &k.qp, &k.kvp};
+    const int row0[4] = {0, k.q.out, k.q.out + k.kv.out, k.q.out + k.kv.out + k.qp.out};
+    db.wproj = w.img(true, (size_t)iv.proj_out * cs * esz, [&](char* at) {
+      for (int p = 0; p < 4; ++p) RC(copy_cols(esz, parts[p]->out, cs, cs, P + parts[p]->w, cs, 0, 1.f, at + (size_t)row0[p] * cs * esz, st));
+      return FDIPT_OK;
+    });
+    const size_t pib = (size_t)((iv.proj_out + 127) / 128) * 65536, tile = (size_t)(cs / 16) * 1024;
+    auto proj_img = [&](int lo) {
+      return w.img(proj_image(d), pib, [&](char* at) {
+        if (hipMemsetAsync(at, 0, pib, st) != hipSuccess) return FDIPT_ELAUNCH;
+        for (int p = 0; p < 4; ++p) {
+          if (parts[p]->out % 32) return FDIPT_ESIZE;
+          RC(fd_chain_build_image(P + parts[p]->w, parts[p]->out, cs, cs, 0, lo, at + (size_t)(row0[p] / 32) * tile, st));
+        }
+        return C % 128 == 0 && (H * C) % 128 == 0 ? fd_ipa_proj2_permute_image(at, H, C, cs, st) : FDIPT_OK;  // (what fd_ipa_proj2 reads)
+      });
+    };
+    db.wproj_img = proj_img(0);
+    db.wproj_img_lo = proj_img(1);
+    db.bproj = w.img(true, (size_t)iv.proj_out * 4, [&](char* at) {
+      for (int p = 0; p < 4; ++p) RC(vec(parts[p]->b, parts[p]->out, at + (size_t)row0[p] * 4));
+      return FDIPT_OK;
+    });
+    // merged IPA projections (ForwardPlan::merged): q' = W_k^T (W_q s + b_q) per head as [H C, c_s] fp32 — prepare-time scratch, the
+    // source of the merged projection image; merge_qk writes it with the q' part of the bias [q' | q_pts | kv_pts]
+    const int HC = H * C, n2 = iv.proj_out - 2 * HC;
+    db.wq_m = w.img(merged_weights(d), (size_t)HC * cs * 4);
+    db.bproj2 = w.img(merged_weights(d), (size_t)n2 * 4, [&](char* at) {
+      hipLaunchKernelGGL(merge_qk_kernel, dim3(512), dim3(256), 0, st, H, C, cs, P + k.q.w, P + k.q.b, P + k.kv.w, (float*)(D + db.wq_m), (float*)at);
+      FD_CHECK_LAUNCH();
+      RC(vec(k.qp.b, k.qp.out, at + (size_t)HC * 4));
+      return vec(k.kvp.b, k.kvp.out, at + (size_t)(HC + k.qp.out) * 4);
+    });
+    // ... the fragment images of [q' | q_pts | kv_pts] (hi, lo; the parts' rows are whole tiles: the projection images above
+    // refuse the shapes otherwise)
+    const size_t mib = (size_t)((n2 + 127) / 128) * 65536;
+    auto merged_img = [&](int lo) {
+      return w.img(merged_image(d), mib, [&](char* at) {
+        if (hipMemsetAsync(at, 0, mib, st) != hipSuccess) return FDIPT_ELAUNCH;
+        const float* srcs[3] = {(const float*)(D + db.wq_m), P + k.qp.w, P + k.kvp.w};
+        const int rows[3] = {HC, k.qp.out, k.kvp.out};
+        for (int p = 0, r0 = 0; p < 3; r0 += rows[p++]) RC(fd_chain_build_image(srcs[p], rows[p], cs, cs, 0, lo, at + (size_t)(r0 / 32) * tile, st));
+        return fd_ipa_proj2_permute_image_q(at, H, C, cs, st);
+      });
+    };
+    db.wproj2_img = merged_img(0);
+    db.wproj2_img_lo = merged_img(1);
+    // ... the same with the point columns regrouped for the projection's point epilogue (the bias is written with each image)
+    const size_t pcols = (size_t)fd_ipa_proj2_points_cols(H, C);
+    db.bproj2p = w.img(points_image(d), pcols * 4);
+    db.wproj2p_img = w.img(points_image(d), pcols / 128 * 65536, [&](char* at) {
+      return fd_ipa_proj2_points_image(D + db.wproj2_img, (const float*)(D + db.bproj2), at, (float*)(D + db.bproj2p), H, C, cs, st);
+    });
+    db.wproj2p_img_lo = w.img(points_image(d), pcols / 128 * 65536, [&](char* at) {
+      return fd_ipa_proj2_points_image(D + db.wproj2_img_lo, (const float*)(D + db.bproj2), at, (float*)(D + db.bproj2p), H, C, cs, st);
+    });
+    // ... linear_out with W_v folded into its o columns (merge_vo writes it with its bias), and as hi / lo fragment images
+    db.wout_m = w.img(merged_weights(d), (size_t)cs * iv.feat_dim * 4);
+    db.bout_m = w.img(merged_weights(d), (size_t)cs * 4, [&](char* at) {
+      hipLaunchKernelGGL(merge_vo_kernel, dim3(512), dim3(256), 0, st, H, C, cs, iv.feat_dim, P + k.out.w, P + k.out.b, P + k.kv.w, P + k.kv.b,
+                         (float*)(D + db.wout_m), (float*)at);
+      FD_CHECK_LAUNCH();
+      return FDIPT_OK;
+    });
+    auto outproj_img = [&](int lo) {
+      return w.img(outproj_image(d, iv), fd_chain_image_bytes(cs, iv.feat_dim), [&](char* at) {
+        return fd_chain_build_image((const float*)(D + db.wout_m), cs, iv.feat_dim, iv.feat_dim, 0, lo, at, st);
+      });
+    };
+    db.wout_img = outproj_img(0);
+    db.wout_img_lo = outproj_img(1);
+    db.gamma = w.img(true, (size_t)H * 4, [&](char* at) {
+      hipLaunchKernelGGL(gamma_kernel, dim3(1), dim3(64), 0, st, H, d->no_qk_points, P + k.head_w, (float*)at);
+      FD_CHECK_LAUNCH();
+      return FDIPT_OK;
+    });
+    // pair bias pre-scaled by sqrt(1/3) (ipa_pytorch.py:256-257); linear_b as 16 x 128 (edge_transition3 epilogue) and compact (8 head
+    // rows: 2 KB) in the hand-off order of edge_transition4 / edge_embed2
+    db.wb = w.img(true, (size_t)H * cz * esz, [&](char* at) { return copy_cols(esz, H, cz, cz, P + k.lb.w, cz, 0, s3, at, st); });
+    db.bb = w.img(true, (size_t)H * 4, [&](char* at) { return copy_cols(4, 1, H, H, P + k.lb.b, H, 0, s3, at, st); });
+    db.wb_img3 = w.img(bias_images(d), 4096, [&](char* at) { return fd_et3_build_bias_image(P + k.lb.w, H, s3, at, st); });
+    db.wb_img4 = w.img(bias_images(d), 8192, [&](char* at) { return fd_et4_build_bias_image(P + k.lb.w, H, s3, at, st); });
+    // down_z [c_z/4, c_z] as fragment images (MFMA o_pair kernel), of Wdz and of Wdz - half(Wdz), then both with k in the hand-off order
+    // of the LayerNorm epilogues that emit pair_z; the emitting EdgeTransition (the previous block's) finds them in the last chunk of its
+    // weight stream
+    auto dz_img = [&](int permuted, int lo) {
+      return w.img(dz_images(d), fd_chain_image_bytes(cz / 4, cz), [&](char* at) { return fd_chain_build_image(P + k.dz.w, cz / 4, cz, cz, permuted, lo, at, st); });
+    };
+    db.wdz_img = dz_img(0, 0);
+    db.wdz_img_lo = dz_img(0, 1);
+    db.wdz_imgp = dz_img(1, 0);
+    db.wdz_imgp_lo = dz_img(1, 1);
+    w.step(b > 0 && use_regpair(d), [&] { return fd_et4_set_dz(D + L.blk[b - 1].et4, D + db.wdz_imgp, D + db.wdz_imgp_lo, st); });
+    db.wdz_t = w.img(true, (size_t)cz * (cz / 4) * 4, [&](char* at) {  // (transposed for coalesced reads in opair_kernel)
+      hipLaunchKernelGGL(transpose_kernel, dim3(16), dim3(256), 0, st, cz / 4, cz, P + k.dz.w, (float*)at);
+      FD_CHECK_LAUNCH();
+      return FDIPT_OK;
+    });
+    db.et3 = w.img(use_regpair(d) && trunk, fd_et3_stream_bytes(), [&](char* at) { return fd_et3_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, at, st); });
+    db.et4 = w.img(use_regpair(d) && trunk, fd_et4_stream_bytes(), [&](char* at) { return fd_et4_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, at, st); });
+    if (!use_chain(d)) continue;
+    // ---- the fused node path: 32-row images (hi), lo images of the split operands, 16-row images (hi, lo)
+    // [W1[:, e_i]; Wf[:, e_i]; W1[:, e_j]; Wf[:, e_j]] of EdgeTransition's first / final layers, the first `parts` of them stacked
+    // (tile-major images: stacking = concatenation)
+    auto et_rows = [&](int parts, int rows16, int lo) {
+      return w.img(trunk, fd_chain_image_bytes(parts / 2 * (hid + cz), cb), [&](char* at) {
+        const float* src[4] = {P + k.et1.w + cz, P + k.etf.w + cz, P + k.et1.w + cz + cb, P + k.etf.w + cz + cb};
+        for (int p = 0; p < parts; at += fd_chain_image_bytes(p % 2 ? cz : hid, cb), ++p)
+          RC(rows16 ? fd_chain_build_image16(src[p], p % 2 ? cz : hid, cb, cb, hid, lo, at, st)
+                    : fd_chain_build_image(src[p], p % 2 ? cz : hid, cb, hid, 0, lo, at, st));
+        return FDIPT_OK;
+      });
+    };
+    DChain& c = db.ch;
+    for (int l = 0; l < d->tfmr_layers; ++l) {
+      c.inp[l] = chain(k.tf[l].inp, 0); c.outp[l] = chain(k.tf[l].outp, 0); c.l1[l] = chain(k.tf[l].l1, 0); c.l2[l] = chain(k.tf[l].l2, 0);
+    }
+    c.post = chain(k.post, 0);
+    c.t1 = chain(k.t1, 0);
+    c.t23_run = w.run([&] { c.t2 = chain(k.t2, 0); c.t3 = chain(k.t3, 0); });
+    if (trunk) {
+      c.et_init = chain(k.et_init, 0);
+      c.a1af = et_rows(2, 0, 0);  // [A1 | Af] rows (rowblock.hip) and their biases [b1; bf]
+      c.b1f = w.img(true, (size_t)(hid + cz) * 4, [&](char* at) {
+        RC(vec(k.et1.b, hid, at));
+        return vec(k.etf.b, cz, at + (size_t)hid * 4);
+      });
+      c.r4w = et_rows(4, 0, 0);  // edge_transition4 rows, one 1024-row image, and their biases [b1; bf; 0; 0]
+      c.r4b = w.img(true, (size_t)2 * (hid + cz) * 4, [&](char* at) {
+        RC(vec(k.et1.b, hid, at));
+        RC(vec(k.etf.b, cz, at + (size_t)hid * 4));
+        return hipMemsetAsync(at + (size_t)(hid + cz) * 4, 0, (size_t)(hid + cz) * 4, st) == hipSuccess ? FDIPT_OK : FDIPT_ELAUNCH;
+      });
+    }
+    DSplit& s = db.lo;
+    for (int l = 0; l < d->tfmr_layers; ++l) {
+      s.inp[l] = chain(k.tf[l].inp, 1); s.outp[l] = chain(k.tf[l].outp, 1); s.l1[l] = chain(k.tf[l].l1, 1); s.l2[l] = chain(k.tf[l].l2, 1);
+    }
+    s.post = chain(k.post, 1);
+    s.t_run = w.run([&] { s.t1 = chain(k.t1, 1); s.t2 = chain(k.t2, 1); s.t3 = chain(k.t3, 1); });
+    if (trunk) s.et_run = w.run([&] { s.et_init = chain(k.et_init, 1); s.r4w = et_rows(4, 0, 1); });
+    for (int h = 0; h < 2; ++h) {
+      for (int l = 0; l < d->tfmr_layers; ++l)
+        s.tail16_run[l] = w.run([&] {
+          s.o16[l][h] = chain16(k.tf[l].outp, h); s.f16[l][h] = chain16(k.tf[l].l1, h); s.g16[l][h] = chain16(k.tf[l].l2, h);
+          if (l + 1 == d->tfmr_layers) s.p16[h] = chain16(k.post, h);
+        });
+      s.tr16_run = w.run([&] { s.tr16[0][h] = chain16(k.t1, h); s.tr16[1][h] = chain16(k.t2, h); s.tr16[2][h] = chain16(k.t3, h); });
+      // (mlp16_kernel<.., ETR>: the transition launch that folds EdgeTransition's row launch in)
+      if (trunk) s.et16_run = w.run([&] { s.ei16[h] = chain16(k.et_init, h); s.r416[h] = et_rows(4, 1, h); });
+    }
+  }
+  if (use_chain(d)) {  // node embedder and torsion head (iv.node_in <= 96: index_embed 32)
+    auto ne0 = [&](int lo) {
+      return w.img(true, fd_chain_image_bytes(cs, L.kn_pad), [&](char* at) { return fd_chain_build_image(P + iv.ne0.w, cs, iv.node_in, iv.node_in, 0, lo, at, st); });
+    };
+    L.lo_ne0 = ne0(1); L.lo_ne2 = chain(iv.ne2, 1); L.lo_ne4 = chain(iv.ne4, 1);
+    L.lo_tor_run = w.run([&] { L.lo_tor1 = chain(iv.tor1, 1); L.lo_tor2 = chain(iv.tor2, 1); });
+    for (int h = 0; h < 2; ++h)
+      L.ne16_run = w.run([&] {
+        L.ne16[0][h] = w.img(true, fd_chain_image_bytes(cs, 96), [&](char* at) { return fd_chain_build_image16(P + iv.ne0.w, cs, iv.node_in, 96, iv.node_in, h, at, st); });
+        L.ne16[1][h] = chain16(iv.ne2, h); L.ne16[2][h] = chain16(iv.ne4, h);
+      });
+    for (int h = 0; h < 2; ++h) L.tor16_run = w.run([&] { L.tor16[0][h] = chain16(iv.tor1, h); L.tor16[1][h] = chain16(iv.tor2, h); });
+    L.ch_ne0 = ne0(0); L.ch_ne2 = chain(iv.ne2, 0); L.ch_ne4 = chain(iv.ne4, 0); L.ch_tor1 = chain(iv.tor1, 0); L.ch_tor2 = chain(iv.tor2, 0);
+  }
+  // skip_embed of all blocks stacked, in operand precision, its bias, in fp32, and as 16-row images (from the fp32 one)
+  auto skip = [&](int e, int bias) {
+    return w.img(true, (size_t)nsk * (bias ? 1 : cs) * e, [&](char* at) {
+      for (int b = 0; b < d->num_blocks; ++b) {
+        const LinW& l = iv.blk[b].skip;
+        RC(bias ? vec(l.b, l.out, at + (size_t)b * l.out * 4) : copy_cols(e, l.out, cs, cs, P + l.w, cs, 0, 1.f, at + (size_t)b * l.out * cs * e, st));
+      }
+      return FDIPT_OK;
+    });
+  };
+  L.skip_w = skip(esz, 0);
+  L.skip_b = skip(4, 1);
+  L.skip_w32 = skip(4, 0);
+  L.skip16_run = w.run([&] {
+    for (int h = 0; h < 2; ++h)
+      L.skip16[h] = w.img(skip16_image(d), fd_chain_image_bytes(nsk, cs),
+                          [&](char* at) { return fd_chain_build_image16((const float*)(D + L.skip_w32), nsk, cs, cs, cs, h, at, st); });
+  });
+  L.total = w.o;
+  return w.rc;
+}
+
 extern "C" {
 
 int fdipt_param_count(const FdiptDims* dims) {
@@ -346,224 +535,16 @@ size_t fdipt_derived_bytes(const FdiptDims* dims) {
   Inventory iv;
   DLayout L;
   build_inventory(dims, iv);
-  build_layout(dims, iv, L);
+  blob_walk(dims, iv, L);
   return L.total;
 }
 
 int fdipt_model_prepare(const FdiptDims* d, const float* P, void* derived, fdipt_stream_t stream) {
   if (!dims_ok(d) || !P || !derived) return FDIPT_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
   Inventory iv;
   DLayout L;
   build_inventory(d, iv);
-  build_layout(d, iv, L);
-  char* D = (char*)derived;
-  int rc;
-  if (d->precision == FDIPT_PREC_HALF)
-    if ((rc = fd_f32_to_half(iv.offsets.back(), P, (half_t*)(D + L.h16_base), st))) return rc;
-  const int cs = d->c_s, cz = d->c_z, E = d->index_embed, H = d->no_heads, C = d->c_hidden;
-  if ((rc = copy_cols(L.esz, cs, iv.node_in, L.kn_pad, P + iv.ne0.w, iv.node_in, 0, 1.f, D + L.ne0_pad, st))) return rc;
-  if ((rc = copy_cols(4, cz, iv.d1, L.d1_pad, P + iv.ee0.w, iv.edge_in, 0, 1.f, D + L.w1i, st))) return rc;
-  if ((rc = copy_cols(4, cz, iv.d1, L.d1_pad, P + iv.ee0.w, iv.edge_in, iv.d1, 1.f, D + L.w1j, st))) return rc;
-  if ((rc = copy_cols(4, cz, E, E, P + iv.ee0.w, iv.edge_in, 2 * iv.d1, 1.f, D + L.w1r, st))) return rc;
-  hipLaunchKernelGGL(misc_prepare_kernel, dim3(16), dim3(256), 0, st, cz, d->num_bins, iv.edge_in, 2 * iv.d1 + E,
-                     P + iv.ee0.w, d->min_bin, d->max_bin, (float*)(D + L.dtab), (float*)(D + L.edges));
-  FD_CHECK_LAUNCH();
-  if ((rc = copy_cols(4, 1, cz, cz, P + iv.ee0.b, cz, 0, 1.f, D + L.b1, st))) return rc;
-  if (use_regpair(d))
-    if ((rc = fd_ee2_build_images(P + iv.ee2.w, P + iv.ee4.w, D + L.ee2, st))) return rc;
-  const float s3 = sqrtf(1.0f / 3.0f);
-  for (int b = 0; b < d->num_blocks; ++b) {
-    const BlockW& k = iv.blk[b];
-    const DBlock& db = L.blk[b];
-    // fused projection [q | kv | q_pts | kv_pts] rows (ipa_pytorch.py:202-239)
-    if ((rc = copy_cols(L.esz, d->c_skip, cs, cs, P + k.skip.w, cs, 0, 1.f, D + L.skip_w + (size_t)b * d->c_skip * cs * L.esz, st)) ||
-        (rc = copy_cols(4, d->c_skip, cs, cs, P + k.skip.w, cs, 0, 1.f, D + L.skip_w32 + (size_t)b * d->c_skip * cs * 4, st)) ||
-        (rc = copy_cols(4, 1, d->c_skip, d->c_skip, P + k.skip.b, d->c_skip, 0, 1.f, D + L.skip_b + (size_t)b * d->c_skip * 4, st)))
-      return rc;
-    const LinW* parts[4] = {&k.q, &k.kv, &k.qp, &k.kvp};
-    long row = 0;
-    const bool proj_img = L.esz == 2 && cs == 256;
-    if (proj_img && (hipMemsetAsync(D + db.wproj_img, 0, (size_t)((iv.proj_out + 127) / 128) * 65536, st) != hipSuccess ||
-                     hipMemsetAsync(D + db.wproj_img_lo, 0, (size_t)((iv.proj_out + 127) / 128) * 65536, st) != hipSuccess))
-      return FDIPT_ELAUNCH;
-    for (int p = 0; p < 4; ++p) {
-      // (tile-major images: stacking row blocks of 32 = concatenation)
-      if (proj_img && (parts[p]->out % 32 || (rc = fd_chain_build_image(P + parts[p]->w, parts[p]->out, cs, cs, 0,
-                                                                         D + db.wproj_img + (size_t)(row / 32) * (cs / 16) * 1024, st)) ||
-                       (rc = fd_chain_build_image_lo(P + parts[p]->w, parts[p]->out, cs, cs,
-                                                     D + db.wproj_img_lo + (size_t)(row / 32) * (cs / 16) * 1024, st))))
-        return rc ? rc : FDIPT_ESIZE;
-      if ((rc = copy_cols(L.esz, parts[p]->out, cs, cs, P + parts[p]->w, cs, 0, 1.f, D + db.wproj + row * cs * L.esz, st)))
-        return rc;
-      if ((rc = copy_cols(4, 1, parts[p]->out, parts[p]->out, P + parts[p]->b, parts[p]->out, 0, 1.f,
-                          D + db.bproj + row * 4, st)))
-        return rc;
-      row += parts[p]->out;
-    }
-    // (only shapes fd_ipa_proj2_supported accepts ever read the image)
-    if (proj_img && C % 128 == 0 && (H * C) % 128 == 0 &&
-        ((rc = fd_ipa_proj2_permute_image(D + db.wproj_img, H, C, cs, st)) || (rc = fd_ipa_proj2_permute_image(D + db.wproj_img_lo, H, C, cs, st))))
-      return rc;
-    if (cs == C) {  // merged projections (the o columns of linear_out keep their width: H cs = H C)
-      hipLaunchKernelGGL(merge_qk_kernel, dim3(512), dim3(256), 0, st, H, C, cs, P + k.q.w, P + k.q.b, P + k.kv.w, (float*)(D + db.wq_m),
-                         (float*)(D + db.bproj2));
-      hipLaunchKernelGGL(merge_vo_kernel, dim3(512), dim3(256), 0, st, H, C, cs, iv.feat_dim, P + k.out.w, P + k.out.b, P + k.kv.w, P + k.kv.b,
-                         (float*)(D + db.wout_m), (float*)(D + db.bout_m));
-      FD_CHECK_LAUNCH();
-      if (fd_outproj_split_supported(cs, iv.feat_dim) &&
-          ((rc = fd_chain_build_image((const float*)(D + db.wout_m), cs, iv.feat_dim, iv.feat_dim, 0, D + db.wout_img, st)) ||
-           (rc = fd_chain_build_image_lo((const float*)(D + db.wout_m), cs, iv.feat_dim, iv.feat_dim, D + db.wout_img_lo, st))))
-        return rc;
-      const int HCm = H * C, n2 = iv.proj_out - 2 * HCm;
-      if ((rc = copy_cols(4, 1, k.qp.out, k.qp.out, P + k.qp.b, k.qp.out, 0, 1.f, D + db.bproj2 + (size_t)HCm * 4, st)) ||
-          (rc = copy_cols(4, 1, k.kvp.out, k.kvp.out, P + k.kvp.b, k.kvp.out, 0, 1.f, D + db.bproj2 + (size_t)(HCm + k.qp.out) * 4, st)))
-        return rc;
-      if (proj_img && C % 128 == 0 && HCm % 128 == 0 && k.qp.out % 32 == 0 && k.kvp.out % 32 == 0) {
-        const size_t ib = (size_t)((n2 + 127) / 128) * 65536, tile = (size_t)(cs / 16) * 1024;
-        if (hipMemsetAsync(D + db.wproj2_img, 0, ib, st) != hipSuccess || hipMemsetAsync(D + db.wproj2_img_lo, 0, ib, st) != hipSuccess) return FDIPT_ELAUNCH;
-        const float* srcs[3] = {(const float*)(D + db.wq_m), P + k.qp.w, P + k.kvp.w};
-        const int rows[3] = {HCm, k.qp.out, k.kvp.out};
-        long r0 = 0;
-        for (int p3 = 0; p3 < 3; ++p3) {  // (tile-major images: stacking row blocks of 32 = concatenation)
-          if ((rc = fd_chain_build_image(srcs[p3], rows[p3], cs, cs, 0, D + db.wproj2_img + (size_t)(r0 / 32) * tile, st)) ||
-              (rc = fd_chain_build_image_lo(srcs[p3], rows[p3], cs, cs, D + db.wproj2_img_lo + (size_t)(r0 / 32) * tile, st)))
-            return rc;
-          r0 += rows[p3];
-        }
-        if ((rc = fd_ipa_proj2_permute_image_q(D + db.wproj2_img, H, C, cs, st)) || (rc = fd_ipa_proj2_permute_image_q(D + db.wproj2_img_lo, H, C, cs, st)))
-          return rc;
-        if (H == 8 && C == 256 && cs == 256 && d->no_qk_points == 8 && d->no_v_points == 12 &&
-            ((rc = fd_ipa_proj2_points_image(D + db.wproj2_img, (const float*)(D + db.bproj2), D + db.wproj2p_img, (float*)(D + db.bproj2p), H, C, cs, st)) ||
-             (rc = fd_ipa_proj2_points_image(D + db.wproj2_img_lo, (const float*)(D + db.bproj2), D + db.wproj2p_img_lo, (float*)(D + db.bproj2p), H, C, cs, st))))
-          return rc;
-      }
-    }
-    hipLaunchKernelGGL(gamma_kernel, dim3(1), dim3(64), 0, st, H, d->no_qk_points, P + k.head_w, (float*)(D + db.gamma));
-    FD_CHECK_LAUNCH();
-    // pair bias pre-scaled by sqrt(1/3) (ipa_pytorch.py:256-257)
-    if ((rc = copy_cols(L.esz, H, cz, cz, P + k.lb.w, cz, 0, s3, D + db.wb, st))) return rc;
-    if ((rc = copy_cols(4, 1, H, H, P + k.lb.b, H, 0, s3, D + db.bb, st))) return rc;
-    if (cz == 128 && H <= 8)
-      if ((rc = fd_et3_build_bias_image(P + k.lb.w, H, s3, D + db.wb_img3, st)) ||
-          (rc = fd_et4_build_bias_image(P + k.lb.w, H, s3, D + db.wb_img4, st)))
-        return rc;
-    hipLaunchKernelGGL(transpose_kernel, dim3(16), dim3(256), 0, st, cz / 4, cz, P + k.dz.w, (float*)(D + db.wdz_t));
-    FD_CHECK_LAUNCH();
-    if (cz == 128 && ((rc = fd_chain_build_image(P + k.dz.w, cz / 4, cz, cz, 0, D + db.wdz_img, st)) ||
-                      (rc = fd_chain_build_image_lo(P + k.dz.w, cz / 4, cz, cz, D + db.wdz_img_lo, st)) ||
-                      (rc = fd_chain_build_image_ex(P + k.dz.w, cz / 4, cz, cz, 1, 0, D + db.wdz_imgp, st)) ||
-                      (rc = fd_chain_build_image_ex(P + k.dz.w, cz / 4, cz, cz, 1, 1, D + db.wdz_imgp_lo, st))))
-      return rc;
-    // ... which ride in the last chunk of the PREVIOUS block's EdgeTransition weight stream (its epilogue emits this block's pair_z; the
-    // stream itself is built in that block's iteration, below: same stream, in order)
-    if (b > 0 && cz == 128 && use_regpair(d) && (rc = fd_et4_set_dz(D + L.blk[b - 1].et4, D + db.wdz_imgp, D + db.wdz_imgp_lo, st))) return rc;
-    if (use_regpair(d) && b < d->num_blocks - 1)
-      if ((rc = fd_et3_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, D + db.et3, st)) ||
-          (rc = fd_et4_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, D + db.et4, st)))
-        return rc;
-    if (use_chain(d)) {
-      const DChain& c = db.ch;
-      auto bi = [&](const LinW& l, int perm, size_t off) { return fd_chain_build_image(P + l.w, l.out, l.in, l.in, perm, D + off, st); };
-      if ((rc = bi(k.skip, 0, c.skip))) return rc;
-      for (int l = 0; l < d->tfmr_layers; ++l) {
-        if ((rc = bi(k.tf[l].inp, 0, c.inp[l])) || (rc = bi(k.tf[l].outp, 0, c.outp[l])) || (rc = bi(k.tf[l].l1, 0, c.l1[l])) ||
-            (rc = bi(k.tf[l].l2, 1, c.l2[l])) || (rc = bi(k.tf[l].l2, 0, c.l2n[l])))
-          return rc;
-      }
-      if ((rc = bi(k.post, 0, c.post)) || (rc = bi(k.t1, 0, c.t1)) || (rc = bi(k.t2, 1, c.t2)) || (rc = bi(k.t3, 1, c.t3)) ||
-          (rc = bi(k.t2, 0, c.t2n)) || (rc = bi(k.t3, 0, c.t3n)))
-        return rc;
-      if (b < d->num_blocks - 1) {
-        if ((rc = bi(k.et_init, 0, c.et_init))) return rc;
-        // e_i columns of the first / final EdgeTransition layers as [hid, cb] / [cz, cb] matrices
-        if ((rc = fd_chain_build_image(P + k.et1.w + cz, iv.hid, iv.cb, iv.hid, 0, D + c.a1, st))) return rc;
-        // the same two matrices stacked (tile-major images: stacking = concatenation) and their biases, for the fused
-        // initial_embed -> [A1 | Af] row-block kernel
-        if ((rc = fd_chain_build_image(P + k.et1.w + cz, iv.hid, iv.cb, iv.hid, 0, D + c.a1af, st)) ||
-            (rc = fd_chain_build_image(P + k.etf.w + cz, cz, iv.cb, iv.hid, 0, D + c.a1af + fd_chain_image_bytes(iv.hid, iv.cb), st)) ||
-            (rc = copy_cols(4, 1, iv.hid, iv.hid, P + k.et1.b, iv.hid, 0, 1.f, D + c.b1f, st)) ||
-            (rc = copy_cols(4, 1, cz, cz, P + k.etf.b, cz, 0, 1.f, D + c.b1f + (size_t)iv.hid * 4, st)))
-          return rc;
-        if ((rc = fd_chain_build_image(P + k.etf.w + cz, cz, iv.cb, iv.hid, 0, D + c.af, st))) return rc;
-        {  // edge_transition4 rows: e_i columns (+ bias) then e_j columns of the first / final layers, one 1024-row image
-          const size_t i1 = fd_chain_image_bytes(iv.hid, iv.cb), i2 = fd_chain_image_bytes(cz, iv.cb);
-          if ((rc = fd_chain_build_image(P + k.et1.w + cz, iv.hid, iv.cb, iv.hid, 0, D + c.r4w, st)) ||
-              (rc = fd_chain_build_image(P + k.etf.w + cz, cz, iv.cb, iv.hid, 0, D + c.r4w + i1, st)) ||
-              (rc = fd_chain_build_image(P + k.et1.w + cz + iv.cb, iv.hid, iv.cb, iv.hid, 0, D + c.r4w + i1 + i2, st)) ||
-              (rc = fd_chain_build_image(P + k.etf.w + cz + iv.cb, cz, iv.cb, iv.hid, 0, D + c.r4w + 2 * i1 + i2, st)) ||
-              (rc = copy_cols(4, 1, iv.hid, iv.hid, P + k.et1.b, iv.hid, 0, 1.f, D + c.r4b, st)) ||
-              (rc = copy_cols(4, 1, cz, cz, P + k.etf.b, cz, 0, 1.f, D + c.r4b + (size_t)iv.hid * 4, st)))
-            return rc;
-          if (hipMemsetAsync(D + c.r4b + (size_t)(iv.hid + cz) * 4, 0, (size_t)(iv.hid + cz) * 4, st) != hipSuccess) return FDIPT_ELAUNCH;
-        }
-      }
-    }
-  }
-  if (use_chain(d)) {
-    auto lo = [&](const LinW& l, size_t off) { return fd_chain_build_image_lo(P + l.w, l.out, l.in, l.in, D + off, st); };
-    for (int b = 0; b < d->num_blocks; ++b) {
-      const BlockW& k = iv.blk[b];
-      const DSplit& c = L.blk[b].lo;
-      for (int l = 0; l < d->tfmr_layers; ++l)
-        if ((rc = lo(k.tf[l].inp, c.inp[l])) || (rc = lo(k.tf[l].outp, c.outp[l])) || (rc = lo(k.tf[l].l1, c.l1[l])) || (rc = lo(k.tf[l].l2, c.l2[l])))
-          return rc;
-      if ((rc = lo(k.post, c.post)) || (rc = lo(k.t1, c.t1)) || (rc = lo(k.t2, c.t2)) || (rc = lo(k.t3, c.t3))) return rc;
-      if (tail16_shapes(d, iv)) {  // 16-row images of the tail (tfmr_tail16_kernel)
-        auto i16 = [&](const LinW& l, int h, size_t off) { return fd_chain_build_image16(P + l.w, l.out, l.in, l.in, l.in, h, D + off, st); };
-        for (int h = 0; h < 2; ++h) {
-          for (int l = 0; l < d->tfmr_layers; ++l)
-            if ((rc = i16(k.tf[l].outp, h, c.o16[l][h])) || (rc = i16(k.tf[l].l1, h, c.f16[l][h])) || (rc = i16(k.tf[l].l2, h, c.g16[l][h]))) return rc;
-          if ((rc = i16(k.post, h, c.p16[h]))) return rc;
-          if ((rc = i16(k.t1, h, c.tr16[0][h])) || (rc = i16(k.t2, h, c.tr16[1][h])) || (rc = i16(k.t3, h, c.tr16[2][h]))) return rc;
-        }
-      }
-      if (b < d->num_blocks - 1 && tail16_shapes(d, iv) && iv.cb == 128 && (iv.hid & 15) == 0 && (cz & 15) == 0) {
-        // ... and as 16-row images for the transition launch that folds the row launch in (rowblock.hip: mlp16_kernel<.., ETR>)
-        const size_t i1 = fd_chain_image_bytes(iv.hid, iv.cb), i2 = fd_chain_image_bytes(cz, iv.cb);
-        for (int h = 0; h < 2; ++h)
-          if ((rc = fd_chain_build_image16(P + k.et_init.w, iv.cb, cs, cs, cs, h, D + c.ei16[h], st)) ||
-              (rc = fd_chain_build_image16(P + k.et1.w + cz, iv.hid, iv.cb, iv.cb, iv.hid, h, D + c.r416[h], st)) ||
-              (rc = fd_chain_build_image16(P + k.etf.w + cz, cz, iv.cb, iv.cb, iv.hid, h, D + c.r416[h] + i1, st)) ||
-              (rc = fd_chain_build_image16(P + k.et1.w + cz + iv.cb, iv.hid, iv.cb, iv.cb, iv.hid, h, D + c.r416[h] + i1 + i2, st)) ||
-              (rc = fd_chain_build_image16(P + k.etf.w + cz + iv.cb, cz, iv.cb, iv.cb, iv.hid, h, D + c.r416[h] + 2 * i1 + i2, st)))
-            return rc;
-      }
-      if (b < d->num_blocks - 1) {  // EdgeTransition per-residue rows: initial_embed and the e_i / e_j columns of the first / final layers
-        const size_t i1 = fd_chain_image_bytes(iv.hid, iv.cb), i2 = fd_chain_image_bytes(cz, iv.cb);
-        if ((rc = lo(k.et_init, c.et_init)) ||
-            (rc = fd_chain_build_image_lo(P + k.et1.w + cz, iv.hid, iv.cb, iv.hid, D + c.r4w, st)) ||
-            (rc = fd_chain_build_image_lo(P + k.etf.w + cz, cz, iv.cb, iv.hid, D + c.r4w + i1, st)) ||
-            (rc = fd_chain_build_image_lo(P + k.et1.w + cz + iv.cb, iv.hid, iv.cb, iv.hid, D + c.r4w + i1 + i2, st)) ||
-            (rc = fd_chain_build_image_lo(P + k.etf.w + cz + iv.cb, cz, iv.cb, iv.hid, D + c.r4w + 2 * i1 + i2, st)))
-          return rc;
-      }
-    }
-    if ((rc = lo(iv.ne0, L.lo_ne0)) || (rc = lo(iv.ne2, L.lo_ne2)) || (rc = lo(iv.ne4, L.lo_ne4)) || (rc = lo(iv.tor1, L.lo_tor1)) ||
-        (rc = lo(iv.tor2, L.lo_tor2)))
-      return rc;
-    if (cs == 256 && d->num_blocks * d->c_skip == 256)  // (skip_w32 was stacked block by block above)
-      for (int h = 0; h < 2; ++h)
-        if ((rc = fd_chain_build_image16((const float*)(D + L.skip_w32), 256, cs, cs, cs, h, D + L.skip16[h], st))) return rc;
-    if (cs == 256 && iv.node_in <= 96)
-      for (int h = 0; h < 2; ++h)
-        if ((rc = fd_chain_build_image16(P + iv.ne0.w, cs, iv.node_in, 96, iv.node_in, h, D + L.ne16[0][h], st)) ||
-            (rc = fd_chain_build_image16(P + iv.ne2.w, cs, cs, cs, cs, h, D + L.ne16[1][h], st)) ||
-            (rc = fd_chain_build_image16(P + iv.ne4.w, cs, cs, cs, cs, h, D + L.ne16[2][h], st)) ||
-            (rc = fd_chain_build_image16(P + iv.tor1.w, cs, cs, cs, cs, h, D + L.tor16[0][h], st)) ||
-            (rc = fd_chain_build_image16(P + iv.tor2.w, cs, cs, cs, cs, h, D + L.tor16[1][h], st)))
-          return rc;
-    if ((rc = fd_chain_build_image(P + iv.ne0.w, cs, iv.node_in, iv.node_in, 0, D + L.ch_ne0, st))) return rc;
-    if ((rc = fd_chain_build_image(P + iv.ne2.w, cs, cs, cs, 1, D + L.ch_ne2, st))) return rc;
-    if ((rc = fd_chain_build_image(P + iv.ne4.w, cs, cs, cs, 1, D + L.ch_ne4, st))) return rc;
-    if ((rc = fd_chain_build_image(P + iv.tor1.w, cs, cs, cs, 0, D + L.ch_tor1, st))) return rc;
-    if ((rc = fd_chain_build_image(P + iv.tor2.w, cs, cs, cs, 1, D + L.ch_tor2, st))) return rc;
-    if ((rc = fd_chain_build_image(P + iv.ne2.w, cs, cs, cs, 0, D + L.ch_ne2n, st))) return rc;
-    if ((rc = fd_chain_build_image(P + iv.ne4.w, cs, cs, cs, 0, D + L.ch_ne4n, st))) return rc;
-    if ((rc = fd_chain_build_image(P + iv.tor2.w, cs, cs, cs, 0, D + L.ch_tor2n, st))) return rc;
-  }
-  (void)C;
-  return FDIPT_OK;
+  return blob_walk(d, iv, L, P, (char*)derived, (hipStream_t)stream);
 }
 
 size_t fdipt_setup_bytes(const FdiptDims* dims, int B, int N, int n_rel) {
@@ -577,7 +558,7 @@ int fdipt_sample_setup(const FdiptDims* d, const float* P, const void* derived, 
   Inventory iv;
   DLayout L;
   build_inventory(d, iv);
-  build_layout(d, iv, L);
+  blob_walk(d, iv, L);
   // R[b, r, :] = W1[:, 2*d1 : 2*d1+E] index_embedding(r - rel_off)   (fp32; constant along the trajectory)
   return fd_linear(FDIPT_PREC_F32, B * n_rel, d->c_z, d->index_embed, rel_emb, d->index_embed,
                    (const char*)derived + L.w1r, d->index_embed, nullptr, nullptr, 0, nullptr, 0, (float*)setup, d->c_z,
@@ -638,16 +619,10 @@ size_t fdipt_forward_workspace_bytes(const FdiptDims* dims, int B, int N) {
   DLayout L;
   WS w;
   build_inventory(dims, iv);
-  build_layout(dims, iv, L);
+  blob_walk(dims, iv, L);
   build_ws(dims, iv, L, B, N, w);
   return w.total;
 }
-
-#define RC(x)                   \
-  do {                          \
-    int rc__ = (x);             \
-    if (rc__) return rc__;      \
-  } while (0)
 
 }  // extern "C"
 
@@ -711,8 +686,8 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   // (profiles/r01_chain_vs_gemm.md): post_tfmr and EdgeTransition.initial_embed when the row-block kernels do not take them
   p.chain = use_chain(d);
   // row-complete fused MLPs (rowblock.hip) take the multi-layer kinds and the 320-wide transformer layers (FDIPT_KF_UNFUSED_NODE
-  // clears use_chain)
-  p.rbk = p.chain && cs == 256 && iv.d_t == 320;
+  // clears use_chain, whose widths are theirs)
+  p.rbk = p.chain;
   // split operands (hi + lo half-precision parts, 3 MFMAs per k-step) for the dense layers of the node path, whose operand
   // rounding dominates the error of the predicted frames and psi (tests/err_budget.py): node embedder, IPA projection and output
   // projection, attention P V, o_pair down-projection, sequence transformer (in_proj, out_proj, feed-forward), post_tfmr, transition,
@@ -721,17 +696,15 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   // 16-row node-path blocks pay off while they are about one round of the chip (B N <= ~4000 rows: twice the blocks of the 32-row kernels, each
   // streaming all weights, half the matrix work per block); with every CU busy anyway the 32-row kernels move half the weight bytes (measured: c4
   // with 64 samples per GPU 1.277 -> 1.246 M).  The choice goes by N alone — a sample's result must not depend on the batch it rides in.
+  // (the 16-row images exist with the 32-row ones: use_chain)
   const bool rows16 = p.split && !(f & FDIPT_KF_ROWS32) && N <= 512;
-  const bool ends16 = rows16 && cs == 256 && iv.node_in <= 96;  // node embedder and torsion head (rowblock.hip: mlp16_kernel)
-  const bool mid16 = rows16 && tail16_shapes(d, iv);            // transformer tails and transition
-  p.embed = p.rbk && (L.kn_pad == 72 || L.kn_pad == 88) ? (ends16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
-  p.torsion = p.rbk ? (ends16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
-  p.tail = p.transition = p.rbk ? (mid16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
+  p.embed = p.rbk && (L.kn_pad == 72 || L.kn_pad == 88) ? (rows16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
+  p.torsion = p.tail = p.transition = p.rbk ? (rows16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
   // the IPA output projection as split-K slices that its LayerNorm sums; skip_embed(init_node) of every block depends on the
   // embedder output only: one launch for all blocks, copied behind the LayerNorm output by that LayerNorm (FDIPT_KF_UNFOLDED: per block)
   const bool splitk = p.bf && iv.feat_dim >= 1024 && !(f & FDIPT_KF_UNFUSED_NODE);
   if (!splitk || unfolded || op != OP_ALL) p.skip = SKIP_PER_BLOCK;
-  else if (p.embed == NF_ROWS16 && d->num_blocks * d->c_skip == 256) p.skip = SKIP_EMBED16;  // a fourth layer of the embedder launch
+  else if (p.embed == NF_ROWS16 && skip16_image(d)) p.skip = SKIP_EMBED16;  // a fourth layer of the embedder launch
   else p.skip = p.split && (cs & 7) == 0 ? SKIP_SPLITK : SKIP_GEMM;
   // the split of x_t (ipa_pytorch.py:516-524) and the per-residue halves of the first edge-embedder layer in the feature launch
   // (FDIPT_KF_UNFOLDED: three GEMM / element-wise launches more)
@@ -740,7 +713,7 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   Attn3Args a3 = {};
   a3.B = B; a3.N = N; a3.H = H; a3.Np = Np; a3.vpt = (const half_t*)&kImage;
   OPairArgs oa = {};
-  oa.B = B; oa.N = N; oa.H = H; oa.CZ = cz; oa.CD = cz / 4; oa.wdz_img = p.bf && cz == 128 ? &kImage : nullptr;
+  oa.B = B; oa.N = N; oa.H = H; oa.CZ = cz; oa.CD = cz / 4; oa.wdz_img = p.bf && dz_images(d) ? &kImage : nullptr;
   // key-streaming attention (attention3.hip / attention_seq.hip: two sweeps over key chunks) for every N <= 2048; it lifts the register
   // kernels' N <= 1024 wherever this plan tests a length (IPA attention, o_pair, pair bias producers, sequence attention)
   p.stream = (f & FDIPT_KF_STREAM_ATTN) && p.bf && !generic_attn && N <= 2048;
@@ -751,7 +724,7 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   p.probs_h16 = p.a3 && opair_mfma && 2 * Np <= 4 * N;
   // the next block's pair bias linear_b(z)/sqrt(3) from the LayerNorm epilogue of the producer of z (saves a pass over z): the
   // embedder for block 0 (register kernel only), the EdgeTransition of block b for block b + 1
-  const bool bias_rule = cz == 128 && C == 256 && Pq == 8 && Pv == 12 && H <= 8 && N <= n_attn && !generic_attn && !unfolded;
+  const bool bias_rule = bias_images(d) && C == 256 && Pq == 8 && Pv == 12 && N <= n_attn && !generic_attn && !unfolded;
   p.regpair = use_regpair(d);
   p.ee_bias = bias_rule && p.regpair;
   p.et_bias = bias_rule;
@@ -773,18 +746,18 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   p.vpt = p.a3 && Pv == 12;
   ProjArgs pj = {};
   pj.B = B; pj.N = N; pj.H = H; pj.C = C; pj.K = cs; pj.PT = iv.proj_out - 3 * H * C; pj.Np = Np; pj.lda = cs;
-  pj.W_img = cs == 256 ? &kImage : nullptr;
+  pj.W_img = proj_image(d) ? &kImage : nullptr;
   pj.W_img_lo = pj.W_img && p.split ? &kImage : nullptr;
   // Merged projections (the default of the split mode at the reference widths): no k, no v — the node rows are keys and values of
   // every head (fd_node_images), q' = W_k^T (W_q s + b_q), W_v sits in the output projection (prepare: merge_qk / merge_vo).  40 % of
   // the projection's columns, and K / V images an eighth of the size.  Exact algebra (softmax shift invariance, linearity); the
   // per-op entries and FDIPT_KF_NO_MERGE keep the reference's formulation.
-  p.merged = p.a3 && pj.W_img_lo && cs == C && !(f & FDIPT_KF_NO_MERGE) && op == OP_ALL && fd_ipa_proj2_supported(pj);
+  p.merged = p.a3 && pj.W_img_lo && merged_image(d) && !(f & FDIPT_KF_NO_MERGE) && op == OP_ALL && fd_ipa_proj2_supported(pj);
   pj.merged = p.merged;
   // point epilogue (ipa_proj2.hip: p2_points_walk / p2_node_rows): the merged projection also writes the rotated points (qp, kpf, vpt,
   // rot) and the node-row images; no point launch, no fp32 point columns.  This flag decides the projection's image, the pads and
   // the launches dropped
-  p.proj_pts = p.merged && !(f & FDIPT_KF_POINTS_LAUNCH) && p.vpt && fd_ipa_proj2_points_supported(pj, Pq, Pv);
+  p.proj_pts = p.merged && !(f & FDIPT_KF_POINTS_LAUNCH) && p.vpt && points_image(d) && fd_ipa_proj2_points_supported(pj, Pq, Pv);
   if (p.proj_pts) pj.PT = fd_ipa_proj2_points_cols(H, C) - H * C;
   // second generation (activation fragments in registers, weights by LDS-DMA) where it applies, else the tiled GEMM
   p.proj2 = p.a3 && fd_ipa_proj2_supported(pj);
@@ -812,7 +785,7 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   // 4 slices = 608 blocks need two rounds, 41 us).  The slice count must not depend on the batch size: the order of the
   // partial sums is part of a sample's result (sub-batches and sharded runs reproduce the whole-batch result bit for bit)
   if (!splitk) p.outproj = OUT_GEMM;
-  else if (p.split && p.merged && fd_outproj_split_supported(cs, iv.feat_dim)) p.outproj = OUT_DEDICATED;
+  else if (p.split && p.merged && outproj_image(d, iv)) p.outproj = OUT_DEDICATED;
   else p.outproj = p.split ? OUT_SPLITK_SPLIT : p.feats_h16 ? OUT_SPLITK_A16 : OUT_SPLITK;
   p.slices = p.outproj == OUT_DEDICATED ? fd_outproj_split_slices() : p.split ? 3 : 4;
   // the last layer's tail also applies post_tfmr + the node residual (FDIPT_KF_UNFOLDED: its own launch)
@@ -876,31 +849,27 @@ struct Fwd {
         return L2Warm{{D + db.ch.inp[l], p.split ? D + db.lo.inp[l] : nullptr, nullptr}, {n, p.split ? n : 0u, 0}};
       }
       case WARM_TAIL: {  // layer l's tail (fd_tfmr_tail)
+        // its three hi images and its three lo images (the last layer's runs end with post_tfmr)
+        if (p.tail == NF_ROWS16) return L2Warm{{D + db.lo.o16[l][0], D + db.lo.o16[l][1], nullptr}, {db.lo.tail16_run[l], db.lo.tail16_run[l], 0}};
         const unsigned wimg = (unsigned)fd_chain_image_bytes(dt, dt);
-        if (p.tail == NF_ROWS16) {  // its three hi images and its three lo images (each run contiguous; the last layer's run ends with post_tfmr)
-          const unsigned run = 3 * wimg + (l + 1 == d->tfmr_layers ? (unsigned)fd_chain_image_bytes(cs, dt) : 0u);
-          return L2Warm{{D + db.lo.o16[l][0], D + db.lo.o16[l][1], nullptr}, {run, run, 0}};
-        }
-        return L2Warm{{D + db.ch.outp[l], D + db.ch.l1[l], D + db.ch.l2n[l]}, {wimg, wimg, wimg}};
+        return L2Warm{{D + db.ch.outp[l], D + db.ch.l1[l], D + db.ch.l2[l]}, {wimg, wimg, wimg}};
       }
       case WARM_POST: return L2Warm{{D + db.ch.post, nullptr, nullptr}, {(unsigned)fd_chain_image_bytes(cs, dt), 0, 0}};
       case WARM_TRANSITION:
-        if (p.transition == NF_ROWS16) return L2Warm{{D + db.lo.tr16[0][0], D + db.lo.tr16[0][1], nullptr}, {3 * tb, 3 * tb, 0}};  // (hi run, lo run)
-        if (p.split) return L2Warm{{D + db.ch.t1, D + db.ch.t2n, D + db.lo.t1}, {tb, 2 * tb, 3 * tb}};  // (t2n | t3n and lo t1 | t2 | t3 are contiguous)
+        if (p.transition == NF_ROWS16) return L2Warm{{D + db.lo.tr16[0][0], D + db.lo.tr16[0][1], nullptr}, {db.lo.tr16_run, db.lo.tr16_run, 0}};
+        if (p.split) return L2Warm{{D + db.ch.t1, D + db.ch.t2, D + db.lo.t1}, {tb, db.ch.t23_run, db.lo.t_run}};
         [[fallthrough]];
       case WARM_TRANSITION32:  // (the post_tfmr chain hands over the 32-row hi images whatever the transition form)
-        return L2Warm{{D + db.ch.t1, D + db.ch.t2n, D + db.ch.t3n}, {tb, tb, tb}};
-      case WARM_ET_ROWS: {  // the EdgeTransition row launch (lo et_init | r4w are contiguous)
+        return L2Warm{{D + db.ch.t1, D + db.ch.t2, D + db.ch.t3}, {tb, tb, tb}};
+      case WARM_ET_ROWS: {  // the EdgeTransition row launch
         const unsigned ei = (unsigned)fd_chain_image_bytes(iv.cb, cs), r4 = (unsigned)fd_chain_image_bytes(2 * (iv.hid + d->c_z), iv.cb);
-        return L2Warm{{D + db.ch.et_init, D + db.ch.r4w, p.split ? D + db.lo.et_init : nullptr}, {ei, r4, p.split ? ei + r4 : 0u}};
+        return L2Warm{{D + db.ch.et_init, D + db.ch.r4w, p.split ? D + db.lo.et_init : nullptr}, {ei, r4, p.split ? db.lo.et_run : 0u}};
       }
-      case WARM_ET_FOLDED: {  // the transition launch's own later-stage images (hi run, lo run)
-        const unsigned run = (unsigned)(fd_chain_image_bytes(iv.cb, cs) + fd_chain_image_bytes(2 * (iv.hid + d->c_z), iv.cb));
-        return L2Warm{{D + db.lo.ei16[0], D + db.lo.ei16[1], nullptr}, {run, run, 0}};
-      }
+      case WARM_ET_FOLDED:  // the transition launch's own later-stage images (hi run, lo run)
+        return L2Warm{{D + db.lo.ei16[0], D + db.lo.ei16[1], nullptr}, {db.lo.et16_run, db.lo.et16_run, 0}};
       case WARM_TORSION:
-        if (p.torsion == NF_ROWS16) return L2Warm{{D + L.tor16[0][0], D + L.tor16[0][1], nullptr}, {2 * tb, 2 * tb, 0}};  // (hi run, lo run)
-        return L2Warm{{D + L.ch_tor1, D + L.ch_tor2n, p.split ? D + L.lo_tor1 : nullptr}, {tb, tb, p.split ? 2 * tb : 0u}};  // (lo tor1 | tor2 are contiguous)
+        if (p.torsion == NF_ROWS16) return L2Warm{{D + L.tor16[0][0], D + L.tor16[0][1], nullptr}, {L.tor16_run, L.tor16_run, 0}};
+        return L2Warm{{D + L.ch_tor1, D + L.ch_tor2, p.split ? D + L.lo_tor1 : nullptr}, {tb, tb, p.split ? L.lo_tor_run : 0u}};
     }
     return L2Warm{};
   }
@@ -921,7 +890,7 @@ struct Fwd {
       const bool r16 = p.embed == NF_ROWS16;
       RowBlockArgs r;
       r.M = R; r.in = F(w.node_feat); r.ld_in = L.kn_pad;
-      r.w0 = D + (r16 ? L.ne16[0][0] : L.ch_ne0); r.w1 = D + (r16 ? L.ne16[1][0] : L.ch_ne2n); r.w2 = D + (r16 ? L.ne16[2][0] : L.ch_ne4n);
+      r.w0 = D + (r16 ? L.ne16[0][0] : L.ch_ne0); r.w1 = D + (r16 ? L.ne16[1][0] : L.ch_ne2); r.w2 = D + (r16 ? L.ne16[2][0] : L.ch_ne4);
       if (p.split) {
         r.w0l = D + (r16 ? L.ne16[0][1] : L.lo_ne0); r.w1l = D + (r16 ? L.ne16[1][1] : L.lo_ne2); r.w2l = D + (r16 ? L.ne16[2][1] : L.lo_ne4);
       }
@@ -930,10 +899,9 @@ struct Fwd {
       if (p.skip == SKIP_EMBED16) {  // skip_embed(init_node) of all blocks as a fourth layer of the same launch
         r.w3 = D + L.skip16[0]; r.w3l = D + L.skip16[1]; r.b3 = (const float*)(D + L.skip_b);
         r.out2 = F(w.skip_all); r.ld_out2 = d->num_blocks * d->c_skip;
-        // (the kernel touches its own last stage's images while it starts: they were last read a whole step ago)
-        // ... and so were its own hi / lo runs (ne16: three images each; skip16 hi | lo are contiguous)
-        const unsigned run = (unsigned)(fd_chain_image_bytes(256, 96) + 2 * fd_chain_image_bytes(256, 256));
-        r.warm = L2Warm{{r.w0, r.w0l, r.w3}, {run, run, 2 * (unsigned)fd_chain_image_bytes(256, 256)}};
+        // (the kernel touches its own last stage's images while it starts: they were last read a whole step ago, and so were its own
+        // hi / lo runs)
+        r.warm = L2Warm{{r.w0, r.w0l, r.w3}, {L.ne16_run, L.ne16_run, L.skip16_run}};
       }
       if (r16) RC(fd_node_embed16(r, L.kn_pad, st));
       else if (p.split) RC(fd_rowblock(L.kn_pad == 72 ? FD_RB_NODE_EMBED_72_SPLIT : FD_RB_NODE_EMBED_88_SPLIT, r, st));
@@ -980,7 +948,7 @@ struct Fwd {
     pj.W = D + db.wproj; pj.bias = (const float*)(D + db.bproj); pj.qscale = sqrtf(1.0f / (3.0f * (float)C));
     pj.Qb = (half_t*)(W + w.qb); pj.Kb = (half_t*)(W + w.kb); pj.Vt = (half_t*)(W + w.vt); pj.pts = F(w.pts);
     pj.zero_pads = first_block(b);
-    pj.W_img = cs == 256 ? D + db.wproj_img : nullptr;
+    pj.W_img = proj_image(d) ? D + db.wproj_img : nullptr;
     pj.W_img_lo = pj.W_img && p.split ? D + db.wproj_img_lo : nullptr;
     if (p.merged) { pj.merged = 1; pj.W_img = D + db.wproj2_img; pj.W_img_lo = D + db.wproj2_img_lo; pj.bias = (const float*)(D + db.bproj2); }
     if (p.proj_pts) {
@@ -1023,7 +991,7 @@ struct Fwd {
     const int cz = d->c_z, H = d->no_heads, C = d->c_hidden, Pv = d->no_v_points, feat = iv.feat_dim;
     OPairArgs oa;
     oa.B = B; oa.N = N; oa.H = H; oa.CZ = cz; oa.CD = cz / 4; oa.z = W + w.z; oa.probs = F(w.probs); oa.probs_h16 = nullptr;
-    oa.probs_np = 0; oa.out_h16 = nullptr; oa.wdz = (const float*)(D + db.wdz_t); oa.wdz_img = p.bf && cz == 128 ? D + db.wdz_img : nullptr;
+    oa.probs_np = 0; oa.out_h16 = nullptr; oa.wdz = (const float*)(D + db.wdz_t); oa.wdz_img = p.bf && dz_images(d) ? D + db.wdz_img : nullptr;
     oa.wdz_img_lo = oa.wdz_img && p.split ? D + db.wdz_img_lo : nullptr; oa.bdz = P + iv.blk[b].dz.b;
     oa.out = F(w.feats); oa.out_ld = feat; oa.off = H * C + 4 * H * Pv;
     if (p.a3) {
@@ -1135,7 +1103,7 @@ struct Fwd {
       const bool r16 = p.tail == NF_ROWS16;  // 16-row blocks (150 blocks at 2400 rows)
       TfmrTailArgs tt;
       tt.M = R; tt.ld = dt; tt.att = F(w.att); tt.x = x;
-      tt.wo = D + (r16 ? db.lo.o16[l][0] : db.ch.outp[l]); tt.w1 = D + (r16 ? db.lo.f16[l][0] : db.ch.l1[l]); tt.w2 = D + (r16 ? db.lo.g16[l][0] : db.ch.l2n[l]);
+      tt.wo = D + (r16 ? db.lo.o16[l][0] : db.ch.outp[l]); tt.w1 = D + (r16 ? db.lo.f16[l][0] : db.ch.l1[l]); tt.w2 = D + (r16 ? db.lo.g16[l][0] : db.ch.l2[l]);
       if (p.split) { tt.wol = D + (r16 ? db.lo.o16[l][1] : db.lo.outp[l]); tt.w1l = D + (r16 ? db.lo.f16[l][1] : db.lo.l1[l]); tt.w2l = D + (r16 ? db.lo.g16[l][1] : db.lo.l2[l]); }
       tt.bo = P + t.outp.b; tt.g1 = P + t.n1.g; tt.be1 = P + t.n1.b; tt.b1 = P + t.l1.b; tt.b2 = P + t.l2.b; tt.g2 = P + t.n2.g;
       tt.be2 = P + t.n2.b; tt.out = x == F(w.x_b) ? F(w.x_a) : F(w.x_b);
@@ -1182,7 +1150,7 @@ struct Fwd {
     const bool r16 = p.transition == NF_ROWS16;  // 16-row blocks (rowblock.hip: transition16_kernel)
     RowBlockArgs r;
     r.M = R; r.in = F(w.h_a); r.ld_in = cs;
-    r.w0 = D + (r16 ? db.lo.tr16[0][0] : db.ch.t1); r.w1 = D + (r16 ? db.lo.tr16[1][0] : db.ch.t2n); r.w2 = D + (r16 ? db.lo.tr16[2][0] : db.ch.t3n);
+    r.w0 = D + (r16 ? db.lo.tr16[0][0] : db.ch.t1); r.w1 = D + (r16 ? db.lo.tr16[1][0] : db.ch.t2); r.w2 = D + (r16 ? db.lo.tr16[2][0] : db.ch.t3);
     if (p.split) { r.w0l = D + (r16 ? db.lo.tr16[0][1] : db.lo.t1); r.w1l = D + (r16 ? db.lo.tr16[1][1] : db.lo.t2); r.w2l = D + (r16 ? db.lo.tr16[2][1] : db.lo.t3); }
     r.b0 = P + k.t1.b; r.b1 = P + k.t2.b; r.b2 = P + k.t3.b; r.residual = F(w.h_a); r.ld_res = cs; r.gamma = P + k.tln.g; r.beta = P + k.tln.b;
     r.rowmask_post = a->res_mask; r.out = F(w.node); r.ld_out = cs; r.bb_w = P + k.bb.w; r.bb_b = P + k.bb.b;
@@ -1274,7 +1242,7 @@ struct Fwd {
     } else {
       const bool r16 = p.torsion == NF_ROWS16;
       RowBlockArgs r;
-      r.M = R; r.in = node; r.ld_in = cs; r.w0 = D + (r16 ? L.tor16[0][0] : L.ch_tor1); r.w1 = D + (r16 ? L.tor16[1][0] : L.ch_tor2n);
+      r.M = R; r.in = node; r.ld_in = cs; r.w0 = D + (r16 ? L.tor16[0][0] : L.ch_tor1); r.w1 = D + (r16 ? L.tor16[1][0] : L.ch_tor2);
       if (p.split) { r.w0l = D + (r16 ? L.tor16[0][1] : L.lo_tor1); r.w1l = D + (r16 ? L.tor16[1][1] : L.lo_tor2); }
       r.b0 = P + iv.tor1.b; r.b1 = P + iv.tor2.b; r.residual = node; r.ld_res = cs; r.out = F(w.h_b); r.ld_out = cs;
       if (r16) RC(fd_torsion16(r, st));
@@ -1314,7 +1282,7 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
   DLayout L;
   WS w;
   build_inventory(d, iv);
-  build_layout(d, iv, L);
+  blob_walk(d, iv, L);
   const int B = a->B, N = a->N, R = B * N;
   build_ws(d, iv, L, B, N, w);
   if (workspace_bytes < w.total) return FDIPT_ESIZE;
