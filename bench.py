@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: residue x diffusion-steps / s of the sampler hot loop (BASELINE.json metric).
 
-    python bench.py --gpus 1 [--steps K] [--warmup W] [--config c4|c2|c3|c5] [--precision fp16|fp32] [--dump-outputs DIR]
+    python bench.py --gpus 1 [--steps K] [--warmup W] [--config c4|c2|c3|c5] [--precision fp16|fp32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -30,15 +30,19 @@ ReverseLoop.results() returns (prot_traj, rigid_traj: x_{t-1}, trans_traj, rigid
 DIR/<name>.npy (rank r > 0 of a multi-GPU run: DIR/<name>_rank<r>.npy), so that two builds can be compared output for output.
 Above DUMP_BYTES in all, a fixed seeded sample of the batch rows is written instead.
 
-Also on the JSON line:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.  Also on that line:
   loop         : how the timed steps were issued — the default product path (inference.ReverseLoop: cursor-addressed launches replayed
                  as HIP graphs; `--eager`: launch by launch), host time per step, set-up and graph capture before the timed region.
   roofline     : the dominant kernel (EdgeTransition, 89 % of the reference FLOPs) timed with HIP events recorded by the library
                  on the launch stream around its launches in 4 (K <= 32) or 16 steps of the timed region — those steps are enqueued
                  launch by launch through the same step cursor (events inside a captured graph cannot be timed on ROCm) —, read back
                  after the region; achieved = reference-formulation FLOPs per launch / duration (executed FLOPs stated beside it).
+  (flat copy: whole_forward_frac, for parsers that keep top-level keys)
+
+--full adds the records that take work of their own after the timed region (each but results_d2h can be left out with its --no-* option):
+  results_d2h  : K == T only — the D2H copy of the whole trajectories, as inference_fn returns them.
   all_samples_one_gpu : c4 on one GPU only — all 64 samples of BASELINE configs[3] in one batch, a few steps, own roofline.
-  (flat copies: whole_forward_frac, fp32_value / fp32_ms_per_step / fp32_whole_forward_frac, all64_value / ... for parsers that keep top-level keys)
+  (flat copies: fp32_value / fp32_ms_per_step / fp32_whole_forward_frac, all64_value / ... for parsers that keep top-level keys)
   cpu_baseline : the oracle loop with a torch-CPU forward (oracle/torch_port.py) on this box's host cores: best thread count of a short scan,
                  all physical cores and one thread; bounded sample, rank 0, N = 1 only.
   reference_precision : the same workload in fp32 (the reference's arithmetic) for a few steps: value + roofline of that mode.
@@ -210,8 +214,10 @@ def main():
     ap.add_argument("--kernel-flags", type=lambda s: int(s, 0), default=0, help="FdiptDims.kernel_flags (development)")
     ap.add_argument("--bf16", action="store_true", help="the half-precision mode with bf16 operands / pair representation (the -DFDIPT_HALF_BF16 "
                     "build of the library, lib/libfdipt_hip_bf16.so): what BASELINE configs[1] literally names; misses the parity bar (DESIGN.md section 5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-reference-precision", action="store_true", help="skip the fp32 (reference precision) sub-record")
+    ap.add_argument("--full", action="store_true", help="also run the sub-records after the timed region: results_d2h, all_samples_one_gpu, "
+                    "reference_precision, cpu_baseline (a plain run prints the headline line alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline sub-record")
+    ap.add_argument("--no-reference-precision", action="store_true", help="--full: skip the fp32 (reference precision) sub-record")
     ap.add_argument("--reference-steps", type=int, default=6, help="timed steps of the fp32 sub-record")
     ap.add_argument("--seed", type=int, default=123)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
@@ -219,7 +225,7 @@ def main():
                     "config's whole sample set (c4: BASELINE configs[3]'s 64 samples) split over the GPUs, so that value(N) / value(1) is the "
                     "speed-up of a fixed job")
     ap.add_argument("--total-samples", type=int, default=64, help="--scaling strong: samples of the whole job")
-    ap.add_argument("--no-all-samples", action="store_true", help="skip the all_samples_one_gpu sub-record (c4, one GPU: configs[3]'s 64 samples "
+    ap.add_argument("--no-all-samples", action="store_true", help="--full: skip the all_samples_one_gpu sub-record (c4, one GPU: configs[3]'s 64 samples "
                     "in one batch, a few steps)")
     ap.add_argument("--all-samples-steps", type=int, default=8, help="timed steps of the all_samples_one_gpu sub-record")
     ap.add_argument("--reserve-cus", type=int, default=48, help="with --streams > 1: CUs the persistent pair kernels leave to the other streams")
@@ -438,7 +444,7 @@ def main():
                               ("psi_pred", lambda lp: lp.st.psi)):
                 outputs[name] = torch.cat([row(lp) for lp in lps]).float().cpu().numpy()
         d2h = d2h_bytes = None
-        if K == T:  # D2H of the whole trajectories, as inference_fn returns them (never part of `value`; only meaningful for a whole run)
+        if K == T and a.full:  # D2H of the whole trajectories, as inference_fn returns them (never part of `value`; only meaningful for a whole run)
             t1 = time.perf_counter()
             res = loop.results()
             d2h = time.perf_counter() - t1
@@ -505,7 +511,7 @@ def main():
     if last:
         dump_outputs(a.dump_outputs, last, rank, world)
     all_rec = None
-    if (world == 1 and a.config == "c4" and prec != "fp32" and a.scaling == "weak" and not a.no_all_samples and a.streams == 1
+    if (a.full and world == 1 and a.config == "c4" and prec != "fp32" and a.scaling == "weak" and not a.no_all_samples and a.streams == 1
             and a.n_res is None and a.total_samples > B):
         # BASELINE configs[3] names 64 samples; the headline line holds one GPU's share of them when they are spread over 8 GPUs.  The same
         # GPU with ALL of them in one batch (what a one-GPU run of the config would do): a few steps of the same schedule, own value and
@@ -523,7 +529,7 @@ def main():
         del feats_a, tape_a, dsa
         torch.cuda.empty_cache()
     ref_rec = None
-    if prec != "fp32" and not a.no_reference_precision:
+    if a.full and prec != "fp32" and not a.no_reference_precision:
         # the same workload in the reference's precision (fp32 end to end), a short window of the same schedule: its own value and
         # roofline, so that one command yields both modes (BASELINE.json: the reference never leaves fp32)
         del net
@@ -570,7 +576,7 @@ def main():
             out.update({"fp32_value": ref_rec["value"], "fp32_ms_per_step": ref_rec["ms_per_step"],
                         "fp32_roofline_frac": ref_rec["roofline"]["frac"], "fp32_whole_forward_frac": ref_rec["roofline"]["whole_forward_frac"]})
         out["whole_forward_frac"] = roof["whole_forward_frac"]
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(300 if not inp else min(N, 300), config.base_config(), 7)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -272,9 +272,10 @@ def test_length_limit_is_refused_loudly(prec):
 
 
 def test_bench_line_of_the_driver_command_shape():
-    """bench.py with the driver's flag shape (--gpus 1 --steps K --warmup W; here on config c2 and without the slow sub-records' defaults
-    changed): ONE JSON line carrying the contract keys, the roofline and loop records, the flat copies of the sub-records' values — and the
-    timed region went through graph replays (the default product path), K consecutive steps."""
+    """bench.py with the driver's flag shape (--gpus 1 --steps K --warmup W; here on config c2, with --full for the sub-records and without
+    their defaults changed): ONE JSON line carrying the contract keys, the roofline and loop records, the flat copies of the sub-records'
+    values — and the timed region went through graph replays (the default product path), K consecutive steps.  The same command without
+    --full: the same line without the sub-records."""
     import json
     import os
     import subprocess
@@ -282,11 +283,14 @@ def test_bench_line_of_the_driver_command_shape():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--config", "c2", "--no-cpu-baseline",
            "--reference-steps", "2"]
-    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
-    assert len(lines) == 1, out.stdout[-2000:]
-    d = json.loads(lines[0])
+
+    def line(cmd):
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        return json.loads(lines[0])
+    d = line(cmd + ["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "loop", "whole_forward_frac", "fp32_value", "fp32_whole_forward_frac"):
         assert k in d, k
@@ -296,6 +300,10 @@ def test_bench_line_of_the_driver_command_shape():
     assert r["bound"] == "mfma" and 0 < r["frac"] < 1 and r["launches_timed"] == 3 * 4 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert "12 consecutive steps" in d["config"]["workload"]
     assert abs(d["value"] - 8 * 128 * 12 / (d["ms_per_step"] * 12e-3)) / d["value"] < 1e-6
+    p = line(cmd)
+    assert sorted(p) == sorted(k for k in d if k not in ("reference_precision", "fp32_value", "fp32_ms_per_step", "fp32_roofline_frac",
+                                                         "fp32_whole_forward_frac"))
+    assert p["steps"] == 12 and p["warmup"] == 3 and p["loop"]["graph"] is True and p["roofline"]["launches_timed"] == 3 * 4
 
 
 def test_bench_steps_beyond_the_schedule_and_dumped_outputs(tmp_path):
