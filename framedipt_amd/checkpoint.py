@@ -212,7 +212,8 @@ def apply_checkpoint_conf(cfg, ckpt_conf: dict, seed=None, conf_overrides: dict 
 
 
 def load_model(weights_path, cfg=None, inpainting: bool = False, precision: str = "fp16", device="cuda", conf_overrides=None):
-    """``Inference._load_ckpt``: checkpoint -> (cfg, SE3Diffuser, ScoreNetwork on ``device``)."""
+    """``Inference._load_ckpt``: checkpoint -> (cfg, SE3Diffuser, ScoreNetwork on ``device``).  ``precision``: a key of
+    ``model.score_network.PRECISIONS`` ("fp16", "fp16x", "fp32")."""
     from . import config
     from .diffusion import SE3Diffuser
     from .model import ScoreNetwork

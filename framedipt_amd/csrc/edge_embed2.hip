@@ -221,12 +221,37 @@ __global__ void ee2_build_images_kernel(const float* __restrict__ w2, const floa
     }
   }
 }
-int fd_ee2_build_images(const float* w2, const float* w3, void* img, hipStream_t st) {
+// fp16x: W - half(W) in the same layout, read by the LO kernels from L2 (the LDS holds the hi images and is full)
+__global__ void ee2_build_lo_images_kernel(const float* __restrict__ w2, const float* __restrict__ w3,
+                                           half_t* __restrict__ img) {
+  const int n_chunks = 2 * EE2_IMG / 16;
+  for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n_chunks; g += gridDim.x * blockDim.x) {
+    const int layer = g / (EE2_IMG / 16), q = g % (EE2_IMG / 16);
+    const int row = q / 16, cp = q % 16, c = cp ^ (row & 15);
+    const float* src = layer == 0 ? w2 : w3;
+    for (int e = 0; e < 8; ++e) {
+      const int k = c * 8 + e;
+      const int col = layer == 0 ? k : (k & ~15) + et2_perm16(k & 15);
+      const float v = src[(long)row * 128 + col];
+      img[(long)g * 8 + e] = f2h(v - h2f(f2h(v)));
+    }
+  }
+}
+int fd_ee2_build_images(const float* w2, const float* w3, void* img, hipStream_t st, int lo) {
   hipLaunchKernelGGL(ee2_build_images_kernel, dim3(16), dim3(256), 0, st, w2, w3, (half_t*)img);
+  if (lo) hipLaunchKernelGGL(ee2_build_lo_images_kernel, dim3(16), dim3(256), 0, st, w2, w3, (half_t*)img + 2 * EE2_IMG / 2);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
-size_t fd_ee2_image_bytes() { return 2 * EE2_IMG; }
+size_t fd_ee2_image_bytes(int lo) { return (lo ? 4 : 2) * EE2_IMG; }
+// acc += W_lo slab * B with the A fragments straight from global memory (L2-resident 64 KB lo images, layout of the LDS slabs)
+__device__ __forceinline__ void mma_slab_lo(f32x16& acc, const char* __restrict__ slab, int li, int hi, const hx8* Bf) {
+  hx8 r[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) r[s] = __builtin_bit_cast(hx8, *(const u16x8*)(slab + et2_off_wide(li, 2 * s + hi, 256)));
+#pragma unroll
+  for (int s = 0; s < 8; ++s) acc = fd_mfma32(r[s], Bf[s], acc);
+}
 
 // 512-thread persistent blocks: 8 independent waves (two per SIMD) share the 64 KB weight images; every wave owns an
 // 8 KB LDS tile that transposes between "whole 512 B table rows per 32 lanes" (the global side) and MFMA fragments.
@@ -262,8 +287,9 @@ __device__ unsigned ee2_prof[256 * 8];
 // the reference model's 22 bins keep their table rows in LDS with 64 B to spare: the epilogue's images cannot grow without moving
 // them to the L2 path
 static_assert(EE2_LDS_BASE + (22 + 1) * ET2_CZ * 4 <= EE2_LDS_MAX, "edge_embed2: the 22-bin distogram rows no longer fit in LDS");
-// DIST = false: the model has no distogram channels (num_bins = 0); DLDS is then false as well
-template <bool DIST, bool DLDS, bool TRACE>
+// DIST = false: the model has no distogram channels (num_bins = 0); DLDS is then false as well.  LO (fp16x): layers 2 and 3 add W_lo h,
+// the lo images following the hi ones in `img` (fd_ee2_build_images lo = 1)
+template <bool DIST, bool DLDS, bool TRACE, bool LO = false>
 __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedArgs a, const char* __restrict__ img, int nt, int wpg,
                                                                      int rpw, int n_items) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -435,6 +461,7 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
           for (int q = 0; q < 4; ++q) acc[4 * g + q] = bv[q];
         }
         mma_slab<8, 256>(acc, smem + T * 32 * 256, li, hi, H1);
+        if constexpr (LO) mma_slab_lo(acc, img + 2 * EE2_IMG + T * 32 * 256, li, hi, H1);
         ee_hand_off(acc, H2[2 * T], H2[2 * T + 1]);
       }
       EE2_STAMP(3);
@@ -448,6 +475,7 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
           for (int q = 0; q < 4; ++q) Y[t][4 * g + q] = bv[q];
         }
         mma_slab<8, 256>(Y[t], smem + EE2_IMG + t * 32 * 256, li, hi, H2);
+        if constexpr (LO) mma_slab_lo(Y[t], img + 3 * EE2_IMG + t * 32 * 256, li, hi, H2);
       }
       EE2_STAMP(4);
       asm volatile("" ::: "memory");
@@ -472,7 +500,7 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
 #endif
 }
 
-int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st) {
+int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st, int lo) {
   const bool dist = a.num_bins > 0;  // num_bins = 0: the model has no distogram channels (sc_ca, dtab and edges are not read)
   if (a.num_bins > EE2_MAXB || (dist && a.num_bins < 3)) return FDIPT_EINVAL;
   if (dist && (!a.sc_ca || !a.dtab || !a.edges)) return FDIPT_EINVAL;
@@ -480,11 +508,14 @@ int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st) {
   const bool dlds = dist && a.num_bins <= EE2_MAXB_LDS && EE2_LDS_BASE + (a.num_bins + 1) * ET2_CZ * 4 <= EE2_LDS_MAX;  // (else the distogram rows come from L2)
   const int lds = dist ? EE2_LDS_BASE + (dlds ? (a.num_bins + 1) * ET2_CZ * 4 : 0) : EE2_LDS_NODIST;
   typedef void (*kern_t)(EdgeEmbedArgs, const char*, int, int, int, int);
-  static const kern_t kerns[6] = {edge_embed2_kernel<true, false, false>, edge_embed2_kernel<true, false, true>,
-                                  edge_embed2_kernel<true, true, false>,  edge_embed2_kernel<true, true, true>,
-                                  edge_embed2_kernel<false, false, false>, edge_embed2_kernel<false, false, true>};
-  const int kid = (dist ? 2 * dlds : 4) + (a.trace != nullptr);
-  static FdPerDevice attr_dev[6];
+  static const kern_t kerns[12] = {edge_embed2_kernel<true, false, false>, edge_embed2_kernel<true, false, true>,
+                                   edge_embed2_kernel<true, true, false>,  edge_embed2_kernel<true, true, true>,
+                                   edge_embed2_kernel<false, false, false>, edge_embed2_kernel<false, false, true>,
+                                   edge_embed2_kernel<true, false, false, true>, edge_embed2_kernel<true, false, true, true>,
+                                   edge_embed2_kernel<true, true, false, true>,  edge_embed2_kernel<true, true, true, true>,
+                                   edge_embed2_kernel<false, false, false, true>, edge_embed2_kernel<false, false, true, true>};
+  const int kid = (lo ? 6 : 0) + (dist ? 2 * dlds : 4) + (a.trace != nullptr);
+  static FdPerDevice attr_dev[12];
   const int dev_ = fd_device();
   if (!attr_dev[kid].get(dev_)) {
     if (hipFuncSetAttribute((const void*)kerns[kid], hipFuncAttributeMaxDynamicSharedMemorySize, EE2_LDS_MAX) != hipSuccess)

@@ -40,6 +40,14 @@
 #define E4_STREAM_FR 512
 #define E4_STREAM_BYTES (E4_STREAM_FR * 1024)
 static_assert(E4_L1_FR + E4_L2_FR + E4_LF_FR == 480, "480 weight fragments, then one unused chunk and the down_z chunk");
+// fp16x (FDIPT_PREC_F16X): the final layer also runs W_lo = Wf - half(Wf) against the same h2 + x fragments (k-major, per k-step the
+// 4 hi tiles, then the 4 lo tiles): 192 final-layer fragments, 576 in all = 36 chunks, then three unused chunks and the down_z chunk
+// (40 = a multiple of the ring's four slots, the last in slot 3)
+#define E4X_LF_FR (24 * 8)
+#define E4X_DZ_FR0 624
+#define E4X_STREAM_FR 640
+#define E4X_STREAM_BYTES (E4X_STREAM_FR * 1024)
+static_assert(E4_L1_FR + E4_L2_FR + E4X_LF_FR == 576 && E4X_DZ_FR0 + 16 == E4X_STREAM_FR, "fp16x stream: 36 weight chunks, down_z in the last");
 #define E4_ZOFF (2 * E4_BUF)                 // per-wave z rows [8][32 rows x 256 B]
 #define E4_VOFF (E4_ZOFF + E4_WAVES * 8192)         // b2[384] | gamma[128] | beta[128] | down_z bias [32] f32, then the epilogue's images (E4_WBI)
 #define E4_VEC_BYTES (1536 + 1024 + 128)
@@ -106,15 +114,45 @@ __global__ void et4_build_stream_kernel(const float* __restrict__ w1, const floa
     for (int e = 0; e < 8; ++e) stream[(long)g * 8 + e] = out[e];
   }
 }
-int fd_et4_build_stream(const float* w1, const float* w2, const float* wf, void* stream, hipStream_t st) {
-  hipLaunchKernelGGL(et4_build_stream_kernel, dim3(128), dim3(256), 0, st, w1, w2, wf, (half_t*)stream);
+// fp16x stream: layers 1 and 2 as above, the final layer with hi and lo fragments (E4X_LF_FR), zeros behind
+__global__ void et4x_build_stream_kernel(const float* __restrict__ w1, const float* __restrict__ w2,
+                                         const float* __restrict__ wf, half_t* __restrict__ stream) {
+  const int n_units = E4X_STREAM_BYTES / 16;
+  for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n_units; g += gridDim.x * blockDim.x) {
+    int frag = g >> 6;
+    const int lane = g & 63, f = lane & 31, half = lane >> 5;
+    const float* src;
+    int n, s;
+    bool chained, lo = false;
+    if (frag < E4_L1_FR) { src = w1; n = 32 * (frag / 8) + f; s = frag % 8; chained = false; }
+    else if (frag < E4_L1_FR + E4_L2_FR) { frag -= E4_L1_FR; src = w2; n = 32 * (frag / 24) + f; s = frag % 24; chained = true; }
+    else if (frag < E4_L1_FR + E4_L2_FR + E4X_LF_FR) {
+      frag -= E4_L1_FR + E4_L2_FR;
+      src = wf; n = 32 * (frag & 3) + f; s = frag >> 3; lo = (frag >> 2) & 1;
+      chained = true;
+    } else {  // unused chunks / down_z chunk (fd_et4_set_dz): zeros
+      for (int e = 0; e < 8; ++e) stream[(long)g * 8 + e] = 0;
+      continue;
+    }
+    half_t out[8];
+    for (int e = 0; e < 8; ++e) {
+      const int col = chained ? 32 * (s >> 1) + e4_chain_feat(s & 1, half, e) : 16 * s + 8 * half + e;
+      const float v = src[(long)n * E4_H + col];
+      out[e] = lo ? f2h(v - h2f(f2h(v))) : f2h(v);
+    }
+    for (int e = 0; e < 8; ++e) stream[(long)g * 8 + e] = out[e];
+  }
+}
+int fd_et4_build_stream(const float* w1, const float* w2, const float* wf, void* stream, hipStream_t st, int lo) {
+  if (lo) hipLaunchKernelGGL(et4x_build_stream_kernel, dim3(128), dim3(256), 0, st, w1, w2, wf, (half_t*)stream);
+  else hipLaunchKernelGGL(et4_build_stream_kernel, dim3(128), dim3(256), 0, st, w1, w2, wf, (half_t*)stream);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
-size_t fd_et4_stream_bytes() { return E4_STREAM_BYTES; }
+size_t fd_et4_stream_bytes(int lo) { return lo ? E4X_STREAM_BYTES : E4_STREAM_BYTES; }
 // down_z of the NEXT block's IPA into the stream's last chunk: img_hi / img_lo = fd_chain_build_image(Wdz, 32, 128, 128, permuted = 1, lo = 0 / 1), 8 KB each
-int fd_et4_set_dz(void* stream, const void* img_hi, const void* img_lo, hipStream_t st) {
-  char* dst = (char*)stream + (size_t)E4_DZ_FR0 * 1024;
+int fd_et4_set_dz(void* stream, const void* img_hi, const void* img_lo, hipStream_t st, int lo) {
+  char* dst = (char*)stream + (size_t)(lo ? E4X_DZ_FR0 : E4_DZ_FR0) * 1024;
   if (hipMemcpyAsync(dst, img_hi, 8192, hipMemcpyDeviceToDevice, st) != hipSuccess || hipMemcpyAsync(dst + 8192, img_lo, 8192, hipMemcpyDeviceToDevice, st) != hipSuccess)
     return FDIPT_ELAUNCH;
   return FDIPT_OK;
@@ -496,23 +534,27 @@ struct E4Flat {
   unsigned lds0, pa;
   int tid, wave;
 };
+template <int NCH = E4_NCHUNK>  // chunks of the stream (fp16x: E4X_STREAM_FR / E4_CFR)
 __device__ __forceinline__ void e4_point(const E4Flat& F, int c) {
   e4_vm_wait(e4_vm_younger(c));
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  const int cn = (c + E4_NSLOT - 1) % E4_NCHUNK;
+  const int cn = (c + E4_NSLOT - 1) % NCH;
   e4_dma_chunk<E4_CHUNK>(F.stream + (size_t)cn * E4_CHUNK, F.lds0 + (unsigned)(cn % E4_NSLOT) * E4_CHUNK, F.tid, F.wave);
 }
 // one k-step of the stream: the operand ring is refilled E4_DR - 1 fragments ahead (not past the tile's last fragment)
 #define E4_STEP(f_, B_, acc_)                                                                                   \
   do {                                                                                                          \
-    if ((f_) + E4_DR - 1 < E4_NCHUNK * E4_CFR) r[((f_) + E4_DR - 1) % E4_DR] = e4_frag(F.pa + e4_ring_off((f_) + E4_DR - 1)); \
+    if ((f_) + E4_DR - 1 < NCH * E4_CFR) r[((f_) + E4_DR - 1) % E4_DR] = e4_frag(F.pa + e4_ring_off((f_) + E4_DR - 1)); \
     acc_ = e4_mfma(r[(f_) % E4_DR], B_, acc_);                                                                  \
     __builtin_amdgcn_sched_barrier(0);                                                                          \
   } while (0)
 
-template <bool PZ, bool STZ = true>
+// LO (fp16x): the final layer adds W_lo h2 (the fp16x stream: et4x_build_stream_kernel)
+template <bool PZ, bool STZ = true, bool LO = false>
 __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_flat_kernel(ET2Args a, int n_tiles, int n_wt) {
+  constexpr int NCH = (LO ? E4X_STREAM_FR : E4_STREAM_FR) / E4_CFR;  // stream chunks
+  constexpr int LFW = LO ? 8 : 4;                                     // final-layer fragments per k-step
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem;
   const unsigned vec = lds0 + E4_VOFF;
@@ -595,7 +637,7 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
           const int f = 8 * T + s;
-          if (f % E4_CFR == E4_CFR / 2) e4_point(F, f / E4_CFR);
+          if (f % E4_CFR == E4_CFR / 2) e4_point<NCH>(F, f / E4_CFR);
           E4_STEP(f, Zf[s], acc);
         }
         e4_hand_off(acc, H1[2 * T], H1[2 * T + 1]);
@@ -616,7 +658,7 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
 #pragma unroll
       for (int s = 0; s < 24; ++s) {
         const int f = E4_L1_FR + 24 * T + s;
-        if (f % E4_CFR == E4_CFR / 2) e4_point(F, f / E4_CFR);
+        if (f % E4_CFR == E4_CFR / 2) e4_point<NCH>(F, f / E4_CFR);
         E4_STEP(f, H1[s], acc);
       }
       e4_hand_off(acc, H2[2 * T], H2[2 * T + 1]);
@@ -649,10 +691,11 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
 #pragma unroll
     for (int s = 0; s < 24; ++s)
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int f = E4_L1_FR + E4_L2_FR + 4 * s + t;
+      for (int u = 0; u < LFW; ++u) {  // (LO: u >= 4 are the lo fragments of tile u - 4)
+        const int t = u & 3;
+        const int f = E4_L1_FR + E4_L2_FR + LFW * s + u;
         if (f % E4_CFR == E4_CFR / 2) {
-          e4_point(F, f / E4_CFR);
+          e4_point<NCH>(F, f / E4_CFR);
           // point E4_PT_Z: the wave's z rows are free since the fourth hand-over of layer 2 — the next tile's are requested here, seven chunks
           // before the tile ends (always issued, the last tile re-requests its own: the counts of e4_vm_younger stay static)
           if (f / E4_CFR == E4_PT_Z) e4_request_z(a, tn, lane_id(), lds0 + E4_ZOFF + wave * 8192, M);
@@ -664,8 +707,14 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
         }
         E4_STEP(f, H2[s], E.Y[t]);
       }
-    e4_point(F, 30);  // the unused chunk and the down_z chunk: their stream points without products (the ring keeps turning)
-    e4_point(F, 31);
+    // the unused chunk(s) and the down_z chunk: their stream points without products (the ring keeps turning)
+    static_assert((E4_L1_FR + E4_L2_FR + 24 * LFW) / E4_CFR == NCH - (LO ? 4 : 2), "stream points behind the final layer");
+    if constexpr (LO) {
+      e4_point<NCH>(F, NCH - 4);
+      e4_point<NCH>(F, NCH - 3);
+    }
+    e4_point<NCH>(F, NCH - 2);
+    e4_point<NCH>(F, NCH - 1);
     {
       const hx8 SEL = e4_sel(lane, tc.ns);
 #pragma unroll
@@ -705,22 +754,17 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
 
 int fd_edge_transition4_supported(int N) { return N >= 8 && N <= 2048 && N % 4 == 0; }
 
-int fd_edge_transition4(const ET2Args& a, hipStream_t st) {
-  const long n_pairs = (long)a.B * a.N * a.N;
-  if (n_pairs >= (1L << 31) - 256 || !a.a1_img || !a.b1_img || a.N % 4) return FDIPT_EINVAL;  // 32-bit pair indices in the kernel
-  if (!a.z_out && !a.pz_out) return FDIPT_EINVAL;  // (z' may stay unstored only when pair_z is what the next block reads)
-  {  // the kernel addresses both fold images with 32-bit offsets from a1_img
-    const long d = (const char*)a.b1_img - (const char*)a.a1_img;
-    if (d < 0 || d + (long)fd_et4_b_image_bytes(a.B, a.N) >= (1L << 32)) return FDIPT_EINVAL;
-  }
+// LO: the fp16x kernels (a.stream from fd_et4_build_stream(..., lo = 1))
+template <bool LO>
+static int e4_launch(const ET2Args& a, hipStream_t st) {
   const int n_wt = ((a.B * a.N + 7) / 8) * (a.N / 4);
   const int n_tiles = cdiv(n_wt, E4_WAVES);
   static FdPerDevice attr_dev;
   const int dev_ = fd_device();
   if (!attr_dev.get(dev_)) {
-    if (hipFuncSetAttribute((const void*)edge_transition4_flat_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, E4_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)edge_transition4_flat_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, E4_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)edge_transition4_flat_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, E4_LDS) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)edge_transition4_flat_kernel<false, true, LO>, hipFuncAttributeMaxDynamicSharedMemorySize, E4_LDS) != hipSuccess ||
+        hipFuncSetAttribute((const void*)edge_transition4_flat_kernel<true, true, LO>, hipFuncAttributeMaxDynamicSharedMemorySize, E4_LDS) != hipSuccess ||
+        hipFuncSetAttribute((const void*)edge_transition4_flat_kernel<true, false, LO>, hipFuncAttributeMaxDynamicSharedMemorySize, E4_LDS) != hipSuccess)
       return FDIPT_ELAUNCH;
     attr_dev.set(dev_, 1);
   }
@@ -733,12 +777,22 @@ int fd_edge_transition4(const ET2Args& a, hipStream_t st) {
     if (!a.wb_img || !a.bdz) return FDIPT_EINVAL;  // (down_z hi / lo: the stream's last chunk, fd_et4_set_dz)
     if (!a.z_out) {  // (only next to both emissions and without a trace: checked by the caller's conditions, and here)
       if (a.trace) return FDIPT_EINVAL;
-      hipLaunchKernelGGL((edge_transition4_flat_kernel<true, false>), dim3(grid), dim3(E4_THREADS), E4_LDS, st, a, n_tiles, n_wt);
+      hipLaunchKernelGGL((edge_transition4_flat_kernel<true, false, LO>), dim3(grid), dim3(E4_THREADS), E4_LDS, st, a, n_tiles, n_wt);
     } else
-    hipLaunchKernelGGL(edge_transition4_flat_kernel<true>, dim3(grid), dim3(E4_THREADS), E4_LDS, st, a, n_tiles, n_wt);
+    hipLaunchKernelGGL((edge_transition4_flat_kernel<true, true, LO>), dim3(grid), dim3(E4_THREADS), E4_LDS, st, a, n_tiles, n_wt);
   } else
-    hipLaunchKernelGGL(edge_transition4_flat_kernel<false>, dim3(grid), dim3(E4_THREADS), E4_LDS, st, a, n_tiles, n_wt);
+    hipLaunchKernelGGL((edge_transition4_flat_kernel<false, true, LO>), dim3(grid), dim3(E4_THREADS), E4_LDS, st, a, n_tiles, n_wt);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
 
+int fd_edge_transition4(const ET2Args& a, hipStream_t st, int lo) {
+  const long n_pairs = (long)a.B * a.N * a.N;
+  if (n_pairs >= (1L << 31) - 256 || !a.a1_img || !a.b1_img || a.N % 4) return FDIPT_EINVAL;  // 32-bit pair indices in the kernel
+  if (!a.z_out && !a.pz_out) return FDIPT_EINVAL;  // (z' may stay unstored only when pair_z is what the next block reads)
+  {  // the kernel addresses both fold images with 32-bit offsets from a1_img
+    const long d = (const char*)a.b1_img - (const char*)a.a1_img;
+    if (d < 0 || d + (long)fd_et4_b_image_bytes(a.B, a.N) >= (1L << 32)) return FDIPT_EINVAL;
+  }
+  return lo ? e4_launch<true>(a, st) : e4_launch<false>(a, st);
+}

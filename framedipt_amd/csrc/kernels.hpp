@@ -166,19 +166,21 @@ int fd_edge_transition3(const ET2Args& a, hipStream_t st);
 int fd_et3_build_bias_image(const float* wb, int H, float scale, void* img, hipStream_t st);  // 4 KB, for ET2Args.wb_img
 int fd_edge_transition3_supported(int N);
 // edge_transition4.hip (default, N % 4 == 0): 32-pair waves (8 i x 4 j patches), e_i / e_j parts folded into one k-step
-int fd_et4_build_stream(const float* w1, const float* w2, const float* wf, void* stream, hipStream_t st);
-int fd_et4_set_dz(void* stream, const void* img_hi, const void* img_lo, hipStream_t st);  // down_z of the next block -> the stream's last chunk
-size_t fd_et4_stream_bytes();
+// lo = 1: the fp16x stream (FDIPT_PREC_F16X: the final layer also on W_lo = Wf - half(Wf)), for fd_edge_transition4(..., lo = 1)
+int fd_et4_build_stream(const float* w1, const float* w2, const float* wf, void* stream, hipStream_t st, int lo = 0);
+int fd_et4_set_dz(void* stream, const void* img_hi, const void* img_lo, hipStream_t st, int lo = 0);  // down_z of the next block -> the stream's last chunk
+size_t fd_et4_stream_bytes(int lo = 0);
 int fd_et4_build_bias_image(const float* wb, int H, float scale, void* img, hipStream_t st);  // 8 KB, for ET2Args.wb_img
 size_t fd_et4_a_image_bytes(int B, int N);
 size_t fd_et4_b_image_bytes(int B, int N);
 // rows [B*N][1024] f32 = [A1 | Af | B1 | Bf] -> ET2Args.a1_img / b1_img
 int fd_et4_row_images(const float* rows, int B, int N, void* a_img, void* b_img, hipStream_t st);
-int fd_edge_transition4(const ET2Args& a, hipStream_t st);
+int fd_edge_transition4(const ET2Args& a, hipStream_t st, int lo = 0);
 int fd_edge_transition4_supported(int N);
-int fd_ee2_build_images(const float* w2, const float* w3, void* img, hipStream_t st);
-size_t fd_ee2_image_bytes();
-int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st);
+// lo = 1 (fp16x): the lo images (W - half(W)) follow the hi ones, and the embedder adds W_lo h in layers 2 and 3
+int fd_ee2_build_images(const float* w2, const float* w3, void* img, hipStream_t st, int lo = 0);
+size_t fd_ee2_image_bytes(int lo = 0);
+int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st, int lo = 0);
 
 struct ProjArgs {
   int B, N, H, C, K, PT, Np;  // K = c_s, PT = point columns (3*H*Pq + 3*H*(Pq+Pv)), Np = keys padded to 32

@@ -39,11 +39,19 @@ struct Inventory {
   int d1, node_in, edge_in, d_t, cb, hid, feat_dim, proj_out;
 };
 
+// The half-precision mode of the build, or fp16x (FDIPT_PREC_F16X: the fp16 mode with split terms in the pair path; the default
+// build only).  Every choice of the half-precision mode goes by half_mode; what fp16x adds goes by ForwardPlan::x and the blob's
+// et4x_stream.  op_precision: the operand precision the kernels see (fp16x runs the fp16 kernels).
+static bool half_mode(const FdiptDims* d) {
+  return d->precision == FDIPT_PREC_HALF || (FDIPT_PREC_HALF == FDIPT_PREC_F16 && d->precision == FDIPT_PREC_F16X);
+}
+static int op_precision(const FdiptDims* d) { return half_mode(d) ? FDIPT_PREC_HALF : d->precision; }
+
 static bool dims_ok(const FdiptDims* d) {
   return d && d->num_blocks >= 1 && d->num_blocks <= FD_MAX_BLOCKS && d->tfmr_layers >= 1 && d->tfmr_layers <= FD_MAX_TL &&
          d->c_s > 0 && (d->c_s % 8) == 0 && d->c_z > 0 && (d->c_z % 8) == 0 && d->no_heads > 0 && d->no_heads <= 16 &&
          d->index_embed == 32 && d->num_bins >= 0 && d->num_bins < 64 && (d->c_skip % 8) == 0 &&
-         (d->precision == FDIPT_PREC_F32 || d->precision == FDIPT_PREC_HALF) && (d->kernel_flags & ~FDIPT_KF_ALL) == 0;
+         (d->precision == FDIPT_PREC_F32 || half_mode(d)) && (d->kernel_flags & ~FDIPT_KF_ALL) == 0;
 }
 
 static void build_inventory(const FdiptDims* d, Inventory& iv) {
@@ -107,12 +115,13 @@ struct DChain {  // weight images of the fused node-path chains (chain.hip, rowb
   size_t inp[FD_MAX_TL], outp[FD_MAX_TL], l1[FD_MAX_TL], l2[FD_MAX_TL], post, t1, t2, t3, et_init, a1af, b1f, r4w, r4b;
   unsigned t23_run;  // run t2 | t3
 };
-struct DBlock { size_t wq_m, wproj2_img, wproj2_img_lo, bproj2, wproj2p_img, wproj2p_img_lo, bproj2p, wout_m, bout_m, wout_img, wout_img_lo, wproj, wproj_img, wproj_img_lo, bproj, gamma, wb, bb, wb_img3, wb_img4, et3, et4, wdz_t, wdz_img, wdz_img_lo, wdz_imgp, wdz_imgp_lo; DChain ch; DSplit lo; };
+struct DBlock { size_t wq_m, wproj2_img, wproj2_img_lo, bproj2, wproj2p_img, wproj2p_img_lo, bproj2p, wout_m, bout_m, wout_img, wout_img_lo, wproj, wproj_img, wproj_img_lo, bproj, gamma, wb, bb, wb_img3, wb_img4, et3, et4, et4x, wdz_t, wdz_img, wdz_img_lo, wdz_imgp, wdz_imgp_lo; DChain ch; DSplit lo; };
 struct DLayout {
   size_t h16_base;   // bf16 image of the whole fp32 blob (bf16 mode): element offset == fp32 element offset
   size_t ne0_pad;     // [cs, kn_pad] operand precision
   size_t w1i, w1j, w1r, dtab, edges, b1;  // fp32 pieces of the concat-free first edge-embedder layer
   size_t ee2;         // LDS images of edge-embedder layers 2/3 (register-resident bf16 kernel)
+  size_t ee2x;        // fp16x: the same, followed by their lo images
   size_t ch_ne0, ch_ne2, ch_ne4, ch_tor1, ch_tor2;  // chain images: node embedder, torsion head
   size_t lo_ne0, lo_ne2, lo_ne4, lo_tor1, lo_tor2;  // lo images: node embedder, torsion head
   size_t skip16[2];                                 // ... of the stacked skip_embed matrices [num_blocks * c_skip = 256, c_s] (fused into the node embedder)
@@ -130,17 +139,22 @@ struct DLayout {
 // the register-resident half-precision pair kernels (edge_transition3/4.hip, edge_embed2) are compiled for the reference widths only:
 // the edge embedder's LDS images, the EdgeTransition weight streams
 static bool use_regpair(const FdiptDims* d) {
-  return d->precision == FDIPT_PREC_HALF && d->c_z == 128 && d->c_s == 256 && !(d->kernel_flags & FDIPT_KF_GENERIC_PAIR);
+  return half_mode(d) && d->c_z == 128 && d->c_s == 256 && !(d->kernel_flags & FDIPT_KF_GENERIC_PAIR);
 }
+// fp16x: edge_transition4's weight stream with the final layer's lo fragments (fd_et4_build_stream lo = 1) in place of the plain one;
+// no edge_transition3 stream (fp16x refuses every plan that would run it)
+static bool et4x_stream(const FdiptDims* d) { return use_regpair(d) && d->precision == FDIPT_PREC_F16X; }
+// fp16x: the edge embedder's layer-2/3 images followed by their lo images (fd_ee2_build_images lo = 1) in place of the plain ones
+static bool ee2x_images(const FdiptDims* d) { return use_regpair(d) && d->precision == FDIPT_PREC_F16X; }
 // fused node-path kernels (chain.hip, rowblock.hip) are compiled for the reference widths only: their 32-row images, the lo images of
 // split operands and the 16-row images.  (c_s 256, c_skip 64, c_z 128 fix d_t 320, cb 128, hid 384: the shapes of the 16-row kernels)
 static bool use_chain(const FdiptDims* d) {
-  return d->precision == FDIPT_PREC_HALF && d->c_s == 256 && d->c_skip == 64 && d->c_z == 128 && !(d->kernel_flags & FDIPT_KF_UNFUSED_NODE);
+  return half_mode(d) && d->c_s == 256 && d->c_skip == 64 && d->c_z == 128 && !(d->kernel_flags & FDIPT_KF_UNFUSED_NODE);
 }
 // the stacked skip_embed matrices as 16-row images: a fourth layer of the 16-row node embedder, 256 rows
 static bool skip16_image(const FdiptDims* d) { return use_chain(d) && d->num_blocks * d->c_skip == 256; }
 // the fused IPA projection as fragment images, zero-padded to whole 128-column blocks (ipa_proj2.hip: K = c_s = 256)
-static bool proj_image(const FdiptDims* d) { return d->precision == FDIPT_PREC_HALF && d->c_s == 256; }
+static bool proj_image(const FdiptDims* d) { return half_mode(d) && d->c_s == 256; }
 // merged IPA projections (ForwardPlan::merged; the o columns of linear_out keep their width: H c_s = H C): q', its bias and the
 // merged linear_out
 static bool merged_weights(const FdiptDims* d) { return d->c_s == d->c_hidden; }
@@ -287,7 +301,7 @@ struct Blob {
 static int blob_walk(const FdiptDims* d, const Inventory& iv, DLayout& L, const float* P = nullptr, char* D = nullptr, hipStream_t st = nullptr) {
   Blob w{P, D, st};
   L = DLayout{};
-  L.esz = d->precision == FDIPT_PREC_HALF ? 2 : 4;
+  L.esz = half_mode(d) ? 2 : 4;
   L.kn_pad = rup8(iv.node_in);
   L.d1_pad = rup8(iv.d1);
   const int esz = L.esz, cs = d->c_s, cz = d->c_z, E = d->index_embed, H = d->no_heads, C = d->c_hidden, cb = iv.cb, hid = iv.hid;
@@ -301,7 +315,7 @@ static int blob_walk(const FdiptDims* d, const Inventory& iv, DLayout& L, const 
   auto chain16 = [&](const LinW& l, int lo) {
     return w.img(true, fd_chain_image_bytes(l.out, l.in), [&](char* at) { return fd_chain_build_image16(P + l.w, l.out, l.in, l.in, l.in, lo, at, st); });
   };
-  L.h16_base = w.img(d->precision == FDIPT_PREC_HALF, (size_t)iv.offsets.back() * 2,
+  L.h16_base = w.img(half_mode(d), (size_t)iv.offsets.back() * 2,
                      [&](char* at) { return fd_f32_to_half(iv.offsets.back(), P, (half_t*)at, st); });
   // the node embedder's first layer [c_s, kn_pad] in operand precision; fp32 pieces of the concat-free first edge-embedder layer: the e_i,
   // e_j and relative-position columns, the distogram table [num_bins + 1, c_z] with the bin edges (one launch writes both; neither exists
@@ -319,7 +333,8 @@ static int blob_walk(const FdiptDims* d, const Inventory& iv, DLayout& L, const 
     return FDIPT_OK;
   });
   L.b1 = w.img(true, (size_t)cz * 4, [&](char* at) { return vec(iv.ee0.b, cz, at); });
-  L.ee2 = w.img(use_regpair(d), fd_ee2_image_bytes(), [&](char* at) { return fd_ee2_build_images(P + iv.ee2.w, P + iv.ee4.w, at, st); });
+  L.ee2 = w.img(use_regpair(d) && !ee2x_images(d), fd_ee2_image_bytes(), [&](char* at) { return fd_ee2_build_images(P + iv.ee2.w, P + iv.ee4.w, at, st); });
+  L.ee2x = w.img(ee2x_images(d), fd_ee2_image_bytes(1), [&](char* at) { return fd_ee2_build_images(P + iv.ee2.w, P + iv.ee4.w, at, st, 1); });
   for (int b = 0; b < d->num_blocks; ++b) {
     const BlockW& k = iv.blk[b];
     DBlock& db = L.blk[b];
@@ -418,14 +433,16 @@ static int blob_walk(const FdiptDims* d, const Inventory& iv, DLayout& L, const 
     db.wdz_img_lo = dz_img(0, 1);
     db.wdz_imgp = dz_img(1, 0);
     db.wdz_imgp_lo = dz_img(1, 1);
-    w.step(b > 0 && use_regpair(d), [&] { return fd_et4_set_dz(D + L.blk[b - 1].et4, D + db.wdz_imgp, D + db.wdz_imgp_lo, st); });
+    w.step(b > 0 && use_regpair(d) && !et4x_stream(d), [&] { return fd_et4_set_dz(D + L.blk[b - 1].et4, D + db.wdz_imgp, D + db.wdz_imgp_lo, st); });
+    w.step(b > 0 && et4x_stream(d), [&] { return fd_et4_set_dz(D + L.blk[b - 1].et4x, D + db.wdz_imgp, D + db.wdz_imgp_lo, st, 1); });
     db.wdz_t = w.img(true, (size_t)cz * (cz / 4) * 4, [&](char* at) {  // (transposed for coalesced reads in opair_kernel)
       hipLaunchKernelGGL(transpose_kernel, dim3(16), dim3(256), 0, st, cz / 4, cz, P + k.dz.w, (float*)at);
       FD_CHECK_LAUNCH();
       return FDIPT_OK;
     });
-    db.et3 = w.img(use_regpair(d) && trunk, fd_et3_stream_bytes(), [&](char* at) { return fd_et3_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, at, st); });
-    db.et4 = w.img(use_regpair(d) && trunk, fd_et4_stream_bytes(), [&](char* at) { return fd_et4_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, at, st); });
+    db.et3 = w.img(use_regpair(d) && !et4x_stream(d) && trunk, fd_et3_stream_bytes(), [&](char* at) { return fd_et3_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, at, st); });
+    db.et4 = w.img(use_regpair(d) && !et4x_stream(d) && trunk, fd_et4_stream_bytes(), [&](char* at) { return fd_et4_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, at, st); });
+    db.et4x = w.img(et4x_stream(d) && trunk, fd_et4_stream_bytes(1), [&](char* at) { return fd_et4_build_stream(P + k.et1.w, P + k.et2.w, P + k.etf.w, at, st, 1); });
     if (!use_chain(d)) continue;
     // ---- the fused node path: 32-row images (hi), lo images of the split operands, 16-row images (hi, lo)
     // [W1[:, e_i]; Wf[:, e_i]; W1[:, e_j]; Wf[:, e_j]] of EdgeTransition's first / final layers, the first `parts` of them stacked
@@ -672,6 +689,8 @@ struct ForwardPlan {
   bool torf_fused, bb_fold;
   bool regpair;                        // register-resident pair kernels (edge_embed2, edge_transition3/4)
   bool ipa_bias_f32, ipa_attn_f32;     // fp32 mode: the one-pass pair bias, the register-score IPA attention (where it takes the call)
+  bool x;                              // fp16x: edge_transition4 on the lo stream (et4x)
+  bool refused;                        // fp16x: the plan would run a kernel without its split terms (the forward answers FDIPT_EINVAL)
 };
 static const char kImage = 0;  // stands for an operand image in the probe arguments below (the predicates test only that it is set)
 
@@ -682,7 +701,7 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   const int Np = (N + 31) / 32 * 32;
   ForwardPlan p = {};
   p.op = op;
-  p.bf = d->precision == FDIPT_PREC_HALF;
+  p.bf = half_mode(d);
   // fused chains (chain.hip) where they beat the GEMM + LayerNorm launches they replace at B*N ~ 2400 rows on MI355X
   // (profiles/r01_chain_vs_gemm.md): post_tfmr and EdgeTransition.initial_embed when the row-block kernels do not take them
   p.chain = use_chain(d);
@@ -719,7 +738,7 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   // kernels' N <= 1024 wherever this plan tests a length (IPA attention, o_pair, pair bias producers, sequence attention)
   p.stream = (f & FDIPT_KF_STREAM_ATTN) && p.bf && !generic_attn && N <= 2048;
   const int n_attn = p.stream ? 2048 : 1024;  // the attention kernels' bound on N
-  const bool opair_mfma = fd_opair_mfma_eligible(d->precision, oa, p.stream);
+  const bool opair_mfma = fd_opair_mfma_eligible(op_precision(d), oa, p.stream);
   p.a3 = p.bf && cz == 128 && C == 256 && Pq == 8 && Pv == 12 && !generic_attn &&
          (p.stream ? fd_attention3_stream_supported(a3) : fd_attention3_supported(a3));
   p.probs_h16 = p.a3 && opair_mfma && 2 * Np <= 4 * N;
@@ -794,6 +813,14 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   // the last torsion layer (Linear(c_s, 2), fp32) and the backbone atoms ride on the score launch (FDIPT_KF_UNFOLDED: own launches)
   p.torf_fused = (cs & 3) == 0 && !unfolded;
   p.bb_fold = !unfolded;
+  // fp16x runs only where its split kernel takes every EdgeTransition, with split operands on the node path; the flags that swap out
+  // the split kernels (include/fdipt.h) are refused as well, whichever kernels they would touch at this shape
+  p.x = d->precision == FDIPT_PREC_F16X;
+  const unsigned x_refused = FDIPT_KF_ET3 | FDIPT_KF_GENERIC_PAIR | FDIPT_KF_GENERIC_ATTN | FDIPT_KF_UNFUSED_NODE | FDIPT_KF_NO_SPLIT |
+                             FDIPT_KF_STREAM_ATTN;
+  // (the EdgeTransition test only where one runs: the embedder's per-op entry takes any N; N > 1024 is the key-streaming kernels' range)
+  const bool runs_et = op == OP_ALL || op == OP_ET;
+  p.refused = p.x && ((f & x_refused) || (runs_et && p.et != ET_ET4) || !p.split || N > 1024);
   return p;
 }
 
@@ -821,7 +848,7 @@ struct Fwd {
   // operand-precision view of a weight matrix of the fp32 blob
   const void* WM(const LinW& l) const { return p.bf ? (const void*)((const half_t*)(D + L.h16_base) + l.w) : (const void*)(P + l.w); }
   int lin(const LinW& l, const float* A, int lda, const float* res, int ldr, const float* rm, int relu, float* out, int ldo) const {
-    return fd_linear(d->precision, R, l.out, l.in, A, lda, WM(l), l.in, P + l.b, res, ldr, rm, relu, out, ldo, st);
+    return fd_linear(op_precision(d), R, l.out, l.in, A, lda, WM(l), l.in, P + l.b, res, ldr, rm, relu, out, ldo, st);
   }
   int lin32(const LinW& l, const float* A, int lda, float* out, int ldo) const {
     return fd_linear(FDIPT_PREC_F32, R, l.out, l.in, A, lda, P + l.w, l.in, P + l.b, nullptr, 0, nullptr, 0, out, ldo, st);
@@ -882,7 +909,7 @@ struct Fwd {
                       F(w.trans), F(w.dmask), (const float*)(D + L.w1i), (const float*)(D + L.w1j), (const float*)(D + L.b1), cz,
                       p.feats_fused ? F(w.pi) : nullptr, F(w.pj), a->step_cursor, st));
     if (p.embed == NF_GEMM) {
-      RC(fd_linear(d->precision, R, cs, L.kn_pad, F(w.node_feat), L.kn_pad, D + L.ne0_pad, L.kn_pad, P + iv.ne0.b, nullptr, 0, nullptr, 1,
+      RC(fd_linear(op_precision(d), R, cs, L.kn_pad, F(w.node_feat), L.kn_pad, D + L.ne0_pad, L.kn_pad, P + iv.ne0.b, nullptr, 0, nullptr, 1,
                    F(w.h_a), cs, st));
       RC(lin(iv.ne2, F(w.h_a), cs, nullptr, 0, nullptr, 1, F(w.h_b), cs));
       RC(lin(iv.ne4, F(w.h_b), cs, nullptr, 0, nullptr, 0, F(w.h_a), cs));
@@ -925,8 +952,8 @@ struct Fwd {
     if (p.pz) {
       ea.wdz_img = D + L.blk[0].wdz_imgp; ea.wdz_img_lo = D + L.blk[0].wdz_imgp_lo; ea.bdz = P + iv.blk[0].dz.b; ea.pz_out = (half_t*)(W + w.pz);
     }
-    if (p.regpair) RC(fd_edge_embed2(ea, D + L.ee2, st));
-    else RC(fd_edge_embed(d->precision, cz, ea, st));
+    if (p.regpair) RC(fd_edge_embed2(ea, D + (p.x ? L.ee2x : L.ee2), st, p.x));
+    else RC(fd_edge_embed(op_precision(d), cz, ea, st));
     return FDIPT_OK;
   }
   // ---- IPA (ipa_pytorch.py:244-330), part 1: the fused q | kv | q_pts | kv_pts projection and the global-frame points
@@ -938,7 +965,7 @@ struct Fwd {
     pa.qp = F(w.qp); pa.kp = F(w.kp); pa.vp = F(w.vp); pa.rot = F(w.rot);
     pa.vpt = p.vpt ? (unsigned short*)(W + w.vpt) : nullptr; pa.Np = Np;
     if (!p.a3) {  // fp32 activations for the LDS / register attention kernels
-      RC(fd_linear(d->precision, R, iv.proj_out, cs, node, cs, D + db.wproj, cs, (const float*)(D + db.bproj), nullptr, 0,
+      RC(fd_linear(op_precision(d), R, iv.proj_out, cs, node, cs, D + db.wproj, cs, (const float*)(D + db.bproj), nullptr, 0,
                    nullptr, 0, F(w.proj), iv.proj_out, st));
       pa.proj = F(w.proj); pa.ld = iv.proj_out; pa.q_off = 3 * H * C; pa.kv_off = 3 * H * C + 3 * H * Pq;
       return fd_points(pa, st);
@@ -1021,16 +1048,16 @@ struct Fwd {
       if (p.ipa_bias_f32)
         RC(fd_pair_bias_f32((long)NN, H, cz, F(w.z), (const float*)(D + db.wb), (const float*)(D + db.bb), F(w.bias), st));  // [B,N,N,H]
       else
-        RC(fd_linear_z(d->precision, (long)NN, H, cz, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), st));  // [B,N,N,H]
+        RC(fd_linear_z(op_precision(d), (long)NN, H, cz, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), st));  // [B,N,N,H]
       if (p.ipa_attn_f32 && fd_ipa_attention_f32_supported(aa)) RC(fd_ipa_attention_f32(aa, st));  // scores in registers (round 5)
-      else RC(fd_attention(d->precision, 1, aa, st));
+      else RC(fd_attention(op_precision(d), 1, aa, st));
     }
     if (p.pz) {  // (z itself may not have been stored)
       if (!oa.probs_h16) return FDIPT_EINVAL;
       oa.pz = (const half_t*)(W + w.pz);
       return fd_opair_pz(oa, st);
     }
-    return fd_opair(d->precision, oa, st, p.stream);
+    return fd_opair(op_precision(d), oa, st, p.stream);
   }
   // ---- IPA, part 3: node = LN(node + linear_out(features)) in tf_in[:, :cs]; tf_in[:, cs:] = skip_embed(init_node)   (ipa:531-535)
   int ipa_out(int b, const float* node) const {
@@ -1089,7 +1116,7 @@ struct Fwd {
         ta.C = hd; ta.Dv = hd; ta.scale = 1.0f / sqrtf((float)hd); ta.res_mask = res_mask; ta.out = F(w.att); ta.out_ld = dt;
         if (p.seq == SEQ_BF16) RC(fd_seq_attention(B, N, th, F(w.qkv), 3 * dt, ta.scale, res_mask, W + w.seqimg, F(w.att), dt, st, p.stream));
         else if (p.seq == SEQ_F32) RC(fd_seq_attention_f32(B, N, th, F(w.qkv), 3 * dt, ta.scale, res_mask, F(w.att), dt, st));
-        else RC(fd_attention(d->precision, 0, ta, st));
+        else RC(fd_attention(op_precision(d), 0, ta, st));
       }
       // x_a = norm1(x + out_proj(att)); x_b = norm2(x_a + linear2(relu(linear1(x_a))))
       if (p.tail == NF_GEMM) {
@@ -1207,7 +1234,7 @@ struct Fwd {
       ET2Args t2;
       t2.B = B; t2.N = N; t2.z_in = (const half_t*)(W + w.z); t2.z_out = (half_t*)(W + w.z); t2.e = F(w.e);
       t2.e_h16 = (const half_t*)(W + w.e_bf);
-      t2.a1 = F(w.a1); t2.af = F(w.af); t2.stream = D + (p.et == ET_ET4 ? db.et4 : db.et3); t2.b2 = P + k.et2.b; t2.gamma = P + k.et_ln.g;
+      t2.a1 = F(w.a1); t2.af = F(w.af); t2.stream = D + (p.et == ET_ET3 ? db.et3 : p.x ? db.et4x : db.et4); t2.b2 = P + k.et2.b; t2.gamma = P + k.et_ln.g;
       t2.beta = P + k.et_ln.b; t2.res_mask = a->res_mask; t2.trace = tr_ptr;
       // the next block's attention consumes linear_b(z') in fragment order when it runs attention3
       // (end to end +0.8 % at N = 300: the launch grows by about as much as the pair_bias2 launch it replaces, the gain
@@ -1222,14 +1249,14 @@ struct Fwd {
         if (b + 1 == d->num_blocks - 1 && !tr_ptr) t2.z_out = nullptr;
       }
       t2.clock = a->clock_out;
-      if (p.et == ET_ET4) RC(fd_edge_transition4(t2, st));
+      if (p.et == ET_ET4) RC(fd_edge_transition4(t2, st, p.x));
       else RC(fd_edge_transition3(t2, st));
     } else {
       EdgeTransArgs ta;
       ta.B = B; ta.N = N; ta.z_in = W + w.z; ta.z_out = W + w.z; ta.e = F(w.e);
       ta.w1 = WM(k.et1); ta.w2 = WM(k.et2); ta.wf = WM(k.etf); ta.b1 = P + k.et1.b; ta.b2 = P + k.et2.b; ta.bf = P + k.etf.b;
       ta.gamma = P + k.et_ln.g; ta.beta = P + k.et_ln.b; ta.res_mask = a->res_mask; ta.trace = tr_ptr; ta.clock = a->clock_out;
-      RC(fd_edge_transition(d->precision, cz, iv.cb, ta, st));
+      RC(fd_edge_transition(op_precision(d), cz, iv.cb, ta, st));
     }
     if (a->ev_stop && a->ev_stop[b]) hipEventRecord((hipEvent_t)a->ev_stop[b], st);
     return FDIPT_OK;
@@ -1289,6 +1316,7 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
   if (workspace_bytes < w.total) return FDIPT_ESIZE;
   if ((long)B * N * N > 2000000000L / 1) return FDIPT_ESIZE;
   const ForwardPlan p = plan_forward(d, iv, L, B, N, op.kind);
+  if (p.refused) return FDIPT_EINVAL;
   const Fwd f = {d, iv, L, w, p, P, (const char*)derived, (char*)workspace, setup, a, (hipStream_t)stream, B, N, R, (N + 31) / 32 * 32, (size_t)R * N};
   if (a->trace_inner && (p.rbk || p.outproj != OUT_GEMM)) return FDIPT_EINVAL;  // fused node path: the tensors never exist
   const size_t node_bytes = (size_t)R * d->c_s * 4, z_bytes = f.NN * d->c_z * L.esz;
@@ -1334,7 +1362,7 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
     RC(fd_linear_splitk_split(R, nsk, cs, 1, f.F(w.node0), cs, (const float*)(f.D + L.skip_w32), cs, (const float*)(f.D + L.skip_b),
                               nullptr, f.F(w.skip_all), 0, nsk, f.st));
   else if (p.skip == SKIP_GEMM)
-    RC(fd_linear(d->precision, R, nsk, cs, f.F(w.node0), cs, f.D + L.skip_w, cs, (const float*)(f.D + L.skip_b), nullptr, 0,
+    RC(fd_linear(op_precision(d), R, nsk, cs, f.F(w.node0), cs, f.D + L.skip_w, cs, (const float*)(f.D + L.skip_b), nullptr, 0,
                  nullptr, 0, f.F(w.skip_all), nsk, f.st));
   const float* node = f.F(w.node0);
   for (int b = 0; b < d->num_blocks; ++b) {

@@ -17,6 +17,7 @@ from .. import _lib, embedding, residue_tables, weights
 
 
 PRECISIONS = {"fp32": _lib.PREC_F32, "f32": _lib.PREC_F32, "fp16": _lib.PREC_F16, "f16": _lib.PREC_F16,
+              "fp16x": _lib.PREC_F16X, "f16x": _lib.PREC_F16X,
               "bf16": _lib.PREC_BF16}  # bf16: only with a library built with -DFDIPT_HALF_BF16
 
 
@@ -123,7 +124,9 @@ class ScoreNetwork:
     def __init__(self, model_conf, diffuser, inpainting: bool = False, precision: str = "fp32", device=None,
                  kernel_flags: int = 0):
         """``precision``: "fp32" (exact fp32 FMA chains, any width) or "fp16" (fp16 MFMA operands and pair representation,
-        fp32 accumulation / frames / statistics: the throughput mode).  ``kernel_flags``: ``_lib.KF_*`` bits."""
+        fp32 accumulation / frames / statistics: the throughput mode) or "fp16x" (the fp16 mode plus split hi + lo weight terms in the
+        EdgeTransition's final layer and the edge embedder's layers 2 and 3: inside the 1e-3 A step bar at BackboneUpdate gain 0.5, where fp16
+        is not; reference widths, N <= 1024, N % 4 == 0).  ``kernel_flags``: ``_lib.KF_*`` bits."""
         self._model_conf = model_conf
         self.diffuser = diffuser
         self.inpainting = inpainting

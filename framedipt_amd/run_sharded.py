@@ -195,7 +195,7 @@ def main():
     ap.add_argument("--min-t", type=float, default=0.01)
     ap.add_argument("--noise-scale", type=float, default=0.1)
     ap.add_argument("--max-batch", type=int, default=8)
-    ap.add_argument("--precision", default="fp16", choices=["fp16", "fp32"])
+    ap.add_argument("--precision", default="fp16", choices=["fp16", "fp16x", "fp32"])
     ap.add_argument("--kernel-flags", type=int, default=0, help="FdiptDims.kernel_flags (_lib.KF_*); 1024 = KF_STREAM_ATTN: fp16 chains up to 2048")
     ap.add_argument("--seed", type=int, default=123)
     ap.add_argument("--weights-seed", type=int, default=7, help="synthetic weights (no checkpoint is available offline)")

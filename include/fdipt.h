@@ -41,6 +41,16 @@ extern "C" {
 #define FDIPT_PREC_F16 2  /* v_mfma_f32_32x32x16_f16: fp16 operands (11 significant bits, same MFMA rate as bf16), pair
                              rep kept in fp16; frames, points, softmax statistics, LayerNorm and scores stay fp32/fp64.
                              Throughput mode of the default build */
+#define FDIPT_PREC_F16X 3 /* the fp16 mode plus split (hi + lo) weight terms where its own operand rounding costs most: the
+                             EdgeTransition final layer and the edge embedder's layers 2 and 3 run W_lo h alongside W_hi h
+                             (W_lo = W - fp16(W)).  Same parameters as FDIPT_PREC_F16, a different derived blob; pair rep in fp16.
+                             Default build only (the -DFDIPT_HALF_BF16 library answers FDIPT_EINVAL).  Reference widths and N <= 1024
+                             only; the forward and fdipt_edge_transition_fwd also need edge_transition4 (N % 4 == 0, N >= 8), while
+                             fdipt_edge_embed_fwd takes any N.  FDIPT_EINVAL from the forward and the per-op entries otherwise,
+                             and for every flag that swaps out a split kernel or the split operands: FDIPT_KF_ET3,
+                             FDIPT_KF_GENERIC_PAIR, FDIPT_KF_GENERIC_ATTN, FDIPT_KF_UNFUSED_NODE, FDIPT_KF_NO_SPLIT,
+                             FDIPT_KF_STREAM_ATTN.  Accepted flags: FDIPT_KF_UNFOLDED, FDIPT_KF_NO_MERGE, FDIPT_KF_ROWS32,
+                             FDIPT_KF_PASS_Z, FDIPT_KF_POINTS_LAUNCH */
 
 /* FdiptDims.kernel_flags: run a fallback path of the half-precision mode at shapes where the default selection would not
  * (each of them is what some other shape uses anyway; parity tests run them at the golden sizes).  Same flags for
