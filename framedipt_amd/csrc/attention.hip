@@ -459,13 +459,6 @@ __global__ __launch_bounds__(FD_THREADS) void opair_kernel(OPairArgs a) {
 // CU.  NH passes over the key range (round 2): longer rows are taken in two passes of 32 groups (N <= 1024) so that the pieces of a
 // pass fit 128 registers and TWO blocks share a CU and overlap each other's memory round trips - a single 64-group pass (256
 // registers, one block per CU) streamed z at 2.7 TB/s at N = 724.
-template <int N_, class F>
-__device__ __forceinline__ void om_for(F&& f) {
-  if constexpr (N_ > 0) {
-    om_for<N_ - 1>(f);
-    f(std::integral_constant<int, N_ - 1>{});
-  }
-}
 // SB (round 4): ONE Zt buffer (two barriers per chunk instead of one), the cross-wave exchange tile `red` overlays it, and the down_z
 // fragments are requested after the main loop instead of at the top: 24 KB of LDS and <= 128 registers -> FOUR blocks per CU instead
 // of three.  A row is a latency chain (HBM round trip, five chunk hand-overs, a serial tail on one wave) whose matrix work is 2 % of
@@ -580,7 +573,7 @@ __global__ __launch_bounds__(FD_THREADS, LB) void opair_mfma_kernel(OPairArgs a,
         __syncthreads();
       }
     };
-    om_for<OM_NK / 4>(chunk);
+    fd_static_for<OM_NK / 4>(chunk);
   }
   if (SB && wave == 0) wdz_load();  // (in flight across the exchange barrier)
   // D[h, Zt row]: lane (row 32 wave + li, hi) holds heads 4 hi + r in registers r < 4; row 16 e + cg = channel 8 cg + e
@@ -724,8 +717,6 @@ int fd_opair_pz(const OPairArgs& a, hipStream_t st) {
 
 // ------------------------------------------------------------------ projected points -> global frame
 
-__device__ __forceinline__ int pt_perm16(int pos) { return 4 * (pos >> 3) + (pos & 3) + 8 * ((pos & 7) >> 2); }
-
 __global__ void points_kernel(PointsArgs a) {
   const long r = blockIdx.x;  // residue row b*N+i
   const int tid = threadIdx.x;
@@ -760,7 +751,7 @@ __global__ void points_kernel(PointsArgs a) {
       const int pp2 = p - HPq, hh = pp2 / Pkv, e = pp2 % Pkv;
       if (e >= a.Pq) {  // a value point: coordinates 3 (e - Pq) + {0,1,2} of head hh, key = residue index in its sample
         const long bidx = r / a.N;
-        const int key = (int)(r - bidx * a.N), pos = (key & ~15) + pt_perm16(key & 15), ks = a.Np >> 4;
+        const int key = (int)(r - bidx * a.N), pos = (key & ~15) + fd_perm16(key & 15), ks = a.Np >> 4;
         const float g3[3] = {gx, gy, gz};
         for (int c = 0; c < 3; ++c) {
           const int row = 3 * (e - a.Pq) + c;
@@ -828,7 +819,7 @@ __global__ __launch_bounds__(256) void points16_kernel(PointsArgs a) {
       } else {
         const int ln = u & 63, hf = ln >> 5, cc = 32 * (u >> 6) + (ln & 31);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {  // slot 8 hf + e of the 16-group -> key (inverse of pt_perm16)
+        for (int e = 0; e < 8; ++e) {  // slot 8 hf + e of the 16-group -> key (inverse of fd_perm16)
           const int sl = 8 * hf + e, pos = 8 * ((sl >> 2) & 1) + 4 * (sl >> 3) + (sl & 3), ky = 16 * g + pos;
           nx[8 * q + e] = a.node[((long)b * a.N + (ky < a.N ? ky : a.N - 1)) * a.ld_node + cc];
         }
@@ -836,14 +827,14 @@ __global__ __launch_bounds__(256) void points16_kernel(PointsArgs a) {
     }
   }
   if (!live)  // keys beyond the sample: their slots of the image stay zero
-    for (int v = sub; v < HH * 72; v += 16) vs[v * 16 + pt_perm16(kk)] = 0;
+    for (int v = sub; v < HH * 72; v += 16) vs[v * 16 + fd_perm16(kk)] = 0;
   const float w = q4[0], x = q4[1], y = q4[2], z = q4[3];
   float R[9];  // quat_to_rot (openfold/utils/rigid_utils.py:173-205), no normalisation
   R[0] = w * w + x * x - y * y - z * z; R[1] = 2 * x * y - 2 * w * z; R[2] = 2 * x * z + 2 * w * y;
   R[3] = 2 * x * y + 2 * w * z; R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * y * z - 2 * w * x;
   R[6] = 2 * x * z - 2 * w * y; R[7] = 2 * y * z + 2 * w * x; R[8] = w * w - x * x - y * y + z * z;
   if (live && half == 0 && sub < 9) a.rot[r * 9 + sub] = R[sub];
-  const int slot = pt_perm16(kk);
+  const int slot = fd_perm16(kk);
 #pragma unroll
   for (int it = 0; it < MAXI; ++it) {
     const int p = sub + 16 * it;

@@ -23,15 +23,8 @@
 #define A3_C 256
 #define A3_NTW_MAX 8  // key tiles per wave -> N <= 8 * 4 * 32 = 1024
 
-__device__ __forceinline__ hx8 a3_pack8(const float* v) {
-  hx8 o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = (fd_h)v[e];
-  return o;
-}
 // bytes of the LDS region shared by the P fragments (64 B per key) and, after them, the o_pt tile (32 x 96 floats)
 __host__ __device__ __forceinline__ int a3_pf_region(int nt) { return 2 * nt * 64 * 16 > 32 * 96 * 4 ? 2 * nt * 64 * 16 : 32 * 96 * 4; }
-__device__ __forceinline__ hx8 a3_ld(const half_t* p) { return __builtin_bit_cast(hx8, *(const u16x8*)p); }
 
 // NTW: key tiles per wave (N <= 128 NTW).  NTW = 3 (N <= 384): 234 registers -> launch bound 2 -> TWO blocks per CU hide each
 // other's memory latency, so the operands of a tile are simply fetched when needed (DB = false).  NTW = 4: one block per
@@ -94,7 +87,7 @@ __global__ __launch_bounds__(FD_THREADS, LB) void ipa_attn3_kernel(Attn3Args a) 
       __syncthreads();
     } else {
 #pragma unroll
-      for (int s = 0; s < 16; ++s) Qf[s] = a3_ld(qr + s * 512);
+      for (int s = 0; s < 16; ++s) Qf[s] = fd_frag(qr + s * 512);
     }
   }
   const float mi = a.res_mask[rb + i];
@@ -129,7 +122,7 @@ __global__ __launch_bounds__(FD_THREADS, LB) void ipa_attn3_kernel(Attn3Args a) 
   auto tile_load = [&](TileIn& ti, int t) {
     const half_t* kr = a.Kb + ((kvh * nt + t) * 16 * 64 + lane) * 8;  // fragment order (padded keys are zero rows)
 #pragma unroll
-    for (int s = 0; s < 16; ++s) ti.k[s] = a3_ld(kr + s * 512);
+    for (int s = 0; s < 16; ++s) ti.k[s] = fd_frag(kr + s * 512);
     const half_t* pr = a.kpf + ((bh * nt + t) * (FD_KPF_FRAGS * 64) + lane) * 8;  // key-point fragments (padded keys: marker in X)
 #pragma unroll
     for (int f = 0; f < FD_KPF_FRAGS; ++f) ti.kf[f] = __builtin_bit_cast(f16x8, *(const u16x8*)(pr + f * 512));
@@ -237,7 +230,7 @@ __global__ __launch_bounds__(FD_THREADS, LB) void ipa_attn3_kernel(Attn3Args a) 
           }
         }
       }
-      const hx8 p0 = a3_pack8(v), p1 = a3_pack8(v + 8);
+      const hx8 p0 = fd_pack8(v), p1 = fd_pack8(v + 8);
       Pfs[(2 * t) * 64 + lane] = __builtin_bit_cast(u16x8, p0);
       Pfs[(2 * t + 1) * 64 + lane] = __builtin_bit_cast(u16x8, p1);
       if constexpr (SPLIT) {
@@ -247,8 +240,8 @@ __global__ __launch_bounds__(FD_THREADS, LB) void ipa_attn3_kernel(Attn3Args a) 
           w[r] = v[r] - (float)p0[r];
           w[8 + r] = v[8 + r] - (float)p1[r];
         }
-        Pls[(2 * t) * 64 + lane] = __builtin_bit_cast(u16x8, a3_pack8(w));
-        Pls[(2 * t + 1) * 64 + lane] = __builtin_bit_cast(u16x8, a3_pack8(w + 8));
+        Pls[(2 * t) * 64 + lane] = __builtin_bit_cast(u16x8, fd_pack8(w));
+        Pls[(2 * t + 1) * 64 + lane] = __builtin_bit_cast(u16x8, fd_pack8(w + 8));
       }
     }
   }
@@ -267,7 +260,7 @@ __global__ __launch_bounds__(FD_THREADS, LB) void ipa_attn3_kernel(Attn3Args a) 
       constexpr int bf = decltype(BUF)::value;
 #pragma unroll
       for (int s = 0; s < KSM; ++s)
-        if (s < ks) Va[bf][s] = a3_ld(base + ((size_t)s * 64 + lane) * 8);
+        if (s < ks) Va[bf][s] = fd_frag(base + ((size_t)s * 64 + lane) * 8);
     };
     auto v_mma = [&](auto BUF, f32x16& acc) {
       constexpr int bf = decltype(BUF)::value;
@@ -487,7 +480,7 @@ __global__ __launch_bounds__(FD_THREADS, 2) void ipa_attn3_stream_kernel(Attn3Ar
     f32x4 bv[4];
     const half_t* kr = a.Kb + ((kvh * nt + t) * 16 * 64 + lane) * 8;
 #pragma unroll
-    for (int s = 0; s < 16; ++s) k[s] = a3_ld(kr + s * 512);
+    for (int s = 0; s < 16; ++s) k[s] = fd_frag(kr + s * 512);
     const half_t* pr = a.kpf + ((bh * nt + t) * (FD_KPF_FRAGS * 64) + lane) * 8;
 #pragma unroll
     for (int f = 0; f < FD_KPF_FRAGS; ++f) kf[f] = __builtin_bit_cast(f16x8, *(const u16x8*)(pr + f * 512));
@@ -588,7 +581,7 @@ __global__ __launch_bounds__(FD_THREADS, 2) void ipa_attn3_stream_kernel(Attn3Ar
             }
           }
         }
-        const hx8 p0 = a3_pack8(v), p1 = a3_pack8(v + 8);
+        const hx8 p0 = fd_pack8(v), p1 = fd_pack8(v + 8);
         Pfs[(2 * tl) * 64 + lane] = __builtin_bit_cast(u16x8, p0);
         Pfs[(2 * tl + 1) * 64 + lane] = __builtin_bit_cast(u16x8, p1);
         if constexpr (SPLIT) {
@@ -598,8 +591,8 @@ __global__ __launch_bounds__(FD_THREADS, 2) void ipa_attn3_stream_kernel(Attn3Ar
             w[r] = v[r] - (float)p0[r];
             w[8 + r] = v[8 + r] - (float)p1[r];
           }
-          Pls[(2 * tl) * 64 + lane] = __builtin_bit_cast(u16x8, a3_pack8(w));
-          Pls[(2 * tl + 1) * 64 + lane] = __builtin_bit_cast(u16x8, a3_pack8(w + 8));
+          Pls[(2 * tl) * 64 + lane] = __builtin_bit_cast(u16x8, fd_pack8(w));
+          Pls[(2 * tl + 1) * 64 + lane] = __builtin_bit_cast(u16x8, fd_pack8(w + 8));
         }
       }
     }
@@ -610,7 +603,7 @@ __global__ __launch_bounds__(FD_THREADS, 2) void ipa_attn3_stream_kernel(Attn3Ar
       const half_t* base = img + (tile * ks + s0) * 512 + lane * 8;
 #pragma unroll
       for (int s = 0; s < A3S_KC; ++s)
-        if (s < kc) Va[s] = a3_ld(base + s * 512);
+        if (s < kc) Va[s] = fd_frag(base + s * 512);
     };
     auto v_mma = [&](f32x16& acc, const u16x8* P) {
 #pragma unroll

@@ -28,11 +28,6 @@
 // the key-streaming form (FDIPT_KF_STREAM_ATTN, below): its launch
 static int seq_attention_stream_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm& wm, hipStream_t st);
 
-__host__ __device__ __forceinline__ int sa_perm16(int pos) {  // involution
-  const int hi = pos >> 3, e = pos & 7;
-  return 4 * hi + (e & 3) + 8 * (e >> 2);
-}
-
 __global__ void seq_images_kernel(int B, int N, int Np, int H, const float* __restrict__ qkv, int ld, float qscale,
                                   const float* __restrict__ res_mask,
                                   half_t* __restrict__ Qi, half_t* __restrict__ Ki, half_t* __restrict__ Vi) {
@@ -75,7 +70,7 @@ __global__ void seq_images_kernel(int B, int N, int Np, int H, const float* __re
       if (d < SA_HD) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const int pos = 16 * s + 8 * (lane >> 5) + e, key = (pos & ~15) + sa_perm16(pos & 15);
+          const int pos = 16 * s + 8 * (lane >> 5) + e, key = (pos & ~15) + fd_perm16(pos & 15);
           if (key < N) o[e] = f2h(qkv[(b * N + key) * ld + 2 * dm + h * SA_HD + d]);
         }
       }
@@ -145,7 +140,6 @@ __global__ void seq_images_init_kernel(int B, int N, int Np, int H, const float*
 #define SQ_K 320
 #define SQ_KS (SQ_K / 16)
 #define SQ_XROW (SQ_K * 2 + 16)
-typedef fd_h sa_hx4 __attribute__((ext_vector_type(4)));
 // SPLIT: the product runs on split operands (x = hi + lo, W = hi + lo: Whi.xhi + Whi.xlo + Wlo.xhi, see rowblock.hip); the
 // images still receive half-precision values (their rounding is averaged over the keys by the attention, tests/err_budget.py).
 template <bool SPLIT>
@@ -181,14 +175,14 @@ __global__ __launch_bounds__(FD_THREADS, 1) void seq_qkv_kernel(int B, int N, in
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
       const int idx = tid + k * FD_THREADS, r = idx / 80, c4 = idx % 80;
-      sa_hx4 pk, pl;
+      hx4 pk, pl;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         pk[q] = (fd_h)xv[k][q];
         pl[q] = (fd_h)(xv[k][q] - (float)pk[q]);
       }
-      *(sa_hx4*)(xs + r * SQ_XROW + 8 * c4) = pk;
-      if constexpr (SPLIT) *(sa_hx4*)(xs + XLO + r * SQ_XROW + 8 * c4) = pl;
+      *(hx4*)(xs + r * SQ_XROW + 8 * c4) = pk;
+      if constexpr (SPLIT) *(hx4*)(xs + XLO + r * SQ_XROW + 8 * c4) = pl;
     }
   }
   __syncthreads();
@@ -264,12 +258,12 @@ __global__ __launch_bounds__(FD_THREADS, 1) void seq_qkv_kernel(int B, int N, in
           const int c = isk ? f - SQ_K : f, h = c / SA_HD, cc = c - h * SA_HD;
           const f32x4 bv = bq[u][g];
           const float sc = isk ? 1.f : qscale;
-          sa_hx4 o;
+          hx4 o;
 #pragma unroll
           for (int q = 0; q < 4; ++q) o[q] = (fd_h)((acc[4 * g + q] + bv[q]) * sc);
           half_t* dst = (isk ? Ki : Qi) +
                         ((((((long)mb * H + h) * nt + (mr >> 5)) * SA_KS + (cc >> 4)) * 64 + ((cc >> 3) & 1) * 32 + (mr & 31)) << 3) + (cc & 7);
-          *(sa_hx4*)dst = o;
+          *(hx4*)dst = o;
         }
       }
     } else {
@@ -284,25 +278,17 @@ __global__ __launch_bounds__(FD_THREADS, 1) void seq_qkv_kernel(int B, int N, in
         const int m0 = row0 + 8 * g + 4 * hi;  // 4 consecutive rows = 4 consecutive keys of one sample (N % 4 == 0)
         if (m0 < M) {
           const int b0 = m0 / N, key = m0 - b0 * N;
-          const int pp = (key & ~15) + sa_perm16(key & 15);
-          sa_hx4 o;
+          const int pp = (key & ~15) + fd_perm16(key & 15);
+          hx4 o;
 #pragma unroll
           for (int q = 0; q < 4; ++q) o[q] = (fd_h)(acc[4 * g + q] + bv);
           half_t* dst = Vi + ((((((long)b0 * H + h) * SA_DT + (d >> 5)) * (2 * nt) + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (d & 31)) << 3) + (pp & 7);
-          *(sa_hx4*)dst = o;
+          *(hx4*)dst = o;
         }
       }
     }
   }
   (void)dm;
-}
-
-__device__ __forceinline__ hx8 sa_ld(const half_t* p) { return __builtin_bit_cast(hx8, *(const u16x8*)p); }
-__device__ __forceinline__ hx8 sa_pack8(const float* v) {
-  hx8 o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = (fd_h)v[e];
-  return o;
 }
 
 // SA_NTW: key tiles per wave (N <= 128 SA_NTW); with 3 the kernel fits 256 registers and two blocks share a CU (LB = 2)
@@ -339,20 +325,20 @@ __global__ __launch_bounds__(FD_THREADS, LB) void seq_attn_kernel(int B, int N, 
       const half_t* vr = Vi + (((bh * SA_DT + wave) * ks) * 64 + lane) * 8;
 #pragma unroll
       for (int s = 0; s < 8 * SA_NTW; ++s)
-        if (s < ks) Va[s] = sa_ld(vr + s * 512);
+        if (s < ks) Va[s] = fd_frag(vr + s * 512);
     }
   };
   if constexpr (EARLY_V) v_request();
   hx8 Qf[SA_KS];
 #pragma unroll
-  for (int s = 0; s < SA_KS; ++s) Qf[s] = sa_ld(Qi + (((bh * nt + qt) * SA_KS + s) * 64 + lane) * 8);
+  for (int s = 0; s < SA_KS; ++s) Qf[s] = fd_frag(Qi + (((bh * nt + qt) * SA_KS + s) * 64 + lane) * 8);
   hx8 Kf[SA_NTW][SA_KS];
 #pragma unroll
   for (int u = 0; u < SA_NTW; ++u) {
     const int t = wave + 4 * u;
     if (t < nt)
 #pragma unroll
-      for (int s = 0; s < SA_KS; ++s) Kf[u][s] = sa_ld(Ki + (((bh * nt + t) * SA_KS + s) * 64 + lane) * 8);
+      for (int s = 0; s < SA_KS; ++s) Kf[u][s] = fd_frag(Ki + (((bh * nt + t) * SA_KS + s) * 64 + lane) * 8);
   }
   // ---- scores of this wave's key tiles (mask included: channel 80)
   f32x16 S[SA_NTW];
@@ -398,8 +384,8 @@ __global__ __launch_bounds__(FD_THREADS, LB) void seq_attn_kernel(int B, int N, 
       float v[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) v[r] = S[u][r] * inv;
-      Pfs[(2 * t) * 64 + lane] = __builtin_bit_cast(u16x8, sa_pack8(v));
-      Pfs[(2 * t + 1) * 64 + lane] = __builtin_bit_cast(u16x8, sa_pack8(v + 8));
+      Pfs[(2 * t) * 64 + lane] = __builtin_bit_cast(u16x8, fd_pack8(v));
+      Pfs[(2 * t + 1) * 64 + lane] = __builtin_bit_cast(u16x8, fd_pack8(v + 8));
     }
   }
   if constexpr (!EARLY_V) v_request();
@@ -538,11 +524,11 @@ __global__ __launch_bounds__(FD_THREADS, 2) void seq_attn_stream_kernel(int B, i
   const int i = 32 * qt + li;
   hx8 Qf[SA_KS];
 #pragma unroll
-  for (int s = 0; s < SA_KS; ++s) Qf[s] = sa_ld(Qi + (((bh * nt + qt) * SA_KS + s) * 64 + lane) * 8);
+  for (int s = 0; s < SA_KS; ++s) Qf[s] = fd_frag(Qi + (((bh * nt + qt) * SA_KS + s) * 64 + lane) * 8);
   auto scores = [&](int t) {  // S^T[key, query] of key tile t (mask included: channel 80)
     hx8 Kf[SA_KS];
 #pragma unroll
-    for (int s = 0; s < SA_KS; ++s) Kf[s] = sa_ld(Ki + (((bh * nt + t) * SA_KS + s) * 64 + lane) * 8);
+    for (int s = 0; s < SA_KS; ++s) Kf[s] = fd_frag(Ki + (((bh * nt + t) * SA_KS + s) * 64 + lane) * 8);
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -599,8 +585,8 @@ __global__ __launch_bounds__(FD_THREADS, 2) void seq_attn_stream_kernel(int B, i
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = __builtin_amdgcn_exp2f((S[r] - M) * L2E) * inv;
-        Pfs[(2 * tl) * 64 + lane] = __builtin_bit_cast(u16x8, sa_pack8(v));
-        Pfs[(2 * tl + 1) * 64 + lane] = __builtin_bit_cast(u16x8, sa_pack8(v + 8));
+        Pfs[(2 * tl) * 64 + lane] = __builtin_bit_cast(u16x8, fd_pack8(v));
+        Pfs[(2 * tl + 1) * 64 + lane] = __builtin_bit_cast(u16x8, fd_pack8(v + 8));
       }
     }
     __syncthreads();  // the chunk's P fragments are complete
@@ -610,7 +596,7 @@ __global__ __launch_bounds__(FD_THREADS, 2) void seq_attn_stream_kernel(int B, i
       hx8 Va[SAS_KC];
 #pragma unroll
       for (int s = 0; s < SAS_KC; ++s)
-        if (s < kc) Va[s] = sa_ld(vr + s * 512);
+        if (s < kc) Va[s] = fd_frag(vr + s * 512);
 #pragma unroll
       for (int s = 0; s < SAS_KC; ++s)
         if (s < kc) acc = fd_mfma32(Va[s], __builtin_bit_cast(hx8, Pfs[s * 64 + lane]), acc);

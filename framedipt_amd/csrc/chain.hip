@@ -4,8 +4,9 @@
 //
 // M = B*N is only a few thousand rows, so these layers are launch/latency-bound as separate GEMM launches.  Here ONE
 // WAVE owns 32 rows for a whole chain of up to 3 Linear layers (+ReLU) + residual + LayerNorm + mask:
-//   * transposed MFMA scheme of edge_transition2.hip: D[out feature, row] = W * X^T, activations stay in registers as
-//     B fragments between layers (C/D fragment -> B fragment with the 16-wise k permutation folded into the weights);
+//   * transposed MFMA scheme of the pair kernels (common.hpp, "primitives of the register-resident kernels"):
+//     D[out feature, row] = W * X^T, activations stay in registers as B fragments between layers (C/D fragment -> B
+//     fragment with the 16-wise k permutation folded into the weights);
 //   * weight fragments are read STRAIGHT FROM L2 in fragment order ([tile][k-step][lane][8 bf16] images built at
 //     prepare time: one coalesced 1 KB load per MFMA) through a 16-deep register ring — no LDS, no barrier, waves are
 //     independent (grid = M/32 single-wave blocks spread over the CUs);
@@ -14,8 +15,6 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
-
-__host__ __device__ __forceinline__ int ch_perm16(int pos) { return 4 * (pos >> 3) + (pos & 3) + 8 * ((pos & 7) >> 2); }
 
 // ------------------------------------------------------------------ weight image
 // img[((T*KS + s)*64 + lane)*8 + e] = W[32T + (lane&31)][k], k = 16s + 8(lane>>5) + e  (natural)  or
@@ -29,7 +28,7 @@ __global__ void chain_image_kernel(const float* __restrict__ w, int N, int K, in
     const long ts = i >> 9;
     const int s = (int)(ts % KS), T = (int)(ts / KS);
     const int row = 32 * T + (lane & 31), pos = 8 * (lane >> 5) + e;
-    const int k = 16 * s + (permuted ? ch_perm16(pos) : pos);
+    const int k = 16 * s + (permuted ? fd_perm16(pos) : pos);
     const float v = (row < N && k < K) ? w[(long)row * ldw + k] * scale : 0.f;
     img[i] = lo ? f2h(v - h2f(f2h(v))) : f2h(v);
   }
@@ -63,13 +62,6 @@ int fd_chain_build_image16(const float* w, int N, int K, int Kpad, int ldw, int 
 }
 
 // ------------------------------------------------------------------ device pieces
-__device__ __forceinline__ hx8 ch_pack8(const float* v) {
-  hx8 o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = (fd_h)v[e];
-  return o;
-}
-typedef fd_h hx4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void ch_lds_t;
 typedef __attribute__((address_space(1))) const void ch_gl_t;
 
@@ -89,13 +81,6 @@ __device__ __forceinline__ void ch_wait_barrier() {  // all but the newest K vec
 }
 template <int I>
 using ch_ic = std::integral_constant<int, I>;
-template <int B, int E, class F>
-__device__ __forceinline__ void ch_static_for(F&& f) {
-  if constexpr (B < E) {
-    f(ch_ic<B>{});
-    ch_static_for<B + 1, E>(f);
-  }
-}
 
 // two output tiles of one layer, D^T[feature, row] = W X^T, from an LDS-resident fragment image of the pair:
 // [tile A: KS KB][tile B: KS KB]; the result chains into the next layer's B operand without leaving registers.
@@ -218,7 +203,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void chain_kernel(ChainArgs a) {
   hx8 X[KS0];
   {
     constexpr int NCH = (K0 + 63) / 64, GRP = 3;  // 64-column chunks, loaded GRP at a time (register pressure)
-    ch_static_for<0, (NCH + GRP - 1) / GRP>([&](auto G) {
+    fd_static_for<(NCH + GRP - 1) / GRP>([&](auto G) {
       constexpr int c0 = decltype(G)::value * GRP, c1 = c0 + GRP < NCH ? c0 + GRP : NCH;
       f32x4 xin[GRP][8];
 #pragma unroll
@@ -265,7 +250,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void chain_kernel(ChainArgs a) {
 #pragma unroll
   for (int it = 0; it < 8; ++it) S1[it] = 0.f;
 
-  ch_static_for<0, NSTEP>([&](auto I) {
+  fd_static_for<NSTEP>([&](auto I) {
     constexpr int i = decltype(I)::value;
     constexpr int l = S::layer_of(i), j = S::pair_of(i), KS = S::ks(l), tiles = S::tiles_in(i);
     constexpr bool LAST = l == NL - 1;
@@ -315,8 +300,8 @@ __global__ __launch_bounds__(FD_THREADS, 1) void chain_kernel(ChainArgs a) {
             if (RELU) v[4 * g + q] = fmaxf(v[4 * g + q], 0.f);
           }
         }
-        Hn[2 * (2 * j + u)] = ch_pack8(v);
-        Hn[2 * (2 * j + u) + 1] = ch_pack8(v + 8);
+        Hn[2 * (2 * j + u)] = fd_pack8(v);
+        Hn[2 * (2 * j + u) + 1] = fd_pack8(v + 8);
       }
     } else {
       // output pair: (acc + bias) * pre-mask -> wave-private [32 rows][64 fp32] tile (16 B unit u of row r at u ^ (r & 15))

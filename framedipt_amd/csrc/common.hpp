@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/fdipt.h"
 
@@ -21,6 +22,9 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 typedef __attribute__((ext_vector_type(4))) unsigned short u16x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
 
 // ------------------------------------------------------------------ half-precision operand type of the throughput mode
 // One 16-bit operand type per build.  Default: IEEE fp16 (v_mfma_f32_32x32x16_f16 runs at the bf16 rate with three more
@@ -77,6 +81,65 @@ __device__ __forceinline__ unsigned fd_cvt_pk(float lo, float hi) {
 }
 
 __device__ __forceinline__ int c_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+
+// ------------------------------------------------------------------ primitives of the register-resident kernels
+// The transposed scheme (D^T[feature, row] = W X^T: weights are the A operand, activations stay in registers as B fragments
+// between layers) and the LDS-DMA weight streams are built from these; a new kernel starts here, not from another kernel's file.
+//
+// position inside a 16-group of k -> feature offset inside the 16-group that the C/D fragment layout produces (an involution):
+// the C/D registers of a tile are the B fragment of the next layer up to this permutation of k, which is folded into the weight images
+__host__ __device__ __forceinline__ int fd_perm16(int pos) { return 4 * (pos >> 3) + (pos & 3) + 8 * ((pos & 7) >> 2); }
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a compile-time constant in the body
+template <int N, class F>
+__device__ __forceinline__ void fd_static_for(F&& f) {
+  if constexpr (N > 0) {
+    fd_static_for<N - 1>(f);
+    f(std::integral_constant<int, N - 1>{});
+  }
+}
+// One 16 B-per-lane LDS-DMA (global_load_lds_dwordx4; LDS destination = wave-uniform `lds_dst` + lane * 16), written as
+// inline asm ON PURPOSE: hipcc's waitcnt pass treats the builtin as a FLAT access that is pending on both counters and
+// then forces EVERY later LDS wait to lgkmcnt(0) until the DMA has been waited for.  With the asm form the pass does not see
+// the DMA at all: every consumer of DMA'd data therefore sits behind an explicit fd_dma_wait() + barrier.
+// Two address forms.  Kernels whose only LDS is the dynamic segment (it starts at 0) address it by 32-bit byte offsets
+// throughout: no generic pointers, no address-space casts with their null checks.  The others pass a generic LDS pointer.
+__device__ __forceinline__ void fd_dma16(const void* gsrc, unsigned lds_dst) {
+  const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_dst);
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(m0v), "v"(gsrc) : "memory", "m0");
+}
+__device__ __forceinline__ void fd_dma16(const void* gsrc, const char* lds_dst) {
+  fd_dma16(gsrc, (unsigned)(unsigned long)(const __attribute__((address_space(3))) char*)lds_dst);
+}
+__device__ __forceinline__ void fd_dma_wait() {  // every DMA (and ordinary vector-memory op) of this wave retired
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), the other counters left alone
+  __builtin_amdgcn_sched_barrier(0);
+}
+// one 16 B operand fragment (8 half values of this lane): from memory (global or a generic LDS pointer) / from an LDS byte offset
+typedef const __attribute__((address_space(3))) u16x8* fd_lds_u16x8;
+typedef const __attribute__((address_space(3))) f32x4* fd_lds_f32x4;
+__device__ __forceinline__ hx8 fd_frag(const void* p) { return __builtin_bit_cast(hx8, *(const u16x8*)p); }
+__device__ __forceinline__ hx8 fd_frag(unsigned lds_off) { return __builtin_bit_cast(hx8, *(fd_lds_u16x8)(unsigned long)lds_off); }
+__device__ __forceinline__ hx8 fd_pack8(const float* v) {  // eight floats -> one fragment
+  hx8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (fd_h)v[e];
+  return o;
+}
+// ReLU + conversion: C/D of one tile (bias already in it) -> the two B fragments it hands to the next layer.  ReLU runs after
+// the conversion, on the half-precision bit patterns as signed 16-bit integers (negative values have the sign bit set): one
+// v_pk_max_i16 per two values, 8 + 8 instructions instead of 16 + 16 + 8
+__device__ __forceinline__ void fd_hand_off(const f32x16& acc, hx8& h0, hx8& h1) {
+  u32x4 w0, w1;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    w0[k] = fd_cvt_pk(acc[2 * k], acc[2 * k + 1]);
+    w1[k] = fd_cvt_pk(acc[8 + 2 * k], acc[8 + 2 * k + 1]);
+  }
+  const s16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  h0 = __builtin_bit_cast(hx8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, w0), zero));
+  h1 = __builtin_bit_cast(hx8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, w1), zero));
+}
 
 // ------------------------------------------------------------------ precision traits
 struct PrecF32 {

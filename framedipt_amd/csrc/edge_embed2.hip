@@ -22,67 +22,25 @@
 __host__ __device__ __forceinline__ int et2_off_wide(int row, int c, int row_bytes) {
   return row * row_bytes + ((c ^ (row & 15)) << 4);
 }
-// position inside a 16-group of k  ->  feature offset inside the 16-group produced by the C/D fragment layout
-__host__ __device__ __forceinline__ int et2_perm16(int pos) {
-  const int hi = pos >> 3, e = pos & 7;
-  return 4 * hi + (e & 3) + 8 * (e >> 2);
-}
-// One 16 B-per-lane LDS-DMA (global_load_lds_dwordx4; LDS destination = wave-uniform `lds_dst` + lane * 16), written as
-// inline asm ON PURPOSE: hipcc's waitcnt pass treats the builtin as a FLAT access that is pending on both counters and
-// then forces EVERY later LDS wait to lgkmcnt(0) until the DMA has been waited for.  With the asm form the pass does not see
-// the DMA at all: every consumer of DMA'd data therefore sits behind an explicit et2_dma_wait() + barrier.
-__device__ __forceinline__ void et2_dma16(const void* gsrc, const char* lds_dst) {
-  const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(const __attribute__((address_space(3))) char*)lds_dst);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(m0v), "v"(gsrc) : "memory", "m0");
-}
-__device__ __forceinline__ void et2_dma_wait() {  // every DMA (and ordinary vector-memory op) of this wave retired
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ hx8 lds_frag(const char* slab, int off) {
-  return __builtin_bit_cast(hx8, *(const u16x8*)(slab + off));
-}
 // acc += W_slab[32 x 16*KS] * B[16*KS x 32]: A fragments stream from LDS through a DEPTH-deep register ring so that
 // every ds_read_b128 is issued DEPTH MFMAs (= DEPTH*32 cycles) ahead of its consumer.
 template <int KS, int ROWB, int DEPTH = 8, int ABL = 0>
 __device__ __forceinline__ void mma_slab(f32x16& acc, const char* slab, int li, int hi, const hx8* Bf) {
   hx8 ring[DEPTH];
 #pragma unroll
-  for (int s = 0; s < DEPTH; ++s) ring[s] = lds_frag(slab, et2_off_wide(li, 2 * s + hi, ROWB));
+  for (int s = 0; s < DEPTH; ++s) ring[s] = fd_frag(slab + et2_off_wide(li, 2 * s + hi, ROWB));
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     acc = fd_mfma32(ring[s % DEPTH], Bf[s], acc);
-    if (s + DEPTH < KS) ring[s % DEPTH] = lds_frag(slab, et2_off_wide(li, 2 * (s + DEPTH) + hi, ROWB));
+    if (s + DEPTH < KS) ring[s % DEPTH] = fd_frag(slab + et2_off_wide(li, 2 * (s + DEPTH) + hi, ROWB));
     __builtin_amdgcn_sched_barrier(0);  // pin the MFMA / ds_read interleave (hipcc otherwise sinks the reads)
   }
 }
 
 // ---- VALU-lean pieces for the embedder (its waves are issue-bound: ~1500 VALU instructions per 32-pair tile before) ----
-typedef float ee_f32x2 __attribute__((ext_vector_type(2)));
-typedef fd_h ee_hx2 __attribute__((ext_vector_type(2)));
-typedef unsigned ee_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned ee_u32x4 __attribute__((ext_vector_type(4)));
-typedef short ee_s16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned ee_cvt_pk(float lo, float hi) {  // one v_cvt_pk_bf16_f32
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(ee_f32x2{lo, hi}, ee_hx2));
-}
-// relu + bf16 of an accumulator tile (bias already in it): conversion first, then max(x, 0) on the bf16 bit patterns as signed
-// 16-bit integers (negative values have the sign bit set): 8 + 8 instructions instead of 16 + 16 + 8
-__device__ __forceinline__ void ee_hand_off(const f32x16& acc, hx8& h0, hx8& h1) {
-  ee_u32x4 w0, w1;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    w0[k] = ee_cvt_pk(acc[2 * k], acc[2 * k + 1]);
-    w1[k] = ee_cvt_pk(acc[8 + 2 * k], acc[8 + 2 * k + 1]);
-  }
-  const ee_s16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-  h0 = __builtin_bit_cast(hx8, __builtin_elementwise_max(__builtin_bit_cast(ee_s16x8, w0), zero));
-  h1 = __builtin_bit_cast(hx8, __builtin_elementwise_max(__builtin_bit_cast(ee_s16x8, w1), zero));
-}
-// LayerNorm epilogue of the embedder in packed fp32 math (one pass: sum and sum of squares; the layer bias is already in Y):
-// same staging / stores / pair-bias emission as ln_epilogue_staged
+// LayerNorm epilogue of the embedder in packed fp32 math (one pass: sum and sum of squares; the layer bias is already in Y).  z' is
+// staged in the wave's LDS tile and stored as whole 64 B row segments; the first block's pair bias comes from the same fragments.
 // pz_tile (round 6): when set, the epilogue also emits pair_z = down_z(z') + b of the first block's IPA for this row's 32 keys (8 key
 // groups of 256 B, layout fd_pz_bytes; groups >= ng_valid are beyond N): z' is the A operand of these MFMAs, so a lane (d, half) ends
 // up with four consecutive keys per register quad = 8 B of the image; hi + lo weight fragments follow the compact linear_b image in LDS
@@ -92,12 +50,12 @@ __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamm
                                                float* __restrict__ tr_row, bool valid, const char* wb_lds, const f32x4 bbv,
                                                float* __restrict__ bias_out, int H, long bidx, int ii, int jj, int nt,
                                                half_t* __restrict__ pz_tile, int ng_valid) {
-  ee_f32x2 u1 = {0.f, 0.f}, u2 = {0.f, 0.f};
+  f32x2 u1 = {0.f, 0.f}, u2 = {0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
-      const ee_f32x2 y = {Y[t][r], Y[t][r + 1]};
+      const f32x2 y = {Y[t][r], Y[t][r + 1]};
       u1 += y;
       u2 = __builtin_elementwise_fma(y, y, u2);
     }
@@ -106,8 +64,8 @@ __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamm
   s2 += __shfl_xor(s2, 32, 64);
   const float mu = s1 * (1.0f / ET2_CZ);
   const float rstd = 1.0f / sqrtf(fmaxf(s2 * (1.0f / ET2_CZ) - mu * mu, 0.f) + 1e-5f);
-  const ee_f32x2 sa = {rstd, rstd}, sc = {-mu * rstd, -mu * rstd}, em2 = {em, em};
-  ee_u32x4 zB[8];  // half-precision z' as B fragments
+  const f32x2 sa = {rstd, rstd}, sc = {-mu * rstd, -mu * rstd}, em2 = {em, em};
+  u32x4 zB[8];  // half-precision z' as B fragments
   // (gamma, beta) of a feature group come from LDS one group AHEAD of their use; the interleave is pinned: left alone hipcc
   // emits read -> s_waitcnt lgkmcnt(0) -> use for each of the 16 groups (16 exposed LDS round trips per tile)
   f32x4 gq[2], bq[2];
@@ -122,14 +80,14 @@ __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamm
       bq[(idx + 1) & 1] = *(const f32x4*)(beta_l + f1);
     }
     const f32x4 gm = gq[idx & 1], bt = bq[idx & 1];
-    ee_f32x2 o0 = {Y[t][4 * g], Y[t][4 * g + 1]}, o1 = {Y[t][4 * g + 2], Y[t][4 * g + 3]};
+    f32x2 o0 = {Y[t][4 * g], Y[t][4 * g + 1]}, o1 = {Y[t][4 * g + 2], Y[t][4 * g + 3]};
     o0 = __builtin_elementwise_fma(o0, sa, sc);
     o1 = __builtin_elementwise_fma(o1, sa, sc);
-    o0 = __builtin_elementwise_fma(o0, ee_f32x2{gm[0], gm[1]}, ee_f32x2{bt[0], bt[1]}) * em2;
-    o1 = __builtin_elementwise_fma(o1, ee_f32x2{gm[2], gm[3]}, ee_f32x2{bt[2], bt[3]}) * em2;
-    const ee_u32x2 ow = {ee_cvt_pk(o0[0], o0[1]), ee_cvt_pk(o1[0], o1[1])};
+    o0 = __builtin_elementwise_fma(o0, f32x2{gm[0], gm[1]}, f32x2{bt[0], bt[1]}) * em2;
+    o1 = __builtin_elementwise_fma(o1, f32x2{gm[2], gm[3]}, f32x2{bt[2], bt[3]}) * em2;
+    const u32x2 ow = {fd_cvt_pk(o0[0], o0[1]), fd_cvt_pk(o1[0], o1[1])};
     // features f0..f0+3 = bytes 2 f0 .. 2 f0 + 7 of the pair's row: 16 B unit 4t + g, half hi; unit u of row r at u ^ (r & 15)
-    *(ee_u32x2*)(stage + li * 256 + (((4 * t + g) ^ (li & 15)) << 4) + 8 * hi) = ow;
+    *(u32x2*)(stage + li * 256 + (((4 * t + g) ^ (li & 15)) << 4) + 8 * hi) = ow;
     zB[2 * t + (g >> 1)][2 * (g & 1)] = ow[0];
     zB[2 * t + (g >> 1)][2 * (g & 1) + 1] = ow[1];
     if (TRACE && valid) *(f32x4*)(tr_row + f0) = f32x4{o0[0], o0[1], o1[0], o1[1]};
@@ -150,7 +108,7 @@ __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamm
     {  // compact image (8 head rows): lanes >= 8 read the zero unit behind it
       const int wl = li < 8 ? hi * 128 + li * 16 : EE2_WBC, ws = li < 8 ? 256 : 0;
 #pragma unroll
-      for (int s = 0; s < 8; ++s) wf[s] = lds_frag(wb_lds, wl + s * ws);
+      for (int s = 0; s < 8; ++s) wf[s] = fd_frag(wb_lds + wl + s * ws);
     }
     __builtin_amdgcn_sched_barrier(0);
     f32x16 accb;
@@ -177,7 +135,7 @@ __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamm
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2) {  // hi image, then lo image: 8 fragments each, requested a batch ahead of their MFMAs
 #pragma unroll
-        for (int s = 0; s < 8; ++s) wf[s] = lds_frag(dzh, h2 * 8192 + s * 1024 + lane * 16);
+        for (int s = 0; s < 8; ++s) wf[s] = fd_frag(dzh + h2 * 8192 + s * 1024 + lane * 16);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 8; ++s) accd = fd_mfma32(__builtin_bit_cast(hx8, zB[s]), wf[s], accd);
@@ -185,8 +143,8 @@ __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamm
       // registers 4 g .. 4 g + 3 = keys 8 g + 4 hi + q of the tile = key group 2 g + hi, channel d = li
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const ee_u32x2 ow = {ee_cvt_pk(accd[4 * g], accd[4 * g + 1]), ee_cvt_pk(accd[4 * g + 2], accd[4 * g + 3])};
-        if (2 * g + hi < ng_valid) *(ee_u32x2*)(pz_tile + ((2 * g + hi) * 32 + li) * 4) = ow;
+        const u32x2 ow = {fd_cvt_pk(accd[4 * g], accd[4 * g + 1]), fd_cvt_pk(accd[4 * g + 2], accd[4 * g + 3])};
+        if (2 * g + hi < ng_valid) *(u32x2*)(pz_tile + ((2 * g + hi) * 32 + li) * 4) = ow;
       }
     }
   }
@@ -216,7 +174,7 @@ __global__ void ee2_build_images_kernel(const float* __restrict__ w2, const floa
     const float* src = layer == 0 ? w2 : w3;
     for (int e = 0; e < 8; ++e) {
       const int k = c * 8 + e;
-      const int col = layer == 0 ? k : (k & ~15) + et2_perm16(k & 15);
+      const int col = layer == 0 ? k : (k & ~15) + fd_perm16(k & 15);
       img[(long)g * 8 + e] = f2h(src[(long)row * 128 + col]);
     }
   }
@@ -231,7 +189,7 @@ __global__ void ee2_build_lo_images_kernel(const float* __restrict__ w2, const f
     const float* src = layer == 0 ? w2 : w3;
     for (int e = 0; e < 8; ++e) {
       const int k = c * 8 + e;
-      const int col = layer == 0 ? k : (k & ~15) + et2_perm16(k & 15);
+      const int col = layer == 0 ? k : (k & ~15) + fd_perm16(k & 15);
       const float v = src[(long)row * 128 + col];
       img[(long)g * 8 + e] = f2h(v - h2f(f2h(v)));
     }
@@ -304,15 +262,15 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
   float* edg = (float*)(wbl + EE2_EPI_IMG);              // [num_bins + 1] distogram edges, the last one 1e8
   float* dl = edg + 64;                                  // DLDS: [num_bins + 1][128] distogram rows of the first layer
   if (DIST && tid <= a.num_bins) edg[tid] = tid < a.num_bins ? a.edges[tid] : 1e8f;
-  if (a.wb_img && tid < EE2_WBC / 16) et2_dma16((const char*)a.wb_img + tid * 16, wbl + (tid & ~63) * 16);
+  if (a.wb_img && tid < EE2_WBC / 16) fd_dma16((const char*)a.wb_img + tid * 16, wbl + (tid & ~63) * 16);
   if (tid < 16) *(unsigned*)(wbl + EE2_WBC + 4 * tid) = 0u;
   if (a.pz_out) {
-    et2_dma16((const char*)a.wdz_img + tid * 16, wbl + EE2_WBC + 64 + (tid & ~63) * 16);
-    et2_dma16((const char*)a.wdz_img_lo + tid * 16, wbl + EE2_WBC + 64 + 8192 + (tid & ~63) * 16);
+    fd_dma16((const char*)a.wdz_img + tid * 16, wbl + EE2_WBC + 64 + (tid & ~63) * 16);
+    fd_dma16((const char*)a.wdz_img_lo + tid * 16, wbl + EE2_WBC + 64 + 8192 + (tid & ~63) * 16);
     if (tid < 32) *(float*)(wbl + EE2_WBC + 64 + 2 * 8192 + 4 * tid) = a.bdz[tid];
   }
   for (int u = 0; u < 2 * EE2_IMG / 16 / EE2_THREADS; ++u)
-    et2_dma16(img + (size_t)(u * EE2_THREADS + tid) * 16, smem + (size_t)(u * EE2_THREADS + (tid & ~63)) * 16);
+    fd_dma16(img + (size_t)(u * EE2_THREADS + tid) * 16, smem + (size_t)(u * EE2_THREADS + (tid & ~63)) * 16);
   if (tid < 4 * ET2_CZ) {
     const int which = tid >> 7, c = tid & 127;
     vec[tid] = which == 0 ? a.b2[c] : (which == 1 ? a.b3[c] : (which == 2 ? a.gamma[c] : a.beta[c]));
@@ -330,7 +288,7 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
       if (v < (a.num_bins + 1) * 32) *(f32x4*)(dl + (long)v * 4) = t[u];
     }
   }
-  et2_dma_wait();
+  fd_dma_wait();
   __syncthreads();
   EE2_STAMP(0);
   const int N = a.N, nb = a.num_bins;
@@ -428,20 +386,20 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
         const int it = 4 * half + q, r = 2 * it + hi;
         const f32x4 x1 = PI, x2 = PJ[it], x3 = RR[it];
         // packed adds, conversion, then relu on the half-precision bit patterns (v_pk_max_i16)
-        ee_f32x2 sA, sB;
+        f32x2 sA, sB;
         if constexpr (DIST) {
           const f32x4 x4 = DD[q];
-          sA = (ee_f32x2{x1[0], x1[1]} + ee_f32x2{x2[0], x2[1]}) + (ee_f32x2{x3[0], x3[1]} + ee_f32x2{x4[0], x4[1]});
-          sB = (ee_f32x2{x1[2], x1[3]} + ee_f32x2{x2[2], x2[3]}) + (ee_f32x2{x3[2], x3[3]} + ee_f32x2{x4[2], x4[3]});
+          sA = (f32x2{x1[0], x1[1]} + f32x2{x2[0], x2[1]}) + (f32x2{x3[0], x3[1]} + f32x2{x4[0], x4[1]});
+          sB = (f32x2{x1[2], x1[3]} + f32x2{x2[2], x2[3]}) + (f32x2{x3[2], x3[3]} + f32x2{x4[2], x4[3]});
         } else {
-          sA = (ee_f32x2{x1[0], x1[1]} + ee_f32x2{x2[0], x2[1]}) + ee_f32x2{x3[0], x3[1]};
-          sB = (ee_f32x2{x1[2], x1[3]} + ee_f32x2{x2[2], x2[3]}) + ee_f32x2{x3[2], x3[3]};
+          sA = (f32x2{x1[0], x1[1]} + f32x2{x2[0], x2[1]}) + f32x2{x3[0], x3[1]};
+          sB = (f32x2{x1[2], x1[3]} + f32x2{x2[2], x2[3]}) + f32x2{x3[2], x3[3]};
         }
         typedef short s16x4 __attribute__((ext_vector_type(4)));
-        const ee_u32x2 cw = {ee_cvt_pk(sA[0], sA[1]), ee_cvt_pk(sB[0], sB[1])};
-        const ee_u32x2 pk = __builtin_bit_cast(ee_u32x2, __builtin_elementwise_max(__builtin_bit_cast(s16x4, cw), s16x4{0, 0, 0, 0}));
+        const u32x2 cw = {fd_cvt_pk(sA[0], sA[1]), fd_cvt_pk(sB[0], sB[1])};
+        const u32x2 pk = __builtin_bit_cast(u32x2, __builtin_elementwise_max(__builtin_bit_cast(s16x4, cw), s16x4{0, 0, 0, 0}));
         // [32 pairs][256 B] tile, 16 B unit u of row r at u ^ (r & 15)
-        *(ee_u32x2*)(stage + r * 256 + (((li >> 1) ^ (r & 15)) << 4) + 8 * (li & 1)) = pk;
+        *(u32x2*)(stage + r * 256 + (((li >> 1) ^ (r & 15)) << 4) + 8 * (li & 1)) = pk;
       }
       }
       EE2_STAMP(2);
@@ -449,7 +407,7 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
       row_ids(rin, rel, bin, msk);  // the next row's ids (this row's were consumed by the gather above)
       hx8 H1[8];
 #pragma unroll
-      for (int s = 0; s < 8; ++s) H1[s] = lds_frag(stage, li * 256 + (((2 * s + hi) ^ (li & 15)) << 4));
+      for (int s = 0; s < 8; ++s) H1[s] = fd_frag(stage + li * 256 + (((2 * s + hi) ^ (li & 15)) << 4));
       hx8 H2[8];
 #pragma unroll
       for (int T = 0; T < 4; ++T) {
@@ -462,7 +420,7 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
         }
         mma_slab<8, 256>(acc, smem + T * 32 * 256, li, hi, H1);
         if constexpr (LO) mma_slab_lo(acc, img + 2 * EE2_IMG + T * 32 * 256, li, hi, H1);
-        ee_hand_off(acc, H2[2 * T], H2[2 * T + 1]);
+        fd_hand_off(acc, H2[2 * T], H2[2 * T + 1]);
       }
       EE2_STAMP(3);
       f32x16 Y[4];

@@ -1,7 +1,7 @@
 // edge_transition3.hip — bf16 EdgeTransition (framedipt/model/ipa_pytorch.py:84-102), second generation of the
-// register-resident kernel (edge_transition2.hip), re-tiled so that TWO waves share every SIMD.
+// register-resident kernel, re-tiled so that TWO waves share every SIMD.
 //
-// edge_transition2 gives a wave 32 pairs and the whole 512-register file: one wave per SIMD, so everything a wave does
+// The first generation (32-pair waves; in the git history) gives a wave 32 pairs and the whole 512-register file: one wave per SIMD, so everything a wave does
 // besides issuing MFMAs (LDS-DMA issue ≈ 60 cycles per KB, bias / ReLU / pack epilogues, barrier skew, the tile prologue
 // and the LayerNorm epilogue) leaves its matrix core idle — 37 % MFMA utilisation in the phase profile.  Here a wave owns
 // 16 pairs and works with v_mfma_f32_16x16x32_bf16:
@@ -15,7 +15,7 @@
 //     the final layer): y = Wf[:, z|e_j] x + Wf[:, h] h2 is one K = 640 product;
 //   * weight stream: lane-linear 1 KB fragments [feature tile][k-step][lane][8 bf16] (no swizzle: a fragment read is
 //     ds_read_b128 at lane * 16), 640 KB per 128 pairs in 13 chunks through a 2 x 64 KB LDS double buffer by LDS-DMA.
-// Concat-free exactly as edge_transition2: the e_i columns of layer 1 / the final layer are per-residue rows A1[i], Af[i].
+// Concat-free: the e_i columns of layer 1 / the final layer are per-residue rows A1[i], Af[i].
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -33,11 +33,6 @@
 #define E3_BROWS 4
 #define E3_BROW_BYTES 2048
 #define E3_LDS (2 * E3_CHUNK + 2 * E3_BROWS * E3_BROW_BYTES + 1536 + 1024 + 4096)  // ... + linear_b image of the next block
-
-typedef __attribute__((ext_vector_type(4))) float e3_f32x4;
-typedef fd_h e3_hx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int e3_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int e3_u32x2 __attribute__((ext_vector_type(2)));
 
 // k position (0..31) of a k-step whose B fragment is the C/D hand-off of tiles (2s, 2s+1) -> feature offset in [0, 32)
 __host__ __device__ __forceinline__ int e3_chain_feat(int pos) {
@@ -98,50 +93,33 @@ int fd_et3_build_bias_image(const float* wb, int H, float scale, void* img, hipS
 }
 
 // ------------------------------------------------------------------ device helpers
-typedef __attribute__((address_space(3))) void e3_lds_t;
-// 16 B-per-lane LDS-DMA as inline asm (see edge_transition2.hip: the builtin makes hipcc force lgkmcnt(0) everywhere)
-__device__ __forceinline__ void e3_dma16(const void* gsrc, const char* lds_dst) {
-  const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(const __attribute__((address_space(3))) char*)lds_dst);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(m0v), "v"(gsrc) : "memory", "m0");
-}
-__device__ __forceinline__ void e3_dma_wait() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ hx8 e3_frag(const char* p) { return __builtin_bit_cast(hx8, *(const u16x8*)p); }
-__device__ __forceinline__ hx8 e3_pack8(const float* v) {
-  hx8 o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = (fd_h)v[e];
-  return o;
-}
+// (LDS-DMA, its wait, fragment loads and packing: fd_dma16 / fd_dma_wait / fd_frag / fd_pack8 of common.hpp)
 template <int BYTES>
 __device__ __forceinline__ void e3_dma_chunk(const char* __restrict__ src, char* dst, int tid) {
 #pragma unroll
   for (int u = 0; u < (BYTES / 16 + E3_THREADS - 1) / E3_THREADS; ++u)
     if ((u + 1) * E3_THREADS * 16 <= BYTES || (u * E3_THREADS + tid) * 16 < BYTES)
-      e3_dma16(src + (size_t)(u * E3_THREADS + tid) * 16, dst + (size_t)(u * E3_THREADS + (tid & ~63)) * 16);
+      fd_dma16(src + (size_t)(u * E3_THREADS + tid) * 16, dst + (size_t)(u * E3_THREADS + (tid & ~63)) * 16);
 }
 
 // two 16-feature tiles (A, B) against the same B fragments: fragments of the pair are [tile A: KS KB][tile B: KS KB] at `base`
 template <int KS>
-__device__ __forceinline__ void e3_pair(e3_f32x4& accA, e3_f32x4& accB, const char* base, int lane, const hx8* Bf) {
+__device__ __forceinline__ void e3_pair(f32x4& accA, f32x4& accB, const char* base, int lane, const hx8* Bf) {
   constexpr int DEPTH = 3;  // fragments are requested 2 k-steps (4 MFMAs of this wave) ahead of their use (4: slower, 5+: spills)
   const char* pa = base + lane * 16;
   const char* pb = pa + KS * 1024;
   hx8 rA[DEPTH], rB[DEPTH];
 #pragma unroll
   for (int s = 0; s < DEPTH - 1; ++s) {
-    rA[s] = e3_frag(pa + s * 1024);
-    rB[s] = e3_frag(pb + s * 1024);
+    rA[s] = fd_frag(pa + s * 1024);
+    rB[s] = fd_frag(pb + s * 1024);
   }
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     if (s + DEPTH - 1 < KS) {
-      rA[(s + DEPTH - 1) % DEPTH] = e3_frag(pa + (s + DEPTH - 1) * 1024);
-      rB[(s + DEPTH - 1) % DEPTH] = e3_frag(pb + (s + DEPTH - 1) * 1024);
+      rA[(s + DEPTH - 1) % DEPTH] = fd_frag(pa + (s + DEPTH - 1) * 1024);
+      rB[(s + DEPTH - 1) % DEPTH] = fd_frag(pb + (s + DEPTH - 1) * 1024);
     }
     accA = fd_mfma16(rA[s % DEPTH], Bf[s], accA);
     accB = fd_mfma16(rB[s % DEPTH], Bf[s], accB);
@@ -189,10 +167,10 @@ __device__ __forceinline__ void e3_request(const ET2Args& a, int tile, int tid, 
     int r = 4 * k + (lane >> 4);
     const int u = (lane & 15) ^ r;
     if (r > rmax) r = rmax;
-    e3_dma16(a.z_in + (long)(pw + r) * E3_CZ + 8 * u, xst + k * 1024);
+    fd_dma16(a.z_in + (long)(pw + r) * E3_CZ + 8 * u, xst + k * 1024);
     int rbj = b0 * N + j0 + r;
     if (j0 + r >= N && !last_i) rbj -= N;   // wrap to (i + 1, j - N); past the sample's last row it is the next sample
-    e3_dma16(a.e_h16 + (long)rbj * E3_CB + 8 * u, xst + 4096 + k * 1024);
+    fd_dma16(a.e_h16 + (long)rbj * E3_CB + 8 * u, xst + 4096 + k * 1024);
   }
   e3_dma_chunk<E3_CHUNK>(stream, smem, tid);
   {  // A1 | Af rows i_lo .. i_lo+3: 4 x 128 units of 16 B = one per thread
@@ -200,7 +178,7 @@ __device__ __forceinline__ void e3_request(const ET2Args& a, int tile, int tid, 
     int r = (tile * 128) / N + row;
     if (r >= n_rows) r = n_rows - 1;
     const float* src = qq < 96 ? a.a1 + (long)r * E3_H + 4 * qq : a.af + (long)r * E3_CZ + 4 * (qq - 96);
-    e3_dma16(src, brow + (size_t)(tid & ~63) * 16);
+    fd_dma16(src, brow + (size_t)(tid & ~63) * 16);
   }
 }
 
@@ -222,14 +200,14 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
     e3_request(a, tile, tid, lane, wave, n_pairs, n_rows, stream, smem, smem + E3_CHUNK + wave * 8192, brow_lds);
     if (tid < 160) {
       const float* src = tid < 96 ? a.b2 + 4 * tid : (tid < 128 ? a.gamma + 4 * (tid - 96) : a.beta + 4 * (tid - 128));
-      e3_dma16(src, (const char*)vec + (tid & ~63) * 16);
+      fd_dma16(src, (const char*)vec + (tid & ~63) * 16);
     }
-    if (a.wb_img && tid < 256) e3_dma16((const char*)a.wb_img + tid * 16, (const char*)vec + 2560 + (tid & ~63) * 16);
+    if (a.wb_img && tid < 256) fd_dma16((const char*)a.wb_img + tid * 16, (const char*)vec + 2560 + (tid & ~63) * 16);
   }
   E3Tile tc = e3_tile(tile, wave, n0, N, n_pairs);
   float em = a.res_mask[tc.bi] * a.res_mask[tc.bj];
   int par = 0;  // parity of the A1 | Af row buffer of the current tile
-  e3_dma_wait();
+  fd_dma_wait();
   __syncthreads();
   FD_STAMP(1);
 #pragma unroll 1
@@ -243,15 +221,15 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
     hx8 X[8];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      X[s] = e3_frag(xst + n * 256 + (((4 * s + q) ^ n) << 4));
-      X[4 + s] = e3_frag(xst + 4096 + n * 256 + (((4 * s + q) ^ n) << 4));
+      X[s] = fd_frag(xst + n * 256 + (((4 * s + q) ^ n) << 4));
+      X[4 + s] = fd_frag(xst + 4096 + n * 256 + (((4 * s + q) ^ n) << 4));
     }
     const float* a1l = (const float*)(brow_lds + par * E3_BROWS * E3_BROW_BYTES + (tc.bi - tc.i_lo) * E3_BROW_BYTES) + 4 * q;
     __builtin_amdgcn_s_waitcnt(0x0070);
     __syncthreads();  // every wave has its x fragments: chunk buffer 1 may receive the second chunk
 
     hx8 H1[12], H2[12];
-    e3_f32x4 Y[8];
+    f32x4 Y[8];
     size_t soff = 0;
     int buf = 0;
     // ================= layer 1: 3 chunks x 4 tile pairs, K = 256
@@ -262,7 +240,7 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int P = 4 * c + u;  // tiles 2P, 2P+1
-        e3_f32x4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
+        f32x4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
         e3_pair<8>(accA, accB, smem + buf * E3_CHUNK + u * 16384, lane, X);
         const f32x4 bA = *(const f32x4*)(a1l + 32 * P), bB = *(const f32x4*)(a1l + 32 * P + 16);
         float v[8];
@@ -271,9 +249,9 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
           v[r] = fmaxf(accA[r] + bA[r], 0.f);
           v[4 + r] = fmaxf(accB[r] + bB[r], 0.f);
         }
-        H1[P] = e3_pack8(v);
+        H1[P] = fd_pack8(v);
       }
-      e3_dma_wait();
+      fd_dma_wait();
       __syncthreads();
       buf ^= 1;
       soff += E3_CHUNK;
@@ -288,7 +266,7 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int P = 2 * c + u;
-        e3_f32x4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
+        f32x4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
         e3_pair<12>(accA, accB, smem + buf * E3_CHUNK + u * 24576, lane, H1);
         const f32x4 bA = *(const f32x4*)(b2l + 32 * P), bB = *(const f32x4*)(b2l + 32 * P + 16);
         float v[8];
@@ -297,9 +275,9 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
           v[r] = fmaxf(accA[r] + bA[r], 0.f);
           v[4 + r] = fmaxf(accB[r] + bB[r], 0.f);
         }
-        H2[P] = e3_pack8(v);
+        H2[P] = fd_pack8(v);
       }
-      e3_dma_wait();
+      fd_dma_wait();
       __syncthreads();
       buf ^= 1;
       soff += 2 * 24 * 1024;
@@ -314,12 +292,12 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       if (c < 3) e3_dma_chunk<40 * 1024>(stream + soff + 40 * 1024, smem + (buf ^ 1) * E3_CHUNK, tid);
-      e3_f32x4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
+      f32x4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
       e3_pair<20>(accA, accB, smem + buf * E3_CHUNK, lane, XF);
       Y[2 * c] = accA;
       Y[2 * c + 1] = accB;
       if (c < 3) {
-        e3_dma_wait();
+        fd_dma_wait();
         __syncthreads();
         buf ^= 1;
         soff += 40 * 1024;
@@ -362,36 +340,36 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
       s2 += __shfl_xor(s2, 16, 64);
       s2 += __shfl_xor(s2, 32, 64);
       const float rstd = 1.0f / sqrtf(s2 * (1.0f / E3_CZ) + 1e-5f);
-      e3_u32x4 zB[4];
+      u32x4 zB[4];
       half_t* zo = a.z_out + (long)tc.p * E3_CZ + 4 * q;
       float* tr_row = a.trace ? a.trace + (long)tc.p * E3_CZ + 4 * q : nullptr;
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const f32x4 gm = *(const f32x4*)(gml + 16 * t), bt = *(const f32x4*)(btl + 16 * t);
         float of[4];
-        e3_hx4 o;
+        hx4 o;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           of[r] = ((Y[t][r] - mu) * rstd * gm[r] + bt[r]) * em;
           o[r] = (fd_h)of[r];
         }
         if (tc.valid) {
-          *(e3_hx4*)(zo + 16 * t) = o;
+          *(hx4*)(zo + 16 * t) = o;
           if (tr_row) {
             f32x4 tv = {of[0], of[1], of[2], of[3]};
             *(f32x4*)(tr_row + 16 * t) = tv;
           }
         }
-        const e3_u32x2 ow = __builtin_bit_cast(e3_u32x2, o);  // C/D hand-off of tiles (2s, 2s+1) -> B fragment s of z'
+        const u32x2 ow = __builtin_bit_cast(u32x2, o);  // C/D hand-off of tiles (2s, 2s+1) -> B fragment s of z'
         zB[t >> 1][2 * (t & 1)] = ow[0];
         zB[t >> 1][2 * (t & 1) + 1] = ow[1];
       }
       if (a.wb_img) {
         // pair bias of the next block's attention: D[head, pair] = Wb z' (4 MFMAs), heads 4q + r live in lane groups q < 2
-        e3_f32x4 accb = {0.f, 0.f, 0.f, 0.f};
+        f32x4 accb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < 4; ++s)
-          accb = fd_mfma16(e3_frag((const char*)vec + 2560 + s * 1024 + lane * 16),
+          accb = fd_mfma16(fd_frag((const char*)vec + 2560 + s * 1024 + lane * 16),
                                                          __builtin_bit_cast(hx8, zB[s]), accb);
         if (tc.valid && q < 2) {
           const int b_idx = tc.bi / N, ii = tc.bi - b_idx * N, jj = tc.bj - b_idx * N, nt = (N + 31) >> 5;
@@ -410,7 +388,7 @@ __global__ __launch_bounds__(E3_THREADS, 1) void edge_transition3_kernel(ET2Args
     tc = e3_tile(tile, wave, n, N, n_pairs);
     em = a.res_mask[tc.bi] * a.res_mask[tc.bj];
     par ^= 1;
-    e3_dma_wait();
+    fd_dma_wait();
     __syncthreads();
   }
 }

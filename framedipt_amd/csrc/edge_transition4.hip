@@ -77,10 +77,6 @@ __device__ unsigned long long e4_span[1024 * 3];  // per block: start, end (s_me
 // into the caller's FdiptForwardArgs.clock_out (ET2Args.clock) when that is set; no atomics and no state otherwise.
 #define E4_CLK_BEGIN FD_CLK_BEGIN
 #define E4_CLK_END FD_CLK_END(a.clock)
-typedef fd_h e4_hx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int e4_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int e4_u32x2 __attribute__((ext_vector_type(2)));
-typedef short e4_s16x2 __attribute__((ext_vector_type(2)));
 
 // C/D register 8u + e of lane half `half` of a 32-feature tile holds feature (offset in the tile):
 __host__ __device__ __forceinline__ int e4_chain_feat(int u, int half, int e) { return (e & 3) + 8 * (2 * u + (e >> 2)) + 4 * half; }
@@ -212,51 +208,15 @@ int fd_et4_row_images(const float* rows, int B, int N, void* a_img, void* b_img,
 }
 
 // ------------------------------------------------------------------ device helpers
-// 16 B-per-lane LDS-DMA as inline asm (see edge_transition2.hip: the builtin makes hipcc force lgkmcnt(0) everywhere)
-// LDS is addressed by 32-bit byte offsets into the dynamic segment (the only LDS of the kernel, so it starts at 0): no
-// generic pointers, no address-space casts with their null checks
-typedef const __attribute__((address_space(3))) u16x8* e4_lds_u16x8;
-typedef const __attribute__((address_space(3))) f32x4* e4_lds_f32x4;
-__device__ __forceinline__ void e4_dma16(const void* gsrc, unsigned lds_dst) {
-  const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_dst);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(m0v), "v"(gsrc) : "memory", "m0");
-}
-// The pair stream (z rows in, z' rows out: 2 x 184 MB per launch at N = 300, B = 8, read / written exactly once) goes with the default
-// cache policy (round 2: `nt` loads, `sc1` or `nt` stores measured against it).  The 512 KB weight stream every block re-reads 11 times
-// per launch should stay L2-resident next to it (round 2: re-fetched ~38 times per launch from the Infinity Cache:
-// profiles/r02_pmc_bench_c4_fp16.md).
-__device__ __forceinline__ void e4_dma16_z(const void* gsrc, unsigned lds_dst) { e4_dma16(gsrc, lds_dst); }
-__device__ __forceinline__ void e4_store_z(half_t* dst, u16x8 v) { *(u16x8*)dst = v; }
-__device__ __forceinline__ void e4_dma_wait() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ hx8 e4_frag(unsigned off) { return __builtin_bit_cast(hx8, *(e4_lds_u16x8)(unsigned long)off); }
-__device__ __forceinline__ f32x4 e4_ldsf4(unsigned off) { return *(e4_lds_f32x4)(unsigned long)off; }
-__device__ __forceinline__ hx8 e4_gfrag(const char* p) { return __builtin_bit_cast(hx8, *(const u16x8*)p); }
+// LDS is addressed by 32-bit byte offsets into the dynamic segment (the only LDS of the kernel, so it starts at 0): the offset
+// forms of fd_dma16 / fd_frag (common.hpp), no generic pointers
+__device__ __forceinline__ f32x4 e4_ldsf4(unsigned off) { return *(fd_lds_f32x4)(unsigned long)off; }
 template <int BYTES>
 __device__ __forceinline__ void e4_dma_chunk(const char* __restrict__ src, unsigned dst, int tid, int wave) {
   static_assert(BYTES % (E4_THREADS * 16) == 0, "whole DMA instructions");
 #pragma unroll
   for (int u = 0; u < BYTES / (E4_THREADS * 16); ++u)
-    e4_dma16(src + (size_t)(u * E4_THREADS + tid) * 16, dst + (unsigned)(u * E4_THREADS + wave * 64) * 16);  // (scalar destination)
-}
-__device__ __forceinline__ f32x16 e4_mfma(hx8 a, hx8 b, f32x16 c) { return fd_mfma32(a, b, c); }
-// relu + bf16: C/D of one tile -> the two B fragments it hands to the next layer.  ReLU runs after the conversion, on the
-// bf16 bit patterns as signed 16-bit integers (negative values have the sign bit set): one v_pk_max_i16 per two values.
-__device__ __forceinline__ void e4_hand_off(const f32x16& acc, hx8& h0, hx8& h1) {
-  e4_u32x4 w0, w1;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    w0[k] = fd_cvt_pk(acc[2 * k], acc[2 * k + 1]);
-    w1[k] = fd_cvt_pk(acc[8 + 2 * k], acc[8 + 2 * k + 1]);
-  }
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-  h0 = __builtin_bit_cast(hx8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, w0), zero));
-  h1 = __builtin_bit_cast(hx8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, w1), zero));
-  __builtin_amdgcn_sched_barrier(0);  // the hand-off of a tile happens here, not batched with later tiles' (register pressure)
+    fd_dma16(src + (size_t)(u * E4_THREADS + tid) * 16, dst + (unsigned)(u * E4_THREADS + wave * 64) * 16);  // (scalar destination)
 }
 
 // one 32-feature tile: KS weight fragments at `pa` (this lane's 16 B of fragment 0) against B fragments Bf[0..KS)
@@ -264,12 +224,12 @@ template <int KS, int DEPTH>
 __device__ __forceinline__ void e4_tile(f32x16& acc, unsigned pa, const hx8* Bf) {
   hx8 r[DEPTH];
 #pragma unroll
-  for (int s = 0; s < DEPTH - 1; ++s) r[s] = e4_frag(pa + s * 1024);
+  for (int s = 0; s < DEPTH - 1; ++s) r[s] = fd_frag(pa + s * 1024);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
-    if (s + DEPTH - 1 < KS) r[(s + DEPTH - 1) % DEPTH] = e4_frag(pa + (s + DEPTH - 1) * 1024);
-    acc = e4_mfma(r[s % DEPTH], Bf[s], acc);
+    if (s + DEPTH - 1 < KS) r[(s + DEPTH - 1) % DEPTH] = fd_frag(pa + (s + DEPTH - 1) * 1024);
+    acc = fd_mfma32(r[s % DEPTH], Bf[s], acc);
     __builtin_amdgcn_sched_barrier(0);  // pin: one ds_read, one MFMA per k-step (hipcc otherwise sinks every read to its use)
   }
 }
@@ -281,7 +241,7 @@ __device__ __forceinline__ hx8 e4_sel(int lane, int ns) {
   asm volatile("" : "+v"(lane));
   const int p = lane & 31, want = (lane >> 5) ? (p & 3) + ((p >> 2) >= ns ? 4 : 0) : (p >> 2);
   const unsigned one = (want & 1) ? (FD_H_ONE_BITS << 16) : FD_H_ONE_BITS;  // 1.0 in the odd / even half of a word
-  e4_u32x4 w;
+  u32x4 w;
 #pragma unroll
   for (int k = 0; k < 4; ++k) w[k] = (want >> 1) == k ? one : 0u;
   return __builtin_bit_cast(hx8, w);
@@ -308,7 +268,11 @@ __device__ __forceinline__ E4Tile e4_tile_of(int w, int n_wt, int N, int NJ4) {
 }
 
 // z rows of the wave's patch -> its LDS rows (row p = 4 k + (j - 4 jt), 256 B, unit u of row p at u ^ (p & 15)):
-// 8 DMA instructions, one per residue row k (4 pairs = 1 KB contiguous in HBM), swizzle applied on the source side
+// 8 DMA instructions, one per residue row k (4 pairs = 1 KB contiguous in HBM), swizzle applied on the source side.
+// The pair stream (z rows in, z' rows out: 2 x 184 MB per launch at N = 300, B = 8, read / written exactly once) goes with the default
+// cache policy, here and at the z' stores of the epilogue (round 2: `nt` loads, `sc1` or `nt` stores measured against it).  The 512 KB
+// weight stream every block re-reads 11 times per launch should stay L2-resident next to it (round 2: re-fetched ~38 times per launch
+// from the Infinity Cache: profiles/r02_pmc_bench_c4_fp16.md).
 __device__ __forceinline__ void e4_request_z(const ET2Args& a, const E4Tile& t, int lane, unsigned zst, int M) {
   const int N = a.N;
 #pragma unroll
@@ -318,7 +282,7 @@ __device__ __forceinline__ void e4_request_z(const ET2Args& a, const E4Tile& t, 
     const int lrow = 4 * r + (lane >> 4);
     const int u = (lane & 15) ^ (lrow & 15);
     const long pair = ((long)row * N + 4 * t.jt) + (lane >> 4);
-    e4_dma16_z(a.z_in + pair * E4_CZ + 8 * u, zst + r * 1024);
+    fd_dma16(a.z_in + pair * E4_CZ + 8 * u, zst + r * 1024);
   }
 }
 
@@ -339,7 +303,7 @@ struct E4EpiTmp {     // lives inside one epilogue run only
   unsigned moff;      // LDS address of this lane's pair mask
   unsigned boff;      // LDS address of the linear_b bias
 };
-typedef __attribute__((address_space(3))) e4_u32x2* e4_lds_w64;
+typedef __attribute__((address_space(3))) u32x2* e4_lds_w64;
 // x(lane) + x(lane ^ 32).  ds_bpermute with the partner address computed on the spot from the caller's (opaque) lane index:
 // __shfl_xor computes its own lane id, which hipcc hoists out of the tile loop and spills — and the reload is a vmcnt wait
 // that drains the whole DMA queue of the next tile.  (v_permlane32_swap would avoid LDS, but hipcc mis-handles its second
@@ -400,7 +364,7 @@ __device__ __forceinline__ void e4_epi(E4Epi& E, E4EpiTmp& X, const ET2Args& a, 
     constexpr int t = SLOT - 2;
     const unsigned gml = vec + 4 * (E4_H + 4 * half + 32 * t);
     const unsigned btl = gml + 4 * E4_CZ;
-    e4_u32x4 zB[2];
+    u32x4 zB[2];
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {  // two halves of the tile: their gamma / beta first, then the math (no control flow between)
       f32x4 gm[2], bt[2];
@@ -424,7 +388,7 @@ __device__ __forceinline__ void e4_epi(E4Epi& E, E4EpiTmp& X, const ET2Args& a, 
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int g = 2 * h2 + k;
-        const e4_u32x2 ow = {fd_cvt_pk(o[2 * k][0], o[2 * k][1]), fd_cvt_pk(o[2 * k + 1][0], o[2 * k + 1][1])};
+        const u32x2 ow = {fd_cvt_pk(o[2 * k][0], o[2 * k][1]), fd_cvt_pk(o[2 * k + 1][0], o[2 * k + 1][1])};
         // registers 4 g .. 4 g + 3 of tile t -> B fragment 2 t + (g >> 1) of z'
         zB[h2][2 * k] = ow[0];
         zB[h2][2 * k + 1] = ow[1];
@@ -441,13 +405,13 @@ __device__ __forceinline__ void e4_epi(E4Epi& E, E4EpiTmp& X, const ET2Args& a, 
       const unsigned wl = p < 8 ? wbi + half * 128 + p * 16 : wbi + 2048, ws = p < 8 ? 256u : 0u;
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2)
-        X.accb = fd_mfma32(e4_frag(wl + (2 * t + h2) * ws), __builtin_bit_cast(hx8, zB[h2]), X.accb);
+        X.accb = fd_mfma32(fd_frag(wl + (2 * t + h2) * ws), __builtin_bit_cast(hx8, zB[h2]), X.accb);
     }
     if constexpr (PZ) {  // D[pair, d] += z' Wdz[d, this tile's features]  (hi from LDS, lo from registers)
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2) {
-        X.accd = fd_mfma32(__builtin_bit_cast(hx8, zB[h2]), e4_frag(dzf + (2 * t + h2) * 1024 + lane * 16), X.accd);
-        X.accd = fd_mfma32(__builtin_bit_cast(hx8, zB[h2]), e4_frag(dzf + 8192 + (2 * t + h2) * 1024 + lane * 16), X.accd);
+        X.accd = fd_mfma32(__builtin_bit_cast(hx8, zB[h2]), fd_frag(dzf + (2 * t + h2) * 1024 + lane * 16), X.accd);
+        X.accd = fd_mfma32(__builtin_bit_cast(hx8, zB[h2]), fd_frag(dzf + 8192 + (2 * t + h2) * 1024 + lane * 16), X.accd);
       }
     }
     // read the staged tile back as 64 B row segments (the LDS operations of one wave execute in order: no barrier) and store
@@ -455,8 +419,8 @@ __device__ __forceinline__ void e4_epi(E4Epi& E, E4EpiTmp& X, const ET2Args& a, 
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int pr = 16 * k + (lane >> 2);
-      const u16x8 v = *(e4_lds_u16x8)(unsigned long)(stg + pr * 64 + (((lane & 3) ^ ((pr >> 2) & 3)) << 4));
-      if (X.svalid[k]) e4_store_z(a.z_out + X.srow[k] * E4_CZ + 32 * t + 8 * (lane & 3), v);
+      const u16x8 v = *(fd_lds_u16x8)(unsigned long)(stg + pr * 64 + (((lane & 3) ^ ((pr >> 2) & 3)) << 4));
+      if (X.svalid[k]) *(u16x8*)(a.z_out + X.srow[k] * E4_CZ + 32 * t + 8 * (lane & 3)) = v;
     }
   } else if constexpr (SLOT == 6) {
     if (a.wb_img) {
@@ -479,9 +443,9 @@ __device__ __forceinline__ void e4_epi(E4Epi& E, E4EpiTmp& X, const ET2Args& a, 
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int row = 8 * E.t.rt + 2 * g + half;
-        const e4_u32x2 ow = {fd_cvt_pk(X.accd[4 * g], X.accd[4 * g + 1]), fd_cvt_pk(X.accd[4 * g + 2], X.accd[4 * g + 3])};
+        const u32x2 ow = {fd_cvt_pk(X.accd[4 * g], X.accd[4 * g + 1]), fd_cvt_pk(X.accd[4 * g + 2], X.accd[4 * g + 3])};
         if (E.t.valid && row < M)
-          *(e4_u32x2*)(a.pz_out + (((long)row * NJ4 + E.t.jt) * 32 + p) * 4) = ow;
+          *(u32x2*)(a.pz_out + (((long)row * NJ4 + E.t.jt) * 32 + p) * 4) = ow;
       }
     }
   }
@@ -545,8 +509,8 @@ __device__ __forceinline__ void e4_point(const E4Flat& F, int c) {
 // one k-step of the stream: the operand ring is refilled E4_DR - 1 fragments ahead (not past the tile's last fragment)
 #define E4_STEP(f_, B_, acc_)                                                                                   \
   do {                                                                                                          \
-    if ((f_) + E4_DR - 1 < NCH * E4_CFR) r[((f_) + E4_DR - 1) % E4_DR] = e4_frag(F.pa + e4_ring_off((f_) + E4_DR - 1)); \
-    acc_ = e4_mfma(r[(f_) % E4_DR], B_, acc_);                                                                  \
+    if ((f_) + E4_DR - 1 < NCH * E4_CFR) r[((f_) + E4_DR - 1) % E4_DR] = fd_frag(F.pa + e4_ring_off((f_) + E4_DR - 1)); \
+    acc_ = fd_mfma32(r[(f_) % E4_DR], B_, acc_);                                                                  \
     __builtin_amdgcn_sched_barrier(0);                                                                          \
   } while (0)
 
@@ -581,16 +545,16 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
   for (int c = 0; c < E4_NSLOT - 1; ++c) e4_dma_chunk<E4_CHUNK>(stream + c * E4_CHUNK, lds0 + c * E4_CHUNK, tid0, wave);
   if (tid0 < (PZ ? 168 : 160)) {
     const float* src = tid0 < 96 ? a.b2 + 4 * tid0 : (tid0 < 128 ? a.gamma + 4 * (tid0 - 96) : (tid0 < 160 ? a.beta + 4 * (tid0 - 128) : a.bdz + 4 * (tid0 - 160)));
-    e4_dma16(src, vec + (tid0 & ~63) * 16);
+    fd_dma16(src, vec + (tid0 & ~63) * 16);
   }
-  if (a.wb_img && tid0 < 128) e4_dma16((const char*)a.wb_img + tid0 * 16, wbi + (tid0 & ~63) * 16);  // compact image (2 KB)
+  if (a.wb_img && tid0 < 128) fd_dma16((const char*)a.wb_img + tid0 * 16, wbi + (tid0 & ~63) * 16);  // compact image (2 KB)
   if (tid0 < 4) *(__attribute__((address_space(3))) unsigned*)(unsigned long)(wbi + 2048 + tid0 * 4) = 0u;  // the zero unit
   auto fold_ptr = [&](const E4Tile& t, int lane) {
     const unsigned fold_b1 = (unsigned)((const char*)a.b1_img - (const char*)a.a1_img);
     const unsigned ob = fold_b1 + (unsigned)((t.b0 * NJ4 + t.jt) * 16) * 512u, oa = (unsigned)(t.rt * 16) * 512u;  // scalar
     return oa + (unsigned)(lane >> 5) * (ob - oa) + (lane & 31) * 16;
   };
-  auto fold_ld = [&](unsigned off) { return e4_gfrag((const char*)a.a1_img + off); };
+  auto fold_ld = [&](unsigned off) { return fd_frag((const char*)a.a1_img + off); };
   unsigned fold_base = fold_ptr(tc, lane0);
   hx8 FA[12];
 #pragma unroll
@@ -605,7 +569,7 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
   E4Epi E;
   E4EpiTmp X;
 #define E4_EPI(k, emr) e4_epi<k, PZ, STZ, emr>(E, X, a, lane_id(), vec, wbi, lds0 + E4_SOFF + wave * 2048, M, lds0 + E4_DZ_LDS)
-  e4_dma_wait();
+  fd_dma_wait();
   *(__attribute__((address_space(3))) float*)(unsigned long)(lds0 + E4_MOFF + tid0 * 4) = em_req;
   __syncthreads();
   E4_STAMP(0);
@@ -619,28 +583,29 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
     F.stream = stream; F.lds0 = lds0; F.pa = lds0 + lane * 16; F.tid = tid; F.wave = wave;
     hx8 r[E4_DR];
 #pragma unroll
-    for (int m = 0; m < E4_DR - 1; ++m) r[m] = e4_frag(F.pa + e4_ring_off(m));
+    for (int m = 0; m < E4_DR - 1; ++m) r[m] = fd_frag(F.pa + e4_ring_off(m));
     hx8 H1[24], H2[24];
     // ================= layer 1: fragments 0 .. 95 (12 tiles x 8 k-steps of z, + the fold step)
     {
       const hx8 SEL = e4_sel(lane, tc.ns);
       hx8 Zf[8];
 #pragma unroll
-      for (int s = 0; s < 8; ++s) Zf[s] = e4_frag(zrow + (((2 * s) ^ (half ^ (p & 15))) << 4));
+      for (int s = 0; s < 8; ++s) Zf[s] = fd_frag(zrow + (((2 * s) ^ (half ^ (p & 15))) << 4));
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int T = 0; T < 12; ++T) {
         f32x16 acc;
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-        acc = e4_mfma(FA[T], SEL, acc);
+        acc = fd_mfma32(FA[T], SEL, acc);
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
           const int f = 8 * T + s;
           if (f % E4_CFR == E4_CFR / 2) e4_point<NCH>(F, f / E4_CFR);
           E4_STEP(f, Zf[s], acc);
         }
-        e4_hand_off(acc, H1[2 * T], H1[2 * T + 1]);
+        fd_hand_off(acc, H1[2 * T], H1[2 * T + 1]);
+        __builtin_amdgcn_sched_barrier(0);  // the hand-off of a tile happens here, not batched with later tiles' (register pressure)
       }
     }
     E4_STAMP(1);
@@ -661,7 +626,8 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
         if (f % E4_CFR == E4_CFR / 2) e4_point<NCH>(F, f / E4_CFR);
         E4_STEP(f, H1[s], acc);
       }
-      e4_hand_off(acc, H2[2 * T], H2[2 * T + 1]);
+      fd_hand_off(acc, H2[2 * T], H2[2 * T + 1]);
+      __builtin_amdgcn_sched_barrier(0);  // (as in layer 1)
       if (T < 4) {
         // z in hand-off order: element (half, e) of fragment 2 T + u = feature 32 T + 16 u + 8 (e >> 2) + 4 half + (e & 3): two 8 B pieces of
         // the lane's z row (16 B unit n of row p at n ^ (p & 15)); packed half-precision adds
@@ -669,9 +635,9 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
         const unsigned zrow3 = lds0 + E4_ZOFF + wave * 8192 + (l3 & 31) * 256 + 8 * (l3 >> 5), zsw = l3 & 15;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-          e4_u32x4 zw;
-          const e4_u32x2 z0 = *(e4_lds_w64)(unsigned long)(zrow3 + (((4 * T + 2 * u) ^ zsw) << 4));
-          const e4_u32x2 z1 = *(e4_lds_w64)(unsigned long)(zrow3 + (((4 * T + 2 * u + 1) ^ zsw) << 4));
+          u32x4 zw;
+          const u32x2 z0 = *(e4_lds_w64)(unsigned long)(zrow3 + (((4 * T + 2 * u) ^ zsw) << 4));
+          const u32x2 z1 = *(e4_lds_w64)(unsigned long)(zrow3 + (((4 * T + 2 * u + 1) ^ zsw) << 4));
           zw[0] = z0[0]; zw[1] = z0[1]; zw[2] = z1[0]; zw[3] = z1[1];
           H2[2 * T + u] = H2[2 * T + u] + __builtin_bit_cast(hx8, zw);
         }
@@ -718,7 +684,7 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
     {
       const hx8 SEL = e4_sel(lane, tc.ns);
 #pragma unroll
-      for (int t = 0; t < 4; ++t) E.Y[t] = e4_mfma(FL[t], SEL, E.Y[t]);
+      for (int t = 0; t < 4; ++t) E.Y[t] = fd_mfma32(FL[t], SEL, E.Y[t]);
     }
     E4_STAMP(3);
     // ================= tile boundary: the next tile's fold fragments and pair mask are requested, then the LayerNorm epilogue runs
@@ -739,7 +705,7 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
     *(__attribute__((address_space(3))) float*)(unsigned long)(lds0 + E4_MOFF + tid * 4) = em_req;  // (this lane's own slot)
     E4_STAMP(5);
   }
-  e4_dma_wait();  // the last tile's stream DMAs (chunks 0..2 again, never read) must not outlive the block's LDS
+  fd_dma_wait();  // the last tile's stream DMAs (chunks 0..2 again, never read) must not outlive the block's LDS
   E4_CLK_END;
 #ifdef E4_PROF
   if (tid0 == 0 && blockIdx.x < 256)

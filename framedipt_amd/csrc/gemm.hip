@@ -211,7 +211,6 @@ __global__ __launch_bounds__(FD_THREADS) void linear_splitk_kernel(int M, int N,
 //   Qb the same with queries (B fragments);  rows >= N of Kb are zeroed (kv_zero_pad_kernel)
 //   Vt [B,H,C/32,Np/16,64,8] bf16: V transposed in fragment order, row = channel 32dt + (lane & 31), key position
 //      16s + 8(lane >> 5) + e with the keys permuted inside every 16-group (perm16: C/D fragment -> B fragment order)
-__device__ __forceinline__ int g_perm16(int pos) { return 4 * (pos >> 3) + (pos & 3) + 8 * ((pos & 7) >> 2); }
 
 __global__ __launch_bounds__(FD_THREADS) void ipa_proj_kernel(ProjArgs a) {
   typedef PrecHalf P;
@@ -282,7 +281,7 @@ __global__ __launch_bounds__(FD_THREADS) void ipa_proj_kernel(ProjArgs a) {
         const int ntl = a.Np >> 5;
         if (kind == 2 && mg + 3 < M && (a.N & 3) == 0) {
           const int b = mg / a.N, key = mg - b * a.N;  // 4 keys of one sample (N % 4 == 0), contiguous after perm16
-          const int pp = (key & ~15) + g_perm16(key & 15);
+          const int pp = (key & ~15) + fd_perm16(key & 15);
           u16x4 o = {f2h(v[0]), f2h(v[1]), f2h(v[2]), f2h(v[3])};
           *(u16x4*)(a.Vt + ((((((long)b * a.H + hh) * (a.C >> 5) + (cc >> 5)) * (2 * ntl) + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 +
                              (cc & 31)) << 3) + (pp & 7)) = o;
@@ -298,7 +297,7 @@ __global__ __launch_bounds__(FD_THREADS) void ipa_proj_kernel(ProjArgs a) {
             dst[((((((long)b * a.H + hh) * ntl + (r >> 5)) * (a.C >> 4) + (cc >> 4)) * 64 + ((cc >> 3) & 1) * 32 + (r & 31)) << 3) +
                 (cc & 7)] = f2h(kind == 0 ? v[q] * a.qscale : v[q]);
           } else if (kind == 2) {
-            const int pp = (r & ~15) + g_perm16(r & 15);
+            const int pp = (r & ~15) + fd_perm16(r & 15);
             a.Vt[((((((long)b * a.H + hh) * (a.C >> 5) + (cc >> 5)) * (2 * ntl) + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (cc & 31)) << 3) +
                  (pp & 7)] = f2h(v[q]);
           } else a.pts[(long)m * a.PT + cc] = v[q];
@@ -325,7 +324,7 @@ __global__ void kv_zero_pad_kernel(long BH, int N, int Np, int C, half_t* __rest
     // Kb: channels 8g .. 8g+7 of this key are one 16 B unit
     *(u16x8*)(Kb + ((((bh * ntl + (key >> 5)) * (C >> 4) + (g >> 1)) * 64 + (g & 1) * 32 + (key & 31)) << 3)) = z8;
     // Vt: this key in channels 8g .. 8g+7
-    const int pp = (key & ~15) + g_perm16(key & 15);
+    const int pp = (key & ~15) + fd_perm16(key & 15);
     for (int c = 8 * g; c < 8 * g + 8; ++c) {
       const long o = ((((bh * (C >> 5) + (c >> 5)) * (2 * ntl) + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (c & 31)) << 3) + (pp & 7);
       Vt[o] = 0;
@@ -579,7 +578,6 @@ __global__ __launch_bounds__(512, 1) void outproj_split_kernel(int M, const floa
   float* rm = (float*)(op_smem + 2 * XLO);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, hi = lane >> 5;
   const int m0 = blockIdx.x * 64, z = blockIdx.y;
-  typedef fd_h op_hx4 __attribute__((ext_vector_type(4)));
   FD_STAMP(0);
   // weight fragments of the first k-steps: in flight before anything else
   const size_t woff = ((size_t)(wave * ks_total + z * KSL) * 64 + lane) * 16;
@@ -605,14 +603,14 @@ __global__ __launch_bounds__(512, 1) void outproj_split_kernel(int M, const floa
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int idx = tid + k * 512, r = idx / C4, c4 = idx - r * C4;
-      op_hx4 pk, pl;
+      hx4 pk, pl;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         pk[q] = (fd_h)xv[k][q];
         pl[q] = (fd_h)(xv[k][q] - (float)pk[q]);
       }
-      *(op_hx4*)(op_smem + r * XROW + 8 * c4) = pk;
-      *(op_hx4*)(op_smem + XLO + r * XROW + 8 * c4) = pl;
+      *(hx4*)(op_smem + r * XROW + 8 * c4) = pk;
+      *(hx4*)(op_smem + XLO + r * XROW + 8 * c4) = pl;
     }
   }
   FD_STAMP(3);

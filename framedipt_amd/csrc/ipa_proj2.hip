@@ -24,19 +24,8 @@
 #define P2_XROW (P2_K * 2)                  // bf16 activation row in LDS: 128 rows = exactly one weight buffer (buffer 1)
 #define P2_LDS (2 * P2_WBLK)
 
-typedef fd_h p2_hx2 __attribute__((ext_vector_type(2)));
-typedef float p2_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned p2_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned p2_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int p2_perm16(int pos) { return 4 * (pos >> 3) + (pos & 3) + 8 * ((pos & 7) >> 2); }
-__device__ __forceinline__ void p2_dma16(const void* gsrc, unsigned lds_dst) {
-  const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_dst);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(m0v), "v"(gsrc) : "memory", "m0");
-}
-typedef const __attribute__((address_space(3))) u16x8* p2_lds_u16x8;
-typedef const __attribute__((address_space(3))) f32x4* p2_lds_f32x4;
+// (LDS by 32-bit byte offsets into the dynamic segment: the offset forms of fd_dma16 / fd_frag, common.hpp)
 typedef const __attribute__((address_space(3))) float* p2_lds_f32;
-__device__ __forceinline__ hx8 p2_frag(unsigned off) { return __builtin_bit_cast(hx8, *(p2_lds_u16x8)(unsigned long)off); }
 
 // QK: this block walks the Q / K column blocks (n_walk_qk walkers, blockIdx.y < n_walk_qk) or the V / point blocks
 //
@@ -104,8 +93,8 @@ __device__ __forceinline__ void p2_kpf_units(const ProjArgs& a, const float (&kv
         o[e] = lo ? f2f16(x - f162f(xh)) : xh;
       }
     }
-    const p2_u32x4 val = {o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16), o[4] | ((unsigned)o[5] << 16), o[6] | ((unsigned)o[7] << 16)};
-    *(p2_u32x4*)(a.kpf + ((((((long)b * a.H + h) * ntl + (key >> 5)) * FD_KPF_FRAGS + f) * 64 + hf * 32 + (key & 31)) << 3)) = val;
+    const u32x4 val = {o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16), o[4] | ((unsigned)o[5] << 16), o[6] | ((unsigned)o[7] << 16)};
+    *(u32x4*)(a.kpf + ((((((long)b * a.H + h) * ntl + (key >> 5)) * FD_KPF_FRAGS + f) * 64 + hf * 32 + (key & 31)) << 3)) = val;
   }
 }
 
@@ -172,13 +161,13 @@ __device__ __forceinline__ void p2_points_walk(const ProjArgs& a, const hx8 (&Af
         constexpr int DEPTH = 3;
         hx8 wh[DEPTH], wl[DEPTH];
 #pragma unroll
-        for (int s = 0; s < DEPTH - 1; ++s) { wh[s] = p2_frag(wbh + s * 1024); wl[s] = p2_frag(wbl + s * 1024); }
+        for (int s = 0; s < DEPTH - 1; ++s) { wh[s] = fd_frag(wbh + s * 1024); wl[s] = fd_frag(wbl + s * 1024); }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < P2_KS; ++s) {  // (the order of the three products of the other point epilogue: same sums)
           if (s + DEPTH - 1 < P2_KS) {
-            wh[(s + DEPTH - 1) % DEPTH] = p2_frag(wbh + (s + DEPTH - 1) * 1024);
-            wl[(s + DEPTH - 1) % DEPTH] = p2_frag(wbl + (s + DEPTH - 1) * 1024);
+            wh[(s + DEPTH - 1) % DEPTH] = fd_frag(wbh + (s + DEPTH - 1) * 1024);
+            wl[(s + DEPTH - 1) % DEPTH] = fd_frag(wbl + (s + DEPTH - 1) * 1024);
           }
           const hx8 h = wh[s % DEPTH], l = wl[s % DEPTH];
           acc[j] = fd_mfma32(Af[s], l, acc[j]);
@@ -236,10 +225,10 @@ __device__ __forceinline__ void p2_points_walk(const ProjArgs& a, const hx8 (&Af
       for (int t = tid; t < 64 * 24; t += 512) {
         const int k4 = t & 63, rest = t >> 6, vh = rest / 12, e = rest - 12 * vh, mg = m0 + 4 * k4;
         if (mg >= M) continue;  // (M % 4 == 0: the 4-run is whole)
-        const int b = mg / a.N, key = mg - b * a.N, pp = (key & ~15) + p2_perm16(key & 15), h = 2 * k + vh;
+        const int b = mg / a.N, key = mg - b * a.N, pp = (key & ~15) + fd_perm16(key & 15), h = 2 * k + vh;
         f32x4 pc[3];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) pc[d] = *(p2_lds_f32x4)(unsigned long)tile_at(36 * vh + 3 * e + d, k4);
+        for (int d = 0; d < 3; ++d) pc[d] = *(fd_lds_f32x4)(unsigned long)tile_at(36 * vh + 3 * e + d, k4);
         unsigned short vhs[3][4], vls[3][4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -258,8 +247,8 @@ __device__ __forceinline__ void p2_points_walk(const ProjArgs& a, const hx8 (&Af
           const long bh3 = ((long)b * H + h) * 3;
           const long oh = ((((bh3 + (rw >> 5)) * ks + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (rw & 31)) << 3) + (pp & 7);
           const long ol = ((((bh3 + (rl >> 5)) * ks + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (rl & 31)) << 3) + (pp & 7);
-          *(p2_u32x2*)(a.vpt + oh) = p2_u32x2{vhs[d][0] | ((unsigned)vhs[d][1] << 16), vhs[d][2] | ((unsigned)vhs[d][3] << 16)};
-          *(p2_u32x2*)(a.vpt + ol) = p2_u32x2{vls[d][0] | ((unsigned)vls[d][1] << 16), vls[d][2] | ((unsigned)vls[d][3] << 16)};
+          *(u32x2*)(a.vpt + oh) = u32x2{vhs[d][0] | ((unsigned)vhs[d][1] << 16), vhs[d][2] | ((unsigned)vhs[d][3] << 16)};
+          *(u32x2*)(a.vpt + ol) = u32x2{vls[d][0] | ((unsigned)vls[d][1] << 16), vls[d][2] | ((unsigned)vls[d][3] << 16)};
         }
       }
     } else {
@@ -319,10 +308,10 @@ __device__ __forceinline__ void p2_node_rows(const ProjArgs& a, const hx8 (&Af)[
         w[q] = *(p2_lds_u32)(unsigned long)(xl + rr * P2_XROW + (((cc >> 3) ^ (rr & 15)) << 4) + (cc & 7) * 2);
       }
       if (mg >= M) continue;
-      const int b = mg / a.N, key = mg - b * a.N, pp = (key & ~15) + p2_perm16(key & 15);
+      const int b = mg / a.N, key = mg - b * a.N, pp = (key & ~15) + fd_perm16(key & 15);
       const long u0 = ((((long)b * 8 + (cc >> 5)) * (2 * ntl) + (pp >> 4)) * 64 + ((pp >> 3) & 1) * 32 + (cc & 31)) * 8 + (pp & 7);
-      *(p2_u32x2*)(img + u0) = p2_u32x2{(w[0] & 0xffffu) | (w[1] << 16), (w[2] & 0xffffu) | (w[3] << 16)};
-      *(p2_u32x2*)(img + u0 + 8) = p2_u32x2{(w[0] >> 16) | (w[1] & 0xffff0000u), (w[2] >> 16) | (w[3] & 0xffff0000u)};
+      *(u32x2*)(img + u0) = u32x2{(w[0] & 0xffffu) | (w[1] << 16), (w[2] & 0xffffu) | (w[3] << 16)};
+      *(u32x2*)(img + u0 + 8) = u32x2{(w[0] >> 16) | (w[1] & 0xffff0000u), (w[2] >> 16) | (w[3] & 0xffff0000u)};
     }
   }
 }
@@ -354,15 +343,15 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
     const char* src = wimg + (size_t)c * P2_WBLK;
 #pragma unroll
     for (int u = 0; u < P2_WBLK / (FD_THREADS * 16); ++u)
-      p2_dma16(src + (size_t)(u * FD_THREADS + tid) * 16, lds0 + buf * P2_WBLK + (unsigned)(u * FD_THREADS + (tid & ~63)) * 16);
+      fd_dma16(src + (size_t)(u * FD_THREADS + tid) * 16, lds0 + buf * P2_WBLK + (unsigned)(u * FD_THREADS + (tid & ~63)) * 16);
   };
   auto request_half = [&](int c, int half, int buf) {  // SPLIT: tiles 2 half, 2 half + 1 of column block c, hi then lo part
     const size_t so = (size_t)c * P2_WBLK + (size_t)half * P2S_HALF;
 #pragma unroll
     for (int u = 0; u < P2S_HALF / (NTH * 16); ++u) {
       const unsigned d = lds0 + buf * P2S_STAGE + (unsigned)(u * NTH + (tid & ~63)) * 16;
-      p2_dma16(wimg + so + (size_t)(u * NTH + tid) * 16, d);
-      p2_dma16(wimg_lo + so + (size_t)(u * NTH + tid) * 16, d + P2S_HALF);
+      fd_dma16(wimg + so + (size_t)(u * NTH + tid) * 16, d);
+      fd_dma16(wimg_lo + so + (size_t)(u * NTH + tid) * 16, d + P2S_HALF);
     }
   };
   FD_STAMP(0);
@@ -406,13 +395,13 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
 #pragma unroll
           for (int q = 0; q < 4; ++q) x[q] -= h2f(f2h(x[q]));
         }
-        const p2_u32x2 h = {fd_cvt_pk(x[0], x[1]), fd_cvt_pk(x[2], x[3])};
-        *(p2_u32x2*)(xs + r * P2_XROW + (((lane >> 1) ^ (r & 15)) << 4) + 8 * (lane & 1)) = h;
+        const u32x2 h = {fd_cvt_pk(x[0], x[1]), fd_cvt_pk(x[2], x[3])};
+        *(u32x2*)(xs + r * P2_XROW + (((lane >> 1) ^ (r & 15)) << 4) + 8 * (lane & 1)) = h;
       }
       __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the wave's own writes have landed (wave-private tile: no barrier)
 #pragma unroll
       for (int s = 0; s < P2_KS; ++s) {
-        const hx8 f = p2_frag(xl + li * P2_XROW + (((2 * s + hi) ^ (li & 15)) << 4));
+        const hx8 f = fd_frag(xl + li * P2_XROW + (((2 * s + hi) ^ (li & 15)) << 4));
         if (pass == 0) Af[0][s] = f;
         else Al[0][s] = f;
       }
@@ -426,8 +415,8 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
       const int idx = tid + it * FD_THREADS, r = idx >> 6, c4 = idx & 63;
       const int gr = m0 + r < M ? m0 + r : M - 1;
       const f32x4 x = *(const f32x4*)(a.A + (long)gr * a.lda + 4 * c4);
-      const p2_u32x2 h = {fd_cvt_pk(x[0], x[1]), fd_cvt_pk(x[2], x[3])};
-      *(p2_u32x2*)(xs + r * P2_XROW + (((c4 >> 1) ^ (r & 15)) << 4) + 8 * (c4 & 1)) = h;
+      const u32x2 h = {fd_cvt_pk(x[0], x[1]), fd_cvt_pk(x[2], x[3])};
+      *(u32x2*)(xs + r * P2_XROW + (((c4 >> 1) ^ (r & 15)) << 4) + 8 * (c4 & 1)) = h;
     }
     __syncthreads();
 #pragma unroll
@@ -435,7 +424,7 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
 #pragma unroll
       for (int s = 0; s < P2_KS; ++s) {
         const int r = (wr * 2 + i) * 32 + li;
-        Af[i][s] = p2_frag(lds0 + P2_WBLK + r * P2_XROW + (((2 * s + hi) ^ (r & 15)) << 4));
+        Af[i][s] = fd_frag(lds0 + P2_WBLK + r * P2_XROW + (((2 * s + hi) ^ (r & 15)) << 4));
       }
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the fragments are in registers before the buffer is overwritten
   }
@@ -463,7 +452,7 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int mg = m0 + (wr * TM + i) * 32 + 8 * g + 4 * hi;
-      const int bb = mg < M ? mg / a.N : 0, key = mg - bb * a.N, pp = (key & ~15) + p2_perm16(key & 15);
+      const int bb = mg < M ? mg / a.N : 0, key = mg - bb * a.N, pp = (key & ~15) + fd_perm16(key & 15);
       v_row[i][g] = mg + 3 < M ? (bb * a.H * (a.C >> 5) * (2 * ntl) + (pp >> 4)) * 512 + ((pp >> 3) & 1) * 256 + (pp & 7) : -1;
       p_row[i][g] = mg + 3 < M ? mg * a.PT : -1;
     }
@@ -481,13 +470,13 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
       if ((g & 1) || qk_row[i] < 0) return;
       const f32x4 b0 = BQ.q(j, g), b1 = BQ.q(j, g + 1);
       const float sc = kind == 0 ? a.qscale : 1.f;
-      const p2_u32x4 o = {fd_cvt_pk((acc[i][j][4 * g] + b0[0]) * sc, (acc[i][j][4 * g + 1] + b0[1]) * sc),
+      const u32x4 o = {fd_cvt_pk((acc[i][j][4 * g] + b0[0]) * sc, (acc[i][j][4 * g + 1] + b0[1]) * sc),
                           fd_cvt_pk((acc[i][j][4 * g + 2] + b0[2]) * sc, (acc[i][j][4 * g + 3] + b0[3]) * sc),
                           fd_cvt_pk((acc[i][j][4 * g + 4] + b1[0]) * sc, (acc[i][j][4 * g + 5] + b1[1]) * sc),
                           fd_cvt_pk((acc[i][j][4 * g + 6] + b1[2]) * sc, (acc[i][j][4 * g + 7] + b1[3]) * sc)};
       // cc = cbase + (2 wc + j) 32 + 16 G + 8 hi: cc >> 4 = (cbase >> 4) + 2 (2 wc + j) + G, (cc >> 3) & 1 = hi, cc & 7 = 0
       half_t* dst = (kind == 0 ? a.Qb : a.Kb) + (long)qk_row[i] + cpart[0] + ((2 * j + (g >> 1)) * 64) * 8;
-      *(p2_u32x4*)dst = o;
+      *(u32x4*)dst = o;
     } else {
       if (cpart[j] < 0) return;
       const float bv = BQ.s(j);
@@ -496,14 +485,14 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
       for (int q = 0; q < 4; ++q) v[q] = acc[i][j][4 * g + q] + bv;
       if (kind == 2) {
         if (v_row[i][g] < 0) return;
-        const p2_u32x2 o = {fd_cvt_pk(v[0], v[1]), fd_cvt_pk(v[2], v[3])};
-        *(p2_u32x2*)(a.Vt + (long)v_row[i][g] + cpart[j]) = o;
+        const u32x2 o = {fd_cvt_pk(v[0], v[1]), fd_cvt_pk(v[2], v[3])};
+        *(u32x2*)(a.Vt + (long)v_row[i][g] + cpart[j]) = o;
         if (SPLIT && a.Vt_lo) {  // V - half(V): the attention multiplies P with V_hi + V_lo (attention3.hip)
           float w[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) w[q] = v[q] - h2f(f2h(v[q]));
-          const p2_u32x2 ol = {fd_cvt_pk(w[0], w[1]), fd_cvt_pk(w[2], w[3])};
-          *(p2_u32x2*)(a.Vt_lo + (long)v_row[i][g] + cpart[j]) = ol;
+          const u32x2 ol = {fd_cvt_pk(w[0], w[1]), fd_cvt_pk(w[2], w[3])};
+          *(u32x2*)(a.Vt_lo + (long)v_row[i][g] + cpart[j]) = ol;
         }
       } else {
         if (p_row[i][g] < 0) return;
@@ -539,7 +528,7 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
     // bias from LDS: nb = first column of the half block (c * 128 + 64 wc)
     struct BiasLds {
       unsigned base; int hi, li;
-      __device__ __forceinline__ f32x4 q(int j, int g) const { return *(p2_lds_f32x4)(unsigned long)(base + 4 * (j * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1))); }
+      __device__ __forceinline__ f32x4 q(int j, int g) const { return *(fd_lds_f32x4)(unsigned long)(base + 4 * (j * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1))); }
       __device__ __forceinline__ float s(int j) const { return *(p2_lds_f32)(unsigned long)(base + 4 * (j * 32 + li)); }
     };
     const int n_hs = kb < n_class ? 2 * ((n_class - 1 - kb) / n_walkers + 1) : 0;  // half-steps of this walker
@@ -574,13 +563,13 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
       constexpr int DEPTH = 3;
       hx8 wh[DEPTH], wl[DEPTH];
 #pragma unroll
-      for (int s = 0; s < DEPTH - 1; ++s) { wh[s] = p2_frag(wbh + s * 1024); wl[s] = p2_frag(wbl + s * 1024); }
+      for (int s = 0; s < DEPTH - 1; ++s) { wh[s] = fd_frag(wbh + s * 1024); wl[s] = fd_frag(wbl + s * 1024); }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < P2_KS; ++s) {
         if (s + DEPTH - 1 < P2_KS) {
-          wh[(s + DEPTH - 1) % DEPTH] = p2_frag(wbh + (s + DEPTH - 1) * 1024);
-          wl[(s + DEPTH - 1) % DEPTH] = p2_frag(wbl + (s + DEPTH - 1) * 1024);
+          wh[(s + DEPTH - 1) % DEPTH] = fd_frag(wbh + (s + DEPTH - 1) * 1024);
+          wl[(s + DEPTH - 1) % DEPTH] = fd_frag(wbl + (s + DEPTH - 1) * 1024);
         }
         const hx8 h = wh[s % DEPTH], l = wl[s % DEPTH];
         if constexpr (QK) {  // operands exchanged: lane = row.  Small terms first, then the hi x hi product
@@ -652,15 +641,15 @@ __device__ __forceinline__ void ipa_proj2_body(const ProjArgs& a, int n_cblk, in
     hx8 w0[DEPTH], w1[DEPTH];
 #pragma unroll
     for (int s = 0; s < DEPTH - 1; ++s) {
-      w0[s] = p2_frag(wb + s * 1024);
-      w1[s] = p2_frag(wb + (P2_KS + s) * 1024);
+      w0[s] = fd_frag(wb + s * 1024);
+      w1[s] = fd_frag(wb + (P2_KS + s) * 1024);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < P2_KS; ++s) {
       if (s + DEPTH - 1 < P2_KS) {
-        w0[(s + DEPTH - 1) % DEPTH] = p2_frag(wb + (s + DEPTH - 1) * 1024);
-        w1[(s + DEPTH - 1) % DEPTH] = p2_frag(wb + (P2_KS + s + DEPTH - 1) * 1024);
+        w0[(s + DEPTH - 1) % DEPTH] = fd_frag(wb + (s + DEPTH - 1) * 1024);
+        w1[(s + DEPTH - 1) % DEPTH] = fd_frag(wb + (P2_KS + s + DEPTH - 1) * 1024);
       }
       if constexpr (QK) {  // operands exchanged: lane = row
 #pragma unroll
@@ -762,14 +751,14 @@ __global__ void node_images_kernel(int B, int N, int Np, const float* __restrict
       const int cg = (int)(u % (C / 8));
       const long br = u / (C / 8);
       const int r = (int)(br % Np), b = (int)(br / Np);
-      p2_u32x4 o = {0u, 0u, 0u, 0u};
+      u32x4 o = {0u, 0u, 0u, 0u};
       if (r < N) {
         const float* x = node + ((long)b * N + r) * ld + 8 * cg;
         const f32x4 x0 = *(const f32x4*)x, x1 = *(const f32x4*)(x + 4);
-        o = p2_u32x4{fd_cvt_pk(x0[0], x0[1]), fd_cvt_pk(x0[2], x0[3]), fd_cvt_pk(x1[0], x1[1]), fd_cvt_pk(x1[2], x1[3])};
+        o = u32x4{fd_cvt_pk(x0[0], x0[1]), fd_cvt_pk(x0[2], x0[3]), fd_cvt_pk(x1[0], x1[1]), fd_cvt_pk(x1[2], x1[3])};
       }
       // element ((((b ntl + (r >> 5)) (C >> 4) + (cc >> 4)) 64 + ((cc >> 3) & 1) 32 + (r & 31)) 8 + (cc & 7), cc = 8 cg
-      *(p2_u32x4*)(Kb + ((((long)b * ntl + (r >> 5)) * (C >> 4) + (cg >> 1)) * 64 + (cg & 1) * 32 + (r & 31)) * 8) = o;
+      *(u32x4*)(Kb + ((((long)b * ntl + (r >> 5)) * (C >> 4) + (cg >> 1)) * 64 + (cg & 1) * 32 + (r & 31)) * 8) = o;
     } else {
       const long v = u - nk;
       const int lane = (int)(v & 63), half = lane >> 5, c5 = lane & 31;
@@ -785,14 +774,14 @@ __global__ void node_images_kernel(int B, int N, int Np, const float* __restrict
         const int key = 16 * s16 + pos;
         xv[e] = key < N ? node[((long)b * N + key) * ld + cc] : 0.f;
       }
-      p2_u32x4 oh, ol;
+      u32x4 oh, ol;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         oh[q] = fd_cvt_pk(xv[2 * q], xv[2 * q + 1]);
         ol[q] = fd_cvt_pk(xv[2 * q] - h2f(f2h(xv[2 * q])), xv[2 * q + 1] - h2f(f2h(xv[2 * q + 1])));
       }
-      *(p2_u32x4*)(Vt + v * 8) = oh;
-      if (Vt_lo) *(p2_u32x4*)(Vt_lo + v * 8) = ol;
+      *(u32x4*)(Vt + v * 8) = oh;
+      if (Vt_lo) *(u32x4*)(Vt_lo + v * 8) = ol;
     }
   }
 }

@@ -428,6 +428,7 @@ struct EtfDma {
     for (int j = 0; j < 5; ++j) {
       // instruction i = mw + 4 j of the slot (18, 19 repeat 14, 15): mw < 2 -> j * 4 KB, else the last one stays at j = 3
       const unsigned m0v = ws + slot * ETF_WS + ((j == 4 && mw >= 2) ? 3u : (unsigned)j) * 4096u;
+      // (fd_dma16 of common.hpp, which says why this is asm, with an SGPR base + 32-bit VGPR offset instead of its 64-bit VGPR address)
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(m0v), "v"(off[j]), "s"(sb) : "memory", "m0");
     }
   }
@@ -739,13 +740,6 @@ __global__ __launch_bounds__(FD_THREADS) void edge_embed_kernel(EdgeEmbedArgs a)
 #ifdef EEP_PROF  // phase profile (tools/micro/eep_bench.hip -DEEP_PROF): cycles of wave 0 / wave 4 of block 0 per phase, and in the barriers
 __device__ unsigned long long eep_prof[2][8];
 #endif
-template <int N_, class F>
-__device__ __forceinline__ void eep_for(F&& f) {  // f(integral_constant<0>) ... f(integral_constant<N_ - 1>)
-  if constexpr (N_ > 0) {
-    eep_for<N_ - 1>(f);
-    f(std::integral_constant<int, N_ - 1>{});
-  }
-}
 __device__ __forceinline__ int eep_off(int row, int col) {  // float offset of element (row, col) of a swizzled [rows][128] fp32 tile
   return row * 128 + ((((col >> 2) ^ (row & 15)) << 2) | (col & 3));
 }
@@ -968,7 +962,7 @@ __global__ __launch_bounds__(2 * FD_THREADS, 1) void edge_embed_f32p_kernel(Edge
   // one only finishes team 1's last tile.  Every wave executes every barrier.
   bool started = team == 0;  // team 1 has no tile in flight during slots 0..2 of round 0
   for (int round = 0; round <= n_first; ++round) {
-    eep_for<6>([&](auto S) {
+    fd_static_for<6>([&](auto S) {
       constexpr int s = decltype(S)::value;
 #ifdef EEP_PROF
       const unsigned long long t0_ = __builtin_amdgcn_s_memtime();

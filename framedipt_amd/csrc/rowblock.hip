@@ -21,8 +21,6 @@
 
 #define RB_SROW 144       // bytes per row of a wave's 32 x 32 fp32 exchange tile
 
-typedef fd_h rb_hx4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ hx8 rb_ld(const char* p) { return __builtin_bit_cast(hx8, *(const u16x8*)p); }
 __host__ __device__ constexpr int rb_max(int a, int b) { return a > b ? a : b; }
 
 // K0: input width (zero-padded to a multiple of 16); N1 / N2: hidden widths (0 = absent); NOUT: output width;
@@ -33,14 +31,6 @@ __host__ __device__ constexpr int rb_max(int a, int b) { return a > b ? a : b; }
 // path whose operand rounding dominates the error of the predicted frames / psi use it (tests/err_budget.py).
 // Activation rows in LDS are [32][width bf16 + 16 B]: with widths 80..320 the 16 lanes of a b128 read hit 16 distinct
 // 16 B slots, no swizzle needed.
-template <int N, class F>
-__device__ __forceinline__ void ch_rb_for(F&& f) {  // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
-  if constexpr (N > 0) {
-    ch_rb_for<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
-
 template <int K0, int N1, int N2, int NOUT, int FLAGS>
 struct RBShape {
   static constexpr int KS0 = (K0 + 15) / 16;
@@ -96,7 +86,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
   auto w_load = [&](auto BUF, auto KSC, const char* img, int T) {
     constexpr int bf = decltype(BUF)::value, KS = decltype(KSC)::value;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) Wf[bf][s] = rb_ld(img + ((size_t)(T * KS + s) * 64 + lane) * 16);
+    for (int s = 0; s < KS; ++s) Wf[bf][s] = fd_frag(img + ((size_t)(T * KS + s) * 64 + lane) * 16);
   };
   w_load(std::integral_constant<int, 0>{}, std::integral_constant<int, KS0>{}, wimg[0], wave);
   if constexpr (SPLIT) w_load(std::integral_constant<int, 1>{}, std::integral_constant<int, KS0>{}, wlo[0], wave);
@@ -135,15 +125,15 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int idx = tid + k * FD_THREADS, r = idx / C4, c4 = idx % C4;
-      rb_hx4 pk, pl;
+      hx4 pk, pl;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         pk[q] = (fd_h)xv[k][q];
         pl[q] = (fd_h)(xv[k][q] - (float)pk[q]);
       }
       if (idx < 32 * C4) {
-        *(rb_hx4*)(xs + r * XROW + 8 * c4) = pk;
-        if constexpr (SPLIT) *(rb_hx4*)(xs + XLO + r * XROW + 8 * c4) = pl;
+        *(hx4*)(xs + r * XROW + 8 * c4) = pk;
+        if constexpr (SPLIT) *(hx4*)(xs + XLO + r * XROW + 8 * c4) = pl;
       }
     }
   }
@@ -175,7 +165,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
       // per tile: Whi.xhi + Whi.xlo out of buffer 0, then Wlo.xhi out of buffer 1; the next tile's hi fragments are requested
       // when buffer 0 is free (under the lo pass), its lo fragments when buffer 1 is (under the next tile's hi passes)
       static_assert(!SWAP, "one tile in flight: untransposed products only");
-      ch_rb_for<NTW>([&](auto U) {
+      fd_static_for<NTW>([&](auto U) {
         constexpr int u = decltype(U)::value;
         const int T = wave + 4 * u;
         if (T < NT) {
@@ -198,7 +188,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
     if constexpr (SPLIT && PAIRS == 2) {
       // two tiles in flight: tile u lives in buffers 2 (u & 1) (hi) and 2 (u & 1) + 1 (lo); tile u + 1 is requested before the
       // products of tile u start (tile 0 was requested by the caller)
-      ch_rb_for<NTW>([&](auto U) {
+      fd_static_for<NTW>([&](auto U) {
         constexpr int u = decltype(U)::value, bh = 2 * (u & 1), bn = 2 * ((u + 1) & 1);
         const int T = wave + 4 * u;
         if (u + 1 < NTW && T + 4 < NT) {
@@ -228,7 +218,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
       load_tile(std::integral_constant<int, 1>{});
       load_tile(std::integral_constant<int, 2>{});
     }
-    ch_rb_for<NTW>([&](auto U) {
+    fd_static_for<NTW>([&](auto U) {
       constexpr int u = decltype(U)::value;
       const int T = wave + 4 * u;
       load_tile(std::integral_constant<int, u + NB - 1>{});
@@ -255,7 +245,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
         for (int g = 0; g < 4; ++g) {
           const int f0 = 32 * T + 8 * g + 4 * hi;
           const f32x4 bv = *(const f32x4*)(bias + f0);
-          rb_hx4 pk, pl;
+          hx4 pk, pl;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             float v = acc[u][4 * g + q] + bv[q];
@@ -263,9 +253,9 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
             pk[q] = (fd_h)v;
             pl[q] = (fd_h)(v - (float)pk[q]);
           }
-          *(rb_hx4*)(dst + li * XROW + 2 * f0) = pk;
-          if constexpr (SPLIT) *(rb_hx4*)(dst + XLO + li * XROW + 2 * f0) = pl;
-          if (hid_h16 && row0 + li < a.M) *(rb_hx4*)(hid_h16 + (long)(row0 + li) * hid_ld + f0) = pk;  // optional bf16 copy of the rows
+          *(hx4*)(dst + li * XROW + 2 * f0) = pk;
+          if constexpr (SPLIT) *(hx4*)(dst + XLO + li * XROW + 2 * f0) = pl;
+          if (hid_h16 && row0 + li < a.M) *(hx4*)(hid_h16 + (long)(row0 + li) * hid_ld + f0) = pk;  // optional bf16 copy of the rows
         }
       }
     }
@@ -273,8 +263,8 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
   auto x_load = [&](auto KSC, const char* buf) {  // this lane's B fragments of the activation rows in `buf`
 #pragma unroll
     for (int s = 0; s < decltype(KSC)::value; ++s) {
-      X[s] = rb_ld(buf + li * XROW + 32 * s + 16 * hi);
-      if constexpr (SPLIT) Xl[s] = rb_ld(buf + XLO + li * XROW + 32 * s + 16 * hi);
+      X[s] = fd_frag(buf + li * XROW + 32 * s + 16 * hi);
+      if constexpr (SPLIT) Xl[s] = fd_frag(buf + XLO + li * XROW + 32 * s + 16 * hi);
     }
   };
   auto w_first = [&](auto KSC, int l, int toff) {  // first tile of layer l: in flight across the barrier
@@ -495,7 +485,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
   auto w_load = [&](auto BUF, const char* img, int T) {
     constexpr int bf = decltype(BUF)::value;
 #pragma unroll
-    for (int s = 0; s < TL_KS; ++s) Wf[bf][s] = rb_ld(img + ((size_t)(T * TL_KS + s) * 64 + lane) * 16);
+    for (int s = 0; s < TL_KS; ++s) Wf[bf][s] = fd_frag(img + ((size_t)(T * TL_KS + s) * 64 + lane) * 16);
   };
   // first tile of a stage: hi fragments -> buffer 0 (SPLIT: lo fragments -> buffer 1)
   auto w_first = [&](const void* img, const void* img_lo) {
@@ -505,14 +495,14 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
   // 4 values -> half-precision row pieces at byte offset `off` of an activation buffer (SPLIT: hi and lo parts)
   auto put4 = [&](char* buf, int off, float v0, float v1, float v2, float v3) {
     const float v[4] = {v0, v1, v2, v3};
-    rb_hx4 pk, pl;
+    hx4 pk, pl;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       pk[q] = (fd_h)v[q];
       pl[q] = (fd_h)(v[q] - (float)pk[q]);
     }
-    *(rb_hx4*)(buf + off) = pk;
-    if constexpr (SPLIT) *(rb_hx4*)(buf + XLO + off) = pl;
+    *(hx4*)(buf + off) = pk;
+    if constexpr (SPLIT) *(hx4*)(buf + XLO + off) = pl;
   };
   w_first(a.wo, a.wol);
   {
@@ -570,14 +560,14 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
   const char* xl_base = nullptr;  // SPLIT: this lane's lo fragments of the current stage input (LDS)
   auto x_load = [&](const char* buf) {
 #pragma unroll
-    for (int s = 0; s < TL_KS; ++s) X[s] = rb_ld(buf + li * TL_XROW + 32 * s + 16 * hi);
+    for (int s = 0; s < TL_KS; ++s) X[s] = fd_frag(buf + li * TL_XROW + 32 * s + 16 * hi);
     xl_base = buf + XLO + li * TL_XROW + 16 * hi;
   };
   auto layer = [&](const void* img_, const void* img_lo_, auto NTC) {
     constexpr int NT = decltype(NTC)::value, NU = (NT + 3) / 4;
     const char* img = (const char*)img_;
     const char* img_lo = (const char*)img_lo_;
-    ch_rb_for<NU>([&](auto U) {
+    fd_static_for<NU>([&](auto U) {
       constexpr int u = decltype(U)::value;
       const int T = wave + 4 * u;
       const bool more = u + 1 < NU && T + 4 < NT;
@@ -592,12 +582,12 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
           for (int s = 0; s < TL_KS; ++s) c = fd_mfma32(Wf[HB][s], X[s], c);
           {  // hi x lo: the lo fragments of the activations from LDS, three reads in flight
             hx8 xr[3];
-            xr[0] = rb_ld(xl_base);
-            xr[1] = rb_ld(xl_base + 32);
+            xr[0] = fd_frag(xl_base);
+            xr[1] = fd_frag(xl_base + 32);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int s = 0; s < TL_KS; ++s) {
-              if (s + 2 < TL_KS) xr[(s + 2) % 3] = rb_ld(xl_base + 32 * (s + 2));
+              if (s + 2 < TL_KS) xr[(s + 2) % 3] = fd_frag(xl_base + 32 * (s + 2));
               c = fd_mfma32(Wf[HB][s], xr[s % 3], c);
               __builtin_amdgcn_sched_barrier(0);  // pin: one read, one product per k-step (hipcc otherwise sinks the reads to their uses)
             }
@@ -826,20 +816,20 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void tfmr_tail16_kernel(Tf
     constexpr int b = decltype(BUF)::value;
 #pragma unroll
     for (int s = 0; s < T16_KS; ++s) {
-      Wh[b][s] = rb_ld((const char*)img + ((size_t)(T * T16_KS + s) * 64 + lane) * 16);
-      Wl[b][s] = rb_ld((const char*)img_lo + ((size_t)(T * T16_KS + s) * 64 + lane) * 16);
+      Wh[b][s] = fd_frag((const char*)img + ((size_t)(T * T16_KS + s) * 64 + lane) * 16);
+      Wl[b][s] = fd_frag((const char*)img_lo + ((size_t)(T * T16_KS + s) * 64 + lane) * 16);
     }
   };
   auto put4 = [&](char* buf, int off, float v0, float v1, float v2, float v3) {
     const float v[4] = {v0, v1, v2, v3};
-    rb_hx4 pk, pl;
+    hx4 pk, pl;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       pk[q] = (fd_h)v[q];
       pl[q] = (fd_h)(v[q] - (float)pk[q]);
     }
-    *(rb_hx4*)(buf + off) = pk;
-    *(rb_hx4*)(buf + T16_XLO + off) = pl;
+    *(hx4*)(buf + off) = pk;
+    *(hx4*)(buf + T16_XLO + off) = pl;
   };
   constexpr std::integral_constant<int, 0> B0{};
   constexpr std::integral_constant<int, 1> B1{};
@@ -882,7 +872,7 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void tfmr_tail16_kernel(Tf
   const char* xl_base = nullptr;  // this lane's lo fragments of the current stage input (read from LDS by the hi x lo pass: 40 registers less)
   auto x_load = [&](const char* buf) {
 #pragma unroll
-    for (int s = 0; s < T16_KS; ++s) X[s] = rb_ld(buf + lr * T16_XROW + (32 * s + 8 * fg) * 2);
+    for (int s = 0; s < T16_KS; ++s) X[s] = fd_frag(buf + lr * T16_XROW + (32 * s + 8 * fg) * 2);
     xl_base = buf + T16_XLO + lr * T16_XROW + 16 * fg;
   };
   f32x4 acc[5], xa[5];
@@ -892,7 +882,7 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void tfmr_tail16_kernel(Tf
   // one stage: tiles wave, wave + 4, ... (< NT); the first tile's fragments are in buffer 0, tile u + 1 is requested when tile u starts
   auto layer = [&](const void* img, const void* img_lo, auto NTC) {
     constexpr int NT = decltype(NTC)::value, NU = NT / 4;
-    ch_rb_for<NU>([&](auto U) {
+    fd_static_for<NU>([&](auto U) {
       constexpr int u = decltype(U)::value, b = u & 1;
       const int T = wave + 4 * u;
       if constexpr (u + 1 < NU) {
@@ -904,11 +894,11 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void tfmr_tail16_kernel(Tf
       for (int s = 0; s < T16_KS; ++s) c = mma(Wh[b][s], X[s], c);
       {
         hx8 xr[3];
-        xr[0] = rb_ld(xl_base);
-        xr[1] = rb_ld(xl_base + 64);
+        xr[0] = fd_frag(xl_base);
+        xr[1] = fd_frag(xl_base + 64);
 #pragma unroll
         for (int s = 0; s < T16_KS; ++s) {
-          if (s + 2 < T16_KS) xr[(s + 2) % 3] = rb_ld(xl_base + 64 * (s + 2));
+          if (s + 2 < T16_KS) xr[(s + 2) % 3] = fd_frag(xl_base + 64 * (s + 2));
           c = mma(Wh[b][s], xr[s % 3], c);
         }
       }
@@ -1065,22 +1055,22 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
     constexpr int b = decltype(BUF)::value, KS = decltype(KSC)::value;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      Wh[b][s] = rb_ld((const char*)img + ((size_t)(T * KS + s) * 64 + lane) * 16);
-      Wl[b][s] = rb_ld((const char*)img_lo + ((size_t)(T * KS + s) * 64 + lane) * 16);
+      Wh[b][s] = fd_frag((const char*)img + ((size_t)(T * KS + s) * 64 + lane) * 16);
+      Wl[b][s] = fd_frag((const char*)img_lo + ((size_t)(T * KS + s) * 64 + lane) * 16);
     }
   };
   constexpr std::integral_constant<int, KS0> K0C{};
   constexpr std::integral_constant<int, TR_KS> K8C{};
   auto put4 = [&](char* buf, int off, float v0, float v1, float v2, float v3) {
     const float v[4] = {v0, v1, v2, v3};
-    rb_hx4 pk, pl;
+    hx4 pk, pl;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       pk[q] = (fd_h)v[q];
       pl[q] = (fd_h)(v[q] - (float)pk[q]);
     }
-    *(rb_hx4*)(buf + off) = pk;
-    *(rb_hx4*)(buf + TR_XLO + off) = pl;
+    *(hx4*)(buf + off) = pk;
+    *(hx4*)(buf + TR_XLO + off) = pl;
   };
   constexpr std::integral_constant<int, 0> B0{};
   constexpr std::integral_constant<int, 1> B1{};
@@ -1127,7 +1117,7 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
   const char* xl_base = nullptr;
   auto x_load = [&](auto KSC, const char* buf) {
 #pragma unroll
-    for (int s = 0; s < decltype(KSC)::value; ++s) X[s] = rb_ld(buf + lr * TR_XROW + (32 * s + 8 * fg) * 2);
+    for (int s = 0; s < decltype(KSC)::value; ++s) X[s] = fd_frag(buf + lr * TR_XROW + (32 * s + 8 * fg) * 2);
     xl_base = buf + TR_XLO + lr * TR_XROW + 16 * fg;
   };
   f32x4 acc[4];
@@ -1136,7 +1126,7 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
   };
   auto layer = [&](auto KSC, const void* img, const void* img_lo) {
     constexpr int KS = decltype(KSC)::value;
-    ch_rb_for<4>([&](auto U) {
+    fd_static_for<4>([&](auto U) {
       constexpr int u = decltype(U)::value, b = u & 1;
       const int T = wave + 4 * u;
       if constexpr (u + 1 < 4) {
@@ -1148,11 +1138,11 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
       for (int s = 0; s < KS; ++s) c = mma(Wh[b][s], X[s], c);
       {
         hx8 xr[3];
-        xr[0] = rb_ld(xl_base);
-        if (KS > 1) xr[1] = rb_ld(xl_base + 64);
+        xr[0] = fd_frag(xl_base);
+        if (KS > 1) xr[1] = fd_frag(xl_base + 64);
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-          if (s + 2 < KS) xr[(s + 2) % 3] = rb_ld(xl_base + 64 * (s + 2));
+          if (s + 2 < KS) xr[(s + 2) % 3] = fd_frag(xl_base + 64 * (s + 2));
           c = mma(Wh[b][s], xr[s % 3], c);
         }
       }
@@ -1260,7 +1250,7 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
   if constexpr (ETR) {
     // ---- stage E1: e = initial_embed(out row), 128 features = 8 tiles of 16: tiles wave and wave + 4 (first fragments requested above)
     f32x4 ea[2];
-    ch_rb_for<2>([&](auto U) {
+    fd_static_for<2>([&](auto U) {
       constexpr int u = decltype(U)::value;
       const int T = wave + 4 * u;
       if constexpr (u == 0) w_load(B1, K8C, a.we0, a.we0l, T + 4);
@@ -1269,11 +1259,11 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
       for (int s = 0; s < TR_KS; ++s) c = mma(Wh[u][s], X[s], c);
       {
         hx8 xr[3];
-        xr[0] = rb_ld(xl_base);
-        xr[1] = rb_ld(xl_base + 64);
+        xr[0] = fd_frag(xl_base);
+        xr[1] = fd_frag(xl_base + 64);
 #pragma unroll
         for (int s = 0; s < TR_KS; ++s) {
-          if (s + 2 < TR_KS) xr[(s + 2) % 3] = rb_ld(xl_base + 64 * (s + 2));
+          if (s + 2 < TR_KS) xr[(s + 2) % 3] = fd_frag(xl_base + 64 * (s + 2));
           c = mma(Wh[u][s], xr[s % 3], c);
         }
       }
@@ -1288,8 +1278,8 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
       constexpr int j = decltype(J)::value, b = j & 1, h = j >> 1;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        Wh[b][4 * h + s] = rb_ld((const char*)a.we1 + ((size_t)(T * 4 + s) * 64 + lane) * 16);
-        Wl[b][4 * h + s] = rb_ld((const char*)a.we1l + ((size_t)(T * 4 + s) * 64 + lane) * 16);
+        Wh[b][4 * h + s] = fd_frag((const char*)a.we1 + ((size_t)(T * 4 + s) * 64 + lane) * 16);
+        Wl[b][4 * h + s] = fd_frag((const char*)a.we1l + ((size_t)(T * 4 + s) * 64 + lane) * 16);
       }
     };
     e2_load(std::integral_constant<int, 2>{}, wave);       // (buffer halves 1: free since E1 used fragments 0..7 of both buffers — loaded
@@ -1311,7 +1301,7 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
     float bvs[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) bvs[u] = a.be1[16 * (wave + 4 * u) + lr];
-    ch_rb_for<16>([&](auto U) {
+    fd_static_for<16>([&](auto U) {
       constexpr int u = decltype(U)::value, j = (u + 2) & 3, b = j & 1, h = j >> 1;  // tile u sits in slot (u + 2) % 4
       const int T = wave + 4 * u;
       if constexpr (u + 3 < 16) e2_load(std::integral_constant<int, (u + 5) & 3>{}, T + 12);  // the slot tile u - 1 has just left
@@ -1319,7 +1309,7 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void mlp16_kernel(RowBlock
 #pragma unroll
       for (int s = 0; s < 4; ++s) c = mma(X[s], Wh[b][4 * h + s], c);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) c = mma(rb_ld(xl_base + 64 * s), Wh[b][4 * h + s], c);
+      for (int s = 0; s < 4; ++s) c = mma(fd_frag(xl_base + 64 * s), Wh[b][4 * h + s], c);
 #pragma unroll
       for (int s = 0; s < 4; ++s) c = mma(X[s], Wl[b][4 * h + s], c);
       const float bv = bvs[u];

@@ -1,5 +1,5 @@
-// Stand-alone timing + in-kernel phase profile of edge_transition2_kernel (build with -DET2_PROF for the profile).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -w [-DET2_PROF] tools/micro/et2_bench.hip -o et2_bench
+// Stand-alone timing + in-kernel phase profile of edge_transition3_kernel (build with -DFD_PROF for the profile).
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -w [-DFD_PROF] tools/micro/et3_bench.hip -o et3_bench
 #include "../../framedipt_amd/csrc/edge_transition3.hip"
 #include <cstdio>
 #include <vector>
