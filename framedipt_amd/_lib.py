@@ -78,6 +78,12 @@ SIGNATURES = {
     "fdipt_se3_reverse_step_traj": (_i, [_i, _i, _P, _P, _P, _P, _P, _P, _d, _d, _d, _i, _i, _i, _d, _d, _d, _d, _d, _P, _P,
                                          _P, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_se3_reverse_step_indexed": (_i, [C.POINTER(ReverseIndexed), _P]),
+    # device noise (include/fdipt.h): noise keys [B] uint64 and a step index in place of the z_rot / z_trans rows
+    "fdipt_noise_fill": (_i, [_i, _i, _P, _i, _i, _i, _P, _P]),
+    "fdipt_se3_reverse_step_traj_gen": (_i, [_i, _i, _P, _P, _P, _P, _P, _i, _d, _d, _d, _i, _i, _i, _d, _d, _d, _d, _d, _P, _P,
+                                             _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fdipt_se3_reverse_step_indexed_gen": (_i, [C.POINTER(ReverseIndexed), _P, _P]),
+    "fdipt_se3_forward_step_gen": (_i, [_i, _i, _P, _P, _P, _P, _i, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),
     "fdipt_backbone_atoms_indexed": (_i, [_i, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_se3_forward_step": (_i, [_i, _i, _P, _P, _P, _P, _P, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),
     "fdipt_se3_step_log_prob": (_i, [_i, _i, _P, _P, _P, _P, _P, _P, _P, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P]),

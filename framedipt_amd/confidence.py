@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import noise as noise_mod
 from .model.score_network import preprocess_aatype
 from .rigid import Rigid, quat_to_rot
 
@@ -31,11 +32,13 @@ class ConfidenceLoop:
     """Device-resident state of the forward walk for a batch of B structures of equal length."""
 
     def __init__(self, model, diffuser, rigids_0, sample_feats, diffuse_mask, num_t, min_t, self_condition=True, noise_tape=None,
-                 state=None):
+                 state=None, noise="host", noise_keys=None):
         self.model, self.diffuser = model, diffuser
         dev = self.dev = model.device
         t7 = rigids_0.to_tensor_7() if isinstance(rigids_0, Rigid) else torch.as_tensor(rigids_0)
         self.batched = t7.dim() == 3
+        # noise="device": the forward-noising kernel draws from the samples' keys (noise.py: the forward purposes)
+        keys = noise_mod.resolve(noise, noise_keys, noise_tape, int(np.prod(t7.shape[:-2])) if self.batched else 1)
         t7 = t7.reshape(-1, t7.shape[-2], 7).to(device=dev, dtype=torch.float32).contiguous()
         B, N = self.B, self.N = t7.shape[0], t7.shape[1]
         f32 = lambda x: x.to(device=dev, dtype=torch.float32).reshape(B, N, *x.shape[2:]).contiguous().clone()  # noqa: E731
@@ -58,10 +61,14 @@ class ConfidenceLoop:
             self.t_all = torch.as_tensor(np.repeat(t32[:, None], B, 1), device=dev)
             self.temb_all = torch.as_tensor(np.repeat(temb[:, None, :], B, 1), device=dev)
             self.sig_all = torch.as_tensor(np.repeat(sig[:, None], B, 1), device=dev)
-            if noise_tape is None:
-                noise_tape = draw_forward_noise_tape(n, B, N)
-            self.z_rot = torch.as_tensor(np.ascontiguousarray(noise_tape[0], dtype=np.float64), device=dev)
-            self.z_trans = torch.as_tensor(np.ascontiguousarray(noise_tape[1], dtype=np.float64), device=dev)
+            self.z_rot = self.z_trans = self.noise_keys = None
+            if keys is not None:
+                self.noise_keys = noise_mod.keys_tensor(keys, dev)
+            else:
+                if noise_tape is None:
+                    noise_tape = draw_forward_noise_tape(n, B, N)
+                self.z_rot = torch.as_tensor(np.ascontiguousarray(noise_tape[0], dtype=np.float64), device=dev)
+                self.z_trans = torch.as_tensor(np.ascontiguousarray(noise_tape[1], dtype=np.float64), device=dev)
             # the reference's state: float32 rotation matrices of Rigid.from_tensor_7(rigids_0) + float32 translations
             self.rot = [quat_to_rot(t7[..., :4]).contiguous(), torch.empty(B, N, 3, 3, device=dev)]
             self.trans = [t7[..., 4:].contiguous(), torch.empty(B, N, 3, device=dev)]
@@ -73,8 +80,11 @@ class ConfidenceLoop:
         st, d = self.st, self.diffuser
         cur, nxt = i & 1, (i + 1) & 1
         with torch.cuda.device(self.dev):
-            d.forward_device(self.rot[cur], self.trans[cur], self.mask, self.z_rot[i], self.z_trans[i], self.forward_steps[i], self.dt,
-                             rot_out=self.rot[nxt], trans_out=self.trans[nxt], rigids_out=self.rigids)
+            dev_noise = self.noise_keys is not None
+            d.forward_device(self.rot[cur], self.trans[cur], self.mask, None if dev_noise else self.z_rot[i],
+                             None if dev_noise else self.z_trans[i], self.forward_steps[i], self.dt,
+                             rot_out=self.rot[nxt], trans_out=self.trans[nxt], rigids_out=self.rigids, noise_keys=self.noise_keys,
+                             step=i if dev_noise else None)
             args = (self.rigids, self.res_mask, self.fixed, self.sc_ca, self.net_aatype, self.gt_psi, self.t_all[i], self.temb_all[i],
                     self.sig_all[i])
             if self.self_condition:  # self_conditioning(): sc_ca_t <- CA of the prediction, then the scoring forward
@@ -105,11 +115,13 @@ class ConfidenceLoop:
 
 
 def logp_confidence_score(model, diffuser, rigids_t, sample_feats, diffuse_mask, num_t, min_t, device=None, self_condition=True,
-                          noise_tape=None):
+                          noise_tape=None, noise="host", noise_keys=None):
     """Same arguments / return as the reference: ``(log_prob, log_probs)`` - a float and a list of ``num_t`` floats for one
     structure (``rigids_t`` shaped [N]); arrays [B] / [num_t, B] when ``rigids_t`` carries a batch dimension.  ``noise_tape=(z_rot,
-    z_trans)`` ([num_t-1,B,N,3] N(0,1)) replaces the draws from the global ``np.random`` stream."""
-    loop = ConfidenceLoop(model, diffuser, rigids_t, sample_feats, diffuse_mask, num_t, min_t, self_condition, noise_tape)
+    z_trans)`` ([num_t-1,B,N,3] N(0,1)) replaces the draws from the global ``np.random`` stream; ``noise="device"`` with ``noise_keys``
+    (as for ``inference_fn``) draws them inside the forward-noising kernel instead."""
+    loop = ConfidenceLoop(model, diffuser, rigids_t, sample_feats, diffuse_mask, num_t, min_t, self_condition, noise_tape,
+                          noise=noise, noise_keys=noise_keys)
     for i in range(len(loop.forward_steps)):
         loop.step(i)
     log_prob, log_probs = loop.finish()

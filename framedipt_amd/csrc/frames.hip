@@ -3,6 +3,7 @@
 // Reference lines are cited per function (paths relative to the reference repository root).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "philox.hpp"
 
 #pragma clang fp contract(off)  // keep the float32 evaluation order of the reference expressions
 
@@ -222,17 +223,33 @@ struct ReverseArgs {
   const double* t_table = nullptr;
 };
 
-__global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a) {
+// GEN (the *_gen entries, noise="device"): z_rot / z_trans are NULL and every value is drawn here from the sample's key (philox.hpp:
+// a function of key, purpose, step, residue index within the sample and component only).  Both passes need z_trans and both draw it:
+// N / rpb times the Philox work of one pass, a few dozen integer operations per residue, against a buffer or a launch of its own.
+// Without GEN the body is the tape kernel as it was.
+struct NoiseKeys { const uint64_t* keys; int step; };
+template <bool GEN, typename... G>  // G = NoiseKeys with GEN, nothing without: the tape kernel keeps its argument block
+__global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a, G... gs) {
+  static_assert(sizeof...(G) == (GEN ? 1 : 0), "noise keys ride along with GEN only");
   __shared__ double red[4][FD_THREADS / 64];
   __shared__ double com[4];
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int N = a.N;
+  uint64_t key = 0;
+  int step = 0;
+  if constexpr (GEN) {
+    const NoiseKeys g = (gs, ...);
+    key = g.keys[b];
+    step = a.cursor ? a.cursor[0] : g.step;
+  }
   if (a.cursor) {
     const long s = a.cursor[0], R = (long)a.B * N;
     a.rigids_t += s * R * 7;
     a.rigids_out += (s + 1) * R * 7;
-    a.z_rot += s * R * 3;
-    a.z_trans += s * R * 3;
+    if (!GEN) {
+      a.z_rot += s * R * 3;
+      a.z_trans += s * R * 3;
+    }
     a.t = a.t_table[s];
     if (a.atom37) a.atom37 += s * R * 111;
     if (a.trans_traj) a.trans_traj += s * R * 3;
@@ -249,11 +266,12 @@ __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a)
   for (int i = tid; i < N; i += FD_THREADS) {
     const long r = (long)b * N + i;
     const double m = a.diffuse_mask ? (double)a.diffuse_mask[r] : 1.0;
-    double x1[3];
+    double x1[3], zt[3] = {0.0, 0.0, 0.0};
+    if (GEN && a.diffuse_trans) fd_noise3(key, (uint32_t)i, (uint32_t)step, FD_NOISE_REV_TRANS, zt);
     for (int c = 0; c < 3; ++c) {
       const double x = (double)a.rigids_t[r * 7 + 4 + c] * a.cs;
       const double f = -0.5 * bt * x;
-      const double z = a.noise_scale * a.z_trans[r * 3 + c];
+      const double z = a.noise_scale * (GEN ? zt[c] : a.z_trans[r * 3 + c]);
       double pert = (f - g_tr * g_tr * (double)a.trans_score[r * 3 + c]) * a.dt + g_tr * sdt * z;
       pert *= m;
       x1[c] = x - pert;
@@ -278,14 +296,15 @@ __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a)
     const bool has_mask = a.diffuse_mask != nullptr;
     const double m = has_mask ? (double)a.diffuse_mask[r] : 1.0;
     // ---- translation
-    double tr_out[3];
+    double tr_out[3], zt[3] = {0.0, 0.0, 0.0}, zr[3] = {0.0, 0.0, 0.0};
+    if (GEN && a.diffuse_trans) fd_noise3(key, (uint32_t)i, (uint32_t)step, FD_NOISE_REV_TRANS, zt);
     for (int c = 0; c < 3; ++c) {
       const double xt = (double)a.rigids_t[r * 7 + 4 + c];
       double x1 = xt;
       if (a.diffuse_trans) {
         const double x = xt * a.cs;
         const double f = -0.5 * bt * x;
-        const double z = a.noise_scale * a.z_trans[r * 3 + c];
+        const double z = a.noise_scale * (GEN ? zt[c] : a.z_trans[r * 3 + c]);
         double pert = (f - g_tr * g_tr * (double)a.trans_score[r * 3 + c]) * a.dt + g_tr * sdt * z;
         pert *= m;
         x1 = x - pert;
@@ -300,8 +319,9 @@ __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a)
     double Rt[9], Ro[9];
     for (int c = 0; c < 9; ++c) Rt[c] = (double)R32[c];
     double pert[3];
+    if (GEN && a.diffuse_rot) fd_noise3(key, (uint32_t)i, (uint32_t)step, FD_NOISE_REV_ROT, zr);
     for (int c = 0; c < 3; ++c)
-      pert[c] = g_rot * g_rot * a.rot_score[r * 3 + c] * a.dt + g_rot * sdt * (a.noise_scale * a.z_rot[r * 3 + c]);
+      pert[c] = g_rot * g_rot * a.rot_score[r * 3 + c] * a.dt + g_rot * sdt * (a.noise_scale * (GEN ? zr[c] : a.z_rot[r * 3 + c]));
     if (!has_mask || m == 1.0 || m == 0.0) {
       // Binary masks (the only ones the samplers produce): the rotation vectors of the reference are only ever passed through
       // exp(log(.)), which is the matrix of the Markley unit quaternion — from_rotvec(as_rotvec(q)).as_matrix() and
@@ -373,6 +393,18 @@ __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a)
       }
     }
   }
+}
+
+// out [n_steps,B,N,3]: the draws of steps k_begin .. k_begin + n_steps - 1 for one purpose, through the step kernels' own device function
+__global__ void noise_fill_kernel(int B, int N, const uint64_t* __restrict__ keys, uint32_t purpose, int k_begin, long n,
+                                  double* __restrict__ out) {
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const int i = (int)(r % N), b = (int)((r / N) % B);
+  const long s = r / ((long)N * B);
+  double z[3];
+  fd_noise3(keys[b], (uint32_t)i, (uint32_t)(k_begin + s), purpose, z);
+  for (int c = 0; c < 3; ++c) out[r * 3 + c] = z[c];
 }
 
 // ------------------------------------------------------------------ IGSO(3) rotation score
@@ -1008,7 +1040,7 @@ int fdipt_se3_reverse_step_atoms(int B, int N, const float* rigids_t, const doub
   ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale, center,
                    diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
                    rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL(reverse_step_kernel, dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(reverse_step_kernel<false>, dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1028,7 +1060,7 @@ int fdipt_se3_reverse_step_traj(int B, int N, const float* rigids_t, const doubl
   ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale, center,
                    diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
                    rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, pred_rigids, traj_fixed_mask, trans_traj};
-  hipLaunchKernelGGL(reverse_step_kernel, dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(reverse_step_kernel<false>, dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1043,7 +1075,53 @@ int fdipt_se3_reverse_step_indexed(const FdiptReverseIndexed* x, fdipt_stream_t 
                    x->r3_max_b, x->coordinate_scaling, x->rigid_traj, nullptr, 64, x->psi, x->aatype,
                    (const BackboneTables*)x->bb_tables, x->prot_traj, x->pred_rigids, x->traj_fixed_mask, x->trans_traj,
                    x->step_cursor, x->t_table};
-  hipLaunchKernelGGL(reverse_step_kernel, dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(reverse_step_kernel<false>, dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+// noise="device": the same launches with the samples' noise keys in place of the tape rows (reverse_step_body<true>)
+int fdipt_se3_reverse_step_traj_gen(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score,
+                                    const float* diffuse_mask, const uint64_t* noise_keys, int step, double t, double dt,
+                                    double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma,
+                                    double so3_max_sigma, double r3_min_b, double r3_max_b, double coordinate_scaling,
+                                    float* rigids_out, float* out_rot, const float* psi, const int32_t* aatype,
+                                    const void* tables, float* atom37, const float* pred_rigids, const float* traj_fixed_mask,
+                                    float* trans_traj, fdipt_stream_t stream) {
+  if (B <= 0 || N <= 0) return FDIPT_OK;
+  if (!rigids_t || !rot_score || !trans_score || !noise_keys || step < 0 || !rigids_out || !(t >= 0 && t <= 1))
+    return FDIPT_EINVAL;
+  if (atom37 && (!psi || !tables || rigids_out == rigids_t)) return FDIPT_EINVAL;
+  if (trans_traj && (!pred_rigids || !traj_fixed_mask)) return FDIPT_EINVAL;
+  const int rpb = rigids_out == rigids_t ? N : 64;
+  ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, nullptr, nullptr, t, dt, noise_scale, center,
+                   diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
+                   rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, pred_rigids, traj_fixed_mask, trans_traj};
+  hipLaunchKernelGGL((reverse_step_kernel<true, NoiseKeys>), dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a, NoiseKeys{noise_keys, step});
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+int fdipt_se3_reverse_step_indexed_gen(const FdiptReverseIndexed* x, const uint64_t* noise_keys, fdipt_stream_t stream) {
+  if (!x) return FDIPT_EINVAL;
+  if (x->B <= 0 || x->N <= 0) return FDIPT_OK;
+  if (!x->rigid_traj || !x->rot_score || !x->trans_score || x->z_rot || x->z_trans || !noise_keys || !x->t_table || !x->step_cursor)
+    return FDIPT_EINVAL;
+  if (x->prot_traj && (!x->psi || !x->bb_tables)) return FDIPT_EINVAL;
+  if (x->trans_traj && (!x->pred_rigids || !x->traj_fixed_mask)) return FDIPT_EINVAL;
+  ReverseArgs a = {x->B, x->N, x->rigid_traj, x->rot_score, x->trans_score, x->diffuse_mask, nullptr, nullptr, 0.0, x->dt,
+                   x->noise_scale, x->center, x->diffuse_rot, x->diffuse_trans, x->so3_min_sigma, x->so3_max_sigma, x->r3_min_b,
+                   x->r3_max_b, x->coordinate_scaling, x->rigid_traj, nullptr, 64, x->psi, x->aatype,
+                   (const BackboneTables*)x->bb_tables, x->prot_traj, x->pred_rigids, x->traj_fixed_mask, x->trans_traj,
+                   x->step_cursor, x->t_table};
+  hipLaunchKernelGGL((reverse_step_kernel<true, NoiseKeys>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a, NoiseKeys{noise_keys, 0});
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+int fdipt_noise_fill(int B, int N, const uint64_t* noise_keys, int purpose, int k_begin, int n_steps, double* out, fdipt_stream_t stream) {
+  if (B <= 0 || N <= 0 || n_steps <= 0) return FDIPT_OK;
+  if (!noise_keys || !out || purpose < 0 || purpose >= (int)FD_NOISE_PURPOSES || k_begin < 0) return FDIPT_EINVAL;
+  const long n = (long)n_steps * B * N;
+  hipLaunchKernelGGL(noise_fill_kernel, dim3(cdiv(n, FD_THREADS)), dim3(FD_THREADS), 0, (hipStream_t)stream, B, N, noise_keys,
+                     (uint32_t)purpose, k_begin, n, out);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1140,12 +1218,21 @@ __device__ __forceinline__ void d_rot32_log(const float* R32, double* rv) {  // 
 }
 
 // SE3Diffuser.forward (se3_diffuser.py:50-95; r3_diffuser.py:122-161 with center=False; so3_diffuser.py:408-443)
-__global__ void se3_forward_step_kernel(long n, const float* __restrict__ rot_1, const float* __restrict__ trans_1,
-                                        const float* __restrict__ mask, const double* __restrict__ z_rot,
-                                        const double* __restrict__ z_trans, double t_1, double dt, double noise_scale, SdeConsts k,
-                                        float* __restrict__ rot_out, float* __restrict__ trans_out, float* __restrict__ t7_out) {
+// GEN (fdipt_se3_forward_step_gen): z_rot / z_trans are NULL and the values are drawn here (philox.hpp, the forward purposes)
+template <bool GEN>
+__device__ __forceinline__ void se3_forward_step_body(long n, const float* __restrict__ rot_1, const float* __restrict__ trans_1,
+                                                      const float* __restrict__ mask, const double* __restrict__ z_rot,
+                                                      const double* __restrict__ z_trans, double t_1, double dt, double noise_scale,
+                                                      const SdeConsts& k, float* __restrict__ rot_out, float* __restrict__ trans_out,
+                                                      float* __restrict__ t7_out, const uint64_t* __restrict__ keys, int N, int step) {
   const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
+  double zt[3] = {0.0, 0.0, 0.0}, zr[3] = {0.0, 0.0, 0.0};
+  if (GEN) {
+    const uint64_t key = keys[r / N];
+    fd_noise3(key, (uint32_t)(r % N), (uint32_t)step, FD_NOISE_FWD_TRANS, zt);
+    fd_noise3(key, (uint32_t)(r % N), (uint32_t)step, FD_NOISE_FWD_ROT, zr);
+  }
   const bool has_mask = mask != nullptr;
   const double m = has_mask ? (double)mask[r] : 1.0;
   const double sdt = sqrt(dt), bt = d_b_t(k, t_1), g_tr = sqrt(bt), g_rot = d_g_rot(k, t_1);
@@ -1153,7 +1240,7 @@ __global__ void se3_forward_step_kernel(long n, const float* __restrict__ rot_1,
   for (int c = 0; c < 3; ++c) {
     const double x0 = (double)trans_1[r * 3 + c];
     const double x = x0 * k.cs;
-    double pert = (-0.5 * bt * x) * dt + g_tr * sdt * (noise_scale * z_trans[r * 3 + c]);
+    double pert = (-0.5 * bt * x) * dt + g_tr * sdt * (noise_scale * (GEN ? zt[c] : z_trans[r * 3 + c]));
     if (has_mask) pert *= m;
     const double xt = (x + pert) / k.cs;
     tr[c] = (float)(has_mask ? m * xt + (1 - m) * x0 : xt);
@@ -1161,7 +1248,7 @@ __global__ void se3_forward_step_kernel(long n, const float* __restrict__ rot_1,
   double rv1[3], pert[3], rvt[3], Ro[9];
   d_rot32_log(rot_1 + r * 9, rv1);
   for (int c = 0; c < 3; ++c) {
-    pert[c] = g_rot * sdt * (noise_scale * z_rot[r * 3 + c]);
+    pert[c] = g_rot * sdt * (noise_scale * (GEN ? zr[c] : z_rot[r * 3 + c]));
     if (has_mask) pert[c] *= m;
   }
   d_compose_rotvec(rv1, pert, rvt);
@@ -1181,6 +1268,18 @@ __global__ void se3_forward_step_kernel(long n, const float* __restrict__ rot_1,
     fd_st(o, (float)q[3]); fd_st(o + 1, (float)q[0]); fd_st(o + 2, (float)q[1]); fd_st(o + 3, (float)q[2]);
     fd_st(o + 4, tr[0]); fd_st(o + 5, tr[1]); fd_st(o + 6, tr[2]);
   }
+}
+__global__ void se3_forward_step_kernel(long n, const float* __restrict__ rot_1, const float* __restrict__ trans_1,
+                                        const float* __restrict__ mask, const double* __restrict__ z_rot,
+                                        const double* __restrict__ z_trans, double t_1, double dt, double noise_scale, SdeConsts k,
+                                        float* __restrict__ rot_out, float* __restrict__ trans_out, float* __restrict__ t7_out) {
+  se3_forward_step_body<false>(n, rot_1, trans_1, mask, z_rot, z_trans, t_1, dt, noise_scale, k, rot_out, trans_out, t7_out, nullptr, 1, 0);
+}
+__global__ void se3_forward_step_gen_kernel(long n, int N, const float* __restrict__ rot_1, const float* __restrict__ trans_1,
+                                            const float* __restrict__ mask, const uint64_t* __restrict__ keys, int step, double t_1,
+                                            double dt, double noise_scale, SdeConsts k, float* __restrict__ rot_out,
+                                            float* __restrict__ trans_out, float* __restrict__ t7_out) {
+  se3_forward_step_body<true>(n, rot_1, trans_1, mask, nullptr, nullptr, t_1, dt, noise_scale, k, rot_out, trans_out, t7_out, keys, N, step);
 }
 
 // One block per sample: out[b] = {log p backward (trans, rot), log q forward (trans, rot)} summed over the diffused residues
@@ -1274,6 +1373,19 @@ int fdipt_se3_forward_step(int B, int N, const float* rot_t_1, const float* tran
   const SdeConsts k = {so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling};
   hipLaunchKernelGGL(se3_forward_step_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, n, rot_t_1, trans_t_1, diffuse_mask,
                      z_rot, z_trans, t_1, dt, noise_scale, k, rot_t, trans_t, rigids_t);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+int fdipt_se3_forward_step_gen(int B, int N, const float* rot_t_1, const float* trans_t_1, const float* diffuse_mask,
+                               const uint64_t* noise_keys, int step, double t_1, double dt, double noise_scale, double so3_min_sigma,
+                               double so3_max_sigma, double r3_min_b, double r3_max_b, double coordinate_scaling, float* rot_t,
+                               float* trans_t, float* rigids_t, fdipt_stream_t stream) {
+  if (B <= 0 || N <= 0) return FDIPT_OK;
+  if (!rot_t_1 || !trans_t_1 || !noise_keys || step < 0 || !rot_t || !trans_t || !(t_1 >= 0 && t_1 <= 1)) return FDIPT_EINVAL;
+  const long n = (long)B * N;
+  const SdeConsts k = {so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling};
+  hipLaunchKernelGGL(se3_forward_step_gen_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, n, N, rot_t_1, trans_t_1,
+                     diffuse_mask, noise_keys, step, t_1, dt, noise_scale, k, rot_t, trans_t, rigids_t);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import noise as noise_mod
 from ..rigid import Rigid, Rotation
 from . import r3_diffuser, so3_diffuser
 
@@ -125,8 +126,9 @@ class SE3Diffuser:
 
     # ------------------------------------------------------------------ reverse step
     def reverse_device(self, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, center=True,
-                       noise_scale=1.0, rigids_out=None, rot_out=None, atoms=None, traj=None):
-        """Device-resident reverse step on tensor_7 frames [B,N,7]; noise given (N(0,1), float64).
+                       noise_scale=1.0, rigids_out=None, rot_out=None, atoms=None, traj=None, noise_keys=None, step=None):
+        """Device-resident reverse step on tensor_7 frames [B,N,7]; noise given (N(0,1), float64) — or, with ``noise_keys`` ([B] int64
+        device tensor, ``noise.keys_tensor``) and the step index ``step`` in place of ``z_rot`` / ``z_trans``, drawn inside the kernel.
         ``atoms=(psi, aatype, bb_tables, atom37)``: also compute_backbone of x_{t-1} in the same launch.
         ``traj=(pred_rigids, fixed_mask * res_mask, trans_traj_row)``: also the step's trans_traj row (utils.py:390-400)."""
         lib = _lib.load()
@@ -137,17 +139,28 @@ class SE3Diffuser:
         so3, r3 = self._so3_diffuser, self._r3_diffuser
         psi, aatype, tables, atom37 = atoms if atoms is not None else (None, None, None, None)
         pred, tfix, ttraj = traj if traj is not None else (None, None, None)
-        for x in (rot_score, trans_score, diffuse_mask, z_rot, z_trans, rigids_out, rot_out, psi, aatype, tables, atom37, pred, tfix, ttraj):
+        if noise_keys is not None and (z_rot is not None or z_trans is not None or step is None):
+            raise ValueError("reverse: noise_keys take a step index and no z_rot / z_trans")
+        for x in (rot_score, trans_score, diffuse_mask, z_rot, z_trans, noise_keys, rigids_out, rot_out, psi, aatype, tables, atom37, pred, tfix, ttraj):
             if x is not None and x.device != rigids_t.device:
                 raise _lib.FdiptError(f"reverse: tensors on different devices ({rigids_t.device} and {x.device})")
         with torch.cuda.device(rigids_t.device):
             self._reverse_launch(lib, B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale,
-                                 center, rigids_out, rot_out, psi, aatype, tables, atom37, pred, tfix, ttraj)
+                                 center, rigids_out, rot_out, psi, aatype, tables, atom37, pred, tfix, ttraj, noise_keys, step)
         return rigids_out
 
     def _reverse_launch(self, lib, B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale, center,
-                        rigids_out, rot_out, psi, aatype, tables, atom37, pred, tfix, ttraj):
+                        rigids_out, rot_out, psi, aatype, tables, atom37, pred, tfix, ttraj, noise_keys=None, step=None):
         so3, r3 = self._so3_diffuser, self._r3_diffuser
+        if noise_keys is not None:
+            _lib.check(lib.fdipt_se3_reverse_step_traj_gen(
+                B, N, _lib.ptr(rigids_t), _lib.ptr(rot_score), _lib.ptr(trans_score), _lib.ptr(diffuse_mask),
+                _lib.ptr(noise_keys), int(step), float(t), float(dt), float(noise_scale), int(bool(center)),
+                int(bool(self._diffuse_rot)), int(bool(self._diffuse_trans)), so3.min_sigma, so3.max_sigma, r3.min_b, r3.max_b,
+                r3._r3_conf.coordinate_scaling, _lib.ptr(rigids_out), _lib.ptr(rot_out), _lib.ptr(psi), _lib.ptr(aatype),
+                _lib.ptr(tables), _lib.ptr(atom37), _lib.ptr(pred), _lib.ptr(tfix), _lib.ptr(ttraj), _lib.stream_ptr()),
+                "se3_reverse_step_gen")
+            return rigids_out
         _lib.check(lib.fdipt_se3_reverse_step_traj(
             B, N, _lib.ptr(rigids_t), _lib.ptr(rot_score), _lib.ptr(trans_score), _lib.ptr(diffuse_mask),
             _lib.ptr(z_rot), _lib.ptr(z_trans), float(t), float(dt), float(noise_scale), int(bool(center)),
@@ -157,9 +170,13 @@ class SE3Diffuser:
         return rigids_out
 
     def reverse(self, rigid_t: Rigid, rot_score, trans_score, t: float, dt: float, diffuse_mask=None,
-                chain_indices=None, center: bool = True, noise_scale: float = 1.0) -> Rigid:
+                chain_indices=None, center: bool = True, noise_scale: float = 1.0, noise_key=None, step=None) -> Rigid:
         """se3_diffuser.py:346-401.  Noise comes from the global ``np.random`` stream in the reference order
-        (SO(3) draw, then R^3 draw, each of ``score.shape``)."""
+        (SO(3) draw, then R^3 draw, each of ``score.shape``).  ``noise_key`` (an int: keys ``noise_key, noise_key + 1, ...`` over the
+        leading dimensions; or one key per sample) with the step index ``step``: the kernel draws the step's values itself
+        (``noise.py``), the global stream is not touched."""
+        if (noise_key is None) != (step is None):
+            raise ValueError("reverse: noise_key and step go together")
         dev = rigid_t.device
         t7 = rigid_t.to_tensor_7().float()
         lead = t7.shape[:-2]
@@ -169,8 +186,12 @@ class SE3Diffuser:
                              dtype=torch.float64)
         ts = torch.as_tensor(np.asarray(trans_score.detach().cpu() if torch.is_tensor(trans_score) else trans_score),
                              dtype=torch.float32)
-        z_rot = np.random.normal(size=tuple(rs.shape)) if self._diffuse_rot else np.zeros(tuple(rs.shape))
-        z_trans = np.random.normal(size=tuple(ts.shape)) if self._diffuse_trans else np.zeros(tuple(ts.shape))
+        keys = z_rot = z_trans = None
+        if noise_key is not None:
+            keys = noise_mod.keys_tensor(noise_mod.as_keys(noise_key, B), dev)
+        else:
+            z_rot = np.random.normal(size=tuple(rs.shape)) if self._diffuse_rot else np.zeros(tuple(rs.shape))
+            z_trans = np.random.normal(size=tuple(ts.shape)) if self._diffuse_trans else np.zeros(tuple(ts.shape))
         dm = None
         if diffuse_mask is not None:
             dm = torch.as_tensor(np.asarray(diffuse_mask.detach().cpu() if torch.is_tensor(diffuse_mask) else diffuse_mask),
@@ -179,8 +200,9 @@ class SE3Diffuser:
         out = self.reverse_device(
             t7.reshape(B, N, 7).contiguous(), rs.reshape(B, N, 3).to(dev).contiguous(),
             ts.reshape(B, N, 3).to(dev).contiguous(), dm,
-            torch.as_tensor(z_rot, device=dev).reshape(B, N, 3).contiguous(),
-            torch.as_tensor(z_trans, device=dev).reshape(B, N, 3).contiguous(), t, dt, center, noise_scale, rot_out=rot_out)
+            None if keys is not None else torch.as_tensor(z_rot, device=dev).reshape(B, N, 3).contiguous(),
+            None if keys is not None else torch.as_tensor(z_trans, device=dev).reshape(B, N, 3).contiguous(), t, dt, center, noise_scale,
+            rot_out=rot_out, noise_keys=keys, step=step)
         return Rigid(Rotation(rot_mats=rot_out.reshape(*lead, N, 3, 3)), out[..., 4:].reshape(*lead, N, 3))
 
     # ------------------------------------------------------------------ forward noising + log-probabilities (EigenFold confidence)
@@ -205,14 +227,23 @@ class SE3Diffuser:
         return torch.as_tensor(np.broadcast_to(m.astype(np.float32).reshape(-1, N), (B, N)).copy(), device=dev)
 
     def forward_device(self, rot_1, trans_1, diffuse_mask, z_rot, z_trans, t_1, dt, noise_scale=1.0, rot_out=None, trans_out=None,
-                       rigids_out=None):
-        """One-step forward noising on device state (rot [B,N,3,3], trans [B,N,3] float32; noise N(0,1) float64)."""
+                       rigids_out=None, noise_keys=None, step=None):
+        """One-step forward noising on device state (rot [B,N,3,3], trans [B,N,3] float32; noise N(0,1) float64 — or drawn inside the
+        kernel from ``noise_keys`` ([B] int64 device tensor) at step index ``step``, with ``z_rot = z_trans = None``)."""
+        if noise_keys is not None and (z_rot is not None or z_trans is not None or step is None):
+            raise ValueError("forward: noise_keys take a step index and no z_rot / z_trans")
         lib = _lib.load()
         _lib.require_cuda(rot_1, "forward")
         B, N = rot_1.shape[0], rot_1.shape[1]
         rot_out = torch.empty_like(rot_1) if rot_out is None else rot_out
         trans_out = torch.empty_like(trans_1) if trans_out is None else trans_out
         with torch.cuda.device(rot_1.device):
+            if noise_keys is not None:
+                _lib.check(lib.fdipt_se3_forward_step_gen(B, N, _lib.ptr(rot_1), _lib.ptr(trans_1), _lib.ptr(diffuse_mask),
+                                                          _lib.ptr(noise_keys), int(step), float(t_1), float(dt), float(noise_scale),
+                                                          *self._consts(), _lib.ptr(rot_out), _lib.ptr(trans_out), _lib.ptr(rigids_out),
+                                                          _lib.stream_ptr()), "se3_forward_step_gen")
+                return rot_out, trans_out
             _lib.check(lib.fdipt_se3_forward_step(B, N, _lib.ptr(rot_1), _lib.ptr(trans_1), _lib.ptr(diffuse_mask), _lib.ptr(z_rot),
                                                   _lib.ptr(z_trans), float(t_1), float(dt), float(noise_scale), *self._consts(),
                                                   _lib.ptr(rot_out), _lib.ptr(trans_out), _lib.ptr(rigids_out), _lib.stream_ptr()),

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, gpu_guard
+from . import noise as noise_mod
 from .model.score_network import preprocess_aatype
 
 
@@ -68,8 +69,10 @@ class ReverseLoop:
 
     def __init__(self, model, diffuser, data_init, num_t, min_t, center=True, aux_traj=False, self_condition=True,
                  noise_scale=1.0, embed_self_conditioning=True, inpainting=False, input_aatype=False, noise_tape=None, state=None,
-                 graph=True, verify=0):
+                 graph=True, verify=0, noise="host", noise_keys=None):
         self.model, self.diffuser = model, diffuser
+        # noise="device": no tape is drawn or uploaded, the reverse-step kernel draws from the samples' keys (noise.py)
+        keys = noise_mod.resolve(noise, noise_keys, noise_tape, int(data_init["rigids_t"].shape[0]))
         dev = self.dev = model.device
         gpu_guard.check(dev, what="inference_fn")  # a foreign compute process on this GPU: warn / refuse (FDIPT_SHARED_GPU)
         self.verify, self.verified = int(verify or 0), 0
@@ -119,10 +122,14 @@ class ReverseLoop:
                 rows = so3.score_table_rows(t32)
                 self.tab_all = torch.as_tensor(np.repeat(rows[:, None, :], B, 1), device=dev)
                 self.omega_edges = torch.as_tensor(so3.omega_edges, device=dev)
-            if noise_tape is None:
-                noise_tape = draw_noise_tape(diffuser, n_noisy, B, N)
-            self.z_rot = torch.as_tensor(np.ascontiguousarray(noise_tape[0], dtype=np.float64), device=dev)
-            self.z_trans = torch.as_tensor(np.ascontiguousarray(noise_tape[1], dtype=np.float64), device=dev)
+            self.z_rot = self.z_trans = self.noise_keys = None
+            if keys is not None:
+                self.noise_keys = noise_mod.keys_tensor(keys, dev)
+            else:
+                if noise_tape is None:
+                    noise_tape = draw_noise_tape(diffuser, n_noisy, B, N)
+                self.z_rot = torch.as_tensor(np.ascontiguousarray(noise_tape[0], dtype=np.float64), device=dev)
+                self.z_trans = torch.as_tensor(np.ascontiguousarray(noise_tape[1], dtype=np.float64), device=dev)
             self.sc_ca = f32(data_init["sc_ca_t"])
             self.rigid_traj = torch.empty(num_t + 1, B, N, 7, device=dev)  # row k = x_t of step k (row 0 = x_T), row k + 1 = its x_{t-1}
             self.rigid_traj[0] = rig0.to(device=dev, dtype=torch.float32)
@@ -131,7 +138,8 @@ class ReverseLoop:
             self.trans_traj = torch.empty(num_t, B, N, 3, device=dev) if aux_traj else None
             self.cursor = torch.zeros(2, dtype=torch.int32, device=dev)  # FdiptForwardArgs.step_cursor: {step index, ticket}
         # step graph: needs the noise rows of step k at row k (any tape drawn for this schedule), and at least a few steps to pay for capture
-        self.graph = bool(graph) and n_noisy >= 3 and self.z_rot.shape[0] >= n_noisy and self.z_trans.shape[0] >= n_noisy
+        # (device noise has no rows: the kernel draws step k's values from the cursor)
+        self.graph = bool(graph) and n_noisy >= 3 and (keys is not None or (self.z_rot.shape[0] >= n_noisy and self.z_trans.shape[0] >= n_noisy))
         self._cursor_host = 0      # host mirror of cursor[0] (every writer of the cursor is ordered on this loop's stream)
         self._g1 = self._gn = None  # captured one-step / GRAPH_CHUNK-step graphs
         self.capture_seconds = 0.0
@@ -188,9 +196,10 @@ class ReverseLoop:
         if t > self.min_t:
             # x_{t-1} lands in its trajectory slot, which is the next forward's input; its atom37 frame comes out of the
             # same launch
+            dev_noise = self.noise_keys is not None
             self.diffuser.reverse_device(self.rigid_traj[k], st.rot_score, st.trans_score, self.diffuse_mask,
-                                         self.z_rot[k], self.z_trans[k], t, self.dt, self.center,
-                                         self.noise_scale, rigids_out=nxt,
+                                         None if dev_noise else self.z_rot[k], None if dev_noise else self.z_trans[k], t, self.dt,
+                                         self.center, self.noise_scale, rigids_out=nxt, noise_keys=self.noise_keys, step=k,
                                          atoms=(st.psi, self.aatype, self.model.bb_tables, self.prot_traj[k]),
                                          traj=(st.rigids, self.fixed_mask, self.trans_traj[k]) if self.aux_traj else None)
         else:  # last step: take the x_0 prediction, utils.py:373-374
@@ -226,7 +235,11 @@ class ReverseLoop:
         a.center, a.diffuse_rot, a.diffuse_trans = int(bool(self.center)), int(bool(d._diffuse_rot)), int(bool(d._diffuse_trans))
         a.so3_min_sigma, a.so3_max_sigma, a.r3_min_b, a.r3_max_b = so3.min_sigma, so3.max_sigma, r3.min_b, r3.max_b
         a.coordinate_scaling = r3._r3_conf.coordinate_scaling
-        _lib.check(lib.fdipt_se3_reverse_step_indexed(C.byref(a), _lib.stream_ptr()), "se3_reverse_step_indexed")
+        if self.noise_keys is not None:  # (z_rot / z_trans are NULL: the draws of step cursor[0])
+            _lib.check(lib.fdipt_se3_reverse_step_indexed_gen(C.byref(a), _lib.ptr(self.noise_keys), _lib.stream_ptr()),
+                       "se3_reverse_step_indexed_gen")
+        else:
+            _lib.check(lib.fdipt_se3_reverse_step_indexed(C.byref(a), _lib.stream_ptr()), "se3_reverse_step_indexed")
 
     def capture_step_graph(self, n_steps=1):
         """A HIP graph of ``n_steps`` consecutive cursor-addressed steps (nothing runs; whatever ``self.st`` carries — event pairs,
@@ -259,7 +272,8 @@ class ReverseLoop:
         # every field of FdiptDims (widths select the fused or the generic kernels) and the options that change which kernels a step
         # launches (round-5 advisor: a second model with other widths at the same B, N was treated as warm)
         return (str(self.dev), bytes(self.model.dims), self.B, self.N, bool(self.aux_traj), bool(self.bb0_from_forward),
-                bool(self._inpainting), self.tab_all is not None, bool(self.embed_sc), bool(self.self_condition))
+                bool(self._inpainting), self.tab_all is not None, bool(self.embed_sc), bool(self.self_condition),
+                self.noise_keys is not None)
 
     def prepare(self):
         """Capture the step graphs now (otherwise: lazily at the first replay).  Nothing runs on the GPU."""
@@ -366,7 +380,8 @@ class StreamedLoops:
     MAX_LENGTH = 384  # ... and for N <= 384 only
     OPT_IN_ENV = "FDIPT_EXPERIMENTAL_STREAMS"  # more than one stream is an explicit opt-in: experimental=True or this variable set to 1
 
-    def __init__(self, model, diffuser, data_init, n_streams, num_t, min_t, noise_tape=None, reserve_cus=48, experimental=False, **kw):
+    def __init__(self, model, diffuser, data_init, n_streams, num_t, min_t, noise_tape=None, reserve_cus=48, experimental=False,
+                 noise="host", noise_keys=None, **kw):
         # Soak results (tools/soak_streams.sh, tools/streams_stat.py; trajectories against the single-stream run):
         #   * N = 128 / 300, two streams, any number of reserved CUs: 0 mismatching runs of ~400;
         #   * N = 300, three or four streams: 15 - 40 % of the runs differ in one sample from some step on;
@@ -379,6 +394,7 @@ class StreamedLoops:
         # is not exposed and is bit-reproducible at every size.
         import os
         B = data_init["rigids_t"].shape[0]
+        keys = noise_mod.resolve(noise, noise_keys, noise_tape, int(B))
         requested, n_streams = n_streams, max(1, min(n_streams, B))  # (the limits apply to what would actually run)
         if n_streams > self.MAX_STREAMS:
             raise ValueError(f"streams={requested}: sub-batch streams are verified bit-identical to the single-stream run for at most "
@@ -391,7 +407,7 @@ class StreamedLoops:
                              f"the verified range (DESIGN.md, concurrency): opt in with experimental_streams=True or {self.OPT_IN_ENV}=1")
         cuts = [round(i * B / n_streams) for i in range(n_streams + 1)]
         self.dev = model.device
-        if noise_tape is None:
+        if noise_tape is None and keys is None:
             n_noisy = int(np.sum(np.linspace(min_t, 1.0, num_t)[::-1] > min_t))
             noise_tape = draw_noise_tape(diffuser, n_noisy, B, data_init["rigids_t"].shape[1])
         self.loops, self.streams = [], _sub_batch_streams(self.dev, n_streams)
@@ -400,8 +416,10 @@ class StreamedLoops:
                 sub = {k: v[lo:hi] for k, v in data_init.items() if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == B}
                 st = model.new_batch_state(sub["seq_idx"])
                 st.reserve_cus = reserve_cus if n_streams > 1 else 0  # the persistent pair kernels leave CUs to the other streams
-                self.loops.append(ReverseLoop(model, diffuser, sub, num_t, min_t, noise_tape=tuple(z[:, lo:hi] for z in noise_tape),
-                                              state=st, graph=False, **kw))
+                # (each sub-batch takes its slice of the tape, or of the keys: a sample's draws do not depend on the batch it rides in)
+                sub_noise = dict(noise="device", noise_keys=keys[lo:hi]) if keys is not None else dict(
+                    noise_tape=tuple(z[:, lo:hi] for z in noise_tape))
+                self.loops.append(ReverseLoop(model, diffuser, sub, num_t, min_t, state=st, graph=False, **sub_noise, **kw))
         torch.cuda.synchronize(self.dev)  # set-up ran on the current stream
         self.st = self.loops[0].st
 
@@ -439,7 +457,8 @@ class StreamedLoops:
 
 def inference_fn(model, diffuser, data_init, num_t, min_t, center=True, aux_traj=False, self_condition=True,
                  noise_scale=1.0, embed_self_conditioning=True, inpainting=False, input_aatype=False, noise_tape=None,
-                 return_device=False, streams=1, experimental_streams=False, graph=True, verify=0, pad_to_four=True):
+                 return_device=False, streams=1, experimental_streams=False, graph=True, verify=0, pad_to_four=True,
+                 noise="host", noise_keys=None):
     """Same arguments / returned keys as the reference.  ``noise_tape=(z_rot, z_trans)`` ([num_t-1,B,N,3] float64
     N(0,1) draws) overrides the global ``np.random`` stream (sample-sharded runs).  ``data_init`` tensors carry a
     leading batch dimension B >= 1 (the reference always passes B = 1).  ``graph=True`` (default): the steps are replays of a HIP
@@ -447,7 +466,11 @@ def inference_fn(model, diffuser, data_init, num_t, min_t, center=True, aux_traj
     enqueued launch by launch.  ``verify=k``: the forward of every k-th step runs twice and must reproduce its bits (``FdiptError``
     otherwise; one host sync per verified step) — for GPUs shared with other compute processes (``gpu_guard``).  ``streams=n``: the batch runs as n sub-batches on n HIP streams (same results; the latency-bound
     node path of one sub-batch overlaps the pair kernels of the other) — experimental: needs ``experimental_streams=True`` (or
-    FDIPT_EXPERIMENTAL_STREAMS=1), at most two streams, N <= 384 (``StreamedLoops``; eager launches)."""
+    FDIPT_EXPERIMENTAL_STREAMS=1), at most two streams, N <= 384 (``StreamedLoops``; eager launches).  ``noise="device"`` (opt-in; the
+    default ``"host"`` is the reference's stream): no tape is drawn or uploaded, the reverse-step kernel draws its N(0,1) values from
+    ``noise_keys`` (B 64-bit keys as a sequence / int64 tensor; an int ``s`` means ``s, s + 1, ...``) — a draw depends on (key, step,
+    residue, component) only, ``noise.filled_tape`` gives the tape that reproduces the run bit for bit."""
+    keys = noise_mod.resolve(noise, noise_keys, noise_tape, int(data_init["rigids_t"].shape[0]))
     # Round 6: lengths that are no multiple of 4 run the half-precision mode's fall-back pair kernels (edge_transition3, the pass over z for
     # o_pair): 2.94 ms per step at N = 302 against 2.14 at 304 (eight samples).  ``pad_to_four`` (default) pads such a sample with masked rows
     # (res_mask = 0, identity frames, zero noise: sharding.pad_item, what run_sharded does to mixed-length batches) and cuts the returned
@@ -458,7 +481,9 @@ def inference_fn(model, diffuser, data_init, num_t, min_t, center=True, aux_traj
     padded = bool(pad_to_four) and n_pad != n_real and getattr(model, "precision", _lib.PREC_F32) != _lib.PREC_F32
     if padded:
         from . import sharding
-        if noise_tape is None:
+        # Device noise needs no change of values here: padding rows are not diffused (diffuse_mask = 0 multiplies their perturbation) and
+        # real rows keep their residue index, which — not the padded length — is what a draw depends on.
+        if noise_tape is None and keys is None:
             n_noisy = int(np.sum(np.linspace(min_t, 1.0, num_t)[::-1] > min_t))
             noise_tape = draw_noise_tape(diffuser, n_noisy, int(data_init["rigids_t"].shape[0]), n_real)
         data_init, noise_tape = sharding.pad_item(data_init, noise_tape, n_pad)
@@ -466,13 +491,15 @@ def inference_fn(model, diffuser, data_init, num_t, min_t, center=True, aux_traj
         # (the sub-loops are eager ReverseLoops: verify= is passed through to them, graph= does not apply)
         loop = StreamedLoops(model, diffuser, data_init, streams, num_t, min_t, noise_tape=noise_tape, center=center, aux_traj=aux_traj,
                              self_condition=self_condition, noise_scale=noise_scale, embed_self_conditioning=embed_self_conditioning,
-                             inpainting=inpainting, input_aatype=input_aatype, experimental=experimental_streams, verify=verify)
+                             inpainting=inpainting, input_aatype=input_aatype, experimental=experimental_streams, verify=verify,
+                             noise=noise, noise_keys=keys)
         loop.prime()
         for k in range(num_t):
             loop.step(k)
     else:
         loop = ReverseLoop(model, diffuser, data_init, num_t, min_t, center, aux_traj, self_condition, noise_scale,
-                           embed_self_conditioning, inpainting, input_aatype, noise_tape, graph=graph, verify=verify).run()
+                           embed_self_conditioning, inpainting, input_aatype, noise_tape, graph=graph, verify=verify, noise=noise,
+                           noise_keys=keys).run()
     res = loop.results(return_device)
     if padded:  # (every returned array carries the residues on the axis behind the batch)
         res = {k: v[:, :, :n_real] for k, v in res.items()}

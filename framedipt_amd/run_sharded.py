@@ -30,16 +30,18 @@ import numpy as np
 
 
 def run_rank(dataset, diffuser, run_batch, rank: int, world: int, out_dir: str, seed: int, num_t: int, min_t: float,
-             max_batch: int = 8, keep=("prot_traj",), final_only: bool = True, mixed: bool = True, write_item=None):
+             max_batch: int = 8, keep=("prot_traj",), final_only: bool = True, mixed: bool = True, write_item=None,
+             noise: str = "host"):
     """Run this rank's share of ``dataset``.  ``run_batch(feats, tape) -> dict of arrays with a batch axis at dim 1`` (the
-    keys of ``inference_fn``).  ``mixed``: samples of similar (not only equal) length share a batch, padded with res_mask = 0
+    keys of ``inference_fn``).  ``noise="device"``: ``run_batch`` receives the batch's noise keys [B] in the tape's place and no tape is
+    drawn before the first launch.  ``mixed``: samples of similar (not only equal) length share a batch, padded with res_mask = 0
     rows (sharding.batches_mixed / stack_items_padded; a batch never spans two kernel-selection classes, so a sample's bits do not
     depend on its batch mates); results are cut back to each sample's own length.
     Returns the list of records written by this rank."""
     from . import sharding
     os.makedirs(out_dir, exist_ok=True)
     mine = sharding.shard_indices(len(dataset), rank, world)
-    items = [sharding.seeded_item(dataset, i, seed, diffuser, num_t, min_t) for i in mine]
+    items = [sharding.seeded_item(dataset, i, seed, diffuser, num_t, min_t, noise=noise) for i in mine]
     lengths = [int(it[2]["rigids_t"].shape[1]) for it in items]
     records = []
     groups = sharding.batches_mixed(lengths, max_batch) if mixed else sharding.batches_by_length(lengths, max_batch)
@@ -198,6 +200,8 @@ def main():
     ap.add_argument("--precision", default="fp16", choices=["fp16", "fp16x", "fp32"])
     ap.add_argument("--kernel-flags", type=int, default=0, help="FdiptDims.kernel_flags (_lib.KF_*); 1024 = KF_STREAM_ATTN: fp16 chains up to 2048")
     ap.add_argument("--seed", type=int, default=123)
+    ap.add_argument("--noise", default="host", choices=["host", "device"], help="host: the reference's np.random stream, a tape per sample; "
+                    "device: the reverse-step kernel draws from the per-sample key seed + item (x_T still comes from np.random)")
     ap.add_argument("--weights-seed", type=int, default=7, help="synthetic weights (no checkpoint is available offline)")
     ap.add_argument("--full-trajectory", action="store_true", help="store every step of prot_traj instead of the final sample")
     # inpainting runs (experiments/inference.py:244-389)
@@ -259,9 +263,12 @@ def main():
                                                   "length_step": a.length_step, "samples_per_length": a.samples_per_length}), diff, dev)
 
     def run_batch(feats, tape):
+        # (--noise device: run_rank hands over the batch's noise keys where the tape would be)
+        how = dict(noise="device", noise_keys=tape) if a.noise == "device" else dict(noise_tape=tape)
+
         def go():
             return inference.inference_fn(net, diff, feats, num_t=a.num_t, min_t=a.min_t, aux_traj=True, noise_scale=a.noise_scale,
-                                          noise_tape=tape, return_device=True, inpainting=inp, verify=a.verify,
+                                          return_device=True, **how, inpainting=inp, verify=a.verify,
                                           input_aatype=inp and not a.no_input_aatype)  # (run_rank overlaps the D2H copy with the next batch)
         if not (one_gpu and world > 1):
             return go()
@@ -290,13 +297,13 @@ def main():
 
     t0 = time.perf_counter()
     recs = run_rank(ds, diff, run_batch, rank, world, a.out_dir, a.seed, a.num_t, a.min_t, a.max_batch, keep=keep,
-                    final_only=not a.full_trajectory, write_item=write_item)
+                    final_only=not a.full_trajectory, write_item=write_item, noise=a.noise)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     if rank == 0:
         el = time.perf_counter() - t0
-        allrecs = write_manifest(a.out_dir, world, len(ds), {"num_t": a.num_t, "precision": a.precision, "seed": a.seed, "wall_s": el})
+        allrecs = write_manifest(a.out_dir, world, len(ds), {"num_t": a.num_t, "precision": a.precision, "seed": a.seed, "noise": a.noise, "wall_s": el})
         print(f"{sum(r['n_res'] for r in allrecs) * a.num_t / el:.0f} residue*steps/s (incl. model set-up and file output)")
         print(f"{len(ds)} samples on {world} GPU(s) in {el:.1f} s -> {a.out_dir}/manifest.json", flush=True)
     if world > 1:

@@ -50,24 +50,34 @@ def max_over_ranks(value: float, device=None) -> float:
 # draw x_T (through the dataset item) and then the whole noise tape of the sample's trajectory in the reference's per-step
 # order: a sample's inputs - and with batch-position-independent kernels its whole trajectory - do not depend on the world
 # size, the rank that runs it or the batch it rides in.
-def seeded_item(dataset, item: int, seed: int, diffuser, num_t: int, min_t: float):
+def seeded_item(dataset, item: int, seed: int, diffuser, num_t: int, min_t: float, noise: str = "host"):
     """``dataset[item]`` and its noise tape drawn from ``np.random.seed(seed + item)``.
-    Returns (name_or_length, sample_i, feats [1,N,...], (z_rot, z_trans) [n_noisy,1,N,3] float64)."""
+    Returns (name_or_length, sample_i, feats [1,N,...], (z_rot, z_trans) [n_noisy,1,N,3] float64).
+    ``noise="device"``: x_T is drawn as above and the item's noise key — ``seed + item``, the per-item seed — takes the tape's place
+    (the step kernel draws from it: noise.py); nothing else is drawn on the host."""
     import numpy as np
 
     from .inference import draw_noise_tape
+    from .noise import MODES
+    if noise not in MODES:
+        raise ValueError(f"noise={noise!r}: expected one of {MODES}")
     np.random.seed(seed + item)
     name, sample_i, feats = dataset[item]
+    if noise == "device":
+        return name, sample_i, feats, int(seed + item)
     n = feats["rigids_t"].shape[1]
     n_noisy = int(np.sum(np.linspace(min_t, 1.0, num_t)[::-1] > min_t))
     return name, sample_i, feats, draw_noise_tape(diffuser, n_noisy, 1, n)
 
 
 def stack_items(items):
-    """Batch of equally sized samples from ``seeded_item`` tuples: (feats [B,N,...], (z_rot, z_trans) [n,B,N,3])."""
+    """Batch of equally sized samples from ``seeded_item`` tuples: (feats [B,N,...], (z_rot, z_trans) [n,B,N,3]); items that carry
+    noise keys (``seeded_item(noise="device")``) give the batch's keys [B] (int64) in the tape's place."""
     import numpy as np
     import torch
     feats = {k: torch.cat([it[2][k] for it in items], dim=0) for k in items[0][2]}
+    if not isinstance(items[0][3], tuple):
+        return feats, np.array([int(it[3]) for it in items], dtype=np.int64)
     tape = tuple(np.concatenate([it[3][j] for it in items], axis=1) for j in range(2))
     return feats, tape
 
@@ -84,7 +94,8 @@ _PAD_ONE = ("rigids_t",)  # padded with identity frames (quaternion 1, 0, 0, 0; 
 
 
 def pad_item(feats: dict, tape, n_pad: int):
-    """One ``[1, N, ...]`` feature dict and its noise tape ``[n, 1, N, 3]`` padded to ``n_pad`` residues."""
+    """One ``[1, N, ...]`` feature dict and its noise tape ``[n, 1, N, 3]`` padded to ``n_pad`` residues.  A noise key (or None) in
+    the tape's place passes through: a key's draws depend on the residue index, not on the padded length."""
     import numpy as np
     import torch
     n = int(feats["rigids_t"].shape[1])
@@ -103,7 +114,8 @@ def pad_item(feats: dict, tape, n_pad: int):
         elif k == "seq_idx":  # any value works (the rows are masked); the last real index keeps the relative-position table small
             pad += v[:, -1:]
         out[k] = torch.cat([v, pad], dim=1)
-    tape = tuple(np.concatenate([z, np.zeros(z.shape[:2] + (n_pad - n, 3), dtype=z.dtype)], axis=2) for z in tape)
+    if isinstance(tape, tuple):
+        tape = tuple(np.concatenate([z, np.zeros(z.shape[:2] + (n_pad - n, 3), dtype=z.dtype)], axis=2) for z in tape)
     return out, tape
 
 

@@ -284,6 +284,34 @@ typedef struct FdiptReverseIndexed {
   int32_t* step_cursor;          /* device int32[2] */
 } FdiptReverseIndexed;
 int fdipt_se3_reverse_step_indexed(const FdiptReverseIndexed* args, fdipt_stream_t stream);
+/* ---------------------------------------------------------------- device noise (opt-in) ---- */
+/* The *_gen entries take the samples' 64-bit noise keys (noise_keys [B] u64, device) in place of the z_rot / z_trans rows and draw the
+ * N(0,1) values inside the step kernel.  Generator (framedipt_amd/csrc/philox.hpp; restated in NumPy by tests/noise_ref.py):
+ *   Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85, ten rounds)
+ *   key     = (low word, high word) of the sample's noise key
+ *   counter = (residue index i within the sample, step index k, purpose, call index j)
+ *   purpose = 0 reverse-step rotation, 1 reverse-step translation, 2 forward-step rotation, 3 forward-step translation
+ *   j = 0 gives components x, y; j = 1 gives z (its second normal is discarded)
+ *   uniform = ((a >> 5) * 2^26 + (b >> 6) + 0.5) * 2^-53 in (0, 1): output words 0, 1 -> u0, words 2, 3 -> u1
+ *   normal  = Box-Muller in float64: r = sqrt(-2 log u0), z0 = r cos(2 pi u1), z1 = r sin(2 pi u1)
+ * CONTRACT: the value of a draw depends on (key, purpose, k, i, component) only.  Not on B, the sample's position in the batch, the
+ * padded N, the grid, the precision mode, graph or eager execution, or the number of ranks.  A step computes exactly what the tape
+ * entry computes on the rows fdipt_noise_fill writes for the same keys, bit for bit.
+ *
+ * out [n_steps,B,N,3] f64: the draws of steps k_begin .. k_begin + n_steps - 1 for one purpose, through the device function the step
+ * kernels call. */
+int fdipt_noise_fill(int B, int N, const uint64_t* noise_keys, int purpose, int k_begin, int n_steps, double* out,
+                     fdipt_stream_t stream);
+/* fdipt_se3_reverse_step_traj with the draws of step index `step` (purposes 0 and 1) in place of z_rot / z_trans. */
+int fdipt_se3_reverse_step_traj_gen(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score,
+                                    const float* diffuse_mask, const uint64_t* noise_keys, int step, double t, double dt,
+                                    double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma,
+                                    double so3_max_sigma, double r3_min_b, double r3_max_b, double coordinate_scaling,
+                                    float* rigids_out, float* out_rot, const float* psi, const int32_t* aatype,
+                                    const void* tables, float* atom37, const float* pred_rigids, const float* traj_fixed_mask,
+                                    float* trans_traj, fdipt_stream_t stream);
+/* fdipt_se3_reverse_step_indexed with args->z_rot == args->z_trans == NULL: the step index of the draws is step_cursor[0]. */
+int fdipt_se3_reverse_step_indexed_gen(const FdiptReverseIndexed* args, const uint64_t* noise_keys, fdipt_stream_t stream);
 /* compute_backbone of n = B*N frames (tensor_7) into row step_cursor[0] of atom37_rows [T,n,37,3] (rigid_0_traj rows built with the
  * caller's aatype view, experiments/utils.py:397-402). */
 int fdipt_backbone_atoms_indexed(int n, const float* t7, const float* psi, const int32_t* aatype, const void* tables,
@@ -298,6 +326,11 @@ int fdipt_se3_forward_step(int B, int N, const float* rot_t_1, const float* tran
                            const double* z_trans, double t_1, double dt, double noise_scale, double so3_min_sigma, double so3_max_sigma,
                            double r3_min_b, double r3_max_b, double coordinate_scaling, float* rot_t, float* trans_t, float* rigids_t,
                            fdipt_stream_t stream);
+/* ... with the draws of step index `step` (purposes 2 and 3 of the device noise above) in place of z_rot / z_trans. */
+int fdipt_se3_forward_step_gen(int B, int N, const float* rot_t_1, const float* trans_t_1, const float* diffuse_mask,
+                               const uint64_t* noise_keys, int step, double t_1, double dt, double noise_scale, double so3_min_sigma,
+                               double so3_max_sigma, double r3_min_b, double r3_max_b, double coordinate_scaling, float* rot_t,
+                               float* trans_t, float* rigids_t, fdipt_stream_t stream);
 /* SE3Diffuser.log_prob_backward / log_prob_forward (se3_diffuser.py:97-196; r3_diffuser.py:163-260; so3_diffuser.py:99-119,466-567;
  * r3_utils.py:10-42) of one step, summed over the diffused residues of each sample in float64:
  * out[b] = { log p_trans(x_{t-1}|x_t), log p_rot(x_{t-1}|x_t), log q_trans(x_t|x_{t-1}), log q_rot(x_t|x_{t-1}) }.
