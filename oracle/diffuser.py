@@ -254,13 +254,17 @@ class SE3Diffuser:
         return self._assemble(rot_ref, trans_ref)
 
     def reverse(self, quat_t, trans_t, rot_score, trans_score, t, dt, diffuse_mask=None, center=True,
-                noise_scale=1.0, z_rot=None, z_trans=None, orthogonalize=False):
-        """se3_diffuser.py:346-401. Returns (rot_mats f32, trans f32) of x_{t-1}."""
+                noise_scale=1.0, z_rot=None, z_trans=None, orthogonalize=False, diffuse_rot=True, diffuse_trans=True):
+        """se3_diffuser.py:346-401. Returns (rot_mats f32, trans f32) of x_{t-1}.
+
+        ``diffuse_rot`` / ``diffuse_trans`` False: the reference's ``_diffuse_rot`` / ``_diffuse_trans`` switches (:373-374, :383-384),
+        x_{t-1} keeps the rotation vectors / translations of x_t and the matching noise is not drawn.
+        """
         tr, rv = self._extract(quat_t, trans_t, orthogonalize)
-        rv1 = self._so3_diffuser.reverse(rv, rot_score, t, dt, noise_scale=noise_scale, z=z_rot,
-                                         orthogonalize=orthogonalize)
-        tr1 = self._r3_diffuser.reverse(tr, trans_score, t, dt, diffuse_mask=diffuse_mask, center=center,
-                                        noise_scale=noise_scale, z=z_trans)
+        rv1 = rv if not diffuse_rot else self._so3_diffuser.reverse(rv, rot_score, t, dt, noise_scale=noise_scale, z=z_rot,
+                                                                    orthogonalize=orthogonalize)
+        tr1 = tr if not diffuse_trans else self._r3_diffuser.reverse(tr, trans_score, t, dt, diffuse_mask=diffuse_mask,
+                                                                     center=center, noise_scale=noise_scale, z=z_trans)
         if diffuse_mask is not None:
             m = diffuse_mask[..., None]
             tr1 = m * tr1 + (1 - m) * tr

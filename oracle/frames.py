@@ -187,19 +187,12 @@ def scipy_from_rotvec_as_matrix(rv: np.ndarray) -> np.ndarray:
     return r
 
 
-def scipy_from_matrix_as_rotvec(m: np.ndarray, orthogonalize: bool = False) -> np.ndarray:
-    """Rotation.from_matrix(m).as_rotvec(): Markley quaternion, then log map (float64).
+def markley_quat(m: np.ndarray):
+    """Rotation.from_matrix of SciPy 1.7.3 up to the quaternion: (q [*,4] scalar-last, unit, sign as computed; branch [*]).
 
-    ``orthogonalize=True`` adds the SVD projection SciPy >= 1.8 applies first
-    (the oracle container has 1.15.3; the reference pins 1.7.3 which does not).
+    branch = argmax(m00, m11, m22, trace), the first maximum on ties (NumPy's argmax, as SciPy calls it); 3 = the trace branch.
     """
     m = np.asarray(m, dtype=np.float64)
-    if orthogonalize:
-        u, _, vt = np.linalg.svd(m)
-        det = np.linalg.det(u @ vt)
-        u = u.copy()
-        u[..., :, 2] *= det[..., None]
-        m = u @ vt
     shp = m.shape[:-2]
     m = m.reshape(-1, 3, 3)
     n = m.shape[0]
@@ -222,6 +215,25 @@ def scipy_from_matrix_as_rotvec(m: np.ndarray, orthogonalize: bool = False) -> n
     q[idx, 2] = m[idx, 1, 0] - m[idx, 0, 1]
     q[idx, 3] = 1 + dec[idx, 3]
     q /= np.linalg.norm(q, axis=1)[:, None]
+    return q.reshape(shp + (4,)), ch.reshape(shp)
+
+
+def scipy_from_matrix_as_rotvec(m: np.ndarray, orthogonalize: bool = False) -> np.ndarray:
+    """Rotation.from_matrix(m).as_rotvec(): Markley quaternion, then log map (float64).
+
+    ``orthogonalize=True`` adds the SVD projection SciPy >= 1.8 applies first
+    (the oracle container has 1.15.3; the reference pins 1.7.3 which does not).
+    """
+    m = np.asarray(m, dtype=np.float64)
+    if orthogonalize:
+        u, _, vt = np.linalg.svd(m)
+        det = np.linalg.det(u @ vt)
+        u = u.copy()
+        u[..., :, 2] *= det[..., None]
+        m = u @ vt
+    shp = m.shape[:-2]
+    q, _ = markley_quat(m)
+    q = q.reshape(-1, 4)
     q = np.where(q[:, 3:4] < 0, -q, q)
     ang = 2 * np.arctan2(np.linalg.norm(q[:, :3], axis=1), q[:, 3])
     a2 = ang * ang
@@ -235,3 +247,66 @@ def compose_rotvec(r1: np.ndarray, r2: np.ndarray, orthogonalize: bool = False) 
     """framedipt/data/transforms.py:33-46: log(exp(r1) exp(r2))."""
     c = np.einsum("...ij,...jk->...ik", scipy_from_rotvec_as_matrix(r1), scipy_from_rotvec_as_matrix(r2))
     return scipy_from_matrix_as_rotvec(c, orthogonalize)
+
+
+# ------------------------------------------------ geomstats-fork SO(3) maps
+def gs_omega(rot: np.ndarray, eps: float = 1e-4) -> np.ndarray:
+    """framedipt/diffusion/so3_utils.py:101-115: rotation angle from the trace shrunk by (1 - eps)."""
+    tr = np.trace(rot, axis1=-2, axis2=-1) * (1 - eps)
+    return np.arccos((tr - 1) / 2)
+
+
+def gs_exp(rv: np.ndarray) -> np.ndarray:
+    """so3_utils.py:89-98: matrix exponential of the skew matrix of rv, in closed form (Rodrigues).
+
+    sin(th)/th and (1 - cos th)/th^2 = sinc(th/2)^2 / 2 through np.sinc: no series switch, accurate at every angle.
+    """
+    rv = np.asarray(rv, dtype=np.float64)
+    th = np.linalg.norm(rv, axis=-1)
+    a = np.sinc(th / np.pi)
+    b = 0.5 * np.sinc(th / (2 * np.pi)) ** 2
+    k = np.zeros(rv.shape[:-1] + (3, 3))
+    k[..., 0, 1], k[..., 0, 2] = -rv[..., 2], rv[..., 1]
+    k[..., 1, 0], k[..., 1, 2] = rv[..., 2], -rv[..., 0]
+    k[..., 2, 0], k[..., 2, 1] = -rv[..., 1], rv[..., 0]
+    return np.eye(3) + a[..., None, None] * k + b[..., None, None] * (k @ k)
+
+
+def gs_regularize(p: np.ndarray) -> np.ndarray:
+    """so3_utils.py:185-222: rotation vector with its angle folded into [0, pi]."""
+    th = np.linalg.norm(p, axis=-1)
+    k = np.floor(th / 2.0 / np.pi)
+    ang = th - 2 * k * np.pi
+    zero = np.isclose(th, 0.0)
+    th_eps = np.where(zero, 1.0, th)
+    na = np.where(ang <= np.pi, ang, 2 * np.pi - ang)
+    ratio = np.where(zero, 1.0, na / th_eps)
+    ratio = np.where(ang > np.pi, -ratio, ratio)
+    return ratio[..., None] * p
+
+
+def gs_log_line_norms(rot: np.ndarray) -> np.ndarray:
+    """Row norms of max(0, .)-clamped (I + R) / 2, whose first maximum picks the signs of the near-pi branch of gs_log."""
+    vo = 0.5 * (np.eye(3) + rot)
+    vo = vo + (np.maximum(0.0, vo) - vo) * np.eye(3)
+    return np.linalg.norm(vo, axis=-1)
+
+
+def gs_log(rot: np.ndarray) -> np.ndarray:
+    """so3_utils.py:119-182 (rotation_vector_from_matrix, adapted from geomstats), rot [n,3,3] -> [n,3]."""
+    rot = np.asarray(rot, dtype=np.float64)
+    ang = gs_omega(rot)
+    d = rot - np.swapaxes(rot, -1, -2)
+    not_pi = np.stack([d[..., 2, 1], d[..., 0, 2], d[..., 1, 0]], axis=-1)  # vee of the skew part (so3_utils.py:25-40)
+    m0 = np.isclose(ang, 0.0).astype(np.float64)
+    mpi = np.isclose(ang, np.pi, atol=1e-2).astype(np.float64)
+    me = (1 - m0) * (1 - mpi)
+    num = 0.5 * m0 + ang * me
+    den = (1 - ang**2 / 6) * m0 + 2 * np.sin(ang) * me + mpi
+    not_pi = not_pi * num[..., None] / den[..., None]
+    vo = 0.5 * (np.eye(3) + rot)
+    vo = vo + (np.maximum(0.0, vo) - vo) * np.eye(3)
+    diag = np.sqrt(np.diagonal(vo, axis1=-2, axis2=-1))
+    line = np.argmax(np.linalg.norm(vo, axis=-1), axis=-1)
+    sel = np.take_along_axis(vo, line[..., None, None], axis=-2)[..., 0, :]
+    return gs_regularize(not_pi + mpi[..., None] * (ang[..., None] * np.sign(sel) * diag))

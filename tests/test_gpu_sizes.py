@@ -237,7 +237,7 @@ def test_round2_frame_ops_vs_reference_goldens():
     _lib.check(lib.fdipt_so3_log_geomstats(n, _lib.ptr(dev(G["gs_log_in"].astype(np.float64))), _lib.ptr(lg), _lib.stream_ptr()))
     # float32 reference flow; near pi the log of a float32-rounded matrix is conditioned like sqrt(eps): looser there
     ang = np.linalg.norm(G["gs_rotvec"], axis=-1)
-    near_pi = ang > np.pi - 3e-2
+    near_pi = ang > np.pi - 3e-2  # (30 or more near-pi items: test_gpu_frames_edges.py::test_geomstats_maps_edges_vs_oracle)
     np.testing.assert_allclose(lg.cpu().numpy()[~near_pi], G["gs_log"][~near_pi], atol=2e-5)
     np.testing.assert_allclose(lg.cpu().numpy()[near_pi], G["gs_log"][near_pi], atol=2e-3)
     r = R.Rigid.from_3_points(dev(G["p3_a"]), dev(G["p3_o"]), dev(G["p3_c"]))
