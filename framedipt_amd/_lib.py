@@ -42,7 +42,8 @@ class ForwardArgs(C.Structure):
                           "t_emb", "t_emb_eps", "so3_sigma", "bb_tables", "psi", "rot_score", "trans_score", "rigids",
                           "atom37", "atom14", "trace_node", "trace_edge", "trace_inner")] + [
         ("ev_start", C.POINTER(C.c_void_p)), ("ev_stop", C.POINTER(C.c_void_p)), ("ca_out", _P), ("reserve_cus", C.c_int32), ("clock_out", _P),
-                ("so3_score_table", _P), ("so3_omega_edges", _P), ("so3_num_omega", C.c_int32), ("step_cursor", _P)]
+                ("so3_score_table", _P), ("so3_omega_edges", _P), ("so3_num_omega", C.c_int32), ("step_cursor", _P),
+                ("frame_rows", _P), ("state_ring", C.c_int32)]  # kept-frame trajectories: row map [T] i32 (-1 = no frame), two-row state ring
 
 
 class ReverseIndexed(C.Structure):
@@ -51,7 +52,8 @@ class ReverseIndexed(C.Structure):
         "rigid_traj", "rot_score", "trans_score", "diffuse_mask", "z_rot", "z_trans", "t_table")] + [
         ("dt", C.c_double), ("noise_scale", C.c_double), ("center", C.c_int32), ("diffuse_rot", C.c_int32), ("diffuse_trans", C.c_int32)] + [
         (n, C.c_double) for n in ("so3_min_sigma", "so3_max_sigma", "r3_min_b", "r3_max_b", "coordinate_scaling")] + [
-        (n, _P) for n in ("psi", "aatype", "bb_tables", "prot_traj", "pred_rigids", "traj_fixed_mask", "trans_traj", "step_cursor")]
+        (n, _P) for n in ("psi", "aatype", "bb_tables", "prot_traj", "pred_rigids", "traj_fixed_mask", "trans_traj", "step_cursor")] + [
+        ("frame_rows", _P), ("state_ring", C.c_int32), ("kept_rigids", _P)]  # kept-frame trajectories (all zero: step-major addressing)
 
 
 _lib = None
@@ -85,6 +87,7 @@ SIGNATURES = {
     "fdipt_se3_reverse_step_indexed_gen": (_i, [C.POINTER(ReverseIndexed), _P, _P]),
     "fdipt_se3_forward_step_gen": (_i, [_i, _i, _P, _P, _P, _P, _i, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),
     "fdipt_backbone_atoms_indexed": (_i, [_i, _P, _P, _P, _P, _P, _P, _P]),
+    "fdipt_backbone_atoms_kept": (_i, [_i, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_se3_forward_step": (_i, [_i, _i, _P, _P, _P, _P, _P, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),
     "fdipt_se3_step_log_prob": (_i, [_i, _i, _P, _P, _P, _P, _P, _P, _P, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P]),
     "fdipt_se3_prior_log_prob": (_i, [_i, _i, _P, _P, _d, _P, _P]),

@@ -228,9 +228,18 @@ struct ReverseArgs {
 // N / rpb times the Philox work of one pass, a few dozen integer operations per residue, against a buffer or a launch of its own.
 // Without GEN the body is the tape kernel as it was.
 struct NoiseKeys { const uint64_t* keys; int step; };
-template <bool GEN, typename... G>  // G = NoiseKeys with GEN, nothing without: the tape kernel keeps its argument block
+// KEEP (FdiptReverseIndexed.frame_rows / state_ring, the *_kept kernels): the rows of prot_traj / trans_traj / kept_rigids come from the
+// row map at the cursor (-1: this step keeps no frame — no backbone construction, no trans_traj row; uniform over the launch), and with
+// `ring` the state is a two-row ping-pong: x_t = row k & 1, x_{t-1} = row (k + 1) & 1.  Without KEEP the instantiations are the kernels as
+// they were (same instructions: tools/isa_cmp_kernels.py).
+struct KeptRows { const int32_t* frame_rows; float* kept_rigids; int ring; };
+template <typename T, typename... G>  // the argument of type T among the ride-along arguments
+__device__ __forceinline__ T fd_arg_of(T first, G...) { return first; }
+template <typename T, typename U, typename... G, typename = std::enable_if_t<!std::is_same_v<T, U>>>
+__device__ __forceinline__ T fd_arg_of(U, G... rest) { return fd_arg_of<T>(rest...); }
+template <bool GEN, bool KEEP, typename... G>  // G = KeptRows with KEEP, then NoiseKeys with GEN: the tape kernel keeps its argument block
 __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a, G... gs) {
-  static_assert(sizeof...(G) == (GEN ? 1 : 0), "noise keys ride along with GEN only");
+  static_assert(sizeof...(G) == (GEN ? 1 : 0) + (KEEP ? 1 : 0), "noise keys ride along with GEN only, the row map with KEEP only");
   __shared__ double red[4][FD_THREADS / 64];
   __shared__ double com[4];
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -238,11 +247,31 @@ __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a,
   uint64_t key = 0;
   int step = 0;
   if constexpr (GEN) {
-    const NoiseKeys g = (gs, ...);
+    const NoiseKeys g = fd_arg_of<NoiseKeys>(gs...);
     key = g.keys[b];
     step = a.cursor ? a.cursor[0] : g.step;
   }
-  if (a.cursor) {
+  [[maybe_unused]] float* kept_out = nullptr;  // (KEEP) this step's row of kept_rigids
+  if constexpr (KEEP) {
+    const KeptRows kr = fd_arg_of<KeptRows>(gs...);
+    const long s = a.cursor[0], R = (long)a.B * N;  // (the kept entries always carry a cursor)
+    const long row = kr.frame_rows ? (long)kr.frame_rows[s] : s;
+    a.rigids_t += (kr.ring ? (s & 1) : s) * R * 7;
+    a.rigids_out += (kr.ring ? ((s + 1) & 1) : s + 1) * R * 7;
+    if (!GEN) {
+      a.z_rot += s * R * 3;
+      a.z_trans += s * R * 3;
+    }
+    a.t = a.t_table[s];
+    if (row < 0) {
+      a.atom37 = nullptr;
+      a.trans_traj = nullptr;
+    } else {
+      if (a.atom37) a.atom37 += row * R * 111;
+      if (a.trans_traj) a.trans_traj += row * R * 3;
+      if (kr.kept_rigids) kept_out = kr.kept_rigids + row * R * 7;
+    }
+  } else if (a.cursor) {
     const long s = a.cursor[0], R = (long)a.B * N;
     a.rigids_t += s * R * 7;
     a.rigids_out += (s + 1) * R * 7;
@@ -372,6 +401,10 @@ __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a,
     float* o = a.rigids_out + r * 7;
     fd_st(o, (float)q[3]); fd_st(o + 1, (float)q[0]); fd_st(o + 2, (float)q[1]); fd_st(o + 3, (float)q[2]);
     fd_st(o + 4, (float)tr_out[0]); fd_st(o + 5, (float)tr_out[1]); fd_st(o + 6, (float)tr_out[2]);
+    if constexpr (KEEP) {
+      if (kept_out)
+        for (int c = 0; c < 7; ++c) fd_st(kept_out + r * 7 + c, o[c]);
+    }
     if (a.atom37) {
       const float tf[3] = {o[4], o[5], o[6]};
       d_backbone_residue(r, Rf, tf, a.psi, a.aatype, a.tables, a.atom37, nullptr);
@@ -444,15 +477,29 @@ struct ScoreTail {
   // step-major arrays, read / written at row *cursor
   const int32_t* cursor = nullptr;
 };
+// KEPT (FdiptForwardArgs.frame_rows / state_ring, rot_score_kept_kernel): x_t is row k & 1 of the two-row state with `ring`, and the atom37
+// row is frame_rows[k] — or none (-1: the backbone atoms are not built at all on this step).  Without KEPT the kernel is as it was.
+template <bool KEPT, typename... K>  // K = FdKept with KEPT, nothing without
 __global__ __launch_bounds__(FD_THREADS) void rot_score_kernel(int B, int N, const float* __restrict__ quats_t_, int ld_t,
                                                                const float* __restrict__ quats_0, int ld_0,
                                                                const double* __restrict__ sigma_,
                                                                const float* __restrict__ res_mask,
-                                                               double* __restrict__ score, ScoreTail x) {
+                                                               double* __restrict__ score, ScoreTail x, K... ks) {
+  static_assert(sizeof...(K) == (KEPT ? 1 : 0), "the row map rides along with KEPT only");
   __shared__ double wtab[2][RS_L];
   const float* __restrict__ quats_t = quats_t_;
   const double* __restrict__ sigma = sigma_;
-  if (x.cursor) {
+  if constexpr (KEPT) {
+    const FdKept kp = (ks, ...);
+    const long s = x.cursor[0];  // (the kept launch always carries a cursor)
+    const long row = kp.frame_rows ? (long)kp.frame_rows[s] : s;
+    quats_t += (kp.ring ? (s & 1) : s) * B * N * ld_t;
+    sigma += s * B;
+    x.t += s * B;
+    if (x.score_table) x.score_table += s * B * x.n_omega;
+    if (row < 0) x.atom37 = x.atom14 = nullptr;
+    else if (x.atom37) x.atom37 += row * B * N * 111;
+  } else if (x.cursor) {
     const long s = x.cursor[0];
     quats_t += s * B * N * ld_t;
     sigma += s * B;
@@ -624,6 +671,20 @@ __global__ void backbone_kernel(int n, const float* __restrict__ t7, const float
   }
   d_backbone_residue(r, Rb, tbv, psi, aatype, tb, atom37, atom14);
 }
+// ... of a kept-frame loop (fdipt_backbone_atoms_kept): tensor_7 frames into row frame_rows[*cursor] of atom37_rows; a step whose row is -1
+// builds nothing (uniform over the launch)
+__global__ void backbone_kept_kernel(int n, const float* __restrict__ t7, const float* __restrict__ psi, const int32_t* __restrict__ aatype,
+                                     const BackboneTables* __restrict__ tb, float* __restrict__ atom37_rows,
+                                     const int32_t* __restrict__ cursor, const int32_t* __restrict__ frame_rows) {
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const long row = frame_rows[cursor[0]];
+  if (row < 0) return;
+  float Rb[9], tbv[3];
+  d_quat_to_rot(t7 + r * 7, Rb);
+  for (int c = 0; c < 3; ++c) tbv[c] = t7[r * 7 + 4 + c];
+  d_backbone_residue(r, Rb, tbv, psi, aatype, tb, atom37_rows + row * n * 111, nullptr);
+}
 
 // ------------------------------------------------------------------ small per-residue kernels of the trunk
 // Rigid.compose_q_update_vec with update_mask (rigid_utils.py:587-616,1039-1063); quat [n,4] / trans [n,3] in place.
@@ -652,19 +713,26 @@ int fd_compose_q_update(long n, float* quat, float* trans, const float* upd, int
 }
 
 // IpaScore.forward prologue (ipa_pytorch.py:516-524): split tensor_7, scale translations; diffuse_mask = (1-fixed)*res.
+template <bool RING>  // RING (FdiptForwardArgs.state_ring): x_t is row *cursor & 1 of a two-row state instead of row *cursor
 __global__ void split_rigids_kernel(long n, const float* __restrict__ t7_, float cs, const float* __restrict__ res_mask,
                                     const float* __restrict__ fixed_mask, float* __restrict__ quat,
                                     float* __restrict__ trans, float* __restrict__ diffuse_mask, const int32_t* __restrict__ cursor) {
   const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
-  const float* __restrict__ t7 = cursor ? t7_ + (long)cursor[0] * n * 7 : t7_;  // (step cursor: row *cursor of a step-major array)
+  const float* __restrict__ t7 = cursor ? t7_ + (long)(RING ? cursor[0] & 1 : cursor[0]) * n * 7 : t7_;  // (step cursor: row *cursor of a step-major array)
   for (int c = 0; c < 4; ++c) quat[r * 4 + c] = t7[r * 7 + c];
   for (int c = 0; c < 3; ++c) fd_st(trans + r * 3 + c, t7[r * 7 + 4 + c] * cs);
   diffuse_mask[r] = (1.f - fixed_mask[r]) * res_mask[r];
 }
 int fd_split_rigids(long n, const float* t7, float cs, const float* res_mask, const float* fixed_mask, float* quat,
-                    float* trans, float* dmask, const int32_t* cursor, hipStream_t st) {
-  hipLaunchKernelGGL(split_rigids_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, n, t7, cs, res_mask, fixed_mask, quat, trans,
+                    float* trans, float* dmask, const int32_t* cursor, hipStream_t st, FdKept kept) {
+  if (cursor && kept.ring) {
+    hipLaunchKernelGGL(split_rigids_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, st, n, t7, cs, res_mask, fixed_mask, quat, trans,
+                       dmask, cursor);
+    FD_CHECK_LAUNCH();
+    return FDIPT_OK;
+  }
+  hipLaunchKernelGGL(split_rigids_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, st, n, t7, cs, res_mask, fixed_mask, quat, trans,
                      dmask, cursor);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
@@ -701,6 +769,7 @@ struct FeatsExtra {  // optional work folded into the feature kernel's launch (n
   const float *w1i, *w1j, *b1; int cz; float *pi, *pj;              // per-residue halves of the first edge-embedder layer
   const int32_t* cursor;  // optional step cursor: t_emb and t7 are bases of step-major arrays, read at row *cursor
 };
+template <bool RING>  // RING (FdiptForwardArgs.state_ring): x_t is row *cursor & 1 of a two-row state instead of row *cursor
 __global__ void build_feats_kernel(int B, int N, int use_aatype, int E, const int32_t* __restrict__ aatype,
                                    const float* __restrict__ t_emb_, const float* __restrict__ t_emb_eps,
                                    const float* __restrict__ fixed_mask, const float* __restrict__ idx_emb,
@@ -711,7 +780,7 @@ __global__ void build_feats_kernel(int B, int N, int use_aatype, int E, const in
   if (x.cursor) {
     const long s = x.cursor[0];
     t_emb += s * B * E;
-    if (x.t7) x.t7 += s * B * N * 7;
+    if (x.t7) x.t7 += (RING ? (s & 1) : s) * B * N * 7;
   }
   const long r = blockIdx.x;
   const int b = (int)(r / N);
@@ -761,11 +830,18 @@ __global__ void build_feats_kernel(int B, int N, int use_aatype, int E, const in
 int fd_build_feats(int B, int N, int use_aatype, int E, const int32_t* aatype, const float* t_emb, const float* t_emb_eps,
                    const float* fixed_mask, const float* idx_emb, float* node_feat, int ld_node, float* pte, int ld_pte,
                    const float* t7, const float* res_mask, float cs, float* quat, float* trans, float* dmask, const float* w1i,
-                   const float* w1j, const float* b1, int cz, float* pi, float* pj, const int32_t* cursor, hipStream_t st) {
+                   const float* w1j, const float* b1, int cz, float* pi, float* pj, const int32_t* cursor, hipStream_t st,
+                   FdKept kept) {
   if (use_aatype && (!aatype || !t_emb_eps)) return FDIPT_EINVAL;
   if (pi && (ld_pte > 128 || (ld_pte & 3))) return FDIPT_EINVAL;
   FeatsExtra x = {t7, res_mask, cs, quat, trans, dmask, w1i, w1j, b1, cz, pi, pj, cursor};
-  hipLaunchKernelGGL(build_feats_kernel, dim3(B * N), dim3(128), 0, st, B, N, use_aatype, E, aatype, t_emb, t_emb_eps,
+  if (cursor && kept.ring) {
+    hipLaunchKernelGGL(build_feats_kernel<true>, dim3(B * N), dim3(128), 0, st, B, N, use_aatype, E, aatype, t_emb, t_emb_eps,
+                       fixed_mask, idx_emb, node_feat, ld_node, pte, ld_pte, x);
+    FD_CHECK_LAUNCH();
+    return FDIPT_OK;
+  }
+  hipLaunchKernelGGL(build_feats_kernel<false>, dim3(B * N), dim3(128), 0, st, B, N, use_aatype, E, aatype, t_emb, t_emb_eps,
                      fixed_mask, idx_emb, node_feat, ld_node, pte, ld_pte, x);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
@@ -774,7 +850,7 @@ int fd_build_feats(int B, int N, int use_aatype, int E, const int32_t* aatype, c
 int fd_rot_score(int B, int N, const float* qt, int ld_t, const float* q0, int ld_0, const double* sigma,
                  const float* res_mask, double* score, hipStream_t st) {
   ScoreTail x = {};
-  hipLaunchKernelGGL(rot_score_kernel, dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, st, B, N, qt, ld_t, q0,
+  hipLaunchKernelGGL(rot_score_kernel<false>, dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, st, B, N, qt, ld_t, q0,
                      ld_0, sigma, res_mask, score, x);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
@@ -785,14 +861,20 @@ int fd_score_tail(int B, int N, const float* rigids_t, const float* quat, const 
                   const float* t, float min_b, float max_b, float* rigids, float* psi, double* rot_score, float* trans_score,
                   float* ca_out, const float* hid, int ld_hid, int c_hid, const float* torf_w, const float* torf_b,
                   const double* score_table, const double* omega_edges, int n_omega, const int32_t* aatype, const void* bb_tables,
-                  float* atom37, float* atom14, const int32_t* cursor, hipStream_t st) {
+                  float* atom37, float* atom14, const int32_t* cursor, hipStream_t st, FdKept kept) {
   if (hid && ((c_hid & 3) || (ld_hid & 3))) return FDIPT_EINVAL;
   if (score_table && (!omega_edges || n_omega < 2)) return FDIPT_EINVAL;
   if ((atom37 || atom14) && !bb_tables) return FDIPT_EINVAL;
   ScoreTail x = {trans, cs, psi_un, ld_psi, gt_psi, fixed_mask, t, min_b, max_b, rigids, psi, trans_score, ca_out,
                  hid, torf_w, torf_b, ld_hid, c_hid, score_table, omega_edges, n_omega, aatype, (const BackboneTables*)bb_tables, atom37, atom14,
                  cursor};
-  hipLaunchKernelGGL(rot_score_kernel, dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, st, B, N, rigids_t, 7,
+  if (cursor && kept.on()) {
+    hipLaunchKernelGGL((rot_score_kernel<true, FdKept>), dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, st, B, N, rigids_t, 7,
+                       quat, 4, sigma, res_mask, rot_score, x, kept);
+    FD_CHECK_LAUNCH();
+    return FDIPT_OK;
+  }
+  hipLaunchKernelGGL(rot_score_kernel<false>, dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, st, B, N, rigids_t, 7,
                      quat, 4, sigma, res_mask, rot_score, x);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
@@ -805,7 +887,15 @@ int fd_trans_score(int B, int N, const float* tt, int ld_t, const float* t0, int
   return FDIPT_OK;
 }
 int fd_backbone(int n, const float* t7, const float* rot, const float* trans, int ld_trans, const float* psi,
-                const int32_t* aatype, const void* tables, float* atom37, float* atom14, hipStream_t st, const int32_t* cursor) {
+                const int32_t* aatype, const void* tables, float* atom37, float* atom14, hipStream_t st, const int32_t* cursor,
+                const int32_t* frame_rows) {
+  if (cursor && frame_rows) {  // kept-frame loop: tensor_7 frames into row frame_rows[*cursor] of atom37, nothing on a step that keeps none
+    if (!t7 || !atom37 || atom14) return FDIPT_EINVAL;
+    hipLaunchKernelGGL(backbone_kept_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, n, t7, psi, aatype, (const BackboneTables*)tables, atom37,
+                       cursor, frame_rows);
+    FD_CHECK_LAUNCH();
+    return FDIPT_OK;
+  }
   hipLaunchKernelGGL(backbone_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, n, t7, rot, trans, ld_trans, psi, aatype,
                      (const BackboneTables*)tables, atom37, atom14, cursor);
   FD_CHECK_LAUNCH();
@@ -1040,7 +1130,7 @@ int fdipt_se3_reverse_step_atoms(int B, int N, const float* rigids_t, const doub
   ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale, center,
                    diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
                    rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL(reverse_step_kernel<false>, dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((reverse_step_kernel<false, false>), dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1060,7 +1150,7 @@ int fdipt_se3_reverse_step_traj(int B, int N, const float* rigids_t, const doubl
   ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale, center,
                    diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
                    rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, pred_rigids, traj_fixed_mask, trans_traj};
-  hipLaunchKernelGGL(reverse_step_kernel<false>, dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((reverse_step_kernel<false, false>), dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1070,12 +1160,19 @@ int fdipt_se3_reverse_step_indexed(const FdiptReverseIndexed* x, fdipt_stream_t 
   if (!x->rigid_traj || !x->rot_score || !x->trans_score || !x->z_rot || !x->z_trans || !x->t_table || !x->step_cursor) return FDIPT_EINVAL;
   if (x->prot_traj && (!x->psi || !x->bb_tables)) return FDIPT_EINVAL;
   if (x->trans_traj && (!x->pred_rigids || !x->traj_fixed_mask)) return FDIPT_EINVAL;
+  if ((x->state_ring & ~1) || (x->kept_rigids && !x->frame_rows)) return FDIPT_EINVAL;
   ReverseArgs a = {x->B, x->N, x->rigid_traj, x->rot_score, x->trans_score, x->diffuse_mask, x->z_rot, x->z_trans, 0.0, x->dt,
                    x->noise_scale, x->center, x->diffuse_rot, x->diffuse_trans, x->so3_min_sigma, x->so3_max_sigma, x->r3_min_b,
                    x->r3_max_b, x->coordinate_scaling, x->rigid_traj, nullptr, 64, x->psi, x->aatype,
                    (const BackboneTables*)x->bb_tables, x->prot_traj, x->pred_rigids, x->traj_fixed_mask, x->trans_traj,
                    x->step_cursor, x->t_table};
-  hipLaunchKernelGGL(reverse_step_kernel<false>, dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
+  if (x->frame_rows || x->state_ring) {  // kept frames / two-row state: the rows come from the map at the cursor
+    hipLaunchKernelGGL((reverse_step_kernel<false, true, KeptRows>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a,
+                       KeptRows{x->frame_rows, x->kept_rigids, x->state_ring});
+    FD_CHECK_LAUNCH();
+    return FDIPT_OK;
+  }
+  hipLaunchKernelGGL((reverse_step_kernel<false, false>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1096,7 +1193,7 @@ int fdipt_se3_reverse_step_traj_gen(int B, int N, const float* rigids_t, const d
   ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, nullptr, nullptr, t, dt, noise_scale, center,
                    diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
                    rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, pred_rigids, traj_fixed_mask, trans_traj};
-  hipLaunchKernelGGL((reverse_step_kernel<true, NoiseKeys>), dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a, NoiseKeys{noise_keys, step});
+  hipLaunchKernelGGL((reverse_step_kernel<true, false, NoiseKeys>), dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a, NoiseKeys{noise_keys, step});
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1107,12 +1204,19 @@ int fdipt_se3_reverse_step_indexed_gen(const FdiptReverseIndexed* x, const uint6
     return FDIPT_EINVAL;
   if (x->prot_traj && (!x->psi || !x->bb_tables)) return FDIPT_EINVAL;
   if (x->trans_traj && (!x->pred_rigids || !x->traj_fixed_mask)) return FDIPT_EINVAL;
+  if ((x->state_ring & ~1) || (x->kept_rigids && !x->frame_rows)) return FDIPT_EINVAL;
   ReverseArgs a = {x->B, x->N, x->rigid_traj, x->rot_score, x->trans_score, x->diffuse_mask, nullptr, nullptr, 0.0, x->dt,
                    x->noise_scale, x->center, x->diffuse_rot, x->diffuse_trans, x->so3_min_sigma, x->so3_max_sigma, x->r3_min_b,
                    x->r3_max_b, x->coordinate_scaling, x->rigid_traj, nullptr, 64, x->psi, x->aatype,
                    (const BackboneTables*)x->bb_tables, x->prot_traj, x->pred_rigids, x->traj_fixed_mask, x->trans_traj,
                    x->step_cursor, x->t_table};
-  hipLaunchKernelGGL((reverse_step_kernel<true, NoiseKeys>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a, NoiseKeys{noise_keys, 0});
+  if (x->frame_rows || x->state_ring) {
+    hipLaunchKernelGGL((reverse_step_kernel<true, true, KeptRows, NoiseKeys>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a,
+                       KeptRows{x->frame_rows, x->kept_rigids, x->state_ring}, NoiseKeys{noise_keys, 0});
+    FD_CHECK_LAUNCH();
+    return FDIPT_OK;
+  }
+  hipLaunchKernelGGL((reverse_step_kernel<true, false, NoiseKeys>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a, NoiseKeys{noise_keys, 0});
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1148,7 +1252,7 @@ int fdipt_igso3_rot_score_cached(int B, int N, const float* quats_t, const float
   ScoreTail x = {};
   x.score_table = score_table; x.omega_edges = omega_edges; x.n_omega = n_omega;
   // (sigma is not read with a table; the table itself stands in for the pointer so that the kernel's per-sample read stays in bounds)
-  hipLaunchKernelGGL(rot_score_kernel, dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, (hipStream_t)s, B, N, quats_t, 4,
+  hipLaunchKernelGGL(rot_score_kernel<false>, dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, (hipStream_t)s, B, N, quats_t, 4,
                      quats_0, 4, score_table, res_mask, score, x);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
@@ -1170,6 +1274,12 @@ int fdipt_backbone_atoms_indexed(int n, const float* t7, const float* psi, const
   if (n <= 0) return FDIPT_OK;
   if (!t7 || !psi || !tables || !atom37_rows || !step_cursor) return FDIPT_EINVAL;
   return fd_backbone(n, t7, nullptr, nullptr, 3, psi, aatype, tables, atom37_rows, nullptr, (hipStream_t)s, step_cursor);
+}
+int fdipt_backbone_atoms_kept(int n, const float* t7, const float* psi, const int32_t* aatype, const void* tables,
+                              float* atom37_rows, const int32_t* step_cursor, const int32_t* frame_rows, fdipt_stream_t s) {
+  if (n <= 0) return FDIPT_OK;
+  if (!t7 || !psi || !tables || !atom37_rows || !step_cursor || !frame_rows) return FDIPT_EINVAL;
+  return fd_backbone(n, t7, nullptr, nullptr, 3, psi, aatype, tables, atom37_rows, nullptr, (hipStream_t)s, step_cursor, frame_rows);
 }
 }  // extern "C"
 

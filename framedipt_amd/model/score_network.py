@@ -53,6 +53,7 @@ class BatchState:
         self.B, self.N = B, N
         d = net.dims
         sidx = seq_idx.detach().cpu().numpy().astype(np.int64)
+        self._sidx = sidx
         self.seq_idx = torch.as_tensor(sidx.astype(np.int32), device=dev)
         E = d.index_embed
         self.idx_emb = torch.as_tensor(embedding.get_index_embedding(sidx, E), device=dev)
@@ -87,13 +88,42 @@ class BatchState:
         self.t_emb_eps = torch.as_tensor(embedding.get_timestep_embedding(np.array([1e-5], dtype=np.float32), E)[0],
                                          device=dev)
 
+    def refresh(self, seq_idx: torch.Tensor) -> bool:
+        """Another batch's ``seq_idx`` (same B, N) written INTO this state's device allocations — captured step graphs hold their
+        pointers (``inference.ReverseLoop.reset``).  True: done in place (``seq_idx`` and its index embedding; the relative-position
+        table in ``setup`` depends on the index range only, which did not change).  False: the range changed, so ``n_rel`` / ``rel_off``
+        (launch scalars) and a new ``setup`` table were made — graphs that captured the old ones must be dropped."""
+        if tuple(seq_idx.shape) != (self.B, self.N):
+            raise ValueError(f"refresh: seq_idx of shape {tuple(seq_idx.shape)}, the state holds B, N = {self.B}, {self.N}")
+        lib, net, dev = _lib.load(), self.net, self.net.device
+        sidx = seq_idx.detach().cpu().numpy().astype(np.int64)
+        if np.array_equal(sidx, self._sidx):
+            return True
+        self._sidx = sidx
+        E, d = net.dims.index_embed, net.dims
+        with torch.cuda.device(dev):
+            self.seq_idx.copy_(torch.as_tensor(sidx.astype(np.int32)))
+            self.idx_emb.copy_(torch.as_tensor(embedding.get_index_embedding(sidx, E)))
+            rng = int(sidx.max() - sidx.min())
+            if rng == self.rel_off:
+                return True
+            self.rel_off, self.n_rel = rng, 2 * rng + 1
+            rel = np.arange(self.n_rel) - rng
+            rel_emb = torch.as_tensor(np.broadcast_to(embedding.get_index_embedding(rel, E)[None], (self.B, self.n_rel, E)).copy(), device=dev)
+            self.setup = torch.empty(lib.fdipt_setup_bytes(C.byref(d), self.B, self.N, self.n_rel), dtype=torch.uint8, device=dev)
+            _lib.check(lib.fdipt_sample_setup(C.byref(d), _lib.ptr(net.params), _lib.ptr(net.derived), self.B, self.N, self.n_rel,
+                                              _lib.ptr(rel_emb), _lib.ptr(self.setup), _lib.stream_ptr()), "sample_setup")
+        return False
+
     def forward(self, rigids_t, res_mask, fixed_mask, sc_ca_t, aatype, gt_psi, t_dev, t_emb_dev, sigma_dev,
-                want_atoms: bool = True, ca_out=None, atom37_out=None, step_cursor=None):
+                want_atoms: bool = True, ca_out=None, atom37_out=None, step_cursor=None, frame_rows=None, state_ring=False):
         """All arguments are device tensors (float32 unless noted); outputs land in this state's buffers.
         ``ca_out`` ([B,N,3], may be ``sc_ca_t`` itself) receives the predicted CA positions for the next step.
         ``step_cursor`` (device int32[2], FdiptForwardArgs.step_cursor): ``rigids_t``, ``t_dev``, ``t_emb_dev``, ``sigma_dev``,
         ``self.score_table`` and ``atom37_out`` are then the step-major arrays of a trajectory and the kernels use row
-        ``step_cursor[0]`` of each — the launch arguments no longer depend on the step (``inference.ReverseLoop``'s step graph)."""
+        ``step_cursor[0]`` of each — the launch arguments no longer depend on the step (``inference.ReverseLoop``'s step graph).
+        With ``step_cursor``: ``frame_rows`` (device int32[T], FdiptForwardArgs.frame_rows) maps the step to its row of ``atom37_out`` (-1:
+        no backbone atoms this step), ``state_ring``: ``rigids_t`` is a two-row state and x_t of step k is row ``k & 1``."""
         lib = _lib.load()
         net = self.net
         a = _lib.ForwardArgs()
@@ -111,6 +141,8 @@ class BatchState:
             a.ev_start, a.ev_stop = self.ev_start, self.ev_stop
         a.reserve_cus = self.reserve_cus
         a.step_cursor = _lib.ptr(step_cursor)
+        if step_cursor is not None:
+            a.frame_rows, a.state_ring = _lib.ptr(frame_rows), int(bool(state_ring))
         a.clock_out = _lib.ptr(self.clock_out)
         if self.score_table is not None:
             a.so3_score_table, a.so3_omega_edges = _lib.ptr(self.score_table), _lib.ptr(self.omega_edges)

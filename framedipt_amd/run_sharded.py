@@ -204,6 +204,9 @@ def main():
                     "device: the reverse-step kernel draws from the per-sample key seed + item (x_T still comes from np.random)")
     ap.add_argument("--weights-seed", type=int, default=7, help="synthetic weights (no checkpoint is available offline)")
     ap.add_argument("--full-trajectory", action="store_true", help="store every step of prot_traj instead of the final sample")
+    ap.add_argument("--keep", default="all", help="inference_fn(keep=...): all (default: every step's frames are built and held on the device), "
+                    "last (only the final structure: what a run without --full-trajectory writes anyway) or an integer stride; with "
+                    "--full-trajectory the writers receive the kept frames only")
     # inpainting runs (experiments/inference.py:244-389)
     ap.add_argument("--download-dir", default=None, help="inpainting: the reference's data.download_dir (cifs/ and / or processed/metadata.csv)")
     ap.add_argument("--csv", default=None, help="inpainting: the reference's data.data_path (database CSV with a pdb_id column; TCR chain columns with --tcr)")
@@ -216,6 +219,11 @@ def main():
                     "(refused by default: kernels of two processes on one GPU can corrupt each other's results, DESIGN.md section 6)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
+    if a.keep not in ("all", "last"):
+        try:
+            a.keep = int(a.keep)
+        except ValueError:
+            ap.error(f"--keep {a.keep}: expected all, last or an integer stride")
 
     import torch
     import torch.distributed as dist
@@ -262,6 +270,12 @@ def main():
         ds = UnconditionalSampler(config.to_conf({"min_length": a.min_length, "max_length": a.max_length,
                                                   "length_step": a.length_step, "samples_per_length": a.samples_per_length}), diff, dev)
 
+    inference.kept_steps(a.num_t, a.keep)  # (a bad stride fails here, before any rank allocates)
+    # one session per rank: batches of a shape this rank has run before reuse that loop's device buffers and captured step graphs
+    # (with --keep all a loop holds the full trajectories — 2 x 4.3 GB at B = 64, N = 300, T = 500 — so only the most recent shape stays
+    #  resident, as much as a rank held at a time before sessions; kept-frame loops are small and four shapes stay)
+    session = inference.Session(max_loops=1 if a.keep == "all" else 4)
+
     def run_batch(feats, tape):
         # (--noise device: run_rank hands over the batch's noise keys where the tape would be)
         how = dict(noise="device", noise_keys=tape) if a.noise == "device" else dict(noise_tape=tape)
@@ -269,7 +283,7 @@ def main():
         def go():
             return inference.inference_fn(net, diff, feats, num_t=a.num_t, min_t=a.min_t, aux_traj=True, noise_scale=a.noise_scale,
                                           return_device=True, **how, inpainting=inp, verify=a.verify,
-                                          input_aatype=inp and not a.no_input_aatype)  # (run_rank overlaps the D2H copy with the next batch)
+                                          input_aatype=inp and not a.no_input_aatype, keep=a.keep, session=session)  # (run_rank overlaps the D2H copy with the next batch)
         if not (one_gpu and world > 1):
             return go()
         # FDIPT_ONE_GPU (tests): the ranks share one GPU.  Kernels of two processes must not be co-resident on it (DESIGN.md section 6:
@@ -299,11 +313,13 @@ def main():
     recs = run_rank(ds, diff, run_batch, rank, world, a.out_dir, a.seed, a.num_t, a.min_t, a.max_batch, keep=keep,
                     final_only=not a.full_trajectory, write_item=write_item, noise=a.noise)
     torch.cuda.synchronize()
+    session.close()
     if world > 1:
         dist.barrier()
     if rank == 0:
         el = time.perf_counter() - t0
-        allrecs = write_manifest(a.out_dir, world, len(ds), {"num_t": a.num_t, "precision": a.precision, "seed": a.seed, "noise": a.noise, "wall_s": el})
+        allrecs = write_manifest(a.out_dir, world, len(ds), {"num_t": a.num_t, "precision": a.precision, "seed": a.seed, "noise": a.noise, "wall_s": el,
+                                                                **({} if a.keep == "all" else {"keep": a.keep})})
         print(f"{sum(r['n_res'] for r in allrecs) * a.num_t / el:.0f} residue*steps/s (incl. model set-up and file output)")
         print(f"{len(ds)} samples on {world} GPU(s) in {el:.1f} s -> {a.out_dir}/manifest.json", flush=True)
     if world > 1:

@@ -192,6 +192,13 @@ typedef struct FdiptForwardArgs {
    * The launch sequence then does not depend on k: a step (this forward + fdipt_se3_reverse_step_indexed, which advances the
    * cursor) can be captured once as a HIP graph and replayed for every step of every trajectory of the shape. */
   const int32_t* step_cursor;
+  /* optional, with step_cursor only (kept-frame trajectories): frame_rows is a device int32[T] row map — step k writes its rigid_0_traj
+   * frame to row frame_rows[k] of atom37 [n_kept,B,N,37,3], or builds no backbone atoms at all where frame_rows[k] == -1 (the decision is
+   * uniform per launch, read from the map at the cursor: the launch sequence stays independent of k).  NULL: row k, as above. */
+  const int32_t* frame_rows;
+  /* optional, with step_cursor only: 1 = rigids_t is a two-row state ring [2,B,N,7] and x_t of step k is row k & 1 (the reverse step
+   * writes x_{t-1} to row (k + 1) & 1: FdiptReverseIndexed.state_ring).  0: row k of the step-major [T+1,B,N,7], as above. */
+  int32_t state_ring;
 } FdiptForwardArgs;
 
 size_t fdipt_forward_workspace_bytes(const FdiptDims* dims, int B, int N);
@@ -282,6 +289,14 @@ typedef struct FdiptReverseIndexed {
   const float* traj_fixed_mask;  /* [B,N] f32 */
   float* trans_traj;             /* [T,B,N,3] f32 or NULL */
   int32_t* step_cursor;          /* device int32[2] */
+  /* kept-frame trajectories (all three zero: the addressing above).  frame_rows: device int32[T], step k writes prot_traj / trans_traj /
+   * kept_rigids at row frame_rows[k] of arrays with n_kept rows; -1 = the step keeps no frame: the kernel skips the backbone-frame
+   * construction and the trans_traj row (uniform per launch).  NULL: row k. */
+  const int32_t* frame_rows;
+  /* 1 = rigid_traj is a two-row state ring [2,B,N,7]: reads x_t = row k & 1, writes x_{t-1} = row (k + 1) & 1.  0: rows k and k + 1. */
+  int32_t state_ring;
+  /* [n_kept,B,N,7] f32 or NULL: x_{t-1} of the kept steps (a copy of the state row, written on kept steps only) */
+  float* kept_rigids;
 } FdiptReverseIndexed;
 int fdipt_se3_reverse_step_indexed(const FdiptReverseIndexed* args, fdipt_stream_t stream);
 /* ---------------------------------------------------------------- device noise (opt-in) ---- */
@@ -316,6 +331,11 @@ int fdipt_se3_reverse_step_indexed_gen(const FdiptReverseIndexed* args, const ui
  * caller's aatype view, experiments/utils.py:397-402). */
 int fdipt_backbone_atoms_indexed(int n, const float* t7, const float* psi, const int32_t* aatype, const void* tables,
                                  float* atom37_rows, const int32_t* step_cursor, fdipt_stream_t s);
+
+/* fdipt_backbone_atoms_indexed of a kept-frame loop: the frames go to row frame_rows[step_cursor[0]] of atom37_rows [n_kept,n,37,3]
+ * (frame_rows: device int32[T], as in FdiptForwardArgs); a step whose row is -1 builds nothing. */
+int fdipt_backbone_atoms_kept(int n, const float* t7, const float* psi, const int32_t* aatype, const void* tables,
+                              float* atom37_rows, const int32_t* step_cursor, const int32_t* frame_rows, fdipt_stream_t s);
 
 /* ---------------------------------------------------------------- EigenFold confidence score (f4) */
 /* SE3Diffuser.forward: one-step forward noising q(x_t | x_{t-1}) (framedipt/diffusion/se3_diffuser.py:50-95; r3_diffuser.py:122-161

@@ -6,8 +6,11 @@ through ReverseLoop (step-graph replays, the product path).  Per trajectory: tap
 priming + first steps + graph capture, the remaining loop, results(); and the GPU time per replayed step (HIP events around the
 replays).  The first trajectory of a process also pays the lazy set-up of the kernels; the JSON line carries every trajectory.
 On a tree without noise="device" only the host mode runs.  DESIGN.md section 7 quotes the table.
+--keep all|last|<stride>: kept-frame trajectories; --session: the trajectories of the process run through one inference.Session (the second
+and later ones reset the first one's loop and replay its graphs).  Both are ignored with a note on a tree that does not have them, so the
+same command lines time a parent checkout.  peak_alloc_mb: torch's peak allocated HBM over the trajectory.
 
-    python tools/trajectory_wall.py [--noise host|device] [--n 300] [--b 8] [--t 500] [--precision fp16] [--reps 2]
+    python tools/trajectory_wall.py [--noise host|device] [--n 300] [--b 8] [--t 500] [--precision fp16] [--reps 2] [--keep last] [--session]
 """
 import argparse
 import json
@@ -28,7 +31,10 @@ def main():
     ap.add_argument("--precision", default="fp16")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--tag", default="")
+    ap.add_argument("--keep", default="all")
+    ap.add_argument("--session", action="store_true")
     a = ap.parse_args()
+    keep = a.keep if a.keep in ("all", "last") else int(a.keep)
     import numpy as np
     import torch
     from framedipt_amd import config, inference
@@ -48,8 +54,16 @@ def main():
     k1 = k0 + (n_noisy - k0) // chunk * chunk        # whole chunk replays only
     sync = torch.cuda.synchronize
     rows = []
+    has_keep = hasattr(inference, "kept_steps")
+    if not has_keep and (keep != "all" or a.session):
+        print("this tree has no keep= / Session: running the default path", file=sys.stderr)
+        keep, a.session = "all", False
+    n_kept = len(inference.kept_steps(T, keep)) if has_keep else T
+    session = inference.Session() if a.session else None
+    opts = dict(aux_traj=True, noise_scale=0.1, **({"keep": keep} if has_keep else {}))
     for rep in range(a.reps):
         sync()
+        torch.cuda.reset_peak_memory_stats()
         w = {}
         t0 = time.perf_counter()
         if a.noise == "host":
@@ -59,7 +73,11 @@ def main():
             how = dict(noise="device", noise_keys=1000 + rep * a.b)
         w["draw_s"] = time.perf_counter() - t0
         t1 = time.perf_counter()
-        loop = inference.ReverseLoop(net, d, feats, T, min_t, aux_traj=True, noise_scale=0.1, **how)
+        if session is not None:
+            loop = session.loop(net, d, feats, T, min_t, noise_tape=how.get("noise_tape"), noise_keys=how.get("noise_keys"), **opts)
+        else:
+            loop = inference.ReverseLoop(net, d, feats, T, min_t, **opts, **how)
+        captures_before = getattr(loop, "captures", 0)
         sync()
         w["setup_upload_s"] = time.perf_counter() - t1
         t2 = time.perf_counter()
@@ -80,9 +98,11 @@ def main():
         w["results_s"] = time.perf_counter() - t4
         w["wall_s"] = time.perf_counter() - t0
         w["gpu_ms_per_step"] = e0.elapsed_time(e1) / max(1, k1 - k0)
-        w["capture_s"] = loop.capture_seconds
+        w["capture_s"] = loop.capture_seconds  # (cumulative over a session loop's life)
+        w["captures"] = getattr(loop, "captures", 0) - captures_before
+        w["peak_alloc_mb"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
         w["noise_bytes_on_device"] = 0 if loop.z_rot is None else int(loop.z_rot.numel() + loop.z_trans.numel()) * 8
-        assert res["prot_traj"].shape == (T, a.b, a.n, 37, 3) and np.isfinite(res["prot_traj"]).all()
+        assert res["prot_traj"].shape == (n_kept, a.b, a.n, 37, 3) and np.isfinite(res["prot_traj"]).all()
         if a.noise == "host":  # the upload alone, outside the wall time above
             sync()
             t5 = time.perf_counter()
@@ -93,7 +113,7 @@ def main():
         del loop, res
         rows.append({k: round(v, 5) if isinstance(v, float) else v for k, v in w.items()})
     print(json.dumps({"tool": "trajectory_wall", "tag": a.tag, "noise": a.noise, "n": a.n, "b": a.b, "t": T, "precision": a.precision,
-                      "event_steps": k1 - k0, "trajectories": rows}), flush=True)
+                      "event_steps": k1 - k0, "keep": keep, "session": bool(a.session), "trajectories": rows}), flush=True)
 
 
 if __name__ == "__main__":
