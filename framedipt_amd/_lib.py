@@ -19,7 +19,8 @@ KF_ET3, KF_GENERIC_PAIR, KF_GENERIC_ATTN, KF_UNFUSED_NODE, KF_UNFOLDED, KF_NO_SP
 KF_POINTS_LAUNCH = 512
 KF_STREAM_ATTN = 1024
 _ERR = {-1: "FDIPT_EINVAL (bad argument)", -2: "FDIPT_ELAUNCH (HIP launch error)",
-        -3: "FDIPT_ESIZE (workspace too small or N beyond the compiled tiling: N <= 1024, N <= 2048 with KF_STREAM_ATTN in the fp16 mode)"}
+        -3: "FDIPT_ESIZE (workspace too small or N beyond the compiled tiling: N <= 1024, N <= 2048 with KF_STREAM_ATTN in the fp16 mode; "
+            "sample selection: a group of more than 64 samples)"}
 
 
 class FdiptError(RuntimeError):
@@ -56,6 +57,18 @@ class ReverseIndexed(C.Structure):
         ("frame_rows", _P), ("state_ring", C.c_int32), ("kept_rigids", _P)]  # kept-frame trajectories (all zero: step-major addressing)
 
 
+class SelectArgs(C.Structure):
+    """FdiptSelectArgs (include/fdipt.h): sample selection over G groups of the B samples of one atom37 array."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "N", "G", "L_max")] + [(n, _P) for n in (
+        "atom37", "diffuse_mask", "group_start", "member", "group_start_host", "n_diffused_host")] + [
+        ("sigma", C.c_double), ("max_iterations", C.c_int32)] + [(n, _P) for n in (
+            "mean", "median", "weights", "density", "dist_to_mean", "dist_to_median", "index", "status", "n_diffused", "workspace")] + [
+        ("workspace_bytes", C.c_size_t)]
+
+
+SELECT_MAX_SAMPLES = 64
+SELECT_ZERO_DISTANCE, SELECT_SKIPPED = 1, 2  # FdiptSelectArgs.status bits
+
 _lib = None
 
 # name -> (restype, argtypes); every symbol declared in include/fdipt.h
@@ -86,6 +99,8 @@ SIGNATURES = {
                                              _P, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_se3_reverse_step_indexed_gen": (_i, [C.POINTER(ReverseIndexed), _P, _P]),
     "fdipt_se3_forward_step_gen": (_i, [_i, _i, _P, _P, _P, _P, _i, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),
+    "fdipt_select_workspace_bytes": (_sz, [_i, _i, _i]),
+    "fdipt_sample_select": (_i, [C.POINTER(SelectArgs), _P]),
     "fdipt_backbone_atoms_indexed": (_i, [_i, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_backbone_atoms_kept": (_i, [_i, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_se3_forward_step": (_i, [_i, _i, _P, _P, _P, _P, _P, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),

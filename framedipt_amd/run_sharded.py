@@ -31,12 +31,13 @@ import numpy as np
 
 def run_rank(dataset, diffuser, run_batch, rank: int, world: int, out_dir: str, seed: int, num_t: int, min_t: float,
              max_batch: int = 8, keep=("prot_traj",), final_only: bool = True, mixed: bool = True, write_item=None,
-             noise: str = "host"):
+             noise: str = "host", collect=None):
     """Run this rank's share of ``dataset``.  ``run_batch(feats, tape) -> dict of arrays with a batch axis at dim 1`` (the
     keys of ``inference_fn``).  ``noise="device"``: ``run_batch`` receives the batch's noise keys [B] in the tape's place and no tape is
     drawn before the first launch.  ``mixed``: samples of similar (not only equal) length share a batch, padded with res_mask = 0
     rows (sharding.batches_mixed / stack_items_padded; a batch never spans two kernel-selection classes, so a sample's bits do not
-    depend on its batch mates); results are cut back to each sample's own length.
+    depend on its batch mates); results are cut back to each sample's own length.  ``collect`` (a dict, ``--select``): every item's final
+    atom37 and what ``run_selection`` needs to group and write it stay on the host under the item's index.
     Returns the list of records written by this rank."""
     from . import sharding
     os.makedirs(out_dir, exist_ok=True)
@@ -56,6 +57,12 @@ def run_rank(dataset, diffuser, run_batch, rank: int, world: int, out_dir: str, 
             else:
                 path = os.path.join(out_dir, f"sample_{item:06d}.npz")
                 np.savez(path, item=item, name=str(name), sample_i=int(sample_i), **arrays)
+            if collect is not None:
+                f = items[p][2]
+                host = lambda k: f[k][0, :n].detach().cpu().numpy() if k in f else None  # noqa: E731
+                collect[int(item)] = {"prot": np.array(np.asarray(res["prot_traj"])[0, b, :n], dtype=np.float32),
+                                      "diffused": (1 - host("fixed_mask")) * host("res_mask") != 0,
+                                      **{k: host(k) for k in ("res_mask", "aatype", "residue_index", "chain_idx")}}
             records.append({"item": int(item), "name": str(name), "sample_i": int(sample_i), "n_res": lengths[p],
                             "rank": rank, "file": os.path.relpath(str(path), out_dir)})
 
@@ -125,6 +132,59 @@ def write_manifest(out_dir: str, world: int, n_items: int, meta: dict):
     with open(os.path.join(out_dir, "manifest.json"), "w") as f:
         json.dump({"n_items": n_items, "world_size": world, **meta, "samples": recs}, f, indent=1)
     return recs
+
+
+def group_records_by_name(records):
+    """{structure name: its records in sample order} of manifest records, names in the order of their first item: the groups of
+    ``--select`` (the samples of one complex)."""
+    groups = {}
+    for r in sorted(records, key=lambda x: x["item"]):
+        groups.setdefault(str(r["name"]), []).append(r)
+    return {name: sorted(rs, key=lambda x: (x["sample_i"], x["item"])) for name, rs in groups.items()}
+
+
+def run_selection(out_dir: str, records, gathered: dict, reference_layout: bool, sigma: float = 30.0, max_iterations: int = 10000):
+    """Rank 0, after the gather (``--select``): one ``selection.select_samples`` launch for every structure of the run - the samples of
+    a name form a group, shorter structures are padded with undiffused rows - then ``selection.json`` (indices, weights, status per
+    structure) and, with the reference's directory layout, ``sample_<strategy>.pdb`` next to the sample each strategy builds on (where
+    get_selected_sample_model_and_path puts it; b-factor 100 = diffused).  Returns the summary written to ``selection.json``."""
+    import pathlib
+
+    from . import output, selection
+    by_name = group_records_by_name(records)
+    order = [r for rs in by_name.values() for r in rs]
+    n_max = max(gathered[r["item"]]["prot"].shape[0] for r in order)
+    prot = np.zeros((len(order), n_max, 37, 3), dtype=np.float32)
+    mask = np.zeros((len(order), n_max), dtype=np.float32)
+    groups = np.zeros(len(order), dtype=np.int64)
+    for b, r in enumerate(order):
+        it = gathered[r["item"]]
+        n = it["prot"].shape[0]
+        prot[b, :n], mask[b, :n] = it["prot"], it["diffused"]
+        groups[b] = list(by_name).index(str(r["name"]))
+    sel = selection.select_samples(prot, mask, groups, sigma=sigma, max_iterations=max_iterations)
+    summary = {"sigma": sigma, "max_iterations": max_iterations, "structures": {}}
+    for g, (name, rs) in enumerate(by_name.items()):
+        entry = {"items": [r["item"] for r in rs], "sample_i": [r["sample_i"] for r in rs], "n_diffused": int(len(sel["residues"][g])),
+                 "status": int(sel["status"][g]), **{k: sel[k][g].tolist() for k in ("weights", "density", "dist_to_mean", "dist_to_median")},
+                 "strategies": {}}
+        for strategy in selection.STRATEGIES:
+            rec = rs[selection.carrier(sel, g, strategy)]
+            chosen = {"item": rec["item"], "sample_i": rec["sample_i"], "file": None}
+            if reference_layout:
+                it = gathered[rec["item"]]
+                n, rm = it["prot"].shape[0], it["res_mask"].astype(bool)
+                pos = selection.selected_structure(sel, g, strategy, prot)[:n]
+                path = (pathlib.Path(out_dir) / rec["file"]).parent / f"sample_{strategy}.pdb"
+                output.write_prot_to_pdb(pos[rm], path, overwrite=True, no_indexing=True, aatype=it["aatype"][rm],
+                                         b_factors=np.tile((it["diffused"] * 100)[:, None], (1, 37))[rm],
+                                         residue_index=it["residue_index"][rm], chain_index=it["chain_idx"][rm])
+                chosen["file"] = os.path.relpath(str(path), out_dir)
+            entry["strategies"][strategy] = chosen
+        summary["structures"][name] = entry
+    with open(os.path.join(out_dir, "selection.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    return summary
 
 
 def reference_layout_writer(out_dir: str, net, final_only: bool):
@@ -217,6 +277,11 @@ def main():
     ap.add_argument("--no-input-aatype", action="store_true", help="inference.input_aatype = False (default True: backbone atoms are built with the true residue types)")
     ap.add_argument("--allow-shared-gpu", action="store_true", help="run although another compute process holds queues on this rank's GPU "
                     "(refused by default: kernels of two processes on one GPU can corrupt each other's results, DESIGN.md section 6)")
+    ap.add_argument("--select", action="store_true", help="after the run, rank 0 forms the reference's five selected structures (mean, median, mode, "
+                    "mean_closest, median_closest: framedipt_amd/selection.py) from the samples of every structure on its GPU: selection.json, "
+                    "and sample_<strategy>.pdb files in inpainting runs")
+    ap.add_argument("--select-sigma", type=float, default=30.0, help="--select: std of the density kernel (reference default)")
+    ap.add_argument("--select-iterations", type=int, default=10000, help="--select: Weiszfeld iterations (reference default)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
     if a.keep not in ("all", "last"):
@@ -310,18 +375,27 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
+    collected = {} if a.select else None
     recs = run_rank(ds, diff, run_batch, rank, world, a.out_dir, a.seed, a.num_t, a.min_t, a.max_batch, keep=keep,
-                    final_only=not a.full_trajectory, write_item=write_item, noise=a.noise)
+                    final_only=not a.full_trajectory, write_item=write_item, noise=a.noise, collect=collected)
     torch.cuda.synchronize()
     session.close()
     if world > 1:
         dist.barrier()
+    gathered = None
+    if a.select:  # (every rank takes part in the gather; rank 0 receives)
+        from . import sharding
+        gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
         el = time.perf_counter() - t0
         allrecs = write_manifest(a.out_dir, world, len(ds), {"num_t": a.num_t, "precision": a.precision, "seed": a.seed, "noise": a.noise, "wall_s": el,
                                                                 **({} if a.keep == "all" else {"keep": a.keep})})
         print(f"{sum(r['n_res'] for r in allrecs) * a.num_t / el:.0f} residue*steps/s (incl. model set-up and file output)")
         print(f"{len(ds)} samples on {world} GPU(s) in {el:.1f} s -> {a.out_dir}/manifest.json", flush=True)
+        if a.select:
+            t1 = time.perf_counter()
+            done = run_selection(a.out_dir, allrecs, gathered, reference_layout=inp, sigma=a.select_sigma, max_iterations=a.select_iterations)
+            print(f"selected structures of {len(done['structures'])} structure(s) in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/selection.json", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

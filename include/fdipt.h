@@ -363,6 +363,50 @@ int fdipt_se3_step_log_prob(int B, int N, const float* rot_t, const float* trans
 int fdipt_se3_prior_log_prob(int B, int N, const float* trans_T, const float* diffuse_mask, double coordinate_scaling, double* out,
                              fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- sample selection (opt-in) */
+/* The five selected structures of evaluation/utils/sample_selection.py (get_selected_models :568-615) from the samples of a complex,
+ * over the backbone atoms C, N, CA, O (BACKBONE_ATOMS order = atom37 columns 2, 0, 1, 4) of its diffused residues, in float64:
+ * get_mean_coordinates (:163), get_median_coordinates (:216 -> weiszfeld_geometric_median :82), gaussian_density_estimation (:63) with
+ * get_mode_index (:256), get_closest_index (:281) against the mean and the median.  One launch serves G groups (complexes) of the B
+ * samples of atom37: group g = samples member[group_start[g] .. group_start[g + 1] - 1], S <= 64 of them, L = the number of rows with
+ * diffuse_mask != 0 of its FIRST member (the caller makes sure that a group's members share the mask); S and L differ freely between
+ * the groups of a launch.  One block per group; all max_iterations Weiszfeld iterations run inside the launch, as iterations on the
+ * weights w of the iterate mu + sum_s w_s (x_s - mu) (mu = the mean, w = 1/S at the start): with the Gram matrix G of the centred
+ * samples, d_s = sqrt(max(G_ss - 2 (G w)_s + w'G w, 0)) and w_s = (1 / d_s) / sum_r (1 / d_r).  Exactly max_iterations iterations, no
+ * convergence test - as the reference - with one divergence: where the reference divides by a distance of exactly 0 (and returns NaN;
+ * always for S = 1) the iteration stops, the median is that sample (w = e_s, lowest s) and FDIPT_SELECT_ZERO_DISTANCE is set. */
+#define FDIPT_SELECT_MAX_SAMPLES 64
+#define FDIPT_SELECT_ZERO_DISTANCE 1 /* status bit: the iteration met a distance of exactly 0 and returned that sample           */
+#define FDIPT_SELECT_SKIPPED 2       /* status bit: the device data contradict the host counts (S, L, a member index out of range):
+                                        the group's other outputs were not written                                             */
+typedef struct FdiptSelectArgs {
+  int32_t B, N, G, L_max;            /* samples, residues per sample, groups, capacity of the coordinate outputs in residues        */
+  const float* atom37;               /* [B,N,37,3] f32                                                                              */
+  const float* diffuse_mask;         /* [B,N] f32                                                                                   */
+  const int32_t* group_start;        /* [G+1] i32, ascending from 0                                                                 */
+  const int32_t* member;             /* [group_start[G]] i32 sample indices, group after group                                      */
+  const int32_t* group_start_host;   /* HOST copy of group_start: the entry validates the group sizes with it                       */
+  const int32_t* n_diffused_host;    /* HOST [G] i32: L of every group, 1 <= L <= L_max (the kernel counts again from the mask)     */
+  double sigma;                      /* std of the Gaussian kernel of the density (reference default 30.0)                          */
+  int32_t max_iterations;            /* Weiszfeld iterations (reference default 10000)                                              */
+  /* outputs; per-sample arrays are indexed like `member` (position group_start[g] + s) */
+  double* mean;                      /* [G,L_max,4,3] f64, rows >= L untouched                                                      */
+  double* median;                    /* [G,L_max,4,3] f64                                                                           */
+  double* weights;                   /* [group_start[G]] f64: w of the median, sums to 1                                            */
+  double* density;                   /* [group_start[G]] f64: sum_r exp(-|x_s - x_r|^2 / sigma^2)                                   */
+  double* dist_to_mean;              /* [group_start[G]] f64: sum over atoms of |x_s,a - mean_a|                                    */
+  double* dist_to_median;            /* [group_start[G]] f64                                                                        */
+  int32_t* index;                    /* [G,3] i32: mode (argmax density), mean_closest, median_closest (argmin); lowest index on ties */
+  int32_t* status;                   /* [G] i32: FDIPT_SELECT_* bits                                                                */
+  int32_t* n_diffused;               /* [G] i32: L as the kernel counted it                                                         */
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptSelectArgs;
+size_t fdipt_select_workspace_bytes(int G, int B, int L_max);
+/* FDIPT_ESIZE: a group of more than FDIPT_SELECT_MAX_SAMPLES samples, workspace too small.  FDIPT_EINVAL: an empty group, L = 0 or
+ * L > L_max, a null pointer, sigma <= 0, max_iterations < 0. */
+int fdipt_sample_select(const FdiptSelectArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */
 int fdipt_quat_to_rot(int n, const float* quat, float* rot, fdipt_stream_t s);           /* :185 */
