@@ -69,6 +69,18 @@ class SelectArgs(C.Structure):
 SELECT_MAX_SAMPLES = 64
 SELECT_ZERO_DISTANCE, SELECT_SKIPPED = 1, 2  # FdiptSelectArgs.status bits
 
+
+class EvalArgs(C.Structure):
+    """FdiptEvalArgs (include/fdipt.h): evaluation of B samples against R ground-truth structures."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "N", "R", "n_regions", "max_regions")] + [(n, _P) for n in (
+        "atom37", "ref37", "ref_index", "diffuse_mask", "res_mask", "align_mask", "chain_idx", "region_start", "region_rows",
+        "ref_index_host", "region_start_host", "res_bb_rmsd", "region_bb_rmsd", "bb_rmsd", "dihedral", "gt_dihedral", "angle_error",
+        "ca_ca_bond_dev", "ca_ca_valid_percent", "num_ca_steric_clashes", "ca_steric_clash_percent", "aligned_mean_dev", "aligned_rmsd",
+        "rotation", "translation", "reflection", "status", "n_diffused", "workspace")] + [("workspace_bytes", C.c_size_t)]
+
+
+EVAL_NAN_DIHEDRAL, EVAL_DEGENERATE_ALIGNMENT, EVAL_SKIPPED = 1, 2, 4  # FdiptEvalArgs.status bits
+
 _lib = None
 
 # name -> (restype, argtypes); every symbol declared in include/fdipt.h
@@ -101,6 +113,8 @@ SIGNATURES = {
     "fdipt_se3_forward_step_gen": (_i, [_i, _i, _P, _P, _P, _P, _i, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),
     "fdipt_select_workspace_bytes": (_sz, [_i, _i, _i]),
     "fdipt_sample_select": (_i, [C.POINTER(SelectArgs), _P]),
+    "fdipt_eval_workspace_bytes": (_sz, [_i, _i]),
+    "fdipt_sample_evaluate": (_i, [C.POINTER(EvalArgs), _P]),
     "fdipt_backbone_atoms_indexed": (_i, [_i, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_backbone_atoms_kept": (_i, [_i, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_se3_forward_step": (_i, [_i, _i, _P, _P, _P, _P, _P, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),

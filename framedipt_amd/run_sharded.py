@@ -31,13 +31,14 @@ import numpy as np
 
 def run_rank(dataset, diffuser, run_batch, rank: int, world: int, out_dir: str, seed: int, num_t: int, min_t: float,
              max_batch: int = 8, keep=("prot_traj",), final_only: bool = True, mixed: bool = True, write_item=None,
-             noise: str = "host", collect=None):
+             noise: str = "host", collect=None, ground_truth=None):
     """Run this rank's share of ``dataset``.  ``run_batch(feats, tape) -> dict of arrays with a batch axis at dim 1`` (the
     keys of ``inference_fn``).  ``noise="device"``: ``run_batch`` receives the batch's noise keys [B] in the tape's place and no tape is
     drawn before the first launch.  ``mixed``: samples of similar (not only equal) length share a batch, padded with res_mask = 0
     rows (sharding.batches_mixed / stack_items_padded; a batch never spans two kernel-selection classes, so a sample's bits do not
     depend on its batch mates); results are cut back to each sample's own length.  ``collect`` (a dict, ``--select``): every item's final
-    atom37 and what ``run_selection`` needs to group and write it stay on the host under the item's index.
+    atom37 and what ``run_selection`` needs to group and write it stay on the host under the item's index; ``ground_truth(feats) -> atom37
+    [N,37,3]`` (``--evaluate``, inpainting) is called for the first sample of every structure and kept with it under ``gt``.
     Returns the list of records written by this rank."""
     from . import sharding
     os.makedirs(out_dir, exist_ok=True)
@@ -63,6 +64,8 @@ def run_rank(dataset, diffuser, run_batch, rank: int, world: int, out_dir: str, 
                 collect[int(item)] = {"prot": np.array(np.asarray(res["prot_traj"])[0, b, :n], dtype=np.float32),
                                       "diffused": (1 - host("fixed_mask")) * host("res_mask") != 0,
                                       **{k: host(k) for k in ("res_mask", "aatype", "residue_index", "chain_idx")}}
+                if ground_truth is not None and int(sample_i) == 0:
+                    collect[int(item)]["gt"] = np.array(ground_truth(f), dtype=np.float32)[:n]
             records.append({"item": int(item), "name": str(name), "sample_i": int(sample_i), "n_res": lengths[p],
                             "rank": rank, "file": os.path.relpath(str(path), out_dir)})
 
@@ -143,11 +146,12 @@ def group_records_by_name(records):
     return {name: sorted(rs, key=lambda x: (x["sample_i"], x["item"])) for name, rs in groups.items()}
 
 
-def run_selection(out_dir: str, records, gathered: dict, reference_layout: bool, sigma: float = 30.0, max_iterations: int = 10000):
+def run_selection(out_dir: str, records, gathered: dict, reference_layout: bool, sigma: float = 30.0, max_iterations: int = 10000, keep=None):
     """Rank 0, after the gather (``--select``): one ``selection.select_samples`` launch for every structure of the run - the samples of
     a name form a group, shorter structures are padded with undiffused rows - then ``selection.json`` (indices, weights, status per
     structure) and, with the reference's directory layout, ``sample_<strategy>.pdb`` next to the sample each strategy builds on (where
-    get_selected_sample_model_and_path puts it; b-factor 100 = diffused).  Returns the summary written to ``selection.json``."""
+    get_selected_sample_model_and_path puts it; b-factor 100 = diffused).  Returns the summary written to ``selection.json``; ``keep`` (a
+    dict, ``--evaluate``) receives the selection and the padded batch it ran on."""
     import pathlib
 
     from . import output, selection
@@ -163,6 +167,8 @@ def run_selection(out_dir: str, records, gathered: dict, reference_layout: bool,
         prot[b, :n], mask[b, :n] = it["prot"], it["diffused"]
         groups[b] = list(by_name).index(str(r["name"]))
     sel = selection.select_samples(prot, mask, groups, sigma=sigma, max_iterations=max_iterations)
+    if keep is not None:
+        keep.update(selection=sel, prot=prot)
     summary = {"sigma": sigma, "max_iterations": max_iterations, "structures": {}}
     for g, (name, rs) in enumerate(by_name.items()):
         entry = {"items": [r["item"] for r in rs], "sample_i": [r["sample_i"] for r in rs], "n_diffused": int(len(sel["residues"][g])),
@@ -184,6 +190,72 @@ def run_selection(out_dir: str, records, gathered: dict, reference_layout: bool,
         summary["structures"][name] = entry
     with open(os.path.join(out_dir, "selection.json"), "w") as f:
         json.dump(summary, f, indent=1)
+    return summary
+
+
+def run_evaluation(out_dir: str, records, gathered: dict, tcr: bool = False, selected=None):
+    """Rank 0, after the gather (``--evaluate``): one ``evaluation.evaluate_samples`` launch for every sample of every structure of the
+    run - and, with ``selected`` (what ``run_selection`` kept), the five selected structures of each - against the structure's ground
+    truth (``gt`` of its first sample's gathered entry); shorter structures are padded with res_mask = 0 rows.  Writes
+    ``evaluation.json`` (per structure the regions and per sample or strategy the scalars) and ``metrics.csv`` (one row per structure and
+    sample or strategy: pdb_name, sample, the scalars, then the reference's flattened per-residue columns; a structure with a region
+    shorter than 4 residues has the scalars only).  Without ground truth (de novo runs) only the CA geometry checks are reported.
+    Returns the summary written to ``evaluation.json``."""
+    import csv
+
+    from . import evaluation, selection
+    by_name = group_records_by_name(records)
+    rows = []  # (structure, label, atom37 [n,37,3], gathered entry)
+    for g, (name, rs) in enumerate(by_name.items()):
+        rows += [(name, str(r["sample_i"]), gathered[r["item"]]["prot"], gathered[r["item"]]) for r in rs]
+        if selected is not None:
+            first = gathered[rs[0]["item"]]
+            n = first["prot"].shape[0]
+            rows += [(name, strategy, selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n], first)
+                     for strategy in selection.STRATEGIES]
+    names = list(by_name)
+    truth = {name: next((gathered[r["item"]]["gt"] for r in rs if "gt" in gathered[r["item"]]), None) for name, rs in by_name.items()}
+    with_truth = all(t is not None for t in truth.values())
+    n_max = max(row[2].shape[0] for row in rows)
+    prot = np.zeros((len(rows), n_max, 37, 3), dtype=np.float32)
+    diffuse, res_mask, chain = (np.zeros((len(rows), n_max), dtype=dt) for dt in (np.float32, np.float32, np.int32))
+    for b, (_, _, pos, it) in enumerate(rows):
+        n = pos.shape[0]
+        prot[b, :n], diffuse[b, :n] = pos, it["diffused"]
+        res_mask[b, :n] = 1 if it.get("res_mask") is None else it["res_mask"]
+        chain[b, :n] = 0 if it.get("chain_idx") is None else np.rint(it["chain_idx"])
+    if with_truth:
+        reference = np.zeros((len(names), n_max, 37, 3), dtype=np.float32)
+        for r, name in enumerate(names):
+            reference[r, :truth[name].shape[0]] = truth[name]
+        res = evaluation.evaluate_samples(prot, reference, diffuse, chain, [names.index(row[0]) for row in rows], res_mask)
+        scalars = evaluation.SCALARS + ("status",)
+    else:  # (no ground truth: every sample against itself, only the geometry of the sample is reported)
+        res = evaluation.evaluate_samples(prot, prot, diffuse, chain, None, res_mask)
+        scalars = evaluation.GEOMETRY_SCALARS
+    number = lambda v: None if isinstance(v, float) and v != v else v  # noqa: E731  (NaN: no bond / no pair)
+    summary = {"ground_truth": with_truth, "structures": {}}
+    table, columns = [], ["pdb_name", "sample"] + list(scalars)
+    for b, (name, label, _, _) in enumerate(rows):
+        entry = summary["structures"].setdefault(name, {"regions": [list(r) for r in res["regions"][b]], "region_rows": [list(r) for r in res["region_rows"][b]],
+                                                        "region_names": evaluation.default_region_names(len(res["regions"][b]), tcr), "samples": {}})
+        values = {k: res[k][b].item() for k in scalars}
+        entry["samples"][label] = {k: number(v) for k, v in values.items()}
+        row = {"pdb_name": name, "sample": label, **values}
+        if with_truth:
+            entry["samples"][label]["region_bb_rmsd"] = res["region_bb_rmsd"][b].tolist()
+            try:
+                row.update(evaluation.eval_columns(res, b, entry["region_names"]))
+            except ValueError:  # a region shorter than 4 residues has no evaluation indices
+                pass
+        columns += [k for k in row if k not in columns]
+        table.append(row)
+    with open(os.path.join(out_dir, "evaluation.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "metrics.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=columns, restval="")
+        w.writeheader()
+        w.writerows({k: repr(v) if isinstance(v, float) else v for k, v in row.items()} for row in table)
     return summary
 
 
@@ -282,6 +354,9 @@ def main():
                     "and sample_<strategy>.pdb files in inpainting runs")
     ap.add_argument("--select-sigma", type=float, default=30.0, help="--select: std of the density kernel (reference default)")
     ap.add_argument("--select-iterations", type=int, default=10000, help="--select: Weiszfeld iterations (reference default)")
+    ap.add_argument("--evaluate", action="store_true", help="after the run, rank 0 evaluates every sample (and with --select the five selected structures) "
+                    "against the ground truth of its structure on its GPU (framedipt_amd/evaluation.py): evaluation.json and metrics.csv; "
+                    "de novo runs have no ground truth and report the CA geometry checks only")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
     if a.keep not in ("all", "last"):
@@ -375,15 +450,20 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select else None
+    collected = {} if a.select or a.evaluate else None
+    ground_truth = None
+    if a.evaluate and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
+        def ground_truth(feats):
+            build = lambda: inference.get_atom_positions_from_rigids(net, feats["rigids_0"], feats["torsion_angles_sin_cos"][..., 2, :], feats["aatype"])[0]  # noqa: E731
+            return one_gpu_turn(build) if one_gpu and world > 1 else build()
     recs = run_rank(ds, diff, run_batch, rank, world, a.out_dir, a.seed, a.num_t, a.min_t, a.max_batch, keep=keep,
-                    final_only=not a.full_trajectory, write_item=write_item, noise=a.noise, collect=collected)
+                    final_only=not a.full_trajectory, write_item=write_item, noise=a.noise, collect=collected, ground_truth=ground_truth)
     torch.cuda.synchronize()
     session.close()
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -392,10 +472,16 @@ def main():
                                                                 **({} if a.keep == "all" else {"keep": a.keep})})
         print(f"{sum(r['n_res'] for r in allrecs) * a.num_t / el:.0f} residue*steps/s (incl. model set-up and file output)")
         print(f"{len(ds)} samples on {world} GPU(s) in {el:.1f} s -> {a.out_dir}/manifest.json", flush=True)
+        selected = {} if a.select and a.evaluate else None
         if a.select:
             t1 = time.perf_counter()
-            done = run_selection(a.out_dir, allrecs, gathered, reference_layout=inp, sigma=a.select_sigma, max_iterations=a.select_iterations)
+            done = run_selection(a.out_dir, allrecs, gathered, reference_layout=inp, sigma=a.select_sigma, max_iterations=a.select_iterations, keep=selected)
             print(f"selected structures of {len(done['structures'])} structure(s) in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/selection.json", flush=True)
+        if a.evaluate:
+            t1 = time.perf_counter()
+            done = run_evaluation(a.out_dir, allrecs, gathered, tcr=a.tcr, selected=selected if inp else None)
+            print(f"evaluated {sum(len(e['samples']) for e in done['structures'].values())} structure(s) in {time.perf_counter() - t1:.2f} s -> "
+                  f"{a.out_dir}/evaluation.json, metrics.csv", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -407,6 +407,63 @@ size_t fdipt_select_workspace_bytes(int G, int B, int L_max);
  * L > L_max, a null pointer, sigma <= 0, max_iterations < 0. */
 int fdipt_sample_select(const FdiptSelectArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- sample evaluation (opt-in) */
+/* The numbers of the reference's evaluation tables for B samples against R ground-truth structures, in float64, in one launch:
+ * (a) backbone deviation without superposition over atom37 columns 2, 0, 1, 4 (C, N, CA, O) of the diffused residues
+ *     (evaluation/utils/metrics.py: residue_backbone_rmsd :146, chain_backbone_rmsd :71, backbone_rmsd :25);
+ * (b) phi, psi, omega in degrees (calc_dihedrals :926 per chain over the rows of res_mask: phi = 0 at a chain's first residue, psi =
+ *     omega = 0 at its last) of sample and ground truth, and angle_error_with_sign (:308) of (ground truth, sample);
+ * (c) ca_ca_distance / ca_ca_clashes (framedipt/analysis/metrics.py:185-218) over the rows with any non-zero coordinate, bonds between
+ *     consecutive kept rows whatever their chains, clashes = pairs at 0 < distance < 1.5, as a fraction of the pairs at distance > 0;
+ * (d) the superposition of the CA atoms of the align_mask rows onto the ground truth by the best proper rotation (rigid_transform_3D,
+ *     data/transforms.py:77; here Horn's quaternion eigenproblem): x -> rotation x + translation.
+ * A chain is a run of consecutive rows with res_mask != 0 and one chain_idx.  A region is a maximal run of diffused rows (diffuse_mask
+ * != 0 and res_mask != 0) of one chain; the host plans the table, the kernel checks it against the masks and skips a sample it does
+ * not describe.  Angles are stored in the order phi, psi, omega.  N is bounded by what a launch can address. */
+#define FDIPT_EVAL_NAN_DIHEDRAL 1         /* status bit: a dihedral of the sample or its ground truth is NaN (coincident atoms)     */
+#define FDIPT_EVAL_DEGENERATE_ALIGNMENT 2 /* status bit: fewer than 3 aligned rows or a covariance whose best rotation is not unique
+                                             (the two largest eigenvalues of Horn's matrix within 1e-9 of its size): finite outputs  */
+#define FDIPT_EVAL_SKIPPED 4              /* status bit: the region table or ref_index contradicts the device data: only status and
+                                             n_diffused were written                                                                 */
+typedef struct FdiptEvalArgs {
+  int32_t B, N, R, n_regions, max_regions; /* samples, residues, ground-truth rows, rows of region_rows, stride of region_bb_rmsd   */
+  const float* atom37;               /* [B,N,37,3] f32                                                                              */
+  const float* ref37;                /* [R,N,37,3] f32                                                                              */
+  const int32_t* ref_index;          /* [B] i32: ground-truth row of each sample                                                    */
+  const float* diffuse_mask;         /* [B,N] f32                                                                                   */
+  const float* res_mask;             /* [B,N] f32                                                                                   */
+  const float* align_mask;           /* [B,N] f32                                                                                   */
+  const int32_t* chain_idx;          /* [B,N] i32                                                                                   */
+  const int32_t* region_start;       /* [B+1] i32, ascending from 0: sample b owns regions region_start[b] .. region_start[b+1] - 1 */
+  const int32_t* region_rows;        /* [n_regions,2] i32: first and last row of every region                                       */
+  const int32_t* ref_index_host;     /* HOST copy of ref_index: the entry validates it                                              */
+  const int32_t* region_start_host;  /* HOST copy of region_start                                                                   */
+  /* outputs */
+  double* res_bb_rmsd;               /* [B,N] f64: sqrt(mean over the 4 atoms of |d|^2) at diffused rows, 0 elsewhere               */
+  double* region_bb_rmsd;            /* [B,max_regions] f64: sqrt(sum |d|^2 / atoms) per region, entries past a sample's own untouched */
+  double* bb_rmsd;                   /* [B] f64: the same over all regions                                                          */
+  double* dihedral;                  /* [B,3,N] f64: phi, psi, omega of the samples in degrees                                      */
+  double* gt_dihedral;               /* [R,3,N] f64: of the ground truth, with the chains of the first sample that names the row    */
+  double* angle_error;               /* [B,3,N] f64: signed error ground truth - sample (residue_signed_angle_error :1088)            */
+  double* ca_ca_bond_dev;            /* [B] f64: mean |d - 3.80209737096| over consecutive kept CA; NaN without a bond              */
+  double* ca_ca_valid_percent;       /* [B] f64: fraction of those d < 3.80209737096 + 0.1                                          */
+  int32_t* num_ca_steric_clashes;    /* [B] i32                                                                                     */
+  double* ca_steric_clash_percent;   /* [B] f64: clashes / pairs at distance > 0; NaN without such a pair                           */
+  double* aligned_mean_dev;          /* [B] f64: MEAN of the per-atom distances after the superposition (calc_aligned_rmsd's number) */
+  double* aligned_rmsd;              /* [B] f64: their root mean square                                                             */
+  double* rotation;                  /* [B,3,3] f64                                                                                 */
+  double* translation;               /* [B,3] f64                                                                                   */
+  int32_t* reflection;               /* [B] i32: rigid_transform_3D's reflection_detected (det of the covariance < 0)               */
+  int32_t* status;                   /* [B] i32: FDIPT_EVAL_* bits                                                                  */
+  int32_t* n_diffused;               /* [B] i32: diffused rows as the kernel counted them                                           */
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptEvalArgs;
+size_t fdipt_eval_workspace_bytes(int B, int N);
+/* FDIPT_EINVAL: a null pointer, R = 0, a ref_index out of range, a region_start that does not ascend from 0 to n_regions or gives a
+ * sample more than max_regions regions.  FDIPT_ESIZE: workspace too small. */
+int fdipt_sample_evaluate(const FdiptEvalArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */
 int fdipt_quat_to_rot(int n, const float* quat, float* rot, fdipt_stream_t s);           /* :185 */
