@@ -196,92 +196,67 @@ __device__ __forceinline__ void d_backbone_atom(int at, int aa, float s, float c
 // residue, the same summation order in every block), then takes rpb residues through the float64 SO(3) exp / log chain (a
 // long dependent sequence: one residue per lane, as many waves on as many CUs as the batch allows).  In-place updates
 // (rigids_out == rigids_t) need the whole sample in one block: rpb = N.
-struct ReverseArgs {
-  int B, N;
-  const float* rigids_t;
-  const double* rot_score;
-  const float* trans_score;
-  const float* diffuse_mask;
-  const double *z_rot, *z_trans;
-  double t, dt, noise_scale;
-  int center, diffuse_rot, diffuse_trans;
-  double so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, cs;
-  float* rigids_out;
-  float* out_rot;
-  int rpb;  // residues per block in the second pass
-  const float* psi;  // optional compute_backbone of x_{t-1} (atom37 != nullptr)
-  const int32_t* aatype;
-  const BackboneTables* tables;
-  float* atom37;
+struct ReverseArgs {  // filled by name (the exported entries below); what an entry does not have stays NULL / 0
+  int B = 0, N = 0;
+  const float* rigids_t = nullptr;
+  const double* rot_score = nullptr;
+  const float* trans_score = nullptr;
+  const float* diffuse_mask = nullptr;
+  const double *z_rot = nullptr, *z_trans = nullptr;
+  double t = 0, dt = 0, noise_scale = 0;
+  int center = 0, diffuse_rot = 0, diffuse_trans = 0;
+  double so3_min_sigma = 0, so3_max_sigma = 0, r3_min_b = 0, r3_max_b = 0, cs = 0;
+  float* rigids_out = nullptr;
+  float* out_rot = nullptr;
+  int rpb = 0;  // residues per block in the second pass (reverse_launch sets it)
+  const float* psi = nullptr;  // optional compute_backbone of x_{t-1} (atom37 != nullptr)
+  const int32_t* aatype = nullptr;
+  const BackboneTables* tables = nullptr;
+  float* atom37 = nullptr;
   // optional trans_traj row of the trajectory (experiments/utils.py:390-400): diffuse_mask * trans(x_0 prediction) + fixed * trans(x_{t-1})
-  const float* pred_rigids;   // [B,N,7] x_0 prediction of this step's forward
-  const float* traj_fixed;    // [B,N] fixed_mask * res_mask
-  float* trans_traj;          // [B,N,3]
-  // optional step cursor (fdipt_se3_reverse_step_indexed): rigids_t / z_* / atom37 / trans_traj are then bases of step-major arrays,
-  // the step's time is t_table[*cursor], x_{t-1} goes to the row behind x_t, and the last block to finish advances the cursor
-  int32_t* cursor = nullptr;       // [2]: step index, ticket of finished blocks
+  const float* pred_rigids = nullptr;   // [B,N,7] x_0 prediction of this step's forward
+  const float* traj_fixed = nullptr;    // [B,N] fixed_mask * res_mask
+  float* trans_traj = nullptr;          // [B,N,3]
+  // optional step cursor (fdipt_se3_reverse_step_indexed; kernels.hpp: FdStep): rigids_t / rigids_out / z_* / atom37 / trans_traj /
+  // kept_rigids are then bases of per-step arrays whose rows fd_step_rows picks, the step's time is t_table[k], and the last block to
+  // finish advances the cursor.  A step that keeps no frame (row -1) builds no backbone and writes no trans_traj / kept_rigids row.
+  FdStep step;
   const double* t_table = nullptr;
+  float* kept_rigids = nullptr;  // [rows,B,N,7] copy of x_{t-1} in the frame's row
+  // GEN (the *_gen entries, noise="device"): z_rot / z_trans are NULL and every value is drawn in the kernel from the sample's key
+  // (philox.hpp: a function of key, purpose, step, residue index within the sample and component only); the step is the cursor's, or
+  // noise_step without a cursor
+  const uint64_t* noise_keys = nullptr;  // [B]
+  int noise_step = 0;
 };
 
-// GEN (the *_gen entries, noise="device"): z_rot / z_trans are NULL and every value is drawn here from the sample's key (philox.hpp:
-// a function of key, purpose, step, residue index within the sample and component only).  Both passes need z_trans and both draw it:
-// N / rpb times the Philox work of one pass, a few dozen integer operations per residue, against a buffer or a launch of its own.
-// Without GEN the body is the tape kernel as it was.
-struct NoiseKeys { const uint64_t* keys; int step; };
-// KEEP (FdiptReverseIndexed.frame_rows / state_ring, the *_kept kernels): the rows of prot_traj / trans_traj / kept_rigids come from the
-// row map at the cursor (-1: this step keeps no frame — no backbone construction, no trans_traj row; uniform over the launch), and with
-// `ring` the state is a two-row ping-pong: x_t = row k & 1, x_{t-1} = row (k + 1) & 1.  Without KEEP the instantiations are the kernels as
-// they were (same instructions: tools/isa_cmp_kernels.py).
-struct KeptRows { const int32_t* frame_rows; float* kept_rigids; int ring; };
-template <typename T, typename... G>  // the argument of type T among the ride-along arguments
-__device__ __forceinline__ T fd_arg_of(T first, G...) { return first; }
-template <typename T, typename U, typename... G, typename = std::enable_if_t<!std::is_same_v<T, U>>>
-__device__ __forceinline__ T fd_arg_of(U, G... rest) { return fd_arg_of<T>(rest...); }
-template <bool GEN, bool KEEP, typename... G>  // G = KeptRows with KEEP, then NoiseKeys with GEN: the tape kernel keeps its argument block
-__global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a, G... gs) {
-  static_assert(sizeof...(G) == (GEN ? 1 : 0) + (KEEP ? 1 : 0), "noise keys ride along with GEN only, the row map with KEEP only");
+// GEN: both passes need z_trans and both draw it: N / rpb times the Philox work of one pass, a few dozen integer operations per residue,
+// against a buffer or a launch of its own.  KEPT is nothing but the argument of fd_step_rows (kernels.hpp).  Measured on one MI355X against
+// the commit before the resolver (c4 bench, medians of three interleaved runs, us per call): <false, false> 24.25 against 26.31 on a lease
+// that spread the parent over 5 us; with the addressing decided at run time 26.46 against 26.00 (allowed 26.31).  DESIGN.md section 7.2.
+template <bool GEN, bool KEPT>
+__global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a) {
   __shared__ double red[4][FD_THREADS / 64];
   __shared__ double com[4];
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int N = a.N;
-  uint64_t key = 0;
-  int step = 0;
-  if constexpr (GEN) {
-    const NoiseKeys g = fd_arg_of<NoiseKeys>(gs...);
-    key = g.keys[b];
-    step = a.cursor ? a.cursor[0] : g.step;
+  const FdStepRows at = fd_step_rows<KEPT>(a.step);
+  const long R = (long)a.B * N;
+  const uint64_t key = GEN ? a.noise_keys[b] : 0;
+  const int step = a.step.cursor ? (int)at.step : a.noise_step;
+  a.rigids_t += at.state_in * R * 7;
+  a.rigids_out += at.state_out * R * 7;
+  if (!GEN) {
+    a.z_rot += at.step * R * 3;
+    a.z_trans += at.step * R * 3;
   }
-  [[maybe_unused]] float* kept_out = nullptr;  // (KEEP) this step's row of kept_rigids
-  if constexpr (KEEP) {
-    const KeptRows kr = fd_arg_of<KeptRows>(gs...);
-    const long s = a.cursor[0], R = (long)a.B * N;  // (the kept entries always carry a cursor)
-    const long row = kr.frame_rows ? (long)kr.frame_rows[s] : s;
-    a.rigids_t += (kr.ring ? (s & 1) : s) * R * 7;
-    a.rigids_out += (kr.ring ? ((s + 1) & 1) : s + 1) * R * 7;
-    if (!GEN) {
-      a.z_rot += s * R * 3;
-      a.z_trans += s * R * 3;
-    }
-    a.t = a.t_table[s];
-    if (row < 0) {
-      a.atom37 = nullptr;
-      a.trans_traj = nullptr;
-    } else {
-      if (a.atom37) a.atom37 += row * R * 111;
-      if (a.trans_traj) a.trans_traj += row * R * 3;
-      if (kr.kept_rigids) kept_out = kr.kept_rigids + row * R * 7;
-    }
-  } else if (a.cursor) {
-    const long s = a.cursor[0], R = (long)a.B * N;
-    a.rigids_t += s * R * 7;
-    a.rigids_out += (s + 1) * R * 7;
-    if (!GEN) {
-      a.z_rot += s * R * 3;
-      a.z_trans += s * R * 3;
-    }
-    a.t = a.t_table[s];
-    if (a.atom37) a.atom37 += s * R * 111;
-    if (a.trans_traj) a.trans_traj += s * R * 3;
+  if (a.step.cursor) a.t = a.t_table[at.step];
+  if (at.frame < 0) {
+    a.atom37 = a.trans_traj = a.kept_rigids = nullptr;
+  } else {
+    if (a.atom37) a.atom37 += at.frame * R * 111;
+    if (a.trans_traj) a.trans_traj += at.frame * R * 3;
+    if (a.kept_rigids) a.kept_rigids += at.frame * R * 7;
   }
   // schedules: so3_diffuser.py:299-319, r3_diffuser.py:48-85
   const double emax = exp(a.so3_max_sigma), emin = exp(a.so3_min_sigma);
@@ -401,10 +376,8 @@ __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a,
     float* o = a.rigids_out + r * 7;
     fd_st(o, (float)q[3]); fd_st(o + 1, (float)q[0]); fd_st(o + 2, (float)q[1]); fd_st(o + 3, (float)q[2]);
     fd_st(o + 4, (float)tr_out[0]); fd_st(o + 5, (float)tr_out[1]); fd_st(o + 6, (float)tr_out[2]);
-    if constexpr (KEEP) {
-      if (kept_out)
-        for (int c = 0; c < 7; ++c) fd_st(kept_out + r * 7 + c, o[c]);
-    }
+    if (a.kept_rigids)
+      for (int c = 0; c < 7; ++c) fd_st(a.kept_rigids + r * 7 + c, o[c]);
     if (a.atom37) {
       const float tf[3] = {o[4], o[5], o[6]};
       d_backbone_residue(r, Rf, tf, a.psi, a.aatype, a.tables, a.atom37, nullptr);
@@ -414,15 +387,16 @@ __global__ __launch_bounds__(FD_THREADS) void reverse_step_kernel(ReverseArgs a,
       for (int c = 0; c < 3; ++c) fd_st(a.trans_traj + r * 3 + c, dm * a.pred_rigids[r * 7 + 4 + c] + fm * o[4 + c]);
     }
   }
-  if (a.cursor) {
+  if (a.step.cursor) {
     // every block read the cursor before any block can get here; the last one to arrive moves it to the next step (the launches of
-    // that step are ordered behind this kernel by the stream / graph)
+    // that step are ordered behind this kernel by the stream / graph).  This is the one launch that writes the cursor.
     __syncthreads();
     if (tid == 0) {
+      int32_t* cursor = const_cast<int32_t*>(a.step.cursor);
       const int n_blocks = (int)(gridDim.x * gridDim.y);
-      if (atomicAdd(a.cursor + 1, 1) == n_blocks - 1) {
-        a.cursor[1] = 0;
-        atomicAdd(a.cursor, 1);
+      if (atomicAdd(cursor + 1, 1) == n_blocks - 1) {
+        cursor[1] = 0;
+        atomicAdd(cursor, 1);
       }
     }
   }
@@ -473,40 +447,25 @@ struct ScoreTail {
   // optional backbone atoms of the finished frames (all_atom.compute_backbone; replaces a backbone_kernel launch): the residue's 16
   // lanes take one atom14 atom each
   const int32_t* aatype = nullptr; const BackboneTables* tables = nullptr; float *atom37 = nullptr, *atom14 = nullptr;
-  // optional step cursor (FdiptForwardArgs.step_cursor): x_t (tensor_7), sigma, t, the score-table rows and atom37 are then bases of
-  // step-major arrays, read / written at row *cursor
-  const int32_t* cursor = nullptr;
+  // optional step cursor (FdiptForwardArgs.step_cursor / frame_rows / state_ring; kernels.hpp: FdStep): x_t (tensor_7), sigma, t, the
+  // score-table rows and atom37 are then bases of per-step arrays: sigma / t / the table at row k, x_t at the state row, atom37 at the
+  // frame's row — or no backbone atoms at all on a step that keeps no frame
+  FdStep step = {};
 };
-// KEPT (FdiptForwardArgs.frame_rows / state_ring, rot_score_kept_kernel): x_t is row k & 1 of the two-row state with `ring`, and the atom37
-// row is frame_rows[k] — or none (-1: the backbone atoms are not built at all on this step).  Without KEPT the kernel is as it was.
-template <bool KEPT, typename... K>  // K = FdKept with KEPT, nothing without
+template <bool KEPT>  // (the argument of fd_step_rows, nothing else)
 __global__ __launch_bounds__(FD_THREADS) void rot_score_kernel(int B, int N, const float* __restrict__ quats_t_, int ld_t,
                                                                const float* __restrict__ quats_0, int ld_0,
                                                                const double* __restrict__ sigma_,
                                                                const float* __restrict__ res_mask,
-                                                               double* __restrict__ score, ScoreTail x, K... ks) {
-  static_assert(sizeof...(K) == (KEPT ? 1 : 0), "the row map rides along with KEPT only");
+                                                               double* __restrict__ score, ScoreTail x) {
   __shared__ double wtab[2][RS_L];
-  const float* __restrict__ quats_t = quats_t_;
-  const double* __restrict__ sigma = sigma_;
-  if constexpr (KEPT) {
-    const FdKept kp = (ks, ...);
-    const long s = x.cursor[0];  // (the kept launch always carries a cursor)
-    const long row = kp.frame_rows ? (long)kp.frame_rows[s] : s;
-    quats_t += (kp.ring ? (s & 1) : s) * B * N * ld_t;
-    sigma += s * B;
-    x.t += s * B;
-    if (x.score_table) x.score_table += s * B * x.n_omega;
-    if (row < 0) x.atom37 = x.atom14 = nullptr;
-    else if (x.atom37) x.atom37 += row * B * N * 111;
-  } else if (x.cursor) {
-    const long s = x.cursor[0];
-    quats_t += s * B * N * ld_t;
-    sigma += s * B;
-    x.t += s * B;
-    if (x.score_table) x.score_table += s * B * x.n_omega;
-    if (x.atom37) x.atom37 += s * B * N * 111;
-  }
+  const FdStepRows at = fd_step_rows<KEPT>(x.step);
+  const float* __restrict__ quats_t = quats_t_ + at.state_in * B * N * ld_t;
+  const double* __restrict__ sigma = sigma_ + at.step * B;
+  x.t += at.step * B;
+  if (x.score_table) x.score_table += at.step * B * x.n_omega;
+  if (at.frame < 0) x.atom37 = x.atom14 = nullptr;
+  else if (x.atom37) x.atom37 += at.frame * B * N * 111;
   constexpr int RPB = FD_THREADS / RS_LANES;  // residues per block
   const long total = (long)B * N;
   const long r_first = (long)blockIdx.x * RPB;
@@ -654,13 +613,17 @@ __global__ void trans_score_kernel(int B, int N, const float* __restrict__ trans
 
 // ------------------------------------------------------------------ backbone atoms
 // all_atom.py:147-176 -> openfold/utils/feats.py:165-228 -> all_atom.py:108-144.  One thread per residue.
+// With a step cursor atom37_ is the base of a per-step array and the frames go to the step's frame row (kernels.hpp: FdStep) — nowhere on
+// a step that keeps no frame.
 __global__ void backbone_kernel(int n, const float* __restrict__ t7, const float* __restrict__ rot,
                                 const float* __restrict__ trans, int ld_trans, const float* __restrict__ psi,
                                 const int32_t* __restrict__ aatype, const BackboneTables* __restrict__ tb,
-                                float* __restrict__ atom37_, float* __restrict__ atom14, const int32_t* __restrict__ cursor) {
+                                float* __restrict__ atom37_, float* __restrict__ atom14, FdStep step) {
   const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
-  float* __restrict__ atom37 = (cursor && atom37_) ? atom37_ + (long)cursor[0] * n * 111 : atom37_;  // (step cursor: row *cursor)
+  const long row = fd_step_rows(step).frame;
+  if (row < 0) return;
+  float* __restrict__ atom37 = atom37_ ? atom37_ + row * n * 111 : atom37_;
   float Rb[9], tbv[3];
   if (rot) {
     for (int c = 0; c < 9; ++c) Rb[c] = rot[r * 9 + c];
@@ -670,20 +633,6 @@ __global__ void backbone_kernel(int n, const float* __restrict__ t7, const float
     for (int c = 0; c < 3; ++c) tbv[c] = t7[r * 7 + 4 + c];
   }
   d_backbone_residue(r, Rb, tbv, psi, aatype, tb, atom37, atom14);
-}
-// ... of a kept-frame loop (fdipt_backbone_atoms_kept): tensor_7 frames into row frame_rows[*cursor] of atom37_rows; a step whose row is -1
-// builds nothing (uniform over the launch)
-__global__ void backbone_kept_kernel(int n, const float* __restrict__ t7, const float* __restrict__ psi, const int32_t* __restrict__ aatype,
-                                     const BackboneTables* __restrict__ tb, float* __restrict__ atom37_rows,
-                                     const int32_t* __restrict__ cursor, const int32_t* __restrict__ frame_rows) {
-  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const long row = frame_rows[cursor[0]];
-  if (row < 0) return;
-  float Rb[9], tbv[3];
-  d_quat_to_rot(t7 + r * 7, Rb);
-  for (int c = 0; c < 3; ++c) tbv[c] = t7[r * 7 + 4 + c];
-  d_backbone_residue(r, Rb, tbv, psi, aatype, tb, atom37_rows + row * n * 111, nullptr);
 }
 
 // ------------------------------------------------------------------ small per-residue kernels of the trunk
@@ -713,27 +662,19 @@ int fd_compose_q_update(long n, float* quat, float* trans, const float* upd, int
 }
 
 // IpaScore.forward prologue (ipa_pytorch.py:516-524): split tensor_7, scale translations; diffuse_mask = (1-fixed)*res.
-template <bool RING>  // RING (FdiptForwardArgs.state_ring): x_t is row *cursor & 1 of a two-row state instead of row *cursor
 __global__ void split_rigids_kernel(long n, const float* __restrict__ t7_, float cs, const float* __restrict__ res_mask,
                                     const float* __restrict__ fixed_mask, float* __restrict__ quat,
-                                    float* __restrict__ trans, float* __restrict__ diffuse_mask, const int32_t* __restrict__ cursor) {
+                                    float* __restrict__ trans, float* __restrict__ diffuse_mask, FdStep step) {
   const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
-  const float* __restrict__ t7 = cursor ? t7_ + (long)(RING ? cursor[0] & 1 : cursor[0]) * n * 7 : t7_;  // (step cursor: row *cursor of a step-major array)
+  const float* __restrict__ t7 = t7_ + fd_step_rows(step).state_in * n * 7;  // (step cursor: the state row of x_t)
   for (int c = 0; c < 4; ++c) quat[r * 4 + c] = t7[r * 7 + c];
   for (int c = 0; c < 3; ++c) fd_st(trans + r * 3 + c, t7[r * 7 + 4 + c] * cs);
   diffuse_mask[r] = (1.f - fixed_mask[r]) * res_mask[r];
 }
 int fd_split_rigids(long n, const float* t7, float cs, const float* res_mask, const float* fixed_mask, float* quat,
-                    float* trans, float* dmask, const int32_t* cursor, hipStream_t st, FdKept kept) {
-  if (cursor && kept.ring) {
-    hipLaunchKernelGGL(split_rigids_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, st, n, t7, cs, res_mask, fixed_mask, quat, trans,
-                       dmask, cursor);
-    FD_CHECK_LAUNCH();
-    return FDIPT_OK;
-  }
-  hipLaunchKernelGGL(split_rigids_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, st, n, t7, cs, res_mask, fixed_mask, quat, trans,
-                     dmask, cursor);
+                    float* trans, float* dmask, FdStep step, hipStream_t st) {
+  hipLaunchKernelGGL(split_rigids_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, n, t7, cs, res_mask, fixed_mask, quat, trans, dmask, step);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -767,21 +708,18 @@ int fd_finish(long n, const float* quat, const float* trans, float cs, const flo
 struct FeatsExtra {  // optional work folded into the feature kernel's launch (nullptr to skip each part)
   const float *t7, *res_mask; float cs; float *quat, *trans, *dmask;  // split of x_t into quaternion / scaled translation
   const float *w1i, *w1j, *b1; int cz; float *pi, *pj;              // per-residue halves of the first edge-embedder layer
-  const int32_t* cursor;  // optional step cursor: t_emb and t7 are bases of step-major arrays, read at row *cursor
+  FdStep step;  // optional step cursor: t_emb and t7 are bases of per-step arrays, read at row k / the state row of x_t
 };
-template <bool RING>  // RING (FdiptForwardArgs.state_ring): x_t is row *cursor & 1 of a two-row state instead of row *cursor
+template <bool KEPT>  // (the argument of fd_step_rows, nothing else)
 __global__ void build_feats_kernel(int B, int N, int use_aatype, int E, const int32_t* __restrict__ aatype,
                                    const float* __restrict__ t_emb_, const float* __restrict__ t_emb_eps,
                                    const float* __restrict__ fixed_mask, const float* __restrict__ idx_emb,
                                    float* __restrict__ node_feat, int ld_node, float* __restrict__ pte, int ld_pte,
                                    FeatsExtra x) {
   __shared__ float pte_s[128];
-  const float* __restrict__ t_emb = t_emb_;
-  if (x.cursor) {
-    const long s = x.cursor[0];
-    t_emb += s * B * E;
-    if (x.t7) x.t7 += (RING ? (s & 1) : s) * B * N * 7;
-  }
+  const FdStepRows at = fd_step_rows<KEPT>(x.step);
+  const float* __restrict__ t_emb = t_emb_ + at.step * B * E;
+  if (x.t7) x.t7 += at.state_in * B * N * 7;
   const long r = blockIdx.x;
   const int b = (int)(r / N);
   const float fm = fixed_mask[r];
@@ -830,18 +768,12 @@ __global__ void build_feats_kernel(int B, int N, int use_aatype, int E, const in
 int fd_build_feats(int B, int N, int use_aatype, int E, const int32_t* aatype, const float* t_emb, const float* t_emb_eps,
                    const float* fixed_mask, const float* idx_emb, float* node_feat, int ld_node, float* pte, int ld_pte,
                    const float* t7, const float* res_mask, float cs, float* quat, float* trans, float* dmask, const float* w1i,
-                   const float* w1j, const float* b1, int cz, float* pi, float* pj, const int32_t* cursor, hipStream_t st,
-                   FdKept kept) {
+                   const float* w1j, const float* b1, int cz, float* pi, float* pj, FdStep step, hipStream_t st) {
   if (use_aatype && (!aatype || !t_emb_eps)) return FDIPT_EINVAL;
   if (pi && (ld_pte > 128 || (ld_pte & 3))) return FDIPT_EINVAL;
-  FeatsExtra x = {t7, res_mask, cs, quat, trans, dmask, w1i, w1j, b1, cz, pi, pj, cursor};
-  if (cursor && kept.ring) {
-    hipLaunchKernelGGL(build_feats_kernel<true>, dim3(B * N), dim3(128), 0, st, B, N, use_aatype, E, aatype, t_emb, t_emb_eps,
-                       fixed_mask, idx_emb, node_feat, ld_node, pte, ld_pte, x);
-    FD_CHECK_LAUNCH();
-    return FDIPT_OK;
-  }
-  hipLaunchKernelGGL(build_feats_kernel<false>, dim3(B * N), dim3(128), 0, st, B, N, use_aatype, E, aatype, t_emb, t_emb_eps,
+  FeatsExtra x = {t7, res_mask, cs, quat, trans, dmask, w1i, w1j, b1, cz, pi, pj, step};
+  const auto kernel = step.kept() ? build_feats_kernel<true> : build_feats_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(B * N), dim3(128), 0, st, B, N, use_aatype, E, aatype, t_emb, t_emb_eps,
                      fixed_mask, idx_emb, node_feat, ld_node, pte, ld_pte, x);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
@@ -861,20 +793,15 @@ int fd_score_tail(int B, int N, const float* rigids_t, const float* quat, const 
                   const float* t, float min_b, float max_b, float* rigids, float* psi, double* rot_score, float* trans_score,
                   float* ca_out, const float* hid, int ld_hid, int c_hid, const float* torf_w, const float* torf_b,
                   const double* score_table, const double* omega_edges, int n_omega, const int32_t* aatype, const void* bb_tables,
-                  float* atom37, float* atom14, const int32_t* cursor, hipStream_t st, FdKept kept) {
+                  float* atom37, float* atom14, FdStep step, hipStream_t st) {
   if (hid && ((c_hid & 3) || (ld_hid & 3))) return FDIPT_EINVAL;
   if (score_table && (!omega_edges || n_omega < 2)) return FDIPT_EINVAL;
   if ((atom37 || atom14) && !bb_tables) return FDIPT_EINVAL;
   ScoreTail x = {trans, cs, psi_un, ld_psi, gt_psi, fixed_mask, t, min_b, max_b, rigids, psi, trans_score, ca_out,
                  hid, torf_w, torf_b, ld_hid, c_hid, score_table, omega_edges, n_omega, aatype, (const BackboneTables*)bb_tables, atom37, atom14,
-                 cursor};
-  if (cursor && kept.on()) {
-    hipLaunchKernelGGL((rot_score_kernel<true, FdKept>), dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, st, B, N, rigids_t, 7,
-                       quat, 4, sigma, res_mask, rot_score, x, kept);
-    FD_CHECK_LAUNCH();
-    return FDIPT_OK;
-  }
-  hipLaunchKernelGGL(rot_score_kernel<false>, dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, st, B, N, rigids_t, 7,
+                 step};
+  const auto kernel = step.kept() ? rot_score_kernel<true> : rot_score_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(cdiv((long)B * N, FD_THREADS / RS_LANES)), dim3(FD_THREADS), 0, st, B, N, rigids_t, 7,
                      quat, 4, sigma, res_mask, rot_score, x);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
@@ -887,17 +814,12 @@ int fd_trans_score(int B, int N, const float* tt, int ld_t, const float* t0, int
   return FDIPT_OK;
 }
 int fd_backbone(int n, const float* t7, const float* rot, const float* trans, int ld_trans, const float* psi,
-                const int32_t* aatype, const void* tables, float* atom37, float* atom14, hipStream_t st, const int32_t* cursor,
-                const int32_t* frame_rows) {
-  if (cursor && frame_rows) {  // kept-frame loop: tensor_7 frames into row frame_rows[*cursor] of atom37, nothing on a step that keeps none
-    if (!t7 || !atom37 || atom14) return FDIPT_EINVAL;
-    hipLaunchKernelGGL(backbone_kept_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, n, t7, psi, aatype, (const BackboneTables*)tables, atom37,
-                       cursor, frame_rows);
-    FD_CHECK_LAUNCH();
-    return FDIPT_OK;
-  }
+                const int32_t* aatype, const void* tables, float* atom37, float* atom14, hipStream_t st, FdStep step) {
+  // kept-frame loop: tensor_7 frames into the map's row of atom37 and nothing else (a step that keeps no frame builds nothing).  rot is
+  // refused on purpose: the former kept kernel had no such input, the merged one would read it (no caller passes it).
+  if (step.frame_rows && (!t7 || rot || !atom37 || atom14)) return FDIPT_EINVAL;
   hipLaunchKernelGGL(backbone_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, n, t7, rot, trans, ld_trans, psi, aatype,
-                     (const BackboneTables*)tables, atom37, atom14, cursor);
+                     (const BackboneTables*)tables, atom37, atom14, step);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1045,6 +967,64 @@ __global__ void cqu_t7_k(int n, const float* __restrict__ t7, const float* __res
   for (int c = 0; c < 3; ++c) out[r * 7 + 4 + c] = q[4 + c] + dt[c] * m;
 }
 
+// ------------------------------------------------------------------ the reverse step's one launcher
+// Validation, block size and launch for every exported reverse-step entry; the entries below only marshal their arguments onto it.
+// gen: the noise comes from keys (tape pointers must be NULL), otherwise from the tape.  indexed: the cursor entries (rigids_t ==
+// rigids_out == the state's base; the time comes from t_table).
+static int reverse_launch(ReverseArgs a, bool gen, bool indexed, hipStream_t st) {
+  if (a.B <= 0 || a.N <= 0) return FDIPT_OK;
+  if (!a.rigids_t || !a.rot_score || !a.trans_score || !a.rigids_out) return FDIPT_EINVAL;
+  if (gen ? (!a.noise_keys || a.noise_step < 0 || a.z_rot || a.z_trans) : (!a.z_rot || !a.z_trans)) return FDIPT_EINVAL;
+  if (indexed ? (!a.step.cursor || !a.t_table) : !(a.t >= 0 && a.t <= 1)) return FDIPT_EINVAL;
+  if (a.atom37 && (!a.psi || !a.tables || (!indexed && a.rigids_out == a.rigids_t))) return FDIPT_EINVAL;
+  if (a.trans_traj && (!a.pred_rigids || !a.traj_fixed)) return FDIPT_EINVAL;
+  if (!a.step.valid() || (a.kept_rigids && !a.step.frame_rows)) return FDIPT_EINVAL;
+  a.rpb = !indexed && a.rigids_out == a.rigids_t ? a.N : 64;  // in place: the whole sample in one block
+  const dim3 grid(cdiv(a.N, a.rpb), a.B);
+  const bool kept = a.step.kept();
+  const auto kernel = gen ? (kept ? reverse_step_kernel<true, true> : reverse_step_kernel<true, false>)
+                          : (kept ? reverse_step_kernel<false, true> : reverse_step_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(FD_THREADS), 0, st, a);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+// the entries that take their arguments one by one (fdipt_se3_reverse_step, _atoms, _traj, _traj_gen)
+static int reverse_flat(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score, const float* diffuse_mask,
+                        const double* z_rot, const double* z_trans, const uint64_t* noise_keys, int noise_step, double t, double dt,
+                        double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma, double so3_max_sigma,
+                        double r3_min_b, double r3_max_b, double coordinate_scaling, float* rigids_out, float* out_rot, const float* psi,
+                        const int32_t* aatype, const void* tables, float* atom37, const float* pred_rigids, const float* traj_fixed_mask,
+                        float* trans_traj, bool gen, fdipt_stream_t stream) {
+  ReverseArgs a;
+  a.B = B; a.N = N;
+  a.rigids_t = rigids_t; a.rot_score = rot_score; a.trans_score = trans_score; a.diffuse_mask = diffuse_mask;
+  a.z_rot = z_rot; a.z_trans = z_trans; a.noise_keys = noise_keys; a.noise_step = noise_step;
+  a.t = t; a.dt = dt; a.noise_scale = noise_scale;
+  a.center = center; a.diffuse_rot = diffuse_rot; a.diffuse_trans = diffuse_trans;
+  a.so3_min_sigma = so3_min_sigma; a.so3_max_sigma = so3_max_sigma; a.r3_min_b = r3_min_b; a.r3_max_b = r3_max_b; a.cs = coordinate_scaling;
+  a.rigids_out = rigids_out; a.out_rot = out_rot;
+  a.psi = psi; a.aatype = aatype; a.tables = (const BackboneTables*)tables; a.atom37 = atom37;
+  a.pred_rigids = pred_rigids; a.traj_fixed = traj_fixed_mask; a.trans_traj = trans_traj;
+  return reverse_launch(a, gen, false, (hipStream_t)stream);
+}
+// the cursor entries (fdipt_se3_reverse_step_indexed, _indexed_gen): noise_keys is the _gen entry's, whose x carries no tape
+static int reverse_indexed(const FdiptReverseIndexed* x, const uint64_t* noise_keys, bool gen, fdipt_stream_t stream) {
+  if (!x) return FDIPT_EINVAL;
+  ReverseArgs a;
+  a.B = x->B; a.N = x->N;
+  a.rigids_t = a.rigids_out = x->rigid_traj; a.rot_score = x->rot_score; a.trans_score = x->trans_score; a.diffuse_mask = x->diffuse_mask;
+  a.z_rot = x->z_rot; a.z_trans = x->z_trans; a.noise_keys = noise_keys;
+  a.dt = x->dt; a.noise_scale = x->noise_scale;
+  a.center = x->center; a.diffuse_rot = x->diffuse_rot; a.diffuse_trans = x->diffuse_trans;
+  a.so3_min_sigma = x->so3_min_sigma; a.so3_max_sigma = x->so3_max_sigma; a.r3_min_b = x->r3_min_b; a.r3_max_b = x->r3_max_b;
+  a.cs = x->coordinate_scaling;
+  a.psi = x->psi; a.aatype = x->aatype; a.tables = (const BackboneTables*)x->bb_tables; a.atom37 = x->prot_traj;
+  a.pred_rigids = x->pred_rigids; a.traj_fixed = x->traj_fixed_mask; a.trans_traj = x->trans_traj;
+  a.step = FdStep{x->step_cursor, x->frame_rows, x->state_ring};
+  a.t_table = x->t_table; a.kept_rigids = x->kept_rigids;
+  return reverse_launch(a, gen, true, (hipStream_t)stream);
+}
+
 #define FD_EW_EXPORT(name, X, Y, O, O2)                                                        \
   if (n <= 0) return FDIPT_OK;                                                                 \
   if (!(X) || !(O)) return FDIPT_EINVAL;                                                       \
@@ -1116,24 +1096,6 @@ int fdipt_so3_log(int n, const double* rot, double* rotvec, fdipt_stream_t s) {
   return FDIPT_OK;
 }
 
-int fdipt_se3_reverse_step_atoms(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score,
-                                 const float* diffuse_mask, const double* z_rot, const double* z_trans, double t, double dt,
-                                 double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma,
-                                 double so3_max_sigma, double r3_min_b, double r3_max_b, double coordinate_scaling,
-                                 float* rigids_out, float* out_rot, const float* psi, const int32_t* aatype,
-                                 const void* tables, float* atom37, fdipt_stream_t stream) {
-  if (B <= 0 || N <= 0) return FDIPT_OK;
-  if (!rigids_t || !rot_score || !trans_score || !z_rot || !z_trans || !rigids_out || !(t >= 0 && t <= 1))
-    return FDIPT_EINVAL;
-  if (atom37 && (!psi || !tables || rigids_out == rigids_t)) return FDIPT_EINVAL;
-  const int rpb = rigids_out == rigids_t ? N : 64;
-  ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale, center,
-                   diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
-                   rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL((reverse_step_kernel<false, false>), dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
-}
 int fdipt_se3_reverse_step_traj(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score,
                                 const float* diffuse_mask, const double* z_rot, const double* z_trans, double t, double dt,
                                 double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma,
@@ -1141,42 +1103,30 @@ int fdipt_se3_reverse_step_traj(int B, int N, const float* rigids_t, const doubl
                                 float* rigids_out, float* out_rot, const float* psi, const int32_t* aatype,
                                 const void* tables, float* atom37, const float* pred_rigids, const float* traj_fixed_mask,
                                 float* trans_traj, fdipt_stream_t stream) {
-  if (B <= 0 || N <= 0) return FDIPT_OK;
-  if (!rigids_t || !rot_score || !trans_score || !z_rot || !z_trans || !rigids_out || !(t >= 0 && t <= 1))
-    return FDIPT_EINVAL;
-  if (atom37 && (!psi || !tables || rigids_out == rigids_t)) return FDIPT_EINVAL;
-  if (trans_traj && (!pred_rigids || !traj_fixed_mask)) return FDIPT_EINVAL;
-  const int rpb = rigids_out == rigids_t ? N : 64;
-  ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale, center,
-                   diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
-                   rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, pred_rigids, traj_fixed_mask, trans_traj};
-  hipLaunchKernelGGL((reverse_step_kernel<false, false>), dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
+  return reverse_flat(B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, nullptr, 0, t, dt, noise_scale, center,
+                      diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling, rigids_out, out_rot,
+                      psi, aatype, tables, atom37, pred_rigids, traj_fixed_mask, trans_traj, false, stream);
 }
-int fdipt_se3_reverse_step_indexed(const FdiptReverseIndexed* x, fdipt_stream_t stream) {
-  if (!x) return FDIPT_EINVAL;
-  if (x->B <= 0 || x->N <= 0) return FDIPT_OK;
-  if (!x->rigid_traj || !x->rot_score || !x->trans_score || !x->z_rot || !x->z_trans || !x->t_table || !x->step_cursor) return FDIPT_EINVAL;
-  if (x->prot_traj && (!x->psi || !x->bb_tables)) return FDIPT_EINVAL;
-  if (x->trans_traj && (!x->pred_rigids || !x->traj_fixed_mask)) return FDIPT_EINVAL;
-  if ((x->state_ring & ~1) || (x->kept_rigids && !x->frame_rows)) return FDIPT_EINVAL;
-  ReverseArgs a = {x->B, x->N, x->rigid_traj, x->rot_score, x->trans_score, x->diffuse_mask, x->z_rot, x->z_trans, 0.0, x->dt,
-                   x->noise_scale, x->center, x->diffuse_rot, x->diffuse_trans, x->so3_min_sigma, x->so3_max_sigma, x->r3_min_b,
-                   x->r3_max_b, x->coordinate_scaling, x->rigid_traj, nullptr, 64, x->psi, x->aatype,
-                   (const BackboneTables*)x->bb_tables, x->prot_traj, x->pred_rigids, x->traj_fixed_mask, x->trans_traj,
-                   x->step_cursor, x->t_table};
-  if (x->frame_rows || x->state_ring) {  // kept frames / two-row state: the rows come from the map at the cursor
-    hipLaunchKernelGGL((reverse_step_kernel<false, true, KeptRows>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a,
-                       KeptRows{x->frame_rows, x->kept_rigids, x->state_ring});
-    FD_CHECK_LAUNCH();
-    return FDIPT_OK;
-  }
-  hipLaunchKernelGGL((reverse_step_kernel<false, false>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a);
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
+int fdipt_se3_reverse_step_atoms(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score,
+                                 const float* diffuse_mask, const double* z_rot, const double* z_trans, double t, double dt,
+                                 double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma,
+                                 double so3_max_sigma, double r3_min_b, double r3_max_b, double coordinate_scaling,
+                                 float* rigids_out, float* out_rot, const float* psi, const int32_t* aatype,
+                                 const void* tables, float* atom37, fdipt_stream_t stream) {
+  return reverse_flat(B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, nullptr, 0, t, dt, noise_scale, center,
+                      diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling, rigids_out, out_rot,
+                      psi, aatype, tables, atom37, nullptr, nullptr, nullptr, false, stream);
 }
-// noise="device": the same launches with the samples' noise keys in place of the tape rows (reverse_step_body<true>)
+int fdipt_se3_reverse_step(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score,
+                           const float* diffuse_mask, const double* z_rot, const double* z_trans, double t, double dt,
+                           double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma,
+                           double so3_max_sigma, double r3_min_b, double r3_max_b, double coordinate_scaling,
+                           float* rigids_out, float* out_rot, fdipt_stream_t stream) {
+  return reverse_flat(B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, nullptr, 0, t, dt, noise_scale, center,
+                      diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling, rigids_out, out_rot,
+                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, stream);
+}
+// noise="device": the same launches with the samples' noise keys in place of the tape rows (reverse_step_kernel<true, .>)
 int fdipt_se3_reverse_step_traj_gen(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score,
                                     const float* diffuse_mask, const uint64_t* noise_keys, int step, double t, double dt,
                                     double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma,
@@ -1184,41 +1134,15 @@ int fdipt_se3_reverse_step_traj_gen(int B, int N, const float* rigids_t, const d
                                     float* rigids_out, float* out_rot, const float* psi, const int32_t* aatype,
                                     const void* tables, float* atom37, const float* pred_rigids, const float* traj_fixed_mask,
                                     float* trans_traj, fdipt_stream_t stream) {
-  if (B <= 0 || N <= 0) return FDIPT_OK;
-  if (!rigids_t || !rot_score || !trans_score || !noise_keys || step < 0 || !rigids_out || !(t >= 0 && t <= 1))
-    return FDIPT_EINVAL;
-  if (atom37 && (!psi || !tables || rigids_out == rigids_t)) return FDIPT_EINVAL;
-  if (trans_traj && (!pred_rigids || !traj_fixed_mask)) return FDIPT_EINVAL;
-  const int rpb = rigids_out == rigids_t ? N : 64;
-  ReverseArgs a = {B, N, rigids_t, rot_score, trans_score, diffuse_mask, nullptr, nullptr, t, dt, noise_scale, center,
-                   diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling,
-                   rigids_out, out_rot, rpb, psi, aatype, (const BackboneTables*)tables, atom37, pred_rigids, traj_fixed_mask, trans_traj};
-  hipLaunchKernelGGL((reverse_step_kernel<true, false, NoiseKeys>), dim3(cdiv(N, rpb), B), dim3(FD_THREADS), 0, (hipStream_t)stream, a, NoiseKeys{noise_keys, step});
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
+  return reverse_flat(B, N, rigids_t, rot_score, trans_score, diffuse_mask, nullptr, nullptr, noise_keys, step, t, dt, noise_scale, center,
+                      diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b, coordinate_scaling, rigids_out, out_rot,
+                      psi, aatype, tables, atom37, pred_rigids, traj_fixed_mask, trans_traj, true, stream);
+}
+int fdipt_se3_reverse_step_indexed(const FdiptReverseIndexed* x, fdipt_stream_t stream) {
+  return reverse_indexed(x, nullptr, false, stream);
 }
 int fdipt_se3_reverse_step_indexed_gen(const FdiptReverseIndexed* x, const uint64_t* noise_keys, fdipt_stream_t stream) {
-  if (!x) return FDIPT_EINVAL;
-  if (x->B <= 0 || x->N <= 0) return FDIPT_OK;
-  if (!x->rigid_traj || !x->rot_score || !x->trans_score || x->z_rot || x->z_trans || !noise_keys || !x->t_table || !x->step_cursor)
-    return FDIPT_EINVAL;
-  if (x->prot_traj && (!x->psi || !x->bb_tables)) return FDIPT_EINVAL;
-  if (x->trans_traj && (!x->pred_rigids || !x->traj_fixed_mask)) return FDIPT_EINVAL;
-  if ((x->state_ring & ~1) || (x->kept_rigids && !x->frame_rows)) return FDIPT_EINVAL;
-  ReverseArgs a = {x->B, x->N, x->rigid_traj, x->rot_score, x->trans_score, x->diffuse_mask, nullptr, nullptr, 0.0, x->dt,
-                   x->noise_scale, x->center, x->diffuse_rot, x->diffuse_trans, x->so3_min_sigma, x->so3_max_sigma, x->r3_min_b,
-                   x->r3_max_b, x->coordinate_scaling, x->rigid_traj, nullptr, 64, x->psi, x->aatype,
-                   (const BackboneTables*)x->bb_tables, x->prot_traj, x->pred_rigids, x->traj_fixed_mask, x->trans_traj,
-                   x->step_cursor, x->t_table};
-  if (x->frame_rows || x->state_ring) {
-    hipLaunchKernelGGL((reverse_step_kernel<true, true, KeptRows, NoiseKeys>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a,
-                       KeptRows{x->frame_rows, x->kept_rigids, x->state_ring}, NoiseKeys{noise_keys, 0});
-    FD_CHECK_LAUNCH();
-    return FDIPT_OK;
-  }
-  hipLaunchKernelGGL((reverse_step_kernel<true, false, NoiseKeys>), dim3(cdiv(x->N, 64), x->B), dim3(FD_THREADS), 0, (hipStream_t)stream, a, NoiseKeys{noise_keys, 0});
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
+  return reverse_indexed(x, noise_keys, true, stream);
 }
 int fdipt_noise_fill(int B, int N, const uint64_t* noise_keys, int purpose, int k_begin, int n_steps, double* out, fdipt_stream_t stream) {
   if (B <= 0 || N <= 0 || n_steps <= 0) return FDIPT_OK;
@@ -1229,16 +1153,6 @@ int fdipt_noise_fill(int B, int N, const uint64_t* noise_keys, int purpose, int 
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
-int fdipt_se3_reverse_step(int B, int N, const float* rigids_t, const double* rot_score, const float* trans_score,
-                           const float* diffuse_mask, const double* z_rot, const double* z_trans, double t, double dt,
-                           double noise_scale, int center, int diffuse_rot, int diffuse_trans, double so3_min_sigma,
-                           double so3_max_sigma, double r3_min_b, double r3_max_b, double coordinate_scaling,
-                           float* rigids_out, float* out_rot, fdipt_stream_t stream) {
-  return fdipt_se3_reverse_step_atoms(B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale,
-                                      center, diffuse_rot, diffuse_trans, so3_min_sigma, so3_max_sigma, r3_min_b, r3_max_b,
-                                      coordinate_scaling, rigids_out, out_rot, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
 int fdipt_igso3_rot_score(int B, int N, const float* quats_t, const float* quats_0, const double* sigma,
                           const float* res_mask, double* score, fdipt_stream_t s) {
   if (B <= 0 || N <= 0) return FDIPT_OK;
@@ -1273,13 +1187,13 @@ int fdipt_backbone_atoms_indexed(int n, const float* t7, const float* psi, const
                                  float* atom37_rows, const int32_t* step_cursor, fdipt_stream_t s) {
   if (n <= 0) return FDIPT_OK;
   if (!t7 || !psi || !tables || !atom37_rows || !step_cursor) return FDIPT_EINVAL;
-  return fd_backbone(n, t7, nullptr, nullptr, 3, psi, aatype, tables, atom37_rows, nullptr, (hipStream_t)s, step_cursor);
+  return fd_backbone(n, t7, nullptr, nullptr, 3, psi, aatype, tables, atom37_rows, nullptr, (hipStream_t)s, FdStep{step_cursor});
 }
 int fdipt_backbone_atoms_kept(int n, const float* t7, const float* psi, const int32_t* aatype, const void* tables,
                               float* atom37_rows, const int32_t* step_cursor, const int32_t* frame_rows, fdipt_stream_t s) {
   if (n <= 0) return FDIPT_OK;
   if (!t7 || !psi || !tables || !atom37_rows || !step_cursor || !frame_rows) return FDIPT_EINVAL;
-  return fd_backbone(n, t7, nullptr, nullptr, 3, psi, aatype, tables, atom37_rows, nullptr, (hipStream_t)s, step_cursor, frame_rows);
+  return fd_backbone(n, t7, nullptr, nullptr, 3, psi, aatype, tables, atom37_rows, nullptr, (hipStream_t)s, FdStep{step_cursor, frame_rows});
 }
 }  // extern "C"
 

@@ -407,31 +407,45 @@ int fd_pair_bias2(int B, int N, int H, const void* z, const void* wb, const floa
 int fd_pair_bias_f32(long n_pairs, int H, int CZ, const float* z, const float* wb, const float* bb, float* out, hipStream_t st);
 int fd_points(const PointsArgs& a, hipStream_t st);
 int fd_compose_q_update(long n, float* quat, float* trans, const float* upd, int ld_upd, const float* mask, hipStream_t st);
-// Kept-frame addressing of the cursor-addressed launches (FdiptForwardArgs.frame_rows / state_ring); all zero = the step-major rows
-struct FdKept {
-  const int32_t* frame_rows = nullptr;  // [T] i32: row of the kept arrays that step k writes, -1 = none
-  int ring = 0;                         // x_t of step k is row k & 1 of a two-row state
-  bool on() const { return frame_rows != nullptr || ring != 0; }
+// Which step a cursor-addressed launch works on (FdiptForwardArgs / FdiptReverseIndexed: step_cursor, frame_rows, state_ring).  All zero:
+// the pointers of the launch are the rows themselves.  With a cursor they are bases of per-step arrays and k = cursor[0] picks the rows.
+struct FdStep {
+  const int32_t* cursor = nullptr;      // [2] i32: step index k (, ticket of the reverse step)
+  const int32_t* frame_rows = nullptr;  // [T] i32: row of the kept arrays that step k writes, -1 = none; NULL = row k
+  int ring = 0;                         // the state is a two-row ping-pong: x_t = row k & 1, x_{t-1} = row (k + 1) & 1; 0 = rows k, k + 1
+  bool valid() const { return (ring & ~1) == 0 && (cursor || (!frame_rows && !ring)); }  // the row map and the ring are the cursor's
+  bool kept() const { return frame_rows != nullptr || ring != 0; }
 };
+struct FdStepRows { long step, state_in, state_out, frame; };  // frame < 0: this step keeps no frame (uniform over the launch)
+// The one place that turns a step into rows: every cursor-addressed kernel takes its row offsets from here.  KEPT = false is for a
+// kernel whose launcher saw !step.kept(): the map and the ring are then known to be absent at compile time.  The three kernels of every
+// step use it, because their run-time form missed the timing check against the parent commit (reverse_step / rot_score / build_feats:
+// 26.46 / 14.54 / 13.63 us per call against 26.00 / 13.67 / 13.31, allowed 26.31 / 13.85 / 13.47; DESIGN.md section 7.2, "Measured").
+template <bool KEPT = true>
+__device__ __forceinline__ FdStepRows fd_step_rows(const FdStep& s) {
+  if (!s.cursor) return {0, 0, 0, 0};
+  const long k = s.cursor[0];
+  if (!KEPT) return {k, k, k + 1, k};
+  return {k, s.ring ? (k & 1) : k, s.ring ? ((k + 1) & 1) : k + 1, s.frame_rows ? (long)s.frame_rows[k] : k};
+}
 int fd_split_rigids(long n, const float* t7, float cs, const float* res_mask, const float* fixed_mask, float* quat,
-                    float* trans, float* dmask, const int32_t* cursor, hipStream_t st, FdKept kept = {});
+                    float* trans, float* dmask, FdStep step, hipStream_t st);
 int fd_finish(long n, const float* quat, const float* trans, float cs, const float* psi_un, int ld_psi,
               const float* gt_psi, const float* fixed_mask, float* rigids, float* psi, hipStream_t st);
 int fd_build_feats(int B, int N, int use_aatype, int E, const int32_t* aatype, const float* t_emb, const float* t_emb_eps,
                    const float* fixed_mask, const float* idx_emb, float* node_feat, int ld_node, float* pte, int ld_pte,
                    const float* t7, const float* res_mask, float cs, float* quat, float* trans, float* dmask, const float* w1i,
-                   const float* w1j, const float* b1, int cz, float* pi, float* pj, const int32_t* cursor, hipStream_t st,
-                   FdKept kept = {});
+                   const float* w1j, const float* b1, int cz, float* pi, float* pj, FdStep step, hipStream_t st);
 int fd_score_tail(int B, int N, const float* rigids_t, const float* quat, const float* trans, float cs, const float* psi_un,
                   int ld_psi, const float* gt_psi, const float* fixed_mask, const float* res_mask, const double* sigma,
                   const float* t, float min_b, float max_b, float* rigids, float* psi, double* rot_score, float* trans_score,
                   float* ca_out, const float* hid, int ld_hid, int c_hid, const float* torf_w, const float* torf_b,
                   const double* score_table, const double* omega_edges, int n_omega, const int32_t* aatype, const void* bb_tables,
-                  float* atom37, float* atom14, const int32_t* cursor, hipStream_t st, FdKept kept = {});
+                  float* atom37, float* atom14, FdStep step, hipStream_t st);
 int fd_rot_score(int B, int N, const float* qt, int ld_t, const float* q0, int ld_0, const double* sigma,
                  const float* res_mask, double* score, hipStream_t st);
 int fd_trans_score(int B, int N, const float* tt, int ld_t, const float* t0, int ld_0, const float* t, float min_b,
                    float max_b, float cs, const float* res_mask, float* score, hipStream_t st);
 int fd_backbone(int n, const float* t7, const float* rot, const float* trans, int ld_trans, const float* psi,
                 const int32_t* aatype, const void* tables, float* atom37, float* atom14, hipStream_t st,
-                const int32_t* cursor = nullptr, const int32_t* frame_rows = nullptr);
+                FdStep step = {});  // a row map: tensor_7 frames into atom37 only, nothing on a step that keeps no frame

@@ -845,7 +845,7 @@ struct Fwd {
   size_t NN;
   const float* res_mask = a->res_mask;
   float* F(size_t off) const { return (float*)(W + off); }
-  FdKept kept() const { return FdKept{a->frame_rows, a->state_ring}; }  // kept-frame addressing of the cursor launches (NULL / 0: step-major)
+  FdStep step() const { return FdStep{a->step_cursor, a->frame_rows, a->state_ring}; }  // which step the cursor-addressed launches work on (all zero: the pointers are the rows)
   // operand-precision view of a weight matrix of the fp32 blob
   const void* WM(const LinW& l) const { return p.bf ? (const void*)((const half_t*)(D + L.h16_base) + l.w) : (const void*)(P + l.w); }
   int lin(const LinW& l, const float* A, int lda, const float* res, int ldr, const float* rm, int relu, float* out, int ldo) const {
@@ -908,7 +908,7 @@ struct Fwd {
     RC(fd_build_feats(B, N, d->use_aatype, d->index_embed, a->aatype, a->t_emb, a->t_emb_eps, a->fixed_mask, a->idx_emb, F(w.node_feat),
                       L.kn_pad, F(w.pte), L.d1_pad, p.feats_fused ? a->rigids_t : nullptr, a->res_mask, d->coordinate_scaling, F(w.quat),
                       F(w.trans), F(w.dmask), (const float*)(D + L.w1i), (const float*)(D + L.w1j), (const float*)(D + L.b1), cz,
-                      p.feats_fused ? F(w.pi) : nullptr, F(w.pj), a->step_cursor, st, kept()));
+                      p.feats_fused ? F(w.pi) : nullptr, F(w.pj), step(), st));
     if (p.embed == NF_GEMM) {
       RC(fd_linear(op_precision(d), R, cs, L.kn_pad, F(w.node_feat), L.kn_pad, D + L.ne0_pad, L.kn_pad, P + iv.ne0.b, nullptr, 0, nullptr, 1,
                    F(w.h_a), cs, st));
@@ -1287,15 +1287,10 @@ struct Fwd {
                      a->res_mask, a->so3_sigma, a->t, d->r3_min_b, d->r3_max_b, a->rigids, a->psi, a->rot_score, a->trans_score,
                      a->ca_out, p.torf_fused ? F(w.h_b) : nullptr, cs, cs, P + iv.torf.w, P + iv.torf.b, a->so3_score_table,
                      a->so3_omega_edges, a->so3_num_omega, a->aatype, bb_fold ? a->bb_tables : nullptr, bb_fold ? a->atom37 : nullptr,
-                     bb_fold ? a->atom14 : nullptr, a->step_cursor, st, kept()));
-    if (atoms && !bb_fold) {
-      if (a->step_cursor && a->frame_rows) {  // kept frames: the row of the map, nothing on a step that keeps none (atom14 is not built)
-        if (a->atom37)
-          RC(fd_backbone(R, a->rigids, nullptr, nullptr, 0, a->psi, a->aatype, a->bb_tables, a->atom37, nullptr, st, a->step_cursor, a->frame_rows));
-      } else {
-        RC(fd_backbone(R, a->rigids, nullptr, nullptr, 0, a->psi, a->aatype, a->bb_tables, a->atom37, a->atom14, st, a->step_cursor));
-      }
-    }
+                     bb_fold ? a->atom14 : nullptr, step(), st));
+    // kept frames: the row of the map, nothing on a step that keeps none (atom14 is not built)
+    if (atoms && !bb_fold && (a->atom37 || !a->frame_rows))
+      RC(fd_backbone(R, a->rigids, nullptr, nullptr, 0, a->psi, a->aatype, a->bb_tables, a->atom37, a->frame_rows ? nullptr : a->atom14, st, step()));
     return FDIPT_OK;
   }
 };
@@ -1312,7 +1307,7 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
                             !a->rigids))
     return FDIPT_EINVAL;
   if ((op.kind == OP_POINTS || op.kind == OP_IPA) && !a->rigids_t) return FDIPT_EINVAL;
-  if ((a->frame_rows || a->state_ring) && (!a->step_cursor || (a->state_ring & ~1))) return FDIPT_EINVAL;  // kept-frame addressing is the cursor's
+  if (!FdStep{a->step_cursor, a->frame_rows, a->state_ring}.valid()) return FDIPT_EINVAL;  // kept-frame addressing is the cursor's
   if (op.kind != OP_ALL && op.kind != OP_EMBED && (op.block < 0 || op.block >= d->num_blocks - (op.kind == OP_ET ? 1 : 0))) return FDIPT_EINVAL;
   Inventory iv;
   DLayout L;
@@ -1337,7 +1332,7 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
   if (a->trace_node && op.kind == OP_ALL) RC(f.d2d(a->trace_node, f.F(w.node0), node_bytes));
   if (!p.feats_fused && a->rigids_t)
     RC(fd_split_rigids(R, a->rigids_t, d->coordinate_scaling, a->res_mask, a->fixed_mask ? a->fixed_mask : a->res_mask, f.F(w.quat),
-                       f.F(w.trans), f.F(w.dmask), a->step_cursor, f.st, f.kept()));
+                       f.F(w.trans), f.F(w.dmask), f.step(), f.st));
   if (op.kind != OP_ALL) {  // per-op entry: the sub-module's inputs come from the caller; one block, cut at the sub-module's boundary
     if (!op.node_in) return FDIPT_EINVAL;
     RC(f.d2d(f.F(w.node), op.node_in, node_bytes));

@@ -152,21 +152,16 @@ class SE3Diffuser:
     def _reverse_launch(self, lib, B, N, rigids_t, rot_score, trans_score, diffuse_mask, z_rot, z_trans, t, dt, noise_scale, center,
                         rigids_out, rot_out, psi, aatype, tables, atom37, pred, tfix, ttraj, noise_keys=None, step=None):
         so3, r3 = self._so3_diffuser, self._r3_diffuser
-        if noise_keys is not None:
-            _lib.check(lib.fdipt_se3_reverse_step_traj_gen(
-                B, N, _lib.ptr(rigids_t), _lib.ptr(rot_score), _lib.ptr(trans_score), _lib.ptr(diffuse_mask),
-                _lib.ptr(noise_keys), int(step), float(t), float(dt), float(noise_scale), int(bool(center)),
-                int(bool(self._diffuse_rot)), int(bool(self._diffuse_trans)), so3.min_sigma, so3.max_sigma, r3.min_b, r3.max_b,
-                r3._r3_conf.coordinate_scaling, _lib.ptr(rigids_out), _lib.ptr(rot_out), _lib.ptr(psi), _lib.ptr(aatype),
-                _lib.ptr(tables), _lib.ptr(atom37), _lib.ptr(pred), _lib.ptr(tfix), _lib.ptr(ttraj), _lib.stream_ptr()),
-                "se3_reverse_step_gen")
-            return rigids_out
-        _lib.check(lib.fdipt_se3_reverse_step_traj(
-            B, N, _lib.ptr(rigids_t), _lib.ptr(rot_score), _lib.ptr(trans_score), _lib.ptr(diffuse_mask),
-            _lib.ptr(z_rot), _lib.ptr(z_trans), float(t), float(dt), float(noise_scale), int(bool(center)),
+        gen = noise_keys is not None  # the two entries differ in the noise arguments only: (keys, step) or the tape rows
+        fn, noise = ((lib.fdipt_se3_reverse_step_traj_gen, (_lib.ptr(noise_keys), int(step))) if gen else
+                     (lib.fdipt_se3_reverse_step_traj, (_lib.ptr(z_rot), _lib.ptr(z_trans))))
+        _lib.check(fn(
+            B, N, _lib.ptr(rigids_t), _lib.ptr(rot_score), _lib.ptr(trans_score), _lib.ptr(diffuse_mask), *noise,
+            float(t), float(dt), float(noise_scale), int(bool(center)),
             int(bool(self._diffuse_rot)), int(bool(self._diffuse_trans)), so3.min_sigma, so3.max_sigma, r3.min_b, r3.max_b,
             r3._r3_conf.coordinate_scaling, _lib.ptr(rigids_out), _lib.ptr(rot_out), _lib.ptr(psi), _lib.ptr(aatype),
-            _lib.ptr(tables), _lib.ptr(atom37), _lib.ptr(pred), _lib.ptr(tfix), _lib.ptr(ttraj), _lib.stream_ptr()), "se3_reverse_step")
+            _lib.ptr(tables), _lib.ptr(atom37), _lib.ptr(pred), _lib.ptr(tfix), _lib.ptr(ttraj), _lib.stream_ptr()),
+            "se3_reverse_step_gen" if gen else "se3_reverse_step")
         return rigids_out
 
     def reverse(self, rigid_t: Rigid, rot_score, trans_score, t: float, dt: float, diffuse_mask=None,

@@ -282,14 +282,13 @@ class ReverseLoop:
         st.forward(self.rigid_traj, self.res_mask, self.fixed, self.sc_ca, self.net_aatype, self.gt_psi, self.t_all, self.temb_all,
                    self.sig_all, direct, ca_out=self.sc_ca if self.embed_sc else None, atom37_out=self.bb0_traj if direct else None,
                    step_cursor=self.cursor, frame_rows=self.frame_rows, state_ring=self.kept)
-        if self.aux_traj and not direct and self.kept:
-            _lib.check(lib.fdipt_backbone_atoms_kept(self.B * self.N, _lib.ptr(st.rigids), _lib.ptr(st.psi), _lib.ptr(self.aatype),
-                                                     _lib.ptr(self.model.bb_tables), _lib.ptr(self.bb0_traj), _lib.ptr(self.cursor),
-                                                     _lib.ptr(self.frame_rows), _lib.stream_ptr()), "backbone_atoms_kept")
-        elif self.aux_traj and not direct:
-            _lib.check(lib.fdipt_backbone_atoms_indexed(self.B * self.N, _lib.ptr(st.rigids), _lib.ptr(st.psi), _lib.ptr(self.aatype),
-                                                        _lib.ptr(self.model.bb_tables), _lib.ptr(self.bb0_traj), _lib.ptr(self.cursor),
-                                                        _lib.stream_ptr()), "backbone_atoms_indexed")
+        if self.aux_traj and not direct:  # (the kept entry is the indexed one with the row map behind the cursor)
+            args = [self.B * self.N, _lib.ptr(st.rigids), _lib.ptr(st.psi), _lib.ptr(self.aatype), _lib.ptr(self.model.bb_tables),
+                    _lib.ptr(self.bb0_traj), _lib.ptr(self.cursor)]
+            if self.kept:
+                _lib.check(lib.fdipt_backbone_atoms_kept(*args, _lib.ptr(self.frame_rows), _lib.stream_ptr()), "backbone_atoms_kept")
+            else:
+                _lib.check(lib.fdipt_backbone_atoms_indexed(*args, _lib.stream_ptr()), "backbone_atoms_indexed")
         so3, r3 = d._so3_diffuser, d._r3_diffuser
         a = _lib.ReverseIndexed()
         a.B, a.N = self.B, self.N

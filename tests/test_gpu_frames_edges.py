@@ -307,3 +307,104 @@ def test_compose_q_update_edges_vs_oracle(lib):
     assert e_q <= 1e-6 and e_t <= 1e-5, (e_q, e_t)
     fixed = inp["mask"] == 0
     assert np.array_equal(got[fixed, 4:], inp["t7"][fixed, 4:])
+
+
+# ---------------------------------------------------------------- step addressing of the cursor entries
+STEP_B, STEP_T = 3, 4
+STEP_MODES = {  # (state_ring, frame_rows): step-major; ring with a row map that skips steps 0 and 2; ring with the step-major frame rows
+    "step_major": (0, None),
+    "ring_map": (1, (-1, 0, -1, 1)),
+    "ring_no_map": (1, None),
+}
+_step_runs = {}
+
+
+def _step_reference(lib, N, gen):
+    """Random inputs of STEP_T steps and, per step, what the non-indexed entry (fdipt_se3_reverse_step_traj / _traj_gen: pinned to the
+    oracle by test_reverse_step_edges_vs_oracle) writes for it: x_{t-1}, the atom37 frame, the trans_traj row.  Computed once per
+    (N, gen) and shared by the addressing modes."""
+    if (N, gen) in _step_runs:
+        return _step_runs[N, gen]
+    from framedipt_amd import config, residue_tables
+    from framedipt_amd import noise as noise_mod
+    B, T = STEP_B, STEP_T
+    rng = np.random.default_rng(1000 + N)
+    so3, r3 = (lambda c: (c.so3, c.r3))(config.base_config().diffuser)
+    consts = (float(so3.min_sigma), float(so3.max_sigma), float(r3.min_b), float(r3.max_b), float(r3.coordinate_scaling))
+    q = rng.normal(size=(B, N, 4))
+    q = q / np.linalg.norm(q, axis=-1, keepdims=True) * np.where(q[..., :1] < 0, -1.0, 1.0)
+    psi = rng.normal(size=(B, N, 2))
+    mask = (rng.random((B, N)) < 0.7).astype(F32)
+    inp = dict(
+        x0=dev(np.concatenate([q, 5.0 * rng.normal(size=(B, N, 3))], -1).astype(F32)),
+        rot_score=dev(0.3 * rng.normal(size=(B, N, 3))), trans_score=dev((0.3 * rng.normal(size=(B, N, 3))).astype(F32)),
+        mask=dev(mask), fixed=dev((1 - mask).astype(F32)), psi=dev((psi / np.linalg.norm(psi, axis=-1, keepdims=True)).astype(F32)),
+        aatype=dev(rng.integers(0, 21, size=(B, N)).astype(np.int32)), pred=dev(rng.normal(size=(B, N, 7)).astype(F32)),
+        z_rot=None if gen else dev(rng.normal(size=(T, B, N, 3))), z_trans=None if gen else dev(rng.normal(size=(T, B, N, 3))),
+        keys=noise_mod.keys_tensor(noise_mod.as_keys(77, B), "cuda") if gen else None,
+        t_table=np.linspace(1.0, 0.25, T), t_dev=dev(np.linspace(1.0, 0.25, T)), dt=1.0 / T, noise_scale=0.1, consts=consts, tables=dev(residue_tables.packed_bytes()))
+    x, steps = inp["x0"], []
+    for k in range(T):
+        out, a37, tt = (torch.full((B, N, *s), 7.0, device="cuda") for s in ((7,), (37, 3), (3,)))
+        noise = (inp["keys"], k) if gen else (inp["z_rot"][k], inp["z_trans"][k])
+        _call(lib, "fdipt_se3_reverse_step_traj_gen" if gen else "fdipt_se3_reverse_step_traj", B, N, x, inp["rot_score"], inp["trans_score"],
+              inp["mask"], *noise, float(inp["t_table"][k]), inp["dt"], inp["noise_scale"], 1, 1, 1, *consts, out, None, inp["psi"],
+              inp["aatype"], inp["tables"], a37, inp["pred"], inp["fixed"], tt)
+        steps.append(dict(x=out, atom37=a37, trans_traj=tt))
+        x = out
+    torch.cuda.synchronize()
+    _step_runs[N, gen] = (inp, steps)
+    return inp, steps
+
+
+@pytest.mark.parametrize("mode", list(STEP_MODES))
+@pytest.mark.parametrize("N", [12, 70])
+def test_step_addressing_of_the_indexed_reverse_step(lib, N, mode):
+    """fdipt_se3_reverse_step_indexed / _indexed_gen driven from cursor 0 through STEP_T steps, atoms and trans_traj on, for the three
+    addressing modes of FdiptReverseIndexed: after every step the row it had to write — of the state, prot_traj, trans_traj and
+    kept_rigids — is bit for bit what the non-indexed entry writes for that step, every other row (all of them on a step whose frame row
+    is -1) is as it was before the launch, and the cursor reads [k + 1, 0].  N = 12: below one 16-residue block and no multiple of 4;
+    N = 70: two row blocks per sample, the second ragged, a ticket of 6 blocks."""
+    import ctypes as C
+
+    from framedipt_amd import _lib
+    B, T = STEP_B, STEP_T
+    ring, frame_rows = STEP_MODES[mode]
+    for gen in (False, True):
+        inp, ref = _step_reference(lib, N, gen)
+        n_frames = T if frame_rows is None else 1 + max(frame_rows)
+        state = torch.full((2 if ring else T + 1, B, N, 7), 7.0, device="cuda")
+        state[0] = inp["x0"]
+        arrays = dict(prot_traj=torch.full((n_frames, B, N, 37, 3), 7.0, device="cuda"),
+                      trans_traj=torch.full((n_frames, B, N, 3), 7.0, device="cuda"))
+        if frame_rows is not None:
+            arrays["kept_rigids"] = torch.full((n_frames, B, N, 7), 7.0, device="cuda")
+        cursor = torch.zeros(2, dtype=torch.int32, device="cuda")
+        rows_dev = None if frame_rows is None else torch.tensor(frame_rows, dtype=torch.int32, device="cuda")
+        a = _lib.ReverseIndexed()
+        a.B, a.N = B, N
+        for name, tns in dict(rigid_traj=state, rot_score=inp["rot_score"], trans_score=inp["trans_score"], diffuse_mask=inp["mask"],
+                              z_rot=inp["z_rot"], z_trans=inp["z_trans"], t_table=inp["t_dev"], psi=inp["psi"], aatype=inp["aatype"],
+                              bb_tables=inp["tables"], pred_rigids=inp["pred"], traj_fixed_mask=inp["fixed"], step_cursor=cursor,
+                              frame_rows=rows_dev, **arrays).items():
+            setattr(a, name, _lib.ptr(tns))
+        a.state_ring = ring
+        a.dt, a.noise_scale, a.center, a.diffuse_rot, a.diffuse_trans = inp["dt"], inp["noise_scale"], 1, 1, 1
+        a.so3_min_sigma, a.so3_max_sigma, a.r3_min_b, a.r3_max_b, a.coordinate_scaling = inp["consts"]
+        for k in range(T):
+            what = f"N={N} {mode} gen={gen} step {k}"
+            before = {name: v.clone() for name, v in dict(arrays, state=state).items()}
+            if gen:
+                _lib.check(lib.fdipt_se3_reverse_step_indexed_gen(C.byref(a), _lib.ptr(inp["keys"]), _lib.stream_ptr()), what)
+            else:
+                _lib.check(lib.fdipt_se3_reverse_step_indexed(C.byref(a), _lib.stream_ptr()), what)
+            assert cursor.tolist() == [k + 1, 0], what
+            frame = k if frame_rows is None else frame_rows[k]
+            wrote = dict(state=((k + 1) & 1 if ring else k + 1, ref[k]["x"]))
+            if frame >= 0:
+                wrote.update({name: (frame, ref[k][dict(prot_traj="atom37", kept_rigids="x").get(name, name)]) for name in arrays})
+            for name, v in dict(arrays, state=state).items():
+                row, want = wrote.get(name, (None, None))
+                for i in range(v.shape[0]):
+                    assert torch.equal(v[i], want if i == row else before[name][i]), (what, name, i, row)
+        assert cursor.tolist() == [T, 0]

@@ -252,14 +252,17 @@ def test_reset_of_a_default_constructed_loop_leaves_the_model_cache_right():
         assert loop.captures > 0 and sess.hits == 1
 
 
-def test_kept_rows_with_the_launch_folds_off():
+@pytest.mark.parametrize("cached_score", [False, True])
+def test_kept_rows_with_the_launch_folds_off(cached_score):
     """FDIPT_KF_UNFOLDED: the forward builds the rigid_0_traj row by its own backbone launch (no fold into the score tail) — keep=3 and
-    "last" against keep="all", graph and eager."""
+    "last" against keep="all", graph and eager.  With so3.use_cached_score the score launch also reads its table row at the cursor (the
+    one row offset that only rot_score_kernel applies)."""
     from framedipt_amd import _lib, config
     from framedipt_amd.diffusion import SE3Diffuser
     from framedipt_amd.inference import inference_fn
     from framedipt_amd.model import ScoreNetwork
     conf = config.base_config()
+    conf.diffuser.so3.use_cached_score = cached_score
     d = SE3Diffuser(conf.diffuser, device="cuda")
     net = ScoreNetwork(conf.model, d, precision="fp16", kernel_flags=_lib.KF_UNFOLDED).load_synthetic(7).to("cuda")
     feats, tape, _ = _batch(d, 16, 2, 3, 20)
