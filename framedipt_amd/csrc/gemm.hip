@@ -506,7 +506,7 @@ int fd_layernorm(int M, int D, const float* x, int ldx, const float* residual, i
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
-// LayerNorm(x + sum_k parts[k]) for the split-K products of fd_linear_splitk
+// LayerNorm(x + sum_k parts[k]) for the split-K products of fd_linear_splitk_split / fd_outproj_split
 int fd_layernorm_parts(int M, int D, const float* x, int ldx, const float* parts, int ldr, int nparts, long part_stride,
                        const float* gamma, const float* beta, const float* rowmask, float* out, int ldo, const float* extra,
                        int ld_extra, int n_extra, const L2Warm* warm, hipStream_t st) {
@@ -523,18 +523,8 @@ int fd_layernorm_parts(int M, int D, const float* x, int ldx, const float* parts
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
-// parts[z][M, ldo] = (A[:, z-th K slice] W[:, slice]^T (+ bias for z = 0)) * rowmask; bf16 operands, fp32 activations in
-int fd_linear_splitk(int M, int N, int K, int nsplit, const float* A, int lda, const void* W, int ldw, const float* bias,
-                     const float* rowmask, float* parts, long part_stride, int ldo, hipStream_t st) {
-  if (M <= 0 || N <= 0 || K <= 0 || nsplit < 1 || (K & 7) || (lda & 3) || (ldw & 7)) return FDIPT_EINVAL;
-  const int kslice = ((K + nsplit - 1) / nsplit + 63) / 64 * 64;
-  if ((long)kslice * (nsplit - 1) >= K) return FDIPT_EINVAL;  // an empty slice
-  hipLaunchKernelGGL((linear_splitk_kernel<PrecHalf, float, half_t>), dim3(cdiv(M, 64), cdiv(N, 64), nsplit), dim3(FD_THREADS),
-                     (size_t)2 * 128 * (64 + PrecHalf::PAD) * sizeof(half_t), st, M, N, K, kslice, A, lda, (const half_t*)W, ldw, bias, rowmask, parts, part_stride, ldo);
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
-}
-// the same on split operands (fp32 activations and the fp32 weight matrix, both split into hi + lo parts while they are staged)
+// parts[z][M, ldo] = (A[:, z-th K slice] W[:, slice]^T (+ bias for z = 0)) * rowmask on split operands
+// (fp32 activations and the fp32 weight matrix, both split into hi + lo parts while they are staged)
 int fd_linear_splitk_split(int M, int N, int K, int nsplit, const float* A, int lda, const float* W, int ldw, const float* bias,
                            const float* rowmask, float* parts, long part_stride, int ldo, hipStream_t st) {
   if (M <= 0 || N <= 0 || K <= 0 || nsplit < 1 || (K & 7) || (lda & 3) || (ldw & 3)) return FDIPT_EINVAL;
@@ -689,16 +679,6 @@ int fd_outproj_split(int M, int N, int K, const float* A, int lda, const void* w
   }
   hipLaunchKernelGGL((outproj_split_kernel<OP_KSL>), dim3(cdiv(M, 64), OP_NS), dim3(512), smem, st, M, A, lda, (const char*)w_hi, (const char*)w_lo,
                      K / 16, bias, rowmask, parts, part_stride, ldo);
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
-}
-int fd_linear_splitk_a16(int M, int N, int K, int nsplit, const half_t* A, int lda, const void* W, int ldw, const float* bias,
-                     const float* rowmask, float* parts, long part_stride, int ldo, hipStream_t st) {
-  if (M <= 0 || N <= 0 || K <= 0 || nsplit < 1 || (K & 7) || (lda & 7) || (ldw & 7)) return FDIPT_EINVAL;
-  const int kslice = ((K + nsplit - 1) / nsplit + 63) / 64 * 64;
-  if ((long)kslice * (nsplit - 1) >= K) return FDIPT_EINVAL;  // an empty slice
-  hipLaunchKernelGGL((linear_splitk_kernel<PrecHalf, half_t, half_t>), dim3(cdiv(M, 64), cdiv(N, 64), nsplit), dim3(FD_THREADS),
-                     (size_t)2 * 128 * (64 + PrecHalf::PAD) * sizeof(half_t), st, M, N, K, kslice, A, lda, (const half_t*)W, ldw, bias, rowmask, parts, part_stride, ldo);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }

@@ -79,7 +79,7 @@ struct OPairArgs {
   const void* wdz_img_lo = nullptr;
   const float* bdz;      // [CD]
   float* out;            // row (b*N+i): out + r*out_ld + off + h*CD + d
-  half_t* out_h16;      // MFMA kernel: if set, bf16 rows (same out_ld, in elements) INSTEAD of out
+  half_t* out_h16;      // MFMA kernel: if set, bf16 rows (same out_ld, in elements) INSTEAD of out (no plan sets it: model.hip)
   long out_ld;
   int off;
   L2Warm warm = {};  // weights of the kernel launched next (common.hpp: L2 warm-up hand-over)
@@ -242,7 +242,7 @@ struct Attn3Args {
   const float* gamma;             // [H]
   const float *rot, *trans;       // [B,N,9], [B,N,3]
   float* probs;                   // [B,H,N,N]
-  half_t* out_h16;               // if set: the output features are written as bf16 rows (same out_ld, in elements) INSTEAD of out
+  half_t* out_h16;               // if set: the output features are written as bf16 rows (same out_ld, in elements) INSTEAD of out (no plan sets it: model.hip)
   half_t* probs_h16;             // if set: written INSTEAD, as bf16 rows [B,N,H,Np] (what the MFMA o_pair kernel consumes)
   float* out;                     // feature rows: o at h*256, point features at pt_off
   long out_ld;
@@ -272,7 +272,7 @@ struct SeqInitExtra {  // once-per-forward fills folded into the sequence-image 
 // stream != 0: the images are read by the key-streaming kernel (N <= 2048), as fd_seq_attention_run(.., stream)
 int fd_seq_images_init(int B, int N, int H, const float* res_mask, void* images, const SeqInitExtra& x, hipStream_t st, int stream = 0);
 int fd_seq_qkv_supported(int N, int H, int d_model);
-// wimg_lo != NULL: split operands (image of W - half(W), fd_chain_build_image(.., lo = 1))
+// split operands: wimg_lo is the image of W - half(W) (fd_chain_build_image(.., lo = 1))
 int fd_seq_qkv(int B, int N, int H, const float* x, int ld_x, const void* wimg, const void* wimg_lo, const float* bias, float scale,
                void* images, hipStream_t st);
 int fd_seq_attention_run(int B, int N, int H, const void* images, float* out, int out_ld, const L2Warm* warm, hipStream_t st,
@@ -289,7 +289,7 @@ struct RowBlockArgs {
   const float* in = nullptr;
   int ld_in = 0;
   const void *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
-  const void *w0l = nullptr, *w1l = nullptr, *w2l = nullptr;  // *_SPLIT kinds: images of W - half(W) (fd_chain_build_image(.., lo = 1))
+  const void *w0l = nullptr, *w1l = nullptr, *w2l = nullptr;  // split-operand kinds: images of W - half(W) (fd_chain_build_image(.., lo = 1))
   const float *b0 = nullptr, *b1 = nullptr, *b2 = nullptr;
   const float* residual = nullptr;  // or NULL
   int ld_res = 0;
@@ -318,20 +318,20 @@ struct RowBlockArgs {
   const void *we0 = nullptr, *we0l = nullptr, *we1 = nullptr, *we1l = nullptr;
   const float *be0 = nullptr, *be1 = nullptr;
 };
-enum { FD_RB_TRANSITION, FD_RB_NODE_EMBED_72, FD_RB_NODE_EMBED_88, FD_RB_TORSION, FD_RB_TRANSITION_BB, FD_RB_ET_ROWS, FD_RB_ET4_ROWS, FD_RB_ET4_IMAGES,
-       FD_RB_TRANSITION_BB_SPLIT, FD_RB_NODE_EMBED_72_SPLIT, FD_RB_NODE_EMBED_88_SPLIT, FD_RB_TORSION_SPLIT };
+// FD_RB_ET_ROWS and FD_RB_ET4_ROWS run on plain operands; every other kind on split operands (its lo images are required)
+enum { FD_RB_NODE_EMBED_72, FD_RB_NODE_EMBED_88, FD_RB_TORSION, FD_RB_TRANSITION_BB, FD_RB_ET_ROWS, FD_RB_ET4_ROWS, FD_RB_ET4_IMAGES };
 int fd_rowblock(int kind, const RowBlockArgs& a, hipStream_t st);
-// FD_RB_TRANSITION_BB_SPLIT on 16-row blocks (rowblock.hip: transition16_kernel); w0 / w1 / w2 and their lo images are fd_chain_build_image16 images
+// FD_RB_TRANSITION_BB on 16-row blocks (rowblock.hip: transition16_kernel); w0 / w1 / w2 and their lo images are fd_chain_build_image16 images
 int fd_transition16(const RowBlockArgs& a, hipStream_t st);
-int fd_node_embed16(const RowBlockArgs& a, int k0, hipStream_t st);  // FD_RB_NODE_EMBED_*_SPLIT (first image: K padded to 96)
-int fd_torsion16(const RowBlockArgs& a, hipStream_t st);             // FD_RB_TORSION_SPLIT
+int fd_node_embed16(const RowBlockArgs& a, int k0, hipStream_t st);  // FD_RB_NODE_EMBED_* (first image: K padded to 96)
+int fd_torsion16(const RowBlockArgs& a, hipStream_t st);             // FD_RB_TORSION
 
 // post-attention half of one encoder layer in one launch (rowblock.hip): x_a = LN1(x + Wo att + bo); out = LN2(x_a + W2 relu(W1 x_a + b1) + b2)
 struct TfmrTailArgs {
   int M, ld;                      // rows; common row stride of att / x / out (d_model = 320)
   const float *att, *x;           // attention output rows, layer input rows (residual)
   const void *wo, *w1, *w2;       // fragment images, natural k order (fd_chain_build_image(.., permuted = 0, ..))
-  const void *wol = nullptr, *w1l = nullptr, *w2l = nullptr, *wpl = nullptr;  // split operands: lo images (fd_chain_build_image(.., lo = 1)); wol selects the split kernel
+  const void *wol = nullptr, *w1l = nullptr, *w2l = nullptr, *wpl = nullptr;  // split operands: lo images (fd_chain_build_image(.., lo = 1)), wpl with wp
   const float *bo, *g1, *be1, *b1, *b2, *g2, *be2;
   float* out;                     // must not alias x
   // optional (last layer of the stack): post_tfmr (Linear 320 -> 256, fragment image wp, bias bp) + residual rows pres on the
@@ -341,7 +341,7 @@ struct TfmrTailArgs {
   float* pout = nullptr;
   int ld_pres = 0, ld_pout = 0;
   L2Warm warm;                    // weights of the kernel launched next (touched once the block's own first loads are out)
-  int rows16 = 0;                 // 1: 16-row blocks (tfmr_tail16_kernel, split operands only): wo / w1 / w2 / wp and their lo images are
+  int rows16 = 0;                 // 1: 16-row blocks (tfmr_tail16_kernel): wo / w1 / w2 / wp and their lo images are
                                   // fd_chain_build_image16 images
 };
 int fd_tfmr_tail(const TfmrTailArgs& a, hipStream_t st);
@@ -377,9 +377,7 @@ int fd_linear_z(int precision, long M, int N, int K, const void* A, const void* 
 int fd_layernorm_parts(int M, int D, const float* x, int ldx, const float* parts, int ldr, int nparts, long part_stride,
                        const float* gamma, const float* beta, const float* rowmask, float* out, int ldo, const float* extra,
                        int ld_extra, int n_extra, const L2Warm* warm, hipStream_t st);
-// the same with bf16 activation rows (what the bf16 GEMM would round them to anyway)
-int fd_linear_splitk_a16(int M, int N, int K, int nsplit, const half_t* A, int lda, const void* W, int ldw, const float* bias,
-                         const float* rowmask, float* parts, long part_stride, int ldo, hipStream_t st);
+// split-K products on split operands: parts[z] = the z-th K slice's product (gemm.hip); fd_layernorm_parts sums them
 int fd_linear_splitk_split(int M, int N, int K, int nsplit, const float* A, int lda, const float* W, int ldw, const float* bias,
                            const float* rowmask, float* parts, long part_stride, int ldo, hipStream_t st);
 // dedicated split-operand kernel for the IPA output projection at the reference widths (gemm.hip: outproj_split_kernel)
@@ -387,8 +385,6 @@ int fd_outproj_split_supported(int N, int K);
 int fd_outproj_split_slices();
 int fd_outproj_split(int M, int N, int K, const float* A, int lda, const void* w_hi, const void* w_lo, const float* bias, const float* rowmask,
                      float* parts, long part_stride, int ldo, hipStream_t st);
-int fd_linear_splitk(int M, int N, int K, int nsplit, const float* A, int lda, const void* W, int ldw, const float* bias,
-                     const float* rowmask, float* parts, long part_stride, int ldo, hipStream_t st);
 int fd_layernorm(int M, int D, const float* x, int ldx, const float* residual, int ldr, const float* gamma,
                  const float* beta, const float* rowmask, float* out, int ldo, hipStream_t st);
 int fd_f32_to_half(long n, const float* in, half_t* out, hipStream_t st);

@@ -127,8 +127,8 @@ struct DLayout {
   size_t skip16[2];                                 // ... of the stacked skip_embed matrices [num_blocks * c_skip = 256, c_s] (fused into the node embedder)
   size_t ne16[3][2], tor16[2][2];                   // 16-row images (fd_chain_build_image16; the embedder's first one zero-padded to K = 96), hi / lo
   unsigned lo_tor_run, ne16_run, tor16_run, skip16_run;  // runs: lo tor1 | tor2; ne16 hi or lo; tor16 hi or lo; skip16 hi | lo
-  size_t skip_w32;                                  // ... in fp32 (split operands: the GEMM splits both operands while it stages them)
-  size_t skip_w, skip_b;                            // skip_embed of ALL blocks stacked: [num_blocks * c_skip, c_s] operand precision, bias f32
+  size_t skip_w32, skip_b;                          // skip_embed of ALL blocks stacked: [num_blocks * c_skip, c_s] fp32 (split operands: the GEMM
+                                                    // splits both operands while it stages them), bias f32
   DBlock blk[FD_MAX_BLOCKS];
   size_t total;
   int kn_pad, d1_pad, esz;
@@ -509,19 +509,18 @@ static int blob_walk(const FdiptDims* d, const Inventory& iv, DLayout& L, const 
     for (int h = 0; h < 2; ++h) L.tor16_run = w.run([&] { L.tor16[0][h] = chain16(iv.tor1, h); L.tor16[1][h] = chain16(iv.tor2, h); });
     L.ch_ne0 = ne0(0); L.ch_ne2 = chain(iv.ne2, 0); L.ch_ne4 = chain(iv.ne4, 0); L.ch_tor1 = chain(iv.tor1, 0); L.ch_tor2 = chain(iv.tor2, 0);
   }
-  // skip_embed of all blocks stacked, in operand precision, its bias, in fp32, and as 16-row images (from the fp32 one)
-  auto skip = [&](int e, int bias) {
-    return w.img(true, (size_t)nsk * (bias ? 1 : cs) * e, [&](char* at) {
+  // skip_embed of all blocks stacked: its bias, the matrix in fp32, and as 16-row images (from the fp32 one)
+  auto skip = [&](int bias) {
+    return w.img(true, (size_t)nsk * (bias ? 1 : cs) * 4, [&](char* at) {
       for (int b = 0; b < d->num_blocks; ++b) {
         const LinW& l = iv.blk[b].skip;
-        RC(bias ? vec(l.b, l.out, at + (size_t)b * l.out * 4) : copy_cols(e, l.out, cs, cs, P + l.w, cs, 0, 1.f, at + (size_t)b * l.out * cs * e, st));
+        RC(bias ? vec(l.b, l.out, at + (size_t)b * l.out * 4) : copy_cols(4, l.out, cs, cs, P + l.w, cs, 0, 1.f, at + (size_t)b * l.out * cs * 4, st));
       }
       return FDIPT_OK;
     });
   };
-  L.skip_w = skip(esz, 0);
-  L.skip_b = skip(4, 1);
-  L.skip_w32 = skip(4, 0);
+  L.skip_b = skip(1);
+  L.skip_w32 = skip(0);
   L.skip16_run = w.run([&] {
     for (int h = 0; h < 2; ++h)
       L.skip16[h] = w.img(skip16_image(d), fd_chain_image_bytes(nsk, cs),
@@ -662,8 +661,8 @@ struct OpSel {
 // shapes use anyway, so that parity tests can run them at the golden sizes.  Every choice below is a function of the dims, the
 // flags, the shape and the op kind only: the same for every block, made once per forward.
 enum NodeForm { NF_GEMM, NF_ROWBLOCK, NF_ROWS16 };  // node-path MLPs: GEMM + LayerNorm launches, 32-row row-block kernel, 16-row kernel
-enum SkipAt { SKIP_PER_BLOCK, SKIP_EMBED16, SKIP_SPLITK, SKIP_GEMM };  // skip_embed(init_node): per block, or once for all blocks
-enum OutProj { OUT_GEMM, OUT_DEDICATED, OUT_SPLITK_SPLIT, OUT_SPLITK_A16, OUT_SPLITK };  // IPA linear_out
+enum SkipAt { SKIP_PER_BLOCK, SKIP_EMBED16, SKIP_SPLITK };  // skip_embed(init_node): per block, or once for all blocks
+enum OutProj { OUT_GEMM, OUT_DEDICATED, OUT_SPLITK_SPLIT };  // IPA linear_out
 enum NodeRows { NR_PROJ, NR_POINTS, NR_LAUNCH };  // merged projection: who writes the node-row images (Kb / Vt / Vt_lo)
 enum SeqAttn { SEQ_FUSED, SEQ_BF16, SEQ_F32, SEQ_GENERIC };  // sequence-transformer attention: in_proj writes the images / bf16 / fp32 / LDS kernel
 enum PostAt { POST_TAIL, POST_CHAIN, POST_GEMM };
@@ -671,7 +670,7 @@ enum EtKind { ET_GEMM, ET_CHAIN, ET_ET3, ET_ET4 };
 enum EtRows { ETR_IMAGES, ETR_ROWS, ETR_FOLDED };  // edge_transition4's per-residue rows: row-block images, rows + image pass, transition launch
 struct ForwardPlan {
   int op;
-  bool bf, chain, rbk, split;  // half-precision mode; fused chains (chain.hip); row-complete MLPs (rowblock.hip); split (hi + lo) operands
+  bool bf, fused_node;  // half-precision mode; the fused node path (below)
   NodeForm embed, tail, transition, torsion;
   SkipAt skip;
   OutProj outproj;
@@ -679,7 +678,7 @@ struct ForwardPlan {
   bool feats_fused, ee_bias, et_bias, pz;
   bool stream;                         // FDIPT_KF_STREAM_ATTN in the half-precision mode, N <= 2048: the key-streaming attention kernels
   bool a3, probs_h16;                  // IPA path: attention3, and the MFMA o_pair fed with bf16 attention weights
-  bool vpt, proj2, merged, proj_pts, vt_lo, init_fused, feats_h16;
+  bool vpt, proj2, merged, proj_pts, vt_lo, init_fused;
   NodeRows node_rows;
   SeqAttn seq;
   PostAt post;
@@ -702,30 +701,27 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   ForwardPlan p = {};
   p.op = op;
   p.bf = half_mode(d);
-  // fused chains (chain.hip) where they beat the GEMM + LayerNorm launches they replace at B*N ~ 2400 rows on MI355X
-  // (profiles/r01_chain_vs_gemm.md): post_tfmr and EdgeTransition.initial_embed when the row-block kernels do not take them
-  p.chain = use_chain(d);
-  // row-complete fused MLPs (rowblock.hip) take the multi-layer kinds and the 320-wide transformer layers (FDIPT_KF_UNFUSED_NODE
-  // clears use_chain, whose widths are theirs)
-  p.rbk = p.chain;
-  // split operands (hi + lo half-precision parts, 3 MFMAs per k-step) for the dense layers of the node path, whose operand
-  // rounding dominates the error of the predicted frames and psi (tests/err_budget.py): node embedder, IPA projection and output
-  // projection, attention P V, o_pair down-projection, sequence transformer (in_proj, out_proj, feed-forward), post_tfmr, transition,
-  // EdgeTransition per-residue rows, skip_embed, torsion head
-  p.split = p.rbk && !(f & FDIPT_KF_NO_SPLIT);
+  // The fused node path (use_chain: the reference widths of the half-precision mode; FDIPT_KF_UNFUSED_NODE clears it).  Row-complete
+  // fused MLPs (rowblock.hip) take the multi-layer kinds and the 320-wide transformer layers; fused chains (chain.hip) take post_tfmr
+  // and EdgeTransition.initial_embed where the row-block kernels do not (they beat the GEMM + LayerNorm launches they replace at
+  // B*N ~ 2400 rows on MI355X, profiles/r01_chain_vs_gemm.md).  Its dense layers run on split operands (hi + lo half-precision parts,
+  // 3 MFMAs per k-step): their operand rounding dominates the error of the predicted frames and psi (tests/err_budget.py) — node
+  // embedder, IPA projection and output projection, attention P V, o_pair down-projection, sequence transformer (in_proj, out_proj,
+  // feed-forward), post_tfmr, transition, EdgeTransition per-residue rows, skip_embed, torsion head
+  p.fused_node = use_chain(d);
   // 16-row node-path blocks pay off while they are about one round of the chip (B N <= ~4000 rows: twice the blocks of the 32-row kernels, each
   // streaming all weights, half the matrix work per block); with every CU busy anyway the 32-row kernels move half the weight bytes (measured: c4
   // with 64 samples per GPU 1.277 -> 1.246 M).  The choice goes by N alone — a sample's result must not depend on the batch it rides in.
   // (the 16-row images exist with the 32-row ones: use_chain)
-  const bool rows16 = p.split && !(f & FDIPT_KF_ROWS32) && N <= 512;
-  p.embed = p.rbk && (L.kn_pad == 72 || L.kn_pad == 88) ? (rows16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
-  p.torsion = p.tail = p.transition = p.rbk ? (rows16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
+  const bool rows16 = p.fused_node && !(f & FDIPT_KF_ROWS32) && N <= 512;
+  p.embed = p.fused_node && (L.kn_pad == 72 || L.kn_pad == 88) ? (rows16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
+  p.torsion = p.tail = p.transition = p.fused_node ? (rows16 ? NF_ROWS16 : NF_ROWBLOCK) : NF_GEMM;
   // the IPA output projection as split-K slices that its LayerNorm sums; skip_embed(init_node) of every block depends on the
   // embedder output only: one launch for all blocks, copied behind the LayerNorm output by that LayerNorm (FDIPT_KF_UNFOLDED: per block)
-  const bool splitk = p.bf && iv.feat_dim >= 1024 && !(f & FDIPT_KF_UNFUSED_NODE);
+  const bool splitk = p.fused_node && iv.feat_dim >= 1024;
   if (!splitk || unfolded || op != OP_ALL) p.skip = SKIP_PER_BLOCK;
   else if (p.embed == NF_ROWS16 && skip16_image(d)) p.skip = SKIP_EMBED16;  // a fourth layer of the embedder launch
-  else p.skip = p.split && (cs & 7) == 0 ? SKIP_SPLITK : SKIP_GEMM;
+  else p.skip = SKIP_SPLITK;
   // the split of x_t (ipa_pytorch.py:516-524) and the per-residue halves of the first edge-embedder layer in the feature launch
   // (FDIPT_KF_UNFOLDED: three GEMM / element-wise launches more)
   p.feats_fused = L.d1_pad <= 128 && (L.d1_pad & 3) == 0 && !unfolded && op == OP_ALL;
@@ -753,10 +749,10 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   // pair_mlp.hip.  edge_transition4's rows come from the transition launch where that is the 16-row kernel (FDIPT_KF_UNFOLDED: a row
   // launch and an image pass)
   p.et_widths = iv.cb == 128 && iv.hid == 384 && cz == 128;
-  const bool reg_ok = p.rbk && p.et_widths && p.regpair;
+  const bool reg_ok = p.fused_node && p.et_widths && p.regpair;
   if (reg_ok && !(f & FDIPT_KF_ET3) && fd_edge_transition4_supported(N)) p.et = ET_ET4;
   else if (reg_ok && fd_edge_transition3_supported(N)) p.et = ET_ET3;
-  else p.et = p.chain ? ET_CHAIN : ET_GEMM;
+  else p.et = p.fused_node ? ET_CHAIN : ET_GEMM;
   p.et_rows = unfolded ? ETR_ROWS : p.et == ET_ET4 && p.transition == NF_ROWS16 && op == OP_ALL ? ETR_FOLDED : ETR_IMAGES;
   // Round 6: o_pair reads pair_z = down_z(z) + b (32 channels) emitted by the producers of the pair bias above (edge_transition4 only)
   // instead of streaming the 128 channels of z once more per block (opair_pz_kernel).  FDIPT_KF_UNFOLDED / FDIPT_KF_PASS_Z keep the pass
@@ -767,8 +763,8 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   ProjArgs pj = {};
   pj.B = B; pj.N = N; pj.H = H; pj.C = C; pj.K = cs; pj.PT = iv.proj_out - 3 * H * C; pj.Np = Np; pj.lda = cs;
   pj.W_img = proj_image(d) ? &kImage : nullptr;
-  pj.W_img_lo = pj.W_img && p.split ? &kImage : nullptr;
-  // Merged projections (the default of the split mode at the reference widths): no k, no v — the node rows are keys and values of
+  pj.W_img_lo = pj.W_img && p.fused_node ? &kImage : nullptr;
+  // Merged projections (the default of the fused node path): no k, no v — the node rows are keys and values of
   // every head (fd_node_images), q' = W_k^T (W_q s + b_q), W_v sits in the output projection (prepare: merge_qk / merge_vo).  40 % of
   // the projection's columns, and K / V images an eighth of the size.  Exact algebra (softmax shift invariance, linearity); the
   // per-op entries and FDIPT_KF_NO_MERGE keep the reference's formulation.
@@ -787,7 +783,7 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   p.node_rows = !p.merged || p.proj_pts ? NR_PROJ : p.vpt && (H & 1) == 0 && cs == 256 ? NR_POINTS : NR_LAUNCH;
   const int th = d->tfmr_heads, hd = iv.d_t / th;
   const bool seq_ok = p.stream ? fd_seq_attention_stream_supported(N, th, hd) : fd_seq_attention_supported(N, th, hd);
-  if (p.rbk && !generic_attn && seq_ok && fd_seq_qkv_supported(N, th, iv.d_t)) p.seq = SEQ_FUSED;
+  if (p.fused_node && !generic_attn && seq_ok && fd_seq_qkv_supported(N, th, iv.d_t)) p.seq = SEQ_FUSED;
   else if (p.bf && !generic_attn && seq_ok) p.seq = SEQ_BF16;
   else if (!p.bf && !generic_attn && fd_seq_attention_f32_supported(N, th, hd, 3 * iv.d_t)) p.seq = SEQ_F32;  // scores in registers (round 5)
   else p.seq = SEQ_GENERIC;
@@ -795,32 +791,26 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   p.ipa_attn_f32 = !p.bf && !generic_attn;
   // every once-per-forward fill of the trunk in one launch: sequence-attention images, value-point image, key pads
   p.init_fused = p.proj2 && p.seq == SEQ_FUSED && !unfolded;  // (proj2: C % 128 == 0; the value-point image: whole 16 B units)
-  // the attention weights go to the MFMA o_pair kernel as bf16 rows [b, i, h, Np] (half the bytes, no conversion pass;
-  // the fp32 buffer is reused: B N H Np bf16 <= B H N N fp32)
-  // ... and both kernels write the attention features as bf16 rows when the output projection is the bf16 split-K GEMM
-  // (the values it would round them to anyway: identical results, half the bytes, no conversion in its staging)
-  p.feats_h16 = p.a3 && opair_mfma && splitk && (iv.feat_dim & 7) == 0 && !p.split && op == OP_ALL;  // (split: the projection splits the features itself)
-  // K = 2688 in slices: 4x the blocks, a quarter of the dependent k-iterations (7 slices: slower).  Split operands: 3 slices
-  // (70 KB of LDS per block = two blocks per CU: at B N = 2400 rows 456 blocks run in one round of the 256 CUs, 30 us;
-  // 4 slices = 608 blocks need two rounds, 41 us).  The slice count must not depend on the batch size: the order of the
+  // (the attention weights go to the MFMA o_pair kernel as bf16 rows [b, i, h, Np]: half the bytes, no conversion pass; the fp32
+  // buffer is reused: B N H Np bf16 <= B H N N fp32)
+  // K = 2688 in 3 slices (70 KB of LDS per block = two blocks per CU: at B N = 2400 rows 456 blocks run in one round of the 256 CUs,
+  // 30 us; 4 slices = 608 blocks need two rounds, 41 us).  The slice count must not depend on the batch size: the order of the
   // partial sums is part of a sample's result (sub-batches and sharded runs reproduce the whole-batch result bit for bit)
   if (!splitk) p.outproj = OUT_GEMM;
-  else if (p.split && p.merged && outproj_image(d, iv)) p.outproj = OUT_DEDICATED;
-  else p.outproj = p.split ? OUT_SPLITK_SPLIT : p.feats_h16 ? OUT_SPLITK_A16 : OUT_SPLITK;
-  p.slices = p.outproj == OUT_DEDICATED ? fd_outproj_split_slices() : p.split ? 3 : 4;
+  else p.outproj = p.merged && outproj_image(d, iv) ? OUT_DEDICATED : OUT_SPLITK_SPLIT;
+  p.slices = p.outproj == OUT_DEDICATED ? fd_outproj_split_slices() : 3;
   // the last layer's tail also applies post_tfmr + the node residual (FDIPT_KF_UNFOLDED: its own launch)
-  p.post = p.rbk && !unfolded ? POST_TAIL : p.chain ? POST_CHAIN : POST_GEMM;
+  p.post = !p.fused_node ? POST_GEMM : unfolded ? POST_CHAIN : POST_TAIL;
   // the last torsion layer (Linear(c_s, 2), fp32) and the backbone atoms ride on the score launch (FDIPT_KF_UNFOLDED: own launches)
   p.torf_fused = (cs & 3) == 0 && !unfolded;
   p.bb_fold = !unfolded;
   // fp16x runs only where its split kernel takes every EdgeTransition, with split operands on the node path; the flags that swap out
   // the split kernels (include/fdipt.h) are refused as well, whichever kernels they would touch at this shape
   p.x = d->precision == FDIPT_PREC_F16X;
-  const unsigned x_refused = FDIPT_KF_ET3 | FDIPT_KF_GENERIC_PAIR | FDIPT_KF_GENERIC_ATTN | FDIPT_KF_UNFUSED_NODE | FDIPT_KF_NO_SPLIT |
-                             FDIPT_KF_STREAM_ATTN;
+  const unsigned x_refused = FDIPT_KF_ET3 | FDIPT_KF_GENERIC_PAIR | FDIPT_KF_GENERIC_ATTN | FDIPT_KF_UNFUSED_NODE | FDIPT_KF_STREAM_ATTN;
   // (the EdgeTransition test only where one runs: the embedder's per-op entry takes any N; N > 1024 is the key-streaming kernels' range)
   const bool runs_et = op == OP_ALL || op == OP_ET;
-  p.refused = p.x && ((f & x_refused) || (runs_et && p.et != ET_ET4) || !p.split || N > 1024);
+  p.refused = p.x && ((f & x_refused) || (runs_et && p.et != ET_ET4) || !p.fused_node || N > 1024);
   return p;
 }
 
@@ -875,7 +865,7 @@ struct Fwd {
     switch (next) {
       case WARM_QKV: {  // layer l's in_proj (fd_seq_qkv)
         const unsigned n = (unsigned)fd_chain_image_bytes(3 * dt, dt);
-        return L2Warm{{D + db.ch.inp[l], p.split ? D + db.lo.inp[l] : nullptr, nullptr}, {n, p.split ? n : 0u, 0}};
+        return L2Warm{{D + db.ch.inp[l], D + db.lo.inp[l], nullptr}, {n, n, 0}};
       }
       case WARM_TAIL: {  // layer l's tail (fd_tfmr_tail)
         // its three hi images and its three lo images (the last layer's runs end with post_tfmr)
@@ -886,19 +876,18 @@ struct Fwd {
       case WARM_POST: return L2Warm{{D + db.ch.post, nullptr, nullptr}, {(unsigned)fd_chain_image_bytes(cs, dt), 0, 0}};
       case WARM_TRANSITION:
         if (p.transition == NF_ROWS16) return L2Warm{{D + db.lo.tr16[0][0], D + db.lo.tr16[0][1], nullptr}, {db.lo.tr16_run, db.lo.tr16_run, 0}};
-        if (p.split) return L2Warm{{D + db.ch.t1, D + db.ch.t2, D + db.lo.t1}, {tb, db.ch.t23_run, db.lo.t_run}};
-        [[fallthrough]];
+        return L2Warm{{D + db.ch.t1, D + db.ch.t2, D + db.lo.t1}, {tb, db.ch.t23_run, db.lo.t_run}};
       case WARM_TRANSITION32:  // (the post_tfmr chain hands over the 32-row hi images whatever the transition form)
         return L2Warm{{D + db.ch.t1, D + db.ch.t2, D + db.ch.t3}, {tb, tb, tb}};
       case WARM_ET_ROWS: {  // the EdgeTransition row launch
         const unsigned ei = (unsigned)fd_chain_image_bytes(iv.cb, cs), r4 = (unsigned)fd_chain_image_bytes(2 * (iv.hid + d->c_z), iv.cb);
-        return L2Warm{{D + db.ch.et_init, D + db.ch.r4w, p.split ? D + db.lo.et_init : nullptr}, {ei, r4, p.split ? db.lo.et_run : 0u}};
+        return L2Warm{{D + db.ch.et_init, D + db.ch.r4w, D + db.lo.et_init}, {ei, r4, db.lo.et_run}};
       }
       case WARM_ET_FOLDED:  // the transition launch's own later-stage images (hi run, lo run)
         return L2Warm{{D + db.lo.ei16[0], D + db.lo.ei16[1], nullptr}, {db.lo.et16_run, db.lo.et16_run, 0}};
       case WARM_TORSION:
         if (p.torsion == NF_ROWS16) return L2Warm{{D + L.tor16[0][0], D + L.tor16[0][1], nullptr}, {L.tor16_run, L.tor16_run, 0}};
-        return L2Warm{{D + L.ch_tor1, D + L.ch_tor2, p.split ? D + L.lo_tor1 : nullptr}, {tb, tb, p.split ? L.lo_tor_run : 0u}};
+        return L2Warm{{D + L.ch_tor1, D + L.ch_tor2, D + L.lo_tor1}, {tb, tb, L.lo_tor_run}};
     }
     return L2Warm{};
   }
@@ -920,9 +909,7 @@ struct Fwd {
       RowBlockArgs r;
       r.M = R; r.in = F(w.node_feat); r.ld_in = L.kn_pad;
       r.w0 = D + (r16 ? L.ne16[0][0] : L.ch_ne0); r.w1 = D + (r16 ? L.ne16[1][0] : L.ch_ne2); r.w2 = D + (r16 ? L.ne16[2][0] : L.ch_ne4);
-      if (p.split) {
-        r.w0l = D + (r16 ? L.ne16[0][1] : L.lo_ne0); r.w1l = D + (r16 ? L.ne16[1][1] : L.lo_ne2); r.w2l = D + (r16 ? L.ne16[2][1] : L.lo_ne4);
-      }
+      r.w0l = D + (r16 ? L.ne16[0][1] : L.lo_ne0); r.w1l = D + (r16 ? L.ne16[1][1] : L.lo_ne2); r.w2l = D + (r16 ? L.ne16[2][1] : L.lo_ne4);
       r.b0 = P + iv.ne0.b; r.b1 = P + iv.ne2.b; r.b2 = P + iv.ne4.b;
       r.gamma = P + iv.neln.g; r.beta = P + iv.neln.b; r.rowmask_post = a->res_mask; r.out = F(w.node0); r.ld_out = cs;
       if (p.skip == SKIP_EMBED16) {  // skip_embed(init_node) of all blocks as a fourth layer of the same launch
@@ -933,7 +920,6 @@ struct Fwd {
         r.warm = L2Warm{{r.w0, r.w0l, r.w3}, {L.ne16_run, L.ne16_run, L.skip16_run}};
       }
       if (r16) RC(fd_node_embed16(r, L.kn_pad, st));
-      else if (p.split) RC(fd_rowblock(L.kn_pad == 72 ? FD_RB_NODE_EMBED_72_SPLIT : FD_RB_NODE_EMBED_88_SPLIT, r, st));
       else RC(fd_rowblock(L.kn_pad == 72 ? FD_RB_NODE_EMBED_72 : FD_RB_NODE_EMBED_88, r, st));
     }
     if (!p.feats_fused) {
@@ -978,7 +964,7 @@ struct Fwd {
     pj.Qb = (half_t*)(W + w.qb); pj.Kb = (half_t*)(W + w.kb); pj.Vt = (half_t*)(W + w.vt); pj.pts = F(w.pts);
     pj.zero_pads = first_block(b);
     pj.W_img = proj_image(d) ? D + db.wproj_img : nullptr;
-    pj.W_img_lo = pj.W_img && p.split ? D + db.wproj_img_lo : nullptr;
+    pj.W_img_lo = pj.W_img && p.fused_node ? D + db.wproj_img_lo : nullptr;
     if (p.merged) { pj.merged = 1; pj.W_img = D + db.wproj2_img; pj.W_img_lo = D + db.wproj2_img_lo; pj.bias = (const float*)(D + db.bproj2); }
     if (p.proj_pts) {
       pj.pts_img = 1; pj.W_img = D + db.wproj2p_img; pj.W_img_lo = D + db.wproj2p_img_lo; pj.bias = (const float*)(D + db.bproj2p);
@@ -1005,7 +991,7 @@ struct Fwd {
         vpt_zero = false;
       }
       RC(fd_ipa_proj2(pj, st));
-      half_t* vt_lo = p.split ? (half_t*)(W + w.vt_lo) : nullptr;
+      half_t* vt_lo = (half_t*)(W + w.vt_lo);  // (the node-row launches: merged projection, which runs on split operands)
       if (p.node_rows == NR_POINTS) { pa.node = node; pa.ld_node = cs; pa.nKb = pj.Kb; pa.nVt = pj.Vt; pa.nVt_lo = vt_lo; }
       if (p.node_rows == NR_LAUNCH) RC(fd_node_images(B, N, Np, node, cs, pj.Kb, pj.Vt, vt_lo, st));
     } else RC(fd_ipa_proj(pj, st));
@@ -1021,7 +1007,7 @@ struct Fwd {
     OPairArgs oa;
     oa.B = B; oa.N = N; oa.H = H; oa.CZ = cz; oa.CD = cz / 4; oa.z = W + w.z; oa.probs = F(w.probs); oa.probs_h16 = nullptr;
     oa.probs_np = 0; oa.out_h16 = nullptr; oa.wdz = (const float*)(D + db.wdz_t); oa.wdz_img = p.bf && dz_images(d) ? D + db.wdz_img : nullptr;
-    oa.wdz_img_lo = oa.wdz_img && p.split ? D + db.wdz_img_lo : nullptr; oa.bdz = P + iv.blk[b].dz.b;
+    oa.wdz_img_lo = oa.wdz_img && p.fused_node ? D + db.wdz_img_lo : nullptr; oa.bdz = P + iv.blk[b].dz.b;
     oa.out = F(w.feats); oa.out_ld = feat; oa.off = H * C + 4 * H * Pv;
     if (p.a3) {
       Attn3Args a3;
@@ -1032,7 +1018,6 @@ struct Fwd {
       a3.probs = F(w.probs); a3.probs_h16 = nullptr; a3.out_h16 = nullptr; a3.out = F(w.feats); a3.out_ld = feat; a3.pt_off = H * C;
       if (!bias_ready(b))
         RC(fd_pair_bias2(B, N, H, W + w.z, D + db.wb, (const float*)(D + db.bb), F(w.bias), 1, st));
-      if (p.feats_h16) { a3.out_h16 = (half_t*)(W + w.feats); oa.out_h16 = a3.out_h16; }
       if (p.probs_h16) { a3.probs_h16 = (half_t*)(W + w.probs); oa.probs_h16 = a3.probs_h16; oa.probs_np = Np; }
       RC(p.stream ? fd_attention3_stream(a3, st) : fd_attention3(a3, st));
     } else {
@@ -1076,13 +1061,8 @@ struct Fwd {
     }
     if (p.outproj == OUT_DEDICATED)
       RC(fd_outproj_split(R, cs, feat, F(w.feats), feat, D + db.wout_img, D + db.wout_img_lo, bout, res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
-    else if (p.outproj == OUT_SPLITK_SPLIT)
-      RC(fd_linear_splitk_split(R, cs, feat, p.slices, F(w.feats), feat, wout, feat, bout, res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
-    else if (p.outproj == OUT_SPLITK_A16)
-      RC(fd_linear_splitk_a16(R, cs, feat, p.slices, (const half_t*)(W + w.feats), feat, WM(k.out), feat, P + k.out.b, res_mask,
-                              F(w.ipa_parts), (long)R * cs, cs, st));
     else
-      RC(fd_linear_splitk(R, cs, feat, p.slices, F(w.feats), feat, WM(k.out), feat, P + k.out.b, res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
+      RC(fd_linear_splitk_split(R, cs, feat, p.slices, F(w.feats), feat, wout, feat, bout, res_mask, F(w.ipa_parts), (long)R * cs, cs, st));
     // the slices summed in the LayerNorm, which also copies skip_embed(init_node) of this block behind its output when that ran batched
     const bool skip_batched = p.skip != SKIP_PER_BLOCK;
     const L2Warm warm = warm_of(b, WARM_QKV, 0);
@@ -1104,7 +1084,7 @@ struct Fwd {
       const bool last = l + 1 == d->tfmr_layers;
       if (p.seq == SEQ_FUSED) {  // default bf16 path: in_proj writes the attention operand images directly (attention_seq.hip)
         if (b == 0 && l == 0 && !p.init_fused) RC(fd_seq_images_init(B, N, th, res_mask, W + w.seqimg, SeqInitExtra{}, st, p.stream));
-        RC(fd_seq_qkv(B, N, th, x, dt, D + db.ch.inp[l], p.split ? D + db.lo.inp[l] : nullptr, P + t.inp.b, 1.0f / sqrtf((float)hd),
+        RC(fd_seq_qkv(B, N, th, x, dt, D + db.ch.inp[l], D + db.lo.inp[l], P + t.inp.b, 1.0f / sqrtf((float)hd),
                       W + w.seqimg, st));
         const L2Warm wt = warm_of(b, WARM_TAIL, l);  // ... and the attention touches the weights of the layer's tail kernel, launched next
         RC(fd_seq_attention_run(B, N, th, W + w.seqimg, F(w.att), dt, &wt, st, p.stream));
@@ -1133,13 +1113,13 @@ struct Fwd {
       TfmrTailArgs tt;
       tt.M = R; tt.ld = dt; tt.att = F(w.att); tt.x = x;
       tt.wo = D + (r16 ? db.lo.o16[l][0] : db.ch.outp[l]); tt.w1 = D + (r16 ? db.lo.f16[l][0] : db.ch.l1[l]); tt.w2 = D + (r16 ? db.lo.g16[l][0] : db.ch.l2[l]);
-      if (p.split) { tt.wol = D + (r16 ? db.lo.o16[l][1] : db.lo.outp[l]); tt.w1l = D + (r16 ? db.lo.f16[l][1] : db.lo.l1[l]); tt.w2l = D + (r16 ? db.lo.g16[l][1] : db.lo.l2[l]); }
+      tt.wol = D + (r16 ? db.lo.o16[l][1] : db.lo.outp[l]); tt.w1l = D + (r16 ? db.lo.f16[l][1] : db.lo.l1[l]); tt.w2l = D + (r16 ? db.lo.g16[l][1] : db.lo.l2[l]);
       tt.bo = P + t.outp.b; tt.g1 = P + t.n1.g; tt.be1 = P + t.n1.b; tt.b1 = P + t.l1.b; tt.b2 = P + t.l2.b; tt.g2 = P + t.n2.g;
       tt.be2 = P + t.n2.b; tt.out = x == F(w.x_b) ? F(w.x_a) : F(w.x_b);
       tt.rows16 = r16;
       const bool post_here = last && p.post == POST_TAIL;
       if (post_here) {
-        tt.wp = D + (r16 ? db.lo.p16[0] : db.ch.post); tt.wpl = r16 ? D + db.lo.p16[1] : p.split ? D + db.lo.post : nullptr;
+        tt.wp = D + (r16 ? db.lo.p16[0] : db.ch.post); tt.wpl = D + (r16 ? db.lo.p16[1] : db.lo.post);
         tt.bp = P + k.post.b; tt.pres = F(w.tf_in); tt.ld_pres = dt; tt.pout = F(w.h_a); tt.ld_pout = cs;
       }
       // next launch: the following layer's in_proj, or the transition / post_tfmr
@@ -1161,7 +1141,7 @@ struct Fwd {
       ChainArgs c;
       c.M = R; c.in = x; c.ld_in = dt; c.w[0] = D + db.ch.post; c.b[0] = P + k.post.b; c.residual = F(w.tf_in); c.ld_res = dt;
       c.out = F(w.h_a); c.ld_out = cs;
-      if (p.rbk) c.warm = warm_of(b, WARM_TRANSITION32);
+      c.warm = warm_of(b, WARM_TRANSITION32);
       RC(fd_chain(FD_CHAIN_POST, c, st));
     } else if (p.post == POST_GEMM) RC(lin(k.post, x, dt, F(w.tf_in), dt, nullptr, 0, F(w.h_a), cs));
     if (p.transition == NF_GEMM) {
@@ -1180,7 +1160,7 @@ struct Fwd {
     RowBlockArgs r;
     r.M = R; r.in = F(w.h_a); r.ld_in = cs;
     r.w0 = D + (r16 ? db.lo.tr16[0][0] : db.ch.t1); r.w1 = D + (r16 ? db.lo.tr16[1][0] : db.ch.t2); r.w2 = D + (r16 ? db.lo.tr16[2][0] : db.ch.t3);
-    if (p.split) { r.w0l = D + (r16 ? db.lo.tr16[0][1] : db.lo.t1); r.w1l = D + (r16 ? db.lo.tr16[1][1] : db.lo.t2); r.w2l = D + (r16 ? db.lo.tr16[2][1] : db.lo.t3); }
+    r.w0l = D + (r16 ? db.lo.tr16[0][1] : db.lo.t1); r.w1l = D + (r16 ? db.lo.tr16[1][1] : db.lo.t2); r.w2l = D + (r16 ? db.lo.tr16[2][1] : db.lo.t3);
     r.b0 = P + k.t1.b; r.b1 = P + k.t2.b; r.b2 = P + k.t3.b; r.residual = F(w.h_a); r.ld_res = cs; r.gamma = P + k.tln.g; r.beta = P + k.tln.b;
     r.rowmask_post = a->res_mask; r.out = F(w.node); r.ld_out = cs; r.bb_w = P + k.bb.w; r.bb_b = P + k.bb.b;
     r.upd_mask = F(w.dmask); r.quat = F(w.quat); r.trans = F(w.trans);
@@ -1196,7 +1176,7 @@ struct Fwd {
       r.warm = warm_of(b, WARM_ET_FOLDED);
     }
     if (r16) return fd_transition16(r, st);
-    return fd_rowblock(p.split ? FD_RB_TRANSITION_BB_SPLIT : FD_RB_TRANSITION_BB, r, st);
+    return fd_rowblock(FD_RB_TRANSITION_BB, r, st);
   }
   // ---- EdgeTransition of block b (ipa:565-572 / 60-96): z <- EdgeTransition(node, z)
   int edge_transition_stage(int b, const float* node) const {
@@ -1213,7 +1193,7 @@ struct Fwd {
         RC(fd_rowblock(FD_RB_ET4_ROWS, r, st));
         RC(fd_et4_row_images(F(w.r4), B, N, W + w.a1img, W + w.b1img, st));
       } else {  // the row-block epilogue writes the fold-fragment images itself
-        if (p.split) { r.w0l = D + db.lo.et_init; r.w1l = D + db.lo.r4w; }
+        r.w0l = D + db.lo.et_init; r.w1l = D + db.lo.r4w;
         RC(fd_rowblock(FD_RB_ET4_IMAGES, r, st));
       }
     } else if (p.et == ET_ET3) {  // A1 | Af rows and e in half precision
@@ -1272,10 +1252,10 @@ struct Fwd {
       const bool r16 = p.torsion == NF_ROWS16;
       RowBlockArgs r;
       r.M = R; r.in = node; r.ld_in = cs; r.w0 = D + (r16 ? L.tor16[0][0] : L.ch_tor1); r.w1 = D + (r16 ? L.tor16[1][0] : L.ch_tor2);
-      if (p.split) { r.w0l = D + (r16 ? L.tor16[0][1] : L.lo_tor1); r.w1l = D + (r16 ? L.tor16[1][1] : L.lo_tor2); }
+      r.w0l = D + (r16 ? L.tor16[0][1] : L.lo_tor1); r.w1l = D + (r16 ? L.tor16[1][1] : L.lo_tor2);
       r.b0 = P + iv.tor1.b; r.b1 = P + iv.tor2.b; r.residual = node; r.ld_res = cs; r.out = F(w.h_b); r.ld_out = cs;
       if (r16) RC(fd_torsion16(r, st));
-      else RC(fd_rowblock(p.split ? FD_RB_TORSION_SPLIT : FD_RB_TORSION, r, st));
+      else RC(fd_rowblock(FD_RB_TORSION, r, st));
     }
     if (!p.torf_fused) RC(lin32(iv.torf, F(w.h_b), cs, F(w.psi_un), 8));
     // tensor_7 / psi epilogue, R^3 score and IGSO(3) score in one launch (frames.hip); the backbone atoms of the finished frames ride on it
@@ -1321,7 +1301,7 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
   const ForwardPlan p = plan_forward(d, iv, L, B, N, op.kind);
   if (p.refused) return FDIPT_EINVAL;
   const Fwd f = {d, iv, L, w, p, P, (const char*)derived, (char*)workspace, setup, a, (hipStream_t)stream, B, N, R, (N + 31) / 32 * 32, (size_t)R * N};
-  if (a->trace_inner && (p.rbk || p.outproj != OUT_GEMM)) return FDIPT_EINVAL;  // fused node path: the tensors never exist
+  if (a->trace_inner && (p.fused_node || p.outproj != OUT_GEMM)) return FDIPT_EINVAL;  // fused node path: the tensors never exist
   const size_t node_bytes = (size_t)R * d->c_s * 4, z_bytes = f.NN * d->c_z * L.esz;
   if (op.kind == OP_ALL || op.kind == OP_EMBED) RC(f.embed_stage());
   if (op.kind == OP_EMBED) {
@@ -1364,9 +1344,6 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
   if (p.skip == SKIP_SPLITK)
     RC(fd_linear_splitk_split(R, nsk, cs, 1, f.F(w.node0), cs, (const float*)(f.D + L.skip_w32), cs, (const float*)(f.D + L.skip_b),
                               nullptr, f.F(w.skip_all), 0, nsk, f.st));
-  else if (p.skip == SKIP_GEMM)
-    RC(fd_linear(op_precision(d), R, nsk, cs, f.F(w.node0), cs, f.D + L.skip_w, cs, (const float*)(f.D + L.skip_b), nullptr, 0,
-                 nullptr, 0, f.F(w.skip_all), nsk, f.st));
   const float* node = f.F(w.node0);
   for (int b = 0; b < d->num_blocks; ++b) {
     const float* x;

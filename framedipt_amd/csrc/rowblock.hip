@@ -455,17 +455,17 @@ __global__ __launch_bounds__(FD_THREADS, 1) void rowblock_kernel(RowBlockArgs a)
 #define TL_NT (TL_D / 32)
 #define TL_XROW (TL_D * 2 + 16)
 #define TL_NP 256  // post_tfmr output width (POST variant)
-#define TL_SMEM(SPLIT) (((SPLIT) ? 4 : 2) * 32 * TL_XROW + 4 * 32 * RB_SROW + (7 * TL_D + TL_NP) * 4 + 2 * 4 * 32 * 4 + 16)
+#define TL_SMEM (4 * 32 * TL_XROW + 4 * 32 * RB_SROW + (7 * TL_D + TL_NP) * 4 + 2 * 4 * 32 * 4 + 16)
 // POST: the last layer of the stack also applies post_tfmr (Linear d_model -> c_s) + the node residual (ipa:539) to its own
 // output rows, which then never go to memory.
-// SPLIT: every product on split operands (activations and weights as hi + lo half-precision parts, 3 MFMAs per k-step; see
+// Every product runs on split operands (activations and weights as hi + lo half-precision parts, 3 MFMAs per k-step; see
 // rowblock_kernel): wol / w1l / w2l / wpl are the lo images.
-template <bool POST, bool SPLIT>
+template <bool POST>
 __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* xs = smem;                                            // att rows, then hidden rows   [32][TL_XROW]
-  constexpr int XLO = 32 * TL_XROW;                           // SPLIT: the lo rows follow the hi rows of a buffer
-  constexpr int XBUF = SPLIT ? 2 * XLO : XLO;
+  constexpr int XLO = 32 * TL_XROW;                           // the lo rows follow the hi rows of a buffer
+  constexpr int XBUF = 2 * XLO;
   char* hs = xs + XBUF;                                       // x_a rows                     [32][TL_XROW]
   char* st_all = hs + XBUF;                                   // per-wave exchange tiles      [4][32][RB_SROW]
   float* cst = (float*)(st_all + 4 * 32 * RB_SROW);           // b_o | g1 | be1 | b1 | b2 | g2 | be2 | b_post
@@ -474,25 +474,25 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
   const int row0 = blockIdx.x * 32;
   char* stg = st_all + wave * 32 * RB_SROW;
   FD_STAMP(0);
-  // SPLIT: THREE fragment buffers.  Tile u of a wave has its hi fragments in buffer (2 u) % 3 and its lo fragments in (2 u + 1) % 3; the
+  // THREE fragment buffers.  Tile u of a wave has its hi fragments in buffer (2 u) % 3 and its lo fragments in (2 u + 1) % 3; the
   // third buffer is free while tile u runs and takes tile u + 1's hi fragments at the START of tile u, the lo fragments follow into the hi
   // buffer once tile u's hi products are done: every fragment load has a whole tile (60 matrix instructions) of lead instead of the 20 lo
   // products.  The 80 registers come from the lo parts of the activation fragments, which the hi x lo pass now reads from LDS (a 3-deep
   // ring, one read per product).  Measured (tools/micro/tt_bench.hip 1): the three stages 9.9 / 9.5 / 8.7 k -> 9.0 / 9.0 / 8.5 k cycles,
   // 24.3 -> 23.0 us stand-alone — the lead was not what bounds a stage: 400 KB of hi + lo fragments per block and stage through the
   // CU's 64 B/clk L2 path are 6.4 k cycles next to 5.8 k of matrix work.
-  hx8 Wf[SPLIT ? 3 : 2][TL_KS];
+  hx8 Wf[3][TL_KS];
   auto w_load = [&](auto BUF, const char* img, int T) {
     constexpr int bf = decltype(BUF)::value;
 #pragma unroll
     for (int s = 0; s < TL_KS; ++s) Wf[bf][s] = fd_frag(img + ((size_t)(T * TL_KS + s) * 64 + lane) * 16);
   };
-  // first tile of a stage: hi fragments -> buffer 0 (SPLIT: lo fragments -> buffer 1)
+  // first tile of a stage: hi fragments -> buffer 0, lo fragments -> buffer 1
   auto w_first = [&](const void* img, const void* img_lo) {
     w_load(std::integral_constant<int, 0>{}, (const char*)img, wave);
-    if constexpr (SPLIT) w_load(std::integral_constant<int, 1>{}, (const char*)img_lo, wave);
+    w_load(std::integral_constant<int, 1>{}, (const char*)img_lo, wave);
   };
-  // 4 values -> half-precision row pieces at byte offset `off` of an activation buffer (SPLIT: hi and lo parts)
+  // 4 values -> half-precision row pieces (hi and lo parts) at byte offset `off` of an activation buffer
   auto put4 = [&](char* buf, int off, float v0, float v1, float v2, float v3) {
     const float v[4] = {v0, v1, v2, v3};
     hx4 pk, pl;
@@ -502,7 +502,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
       pl[q] = (fd_h)(v[q] - (float)pk[q]);
     }
     *(hx4*)(buf + off) = pk;
-    if constexpr (SPLIT) *(hx4*)(buf + XLO + off) = pl;
+    *(hx4*)(buf + XLO + off) = pl;
   };
   w_first(a.wo, a.wol);
   {
@@ -551,13 +551,12 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
         rvp[u][it] = *(const f32x4*)(a.pres + (long)gr * a.ld_pres + 32 * (wave + 4 * u) + 4 * (lane & 7));
       }
   };
-  if constexpr (POST && !SPLIT) load_rvp();  // (SPLIT: requested after the feed-forward, the registers are needed until then)
   const unsigned warm_tok = fd_l2_warm(a.warm, blockIdx.x, gridDim.x, tid, FD_THREADS);
   __syncthreads();
   FD_STAMP(1);
   hx8 X[TL_KS];
   f32x16 acc[3], xa[3];
-  const char* xl_base = nullptr;  // SPLIT: this lane's lo fragments of the current stage input (LDS)
+  const char* xl_base = nullptr;  // this lane's lo fragments of the current stage input (LDS)
   auto x_load = [&](const char* buf) {
 #pragma unroll
     for (int s = 0; s < TL_KS; ++s) X[s] = fd_frag(buf + li * TL_XROW + 32 * s + 16 * hi);
@@ -571,45 +570,31 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
       constexpr int u = decltype(U)::value;
       const int T = wave + 4 * u;
       const bool more = u + 1 < NU && T + 4 < NT;
-      if constexpr (SPLIT) {  // Whi.xhi + Whi.xlo out of buffer HB, Wlo.xhi out of buffer LB; the free buffer takes the next hi fragments
-        constexpr int HB = (2 * u) % 3, LB = (2 * u + 1) % 3, FB = (2 * u + 2) % 3;
-        if (more) w_load(std::integral_constant<int, FB>{}, img, T + 4);
-        if (T < NT) {
-          f32x16 c;
+      // Whi.xhi + Whi.xlo out of buffer HB, Wlo.xhi out of buffer LB; the free buffer takes the next hi fragments
+      constexpr int HB = (2 * u) % 3, LB = (2 * u + 1) % 3, FB = (2 * u + 2) % 3;
+      if (more) w_load(std::integral_constant<int, FB>{}, img, T + 4);
+      if (T < NT) {
+        f32x16 c;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) c[r] = 0.f;
+        for (int r = 0; r < 16; ++r) c[r] = 0.f;
 #pragma unroll
-          for (int s = 0; s < TL_KS; ++s) c = fd_mfma32(Wf[HB][s], X[s], c);
-          {  // hi x lo: the lo fragments of the activations from LDS, three reads in flight
-            hx8 xr[3];
-            xr[0] = fd_frag(xl_base);
-            xr[1] = fd_frag(xl_base + 32);
-            __builtin_amdgcn_sched_barrier(0);
+        for (int s = 0; s < TL_KS; ++s) c = fd_mfma32(Wf[HB][s], X[s], c);
+        {  // hi x lo: the lo fragments of the activations from LDS, three reads in flight
+          hx8 xr[3];
+          xr[0] = fd_frag(xl_base);
+          xr[1] = fd_frag(xl_base + 32);
+          __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int s = 0; s < TL_KS; ++s) {
-              if (s + 2 < TL_KS) xr[(s + 2) % 3] = fd_frag(xl_base + 32 * (s + 2));
-              c = fd_mfma32(Wf[HB][s], xr[s % 3], c);
-              __builtin_amdgcn_sched_barrier(0);  // pin: one read, one product per k-step (hipcc otherwise sinks the reads to their uses)
-            }
+          for (int s = 0; s < TL_KS; ++s) {
+            if (s + 2 < TL_KS) xr[(s + 2) % 3] = fd_frag(xl_base + 32 * (s + 2));
+            c = fd_mfma32(Wf[HB][s], xr[s % 3], c);
+            __builtin_amdgcn_sched_barrier(0);  // pin: one read, one product per k-step (hipcc otherwise sinks the reads to their uses)
           }
-          if (more) w_load(std::integral_constant<int, HB>{}, img_lo, T + 4);
-#pragma unroll
-          for (int s = 0; s < TL_KS; ++s) c = fd_mfma32(Wf[LB][s], X[s], c);
-          acc[u] = c;
         }
-      } else {
-        if (more) {
-          if (u & 1) w_load(std::integral_constant<int, 0>{}, img, T + 4);
-          else w_load(std::integral_constant<int, 1>{}, img, T + 4);
-        }
-        if (T < NT) {
-          f32x16 c;
+        if (more) w_load(std::integral_constant<int, HB>{}, img_lo, T + 4);
 #pragma unroll
-          for (int r = 0; r < 16; ++r) c[r] = 0.f;
-#pragma unroll
-          for (int s = 0; s < TL_KS; ++s) c = fd_mfma32(Wf[u & 1][s], X[s], c);
-          acc[u] = c;
-        }
+        for (int s = 0; s < TL_KS; ++s) c = fd_mfma32(Wf[LB][s], X[s], c);
+        acc[u] = c;
       }
     });
   };
@@ -720,7 +705,7 @@ __global__ __launch_bounds__(FD_THREADS, 1) void tfmr_tail_kernel(TfmrTailArgs a
         for (int q = 0; q < 4; ++q) acc[u][4 * g + q] += bv[q] + xa[u][4 * g + q];
       }
   }
-  if constexpr (POST && SPLIT) load_rvp();
+  if constexpr (POST) load_rvp();  // (requested only now: the registers are needed until the feed-forward is done)
   if constexpr (POST) w_first(a.wp, a.wpl);  // first post_tfmr tile: in flight across the LayerNorm
   layernorm(cst + 5 * TL_D, cst + 6 * TL_D);
   FD_STAMP(8);
@@ -1019,7 +1004,7 @@ __global__ __launch_bounds__(FD_THREADS, RB16_BLOCKS) void tfmr_tail16_kernel(Tf
 }
 
 // ------------------------------------------------------------------ StructureModuleTransition + LayerNorm + mask + BackboneUpdate on 16-row blocks
-// rowblock_kernel<256,256,256,256, relu | relu | LN | BB | SPLIT> (FD_RB_TRANSITION_BB_SPLIT) in the shape of tfmr_tail16_kernel: three stages
+// rowblock_kernel<256,256,256,256, relu | relu | LN | BB | SPLIT> (FD_RB_TRANSITION_BB) in the shape of tfmr_tail16_kernel: three stages
 // 256 -> 256 (ReLU, ReLU, -), + residual, LayerNorm, row mask, then BackboneUpdate (Linear 256 -> 6) and compose_q_update_vec in place
 // (ipa_pytorch.py:365-413,542-545; rigid_utils.py:587-616,1039-1063).  Images: fd_chain_build_image16 (hi, lo) of the three matrices.
 #define TR_D 256
@@ -1379,7 +1364,7 @@ static int mlp16_launch(const RowBlockArgs& a, int k0, hipStream_t st) {
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
-// FD_RB_TRANSITION_BB_SPLIT on 16-row blocks
+// FD_RB_TRANSITION_BB on 16-row blocks
 int fd_transition16(const RowBlockArgs& a, hipStream_t st) {
   if (a.M <= 0 || (a.ld_in & 3) || (a.ld_res & 3) || (a.ld_out & 3) || !a.w0l || !a.w1l || !a.w2l || !a.residual || !a.gamma || !a.beta || !a.bb_w ||
       !a.bb_b || !a.quat || !a.trans)
@@ -1390,7 +1375,7 @@ int fd_transition16(const RowBlockArgs& a, hipStream_t st) {
   }
   return mlp16_launch<8, 3, true, true>(a, TR_D, st);
 }
-// FD_RB_NODE_EMBED_72 / 88_SPLIT (k0 input features, k0 % 4 == 0, k0 <= 96) and FD_RB_TORSION_SPLIT on 16-row blocks
+// FD_RB_NODE_EMBED_72 / 88 (k0 input features, k0 % 4 == 0, k0 <= 96) and FD_RB_TORSION on 16-row blocks
 int fd_node_embed16(const RowBlockArgs& a, int k0, hipStream_t st) {
   if (a.M <= 0 || (a.ld_in & 3) || (a.ld_out & 3) || (k0 & 3) || k0 > 96 || !a.w0l || !a.w1l || !a.w2l || !a.gamma || !a.beta) return FDIPT_EINVAL;
   if (a.w3) {
@@ -1406,20 +1391,16 @@ int fd_torsion16(const RowBlockArgs& a, hipStream_t st) {
 
 int fd_tfmr_tail(const TfmrTailArgs& a, hipStream_t st) {
   if (a.M <= 0 || (a.ld & 3) || a.x == a.out) return FDIPT_EINVAL;
+  if (!a.wol || !a.w1l || !a.w2l || (a.wp && !a.wpl)) return FDIPT_EINVAL;  // split operands: every lo image must be there
   static FdPerDevice attr_dev;
   const int dev_ = fd_device();
   if (!attr_dev.get(dev_)) {
-    if (hipFuncSetAttribute((const void*)tfmr_tail_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TL_SMEM(0)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)tfmr_tail_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TL_SMEM(0)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)tfmr_tail_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TL_SMEM(1)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)tfmr_tail_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TL_SMEM(1)) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)tfmr_tail_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TL_SMEM) != hipSuccess ||
+        hipFuncSetAttribute((const void*)tfmr_tail_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TL_SMEM) != hipSuccess)
       return FDIPT_ELAUNCH;
     attr_dev.set(dev_, 1);
   }
-  const bool split = a.wol != nullptr;  // split operands: every lo image must be there
-  if (split && (!a.w1l || !a.w2l || (a.wp && !a.wpl))) return FDIPT_EINVAL;
-  if (a.rows16) {  // 16-row blocks (split operands, fd_chain_build_image16 images)
-    if (!split) return FDIPT_EINVAL;
+  if (a.rows16) {  // 16-row blocks (fd_chain_build_image16 images)
     if (a.wp && (!a.bp || !a.pres || !a.pout || (a.ld_pres & 3) || (a.ld_pout & 3))) return FDIPT_EINVAL;
     static FdPerDevice attr16;
     if (!attr16.get(dev_)) {
@@ -1435,10 +1416,8 @@ int fd_tfmr_tail(const TfmrTailArgs& a, hipStream_t st) {
   }
   if (a.wp && (!a.bp || !a.pres || !a.pout || (a.ld_pres & 3) || (a.ld_pout & 3))) return FDIPT_EINVAL;
   const dim3 grid(cdiv(a.M, 32)), block(FD_THREADS);
-  if (a.wp && split) hipLaunchKernelGGL((tfmr_tail_kernel<true, true>), grid, block, TL_SMEM(1), st, a);
-  else if (a.wp) hipLaunchKernelGGL((tfmr_tail_kernel<true, false>), grid, block, TL_SMEM(0), st, a);
-  else if (split) hipLaunchKernelGGL((tfmr_tail_kernel<false, true>), grid, block, TL_SMEM(1), st, a);
-  else hipLaunchKernelGGL((tfmr_tail_kernel<false, false>), grid, block, TL_SMEM(0), st, a);
+  if (a.wp) hipLaunchKernelGGL((tfmr_tail_kernel<true>), grid, block, TL_SMEM, st, a);
+  else hipLaunchKernelGGL((tfmr_tail_kernel<false>), grid, block, TL_SMEM, st, a);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
@@ -1464,25 +1443,21 @@ static int rb_launch(const RowBlockArgs& a, hipStream_t st) {
 // shapes of the reference network (c_s 256, d_model 320); FDIPT_EINVAL for anything else
 int fd_rowblock(int kind, const RowBlockArgs& a, hipStream_t st) {
   switch (kind) {
-    case FD_RB_TRANSITION: return rb_launch<256, 256, 256, 256, 1 | 2 | 4>(a, st);  // t1 relu t2 relu t3 + residual, LN, mask
-    case FD_RB_TRANSITION_BB: return rb_launch<256, 256, 256, 256, 1 | 2 | 4 | 8>(a, st);  // ... + BackboneUpdate + compose
-    // split-operand forms (RowBlockArgs.w0l / w1l / w2l): the node embedder, the transition and the torsion head
-    case FD_RB_TRANSITION_BB_SPLIT: return a.w0l && a.w1l && a.w2l ? rb_launch<256, 256, 256, 256, 1 | 2 | 4 | 8 | 32>(a, st) : FDIPT_EINVAL;
-    case FD_RB_NODE_EMBED_72_SPLIT: return a.w0l && a.w1l && a.w2l ? rb_launch<72, 256, 256, 256, 1 | 2 | 4 | 32>(a, st) : FDIPT_EINVAL;
-    case FD_RB_NODE_EMBED_88_SPLIT: return a.w0l && a.w1l && a.w2l ? rb_launch<88, 256, 256, 256, 1 | 2 | 4 | 32>(a, st) : FDIPT_EINVAL;
-    case FD_RB_TORSION_SPLIT: return a.w0l && a.w1l ? rb_launch<256, 256, 0, 256, 1 | 32>(a, st) : FDIPT_EINVAL;
-    case FD_RB_NODE_EMBED_72: return rb_launch<72, 256, 256, 256, 1 | 2 | 4>(a, st);
-    case FD_RB_NODE_EMBED_88: return rb_launch<88, 256, 256, 256, 1 | 2 | 4>(a, st);
-    case FD_RB_TORSION: return rb_launch<256, 256, 0, 256, 1>(a, st);            // l1 relu l2 + residual
+    // on split operands (RowBlockArgs.w0l / w1l / w2l): the transition (t1 relu t2 relu t3 + residual, LN, mask, BackboneUpdate + compose),
+    // the node embedder and the torsion head
+    case FD_RB_TRANSITION_BB: return a.w0l && a.w1l && a.w2l ? rb_launch<256, 256, 256, 256, 1 | 2 | 4 | 8 | 32>(a, st) : FDIPT_EINVAL;
+    case FD_RB_NODE_EMBED_72: return a.w0l && a.w1l && a.w2l ? rb_launch<72, 256, 256, 256, 1 | 2 | 4 | 32>(a, st) : FDIPT_EINVAL;
+    case FD_RB_NODE_EMBED_88: return a.w0l && a.w1l && a.w2l ? rb_launch<88, 256, 256, 256, 1 | 2 | 4 | 32>(a, st) : FDIPT_EINVAL;
+    case FD_RB_TORSION: return a.w0l && a.w1l ? rb_launch<256, 256, 0, 256, 1 | 32>(a, st) : FDIPT_EINVAL;  // l1 relu l2 + residual
+    // on plain operands
     case FD_RB_ET_ROWS: return rb_launch<256, 128, 0, 512, 0>(a, st);            // e = init(node); [A1 | Af] = [W1e; Wfe] e + b
     case FD_RB_ET4_ROWS: return rb_launch<256, 128, 0, 1024, 0>(a, st);          // ... [A1 | Af | B1 | Bf]: e_i and e_j columns
     case FD_RB_ET4_IMAGES:                                                        // ... written as edge_transition4's fold fragments
-      if (!a.img_a || !a.img_b || (a.img_N & 3) || a.M != a.img_B * a.img_N) return FDIPT_EINVAL;
+      if (!a.img_a || !a.img_b || (a.img_N & 3) || a.M != a.img_B * a.img_N || !a.w0l || !a.w1l) return FDIPT_EINVAL;
       // split operands (w0l / w1l): e = initial_embed(node) and the four per-residue products to fp32 accuracy before the rows are
       // rounded to the fold fragments — these rows are shared by all pairs of a residue, their errors do not average out over keys
       // ... in two column parts ([A1 | Af] and [B1 | Bf]: 150 blocks, four instead of eight output tiles per wave)
-      if (a.w0l && a.w1l) return rb_launch<256, 128, 0, 1024, 16 | 32 | 64>(a, st);
-      return rb_launch<256, 128, 0, 1024, 16>(a, st);
+      return rb_launch<256, 128, 0, 1024, 16 | 32 | 64>(a, st);
     default: return FDIPT_EINVAL;
   }
 }

@@ -48,8 +48,7 @@ extern "C" {
                              only; the forward and fdipt_edge_transition_fwd also need edge_transition4 (N % 4 == 0, N >= 8), while
                              fdipt_edge_embed_fwd takes any N.  FDIPT_EINVAL from the forward and the per-op entries otherwise,
                              and for every flag that swaps out a split kernel or the split operands: FDIPT_KF_ET3,
-                             FDIPT_KF_GENERIC_PAIR, FDIPT_KF_GENERIC_ATTN, FDIPT_KF_UNFUSED_NODE, FDIPT_KF_NO_SPLIT,
-                             FDIPT_KF_STREAM_ATTN.  Accepted flags: FDIPT_KF_UNFOLDED, FDIPT_KF_NO_MERGE, FDIPT_KF_ROWS32,
+                             FDIPT_KF_GENERIC_PAIR, FDIPT_KF_GENERIC_ATTN, FDIPT_KF_UNFUSED_NODE, FDIPT_KF_STREAM_ATTN.  Accepted flags: FDIPT_KF_UNFOLDED, FDIPT_KF_NO_MERGE, FDIPT_KF_ROWS32,
                              FDIPT_KF_PASS_Z, FDIPT_KF_POINTS_LAUNCH */
 
 /* FdiptDims.kernel_flags: run a fallback path of the half-precision mode at shapes where the default selection would not
@@ -60,8 +59,7 @@ extern "C" {
 #define FDIPT_KF_GENERIC_ATTN 4  /* attention: the LDS-score kernels (the fallback for non-reference widths) in both modes */
 #define FDIPT_KF_UNFUSED_NODE 8  /* node path as plain GEMM + LayerNorm launches (default for non-reference widths)     */
 #define FDIPT_KF_UNFOLDED 16     /* launch folds off: pair bias / feature split / torsion head / fills as own launches  */
-#define FDIPT_KF_NO_SPLIT 32     /* node-path layers on plain half-precision operands instead of split (hi + lo) operands:
-                                    ~8 % faster, 5x the error of the predicted frames / psi (precision modes)      */
+/* (bit 32 is retired and unassigned: FDIPT_EINVAL like any unknown bit) */
 #define FDIPT_KF_NO_MERGE 64     /* IPA projections in the reference's formulation (k and v explicit) instead of the merged one
                                     (keys = values = the node rows, W_k folded into the query, W_v into the output projection)  */
 #define FDIPT_KF_ROWS32 128      /* node path: the 32-row-block kernels (the default for N > 512) instead of the 16-row ones (tails, transition,
@@ -74,7 +72,7 @@ extern "C" {
                                     over key chunks, LDS and registers independent of N) for every N, and the forward accepts N <= 2048
                                     instead of 1024.  No effect in the fp32 mode or with FDIPT_KF_GENERIC_ATTN (which takes precedence):
                                     there N > 1024 stays FDIPT_ESIZE.  N > 2048 is FDIPT_ESIZE with or without the flag          */
-#define FDIPT_KF_ALL 2047
+#define FDIPT_KF_ALL 2015
 
 typedef void* fdipt_stream_t; /* hipStream_t */
 

@@ -200,7 +200,7 @@ def test_graph_replay_matches_launch_loop():
 
 
 # ------------------------------------------------------------------ refusals
-@pytest.mark.parametrize("flag", ["KF_ET3", "KF_GENERIC_PAIR", "KF_GENERIC_ATTN", "KF_UNFUSED_NODE", "KF_NO_SPLIT", "KF_STREAM_ATTN"])
+@pytest.mark.parametrize("flag", ["KF_ET3", "KF_GENERIC_PAIR", "KF_GENERIC_ATTN", "KF_UNFUSED_NODE", "KF_STREAM_ATTN"])
 def test_refuses_flags_that_drop_a_split_kernel(flag):
     from framedipt_amd import _lib
     G = load_golden("fwd_full_denovo_n64.npz")

@@ -522,11 +522,13 @@ def test_mixed_batches_stay_inside_one_kernel_selection_class():
 
 def test_kernel_flag_constants_match_the_header():
     """framedipt_amd._lib.KF_* (what ScoreNetwork(kernel_flags=...) passes in FdiptDims) against the FDIPT_KF_* macros of include/fdipt.h,
-    incl. round 6's FDIPT_KF_PASS_Z; FDIPT_KF_ALL covers every bit."""
+    incl. round 6's FDIPT_KF_PASS_Z; FDIPT_KF_ALL covers every bit.  Bit 32 (the retired plain-operand node path) is unassigned: no
+    macro has it, and the library refuses it in every precision like any unknown bit, while it takes each remaining flag alone."""
     import os
     import re
 
-    from framedipt_amd import _lib
+    from framedipt_amd import _lib, config
+    from framedipt_amd.model.score_network import dims_from_conf
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     macros = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define FDIPT_KF_(\w+) (\d+)", open(os.path.join(root, "include", "fdipt.h")).read())}
     names = [k for k in macros if k != "ALL"]
@@ -534,6 +536,18 @@ def test_kernel_flag_constants_match_the_header():
     for k in names:
         assert getattr(_lib, "KF_" + k) == macros[k], k
     assert macros["ALL"] == sum(macros[k] for k in names)
+    assert 32 not in macros.values() and macros["ALL"] == 2015
+    lib = _lib.load()
+    conf = config.base_config()
+    for prec in (_lib.PREC_F32, _lib.PREC_F16, _lib.PREC_F16X):
+        d = dims_from_conf(conf.model, conf.diffuser, False, prec)
+        n = lib.fdipt_param_count(C.byref(d))
+        assert n > 0
+        d.kernel_flags = 32
+        assert lib.fdipt_param_count(C.byref(d)) == -1, prec
+        for k in names:
+            d.kernel_flags = macros[k]
+            assert lib.fdipt_param_count(C.byref(d)) == n, (prec, k)
 
 
 def test_bench_dump_outputs_names_and_size_cap(tmp_path):

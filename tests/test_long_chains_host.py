@@ -12,8 +12,10 @@ def test_stream_attn_flag_is_accepted_and_sizes_the_workspace():
     assert lib.fdipt_param_count(C.byref(d)) > 0
     w1024, w2048 = lib.fdipt_forward_workspace_bytes(C.byref(d), 1, 1024), lib.fdipt_forward_workspace_bytes(C.byref(d), 1, 2048)
     assert 0 < w1024 < w2048 < 1 << 40
-    # every bit up to this one is a flag; the next one is not
-    d.kernel_flags = 2 * _lib.KF_STREAM_ATTN - 1
+    # every bit up to this one but the retired 32 is a flag; the next one is not
+    d.kernel_flags = 2 * _lib.KF_STREAM_ATTN - 1 - 32
     assert lib.fdipt_param_count(C.byref(d)) > 0
+    d.kernel_flags = 2 * _lib.KF_STREAM_ATTN - 1
+    assert lib.fdipt_param_count(C.byref(d)) == -1
     d.kernel_flags = 2 * _lib.KF_STREAM_ATTN
     assert lib.fdipt_param_count(C.byref(d)) == -1

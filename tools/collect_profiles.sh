@@ -15,7 +15,6 @@ python "$ROOT/bench.py" --full > "$OUT/bench.json" 2>> "$OUT/bench.err"
 for c in c2 c3 c3e c3w c5; do python "$ROOT/bench.py" --full --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2>> "$OUT/bench.err"; done
 python "$ROOT/bench.py" --precision fp32 --steps 6 --warmup 2 --no-cpu-baseline --no-reference-precision > "$OUT/bench_c4_fp32.json" 2>> "$OUT/bench.err"
 python "$ROOT/bench.py" --full --config c5 --precision fp16 --no-cpu-baseline > "$OUT/bench_c5_fp16.json" 2>> "$OUT/bench.err"
-python "$ROOT/bench.py" --full --kernel-flags 32 --no-cpu-baseline > "$OUT/bench_c4_nosplit.json" 2>> "$OUT/bench.err"
 python "$ROOT/bench.py" --full --samples-per-gpu 24 --steps 100 --no-cpu-baseline --no-reference-precision > "$OUT/bench_c4_b24.json" 2>> "$OUT/bench.err"
 python "$ROOT/bench.py" --samples-per-gpu 64 --steps 40 --no-cpu-baseline --no-reference-precision > "$OUT/bench_c4_b64.json" 2>> "$OUT/bench.err"
 python "$ROOT/bench.py" --full --eager --no-cpu-baseline --no-reference-precision --no-all-samples > "$OUT/bench_c4_eager.json" 2>> "$OUT/bench.err"

@@ -11,7 +11,7 @@ rows = [("c4_fp16_n300_b8_driver_command", "**c4, the driver's command** (`--ste
         ("c2_fp16_n128_b8", "c2: de novo N = 128, 8 samples"), ("c3_fp16_mixed_bucket_of_8_complexes", "c3: bucket of 8 complexes, 746 - 766 residues (padded)"),
         ("c3e_fp16_equal_length_n776_b8", "c3e: 8 samples of one 776-residue complex"), ("c3w_fp16_mixed_whole_range_700_850", "c3w: mixed lengths 700 - 850"),
         ("c5_fp32_n1000_b4", "c5: inpainting N = 1000, 4 samples"), ("c5_shape_in_fp16", "c5's shape in the fp16 mode"),
-        ("c4_fp16_b24", "c4, 24 samples per GPU (100 steps)"), ("c4_fp16_without_split_operands", "c4 without split operands (`--kernel-flags 32`: outside the parity bar)")]
+        ("c4_fp16_b24", "c4, 24 samples per GPU (100 steps)")]
 print("| config | mode | residue·step/s | ms/step | EdgeTransition (ms, frac, in-kernel GHz) | whole forward of the MFMA peak |")
 print("|---|---|---|---|---|---|")
 for k, name in rows:

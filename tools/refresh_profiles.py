@@ -148,7 +148,7 @@ lines = {}
 for tag, fn in (("c4_fp16_n300_b8", "bench.json"), ("c2_fp16_n128_b8", "bench_c2.json"), ("c3_fp16_mixed_bucket_of_8_complexes", "bench_c3.json"),
                 ("c3e_fp16_equal_length_n776_b8", "bench_c3e.json"), ("c3w_fp16_mixed_whole_range_700_850", "bench_c3w.json"), ("c4_fp16_b64", "bench_c4_b64.json"),
                 ("c5_fp32_n1000_b4", "bench_c5.json"), ("c5_shape_in_fp16", "bench_c5_fp16.json"), ("c4_fp32", "bench_c4_fp32.json"),
-                ("c4_fp16_without_split_operands", "bench_c4_nosplit.json"), ("c4_fp16_b24", "bench_c4_b24.json"),
+                ("c4_fp16_b24", "bench_c4_b24.json"),
                 ("c4_fp16_two_sub_batch_streams", "bench_c4_streams2.json"), ("c3_fp16_two_sub_batch_streams", "bench_c3_streams2.json")):
     if os.path.exists(d + fn):
         lines[tag] = json.load(open(d + fn))
