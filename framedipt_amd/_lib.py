@@ -81,6 +81,20 @@ class EvalArgs(C.Structure):
 
 EVAL_NAN_DIHEDRAL, EVAL_DEGENERATE_ALIGNMENT, EVAL_SKIPPED = 1, 2, 4  # FdiptEvalArgs.status bits
 
+
+class ViolationArgs(C.Structure):
+    """FdiptViolationArgs (include/fdipt.h): structural violations of B samples."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "N", "atoms")] + [(n, _P) for n in (
+        "prot", "res_mask", "keep_mask", "residue_index", "bonds_c_n_loss_mean", "angles_ca_c_n_loss_mean", "angles_c_n_ca_loss_mean",
+        "clashes_mean_loss", "violations_extreme_ca_ca_distance", "violations_between_residue_bond", "violations_between_residue_clash",
+        "violations_within_residue", "violations_per_residue", "radius_of_gyration", "num_residue_violations", "n_clash_pairs",
+        "connections_per_residue_loss_sum", "connections_per_residue_violation_mask", "total_per_residue_violations_mask",
+        "clashes_per_atom_loss_sum", "clashes_per_atom_clash_mask", "within_per_atom_loss_sum", "within_per_atom_violations",
+        "workspace")] + [("workspace_bytes", C.c_size_t)]
+
+
+VIOLATION_CONSTANTS = 61  # FDIPT_VIOLATION_CONSTANTS
+
 _lib = None
 
 # name -> (restype, argtypes); every symbol declared in include/fdipt.h
@@ -115,6 +129,9 @@ SIGNATURES = {
     "fdipt_sample_select": (_i, [C.POINTER(SelectArgs), _P]),
     "fdipt_eval_workspace_bytes": (_sz, [_i, _i]),
     "fdipt_sample_evaluate": (_i, [C.POINTER(EvalArgs), _P]),
+    "fdipt_sample_violations_workspace": (_sz, [_i, _i]),
+    "fdipt_sample_violations": (_i, [C.POINTER(ViolationArgs), _P]),
+    "fdipt_violation_constants": (_i, [C.POINTER(_d)]),
     "fdipt_backbone_atoms_indexed": (_i, [_i, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_backbone_atoms_kept": (_i, [_i, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fdipt_se3_forward_step": (_i, [_i, _i, _P, _P, _P, _P, _P, _d, _d, _d, _d, _d, _d, _d, _d, _P, _P, _P, _P]),

@@ -259,6 +259,42 @@ def run_evaluation(out_dir: str, records, gathered: dict, tcr: bool = False, sel
     return summary
 
 
+def run_violations(out_dir: str, records, gathered: dict):
+    """Rank 0, after the gather (``--violations``): one ``violations.structural_violations`` call over every sample of the run, as the
+    reference scores it (``atoms="diffused"``: undiffused rows sit at the origin and count); shorter samples are padded with res_mask = 0
+    rows, residue_index is the position within the sample.  Writes ``violations.json`` (per sample the scalars, the counts and the
+    indices of the violating residues) and ``violations.csv`` (one row per sample: pdb_name, sample, the scalars and counts).  Returns
+    the summary written to ``violations.json``."""
+    import csv
+
+    from . import violations
+    order = [r for rs in group_records_by_name(records).values() for r in rs]
+    n_max = max(gathered[r["item"]]["prot"].shape[0] for r in order)
+    prot = np.zeros((len(order), n_max, 37, 3), dtype=np.float32)
+    diffuse, res_mask = np.zeros((len(order), n_max), dtype=np.float32), np.zeros((len(order), n_max), dtype=np.float32)
+    for b, r in enumerate(order):
+        it = gathered[r["item"]]
+        n = it["prot"].shape[0]
+        prot[b, :n], diffuse[b, :n] = it["prot"], it["diffused"]
+        res_mask[b, :n] = 1 if it.get("res_mask") is None else it["res_mask"]
+    res = violations.structural_violations(prot, diffuse, res_mask, atoms="diffused")
+    number = lambda v: None if isinstance(v, float) and v != v else v  # noqa: E731  (NaN: no kept row)
+    columns = violations.SCALARS + violations.COUNTS
+    summary, table = {"atoms": "diffused", "samples": []}, []
+    for b, r in enumerate(order):
+        values = {k: res[k][b].item() for k in columns}
+        summary["samples"].append({"pdb_name": r["name"], "sample": r["sample_i"], "n_res": int(gathered[r["item"]]["prot"].shape[0]),
+                                   **{k: number(v) for k, v in values.items()}, "residue_violations": violations.residue_violations(res, b)})
+        table.append({"pdb_name": r["name"], "sample": r["sample_i"], **{k: repr(v) if isinstance(v, float) else v for k, v in values.items()}})
+    with open(os.path.join(out_dir, "violations.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "violations.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample"] + list(columns))
+        w.writeheader()
+        w.writerows(table)
+    return summary
+
+
 def reference_layout_writer(out_dir: str, net, final_only: bool):
     """``write_item`` for inpainting runs: what ``Inference.run_conditional_sampling`` leaves on disk per sample
     (experiments/inference.py:250-389): ``<pdb>_length_<L>/`` with the ground-truth structure ``<pdb>_1.pdb`` (b-factor 100 = diffused) and
@@ -357,6 +393,9 @@ def main():
     ap.add_argument("--evaluate", action="store_true", help="after the run, rank 0 evaluates every sample (and with --select the five selected structures) "
                     "against the ground truth of its structure on its GPU (framedipt_amd/evaluation.py): evaluation.json and metrics.csv; "
                     "de novo runs have no ground truth and report the CA geometry checks only")
+    ap.add_argument("--violations", action="store_true", help="after the run, rank 0 scores the structural violations of every sample on its GPU "
+                    "(framedipt_amd/violations.py: C-N bond, CA-C-N and C-N-CA angle, clash and within-residue terms of the reference's "
+                    "violation metrics, radius of gyration): violations.json and violations.csv")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
     if a.keep not in ("all", "last"):
@@ -450,7 +489,7 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate else None
+    collected = {} if a.select or a.evaluate or a.violations else None
     ground_truth = None
     if a.evaluate and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
@@ -463,7 +502,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -482,6 +521,11 @@ def main():
             done = run_evaluation(a.out_dir, allrecs, gathered, tcr=a.tcr, selected=selected if inp else None)
             print(f"evaluated {sum(len(e['samples']) for e in done['structures'].values())} structure(s) in {time.perf_counter() - t1:.2f} s -> "
                   f"{a.out_dir}/evaluation.json, metrics.csv", flush=True)
+        if a.violations:
+            t1 = time.perf_counter()
+            done = run_violations(a.out_dir, allrecs, gathered)
+            print(f"structural violations of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
+                  f"{a.out_dir}/violations.json, violations.csv", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -462,6 +462,59 @@ size_t fdipt_eval_workspace_bytes(int B, int N);
  * sample more than max_regions regions.  FDIPT_ESIZE: workspace too small. */
 int fdipt_sample_evaluate(const FdiptEvalArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- structural violations (opt-in) */
+/* The structural-violation block of the reference's metric tables (framedipt/analysis/metrics.py:protein_metrics through
+ * openfold/np/relax/amber_minimize.py:get_violation_metrics: openfold/utils/loss.py find_structural_violations :1105 and
+ * compute_violation_metrics :1272, tolerance factor 12, overlap tolerance 1.5) for B samples, in float64, in two launches on one
+ * stream.  Every residue is ALA, as create_full_prot makes it without aatype: five atoms per row, atom37 columns 0..4 = N, CA, C, CB,
+ * O, and that is the order of every per-atom output here (the reference's atom14 order is N, CA, C, O, CB).
+ * A row with res_mask = 0 does not exist: the terms are those of the reference on the sample with these rows removed (a bond joins a
+ * row to the next existing one).  A row with res_mask != 0 and keep_mask = 0 exists with its five atoms at the origin, as
+ * make_atom14_positions leaves an undiffused row: it clashes with its like and enters the bond and angle terms.
+ * residue_index is used literally: a bond counts in the means and the masks where the difference of the indices is exactly 1; rows
+ * i, j form a clash pair where residue_index[i] < residue_index[j], with C(i) - N(j) exempt where residue_index[i] + 1 ==
+ * residue_index[j].  Sums run in a fixed order that depends on the sample's own existing rows only.  N is bounded by what a launch can
+ * address. */
+#define FDIPT_VIOLATION_CONSTANTS 61 /* doubles fdipt_violation_constants writes */
+typedef struct FdiptViolationArgs {
+  int32_t B, N, atoms;               /* samples, residues, atoms per row of prot: 37 or 5 (columns 0..4 are read)                   */
+  const float* prot;                 /* [B,N,atoms,3] f32                                                                           */
+  const float* res_mask;             /* [B,N] f32: the row exists                                                                   */
+  const float* keep_mask;            /* [B,N] f32: the row keeps its coordinates (0: they are read as zero)                         */
+  const int32_t* residue_index;      /* [B,N] i32                                                                                   */
+  /* outputs: [B] */
+  double* bonds_c_n_loss_mean;       /* between_residue_bond_loss :712: sum of the masked flat-bottom errors / (bonds + 1e-6)       */
+  double* angles_ca_c_n_loss_mean;   /* its stddev is the C-N bond length's, as the reference has it                                */
+  double* angles_c_n_ca_loss_mean;
+  double* clashes_mean_loss;         /* between_residue_clash_loss :871: sum of the errors / (1e-6 + n_clash_pairs)                 */
+  double* violations_extreme_ca_ca_distance; /* :1235; this and the next four: count / (1e-4 + rows or bonds) (masked_mean)         */
+  double* violations_between_residue_bond;
+  double* violations_between_residue_clash;
+  double* violations_within_residue;
+  double* violations_per_residue;
+  double* radius_of_gyration;        /* root mean square distance of the atoms of the kept rows from their centroid; NaN without one */
+  int32_t* num_residue_violations;   /* rows of total_per_residue_violations_mask                                                   */
+  int64_t* n_clash_pairs;            /* atom pairs of the clash mask                                                                */
+  /* outputs: [B,N], zero at rows that do not exist */
+  double* connections_per_residue_loss_sum;
+  uint8_t* connections_per_residue_violation_mask;
+  uint8_t* total_per_residue_violations_mask;
+  /* outputs: [B,N,5] */
+  double* clashes_per_atom_loss_sum; /* every pair's error is credited to both of its atoms                                         */
+  uint8_t* clashes_per_atom_clash_mask;
+  double* within_per_atom_loss_sum;  /* within_residue_violations :1018: the 5 x 5 error matrix summed along both axes              */
+  uint8_t* within_per_atom_violations;
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptViolationArgs;
+size_t fdipt_sample_violations_workspace(int B, int N);
+/* FDIPT_EINVAL: a null pointer, B or N < 1, atoms not 37 or 5.  FDIPT_ESIZE: workspace too small, more row tiles than a grid holds. */
+int fdipt_sample_violations(const FdiptViolationArgs* args, fdipt_stream_t stream);
+/* The constants of the kernel as it uses them: van der Waals radii of C, N, O; C-N length, its stddev and 12 stddev (float32 values, as
+ * the reference forms them); cos CA-C-N and the stddev it is given; cos C-N-CA and its stddev; ca_ca; then the ALA lower and upper
+ * within-residue bounds, 5 x 5 each in the order N, CA, C, CB, O.  Returns FDIPT_VIOLATION_CONSTANTS. */
+int fdipt_violation_constants(double* out);
+
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */
 int fdipt_quat_to_rot(int n, const float* quat, float* rot, fdipt_stream_t s);           /* :185 */
