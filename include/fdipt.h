@@ -18,6 +18,9 @@
  *   - layouts are row-major contiguous, residue-major.  Quaternions are scalar-first (w,x,y,z);
  *     tensor_7 = quat(4) | translation in Angstrom (3)   (openfold/utils/rigid_utils.py:1200-1230).
  *   - "f32"/"f64" in a parameter comment is the element type of the buffer.
+ *   - the Python binding is derived from this file (framedipt_amd/_header.py), which reads one declaration style and refuses the rest:
+ *     `[const] type* name` with the star at the type and one name per pointer, a name on every parameter, FDIPT_* macros that are plain
+ *     integers; a scalar pointer parameter into HOST memory ends in _host and is bound with its pointee type, every other pointer as void*.
  */
 #ifndef FDIPT_H
 #define FDIPT_H
@@ -513,7 +516,7 @@ int fdipt_sample_violations(const FdiptViolationArgs* args, fdipt_stream_t strea
 /* The constants of the kernel as it uses them: van der Waals radii of C, N, O; C-N length, its stddev and 12 stddev (float32 values, as
  * the reference forms them); cos CA-C-N and the stddev it is given; cos C-N-CA and its stddev; ca_ca; then the ALA lower and upper
  * within-residue bounds, 5 x 5 each in the order N, CA, C, CB, O.  Returns FDIPT_VIOLATION_CONSTANTS. */
-int fdipt_violation_constants(double* out);
+int fdipt_violation_constants(double* out_host);
 
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */

@@ -2,14 +2,12 @@
 (tests/golden/evaluation_cases.npz), the host side of framedipt_amd/evaluation.py (region planning, the reference's nested dicts and
 column names, argument checks) and the C entry's argument checks."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import evaluation_ref as er
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 _CACHE = {}
 
@@ -134,24 +132,6 @@ def test_argument_validation_raises():
     short["region_rows"] = [[(3, 5)]]
     with pytest.raises(ValueError, match="shorter than the 4"):
         evaluation.as_eval_dicts(short, 0)
-
-
-def test_eval_args_mirror_the_header():
-    """framedipt_amd._lib.EvalArgs against ``struct FdiptEvalArgs`` of include/fdipt.h: same members, same order, same types."""
-    from framedipt_amd import _lib
-    text = open(os.path.join(ROOT, "include", "fdipt.h")).read()
-    body = re.search(r"typedef struct FdiptEvalArgs \{(.*?)\} FdiptEvalArgs;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    members = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        names = decl.split(",")
-        typ, first = names[0].rsplit(" ", 1)
-        for n in [first] + [x.strip() for x in names[1:]]:
-            ctype = C.c_void_p if "*" in typ or n.startswith("*") else {"int32_t": C.c_int32, "double": C.c_double, "size_t": C.c_size_t}[typ]
-            members.append((n.lstrip("*"), ctype))
-    assert members == list(_lib.EvalArgs._fields_)
-    for macro, value in (("NAN_DIHEDRAL", _lib.EVAL_NAN_DIHEDRAL), ("DEGENERATE_ALIGNMENT", _lib.EVAL_DEGENERATE_ALIGNMENT), ("SKIPPED", _lib.EVAL_SKIPPED)):
-        assert int(re.search(rf"#define FDIPT_EVAL_{macro} (\d+)", text).group(1)) == value
 
 
 def test_entry_refuses_bad_arguments_before_any_launch():

@@ -1,6 +1,5 @@
 """CPU tests of the kept-frame trajectories (``keep=``): the one rule that says which reverse steps keep their frames, and the ABI the
-device side of it added (struct fields, the kept backbone entry) as the header, the ctypes mirror and the built library state it."""
-import ctypes as C
+device side of it added (struct fields, the kept backbone entry) as the header, the binding derived from it and the built library state it."""
 import os
 import re
 
@@ -47,41 +46,13 @@ def test_kept_steps_refuses_an_empty_trajectory():
         kept_steps(0, "last")
 
 
-_CTYPE = {"int32_t": C.c_int32, "float": C.c_float, "double": C.c_double}
-
-
-def _header_fields(struct):
-    """(name, ctypes type) of every member of ``struct`` in include/fdipt.h, in order; any pointer is a c_void_p."""
-    text = open(os.path.join(ROOT, "include", "fdipt.h")).read()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    out = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"^(?:const )?(?:unsigned long long|void|float|double|int32_t)\s*(\*{0,2})\s*(.+)$", decl)
-        assert m, decl
-        base = re.match(r"^(?:const )?(unsigned long long|void|float|double|int32_t)", decl).group(1)
-        for name in m.group(2).split(","):
-            name = name.strip()
-            ptr = bool(m.group(1)) or name.startswith("*")
-            out.append((name.lstrip("* "), C.c_void_p if ptr else _CTYPE[base]))
-    return out
-
-
 @pytest.mark.parametrize("struct,mirror", [("FdiptForwardArgs", "ForwardArgs"), ("FdiptReverseIndexed", "ReverseIndexed")])
 def test_struct_mirrors_match_the_header(struct, mirror):
-    """The ctypes mirrors of the two structs that carry the row map against include/fdipt.h: the same members in the same order with the
-    same size (every pointer counts as a void*), the new ones appended behind step_cursor, and zero (NULL / 0) by default."""
+    """The two structs that carry the row map, as _lib derives them from include/fdipt.h (tests/test_abi_host.py holds them against the
+    C layout): the new members sit directly behind step_cursor, at the end, and are zero (NULL / 0) by default."""
     from framedipt_amd import _lib
-    want = _header_fields(struct)
     cls = getattr(_lib, mirror)
-    got = [(n, C.c_void_p if C.sizeof(t) == C.sizeof(C.c_void_p) and t not in (C.c_double,) else t) for n, t in cls._fields_]
-    assert [n for n, _ in got] == [n for n, _ in want]
-    for (n, tg), (_, tw) in zip(got, want):
-        assert C.sizeof(tg) == C.sizeof(tw) and (tg is C.c_void_p) == (tw is C.c_void_p), n
-    names = [n for n, _ in want]
+    names = [n for n, _ in cls._fields_]
     new = {"FdiptForwardArgs": ["frame_rows", "state_ring"], "FdiptReverseIndexed": ["frame_rows", "state_ring", "kept_rigids"]}[struct]
     assert names[-len(new) - 1:] == ["step_cursor"] + new
     zero = cls()

@@ -2,14 +2,12 @@
 (tests/golden/selection_cases.npz), the host side of framedipt_amd/selection.py, the C entry's argument checks and the grouping
 helper of ``run_sharded --select``."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import selection_ref as sr
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 _CACHE = {}
 
@@ -111,25 +109,6 @@ def test_grouping_by_structure_name_keeps_sample_order():
     assert list(groups) == ["1xyz", "7abc"]
     assert [[r["item"] for r in rs] for rs in groups.values()] == [[0, 1, 2], [3, 4, 5]]
     assert [r["sample_i"] for r in groups["7abc"]] == [0, 1, 2]
-
-
-def test_select_args_mirror_the_header():
-    """framedipt_amd._lib.SelectArgs against ``struct FdiptSelectArgs`` of include/fdipt.h: same members, same order, same types."""
-    from framedipt_amd import _lib
-    text = open(os.path.join(ROOT, "include", "fdipt.h")).read()
-    body = re.search(r"typedef struct FdiptSelectArgs \{(.*?)\} FdiptSelectArgs;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    members = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        typ, names = decl.rsplit(" ", 1)[0], decl.split(",")
-        first = names[0].rsplit(" ", 1)
-        typ, names = first[0], [first[1]] + [n.strip() for n in names[1:]]
-        for n in names:
-            ctype = C.c_void_p if "*" in typ or n.startswith("*") else {"int32_t": C.c_int32, "double": C.c_double, "size_t": C.c_size_t}[typ]
-            members.append((n.lstrip("*"), ctype))
-    assert members == list(_lib.SelectArgs._fields_)
-    for macro, value in (("MAX_SAMPLES", _lib.SELECT_MAX_SAMPLES), ("ZERO_DISTANCE", _lib.SELECT_ZERO_DISTANCE), ("SKIPPED", _lib.SELECT_SKIPPED)):
-        assert int(re.search(rf"#define FDIPT_SELECT_{macro} (\d+)", text).group(1)) == value
 
 
 def test_entry_refuses_bad_groups_before_any_launch():

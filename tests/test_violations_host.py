@@ -2,14 +2,12 @@
 (tests/golden/violation_cases.npz), the library's constants against the reference's, the C entry's argument checks, the host helpers of
 framedipt_amd/violations.py and the command line of run_sharded."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import violations_ref as vr
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 _CACHE = {}
 
@@ -76,23 +74,6 @@ def test_library_constants_match_the_reference():
     assert fix["constants.head"].tolist() == [vr.RADIUS[1], vr.RADIUS[0], vr.RADIUS[4], vr.C_N_LENGTH, float(np.float32(0.014)), vr.C_N_TOLERANCE,
                                               vr.COS_CA_C_N, vr.CA_C_N_TOLERANCE / 12, vr.COS_C_N_CA, vr.C_N_CA_TOLERANCE / 12, vr.CA_CA]
     assert np.array_equal(vr.LOWER, fix["constants.lower"]) and np.array_equal(vr.UPPER, fix["constants.upper"])
-
-
-def test_violation_args_mirror_the_header():
-    """framedipt_amd._lib.ViolationArgs against ``struct FdiptViolationArgs`` of include/fdipt.h: same members, same order, same types."""
-    from framedipt_amd import _lib
-    text = open(os.path.join(ROOT, "include", "fdipt.h")).read()
-    body = re.search(r"typedef struct FdiptViolationArgs \{(.*?)\} FdiptViolationArgs;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    members = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        names = decl.split(",")
-        typ, first = names[0].rsplit(" ", 1)
-        for n in [first] + [x.strip() for x in names[1:]]:
-            ctype = C.c_void_p if "*" in typ or n.startswith("*") else {"int32_t": C.c_int32, "size_t": C.c_size_t}[typ]
-            members.append((n.lstrip("*"), ctype))
-    assert members == list(_lib.ViolationArgs._fields_)
-    assert int(re.search(r"#define FDIPT_VIOLATION_CONSTANTS (\d+)", text).group(1)) == _lib.VIOLATION_CONSTANTS
 
 
 def test_entry_refuses_bad_arguments_before_any_launch():
