@@ -295,6 +295,44 @@ def run_violations(out_dir: str, records, gathered: dict):
     return summary
 
 
+def run_secondary_structure(out_dir: str, records, gathered: dict):
+    """Rank 0, after the gather (``--secondary-structure``): one ``secondary_structure.secondary_structure`` call over every sample of the
+    run with its res_mask, chain_idx and aatype (a proline donates no hydrogen bond); shorter samples are padded with res_mask = 0
+    rows.  Writes ``secondary_structure.json`` (per sample the C / H / E string over the rows that exist and the four fractions of the
+    reference's ``calc_mdtraj_metrics``) and ``secondary_structure.csv`` (one row per sample: pdb_name, sample, n_res, the fractions, the
+    string).  Returns the summary written to ``secondary_structure.json``."""
+    import csv
+
+    from . import secondary_structure as sec
+    order = [r for rs in group_records_by_name(records).values() for r in rs]
+    n_max = max(gathered[r["item"]]["prot"].shape[0] for r in order)
+    prot = np.zeros((len(order), n_max, 37, 3), dtype=np.float32)
+    res_mask = np.zeros((len(order), n_max), dtype=np.float32)
+    chain, aatype = np.zeros((len(order), n_max), dtype=np.int32), np.zeros((len(order), n_max), dtype=np.int32)
+    for b, r in enumerate(order):
+        it = gathered[r["item"]]
+        n = it["prot"].shape[0]
+        prot[b, :n] = it["prot"]
+        res_mask[b, :n] = 1 if it.get("res_mask") is None else it["res_mask"]
+        chain[b, :n] = 0 if it.get("chain_idx") is None else np.rint(it["chain_idx"])
+        aatype[b, :n] = 0 if it.get("aatype") is None else np.rint(it["aatype"])
+    res = sec.secondary_structure(prot, res_mask, chain, aatype)
+    number = lambda v: None if v != v else v  # noqa: E731  (NaN: no row exists)
+    summary, table = {"alphabet": "C coil, H helix (alpha, 3-10, pi), E strand", "samples": []}, []
+    for b, r in enumerate(order):
+        values = {k: res[k][b].item() for k in sec.FRACTIONS}
+        head = {"pdb_name": r["name"], "sample": r["sample_i"], "n_res": int(gathered[r["item"]]["prot"].shape[0])}
+        summary["samples"].append({**head, **{k: number(v) for k, v in values.items()}, "ss": res["ss_string"][b], "status": int(res["status"][b])})
+        table.append({**head, **{k: repr(v) for k, v in values.items()}, "ss": res["ss_string"][b]})
+    with open(os.path.join(out_dir, "secondary_structure.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "secondary_structure.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "n_res"] + list(sec.FRACTIONS) + ["ss"])
+        w.writeheader()
+        w.writerows(table)
+    return summary
+
+
 def reference_layout_writer(out_dir: str, net, final_only: bool):
     """``write_item`` for inpainting runs: what ``Inference.run_conditional_sampling`` leaves on disk per sample
     (experiments/inference.py:250-389): ``<pdb>_length_<L>/`` with the ground-truth structure ``<pdb>_1.pdb`` (b-factor 100 = diffused) and
@@ -396,6 +434,9 @@ def main():
     ap.add_argument("--violations", action="store_true", help="after the run, rank 0 scores the structural violations of every sample on its GPU "
                     "(framedipt_amd/violations.py: C-N bond, CA-C-N and C-N-CA angle, clash and within-residue terms of the reference's "
                     "violation metrics, radius of gyration): violations.json and violations.csv")
+    ap.add_argument("--secondary-structure", action="store_true", help="after the run, rank 0 assigns the secondary structure of every sample on its GPU "
+                    "(framedipt_amd/secondary_structure.py: hydrogen-bond patterns of Kabsch & Sander in the alphabet C / H / E, the coil, helix and "
+                    "strand fractions of the reference's metric tables): secondary_structure.json and secondary_structure.csv")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
     if a.keep not in ("all", "last"):
@@ -489,7 +530,7 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure else None
     ground_truth = None
     if a.evaluate and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
@@ -502,7 +543,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -526,6 +567,11 @@ def main():
             done = run_violations(a.out_dir, allrecs, gathered)
             print(f"structural violations of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
                   f"{a.out_dir}/violations.json, violations.csv", flush=True)
+        if a.secondary_structure:
+            t1 = time.perf_counter()
+            done = run_secondary_structure(a.out_dir, allrecs, gathered)
+            print(f"secondary structure of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
+                  f"{a.out_dir}/secondary_structure.json, secondary_structure.csv", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -518,6 +518,53 @@ int fdipt_sample_violations(const FdiptViolationArgs* args, fdipt_stream_t strea
  * within-residue bounds, 5 x 5 each in the order N, CA, C, CB, O.  Returns FDIPT_VIOLATION_CONSTANTS. */
 int fdipt_violation_constants(double* out_host);
 
+/* ---------------------------------------------------------------- secondary structure (opt-in) */
+/* Kabsch & Sander's secondary structure in the simplified alphabet coil / helix / strand, the SHAPE_METRICS of the reference's metric
+ * tables (framedipt/analysis/metrics.py:calc_mdtraj_metrics: md.compute_dssp(traj, simplified=True) of the written PDB), for B samples,
+ * in float64, in one launch of a block per sample.  The contract is DESIGN.md section 7.6; no mdtraj was at hand to compare with.
+ * A row exists where res_mask != 0 and each of N, CA, C, O (atom37 columns 0, 1, 2, 4) has a non-zero coordinate; the existing rows
+ * are compacted in order and everything else speaks of the compacted rows.  A break lies before a row whose chain_idx differs from the
+ * row before or whose N is more than 2.5 A from that row's C.  E(donor, acceptor) = -27.888 (1/|HO| - 1/|HC| + 1/|NC| - 1/|NO|), H one
+ * Angstrom from N along the previous row's O -> C, rounded to three decimals (halves away from zero), not below -9.9; evaluated for CA
+ * within 9 A, the donor no proline, the acceptor neither the donor nor the row before it.  A donor keeps its two lowest energies below
+ * 0 (the lower index on a tie); a bond is a kept acceptor below -0.5.  Turns (n = 3, 4, 5), parallel and antiparallel bridges, ladders
+ * and the bulge pass, then strand, alpha (overrides strand), 3-10 and pi helices in this order.  Every integer output depends on the
+ * sample's own existing rows only: rows appended behind a sample and its batch mates change no bit.  N is bounded by what a launch can
+ * address (the ladder list: 40 N < 2^31). */
+#define FDIPT_DSSP_COIL 0
+#define FDIPT_DSSP_HELIX 1             /* alpha, 3-10 or pi                                                                         */
+#define FDIPT_DSSP_STRAND 2            /* a row of a ladder: bridges, ladders' interiors, bulge gaps                                */
+#define FDIPT_DSSP_ABSENT 255          /* ss at a row that does not exist                                                           */
+#define FDIPT_DSSP_BRIDGES_PER_ROW 8   /* bridges (i, .) of one row i under the two-slot limit: 2 donors x 2 slots x 2 acceptors    */
+#define FDIPT_DSSP_BRIDGE_OVERFLOW 1   /* status: a row held more bridges than FDIPT_DSSP_BRIDGES_PER_ROW; the fractions are NaN    */
+#define FDIPT_DSSP_LADDER_OVERFLOW 2   /* status: more ladders than FDIPT_DSSP_BRIDGES_PER_ROW x N; the fractions are NaN           */
+typedef struct FdiptDsspArgs {
+  int32_t B, N, atoms;               /* samples, residues, atoms per row of prot: 37 or 5 (columns 0, 1, 2, 4 are read)             */
+  const float* prot;                 /* [B,N,atoms,3] f32                                                                           */
+  const float* res_mask;             /* [B,N] f32                                                                                   */
+  const int32_t* chain_idx;          /* [B,N] i32                                                                                   */
+  const uint8_t* is_proline;         /* [B,N] u8: the row donates no hydrogen bond                                                  */
+  uint8_t* ss;                       /* [B,N] u8: FDIPT_DSSP_COIL / HELIX / STRAND, FDIPT_DSSP_ABSENT at a row that does not exist  */
+  /* outputs: [B] */
+  double* helix_percent;             /* counts over n_rows; NaN where n_rows = 0 or status != 0                                     */
+  double* strand_percent;
+  double* coil_percent;
+  double* non_coil_percent;          /* (helix + strand) / n_rows                                                                   */
+  int32_t* n_rows;                   /* rows that exist                                                                             */
+  int32_t* n_hbonds;                 /* (donor, acceptor) pairs that are bonds                                                      */
+  int32_t* n_bridges;
+  int32_t* n_ladders;                /* after the bulge pass                                                                        */
+  int32_t* status;                   /* FDIPT_DSSP_*_OVERFLOW bits                                                                  */
+  /* outputs: [B,N,2], the donor's two slots; -1 and 0 where a slot is empty or the row does not exist */
+  int32_t* acceptor;                 /* row of the input                                                                            */
+  double* acceptor_energy;           /* kcal/mol, rounded                                                                           */
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptDsspArgs;
+size_t fdipt_sample_dssp_workspace(int B, int N);
+/* FDIPT_EINVAL: a null pointer, B or N < 1, atoms not 37 or 5.  FDIPT_ESIZE: workspace too small, N beyond the ladder list's index. */
+int fdipt_sample_dssp(const FdiptDsspArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */
 int fdipt_quat_to_rot(int n, const float* quat, float* rot, fdipt_stream_t s);           /* :185 */
