@@ -36,13 +36,14 @@ _ERR = {_H.macros["EINVAL"]: "FDIPT_EINVAL (bad argument)", _H.macros["ELAUNCH"]
         _H.macros["ESIZE"]: "FDIPT_ESIZE (workspace too small or N beyond the compiled tiling: N <= 1024, N <= 2048 with KF_STREAM_ATTN in the fp16 mode; "
                             "sample selection: a group of more than 64 samples)"}
 
-Dims, ForwardArgs, ReverseIndexed, SelectArgs, EvalArgs, ViolationArgs, DsspArgs = (_H.structs["Fdipt" + n] for n in (
-    "Dims", "ForwardArgs", "ReverseIndexed", "SelectArgs", "EvalArgs", "ViolationArgs", "DsspArgs"))
+Dims, ForwardArgs, ReverseIndexed, SelectArgs, EvalArgs, ViolationArgs, DsspArgs, SasaArgs = (_H.structs["Fdipt" + n] for n in (
+    "Dims", "ForwardArgs", "ReverseIndexed", "SelectArgs", "EvalArgs", "ViolationArgs", "DsspArgs", "SasaArgs"))
 for _cls, _doc in ((ReverseIndexed, "one reverse step addressed through a device-side step cursor."),
                    (SelectArgs, "sample selection over G groups of the B samples of one atom37 array."),
                    (EvalArgs, "evaluation of B samples against R ground-truth structures."),
                    (ViolationArgs, "structural violations of B samples."),
-                   (DsspArgs, "secondary structure (coil / helix / strand) of B samples.")):
+                   (DsspArgs, "secondary structure (coil / helix / strand) of B samples."),
+                   (SasaArgs, "solvent accessibility (Shrake-Rupley ASA, RSA) of B samples.")):
     _cls.__doc__ = f"Fdipt{_cls.__name__} (include/fdipt.h): {_doc}"
 
 _lib = None

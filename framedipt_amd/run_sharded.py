@@ -333,6 +333,61 @@ def run_secondary_structure(out_dir: str, records, gathered: dict):
     return summary
 
 
+def run_sasa(out_dir: str, records, gathered: dict, inpainting: bool = False):
+    """Rank 0, after the gather (``--sasa``): one ``sasa.solvent_accessibility`` call over every sample of the run, every chain of the
+    complex shielding the diffused rows (the atoms with a non-zero coordinate exist); shorter samples are padded with res_mask = 0 rows.
+    The RSA denominators follow the run's aatype in inpainting runs and ALA in de novo runs.  With ground truth (inpainting: ``gt`` of a
+    structure's first sample, the structure written as ``<pdb>_1.pdb``) that structure is scored in a second call and every sample
+    carries the reference's eight ASA / RSA keys against it.  Writes ``sasa.json`` (per sample the diffused rows, their ASA and RSA
+    and the total) and ``sasa.csv`` (one row per sample: pdb_name, sample, n_res, total, mean ASA and mean RSA over the diffused rows).
+    Returns the summary written to ``sasa.json``."""
+    import csv
+
+    from . import sasa
+    by_name = group_records_by_name(records)
+    order = [r for rs in by_name.values() for r in rs]
+
+    def batch(entries):  # [(atom37 [n,37,3], gathered entry)] -> one padded call
+        n_max = max(pos.shape[0] for pos, _ in entries)
+        prot = np.zeros((len(entries), n_max, 37, 3), dtype=np.float32)
+        res_mask, aatype = np.zeros((len(entries), n_max), dtype=np.float32), np.zeros((len(entries), n_max), dtype=np.int64)
+        for b, (pos, it) in enumerate(entries):
+            n = pos.shape[0]
+            prot[b, :n] = pos
+            res_mask[b, :n] = 1 if it.get("res_mask") is None else it["res_mask"]
+            aatype[b, :n] = 0 if not inpainting or it.get("aatype") is None else np.rint(it["aatype"])
+        return sasa.solvent_accessibility(prot, None, res_mask, aatype)
+
+    res = batch([(gathered[r["item"]]["prot"], gathered[r["item"]]) for r in order])
+    names = list(by_name)
+    truth = {name: next((gathered[r["item"]] for r in rs if "gt" in gathered[r["item"]]), None) for name, rs in by_name.items()}
+    with_truth = inpainting and all(t is not None for t in truth.values())
+    gt = batch([(truth[name]["gt"], truth[name]) for name in names]) if with_truth else None
+    numbers = lambda v: [None if x != x else x for x in np.asarray(v).tolist()]  # noqa: E731  (NaN: a residue type without a maximal ASA)
+    summary, table = {"unit": "square Angstrom", "probe_radius": 1.40, "n_points": 100, "ground_truth": with_truth, "samples": []}, []
+    for b, r in enumerate(order):
+        it = gathered[r["item"]]
+        n = it["prot"].shape[0]
+        rows = np.flatnonzero(it["diffused"])
+        asa, rsa = res["residue_sasa"][b, rows], res["rsa"][b, rows]
+        head = {"pdb_name": r["name"], "sample": r["sample_i"], "n_res": int(n)}
+        total = float(res["residue_sasa"][b, :n].sum())
+        entry = {**head, "n_atoms": int(res["n_atoms"][b]), "total": total, "rows": rows.tolist(), "asa": numbers(asa), "rsa": numbers(rsa)}
+        if with_truth:  # (the diffused rows as single-row regions: the reference's keys per residue of the diffused regions)
+            metrics = sasa.sasa_metrics(gt, names.index(str(r["name"])), res, b, [(k, k) for k in rows])
+            entry["metrics"] = {k: numbers(v) for k, v in metrics.items()}
+        summary["samples"].append(entry)
+        mean = lambda v: repr(float(np.mean(v))) if len(v) else ""  # noqa: E731
+        table.append({**head, "total": repr(total), "mean_asa": mean(asa), "mean_rsa": mean(rsa)})
+    with open(os.path.join(out_dir, "sasa.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "sasa.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "n_res", "total", "mean_asa", "mean_rsa"])
+        w.writeheader()
+        w.writerows(table)
+    return summary
+
+
 def reference_layout_writer(out_dir: str, net, final_only: bool):
     """``write_item`` for inpainting runs: what ``Inference.run_conditional_sampling`` leaves on disk per sample
     (experiments/inference.py:250-389): ``<pdb>_length_<L>/`` with the ground-truth structure ``<pdb>_1.pdb`` (b-factor 100 = diffused) and
@@ -437,6 +492,9 @@ def main():
     ap.add_argument("--secondary-structure", action="store_true", help="after the run, rank 0 assigns the secondary structure of every sample on its GPU "
                     "(framedipt_amd/secondary_structure.py: hydrogen-bond patterns of Kabsch & Sander in the alphabet C / H / E, the coil, helix and "
                     "strand fractions of the reference's metric tables): secondary_structure.json and secondary_structure.csv")
+    ap.add_argument("--sasa", action="store_true", help="after the run, rank 0 computes the solvent accessibility of every sample on its GPU "
+                    "(framedipt_amd/sasa.py: Shrake-Rupley ASA per residue of the diffused rows with the whole complex as context, and RSA, "
+                    "the ASA / RSA block of the reference's metric table): sasa.json and sasa.csv; inpainting runs score the ground truth too")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
     if a.keep not in ("all", "last"):
@@ -530,9 +588,9 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa else None
     ground_truth = None
-    if a.evaluate and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
+    if (a.evaluate or a.sasa) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
             build = lambda: inference.get_atom_positions_from_rigids(net, feats["rigids_0"], feats["torsion_angles_sin_cos"][..., 2, :], feats["aatype"])[0]  # noqa: E731
             return one_gpu_turn(build) if one_gpu and world > 1 else build()
@@ -543,7 +601,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -572,6 +630,11 @@ def main():
             done = run_secondary_structure(a.out_dir, allrecs, gathered)
             print(f"secondary structure of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
                   f"{a.out_dir}/secondary_structure.json, secondary_structure.csv", flush=True)
+        if a.sasa:
+            t1 = time.perf_counter()
+            done = run_sasa(a.out_dir, allrecs, gathered, inpainting=inp)
+            print(f"solvent accessibility of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
+                  f"{a.out_dir}/sasa.json, sasa.csv", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

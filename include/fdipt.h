@@ -565,6 +565,38 @@ size_t fdipt_sample_dssp_workspace(int B, int N);
 /* FDIPT_EINVAL: a null pointer, B or N < 1, atoms not 37 or 5.  FDIPT_ESIZE: workspace too small, N beyond the ladder list's index. */
 int fdipt_sample_dssp(const FdiptDsspArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- solvent accessibility (opt-in) */
+/* Shrake & Rupley's solvent-accessible surface area per atom and per residue and the relative value, the ASA / RSA block of the
+ * reference's TCR metric table (evaluation/utils/metrics.py:get_sasa: Bio.PDB.SASA.ShrakeRupley().compute(model, level="R") over the
+ * whole complex), for B samples, in float64 with contraction off, in three launches on one stream.  The contract is DESIGN.md section
+ * 7.7; no Biopython was at hand to compare with.  Atom (b, r, a) exists where res_mask[b,r] != 0 and atom_mask[b,r,a] != 0; all existing
+ * atoms of a sample form one set.  Point k of atom i is p = sphere[k] * R_i + c_i (R = atom_radius[a], probe included); it is buried when
+ * another existing atom j of the sample has ((dx dx + dy dy) + dz dz) <= R_j R_j, d = p - c_j.  accessible = points not buried;
+ * atom_sasa = accessible * (R_i R_i * (4 pi / n_points)); residue_sasa = its atoms' sum in ascending column order from 0.0;
+ * rsa = residue_sasa / max_sasa.  Absent atoms and rows give 0 and 0.0.  Every output of a sample depends on that sample's existing
+ * atoms only: rows padded behind it and its batch mates change no bit. */
+typedef struct FdiptSasaArgs {
+  int32_t B, N, atoms, n_points;     /* samples, residues, atoms per row of prot: 37 or 5; sphere points: 1 .. 1024                 */
+  const float* prot;                 /* [B,N,atoms,3] f32                                                                           */
+  const float* res_mask;             /* [B,N] f32                                                                                   */
+  const uint8_t* atom_mask;          /* [B,N,atoms] u8                                                                              */
+  const double* atom_radius;         /* [atoms] f64: radius per atom column, the probe radius already added                         */
+  const double* sphere;              /* [n_points,3] f64: unit points (the caller's table; no sine or cosine on the device)         */
+  const double* max_sasa;            /* [B,N] f64: the denominator of rsa (NaN gives NaN)                                           */
+  /* outputs */
+  int32_t* accessible;               /* [B,N,atoms] i32: points of the atom that no other atom buries                               */
+  double* atom_sasa;                 /* [B,N,atoms] f64, square Angstrom                                                            */
+  double* residue_sasa;              /* [B,N] f64                                                                                   */
+  double* rsa;                       /* [B,N] f64                                                                                   */
+  int32_t* n_atoms;                  /* [B] i32: atoms that exist                                                                   */
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptSasaArgs;
+size_t fdipt_sample_sasa_workspace(int B, int N, int atoms);
+/* FDIPT_EINVAL: a null pointer, B or N < 1, atoms not 37 or 5, n_points outside 1 .. 1024.  FDIPT_ESIZE: workspace too small, or more
+ * work items than a grid holds (B > 65535, B x N x atoms >= 2^31). */
+int fdipt_sample_sasa(const FdiptSasaArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */
 int fdipt_quat_to_rot(int n, const float* quat, float* rot, fdipt_stream_t s);           /* :185 */
