@@ -14,6 +14,7 @@
 // Every floating-point sum is "row i to thread i % 256, the thread's rows in ascending order, then a fixed tree over the block": a row
 // that is masked out adds nothing, so neither rows appended behind a sample nor its batch mates change a bit of its outputs.
 #include "common.hpp"
+#include "horn.hpp"
 
 #define EV_WAVES (FD_THREADS / FD_WAVE)
 #define EV_CA_CA 3.80209737096  // residue_constants.ca_ca
@@ -87,33 +88,6 @@ __device__ __forceinline__ double ev_row_delta2(const float* x, const float* y) 
     acc += ev_dot(d, d);
   }
   return acc;
-}
-
-// one Jacobi rotation of the symmetric A that zeroes A[P][Q]; V collects the rotations (its columns become the eigenvectors)
-template <int P, int Q>
-__device__ __forceinline__ void ev_jacobi(double (&A)[4][4], double (&V)[4][4]) {
-  const double apq = A[P][Q];
-  if (apq == 0.0) return;
-  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-  const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (k != P && k != Q) {
-      const double akp = A[k][P], akq = A[k][Q];
-      A[k][P] = A[P][k] = c * akp - s * akq;
-      A[k][Q] = A[Q][k] = s * akp + c * akq;
-    }
-  }
-  A[P][P] -= t * apq;
-  A[Q][Q] += t * apq;
-  A[P][Q] = A[Q][P] = 0.0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double vkp = V[k][P], vkq = V[k][Q];
-    V[k][P] = c * vkp - s * vkq;
-    V[k][Q] = s * vkp + c * vkq;
-  }
 }
 
 // ground-truth dihedrals of row r, with the chains and the res_mask of the first sample that names it
@@ -328,43 +302,8 @@ __global__ __launch_bounds__(FD_THREADS) void evaluate_kernel(FdiptEvalArgs a) {
   }
   ev_block_sum(H, red);
   if (tid == 0) {
-    // Horn's closed form: the unit quaternion of the best proper rotation is the eigenvector of the largest eigenvalue of this matrix
-    double A[4][4] = {{H[0] + H[4] + H[8], H[5] - H[7], H[6] - H[2], H[1] - H[3]},
-                      {H[5] - H[7], H[0] - H[4] - H[8], H[1] + H[3], H[6] + H[2]},
-                      {H[6] - H[2], H[1] + H[3], H[4] - H[0] - H[8], H[5] + H[7]},
-                      {H[1] - H[3], H[6] + H[2], H[5] + H[7], H[8] - H[0] - H[4]}};
-    double V[4][4] = {{1.0, 0.0, 0.0, 0.0}, {0.0, 1.0, 0.0, 0.0}, {0.0, 0.0, 1.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};
-    double scale = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) scale += fabs(A[p][q]);
-    for (int sweep = 0; sweep < 32; ++sweep) {
-      const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[0][3]) + fabs(A[1][2]) + fabs(A[1][3]) + fabs(A[2][3]);
-      if (off <= 1e-22 * scale) break;
-      ev_jacobi<0, 1>(A, V);
-      ev_jacobi<0, 2>(A, V);
-      ev_jacobi<0, 3>(A, V);
-      ev_jacobi<1, 2>(A, V);
-      ev_jacobi<1, 3>(A, V);
-      ev_jacobi<2, 3>(A, V);
-    }
-    double top = A[0][0], q0 = V[0][0], q1 = V[1][0], q2 = V[2][0], q3 = V[3][0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-      if (A[k][k] > top) { top = A[k][k]; q0 = V[0][k]; q1 = V[1][k]; q2 = V[2][k]; q3 = V[3][k]; }
-    double second = -1.0 / 0.0;
-    bool seen = false;  // (the first diagonal entry equal to `top` is the eigenvalue taken; a second one is a gap of 0)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (A[k][k] == top && !seen) seen = true;
-      else second = fmax(second, A[k][k]);
-    }
-    const double qn = 1.0 / sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-    q0 *= qn; q1 *= qn; q2 *= qn; q3 *= qn;
-    const double R[9] = {q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3, 2.0 * (q1 * q2 - q0 * q3), 2.0 * (q1 * q3 + q0 * q2),
-                         2.0 * (q1 * q2 + q0 * q3), q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3, 2.0 * (q2 * q3 - q0 * q1),
-                         2.0 * (q1 * q3 - q0 * q2), 2.0 * (q2 * q3 + q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3};
+    double R[9], top, second, scale;
+    fd_horn_rotation(H, R, top, second, scale);  // (horn.hpp)
     const double det = H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) + H[2] * (H[3] * H[7] - H[4] * H[6]);
     // the rotation is unique where the two largest eigenvalues differ: their gap is 2 (s2 + s3) of H's singular values, 2 (s2 - s3)
     // with a reflection; below 1e-9 of the matrix it is rounding

@@ -388,6 +388,85 @@ def run_sasa(out_dir: str, records, gathered: dict, inpainting: bool = False):
     return summary
 
 
+def write_diversity(out_dir: str, matrices: dict, tm_score_th: float = 0.5):
+    """``matrices``: sample length -> TM-score matrix [S,S] of the samples of that length.  Writes ``pairwise_tm_score_fixed_length_<L>.npy``
+    per length - deliberately not the reference's cache name ``pairwise_tm_score_length_<L>.npy``: the numbers are those of the row-by-row
+    correspondence, not TM-align's, and must not be picked up as such - and ``diversity.json`` / ``diversity.csv`` (length, samples,
+    clusters, diversity at the threshold).  Returns the summary written to ``diversity.json``."""
+    import csv
+
+    from . import tm_score
+    summary = {"tm_score_th": tm_score_th, "alignment": "fixed: row i with row i (a lower bound of TM-align's score)", "lengths": []}
+    for length in sorted(matrices):
+        matrix = np.asarray(matrices[length], dtype=np.float64)
+        np.save(os.path.join(out_dir, f"pairwise_tm_score_fixed_length_{int(length)}.npy"), matrix)
+        d = tm_score.diversity(matrix, tm_score_th)
+        summary["lengths"].append({"length": int(length), "samples": d["samples"], "clusters": d["clusters"], "diversity": d["diversity"],
+                                   "labels": d["labels"].tolist()})
+    with open(os.path.join(out_dir, "diversity.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "diversity.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["length", "samples", "clusters", "diversity"], extrasaction="ignore")
+        w.writeheader()
+        w.writerows({**e, "diversity": repr(e["diversity"])} for e in summary["lengths"])
+    return summary
+
+
+def write_tm_table(out_dir: str, structures: dict):
+    """``structures``: name -> {"samples": [labels], "tm_score": [S] against the ground truth over the diffused rows, "n_aligned": [S],
+    "matrix": [S,S] among the structure's samples}.  Writes ``tm_score.json`` (all of it) and ``tm_score.csv`` (one row per sample:
+    pdb_name, sample, n_aligned, tm_score).  Returns the summary written to ``tm_score.json``."""
+    import csv
+    number = lambda v: None if v != v else float(v)  # noqa: E731  (NaN: fewer than 3 rows)
+    summary = {"alignment": "fixed: row i with row i over the diffused rows", "structures": {}}
+    table = []
+    for name, e in structures.items():
+        summary["structures"][name] = {"samples": list(e["samples"]), "tm_score": [number(v) for v in e["tm_score"]],
+                                       "n_aligned": [int(v) for v in e["n_aligned"]],
+                                       "matrix": [[number(v) for v in row] for row in np.asarray(e["matrix"], dtype=np.float64)]}
+        table += [{"pdb_name": name, "sample": label, "n_aligned": int(n), "tm_score": repr(float(v))}
+                  for label, n, v in zip(e["samples"], e["n_aligned"], e["tm_score"])]
+    with open(os.path.join(out_dir, "tm_score.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "tm_score.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "n_aligned", "tm_score"])
+        w.writeheader()
+        w.writerows(table)
+    return summary
+
+
+def run_tm_score(out_dir: str, records, gathered: dict, inpainting: bool = False, tm_score_th: float = 0.5):
+    """Rank 0, after the gather (``--tm-score``; framedipt_amd/tm_score.py).  De novo runs: one all-against-all ``tm_scores`` call per
+    sample length, then ``write_diversity``.  Inpainting runs: per structure name one call of every sample against the ground truth
+    (``gt`` of a gathered entry) over the diffused rows that exist, the ``tm_score`` of the reference's protein_metrics, and one
+    all-against-all call among the structure's samples over the same rows, then ``write_tm_table``.  Returns the summary written."""
+    from . import tm_score
+    if not inpainting:
+        by_length = {}
+        for r in records:
+            by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+        matrices = {}
+        for length, rs in by_length.items():
+            prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
+            mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+            matrices[length] = tm_score.tm_scores(prot, mask_a=mask)["matrix"]
+        return write_diversity(out_dir, matrices, tm_score_th)
+    structures = {}
+    for name, rs in group_records_by_name(records).items():
+        items = [gathered[r["item"]] for r in rs]
+        prot = np.stack([it["prot"] for it in items]).astype(np.float32)
+        mask = np.stack([it["diffused"] * (1 if it.get("res_mask") is None else it["res_mask"]) for it in items]).astype(np.float32)
+        truth = next((it["gt"] for it in items if "gt" in it), None)
+        entry = {"samples": [str(r["sample_i"]) for r in rs], "matrix": tm_score.tm_scores(prot, mask_a=mask)["matrix"]}
+        if truth is not None:
+            against = tm_score.tm_scores(prot, np.asarray(truth, dtype=np.float32)[None], mask_a=mask)
+            entry.update(tm_score=against["tm"], n_aligned=against["n_aligned"])
+        else:
+            entry.update(tm_score=np.full(len(rs), np.nan), n_aligned=mask.sum(1).astype(np.int64))
+        structures[str(name)] = entry
+    return write_tm_table(out_dir, structures)
+
+
 def reference_layout_writer(out_dir: str, net, final_only: bool):
     """``write_item`` for inpainting runs: what ``Inference.run_conditional_sampling`` leaves on disk per sample
     (experiments/inference.py:250-389): ``<pdb>_length_<L>/`` with the ground-truth structure ``<pdb>_1.pdb`` (b-factor 100 = diffused) and
@@ -495,6 +574,11 @@ def main():
     ap.add_argument("--sasa", action="store_true", help="after the run, rank 0 computes the solvent accessibility of every sample on its GPU "
                     "(framedipt_amd/sasa.py: Shrake-Rupley ASA per residue of the diffused rows with the whole complex as context, and RSA, "
                     "the ASA / RSA block of the reference's metric table): sasa.json and sasa.csv; inpainting runs score the ground truth too")
+    ap.add_argument("--tm-score", action="store_true", help="after the run, rank 0 computes TM-scores on its GPU (framedipt_amd/tm_score.py: the score of the "
+                    "row-by-row correspondence, not TM-align's alignment search).  De novo runs: all-against-all per sample length, Ward clusters and "
+                    "diversity = clusters / samples: pairwise_tm_score_fixed_length_<L>.npy, diversity.json, diversity.csv.  Inpainting runs: every sample "
+                    "against the ground truth over the diffused rows and the matrix per structure: tm_score.json, tm_score.csv")
+    ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score: the TM-score threshold of the clusters (reference default)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
     if a.keep not in ("all", "last"):
@@ -588,9 +672,9 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score else None
     ground_truth = None
-    if (a.evaluate or a.sasa) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
+    if (a.evaluate or a.sasa or a.tm_score) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
             build = lambda: inference.get_atom_positions_from_rigids(net, feats["rigids_0"], feats["torsion_angles_sin_cos"][..., 2, :], feats["aatype"])[0]  # noqa: E731
             return one_gpu_turn(build) if one_gpu and world > 1 else build()
@@ -601,7 +685,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -635,6 +719,12 @@ def main():
             done = run_sasa(a.out_dir, allrecs, gathered, inpainting=inp)
             print(f"solvent accessibility of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
                   f"{a.out_dir}/sasa.json, sasa.csv", flush=True)
+        if a.tm_score:
+            t1 = time.perf_counter()
+            done = run_tm_score(a.out_dir, allrecs, gathered, inpainting=inp, tm_score_th=a.tm_score_th)
+            what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_score.json, tm_score.csv" if inp else \
+                f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity.json, diversity.csv, pairwise_tm_score_fixed_length_<L>.npy"
+            print(f"TM-scores of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

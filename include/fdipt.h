@@ -597,6 +597,51 @@ size_t fdipt_sample_sasa_workspace(int B, int N, int atoms);
  * work items than a grid holds (B > 65535, B x N x atoms >= 2^31). */
 int fdipt_sample_sasa(const FdiptSasaArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- TM-score (opt-in) */
+/* The TM-score of a GIVEN residue correspondence (row i with row i), Zhang & Skolnick's TMscore search over seed superpositions, for P
+ * pairs of structures, in float64 with contraction off, in one launch of a block per pair.  It is the quantity behind the reference's
+ * tm_score keys (framedipt/analysis/metrics.py:protein_metrics, experiments/inference.py) where the alignment is the identity, and a
+ * lower bound of tmtools.tm_align's score in the all-against-all matrix of evaluation/eval_denovo.py:hierarchy_diversity: TM-align's
+ * alignment search is NOT built, and no tmtools was at hand to compare with.  The contract is DESIGN.md section 7.8.
+ * x, y: the CA atoms of the rows where both structures' masks are set, in ascending row order, float32 widened; n their number;
+ * L = norm_length of the pair where given and > 0, else n.  d0 = 1.24 cbrt(L - 15) - 1.8 for L > 21, else 0.5; d_search = min(max(d0,
+ * 4.5), 8).  S(R, t) = sum over all n rows of d0^2 / (d0^2 + |R x_i + t - y_i|^2); tm = max S / L.  Fragment lengths n >> k, k = 0..4,
+ * while the value exceeds 4, then 4 (n below 4: n); a seed is (length l, start s), every s in 0 .. n - l, numbered level-major,
+ * start-minor.  Per seed: superpose the fragment (Horn, proper rotation), score all rows, select the rows with |d|^2 < cut^2 (cut =
+ * d_search - 1 in the first pass, d_search + 1 later; + 0.5 while fewer than 3 rows are inside and n > 3, up to 10^4), stop where the
+ * set equals the set just superposed or after 20 refinements, else superpose the set and score again.  The result is the first seed in
+ * seed order that holds the largest score, with the transform at which it reached it.  Every output of a pair depends on that pair's
+ * masked rows only: batch mates, rows appended behind a structure and the pair's place in the list change no bit. */
+#define FDIPT_TM_MAX_ROWS 1024       /* N beyond: FDIPT_ESIZE (two traces and the seeds' selected sets live in LDS)                  */
+#define FDIPT_TM_TOO_SHORT 1         /* status: n < 3, no search; tm = NaN                                                          */
+#define FDIPT_TM_SKIPPED 2           /* status: a structure index of the pair is out of range; tm = NaN                             */
+#define FDIPT_TM_NOT_FINITE 4        /* status: no seed scored (coordinates that are not finite); tm = NaN                          */
+typedef struct FdiptTmArgs {
+  int32_t S, N, atoms, ca;           /* structures, rows, atoms per row of prot: 37 or 5; the CA column (1 in both layouts)         */
+  int32_t S_b, atoms_b;              /* of prot_b (ignored where prot_b is NULL)                                                    */
+  int32_t P;                         /* pairs                                                                                       */
+  const float* prot;                 /* [S,N,atoms,3] f32                                                                           */
+  const float* mask;                 /* [S,N] f32                                                                                   */
+  const float* prot_b;               /* [S_b,N,atoms_b,3] f32 or NULL: the second structure of a pair comes from here, else from prot */
+  const float* mask_b;               /* [S_b,N] f32 (with prot_b)                                                                   */
+  const int32_t* pairs;              /* [P,2] i32: (index into prot, index into prot_b or prot); x is the first, y the second       */
+  const int32_t* norm_length;        /* [P] i32 or NULL: L of the pair where > 0                                                    */
+  /* outputs: [P] */
+  double* tm;                        /* f64: max S / L; NaN with a status bit                                                       */
+  double* rotation;                  /* [P,3,3] f64: R x + t ~ y at the best seed's best pass; the identity with a status bit       */
+  double* translation;               /* [P,3] f64                                                                                   */
+  int32_t* n_aligned;                /* i32: n                                                                                      */
+  double* d0;                        /* f64                                                                                         */
+  int32_t* best_seed;                /* i32: the seed number of the result; -1 with a status bit                                    */
+  int32_t* passes;                   /* i32: superpositions scored over all seeds of the pair (a diagnostic)                        */
+  int32_t* status;                   /* i32: FDIPT_TM_* bits                                                                        */
+  void* workspace;                   /* may be NULL: fdipt_sample_tm_score_workspace is 0 (the search lives in LDS and registers)   */
+  size_t workspace_bytes;
+} FdiptTmArgs;
+size_t fdipt_sample_tm_score_workspace(int S, int N, int P);
+/* FDIPT_EINVAL: a null pointer, S, N or P < 1, atoms not 37 or 5, ca outside 0 .. 4.  FDIPT_ESIZE: N > FDIPT_TM_MAX_ROWS. */
+int fdipt_sample_tm_score(const FdiptTmArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */
 int fdipt_quat_to_rot(int n, const float* quat, float* rot, fdipt_stream_t s);           /* :185 */
