@@ -467,6 +467,103 @@ def run_tm_score(out_dir: str, records, gathered: dict, inpainting: bool = False
     return write_tm_table(out_dir, structures)
 
 
+def write_diversity_aligned(out_dir: str, aligned: dict, fixed: dict, tm_score_th: float = 0.5, skipped=()):
+    """``aligned``: sample length -> matrix [S,S] of ``tm_align`` (entry (i, j) = ``tm_b``, mirrored); ``fixed``: the matrix of ``tm_scores``
+    of the same samples.  Both are scores of a valid alignment under the same normalisation, so the larger is the tighter lower bound of
+    the optimum: ``fmax(aligned, fixed)`` - where one of the two is NaN (a status bit), the other - is written as
+    ``pairwise_tm_score_aligned_length_<L>.npy`` - still not the reference's cache name, nothing is pinned against tmtools - and
+    clustered into ``diversity_aligned.json`` / ``diversity_aligned.csv``.  Per length the json records ``fixed_won``, the pairs i < j
+    where the fixed correspondence scored above the search or the search gave no score, and ``nan_pairs``, the pairs without either
+    score: a length with such pairs is written but not clustered (``clusters`` and ``diversity`` null).  ``skipped``: lengths beyond the
+    row limit of the search.  Returns the summary written to ``diversity_aligned.json``."""
+    import csv
+
+    from . import tm_score
+    summary = {"tm_score_th": tm_score_th, "alignment": "searched (DESIGN.md section 7.9; no parity with tmtools.tm_align is claimed), "
+               "the fixed row-by-row score where it is larger", "lengths": [], "skipped_lengths": [int(v) for v in skipped]}
+    for length in sorted(aligned):
+        a, f = np.asarray(aligned[length], dtype=np.float64), np.asarray(fixed[length], dtype=np.float64)
+        matrix = np.fmax(a, f)
+        np.save(os.path.join(out_dir, f"pairwise_tm_score_aligned_length_{int(length)}.npy"), matrix)
+        entry = {"length": int(length), "samples": int(len(a)), "clusters": None, "diversity": None,
+                 "fixed_won": int(np.triu((f > a) | (np.isnan(a) & ~np.isnan(f)), 1).sum()), "nan_pairs": int(np.triu(np.isnan(matrix), 1).sum()),
+                 "pairs": int(len(a) * (len(a) - 1) // 2), "labels": None}
+        if entry["nan_pairs"] == 0:
+            d = tm_score.diversity(matrix, tm_score_th)
+            entry.update(clusters=d["clusters"], diversity=d["diversity"], labels=d["labels"].tolist())
+        summary["lengths"].append(entry)
+    with open(os.path.join(out_dir, "diversity_aligned.json"), "w") as fh:
+        json.dump(summary, fh, indent=1)
+    with open(os.path.join(out_dir, "diversity_aligned.csv"), "w", newline="") as fh:
+        w = csv.DictWriter(fh, fieldnames=["length", "samples", "clusters", "diversity", "fixed_won", "nan_pairs"], extrasaction="ignore")
+        w.writeheader()
+        w.writerows({**e, "diversity": "" if e["diversity"] is None else repr(e["diversity"]), "clusters": "" if e["clusters"] is None else e["clusters"]}
+                    for e in summary["lengths"])
+    return summary
+
+
+def write_tm_align_table(out_dir: str, structures: dict, skipped=None):
+    """``structures``: name -> {"samples": [labels], "rows": the most rows any sample of the structure was aligned over, "matrix": [S,S] of
+    ``tm_align`` among the structure's samples over the diffused rows}; ``skipped``: name -> rows, the structures with more diffused rows
+    than the search takes.  Writes ``tm_align.json``.  Returns the summary written."""
+    number = lambda v: None if v != v else float(v)  # noqa: E731  (NaN: a status bit)
+    summary = {"alignment": "searched over the diffused rows (DESIGN.md section 7.9)", "structures": {
+        name: {"samples": list(e["samples"]), "rows": int(e["rows"]), "matrix": [[number(v) for v in row] for row in np.asarray(e["matrix"], dtype=np.float64)]}
+        for name, e in structures.items()}, "skipped_structures": {str(k): int(v) for k, v in (skipped or {}).items()}}
+    with open(os.path.join(out_dir, "tm_align.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    return summary
+
+
+def compact_rows(prot, mask):
+    """prot [S,N,A,3], mask [S,N] -> (prot [S,M,A,3] float32, mask [S,M] float32): per sample the rows whose mask is set, in ascending
+    order, moved to the front; M is the largest number of set rows of a sample (at least 1), the rows behind a sample's own are masked
+    out.  The alignment search takes each structure over its set rows only and limits the rows of the arrays it is given, so a few
+    dozen diffused rows of a complex of any size pass."""
+    prot, keep = np.asarray(prot, dtype=np.float32), np.asarray(mask) != 0
+    m = max(int(keep.sum(1).max()), 1)
+    out, out_mask = np.zeros((prot.shape[0], m) + prot.shape[2:], dtype=np.float32), np.zeros((prot.shape[0], m), dtype=np.float32)
+    for s in range(prot.shape[0]):
+        k = int(keep[s].sum())
+        out[s, :k], out_mask[s, :k] = prot[s, keep[s]], 1.0
+    return out, out_mask
+
+
+def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False, tm_score_th: float = 0.5):
+    """Rank 0, after the gather (``--tm-align``; framedipt_amd/tm_align.py).  De novo runs: per sample length one all-against-all
+    ``tm_align`` call and one ``tm_scores`` call, then ``write_diversity_aligned``.  Inpainting runs: the aligned matrix among the samples
+    of every structure name over the diffused rows that exist, ``write_tm_align_table`` (the sample-against-ground-truth number stays the
+    fixed one of ``--tm-score``).  The samples go to the search compacted to their set rows (``compact_rows``): its row limit then
+    applies to those rows, not to the complex.  What still exceeds it is recorded as skipped.  Returns the summary written."""
+    from . import tm_align, tm_score
+    if not inpainting:
+        by_length = {}
+        for r in records:
+            by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+        aligned, fixed, skipped = {}, {}, []
+        for length, rs in by_length.items():
+            prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
+            mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+            rows, rows_mask = compact_rows(prot, mask)
+            if rows.shape[1] > tm_align.MAX_ROWS:
+                skipped.append(length)
+                continue
+            aligned[length] = tm_align.tm_align(rows, mask_a=rows_mask)["matrix"]
+            fixed[length] = tm_score.tm_scores(prot, mask_a=mask)["matrix"]
+        return write_diversity_aligned(out_dir, aligned, fixed, tm_score_th, skipped)
+    structures, skipped = {}, {}
+    for name, rs in group_records_by_name(records).items():
+        items = [gathered[r["item"]] for r in rs]
+        prot = np.stack([it["prot"] for it in items]).astype(np.float32)
+        mask = np.stack([it["diffused"] * (1 if it.get("res_mask") is None else it["res_mask"]) for it in items]).astype(np.float32)
+        rows, rows_mask = compact_rows(prot, mask)
+        if rows.shape[1] > tm_align.MAX_ROWS:
+            skipped[str(name)] = rows.shape[1]
+            continue
+        structures[str(name)] = {"samples": [str(r["sample_i"]) for r in rs], "rows": rows.shape[1], "matrix": tm_align.tm_align(rows, mask_a=rows_mask)["matrix"]}
+    return write_tm_align_table(out_dir, structures, skipped)
+
+
 def reference_layout_writer(out_dir: str, net, final_only: bool):
     """``write_item`` for inpainting runs: what ``Inference.run_conditional_sampling`` leaves on disk per sample
     (experiments/inference.py:250-389): ``<pdb>_length_<L>/`` with the ground-truth structure ``<pdb>_1.pdb`` (b-factor 100 = diffused) and
@@ -578,7 +675,11 @@ def main():
                     "row-by-row correspondence, not TM-align's alignment search).  De novo runs: all-against-all per sample length, Ward clusters and "
                     "diversity = clusters / samples: pairwise_tm_score_fixed_length_<L>.npy, diversity.json, diversity.csv.  Inpainting runs: every sample "
                     "against the ground truth over the diffused rows and the matrix per structure: tm_score.json, tm_score.csv")
-    ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score: the TM-score threshold of the clusters (reference default)")
+    ap.add_argument("--tm-align", action="store_true", help="after the run, rank 0 searches structural alignments on its GPU (framedipt_amd/tm_align.py: "
+                    "a TM-align style search, this project's own contract; no parity with tmtools is claimed).  De novo runs: all-against-all per sample "
+                    "length, the larger of the searched and the fixed score: pairwise_tm_score_aligned_length_<L>.npy, diversity_aligned.json, "
+                    "diversity_aligned.csv.  Inpainting runs: the aligned matrix per structure: tm_align.json")
+    ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score, --tm-align: the TM-score threshold of the clusters (reference default)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
     if a.keep not in ("all", "last"):
@@ -672,7 +773,7 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align else None
     ground_truth = None
     if (a.evaluate or a.sasa or a.tm_score) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
@@ -685,7 +786,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -725,6 +826,12 @@ def main():
             what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_score.json, tm_score.csv" if inp else \
                 f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity.json, diversity.csv, pairwise_tm_score_fixed_length_<L>.npy"
             print(f"TM-scores of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
+        if a.tm_align:
+            t1 = time.perf_counter()
+            done = run_tm_align(a.out_dir, allrecs, gathered, inpainting=inp, tm_score_th=a.tm_score_th)
+            what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_align.json" if inp else \
+                f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity_aligned.json, diversity_aligned.csv, pairwise_tm_score_aligned_length_<L>.npy"
+            print(f"structural alignments of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

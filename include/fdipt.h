@@ -642,6 +642,57 @@ size_t fdipt_sample_tm_score_workspace(int S, int N, int P);
 /* FDIPT_EINVAL: a null pointer, S, N or P < 1, atoms not 37 or 5, ca outside 0 .. 4.  FDIPT_ESIZE: N > FDIPT_TM_MAX_ROWS. */
 int fdipt_sample_tm_score(const FdiptTmArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- TM-align search (opt-in) */
+/* A sequence-independent structural alignment search for P pairs of CA traces, in float64 with contraction off, a block per pair: the
+ * quantity evaluation/eval_denovo.py:hierarchy_diversity takes from tmtools.tm_align for its all-against-all matrix.  The contract is
+ * DESIGN.md section 7.9; it is modelled on Zhang & Skolnick's TM-align (its search parameters, three of its initial alignments, its
+ * heuristic dynamic-programming iteration, the d8 filter, final scores per chain length) and is this project's own: no tmtools and no
+ * TM-align source was at hand, and NO parity with tm_align is claimed.
+ * x: the CA atoms of the rows of the first structure whose mask is set, ascending, float32 widened, n1 rows; y likewise for the second
+ * structure, n2 rows (the two are compacted separately; N_b may differ from N_a).  Ls = min(n1, n2); d0s = (Ls <= 19 ? 0.168 : 1.24
+ * cbrt(Ls - 15) - 1.8) + 0.8; ds = min(max(d0s, 4.5), 8); d8 = 1.5 Ls^0.3 + 3.5.  Initial alignments: I1 the best gapless threading
+ * by the fast score, I2 a dynamic programme on the secondary structure of the traces, I3 one on secondary structure plus distance
+ * under the better of their two transforms.  Each is scored by the seed search of the TM-score block above (fragment starts 40 apart,
+ * pairs beyond d8 not scored) and iterated: dynamic programme on d0s^2 / (d0s^2 + d^2) under the search's transform with gap penalty
+ * -0.6 then 0, up to 30 times each, until the score settles.  The best alignment loses its pairs beyond d8 and is scored by the full
+ * search (start step 1, no d8) once per normalisation length.  Every output of a pair depends on that pair's masked rows only. */
+#define FDIPT_TMA_MAX_ROWS 512       /* N_a or N_b beyond: FDIPT_ESIZE (the traces and the programme's directions live in LDS)       */
+#define FDIPT_TMA_TOO_SHORT 1        /* status: n1 < 5 or n2 < 5, no search; tm = NaN                                               */
+#define FDIPT_TMA_SKIPPED 2          /* status: a structure index of the pair is out of range; tm = NaN                             */
+#define FDIPT_TMA_NOT_FINITE 4       /* status: a coordinate of a set row is not finite, no search; tm = NaN                        */
+#define FDIPT_TMA_NO_ALIGNMENT 8     /* status: fewer than 3 pairs of the best alignment lie within d8; tm = NaN                    */
+typedef struct FdiptTmAlignArgs {
+  int32_t S, N_a, atoms, ca;         /* structures, rows, atoms per row of prot: 37 or 5; the CA column (1 in both layouts)         */
+  int32_t S_b, N_b, atoms_b;         /* of prot_b (where prot_b is NULL: S_b and atoms_b ignored, N_b = N_a)                        */
+  int32_t P;                         /* pairs                                                                                       */
+  const float* prot;                 /* [S,N_a,atoms,3] f32                                                                         */
+  const float* mask;                 /* [S,N_a] f32                                                                                 */
+  const float* prot_b;               /* [S_b,N_b,atoms_b,3] f32 or NULL: the second structure of a pair comes from here, else from prot */
+  const float* mask_b;               /* [S_b,N_b] f32 (with prot_b)                                                                 */
+  const int32_t* pairs;              /* [P,2] i32: (index into prot, index into prot_b or prot); x is the first, y the second       */
+  /* outputs: [P] */
+  double* tm;                        /* f64: tm_b, what hierarchy_diversity takes; NaN with a status bit                            */
+  double* tm_a;                      /* f64: the final search's S / n1 with d0(n1)                                                  */
+  double* tm_b;                      /* f64: the final search's S / n2 with d0(n2)                                                  */
+  double* rotation;                  /* [P,3,3] f64: R x + t ~ y of the tm_b search; the identity with a status bit                 */
+  double* translation;               /* [P,3] f64                                                                                   */
+  int32_t* alignment;                /* [P,N_b] i32: the row of the first structure aligned with each row of the second, or -1      */
+  int32_t* n_aligned;                /* i32: aligned pairs (within d8)                                                              */
+  double* rmsd;                      /* f64: of the aligned pairs under the returned transform                                      */
+  double* d0_a;                      /* f64: d0(n1)                                                                                 */
+  double* d0_b;                      /* f64: d0(n2)                                                                                 */
+  double* init_tm;                   /* [P,3] f64: S / Ls of each initial alignment before its iteration; -1 where it was skipped   */
+  int32_t* init_dp;                  /* [P,3] i32: dynamic programmes of each initial alignment's iteration                         */
+  int32_t* best_init;                /* i32: the initial alignment whose iteration gave the result; -1 with a status bit before it  */
+  int32_t* status;                   /* i32: FDIPT_TMA_* bits                                                                       */
+  void* workspace;                   /* may be NULL: fdipt_sample_tm_align_workspace is 0 (the search lives in LDS and registers)   */
+  size_t workspace_bytes;
+} FdiptTmAlignArgs;
+size_t fdipt_sample_tm_align_workspace(int S, int N_a, int N_b, int P);
+/* FDIPT_EINVAL: a null pointer, S, N_a, N_b or P < 1, atoms not 37 or 5, ca outside 0 .. 4.  FDIPT_ESIZE: N_a or N_b >
+ * FDIPT_TMA_MAX_ROWS. */
+int fdipt_sample_tm_align(const FdiptTmAlignArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */
 int fdipt_quat_to_rot(int n, const float* quat, float* rot, fdipt_stream_t s);           /* :185 */
