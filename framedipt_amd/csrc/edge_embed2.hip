@@ -44,7 +44,9 @@ __device__ __forceinline__ void mma_slab(f32x16& acc, const char* slab, int li, 
 // pz_tile (round 6): when set, the epilogue also emits pair_z = down_z(z') + b of the first block's IPA for this row's 32 keys (8 key
 // groups of 256 B, layout fd_pz_bytes; groups >= ng_valid are beyond N): z' is the A operand of these MFMAs, so a lane (d, half) ends
 // up with four consecutive keys per register quad = 8 B of the image; hi + lo weight fragments follow the compact linear_b image in LDS
-template <bool TRACE>
+// TABLE (the row-table launch, below): the 32 "pairs" of the tile are table rows; the same arithmetic, but the pair bias goes to
+// bias_out as [row][8 heads] and pair_z to pz_tile as [row][32 d] (nvalid rows), the records ee2_spread_kernel copies from
+template <bool TRACE, bool TABLE = false>
 __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamma_l, const float* beta_l, float em, int li, int hi,
                                                int lane, char* stage, half_t* __restrict__ z_tile, int nvalid,
                                                float* __restrict__ tr_row, bool valid, const char* wb_lds, const f32x4 bbv,
@@ -118,7 +120,9 @@ __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamm
     for (int s = 0; s < 8; ++s) accb = fd_mfma32(wf[s], __builtin_bit_cast(hx8, zB[s]), accb);
     float* bo = bias_out + fd_bias_frag_off(bidx * H + 4 * hi, nt, ii, valid ? jj : 0);  // 32 lanes = 32 consecutive keys: 128 B rows
     const long hstride = (long)nt * nt * 1024;  // floats per (sample, head)
-    if (full && H == 8) {
+    if constexpr (TABLE) {
+      if (valid) *(f32x4*)(bias_out + li * 8 + 4 * hi) = f32x4{accb[0] + bbv[0], accb[1] + bbv[1], accb[2] + bbv[2], accb[3] + bbv[3]};
+    } else if (full && H == 8) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) bo[r * hstride] = accb[r] + bbv[r];
     } else if (valid) {
@@ -144,7 +148,12 @@ __device__ __forceinline__ void ee_ln_epilogue(f32x16 (&Y)[4], const float* gamm
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const u32x2 ow = {fd_cvt_pk(accd[4 * g], accd[4 * g + 1]), fd_cvt_pk(accd[4 * g + 2], accd[4 * g + 3])};
-        if (2 * g + hi < ng_valid) *(u32x2*)(pz_tile + ((2 * g + hi) * 32 + li) * 4) = ow;
+        if constexpr (TABLE) {  // (the same conversions; one row's 32 channels are 64 contiguous bytes)
+          unsigned short* pt = (unsigned short*)pz_tile + (8 * g + 4 * hi) * 32 + li;
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (8 * g + 4 * hi + q < nvalid) pt[q * 32] = (unsigned short)(ow[q >> 1] >> (16 * (q & 1)));
+        } else if (2 * g + hi < ng_valid) *(u32x2*)(pz_tile + ((2 * g + hi) * 32 + li) * 4) = ow;
       }
     }
   }
@@ -247,9 +256,63 @@ __device__ unsigned ee2_prof[256 * 8];
 static_assert(EE2_LDS_BASE + (22 + 1) * ET2_CZ * 4 <= EE2_LDS_MAX, "edge_embed2: the 22-bin distogram rows no longer fit in LDS");
 // DIST = false: the model has no distogram channels (num_bins = 0); DLDS is then false as well.  LO (fp16x): layers 2 and 3 add W_lo h,
 // the lo images following the hi ones in `img` (fd_ee2_build_images lo = 1)
-template <bool DIST, bool DLDS, bool TRACE, bool LO = false>
+// distogram bin of one distance: calc_distogram's strict inequalities against the stored edges (last upper edge 1e8); the
+// candidate comes from the edge spacing, its neighbours are re-tested, so the result is the one a full scan finds.  One copy for
+// the pair kernel and the spread launch: a pair's bin must not depend on which of them computes it
+struct Ee2Bins {
+  const float* edg;  // [nb + 1] in LDS
+  int nb;
+  float e0, inv_step;
+  __device__ __forceinline__ Ee2Bins(const float* e, int n) : edg(e), nb(n), e0(e[0]), inv_step(n > 1 ? 1.0f / (e[1] - e[0]) : 0.f) {}
+  __device__ __forceinline__ int of(float d) const {
+    int k0 = (int)((d - e0) * inv_step);
+    k0 = k0 < 1 ? 1 : (k0 > nb - 2 ? nb - 2 : k0);
+    int bin = nb;
+#pragma unroll
+    for (int k = -1; k <= 1; ++k) {
+      const int kk = k0 + k;
+      if (kk >= 0 && kk < nb && d > edg[kk] && d < edg[kk + 1]) bin = kk;
+    }
+    return bin;
+  }
+  __device__ __forceinline__ int of_pair(float i0, float i1, float i2, float j0, float j1, float j2) const {
+    const float dx = i0 - j0, dy = i1 - j1, dz = i2 - j2;
+    return of(sqrtf(dx * dx + dy * dy + dz * dz));
+  }
+};
+
+// ---- the row table (model.hip: ForwardPlan.ee_table).  Without aatype features Pi and Pj depend on a residue only through its
+// fixed-mask bit, so the launch's whole output for a pair is a function of (sample, class_i, class_j, rel, bin): the TABLE
+// instantiation evaluates each such row once (same arithmetic as the pair kernel) and ee2_spread_kernel copies the records to the pairs.
+// Row r of sample b: b * rows_per_sample + ((2 class_i + class_j) * n_rel + rel) * (num_bins + 1) + bin; the sample's last row is the
+// all-zero row of masked pairs.  Records: z [128] half, pair bias [8] f32, pair_z [32] half, one array each.
+__host__ __device__ __forceinline__ int ee2_rows_per_sample(int n_rel, int nb) { return 4 * n_rel * (nb + 1) + 1; }
+size_t fd_ee2_table_bytes(int B, int n_rel, int num_bins) {
+  return (size_t)B * ee2_rows_per_sample(n_rel, num_bins) * (ET2_CZ * 2 + 8 * 4 + 32 * 2);
+}
+struct Ee2Table {
+  half_t* z;
+  float* bias;
+  half_t* pz;
+  int rps;
+};
+__host__ __device__ __forceinline__ Ee2Table ee2_table_of(void* table, int B, int n_rel, int nb) {
+  Ee2Table t;
+  t.rps = ee2_rows_per_sample(n_rel, nb);
+  const size_t rows = (size_t)B * t.rps;
+  t.z = (half_t*)table;
+  t.bias = (float*)((char*)table + rows * ET2_CZ * 2);
+  t.pz = (half_t*)((char*)table + rows * (ET2_CZ * 2 + 8 * 4));
+  return t;
+}
+
+// TABLE: a tile is 32 bins of one (sample, class pair, rel) and the walk goes over rel: Pi / Pj are the rows of the first residue of
+// either class (items of a class pair the sample does not have end at once), R[rel] is one row for the whole tile, the mask is 1.
+// nt = bin tiles; items are class-pair major so that the live ones of a one-class batch are consecutive
+template <bool DIST, bool DLDS, bool TRACE, bool LO = false, bool TABLE = false>
 __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedArgs a, const char* __restrict__ img, int nt, int wpg,
                                                                      int rpw, int n_items) {
+  static_assert(!TABLE || (DIST && !TRACE), "the row table: distogram models, no trace");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef EE2_PROF
   unsigned ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = (unsigned)__builtin_amdgcn_s_memtime();
@@ -294,61 +357,77 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
   const int N = a.N, nb = a.num_bins;
   const float* b2row = vec + 4 * hi;
   const f32x4 bbv = a.wb_img ? f32x4{a.bb[4 * hi], a.bb[4 * hi + 1], a.bb[4 * hi + 2], a.bb[4 * hi + 3]} : f32x4{0.f, 0.f, 0.f, 0.f};
-  // distogram bin of one distance: calc_distogram's strict inequalities against the stored edges (last upper edge 1e8); the
-  // candidate comes from the edge spacing, its neighbours are re-tested, so the result is the one a full scan finds
-  const float e0 = edg[0], inv_step = nb > 1 ? 1.0f / (edg[1] - edg[0]) : 0.f;
-  auto bin_of = [&](float d) {
-    int k0 = (int)((d - e0) * inv_step);
-    k0 = k0 < 1 ? 1 : (k0 > nb - 2 ? nb - 2 : k0);
-    int bin = nb;
-#pragma unroll
-    for (int k = -1; k <= 1; ++k) {
-      const int kk = k0 + k;
-      if (kk >= 0 && kk < nb && d > edg[kk] && d < edg[kk + 1]) bin = kk;
+  const Ee2Bins bins(edg, nb);
+  const Ee2Table tab = TABLE ? ee2_table_of(a.table, a.B, a.n_rel, nb) : Ee2Table{};
+  if (TABLE && blockIdx.x == 0 && tid < 64) {  // the zero rows of masked pairs: what the epilogue emits from a zeroed z
+    for (int b = 0; b < a.B; ++b) {
+      const long zr = (long)(b + 1) * tab.rps - 1;
+      ((unsigned*)(tab.z + zr * ET2_CZ))[tid] = 0u;
+      if (tid < 8) tab.bias[zr * 8 + tid] = 0.f + (tid < a.H ? a.bb[tid] : 0.f);
+      if (tid < 32) ((unsigned short*)tab.pz)[zr * 32 + tid] = (unsigned short)fd_cvt_pk(0.f + a.bdz[tid], 0.f);
     }
-    return bin;
-  };
+  }
   for (int item = blockIdx.x * 8 + wave; item < n_items; item += gridDim.x * 8) {
     // ---- group (sample b, key tile jt): per-key state of the 32 keys, resident for the whole walk
-    const int grp = item / wpg, part = item - grp * wpg;
+    const int per_cc = TABLE ? n_items >> 2 : n_items, cc = TABLE ? item / per_cc : 0, it_cc = item - cc * per_cc;
+    const int grp = it_cc / wpg, part = it_cc - grp * wpg;
     const int b = grp / nt, jt = grp - b * nt, j0 = jt * 32;
-    const int i_first = part * rpw, i_end = (i_first + rpw < N) ? i_first + rpw : N;
+    const int n_walk = TABLE ? a.n_rel : N, n_keys = TABLE ? nb + 1 : N;  // TABLE: the walk is over rel, the "keys" are bins
+    const int i_first = part * rpw, i_end = (i_first + rpw < n_walk) ? i_first + rpw : n_walk;
     if (i_first >= i_end) continue;
-    const int nvalid = N - j0 < 32 ? N - j0 : 32;
+    const int nvalid = n_keys - j0 < 32 ? n_keys - j0 : 32;
     const bool valid = li < nvalid;
-    const int j = valid ? j0 + li : N - 1;
+    int rep_i = 0, rep_j = 0;  // TABLE: the first residue of class_i / class_j (wave-uniform)
+    if constexpr (TABLE) {
+      rep_i = rep_j = N;
+      for (int k0 = 0; k0 < N && (rep_i == N || rep_j == N); k0 += 64) {
+        const int k = k0 + lane;
+        const int c = k < N ? (a.fixed_mask[(long)b * N + k] != 0.f ? 1 : 0) : -1;
+        const unsigned long long mi_ = __ballot(c == (cc >> 1)), mj_ = __ballot(c == (cc & 1));
+        if (rep_i == N && mi_) rep_i = k0 + __ffsll((long long)mi_) - 1;
+        if (rep_j == N && mj_) rep_j = k0 + __ffsll((long long)mj_) - 1;
+      }
+      rep_i = __builtin_amdgcn_readfirstlane(rep_i);
+      rep_j = __builtin_amdgcn_readfirstlane(rep_j);
+      if (rep_i == N || rep_j == N) continue;  // the sample has no pair of this class pair
+    }
+    const int j = TABLE ? rep_j : valid ? j0 + li : N - 1;
     const long bj = (long)b * N + j;
-    const int sj = a.seq_idx[bj];
-    const float mj = a.res_mask[bj];
-    const float cj0 = DIST ? a.sc_ca[bj * 3] : 0.f, cj1 = DIST ? a.sc_ca[bj * 3 + 1] : 0.f, cj2 = DIST ? a.sc_ca[bj * 3 + 2] : 0.f;
-    const float* pj_base = a.pj + ((long)b * N + j0) * ET2_CZ + 4 * li;  // row r of the tile at + min(r, nvalid - 1) * 128
+    const int sj = TABLE ? 0 : a.seq_idx[bj];
+    const float mj = TABLE ? 1.f : a.res_mask[bj];
+    const float cj0 = DIST && !TABLE ? a.sc_ca[bj * 3] : 0.f, cj1 = DIST && !TABLE ? a.sc_ca[bj * 3 + 1] : 0.f,
+                cj2 = DIST && !TABLE ? a.sc_ca[bj * 3 + 2] : 0.f;
+    // row r of the tile at + min(r, nvalid - 1) * 128 (TABLE: the one row of class_j)
+    const float* pj_base = a.pj + ((long)b * N + (TABLE ? rep_j : j0)) * ET2_CZ + 4 * li;
     // per-row scalars (wave-uniform addresses: scalar loads) -> this lane's table row ids
     // per-row scalars: requested (scalar loads) at the top of the previous row, turned into table row ids after its gather
     struct RowIn { int si; float mi, c0, c1, c2; };
     auto row_request = [&](int i) {
       const long bi = (long)b * N + i;
-      if constexpr (DIST) return RowIn{a.seq_idx[bi], a.res_mask[bi], a.sc_ca[bi * 3], a.sc_ca[bi * 3 + 1], a.sc_ca[bi * 3 + 2]};
+      if constexpr (TABLE) return RowIn{i, 1.f, 0.f, 0.f, 0.f};
+      else if constexpr (DIST) return RowIn{a.seq_idx[bi], a.res_mask[bi], a.sc_ca[bi * 3], a.sc_ca[bi * 3 + 1], a.sc_ca[bi * 3 + 2]};
       else return RowIn{a.seq_idx[bi], a.res_mask[bi], 0.f, 0.f, 0.f};
     };
     auto row_ids = [&](const RowIn& r, int& rel, int& bin, float& msk) {
       msk = r.mi * mj;
-      rel = b * a.n_rel + r.si - sj + a.rel_off;
-      if constexpr (DIST) {
-        const float dx = r.c0 - cj0, dy = r.c1 - cj1, dz = r.c2 - cj2;
-        bin = bin_of(sqrtf(dx * dx + dy * dy + dz * dz));
+      if constexpr (TABLE) {
+        rel = b * a.n_rel + r.si;
+        bin = valid ? j0 + li : nb;
       } else {
-        bin = 0;
+        rel = b * a.n_rel + r.si - sj + a.rel_off;
+        if constexpr (DIST) bin = bins.of_pair(r.c0, r.c1, r.c2, cj0, cj1, cj2);
+        else bin = 0;
       }
     };
     f32x4 RR[16], PJ[16], PI;
     auto request = [&](int i, int rel, const int it0, const int it1) {
-      if (it0 == 0) PI = *(const f32x4*)(a.pi + ((long)b * N + i) * ET2_CZ + 4 * li);
+      if (it0 == 0) PI = *(const f32x4*)(a.pi + ((long)b * N + (TABLE ? rep_i : i)) * ET2_CZ + 4 * li);
 #pragma unroll
       for (int it = it0; it < it1; ++it) {
         const int r = 2 * it + hi;
         const int rrel = __shfl(rel, r, 64);
         RR[it] = *(const f32x4*)(a.rtab + (long)rrel * ET2_CZ + 4 * li);
-        PJ[it] = *(const f32x4*)(pj_base + (r < nvalid ? r : nvalid - 1) * ET2_CZ);  // (the same 16 KB for every row of the walk: L2 hits)
+        PJ[it] = *(const f32x4*)(pj_base + (TABLE ? 0 : (r < nvalid ? r : nvalid - 1) * ET2_CZ));  // (the same 16 KB for every row of the walk: L2 hits)
       }
     };
     int rel, bin;
@@ -441,11 +520,17 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
       request(i_next, rel, 0, 0);  // the next row's Pi in flight under the epilogue (its R / Pj rows after it: register budget)
       __builtin_amdgcn_sched_barrier(0);
       const int rel_next = rel;
+      if constexpr (TABLE) {
+        const long trow = (long)b * tab.rps + ((long)cc * a.n_rel + i) * (nb + 1) + j0;  // first row of the tile
+        ee_ln_epilogue<false, true>(Y, vec + 2 * ET2_CZ, vec + 3 * ET2_CZ, msk_cur, li, hi, lane, stage, tab.z + trow * ET2_CZ, nvalid, nullptr,
+                                    valid, wbl, bbv, tab.bias + trow * 8, a.H, b, i, j0 + li, nt, tab.pz + trow * 32, (nvalid + 3) >> 2);
+      } else {
       const long prow = ((long)b * N + i) * N + j0;  // first pair of the tile
       ee_ln_epilogue<TRACE>(Y, vec + 2 * ET2_CZ, vec + 3 * ET2_CZ, msk_cur, li, hi, lane, stage, (half_t*)a.z_out + prow * ET2_CZ, nvalid,
                      TRACE ? a.trace + (prow + (valid ? li : 0)) * ET2_CZ : nullptr, valid, a.wb_img ? wbl : nullptr, bbv,
                      a.bias_out, a.H, b, i, j0 + li, nt,
                      a.pz_out ? a.pz_out + (((long)b * N + i) * ((N + 3) >> 2) + (j0 >> 2)) * 128 : nullptr, (nvalid + 3) >> 2);
+      }
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       request(i_next, rel_next, 0, 16);
@@ -490,6 +575,120 @@ int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st, int 
   const int cus = a.reserve_cus > 0 && a.reserve_cus < 248 ? (256 - a.reserve_cus) & ~7 : 256;  // (whole XCD rounds of 8)
   const int grid = cdiv(n_items, 8) < cus ? cdiv(n_items, 8) : cus;
   hipLaunchKernelGGL(kerns[kid], dim3(grid), dim3(EE2_THREADS), lds, st, a, (const char*)img, nt, wpg, rpw, n_items);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+
+// ---- the row table: its launch, and the spread of its records to the pairs
+int fd_edge_embed2_table_supported(const EdgeEmbedArgs& a) {
+  const bool dlds = a.num_bins <= EE2_MAXB_LDS && EE2_LDS_BASE + (a.num_bins + 1) * ET2_CZ * 4 <= EE2_LDS_MAX;
+  return a.num_bins >= 3 && dlds && a.H == 8 && a.N % 4 == 0 && (long)a.B * ee2_rows_per_sample(a.n_rel, a.num_bins) < (1L << 24);
+}
+int fd_edge_embed2_table(const EdgeEmbedArgs& a_, const void* img, hipStream_t st, int lo) {
+  EdgeEmbedArgs a = a_;
+  if (!fd_edge_embed2_table_supported(a) || !a.table || !a.fixed_mask || !a.wb_img || !a.wdz_img || !a.wdz_img_lo || !a.bdz || a.trace)
+    return FDIPT_EINVAL;
+  a.pz_out = (half_t*)a.table;  // (any non-null value: the set-up loads the down_z images; the records go to the table)
+  const int lds = EE2_LDS_BASE + (a.num_bins + 1) * ET2_CZ * 4;
+  typedef void (*kern_t)(EdgeEmbedArgs, const char*, int, int, int, int);
+  static const kern_t kerns[2] = {edge_embed2_kernel<true, true, false, false, true>, edge_embed2_kernel<true, true, false, true, true>};
+  static FdPerDevice attr_dev[2];
+  const int dev_ = fd_device(), kid = lo ? 1 : 0;
+  if (!attr_dev[kid].get(dev_)) {
+    if (hipFuncSetAttribute((const void*)kerns[kid], hipFuncAttributeMaxDynamicSharedMemorySize, EE2_LDS_MAX) != hipSuccess)
+      return FDIPT_ELAUNCH;
+    attr_dev[kid].set(dev_, 1);
+  }
+  // one work item = (class pair, sample, bin tile of 32, range of rpw consecutive rel); a one-class batch (de novo sampling) has a
+  // quarter of the items live, and those should fill the ~2048 waves
+  const int nt = cdiv(a.num_bins + 1, 32), n_groups = a.B * nt, n_waves = 256 * 8;
+  int wpg = n_waves / n_groups < 1 ? 1 : n_waves / n_groups;
+  if (wpg > a.n_rel) wpg = a.n_rel;
+  const int rpw = cdiv(a.n_rel, wpg);
+  wpg = cdiv(a.n_rel, rpw);
+  const int n_items = 4 * n_groups * wpg;
+  const int cus = a.reserve_cus > 0 && a.reserve_cus < 248 ? (256 - a.reserve_cus) & ~7 : 256;
+  const int live = cdiv(n_groups * wpg, 8), grid = live < cus ? live : cus;
+  hipLaunchKernelGGL(kerns[kid], dim3(grid), dim3(EE2_THREADS), lds, st, a, (const char*)img, nt, wpg, rpw, n_items);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+
+// The spread: a wave takes SP_ROWS consecutive query rows against 32 keys, finds every pair's table row exactly as the pair kernel finds
+// its layer-1 rows (row_ids / Ee2Bins) and copies the row's records: the pair bias into the fragment order ipa_attn3 reads, pair_z into
+// the [row][j / 4][32 d][4 j] image, and (WZ) the z row itself.  a.row_idx, when set, receives the row of every pair.
+#define SP_THREADS 256
+#define SP_ROWS 4
+template <bool WZ>
+__global__ __launch_bounds__(SP_THREADS) void ee2_spread_kernel(EdgeEmbedArgs a, int nt, int wpg, int n_items) {
+  __shared__ float edg[64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hi = lane >> 5, li = lane & 31, N = a.N, nb = a.num_bins;
+  if (tid <= nb) edg[tid] = tid < nb ? a.edges[tid] : 1e8f;
+  __syncthreads();
+  const Ee2Bins bins(edg, nb);
+  const Ee2Table tab = ee2_table_of(a.table, a.B, a.n_rel, nb);
+  const long hstride = (long)nt * nt * 1024;  // floats per (sample, head)
+  const int sr = lane >> 4, sc16 = lane & 15;
+  for (int item = blockIdx.x * (SP_THREADS / 64) + wave; item < n_items; item += gridDim.x * (SP_THREADS / 64)) {
+    const int grp = item / wpg, part = item - grp * wpg;
+    const int b = grp / nt, jt = grp - b * nt, j0 = jt * 32;
+    const int i_first = part * SP_ROWS, i_end = (i_first + SP_ROWS < N) ? i_first + SP_ROWS : N;
+    const int nvalid = N - j0 < 32 ? N - j0 : 32;
+    const bool valid = li < nvalid;
+    const int j = valid ? j0 + li : N - 1;
+    const long bj = (long)b * N + j;
+    const int sj = a.seq_idx[bj], fj = a.fixed_mask[bj] != 0.f ? 1 : 0;
+    const float mj = a.res_mask[bj];
+    const float cj0 = a.sc_ca[bj * 3], cj1 = a.sc_ca[bj * 3 + 1], cj2 = a.sc_ca[bj * 3 + 2];
+    for (int i = i_first; i < i_end; ++i) {
+      const long bi = (long)b * N + i;
+      const int si = a.seq_idx[bi], fi = a.fixed_mask[bi] != 0.f ? 1 : 0;
+      const float msk = a.res_mask[bi] * mj;
+      const int rel = si - sj + a.rel_off;
+      const int bin = bins.of_pair(a.sc_ca[bi * 3], a.sc_ca[bi * 3 + 1], a.sc_ca[bi * 3 + 2], cj0, cj1, cj2);
+      const int row = b * tab.rps + (msk != 0.f ? ((2 * fi + fj) * a.n_rel + rel) * (nb + 1) + bin : tab.rps - 1);
+      if (a.row_idx && hi == 0 && valid) a.row_idx[bi * N + j] = row;
+      {  // pair bias: 32 lanes = 32 consecutive keys of one head (128 B rows), heads 4 hi .. 4 hi + 3
+        const f32x4 bv = *(const f32x4*)(tab.bias + (long)row * 8 + 4 * hi);
+        float* bo = a.bias_out + fd_bias_frag_off((long)b * 8 + 4 * hi, nt, i, j);
+        if (valid) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) bo[r * hstride] = bv[r];
+        }
+      }
+      {  // pair_z: lane (d = li, hi) writes the 4 keys of key group 2 g + hi
+        half_t* pz_tile = a.pz_out + (bi * (N >> 2) + (j0 >> 2)) * 128;
+        const unsigned short* tp = (const unsigned short*)tab.pz + li;
+        unsigned short v[16];
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[4 * g + q] = tp[(long)__shfl(row, 8 * g + 4 * hi + q, 64) * 32];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const u32x2 ow = {(unsigned)v[4 * g] | ((unsigned)v[4 * g + 1] << 16), (unsigned)v[4 * g + 2] | ((unsigned)v[4 * g + 3] << 16)};
+          if (8 * g + 4 * hi < nvalid) *(u32x2*)(pz_tile + ((2 * g + hi) * 32 + li) * 4) = ow;
+        }
+      }
+      if constexpr (WZ) {
+        half_t* z_tile = (half_t*)a.z_out + (bi * N + j0) * ET2_CZ;
+        u16x8 zr[8];
+#pragma unroll
+        for (int it = 0; it < 8; ++it) zr[it] = *(const u16x8*)(tab.z + (long)__shfl(row, 4 * it + sr, 64) * ET2_CZ + 8 * sc16);
+#pragma unroll
+        for (int it = 0; it < 8; ++it)
+          if (4 * it + sr < nvalid) *(u16x8*)(z_tile + (4 * it + sr) * ET2_CZ + 8 * sc16) = zr[it];
+      }
+    }
+  }
+}
+int fd_edge_embed2_spread(const EdgeEmbedArgs& a, hipStream_t st, int write_z) {
+  if (!fd_edge_embed2_table_supported(a) || !a.table || !a.fixed_mask || !a.bias_out || !a.pz_out || (write_z && !a.z_out)) return FDIPT_EINVAL;
+  const int nt = cdiv(a.N, 32), wpg = cdiv(a.N, SP_ROWS), n_items = a.B * nt * wpg;
+  const int grid = cdiv(n_items, SP_THREADS / 64);
+  if (write_z) hipLaunchKernelGGL(ee2_spread_kernel<true>, dim3(grid), dim3(SP_THREADS), 0, st, a, nt, wpg, n_items);
+  else hipLaunchKernelGGL(ee2_spread_kernel<false>, dim3(grid), dim3(SP_THREADS), 0, st, a, nt, wpg, n_items);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }

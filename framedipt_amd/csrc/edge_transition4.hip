@@ -285,6 +285,28 @@ __device__ __forceinline__ void e4_request_z(const ET2Args& a, const E4Tile& t, 
     fd_dma16(a.z_in + pair * E4_CZ + 8 * u, zst + r * 1024);
   }
 }
+// GZ (block 0 behind the edge embedder's row table, ET2Args.z_idx): a pair's z row is row z_idx[pair] of the table at z_in, nobody wrote
+// z itself.  The indices of a patch (8 rows x 4 ints = 8 x 16 B) come into the wave's 1 KB index area by one DMA, issued right behind
+// the z requests of the tile BEFORE (e4_request_idx), so that no dependent global load stands in front of these DMAs; the wave reads
+// them here (every lane its row's, one ds_read per DMA instruction)
+#define E4_IXOFF E4_LDS  // per-wave index areas [E4_WAVES][64 lanes x 16 B] (lane l holds patch row l & 7)
+#define E4_LDS_GZ (E4_LDS + E4_WAVES * 1024)
+__device__ __forceinline__ void e4_request_idx(const ET2Args& a, const E4Tile& t, int lane, unsigned ixo, int M) {
+  int row = 8 * t.rt + (lane & 7);
+  if (row > M - 1) row = M - 1;
+  fd_dma16(a.z_idx + ((long)row * a.N + 4 * t.jt), ixo);
+}
+__device__ __forceinline__ void e4_request_z_gather(const ET2Args& a, int lane, unsigned zst, unsigned ixo) {
+  int ix[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) ix[r] = *(const __attribute__((address_space(3))) int*)(unsigned long)(ixo + r * 16 + (lane >> 4) * 4);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int lrow = 4 * r + (lane >> 4);
+    const int u = (lane & 15) ^ (lrow & 15);
+    fd_dma16(a.z_in + (long)ix[r] * E4_CZ + 8 * u, zst + r * 1024);
+  }
+}
 
 // The LayerNorm epilogue, in slices (statistics, four 32-feature tiles, pair bias)
 struct E4Epi {
@@ -498,9 +520,9 @@ struct E4Flat {
   unsigned lds0, pa;
   int tid, wave;
 };
-template <int NCH = E4_NCHUNK>  // chunks of the stream (fp16x: E4X_STREAM_FR / E4_CFR)
+template <int NCH = E4_NCHUNK, bool GZ = false>  // chunks of the stream (fp16x: E4X_STREAM_FR / E4_CFR); GZ: + the index DMA behind the z requests
 __device__ __forceinline__ void e4_point(const E4Flat& F, int c) {
-  e4_vm_wait(e4_vm_younger(c));
+  e4_vm_wait(e4_vm_younger(c) + (GZ && c > E4_PT_Z && c <= E4_PT_Z + E4_NSLOT - 2 ? 1 : 0));
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
   const int cn = (c + E4_NSLOT - 1) % NCH;
@@ -515,7 +537,7 @@ __device__ __forceinline__ void e4_point(const E4Flat& F, int c) {
   } while (0)
 
 // LO (fp16x): the final layer adds W_lo h2 (the fp16x stream: et4x_build_stream_kernel)
-template <bool PZ, bool STZ = true, bool LO = false>
+template <bool PZ, bool STZ = true, bool LO = false, bool GZ = false>
 __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_flat_kernel(ET2Args a, int n_tiles, int n_wt) {
   constexpr int NCH = (LO ? E4X_STREAM_FR : E4_STREAM_FR) / E4_CFR;  // stream chunks
   constexpr int LFW = LO ? 8 : 4;                                     // final-layer fragments per k-step
@@ -540,6 +562,14 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
   const unsigned long long span0 = __builtin_amdgcn_s_memrealtime();
 #endif
   E4Tile tc = e4_tile_of(tile * E4_WAVES + wave, n_wt, N, NJ4);
+  if constexpr (GZ) {  // the first patch's indices, then (behind its z requests) those of the wave's second tile
+    const unsigned ixo = lds0 + E4_IXOFF + wave * 1024;
+    e4_request_idx(a, tc, lane0, ixo, M);
+    fd_dma_wait();
+    e4_request_z_gather(a, lane0, lds0 + E4_ZOFF + wave * 8192, ixo);
+    const int t1 = tile + gridDim.x < n_tiles ? tile + gridDim.x : tile;
+    e4_request_idx(a, e4_tile_of(t1 * E4_WAVES + wave, n_wt, N, NJ4), lane0, ixo, M);
+  } else
   e4_request_z(a, tc, lane0, lds0 + E4_ZOFF + wave * 8192, M);
 #pragma unroll
   for (int c = 0; c < E4_NSLOT - 1; ++c) e4_dma_chunk<E4_CHUNK>(stream + c * E4_CHUNK, lds0 + c * E4_CHUNK, tid0, wave);
@@ -661,9 +691,17 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
         const int t = u & 3;
         const int f = E4_L1_FR + E4_L2_FR + LFW * s + u;
         if (f % E4_CFR == E4_CFR / 2) {
-          e4_point<NCH>(F, f / E4_CFR);
+          e4_point<NCH, GZ>(F, f / E4_CFR);
           // point E4_PT_Z: the wave's z rows are free since the fourth hand-over of layer 2 — the next tile's are requested here, seven chunks
           // before the tile ends (always issued, the last tile re-requests its own: the counts of e4_vm_younger stay static)
+          if constexpr (GZ) {
+            if (f / E4_CFR == E4_PT_Z) {  // (the index area holds tn's rows since the previous tile; then the rows of the tile behind tn)
+              const unsigned ixo = lds0 + E4_IXOFF + wave * 1024;
+              e4_request_z_gather(a, lane_id(), lds0 + E4_ZOFF + wave * 8192, ixo);
+              const int t2 = has_next && ntile + gridDim.x < n_tiles ? ntile + gridDim.x : (has_next ? ntile : tile);
+              e4_request_idx(a, e4_tile_of(t2 * E4_WAVES + wave, n_wt, N, NJ4), lane_id(), ixo, M);
+            }
+          } else
           if (f / E4_CFR == E4_PT_Z) e4_request_z(a, tn, lane_id(), lds0 + E4_ZOFF + wave * 8192, M);
           if (f / E4_CFR == E4_PT_FL) {
             const unsigned fb = fold_ptr(tc, lane_id());
@@ -676,11 +714,11 @@ __global__ __launch_bounds__(E4_THREADS, 8 / E4_WAVES) void edge_transition4_fla
     // the unused chunk(s) and the down_z chunk: their stream points without products (the ring keeps turning)
     static_assert((E4_L1_FR + E4_L2_FR + 24 * LFW) / E4_CFR == NCH - (LO ? 4 : 2), "stream points behind the final layer");
     if constexpr (LO) {
-      e4_point<NCH>(F, NCH - 4);
-      e4_point<NCH>(F, NCH - 3);
+      e4_point<NCH, GZ>(F, NCH - 4);
+      e4_point<NCH, GZ>(F, NCH - 3);
     }
-    e4_point<NCH>(F, NCH - 2);
-    e4_point<NCH>(F, NCH - 1);
+    e4_point<NCH, GZ>(F, NCH - 2);
+    e4_point<NCH, GZ>(F, NCH - 1);
     {
       const hx8 SEL = e4_sel(lane, tc.ns);
 #pragma unroll
@@ -739,6 +777,16 @@ static int e4_launch(const ET2Args& a, hipStream_t st) {
   const int cus = a.reserve_cus > 0 && a.reserve_cus < n_cu - 8 ? (n_cu - a.reserve_cus) & ~7 : n_cu;
   const int slots = cus * (E4_LDS <= 81920 ? 2 : 1);
   const int grid = n_tiles < slots ? n_tiles : slots;
+  if (a.z_idx) {  // z rows gathered from the embedder's row table (block 0; both emissions, z' stored)
+    if (!a.pz_out || !a.wb_img || !a.bdz || !a.z_out || a.z_out == a.z_in) return FDIPT_EINVAL;
+    static FdPerDevice attr_gz;
+    if (!attr_gz.get(dev_)) {
+      if (hipFuncSetAttribute((const void*)edge_transition4_flat_kernel<true, true, LO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, E4_LDS_GZ) != hipSuccess)
+        return FDIPT_ELAUNCH;
+      attr_gz.set(dev_, 1);
+    }
+    hipLaunchKernelGGL((edge_transition4_flat_kernel<true, true, LO, true>), dim3(grid), dim3(E4_THREADS), E4_LDS_GZ, st, a, n_tiles, n_wt);
+  } else
   if (a.pz_out) {  // + pair_z of the next block (needs its bias emission: the zero unit / images share its set-up)
     if (!a.wb_img || !a.bdz) return FDIPT_EINVAL;  // (down_z hi / lo: the stream's last chunk, fd_et4_set_dz)
     if (!a.z_out) {  // (only next to both emissions and without a trace: checked by the caller's conditions, and here)

@@ -42,6 +42,10 @@ struct EdgeEmbedArgs {
   const void* wdz_img_lo = nullptr;
   const float* bdz = nullptr;
   half_t* pz_out = nullptr;
+  // optional (the row table: fd_edge_embed2_table / fd_edge_embed2_spread)
+  const float* fixed_mask = nullptr;  // [B,N]: a residue's class is fixed_mask != 0
+  void* table = nullptr;              // fd_ee2_table_bytes
+  int32_t* row_idx = nullptr;         // [B,N,N] table row of every pair (written by the spread when set)
 };
 
 struct AttnArgs {
@@ -155,6 +159,9 @@ struct ET2Args {
   const void* wdz_img_lo = nullptr;  // ... of Wdz - half(Wdz) (lo = 1).  edge_transition4 finds both in the last chunk of its weight stream (fd_et4_set_dz)
   const float* bdz = nullptr;        // [32]
   half_t* pz_out = nullptr;          // [B*N][N/4][32][4]
+  // optional (edge_transition4, block 0 behind the edge embedder's row table): z_in is the table's z rows [rows][128] and pair p reads
+  // row z_idx[p]; z_out must be set and is another buffer
+  const int32_t* z_idx = nullptr;    // [B,N,N]
 };
 // pair_z image: [flattened residue row b N + i][key group j / 4][channel d < 32][key j % 4] half precision; a 32x32x16 MFMA B fragment of
 // opair_pz_kernel is two 8 B pieces per lane (groups 4 s + 2 (lane >> 5), + 1 of k-step s), its producers write whole 256 B groups
@@ -181,6 +188,13 @@ int fd_edge_transition4_supported(int N);
 int fd_ee2_build_images(const float* w2, const float* w3, void* img, hipStream_t st, int lo = 0);
 size_t fd_ee2_image_bytes(int lo = 0);
 int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st, int lo = 0);
+// The row table of the embedder (models without aatype features): its output for a pair depends on (sample, fixed-mask bits of i and j,
+// rel, bin) only.  fd_edge_embed2_table evaluates every such row once (z row, pair bias, pair_z: a.table), fd_edge_embed2_spread copies
+// the records to the pairs (a.bias_out, a.pz_out and, write_z, a.z_out).  fd_edge_embed2_table_supported: scalars only (plan_forward)
+size_t fd_ee2_table_bytes(int B, int n_rel, int num_bins);
+int fd_edge_embed2_table_supported(const EdgeEmbedArgs& a);
+int fd_edge_embed2_table(const EdgeEmbedArgs& a, const void* img, hipStream_t st, int lo = 0);
+int fd_edge_embed2_spread(const EdgeEmbedArgs& a, hipStream_t st, int write_z);
 
 struct ProjArgs {
   int B, N, H, C, K, PT, Np;  // K = c_s, PT = point columns (3*H*Pq + 3*H*(Pq+Pv)), Np = keys padded to 32

@@ -143,6 +143,24 @@ static bool use_regpair(const FdiptDims* d) {
 }
 // fp16x: edge_transition4's weight stream with the final layer's lo fragments (fd_et4_build_stream lo = 1) in place of the plain one;
 // no edge_transition3 stream (fp16x refuses every plan that would run it)
+// The edge embedder's row table (edge_embed2.hip: fd_edge_embed2_table / fd_edge_embed2_spread).  Without aatype features the embedder's
+// output for a pair is a function of (sample, fixed-mask bits of i and j, rel, bin): n_rel (num_bins + 1) rows per class pair and sample
+// against N^2 pairs.  The static part of the predicate (dims, flags, shape) also decides the workspace region, which holds the four class
+// pairs of a table of up to ee_table_max_rel(N) relative positions (a single chain has 2 N - 1; chain breaks add their gaps).
+// EE_TABLE_CAP: bytes of one class pair's rows of the batch — the spread gathers them, so they should stay cache-resident next to the
+// streams it writes (c4: 39 MB, measured)
+#define EE_TABLE_ROW_BYTES 352
+#define EE_TABLE_CAP (64L << 20)
+static int ee_table_max_rel(int N) { return 5 * N / 2; }
+static bool ee_table_rows_ok(int B, int N, int n_rel, int num_bins) {
+  const long rows = (long)n_rel * (num_bins + 1);
+  return rows <= (long)N * N / 2 && B * rows * EE_TABLE_ROW_BYTES <= EE_TABLE_CAP;
+}
+static bool ee_table_static(const FdiptDims* d, int B, int N) {
+  const unsigned off = FDIPT_KF_UNFOLDED | FDIPT_KF_PASS_Z | FDIPT_KF_ET3 | FDIPT_KF_GENERIC_ATTN;
+  if (!half_mode(d) || d->c_z != 128 || d->c_s != 256 || (d->kernel_flags & (FDIPT_KF_GENERIC_PAIR | off))) return false;
+  return !d->use_aatype && d->num_bins > 0 && d->num_blocks >= 3 && N % 4 == 0 && ee_table_rows_ok(B, N, 2 * N - 1, d->num_bins);
+}
 static bool et4x_stream(const FdiptDims* d) { return use_regpair(d) && d->precision == FDIPT_PREC_F16X; }
 // fp16x: the edge embedder's layer-2/3 images followed by their lo images (fd_ee2_build_images lo = 1) in place of the plain ones
 static bool ee2x_images(const FdiptDims* d) { return use_regpair(d) && d->precision == FDIPT_PREC_F16X; }
@@ -585,7 +603,7 @@ int fdipt_sample_setup(const FdiptDims* d, const float* P, const void* derived, 
 // ------------------------------------------------------------------ workspace
 struct WS {
   size_t node_feat, pte, pi, pj, h_a, h_b, node0, node, z, quat, trans, dmask, rot, proj, qp, kp, vp, bias, probs, feats,
-      ipa_out, tf_in, qkv, att, x_a, x_b, ff, e, upd, psi_un, a1, af, qb, kb, vt, pts, seqimg, ipa_parts, e_bf, vpt, r4, a1img, b1img, skip_all, vt_lo, kpf, pz, total;
+      ipa_out, tf_in, qkv, att, x_a, x_b, ff, e, upd, psi_un, a1, af, qb, kb, vt, pts, seqimg, ipa_parts, e_bf, vpt, r4, a1img, b1img, skip_all, vt_lo, kpf, pz, ee_tab, ee_idx, total;
 };
 static void build_ws(const FdiptDims* d, const Inventory& iv, const DLayout& L, int B, int N, WS& w) {
   size_t o = 0;
@@ -627,6 +645,8 @@ static void build_ws(const FdiptDims* d, const Inventory& iv, const DLayout& L, 
   w.b1img = take(fd_et4_b_image_bytes(B, N));
   w.kpf = take((size_t)B * H * ((((size_t)N + 31) / 32)) * FD_KPF_FRAGS * 1024);  // key-point fragment image (attention3 point logits)
   w.pz = take(use_regpair(d) ? fd_pz_bytes(B, N) : 0);  // pair_z image of the current block (round 6: written by the producer of z)
+  w.ee_tab = take(ee_table_static(d, B, N) ? fd_ee2_table_bytes(B, ee_table_max_rel(N), d->num_bins) : 0);  // the edge embedder's row table
+  w.ee_idx = take(ee_table_static(d, B, N) ? NN * 4 : 0);  // ... and the table row of every pair (block 0's EdgeTransition gathers its z rows)
   w.total = o;
 }
 
@@ -676,6 +696,7 @@ struct ForwardPlan {
   OutProj outproj;
   int slices;   // split-K slices of the output projection
   bool feats_fused, ee_bias, et_bias, pz;
+  bool ee_table;                       // the edge embedder as row table + spread (ee_table_static and the call's n_rel; not with trace_edge)
   bool stream;                         // FDIPT_KF_STREAM_ATTN in the half-precision mode, N <= 2048: the key-streaming attention kernels
   bool a3, probs_h16;                  // IPA path: attention3, and the MFMA o_pair fed with bf16 attention weights
   bool vpt, proj2, merged, proj_pts, vt_lo, init_fused;
@@ -693,7 +714,8 @@ struct ForwardPlan {
 };
 static const char kImage = 0;  // stands for an operand image in the probe arguments below (the predicates test only that it is set)
 
-static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const DLayout& L, int B, int N, int op) {
+static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const DLayout& L, int B, int N, int op, int n_rel, bool trace_edge,
+                                bool pair_embed) {
   const unsigned f = (unsigned)d->kernel_flags;
   const bool generic_attn = f & FDIPT_KF_GENERIC_ATTN, unfolded = f & FDIPT_KF_UNFOLDED;
   const int cs = d->c_s, cz = d->c_z, H = d->no_heads, C = d->c_hidden, Pq = d->no_qk_points, Pv = d->no_v_points;
@@ -758,6 +780,15 @@ static ForwardPlan plan_forward(const FdiptDims* d, const Inventory& iv, const D
   // instead of streaming the 128 channels of z once more per block (opair_pz_kernel).  FDIPT_KF_UNFOLDED / FDIPT_KF_PASS_Z keep the pass
   // over z.  The consumer: the IPA path that reads probs_h16.
   p.pz = op == OP_ALL && p.probs_h16 && p.et == ET_ET4 && bias_rule && !(f & FDIPT_KF_PASS_Z);
+  // The embedder's distinct rows once, then spread (FdiptForwardArgs.pair_embed: every pair evaluated).  Whole forwards on the edge_embed2 /
+  // edge_transition4 path with both emissions; a trace wants the fp32 rows of the pair kernel.  Decided from the shape and the call's
+  // n_rel (set-up data): the launches of a step do not depend on the step's inputs
+  {
+    EdgeEmbedArgs ep = {};
+    ep.B = B; ep.N = N; ep.n_rel = n_rel; ep.num_bins = d->num_bins; ep.H = H;
+    p.ee_table = ee_table_static(d, B, N) && op == OP_ALL && p.ee_bias && p.pz && !trace_edge && !pair_embed && n_rel > 0 && n_rel <= ee_table_max_rel(N) &&
+                 ee_table_rows_ok(B, N, n_rel, d->num_bins) && fd_edge_embed2_table_supported(ep);
+  }
   // IPA projection (attention3 path): fused projection written directly as attention operand images (Qb, Kb, Vt) + raw point columns
   p.vpt = p.a3 && Pv == 12;
   ProjArgs pj = {};
@@ -939,7 +970,12 @@ struct Fwd {
     if (p.pz) {
       ea.wdz_img = D + L.blk[0].wdz_imgp; ea.wdz_img_lo = D + L.blk[0].wdz_imgp_lo; ea.bdz = P + iv.blk[0].dz.b; ea.pz_out = (half_t*)(W + w.pz);
     }
-    if (p.regpair) RC(fd_edge_embed2(ea, D + (p.x ? L.ee2x : L.ee2), st, p.x));
+    if (p.ee_table) {  // the distinct rows once, then their records to the pairs
+      // z0 itself is never written: its only reader, block 0's EdgeTransition, gathers the rows from the table (edge_transition_stage)
+      ea.fixed_mask = a->fixed_mask; ea.table = W + w.ee_tab; ea.row_idx = (int32_t*)(W + w.ee_idx);
+      RC(fd_edge_embed2_table(ea, D + (p.x ? L.ee2x : L.ee2), st, p.x));
+      RC(fd_edge_embed2_spread(ea, st, 0));
+    } else if (p.regpair) RC(fd_edge_embed2(ea, D + (p.x ? L.ee2x : L.ee2), st, p.x));
     else RC(fd_edge_embed(op_precision(d), cz, ea, st));
     return FDIPT_OK;
   }
@@ -1230,6 +1266,9 @@ struct Fwd {
         if (b + 1 == d->num_blocks - 1 && !tr_ptr) t2.z_out = nullptr;
       }
       t2.clock = a->clock_out;
+      if (p.ee_table && b == 0) {  // z0 lives in the embedder's row table only (its z rows lead the table)
+        t2.z_in = (const half_t*)(W + w.ee_tab); t2.z_idx = (const int32_t*)(W + w.ee_idx);
+      }
       if (p.et == ET_ET4) RC(fd_edge_transition4(t2, st, p.x));
       else RC(fd_edge_transition3(t2, st));
     } else {
@@ -1298,7 +1337,7 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
   build_ws(d, iv, L, B, N, w);
   if (workspace_bytes < w.total) return FDIPT_ESIZE;
   if ((long)B * N * N > 2000000000L / 1) return FDIPT_ESIZE;
-  const ForwardPlan p = plan_forward(d, iv, L, B, N, op.kind);
+  const ForwardPlan p = plan_forward(d, iv, L, B, N, op.kind, a->n_rel, a->trace_edge != nullptr, a->pair_embed != 0);
   if (p.refused) return FDIPT_EINVAL;
   const Fwd f = {d, iv, L, w, p, P, (const char*)derived, (char*)workspace, setup, a, (hipStream_t)stream, B, N, R, (N + 31) / 32 * 32, (size_t)R * N};
   if (a->trace_inner && (p.fused_node || p.outproj != OUT_GEMM)) return FDIPT_EINVAL;  // fused node path: the tensors never exist
@@ -1361,6 +1400,16 @@ static int forward_impl(const FdiptDims* d, const float* P, const void* derived,
 }
 
 extern "C" {
+
+int64_t fdipt_embed_table_rows(const FdiptDims* d, int B, int N, int n_rel) {
+  if (!dims_ok(d) || B <= 0 || N <= 0 || n_rel <= 0) return 0;
+  Inventory iv;
+  DLayout L;
+  build_inventory(d, iv);
+  blob_walk(d, iv, L);
+  const ForwardPlan p = plan_forward(d, iv, L, B, N, OP_ALL, n_rel, false, false);
+  return p.ee_table && !p.refused ? (int64_t)n_rel * (d->num_bins + 1) : 0;
+}
 
 int fdipt_score_forward(const FdiptDims* d, const float* P, const void* derived, const void* setup,
                         const FdiptForwardArgs* a, void* workspace, size_t workspace_bytes, fdipt_stream_t stream) {

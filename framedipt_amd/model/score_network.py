@@ -85,6 +85,7 @@ class BatchState:
         self.omega_edges = None
         self.clock_out = None  # optional int64[3] device tensor: shader-clock probe of the EdgeTransition kernels (FdiptForwardArgs.clock_out)
         self.reserve_cus = 0  # CUs the persistent pair kernels leave to concurrent sub-batch streams (inference.StreamedLoops)
+        self.pair_embed = 0  # 1: the edge embedder evaluates every pair instead of its row table (FdiptForwardArgs.pair_embed; parity tests)
         self.t_emb_eps = torch.as_tensor(embedding.get_timestep_embedding(np.array([1e-5], dtype=np.float32), E)[0],
                                          device=dev)
 
@@ -140,6 +141,7 @@ class BatchState:
         if self.ev_start is not None:
             a.ev_start, a.ev_stop = self.ev_start, self.ev_stop
         a.reserve_cus = self.reserve_cus
+        a.pair_embed = self.pair_embed
         a.step_cursor = _lib.ptr(step_cursor)
         if step_cursor is not None:
             a.frame_rows, a.state_ring = _lib.ptr(frame_rows), int(bool(state_ring))

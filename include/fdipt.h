@@ -174,6 +174,11 @@ typedef struct FdiptForwardArgs {
    * on all CUs but `reserve_cus` of them, so that the latency-bound node-path launches of another stream keep finding free
    * CUs while they run.  0 = use every CU (single stream). */
   int32_t reserve_cus;
+  /* optional: 1 = the edge embedder evaluates every pair (edge_embed2_kernel) where the default (0) evaluates the distinct
+   * (class_i, class_j, rel, bin) rows once and spreads them (fdipt_embed_table_rows says where that is).  Same results; a switch for
+   * parity tests, like FdiptDims.kernel_flags, kept per call because it touches no derived image.  (It sits in what was padding
+   * behind reserve_cus: no other member moves.) */
+  int32_t pair_embed;
   /* optional profiling: device buffer of 3 x uint64 (caller-owned, zeroed by the caller).  Thread 0 of every EdgeTransition
    * block adds its shader-clock cycles (s_memtime), its 100 MHz ticks (s_memrealtime) and 1 to [0], [1], [2]: the clock the
    * kernel's blocks actually ran at = [0] / [1] / 10 GHz (bench.py: roofline.clock_ghz).  NULL (the default): the kernels
@@ -203,6 +208,12 @@ typedef struct FdiptForwardArgs {
 } FdiptForwardArgs;
 
 size_t fdipt_forward_workspace_bytes(const FdiptDims* dims, int B, int N);
+/* Rows per sample and class pair of the edge embedder's row table, n_rel * (num_bins + 1), where a whole forward of this shape and
+ * n_rel (FdiptForwardArgs.n_rel) takes the table path when no pair trace is requested; 0 where it evaluates every pair: fp32, models
+ * with aatype features or without a distogram, the kernel flags that swap out the pair kernels or their emissions, N % 4 != 0,
+ * n_rel > 5 N / 2, rows > N * N / 2, or more than 64 MB of rows (352 B each) in the batch.  On that path fixed_mask and res_mask must
+ * hold 0 or 1. */
+int64_t fdipt_embed_table_rows(const FdiptDims* dims, int B, int N, int n_rel);
 int fdipt_score_forward(const FdiptDims* dims, const float* params_f32, const void* derived, const void* setup,
                         const FdiptForwardArgs* args, void* workspace, size_t workspace_bytes, fdipt_stream_t stream);
 
