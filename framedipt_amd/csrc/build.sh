@@ -17,7 +17,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-
 pids=()
 T0=$SECONDS
 NCOMP=0
-for f in gemm ipa_proj2 pair_mlp edge_embed2 edge_transition3 edge_transition4 attention attention3 pair_bias attention_seq chain rowblock frames select evaluate violations dssp sasa tmscore tmalign model; do
+for f in gemm ipa_proj2 pair_mlp edge_embed2 edge_transition3 edge_transition4 attention attention3 pair_bias attention_seq chain rowblock frames select evaluate violations dssp sasa tmscore tmalign mpnn model; do
   if [ ! -f "$BUILD/$f.o" ] || [ "$HERE/$f.hip" -nt "$BUILD/$f.o" ] || [ "$HERE/common.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/kernels.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/philox.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/horn.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/tmsearch.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/../../include/fdipt.h" -nt "$BUILD/$f.o" ]; then
     $HIPCC $FLAGS -c "$HERE/$f.hip" -o "$BUILD/$f.o" &
     pids+=($!)
@@ -25,6 +25,6 @@ for f in gemm ipa_proj2 pair_mlp edge_embed2 edge_transition3 edge_transition4 a
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIBNAME" "$BUILD"/{gemm,ipa_proj2,pair_mlp,edge_embed2,edge_transition3,edge_transition4,attention,attention3,pair_bias,attention_seq,chain,rowblock,frames,select,evaluate,violations,dssp,sasa,tmscore,tmalign,model}.o
-echo "compiled $NCOMP of 21 units for gfx950 in $((SECONDS - T0)) s: $(cd "$BUILD" && ls *.o | tr '\n' ' ')"
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIBNAME" "$BUILD"/{gemm,ipa_proj2,pair_mlp,edge_embed2,edge_transition3,edge_transition4,attention,attention3,pair_bias,attention_seq,chain,rowblock,frames,select,evaluate,violations,dssp,sasa,tmscore,tmalign,mpnn,model}.o
+echo "compiled $NCOMP of 22 units for gfx950 in $((SECONDS - T0)) s: $(cd "$BUILD" && ls *.o | tr '\n' ' ')"
 echo "built $OUT/$LIBNAME"

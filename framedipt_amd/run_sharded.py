@@ -564,6 +564,49 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
     return write_tm_align_table(out_dir, structures, skipped)
 
 
+def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, seq_per_sample: int = 8, weights=None, temperature: float = 0.1,
+               seed: int = 38, max_batch: int = 16):
+    """Rank 0, after the gather (``--design``; framedipt_amd/inverse_folding.py): ``seq_per_sample`` ProteinMPNN sequences per sample at the
+    reference's settings (``--sampling_temp 0.1 --seed 38``, X omitted), what experiments/inference.py:run_protein_mpnn starts a subprocess
+    for.  De novo runs design every row; inpainting runs design the diffused rows with the context fixed to its true residue types.
+    Samples of one length share a call.  ``weights``: a checkpoint in the reference's layout, or None for SYNTHETIC parameters (stated in
+    the output: such sequences exercise the path and mean nothing).  Writes ``seqs/<sample>.fa`` in the reference's FASTA layout and
+    ``design.json``.  Returns the summary written."""
+    from . import inverse_folding
+    model = inverse_folding.ProteinMPNN()
+    model = model.load_checkpoint(weights) if weights else model.load_synthetic(0)
+    os.makedirs(os.path.join(out_dir, "seqs"), exist_ok=True)
+    by_length = {}
+    for r in records:
+        by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+    samples = {}
+    for length, rs in by_length.items():
+        for start in range(0, len(rs), max_batch):
+            chunk = rs[start:start + max_batch]
+            items = [gathered[r["item"]] for r in chunk]
+            rows = lambda k, default: np.stack([default if it.get(k) is None else it[k] for it in items])  # noqa: E731
+            res = model.design(np.stack([it["prot"] for it in items]).astype(np.float32), num_seq=seq_per_sample, temperature=temperature, seed=seed,
+                               res_mask=rows("res_mask", np.ones(length, np.float32)),
+                               chain_mask=np.stack([it["diffused"] for it in items]).astype(np.float32) if inpainting else None,
+                               aatype=np.clip(rows("aatype", np.full(length, 20)), 0, 20) if inpainting else None,
+                               residue_index=rows("residue_index", np.arange(length)), chain_idx=rows("chain_idx", np.ones(length)))
+            for b, r in enumerate(chunk):
+                stem = os.path.splitext(r["file"])[0].replace(os.sep, "_")
+                fasta = os.path.join("seqs", stem + ".fa")
+                with open(os.path.join(out_dir, fasta), "w") as f:
+                    f.write(inverse_folding.fasta_records(res, b, stem, model_name=os.path.basename(str(weights)) if weights else "synthetic"))
+                samples[stem] = {"item": r["item"], "name": r["name"], "sample_i": r["sample_i"], "n_res": length,
+                                 "designed_rows": int((res["chain_mask"][b] * res["res_mask"][b]).sum()), "sequences": res["sequences"][b],
+                                 "score": [float(v) for v in res["score"][b]], "global_score": [float(v) for v in res["global_score"][b]],
+                                 "seq_recovery": [None if np.isnan(v) else float(v) for v in res["seq_recovery"][b]], "status": int(res["status"][b]),
+                                 "fasta": fasta}
+    summary = {"weights": model.source, "synthetic": not weights, "k_neighbors": model.k_neighbors, "temperature": temperature, "seed": seed,
+               "seq_per_sample": seq_per_sample, "omit": "X", "samples": samples}
+    with open(os.path.join(out_dir, "design.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    return summary
+
+
 def reference_layout_writer(out_dir: str, net, final_only: bool):
     """``write_item`` for inpainting runs: what ``Inference.run_conditional_sampling`` leaves on disk per sample
     (experiments/inference.py:250-389): ``<pdb>_length_<L>/`` with the ground-truth structure ``<pdb>_1.pdb`` (b-factor 100 = diffused) and
@@ -679,6 +722,12 @@ def main():
                     "a TM-align style search, this project's own contract; no parity with tmtools is claimed).  De novo runs: all-against-all per sample "
                     "length, the larger of the searched and the fixed score: pairwise_tm_score_aligned_length_<L>.npy, diversity_aligned.json, "
                     "diversity_aligned.csv.  Inpainting runs: the aligned matrix per structure: tm_align.json")
+    ap.add_argument("--design", action="store_true", help="after the run, rank 0 designs sequences for every sample on its GPU (framedipt_amd/inverse_folding.py: "
+                    "ProteinMPNN at T = 0.1, seed 38, X omitted, as the reference's run_protein_mpnn): seqs/<sample>.fa and design.json.  De novo runs design "
+                    "every row, inpainting runs the diffused rows with the context fixed")
+    ap.add_argument("--seq-per-sample", type=int, default=8, help="--design: sequences per sample (the reference's inference.samples.seq_per_sample)")
+    ap.add_argument("--mpnn-weights", default=None, help="--design: a ProteinMPNN checkpoint (.pt with model_state_dict, num_edges, noise_level); default: "
+                    "SYNTHETIC parameters, stated as such in the output")
     ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score, --tm-align: the TM-score threshold of the clusters (reference default)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
@@ -773,7 +822,7 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design else None
     ground_truth = None
     if (a.evaluate or a.sasa or a.tm_score) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
@@ -786,7 +835,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -832,6 +881,11 @@ def main():
             what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_align.json" if inp else \
                 f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity_aligned.json, diversity_aligned.csv, pairwise_tm_score_aligned_length_<L>.npy"
             print(f"structural alignments of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
+        if a.design:
+            t1 = time.perf_counter()
+            done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights)
+            print(f"{a.seq_per_sample} sequence(s) for each of {len(done['samples'])} sample(s) with {'SYNTHETIC ProteinMPNN parameters' if done['synthetic'] else done['weights']} "
+                  f"in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/seqs/<sample>.fa, design.json", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

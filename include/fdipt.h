@@ -704,6 +704,62 @@ size_t fdipt_sample_tm_align_workspace(int S, int N_a, int N_b, int P);
  * FDIPT_TMA_MAX_ROWS. */
 int fdipt_sample_tm_align(const FdiptTmAlignArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- inverse folding (opt-in) */
+/* The vanilla full-backbone ProteinMPNN (ProteinMPNN/protein_mpnn_utils.py: ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward
+ * and .sample), inference only, float32 throughout; the contract is DESIGN.md section 7.10.  Letters are in the MODEL's alphabet
+ * ACDEFGHIKLMNPQRSTVWYX (0 .. 20).  Two entries share the features and the encoder: fdipt_mpnn_score gives the teacher-forced
+ * log-probabilities of forward(..., use_input_decoding_order=True) for M (sequence, decoding order) pairs per backbone,
+ * fdipt_mpnn_design runs the autoregressive loop of sample for M sequences per backbone from caller-supplied uniforms.
+ *
+ * The weight image is ONE float32 array, every matrix stored TRANSPOSED ([in][out], so that a wave reads consecutive outputs), in this
+ * order (reference parameter name -> floats); fdipt_mpnn_weights_floats is its length, 1 660 485 for every K:
+ *   features.embeddings.linear.weight^T [66][16], .bias [16]
+ *   features.edge_embedding.weight^T [416][128]; features.norm_edges.weight [128], .bias [128]
+ *   W_e.weight^T [128][128], W_e.bias [128]; W_s.weight [21][128] (as stored: a row per letter)
+ *   encoder_layers.l, l = 0 .. 2:  W1^T [384][128], b [128]; W2^T [128][128], b; W3^T [128][128], b; norm1 weight, bias [128];
+ *       dense.W_in^T [128][512], b [512]; dense.W_out^T [512][128], b [128]; norm2 weight, bias;
+ *       W11^T [384][128], b; W12^T [128][128], b; W13^T [128][128], b; norm3 weight, bias
+ *   decoder_layers.l, l = 0 .. 2:  W1^T [512][128], b; W2^T, b; W3^T, b; norm1; dense.W_in^T, b; dense.W_out^T, b; norm2
+ *   W_out.weight^T [128][21], W_out.bias [21] */
+#define FDIPT_MPNN_MAX_ROWS 2048      /* N beyond: FDIPT_ESIZE                                                                       */
+#define FDIPT_MPNN_MAX_SEQ 64         /* M beyond: FDIPT_ESIZE                                                                       */
+#define FDIPT_MPNN_MAX_NEIGHBORS 64   /* k_neighbors outside 1 .. 64: FDIPT_EINVAL                                                   */
+#define FDIPT_MPNN_MASKED_NEIGHBOR 1  /* status: a row with res_mask set has a neighbour without; no parity with the reference there */
+typedef struct FdiptMpnnDims {
+  int32_t hidden, enc_layers, dec_layers, vocab; /* 128, 3, 3, 21: anything else is FDIPT_EINVAL                                    */
+  int32_t k_neighbors;                /* K, the checkpoint's num_edges; a row takes K_eff = min(K, N) neighbours                     */
+} FdiptMpnnDims;
+/* floats of the weight image; FDIPT_EINVAL for dims the kernels are not built for */
+int64_t fdipt_mpnn_weights_floats(const FdiptMpnnDims* dims);
+typedef struct FdiptMpnnArgs {
+  int32_t B, N, M, atoms;             /* backbones, rows, sequences per backbone, atoms per row of prot: 37 or 5 (N, CA, C, CB, O)   */
+  const float* weights;               /* f32 [fdipt_mpnn_weights_floats]                                                             */
+  const float* prot;                  /* [B,N,atoms,3] f32: N, CA, C at 0, 1, 2 and O at 4 in both layouts; CB is rebuilt            */
+  const float* res_mask;              /* [B,N] f32                                                                                   */
+  const float* chain_mask;            /* [B,N] f32: 1 = designed, 0 = fixed (design only; score ignores it)                          */
+  const int32_t* residue_index;       /* [B,N] i32                                                                                   */
+  const int32_t* chain_idx;           /* [B,N] i32                                                                                   */
+  const int32_t* S;                   /* [B,M,N] i32: the sequence to score / the input letters fixed and masked rows keep           */
+  const int32_t* decoding_order;      /* [B,M,N] i32: a permutation of 0 .. N-1 per sequence, first decoded row first                */
+  const float* u;                     /* [B,M,N] f32 in [0,1), indexed by ROW (design only)                                          */
+  const float* omit;                  /* [21] f32, 1 = never drawn (design only)                                                     */
+  const float* bias;                  /* [21] f32 (design only)                                                                      */
+  float temperature;                  /* > 0 (design only)                                                                           */
+  /* outputs */
+  int32_t* E_idx;                     /* [B,N,K_eff] i32: the neighbours of a row, nearest first, ties to the lower column           */
+  float* log_probs;                   /* [B,M,N,21] f32 (score only); 0 in rows without res_mask                                     */
+  int32_t* S_out;                     /* [B,M,N] i32 (design only)                                                                   */
+  float* probs;                       /* [B,M,N,21] f32 (design only): chain_mask * res_mask * the row's sampling distribution       */
+  int32_t* status;                    /* [B] i32: FDIPT_MPNN_* bits                                                                  */
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptMpnnArgs;
+size_t fdipt_mpnn_workspace(const FdiptMpnnDims* dims, int B, int N, int M);
+/* FDIPT_EINVAL: a null pointer the entry reads or writes, unsupported dims, B, N or M < 1, atoms not 37 or 5, temperature <= 0
+ * (design).  FDIPT_ESIZE: N > FDIPT_MPNN_MAX_ROWS, M > FDIPT_MPNN_MAX_SEQ, workspace too small.  All before any launch. */
+int fdipt_mpnn_score(const FdiptMpnnDims* dims, const FdiptMpnnArgs* args, fdipt_stream_t stream);
+int fdipt_mpnn_design(const FdiptMpnnDims* dims, const FdiptMpnnArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- frame algebra (a8) ------- */
 /* openfold/utils/rigid_utils.py free functions and Rigid/Rotation methods, n independent items, f32. */
 int fdipt_quat_to_rot(int n, const float* quat, float* rot, fdipt_stream_t s);           /* :185 */
