@@ -12,9 +12,10 @@
 //   mpnn_enc_kernel<false> block per row: [h_V_i, h_E_ij, h_V_j] -> W1, W2, W3 (GELU), masked sum / 30, LN, FFN, LN, mask -> new h_V
 //   mpnn_enc_kernel<true>  block per row: the same gather on the new h_V -> W11, W12, W13, + h_E, LN -> h_E (in place: a row's own edges)
 //   mpnn_order_kernel      block per sequence: the decoding step of every row (the inverse of decoding_order)
-//   mpnn_score_kernel      block per (row, sequence, backbone), one launch per decoder layer
+//   mpnn_score_kernel      block per (row, sequence, backbone), one launch per decoder layer; args.unconditional: no neighbour decoded
 //   mpnn_design_kernel     ONE persistent block per (sequence, backbone) walks the rows in decoding order; its h_V stack lives in the
-//                          workspace and is touched by this block only, the letters live in LDS.  No block waits on another.
+//                          workspace and is touched by this block only, the letters live in LDS.  No block waits on another.  Tied
+//                          groups and the per-row controls of the sampling epilogue: DESIGN.md section 7.11.
 // Sums run in a fixed order (edge slot ascending, k ascending), so a row's bits do not depend on B or M.
 #include "common.hpp"
 
@@ -322,9 +323,11 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_enc_kernel(MpCtx x, int layer
 // ------------------------------------------------------------------------------------------------ decoder
 // One decoder layer of row i of sequence (b, m).  vi (LDS) holds h_V^layer_i on entry and h_V^(layer+1)_i on return.  A neighbour j
 // decoded before i contributes [h_E, W_s[letter_j], h_V^layer_j], any other [h_E, 0, h_V^enc_j].  letter(j) reads the sequence.
+// lettered[k] says whether the letter of a `before` neighbour is known: always, except for the earlier members of a tied group still
+// open, which give [h_E, 0, h_V^layer_j] (tied_sample writes a group's letter after its last member).
 template <class L>
 __device__ __forceinline__ void mp_dec_layer(const MpCtx& x, int layer, long b, long bm, int i, float* tile, float* vi, float* hid, const int* sel,
-                                             const int* before, int tid, L&& letter) {
+                                             const int* before, const int* lettered, int tid, L&& letter) {
   const FdiptMpnnArgs& a = x.a;
   const int N = a.N, K = x.K;
   const float* __restrict__ W = a.weights + mpw::DEC0 + layer * mpw::D_SIZE;
@@ -336,7 +339,7 @@ __device__ __forceinline__ void mp_dec_layer(const MpCtx& x, int layer, long b, 
   auto stage = [&](int ch) {
     mp_stage(tile, K, tid, [&](int k) -> const float* {
       const int j = sel[k];
-      return ch == 0 ? vi : ch == 1 ? hE + k * MP_H : ch == 2 ? (before[k] ? Ws + letter(j) * MP_H : nullptr) : (before[k] ? cur : enc) + (long)j * MP_H;
+      return ch == 0 ? vi : ch == 1 ? hE + k * MP_H : ch == 2 ? (lettered[k] ? Ws + letter(j) * MP_H : nullptr) : (before[k] ? cur : enc) + (long)j * MP_H;
     });
   };
   mp_message<4>(tile, K, W + mpw::D_W1, W + mpw::D_B1, W + mpw::D_W2, W + mpw::D_B2, W + mpw::D_W3, W + mpw::D_B3, tid, stage);
@@ -387,10 +390,10 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_score_kernel(MpCtx x, int lay
   if (tid < MP_H) vi[tid] = (layer == 0 ? x.hV[1] + bi * MP_H : x.stack + ((layer - 1) * BMN + bm * N + i) * MP_H)[tid];
   if (tid < MP_ROWS) {
     const int j = tid < K ? a.E_idx[bi * K + tid] : 0;
-    sel[tid] = j, before[tid] = tid < K && pos[j] < pos[i];
+    sel[tid] = j, before[tid] = !a.unconditional && tid < K && pos[j] < pos[i];  // unconditional: pos and S are never read
   }
   __syncthreads();
-  mp_dec_layer(x, layer, b, bm, i, tile, vi, hid, sel, before, tid, [&](int j) { return mp_letter(S[j]); });
+  mp_dec_layer(x, layer, b, bm, i, tile, vi, hid, sel, before, before, tid, [&](int j) { return mp_letter(S[j]); });
   if (layer != 2) return;
   mp_logits(a.weights, vi, lg, tid);
   if (tid == 0) {
@@ -402,61 +405,130 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_score_kernel(MpCtx x, int lay
   }
 }
 
+// Tied positions: consecutive steps whose rows carry the same tie_group id >= 0 are one group, steps t0 .. gend-1.
+// Each member runs the decoder (earlier members count as before, without a letter), the members' logits are summed with their weights
+// into acc[], and the sampling epilogue runs once, at the last member, whose controls and uniform it reads.  A group's extent comes from
+// a forward scan of the order at its first step, bounded by N, so no step waits for anything and a malformed order gives defined output.
 __global__ __launch_bounds__(FD_THREADS) void mpnn_design_kernel(MpCtx x) {
   __shared__ float tile[MP_ROWS * MP_LD];
-  __shared__ float vi[MP_H], hid[512 + FD_THREADS], lg[MP_V];
-  __shared__ int sel[MP_ROWS], before[MP_ROWS];
-  __shared__ unsigned char S[FDIPT_MPNN_MAX_ROWS];  // the sequence so far: written and read by this block only
+  __shared__ float vi[MP_H], hid[512 + FD_THREADS], lg[MP_V], acc[MP_V];
+  __shared__ int sel[MP_ROWS], before[MP_ROWS], lettered[MP_ROWS];
+  __shared__ unsigned char S[FDIPT_MPNN_MAX_ROWS];      // the sequence so far: written and read by this block only
+  __shared__ unsigned char known[FDIPT_MPNN_MAX_ROWS];  // the row's letter is assigned (rows without res_mask: from the start)
   const FdiptMpnnArgs& a = x.a;
   const int tid = threadIdx.x, N = a.N, K = x.K;
   const long b = blockIdx.y, bm = b * a.M + blockIdx.x;
   const long BMN = (long)a.B * a.M * N;
   const int* pos = x.pos + bm * N;
+  const int* order = a.decoding_order + bm * N;
   const float* __restrict__ W = a.weights;
-  for (int j = tid; j < N; j += FD_THREADS) S[j] = (unsigned char)mp_letter(a.S[bm * N + j]);
+  for (int j = tid; j < N; j += FD_THREADS) S[j] = (unsigned char)mp_letter(a.S[bm * N + j]), known[j] = a.res_mask[b * N + j] == 0.f;
   __syncthreads();
+  // the tie id of step s: -1 for an untied row and for a step that decodes nothing (past the end, out of range, named twice, no res_mask)
+  auto tie_at = [&](int s) -> int {
+    if (!a.tie_group || s >= N) return -1;
+    const int r = order[s];
+    if (r < 0 || r >= N || pos[r] != s || a.res_mask[b * N + r] == 0.f) return -1;
+    return a.tie_group[b * N + r];
+  };
+  int t0 = 0, gend = 0;  // the last group opened
   for (int t = 0; t < N; ++t) {  // the loop bound is N for every block; nothing here waits on another block
-    const int i = a.decoding_order[bm * N + t];
+    const int i = order[t];
     if (i < 0 || i >= N || pos[i] != t) continue;  // not a permutation: the row is never decoded and keeps its input letter
     const long bi = b * N + i;
-    float* pr = a.probs + (bm * N + i) * MP_V;
     if (a.res_mask[bi] == 0.f) {
       for (int l = 0; l < 3; ++l)
         if (tid < MP_H) x.stack[(l * BMN + bm * N + i) * MP_H + tid] = 0.f;
-      if (tid < MP_V) pr[tid] = 0.f;
+      if (tid < MP_V) a.probs[(bm * N + i) * MP_V + tid] = 0.f;
       continue;
+    }
+    const bool tied = tie_at(t) >= 0;
+    if (tied && t >= gend) {
+      const int g = tie_at(t);
+      t0 = t, gend = t + 1;
+      while (tie_at(gend) == g) ++gend;
+      if (tid < MP_V) acc[tid] = 0.f;  // (the threads that add to it)
     }
     if (tid < MP_H) vi[tid] = x.hV[1][bi * MP_H + tid];
     if (tid < MP_ROWS) {
       const int j = tid < K ? a.E_idx[bi * K + tid] : 0;
-      sel[tid] = j, before[tid] = tid < K && pos[j] < t;
+      sel[tid] = j, before[tid] = tid < K && pos[j] < t, lettered[tid] = before[tid] && known[j];
     }
     __syncthreads();
     for (int l = 0; l < 3; ++l) {
-      mp_dec_layer(x, l, b, bm, i, tile, vi, hid, sel, before, tid, [&](int j) { return (int)S[j]; });
+      mp_dec_layer(x, l, b, bm, i, tile, vi, hid, sel, before, lettered, tid, [&](int j) { return (int)S[j]; });
       __threadfence();  // the row of the stack is read back by later steps of this block
       __syncthreads();
     }
     mp_logits(W, vi, lg, tid);
+    if (tied) {
+      if (tid < MP_V) acc[tid] += a.tied_beta[bi] * (lg[tid] / a.temperature) / (float)(gend - t0);
+      __syncthreads();
+      if (t + 1 < gend) continue;  // the same for every thread: the group's letter comes with its last member
+    }
     if (tid == 0) {
-      const float T = a.temperature, cm = a.chain_mask[bi];
+      const float T = a.temperature;
       float z[MP_V], mx = -INFINITY, sum = 0.f;
-      for (int q = 0; q < MP_V; ++q) z[q] = lg[q] / T - a.omit[q] * 1e8f + a.bias[q] / T, mx = fmaxf(mx, z[q]);
+      if (tied) {
+        for (int q = 0; q < MP_V; ++q) z[q] = acc[q] - a.omit[q] * 1e8f + a.bias[q] / T;
+      } else {
+        for (int q = 0; q < MP_V; ++q) z[q] = lg[q] / T - a.omit[q] * 1e8f + a.bias[q] / T;
+      }
+      if (a.bias_by_res)
+        for (int q = 0; q < MP_V; ++q) z[q] += a.bias_by_res[bi * MP_V + q] / T;
+      for (int q = 0; q < MP_V; ++q) mx = fmaxf(mx, z[q]);
       for (int q = 0; q < MP_V; ++q) z[q] = expf(z[q] - mx), sum += z[q];
       float total = 0.f;
       for (int q = 0; q < MP_V; ++q) z[q] = z[q] / sum, total += z[q];
+      // the stages of the reference's flags, each only where its array is present
+      const bool staged = a.pssm_bias || a.pssm_log_odds_mask || a.omit_mask;
+      bool none = false;
+      if (a.pssm_bias) {
+        const float c = a.pssm_multi * a.pssm_coef[bi];
+        for (int q = 0; q < MP_V; ++q) z[q] = (1.f - c) * z[q] + c * a.pssm_bias[bi * MP_V + q];
+      }
+      if (a.pssm_log_odds_mask) {
+        float s = 0.f;
+        for (int q = 0; q < MP_V; ++q) z[q] = z[q] * a.pssm_log_odds_mask[bi * MP_V + q] + z[q] * 0.001f, s += z[q];
+        if (s > 0.f) {
+          for (int q = 0; q < MP_V; ++q) z[q] = z[q] / s;
+        } else {
+          none = true;
+        }
+      }
+      if (a.omit_mask) {
+        float s = 0.f;
+        for (int q = 0; q < MP_V; ++q) z[q] = z[q] * (1.f - a.omit_mask[bi * MP_V + q]), s += z[q];
+        if (s > 0.f) {
+          for (int q = 0; q < MP_V; ++q) z[q] = z[q] / s;
+        } else {
+          none = true;
+        }
+      }
+      if (staged) {
+        total = 0.f;
+        for (int q = 0; q < MP_V; ++q) total += z[q];
+      }
       // the first letter whose cumulative probability exceeds u * total; else the last letter with p > 0
       const float thr = a.u[bm * N + i] * total;
-      int pick = -1, last = 0;
+      int pick = -1, last = -1;
       float cum = 0.f;
       for (int q = 0; q < MP_V; ++q) {
         cum += z[q];
         if (z[q] > 0.f) last = q;
         if (pick < 0 && cum > thr) pick = q;
       }
-      if (pick < 0) pick = last;
-      if (cm != 0.f) S[i] = (unsigned char)pick;
-      for (int q = 0; q < MP_V; ++q) pr[q] = cm * z[q];
+      if (staged && last < 0) none = true;  // no letter left: the rows keep their input letters, probs 0
+      if (pick < 0) pick = max(last, 0);
+      if (none) atomicOr(a.status + b, FDIPT_MPNN_NO_LETTER);
+      for (int s = tied ? t0 : t; s <= t; ++s) {  // every member takes the letter and the distribution
+        const int r = s == t ? i : order[s];
+        const float cm = a.chain_mask[b * N + r];
+        float* pr = a.probs + (bm * N + r) * MP_V;
+        if (cm != 0.f && !none) S[r] = (unsigned char)pick;
+        known[r] = 1;
+        for (int q = 0; q < MP_V; ++q) pr[q] = none ? 0.f : cm * z[q];
+      }
     }
     __syncthreads();
   }
@@ -480,12 +552,15 @@ extern "C" size_t fdipt_mpnn_workspace(const FdiptMpnnDims* dims, int B, int N, 
 
 static int mp_prepare(const FdiptMpnnDims* dims, const FdiptMpnnArgs* a, bool design, MpCtx& x) {
   if (!a || !mp_dims_ok(dims) || a->B < 1 || a->N < 1 || a->M < 1 || (a->atoms != 37 && a->atoms != 5)) return FDIPT_EINVAL;
-  if (!a->weights || !a->prot || !a->res_mask || !a->residue_index || !a->chain_idx || !a->S || !a->decoding_order || !a->E_idx || !a->status)
-    return FDIPT_EINVAL;
+  if (!a->weights || !a->prot || !a->res_mask || !a->residue_index || !a->chain_idx || !a->E_idx || !a->status) return FDIPT_EINVAL;
+  if ((design || !a->unconditional) && (!a->S || !a->decoding_order)) return FDIPT_EINVAL;
   if (design ? (!a->chain_mask || !a->u || !a->omit || !a->bias || !a->S_out || !a->probs || !(a->temperature > 0.f)) : !a->log_probs) return FDIPT_EINVAL;
+  if (design && (((a->pssm_bias || a->pssm_log_odds_mask) && !a->pssm_coef) || (a->tie_group && !a->tied_beta))) return FDIPT_EINVAL;
   if (a->N > FDIPT_MPNN_MAX_ROWS || a->M > FDIPT_MPNN_MAX_SEQ || a->B > 65535) return FDIPT_ESIZE;  // (B is a grid's y / z extent)
   if (!a->workspace || a->workspace_bytes < fdipt_mpnn_workspace(dims, a->B, a->N, a->M)) return FDIPT_ESIZE;
   x.a = *a;
+  if (design) x.a.unconditional = 0;
+  else if (x.a.unconditional) x.a.decoding_order = nullptr, x.a.S = nullptr;
   x.K = dims->k_neighbors < a->N ? dims->k_neighbors : a->N;
   const size_t bn = (size_t)a->B * a->N;
   x.hE = (float*)a->workspace;
@@ -509,6 +584,7 @@ static int mp_encode(const MpCtx& x, hipStream_t s) {
     hipLaunchKernelGGL(mpnn_enc_kernel<true>, rows, dim3(FD_THREADS), 0, s, x, l, src ^ 1);
     FD_CHECK_LAUNCH();
   }
+  if (!x.a.decoding_order) return FDIPT_OK;  // the unconditional score: no order
   hipLaunchKernelGGL(mpnn_order_kernel, dim3((unsigned)(x.a.B * x.a.M)), dim3(FD_THREADS), 0, s, x);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;

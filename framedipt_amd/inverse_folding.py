@@ -3,8 +3,11 @@
 The reference's first step after sampling (experiments/inference.py:run_self_consistency -> run_protein_mpnn) is a subprocess of
 ProteinMPNN/protein_mpnn_run.py per sample directory.  Here the vanilla full-backbone model (ProteinMPNN/protein_mpnn_utils.py:
 ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward and .sample) runs on the device through ``fdipt_mpnn_score`` and
-``fdipt_mpnn_design`` (csrc/mpnn.hip, ABI in include/fdipt.h); DESIGN.md section 7.10 is the contract.  Inference only, float32;
-``ca_only``, tied positions, PSSM, ``omit_AA_mask`` and ``bias_by_res`` are not built.
+``fdipt_mpnn_design`` (csrc/mpnn.hip, ABI in include/fdipt.h); DESIGN.md section 7.10 is the contract.  Inference only, float32.
+Section 7.11 adds what the vendored ProteinMPNN offers beyond that subprocess: the per-row controls of ``sample`` (``bias_by_res``,
+``omit_AA_mask``, the two PSSM stages), tied positions (``tied_sample``; ``tied_positions_from_chains`` for homo-oligomers) and the two
+probability modes ``unconditional_probs`` and ``conditional_probs`` with ``native_scores``.  ``ca_only`` is not built, nor are tied
+groups with a masked or fixed member (``tie_groups`` refuses them).
 
 Two alphabets meet here.  ``S`` arrays, ``probs`` and ``log_probs`` are in the MODEL's alphabet ``ACDEFGHIKLMNPQRSTVWYX``, as in the
 reference; ``aatype`` arrays are in this project's restype order (``output.RESTYPES``, 20 = unknown).  ``aatype_to_mpnn`` and
@@ -23,7 +26,7 @@ from .output import RESTYPES
 ALPHABET = "ACDEFGHIKLMNPQRSTVWYX"
 VOCAB, HIDDEN, LAYERS = 21, 128, 3
 MAX_ROWS, MAX_SEQ, MAX_NEIGHBORS = _lib.MPNN_MAX_ROWS, _lib.MPNN_MAX_SEQ, _lib.MPNN_MAX_NEIGHBORS
-MASKED_NEIGHBOR = _lib.MPNN_MASKED_NEIGHBOR
+MASKED_NEIGHBOR, NO_LETTER = _lib.MPNN_MASKED_NEIGHBOR, _lib.MPNN_NO_LETTER
 _TO_MPNN = np.array([ALPHABET.index(c) for c in RESTYPES] + [20], dtype=np.int64)       # restype index -> model letter
 _TO_AATYPE = np.array([(RESTYPES + "X").index(c) for c in ALPHABET], dtype=np.int64)    # model letter -> restype index
 
@@ -156,6 +159,94 @@ def scores_of(log_probs, S, mask):
         return (-(lp * mask).sum(-1) / mask.sum(-1)).astype(np.float32)
 
 
+def native_scores(cond_log_probs, S, mask):
+    """The mean negative conditional log-probability of the letters ``S`` over the rows of ``mask`` (``scores_of`` on the output of
+    ``conditional_probs``): how well the backbone, with every other letter given, explains the letters of those rows."""
+    return scores_of(cond_log_probs, S, mask)
+
+
+def log_odds_mask(pssm_log_odds, pssm_threshold=0.0):
+    """``pssm_log_odds > pssm_threshold`` as float32 (protein_mpnn_run.py:309): the letters the log-odds stage keeps at full weight."""
+    return (np.asarray(pssm_log_odds, dtype=np.float32) > np.float32(pssm_threshold)).astype(np.float32)
+
+
+def _is_seq(v):
+    return isinstance(v, (list, tuple, np.ndarray))
+
+
+def tie_groups(tied_positions, b, n, res_mask, chain_mask):
+    """``tie_group`` [B,N] int32 (-1 = untied, else the group's index in its backbone's list) and the lists themselves, one per backbone.
+    ``tied_positions``: None, a list of groups (lists of rows) for all backbones, or one such list per backbone.  ValueError, naming the
+    row, for a member without res_mask or without chain_mask, a row in two groups, a group of one and an index out of range: the
+    reference's behaviour there is an accident and nothing is built for it."""
+    tie = np.full((b, n), -1, np.int32)
+    if tied_positions is None:
+        return tie, [[] for _ in range(b)]
+    tp = list(tied_positions)
+    if all(_is_seq(g) and all(_is_seq(e) for e in g) for g in tp) and (len(tp) == b or not tp):
+        per = [[list(g) for g in one] for one in tp] if tp else [[] for _ in range(b)]
+    elif all(_is_seq(g) and not any(_is_seq(e) for e in g) for g in tp):
+        per = [[list(g) for g in tp] for _ in range(b)]
+    else:
+        raise ValueError(f"tied_positions: a list of groups of rows, or one such list for each of the {b} backbones")
+    out = []
+    for i, groups in enumerate(per):
+        clean = []
+        for gi, g in enumerate(groups):
+            rows = []
+            for r in g:
+                if int(r) != r or not 0 <= int(r) < n:
+                    raise ValueError(f"tied_positions: backbone {i}, group {gi}: row {r} outside 0 .. {n - 1}")
+                r = int(r)
+                if tie[i, r] >= 0 or r in rows:
+                    raise ValueError(f"tied_positions: backbone {i}: row {r} is in two groups")
+                if res_mask[i, r] == 0:
+                    raise ValueError(f"tied_positions: backbone {i}, group {gi}: row {r} has no res_mask")
+                if chain_mask[i, r] == 0:
+                    raise ValueError(f"tied_positions: backbone {i}, group {gi}: row {r} is fixed (no chain_mask)")
+                rows.append(r)
+            if len(rows) < 2:
+                raise ValueError(f"tied_positions: backbone {i}, group {gi}: a group of one (row {rows[0] if rows else None})")
+            tie[i, rows] = gi
+            clean.append(rows)
+        out.append(clean)
+    return tie, out
+
+
+def flatten_decoding_order(order, groups):
+    """The reference's ``new_decoding_order`` (tied_sample) for one drawn order [N]: walk it; a row not yet emitted emits its whole group
+    in the group's listed order, an untied row emits itself."""
+    member = {r: g for g in groups for r in g}
+    seen, flat = set(), []
+    for r in (int(v) for v in order):
+        if r in seen:
+            continue
+        rows = member.get(r, [r])
+        flat.extend(rows)
+        seen.update(rows)
+    return np.asarray(flat, dtype=np.int64)
+
+
+def tied_positions_from_chains(chain_idx, res_mask=None):
+    """The ties of a homo-oligomer: row r of every chain is one group (protein_mpnn_run.py's ``--homooligomer``).  chain_idx [N] or
+    [B,N]; chains are the runs of rows with res_mask that share a chain_idx, in order of first appearance, and must have equal lengths.
+    Returns one list of groups per backbone (for a 1-D chain_idx: the list of groups)."""
+    ch = np.asarray(chain_idx)
+    single = ch.ndim == 1
+    ch = ch[None] if single else ch
+    mask = np.ones(ch.shape, bool) if res_mask is None else np.asarray(res_mask).reshape(ch.shape) != 0
+    out = []
+    for i in range(ch.shape[0]):
+        chains = OrderedDict()
+        for r in np.flatnonzero(mask[i]):
+            chains.setdefault(int(ch[i, r]), []).append(int(r))
+        lengths = {len(v) for v in chains.values()}
+        if len(lengths) > 1:
+            raise ValueError(f"tied_positions_from_chains: backbone {i}: chains of lengths {sorted(len(v) for v in chains.values())}")
+        out.append([list(g) for g in zip(*chains.values())] if len(chains) > 1 else [])
+    return out[0] if single else out
+
+
 def _fmt(x):
     return np.format_float_positional(np.float32(x), unique=False, precision=4)
 
@@ -269,12 +360,27 @@ class ProteinMPNN:
         return np.ascontiguousarray(v, dtype=dtype)
 
     @staticmethod
+    def _per_row(v, b, n, width, what):
+        """An optional per-row input as float32 [B,N] (width None) or [B,N,width]; one backbone's array serves all."""
+        if v is None:
+            return None
+        v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+        tail = () if width is None else (width,)
+        if v.shape == (n,) + tail:
+            v = np.broadcast_to(v, (b, n) + tail)
+        if v.shape != (b, n) + tail:
+            raise ValueError(f"{what} {v.shape} should be {(b, n) + tail}")
+        return np.array(v, dtype=np.float32, order="C")  # (a copy: a broadcast view is read-only)
+
+    @staticmethod
     def _check_order(order, n):
         if not np.array_equal(np.sort(order, axis=-1), np.broadcast_to(np.arange(n), order.shape)):
             raise ValueError("decoding_order: every sequence needs a permutation of 0 .. N-1")
 
-    def _run(self, design, dev, x, b, n, m, res_mask, chain_mask, residue_index, chain_idx, S, order, u=None, omit=None, bias=None, temperature=1.0):
-        """One call of fdipt_mpnn_design or fdipt_mpnn_score; NumPy outputs."""
+    def _run(self, design, dev, x, b, n, m, res_mask, chain_mask, residue_index, chain_idx, S, order, u=None, omit=None, bias=None, temperature=1.0,
+             controls=None, pssm_multi=0.0, unconditional=False):
+        """One call of fdipt_mpnn_design or fdipt_mpnn_score; NumPy outputs.  ``controls``: the optional arrays of FdiptMpnnArgs by field
+        name (None = absent).  ``unconditional``: the score entry's mode in which S and order are not read (pass None)."""
         import torch
         lib = _lib.load()
         if m > MAX_SEQ:
@@ -286,7 +392,9 @@ class ProteinMPNN:
                 return None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(dev)
 
             t = {k: up(v) for k, v in (("res_mask", res_mask), ("chain_mask", chain_mask), ("residue_index", residue_index), ("chain_idx", chain_idx),
-                                       ("S", S.astype(np.int32)), ("decoding_order", order.astype(np.int32)), ("u", u), ("omit", omit), ("bias", bias))}
+                                       ("S", None if S is None else S.astype(np.int32)),
+                                       ("decoding_order", None if order is None else order.astype(np.int32)), ("u", u), ("omit", omit), ("bias", bias))}
+            t.update({k: up(v) for k, v in (controls or {}).items()})
             out = {"E_idx": torch.zeros((b, n, k_eff), dtype=torch.int32, device=dev), "status": torch.zeros((b,), dtype=torch.int32, device=dev)}
             if design:
                 out["S_out"] = torch.zeros((b, m, n), dtype=torch.int32, device=dev)
@@ -297,7 +405,8 @@ class ProteinMPNN:
             work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             p = _lib.ptr
             args = _lib.MpnnArgs(B=b, N=n, M=m, atoms=int(x.shape[2]), weights=p(self._weights_on(dev)), prot=p(x), temperature=float(temperature),
-                                 workspace=p(work), workspace_bytes=nbytes, **{k: p(v) for k, v in t.items()}, **{k: p(v) for k, v in out.items()})
+                                 workspace=p(work), workspace_bytes=nbytes, pssm_multi=float(pssm_multi), unconditional=int(bool(unconditional)),
+                                 **{k: p(v) for k, v in t.items()}, **{k: p(v) for k, v in out.items()})
             fn = lib.fdipt_mpnn_design if design else lib.fdipt_mpnn_score
             _lib.check(fn(C.byref(dims), C.byref(args), _lib.stream_ptr()), "fdipt_mpnn_design" if design else "fdipt_mpnn_score")
             return {k: v.cpu().numpy() for k, v in out.items()}
@@ -328,14 +437,27 @@ class ProteinMPNN:
                 "status": out["status"].astype(np.int64)}
 
     def design(self, prot, num_seq: int = 8, temperature: float = 0.1, seed: int = 38, res_mask=None, chain_mask=None, aatype=None,
-               residue_index=None, chain_idx=None, omit: str = "X", bias=None, decoding_order=None, u=None) -> dict:
+               residue_index=None, chain_idx=None, omit: str = "X", bias=None, decoding_order=None, u=None, bias_by_res=None, omit_mask=None,
+               pssm_coef=None, pssm_bias=None, pssm_multi: float = 0.0, pssm_log_odds=None, pssm_threshold: float = 0.0, tied_positions=None,
+               tied_beta=None) -> dict:
         """``num_seq`` sequences per backbone by the autoregressive loop of ``sample``, then the reference's rescoring of each.  Rows with
         chain_mask 0 are fixed to ``aatype`` (restype order; default: all unknown), rows without res_mask keep it too.  ``omit``: letters
         never drawn; ``bias``: a dict letter -> bias or 21 floats in the model's alphabet.  decoding_order and the uniforms u [B,M,N]
         come from ``torch.Generator().manual_seed(seed)`` (a normal draw, then a uniform draw) unless passed in.  A letter is the first
         one whose cumulative probability exceeds u * sum(p).  Returns ``S`` [B,M,N] model letters, ``aatype`` [B,M,N], ``sequences``
         (strings over the rows with res_mask), ``probs`` [B,M,N,21], ``log_probs``, ``decoding_order``, ``u``, ``score``,
-        ``global_score``, ``seq_recovery`` [B,M] (NaN without aatype), ``E_idx``, ``status`` [B]."""
+        ``global_score``, ``seq_recovery`` [B,M] (NaN without aatype), ``E_idx``, ``status`` [B].
+
+        Per-row controls (each [B,N,..] or [N,..] for all backbones, None = absent, and with none given every
+        output keeps its bits): ``bias_by_res`` [.,N,21] joins the logits as bias / T; ``pssm_bias`` [.,N,21] with ``pssm_coef`` [.,N] and
+        ``pssm_multi`` mixes a profile in; ``pssm_log_odds`` [.,N,21] keeps the letters above ``pssm_threshold`` at full weight and the
+        others at 0.001 (needs ``pssm_coef`` too, as the C entry does); ``omit_mask`` [.,N,21] forbids letters per row.  A row left
+        without a letter keeps its input letter, has probs 0 and sets ``NO_LETTER`` in its backbone's status.
+        ``tied_positions`` (``tie_groups``; ``tied_positions_from_chains`` builds a homo-oligomer's) with ``tied_beta`` [.,N] (default 1):
+        the rows of a group get one letter from the weighted sum of their logits, as ``tied_sample`` does; the controls and u of a group
+        are read at its LAST listed member.  The result gains ``tie_group`` [B,N] and ``decoding_order`` is the flattened one (every
+        group emitted whole at its first drawn member), which the rescoring uses too: it is teacher-forced, so the members of a group
+        see each other's letters there and ``log_probs`` of tied rows do not agree with ``probs``."""
         import torch
         if not temperature > 0:
             raise ValueError("temperature must be positive")
@@ -364,8 +486,20 @@ class ProteinMPNN:
         if u.min() < 0 or u.max() >= 1:
             raise ValueError("u outside [0, 1)")
         S_in = self._per_sequence(s_in, b, m, n, np.int64, "aatype")
+        controls = {"bias_by_res": self._per_row(bias_by_res, b, n, VOCAB, "bias_by_res"), "omit_mask": self._per_row(omit_mask, b, n, VOCAB, "omit_mask"),
+                    "pssm_coef": self._per_row(pssm_coef, b, n, None, "pssm_coef"), "pssm_bias": self._per_row(pssm_bias, b, n, VOCAB, "pssm_bias"),
+                    "pssm_log_odds_mask": None if pssm_log_odds is None else log_odds_mask(self._per_row(pssm_log_odds, b, n, VOCAB, "pssm_log_odds"), pssm_threshold)}
+        if (controls["pssm_bias"] is not None or controls["pssm_log_odds_mask"] is not None) and controls["pssm_coef"] is None:
+            raise ValueError("pssm_bias and pssm_log_odds need pssm_coef")
+        tie_group, groups = tie_groups(tied_positions, b, n, res_mask, chain_mask)
+        if tied_positions is not None:
+            beta = self._per_row(tied_beta, b, n, None, "tied_beta")
+            controls["tie_group"], controls["tied_beta"] = tie_group, np.ones((b, n), np.float32) if beta is None else beta
+            order = np.stack([np.stack([flatten_decoding_order(order[i, j], groups[i]) for j in range(m)]) for i in range(b)])
+        elif tied_beta is not None:
+            raise ValueError("tied_beta without tied_positions")
         common = (dev, x, b, n, m, res_mask, chain_mask, residue_index, chain_idx)
-        des = self._run(True, *common, S_in, order, u=u, omit=omit_v, bias=bias_v, temperature=temperature)
+        des = self._run(True, *common, S_in, order, u=u, omit=omit_v, bias=bias_v, temperature=temperature, controls=controls, pssm_multi=pssm_multi)
         S = des["S_out"].astype(np.int64)
         rescored = self._run(False, *common, S, order)
         with np.errstate(invalid="ignore", divide="ignore"):
@@ -376,4 +510,47 @@ class ProteinMPNN:
                 "probs": des["probs"], "log_probs": rescored["log_probs"], "decoding_order": order, "u": u,
                 "score": scores_of(rescored["log_probs"], S, designed[:, None]), "global_score": scores_of(rescored["log_probs"], S, res_mask[:, None]),
                 "seq_recovery": recovery, "E_idx": des["E_idx"].astype(np.int64), "status": (des["status"] | rescored["status"]).astype(np.int64),
-                "S_input": s_in, "res_mask": res_mask, "chain_mask": chain_mask, "temperature": temperature, "seed": seed}
+                "S_input": s_in, "res_mask": res_mask, "chain_mask": chain_mask, "temperature": temperature, "seed": seed, "tie_group": tie_group.astype(np.int64)}
+
+    def unconditional_probs(self, prot, res_mask=None, residue_index=None, chain_idx=None) -> dict:
+        """``unconditional_probs`` of the reference: the decoder with no neighbour counted as decoded, what the backbone alone says.
+        Returns ``log_probs`` [B,N,21] (0 in rows without res_mask), ``E_idx``, ``status`` [B]."""
+        dev, x, b, n, res_mask, chain_mask, residue_index, chain_idx = self._inputs(prot, res_mask, None, residue_index, chain_idx)
+        out = self._run(False, dev, x, b, n, 1, res_mask, chain_mask, residue_index, chain_idx, None, None, unconditional=True)
+        return {"log_probs": out["log_probs"][:, 0], "E_idx": out["E_idx"].astype(np.int64), "status": out["status"].astype(np.int64)}
+
+    def conditional_probs(self, prot, S, res_mask=None, chain_mask=None, residue_index=None, chain_idx=None, backbone_only: bool = False, seed=None,
+                          randn=None) -> dict:
+        """``conditional_probs`` of the reference.  For every row i with chain_mask and res_mask, row i of the teacher-forced
+        log-probabilities of ``S`` [B,N] under the order ``argsort((onehot_i + 0.0001) * |randn|)``: i decoded last, every other letter
+        given.  ``backbone_only``: ``argsort((1 - onehot_i + 0.0001) * |randn|)``, i decoded first, no letter given.  ``randn`` [B,N]:
+        one normal draw per backbone, from ``torch.Generator().manual_seed(seed)`` (0 for None) unless passed in.  Built as host-side
+        chunks of at most MAX_SEQ orders through ``fdipt_mpnn_score`` (each chunk runs the encoder again).
+        Returns ``log_probs`` [B,N,21] (0 in every other row), the ``randn`` used, ``status`` [B]."""
+        import torch
+        dev, x, b, n, res_mask, chain_mask, residue_index, chain_idx = self._inputs(prot, res_mask, chain_mask, residue_index, chain_idx)
+        S = self._per_sequence(S, b, 1, n, np.int64, "S")[:, 0]
+        if S.min() < 0 or S.max() >= VOCAB:
+            raise ValueError("S: letters outside 0 .. 20")
+        if randn is None:
+            randn = torch.randn((b, n), generator=torch.Generator().manual_seed(0 if seed is None else int(seed))).numpy()
+        randn = np.asarray(randn.detach().cpu().numpy() if hasattr(randn, "detach") else randn, dtype=np.float32)
+        randn = randn[None] if randn.ndim == 1 else randn
+        if randn.shape != (b, n):
+            raise ValueError(f"randn {randn.shape} should be {(b, n)}")
+        rows = [np.flatnonzero(chain_mask[i] * res_mask[i]) for i in range(b)]
+        out, status = np.zeros((b, n, VOCAB), np.float32), np.zeros((b,), np.int64)
+        for start in range(0, max(len(r) for r in rows), MAX_SEQ):
+            chunk = [r[start:start + MAX_SEQ] for r in rows]
+            m = max(len(c) for c in chunk)
+            order = np.tile(np.arange(n, dtype=np.int64), (b, m, 1))  # (sequences past a backbone's rows: any order; not read back)
+            for i, c in enumerate(chunk):
+                if len(c):
+                    hot = torch.zeros((len(c), n))
+                    hot[torch.arange(len(c)), torch.from_numpy(c)] = 1.0
+                    order[i, :len(c)] = torch.argsort(((1.0 - hot if backbone_only else hot) + 0.0001) * torch.abs(torch.from_numpy(randn[i]))[None], dim=-1).numpy()
+            res = self._run(False, dev, x, b, n, m, res_mask, chain_mask, residue_index, chain_idx, np.repeat(S[:, None], m, axis=1), order)
+            status |= res["status"].astype(np.int64)
+            for i, c in enumerate(chunk):
+                out[i, c] = res["log_probs"][i, np.arange(len(c)), c]
+        return {"log_probs": out, "randn": randn, "status": status}

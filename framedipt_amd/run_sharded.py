@@ -565,13 +565,15 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
 
 
 def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, seq_per_sample: int = 8, weights=None, temperature: float = 0.1,
-               seed: int = 38, max_batch: int = 16):
+               seed: int = 38, max_batch: int = 16, omit_aas: str = "X"):
     """Rank 0, after the gather (``--design``; framedipt_amd/inverse_folding.py): ``seq_per_sample`` ProteinMPNN sequences per sample at the
     reference's settings (``--sampling_temp 0.1 --seed 38``, X omitted), what experiments/inference.py:run_protein_mpnn starts a subprocess
     for.  De novo runs design every row; inpainting runs design the diffused rows with the context fixed to its true residue types.
     Samples of one length share a call.  ``weights``: a checkpoint in the reference's layout, or None for SYNTHETIC parameters (stated in
     the output: such sequences exercise the path and mean nothing).  Writes ``seqs/<sample>.fa`` in the reference's FASTA layout and
-    ``design.json``.  Returns the summary written."""
+    ``design.json``.  ``omit_aas`` (``--omit-aas``): the letters never drawn.  Inpainting runs add ``native_conditional_score`` per sample:
+    the mean negative conditional log-probability (``conditional_probs``: every other letter given) of the TRUE letters of the diffused
+    rows on the sampled backbone.  Returns the summary written."""
     from . import inverse_folding
     model = inverse_folding.ProteinMPNN()
     model = model.load_checkpoint(weights) if weights else model.load_synthetic(0)
@@ -589,7 +591,13 @@ def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, 
                                res_mask=rows("res_mask", np.ones(length, np.float32)),
                                chain_mask=np.stack([it["diffused"] for it in items]).astype(np.float32) if inpainting else None,
                                aatype=np.clip(rows("aatype", np.full(length, 20)), 0, 20) if inpainting else None,
-                               residue_index=rows("residue_index", np.arange(length)), chain_idx=rows("chain_idx", np.ones(length)))
+                               residue_index=rows("residue_index", np.arange(length)), chain_idx=rows("chain_idx", np.ones(length)), omit=omit_aas)
+            native = None
+            if inpainting:
+                cond = model.conditional_probs(np.stack([it["prot"] for it in items]).astype(np.float32), res["S_input"], res_mask=res["res_mask"],
+                                               chain_mask=res["chain_mask"], residue_index=rows("residue_index", np.arange(length)),
+                                               chain_idx=rows("chain_idx", np.ones(length)), seed=seed)
+                native = inverse_folding.native_scores(cond["log_probs"], res["S_input"], res["chain_mask"] * res["res_mask"])
             for b, r in enumerate(chunk):
                 stem = os.path.splitext(r["file"])[0].replace(os.sep, "_")
                 fasta = os.path.join("seqs", stem + ".fa")
@@ -600,8 +608,10 @@ def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, 
                                  "score": [float(v) for v in res["score"][b]], "global_score": [float(v) for v in res["global_score"][b]],
                                  "seq_recovery": [None if np.isnan(v) else float(v) for v in res["seq_recovery"][b]], "status": int(res["status"][b]),
                                  "fasta": fasta}
+                if native is not None:
+                    samples[stem]["native_conditional_score"] = float(native[b])
     summary = {"weights": model.source, "synthetic": not weights, "k_neighbors": model.k_neighbors, "temperature": temperature, "seed": seed,
-               "seq_per_sample": seq_per_sample, "omit": "X", "samples": samples}
+               "seq_per_sample": seq_per_sample, "omit": omit_aas, "samples": samples}
     with open(os.path.join(out_dir, "design.json"), "w") as f:
         json.dump(summary, f, indent=1)
     return summary
@@ -726,6 +736,7 @@ def main():
                     "ProteinMPNN at T = 0.1, seed 38, X omitted, as the reference's run_protein_mpnn): seqs/<sample>.fa and design.json.  De novo runs design "
                     "every row, inpainting runs the diffused rows with the context fixed")
     ap.add_argument("--seq-per-sample", type=int, default=8, help="--design: sequences per sample (the reference's inference.samples.seq_per_sample)")
+    ap.add_argument("--omit-aas", default="X", help="--design: the letters never drawn (ProteinMPNN's --omit_AAs)")
     ap.add_argument("--mpnn-weights", default=None, help="--design: a ProteinMPNN checkpoint (.pt with model_state_dict, num_edges, noise_level); default: "
                     "SYNTHETIC parameters, stated as such in the output")
     ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score, --tm-align: the TM-score threshold of the clusters (reference default)")
@@ -883,7 +894,7 @@ def main():
             print(f"structural alignments of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
         if a.design:
             t1 = time.perf_counter()
-            done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights)
+            done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights, omit_aas=a.omit_aas)
             print(f"{a.seq_per_sample} sequence(s) for each of {len(done['samples'])} sample(s) with {'SYNTHETIC ProteinMPNN parameters' if done['synthetic'] else done['weights']} "
                   f"in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/seqs/<sample>.fa, design.json", flush=True)
     if world > 1:

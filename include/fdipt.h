@@ -725,6 +725,7 @@ int fdipt_sample_tm_align(const FdiptTmAlignArgs* args, fdipt_stream_t stream);
 #define FDIPT_MPNN_MAX_SEQ 64         /* M beyond: FDIPT_ESIZE                                                                       */
 #define FDIPT_MPNN_MAX_NEIGHBORS 64   /* k_neighbors outside 1 .. 64: FDIPT_EINVAL                                                   */
 #define FDIPT_MPNN_MASKED_NEIGHBOR 1  /* status: a row with res_mask set has a neighbour without; no parity with the reference there */
+#define FDIPT_MPNN_NO_LETTER 2        /* status (design): the controls of a row left no letter with p > 0; it keeps its input letter  */
 typedef struct FdiptMpnnDims {
   int32_t hidden, enc_layers, dec_layers, vocab; /* 128, 3, 3, 21: anything else is FDIPT_EINVAL                                    */
   int32_t k_neighbors;                /* K, the checkpoint's num_edges; a row takes K_eff = min(K, N) neighbours                     */
@@ -753,10 +754,25 @@ typedef struct FdiptMpnnArgs {
   int32_t* status;                    /* [B] i32: FDIPT_MPNN_* bits                                                                  */
   void* workspace;
   size_t workspace_bytes;
+  /* optional inputs; NULL / 0 = absent, so a caller that zero-fills the struct and never names them gets the
+   * entries as they were.  The per-row controls and the ties are read by fdipt_mpnn_design only, at the row being decoded (for a tied
+   * group: at its LAST member, as tied_sample does). */
+  const float* bias_by_res;           /* [B,N,21] f32: added to the logits as bias_by_res / temperature                              */
+  const float* omit_mask;             /* [B,N,21] f32: p *= 1 - omit_mask, renormalised (the reference's omit_AA_mask)                */
+  const float* pssm_coef;             /* [B,N] f32: needed by pssm_bias and pssm_log_odds_mask                                        */
+  const float* pssm_bias;             /* [B,N,21] f32: p = (1 - pssm_multi coef) p + pssm_multi coef pssm_bias                        */
+  const float* pssm_log_odds_mask;    /* [B,N,21] f32: p = p mask + 0.001 p, renormalised                                             */
+  const int32_t* tie_group;           /* [B,N] i32: -1 = untied; consecutive steps of decoding_order whose rows carry the same id >= 0 */
+                                      /* are ONE group: one letter from the weighted sum of the members' logits                      */
+  const float* tied_beta;             /* [B,N] f32: a member's weight in its group's logits; needed by tie_group                      */
+  float pssm_multi;                   /* the scalar of pssm_bias                                                                     */
+  int32_t unconditional;              /* fdipt_mpnn_score only: != 0 = no neighbour counts as decoded (unconditional_probs); S and    */
+                                      /* decoding_order are not read and may be NULL                                                 */
 } FdiptMpnnArgs;
 size_t fdipt_mpnn_workspace(const FdiptMpnnDims* dims, int B, int N, int M);
 /* FDIPT_EINVAL: a null pointer the entry reads or writes, unsupported dims, B, N or M < 1, atoms not 37 or 5, temperature <= 0
- * (design).  FDIPT_ESIZE: N > FDIPT_MPNN_MAX_ROWS, M > FDIPT_MPNN_MAX_SEQ, workspace too small.  All before any launch. */
+ * (design), pssm_bias or pssm_log_odds_mask without pssm_coef (design), tie_group without tied_beta (design).  FDIPT_ESIZE: N >
+ * FDIPT_MPNN_MAX_ROWS, M > FDIPT_MPNN_MAX_SEQ, workspace too small.  All before any launch. */
 int fdipt_mpnn_score(const FdiptMpnnDims* dims, const FdiptMpnnArgs* args, fdipt_stream_t stream);
 int fdipt_mpnn_design(const FdiptMpnnDims* dims, const FdiptMpnnArgs* args, fdipt_stream_t stream);
 

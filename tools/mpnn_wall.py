@@ -4,9 +4,10 @@ calls (device tensor in, NumPy results out, the rescoring included; the first ca
 sequences, the time between device-side events around each C entry, and the time of the torch restatement (tests/mpnn_ref.py) of the same
 work in eager mode, float32, on the same GPU - the stand-in for what the reference's subprocess computes, without its PDB parsing - with
 the number of letters in which the two disagree (float32 rounding next to a boundary of a cumulative distribution; not a parity claim).
-One run; no threshold is attached to these times.
+One run; no threshold is attached to these times.  ``--tied``: the same load as a 3 x 100 homo-trimer, row r of the three chains tied
+(DESIGN.md section 7.11); the restatement is then not run.
 
-    python tools/mpnn_wall.py [out.json] [--restatement-sequences K]
+    python tools/mpnn_wall.py [out.json] [--restatement-sequences K] [--tied]
 """
 import argparse
 import json
@@ -29,8 +30,9 @@ B, N, M, K, T = 8, 300, 8, 48, 0.1
 ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?", default=None)
 ap.add_argument("--restatement-sequences", type=int, default=B * M, help="time the restatement on the first K sequences and scale")
+ap.add_argument("--tied", action="store_true", help="three chains of 100 rows, row r of every chain tied")
 cli = ap.parse_args()
-n_restatement = cli.restatement_sequences
+n_restatement = 0 if cli.tied else cli.restatement_sequences
 
 lib = _lib.load()
 events = {"fdipt_mpnn_design": [], "fdipt_mpnn_score": []}
@@ -58,18 +60,22 @@ d_prot = torch.from_numpy(prot).cuda()
 model = inv.ProteinMPNN(K).load_synthetic(mr.WEIGHT_SEED)
 torch.cuda.synchronize()
 
-out = {"backbones": B, "rows": N, "sequences_per_backbone": M, "k_neighbors": K, "temperature": T}
+out = {"backbones": B, "rows": N, "sequences_per_backbone": M, "k_neighbors": K, "temperature": T, "tied": cli.tied}
+chains = {}
+if cli.tied:
+    chains = {"chain_idx": np.tile(np.repeat([1, 2, 3], N // 3), (B, 1)), "residue_index": np.tile(np.arange(N // 3), (B, 3))}
+    chains["tied_positions"] = inv.tied_positions_from_chains(chains["chain_idx"][0])  # one list of groups serves every backbone
 walls = []
 for _ in range(3):
     t0 = time.perf_counter()
-    des = model.design(d_prot, num_seq=M, temperature=T, seed=38)
+    des = model.design(d_prot, num_seq=M, temperature=T, seed=38, **chains)
     walls.append(time.perf_counter() - t0)
 out["design"] = {"first_call_wall_s": walls[0], "call_wall_s": walls[1:], "letters_used": int(len(np.unique(des["S"]))),
                  "score_mean": float(des["score"].mean()), "statuses": sorted(set(des["status"].tolist()))}
 walls = []
 for _ in range(3):
     t0 = time.perf_counter()
-    sc = model.score(d_prot, des["S"], decoding_order=des["decoding_order"])
+    sc = model.score(d_prot, des["S"], decoding_order=des["decoding_order"], **{k: v for k, v in chains.items() if k != "tied_positions"})
     walls.append(time.perf_counter() - t0)
 torch.cuda.synchronize()
 out["score"] = {"first_call_wall_s": walls[0], "call_wall_s": walls[1:], "equals_design_rescoring": bool(np.array_equal(sc["log_probs"], des["log_probs"]))}
