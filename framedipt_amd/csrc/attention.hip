@@ -707,7 +707,78 @@ __global__ __launch_bounds__(FD_THREADS) void opair_pz_kernel(OPairArgs a, int n
     else a.out[o] = v;
   }
 }
+// The same o_pair with pair_z GATHERED: block 0 behind the edge embedder's row table, where pair_z of a pair is the 64 B record of its
+// table row (a.pz_rows[a.pz_idx[pair]]) and the rows of a batch are few enough to sit in L2 — no image is written or streamed.  A wave
+// fetches the records of OPG_KS k-steps (lane = key of the k-step x 16 B chunk) and transposes them through its own LDS tile into
+// EXACTLY the B fragments of the image form (lane (d, hi): keys 16 s + 8 hi + q of channel d; keys >= N zero, as the image's guards);
+// same A fragments, same k-step order, same accumulator alternation (OPG_KS is even), so the result carries the same bits.  The tile is
+// wave-private and the DS operations of a wave execute in order: no barrier.  A key's record sits at slot 2 (k & 7) + (k >> 3) of its
+// k-step, so that the two keys one fragment read touches are 128 contiguous bytes.
+#define OPG_KS 10
+__global__ __launch_bounds__(FD_THREADS) void opair_pzg_kernel(OPairArgs a, int n_rows) {
+  __shared__ __attribute__((aligned(16))) char tile_s[(FD_THREADS / 64) * OPG_KS * 1024];
+  const int lane = threadIdx.x & 63, li = lane & 31, hi = lane >> 5, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * (FD_THREADS / 64) + wave;
+  if (row >= n_rows) return;
+  char* tile = tile_s + wave * (OPG_KS * 1024);
+  const int N = a.N, ksteps = (N + 15) >> 4;
+  const half_t* pr = a.probs_h16 + ((long)row * 8 + (li & 7)) * a.probs_np + 8 * hi;
+  const int32_t* ix = a.pz_idx + (long)row * N;
+  const int kq = lane >> 2, ch = lane & 3;  // gather side: key kq of a k-step, 16 B chunk ch of its record
+  const char* recs = (const char*)a.pz_rows + ch * 16;
+  char* wr = tile + (((kq & 7) << 1) | (kq >> 3)) * 64 + ch * 16;
+  const char* rd = tile + hi * 64 + li * 2;
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
+  for (int s0 = 0; s0 < ksteps; s0 += OPG_KS) {
+    int id[OPG_KS];
+    u32x4 rec[OPG_KS];
+    u16x8 af[OPG_KS];
+#pragma unroll
+    for (int u = 0; u < OPG_KS; ++u) {
+      const int j = 16 * (s0 + u) + kq;
+      id[u] = j < N ? ix[j] : -1;  // (j < N implies s0 + u < ksteps)
+    }
+#pragma unroll
+    for (int u = 0; u < OPG_KS; ++u) {
+      af[u] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (s0 + u < ksteps && li < 8) af[u] = *(const u16x8*)(pr + 16 * (s0 + u));
+      rec[u] = u32x4{0u, 0u, 0u, 0u};
+      if (id[u] >= 0) rec[u] = *(const u32x4*)(recs + (long)id[u] * 64);
+    }
+#pragma unroll
+    for (int u = 0; u < OPG_KS; ++u) *(u32x4*)(wr + u * 1024) = rec[u];
+#pragma unroll
+    for (int u = 0; u < OPG_KS; ++u) {
+      if (s0 + u < ksteps) {
+        unsigned short v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = *(const unsigned short*)(rd + u * 1024 + q * 128);
+        const u32x4 bw = {(unsigned)v[0] | ((unsigned)v[1] << 16), (unsigned)v[2] | ((unsigned)v[3] << 16), (unsigned)v[4] | ((unsigned)v[5] << 16),
+                          (unsigned)v[6] | ((unsigned)v[7] << 16)};
+        const hx8 bf = __builtin_bit_cast(hx8, bw);
+        if (u & 1) acc1 = fd_mfma32(__builtin_bit_cast(hx8, af[u]), bf, acc1);
+        else acc0 = fd_mfma32(__builtin_bit_cast(hx8, af[u]), bf, acc0);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float v = acc0[r] + acc1[r];
+    const long o = (long)row * a.out_ld + a.off + (4 * hi + r) * 32 + li;
+    if (a.out_h16) a.out_h16[o] = f2h(v);
+    else a.out[o] = v;
+  }
+}
 int fd_opair_pz(const OPairArgs& a, hipStream_t st) {
+  if (a.pz_idx) {
+    if (!a.pz_rows || !a.probs_h16 || a.H != 8 || a.CD != 32 || (a.probs_np & 7) || a.probs_np < ((a.N + 15) & ~15)) return FDIPT_EINVAL;
+    const int n_rows = a.B * a.N;
+    hipLaunchKernelGGL(opair_pzg_kernel, dim3(cdiv(n_rows, FD_THREADS / 64)), dim3(FD_THREADS), 0, st, a, n_rows);
+    FD_CHECK_LAUNCH();
+    return FDIPT_OK;
+  }
   if (!a.pz || !a.probs_h16 || a.H != 8 || a.CD != 32 || (a.probs_np & 7) || a.probs_np < ((a.N + 15) & ~15)) return FDIPT_EINVAL;
   const int n_rows = a.B * a.N;
   hipLaunchKernelGGL(opair_pz_kernel, dim3(cdiv(n_rows, FD_THREADS / 64)), dim3(FD_THREADS), 0, st, a, n_rows, (a.N + 3) >> 2);

@@ -18,7 +18,7 @@ pids=()
 T0=$SECONDS
 NCOMP=0
 for f in gemm ipa_proj2 pair_mlp edge_embed2 edge_transition3 edge_transition4 attention attention3 pair_bias attention_seq chain rowblock frames select evaluate violations dssp sasa tmscore tmalign mpnn model; do
-  if [ ! -f "$BUILD/$f.o" ] || [ "$HERE/$f.hip" -nt "$BUILD/$f.o" ] || [ "$HERE/common.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/kernels.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/philox.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/horn.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/tmsearch.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/../../include/fdipt.h" -nt "$BUILD/$f.o" ]; then
+  if [ ! -f "$BUILD/$f.o" ] || [ "$HERE/$f.hip" -nt "$BUILD/$f.o" ] || [ "$HERE/common.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/kernels.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/philox.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/horn.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/tmsearch.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/ee2_table_map.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/../../include/fdipt.h" -nt "$BUILD/$f.o" ]; then
     $HIPCC $FLAGS -c "$HERE/$f.hip" -o "$BUILD/$f.o" &
     pids+=($!)
     NCOMP=$((NCOMP + 1))

@@ -13,6 +13,7 @@
 //     DIST = false instantiation: three table rows per pair, no distances, no bins, nothing of the distogram in LDS.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "ee2_table_map.hpp"
 
 #define ET2_CZ 128
 #define EE2_WBC 2048     // compact linear_b image of the first block (8 head rows); then a 64 B zero unit, the hi / lo down_z images (8 KB each)
@@ -286,6 +287,8 @@ struct Ee2Bins {
 // instantiation evaluates each such row once (same arithmetic as the pair kernel) and ee2_spread_kernel copies the records to the pairs.
 // Row r of sample b: b * rows_per_sample + ((2 class_i + class_j) * n_rel + rel) * (num_bins + 1) + bin; the sample's last row is the
 // all-zero row of masked pairs.  Records: z [128] half, pair bias [8] f32, pair_z [32] half, one array each.
+// Only LEADERS have their rows evaluated (ee2_leaders_kernel below; a.leaders): a follower's pairs point into its leader's rows, the
+// zero row included, and the follower's own region of the table stays unwritten and unread.
 __host__ __device__ __forceinline__ int ee2_rows_per_sample(int n_rel, int nb) { return 4 * n_rel * (nb + 1) + 1; }
 size_t fd_ee2_table_bytes(int B, int n_rel, int num_bins) {
   return (size_t)B * ee2_rows_per_sample(n_rel, num_bins) * (ET2_CZ * 2 + 8 * 4 + 32 * 2);
@@ -306,9 +309,11 @@ __host__ __device__ __forceinline__ Ee2Table ee2_table_of(void* table, int B, in
   return t;
 }
 
-// TABLE: a tile is 32 bins of one (sample, class pair, rel) and the walk goes over rel: Pi / Pj are the rows of the first residue of
+// TABLE: a tile is 32 bins of one (leader, class pair, rel) and the walk goes over rel: Pi / Pj are the rows of the first residue of
 // either class (items of a class pair the sample does not have end at once), R[rel] is one row for the whole tile, the mask is 1.
-// nt = bin tiles; items are class-pair major so that the live ones of a one-class batch are consecutive
+// nt = bin tiles.  The launcher cannot know how many leaders the batch has: the kernel counts them and derives its items from the count
+// (ee2_table_map.hpp; wpg, rpw and n_items are not read), so that the leaders' rows are shared among all waves, and deals consecutive
+// items to different blocks (the live items of a one-class batch are the first ones: a block then holds as few of them as can be)
 template <bool DIST, bool DLDS, bool TRACE, bool LO = false, bool TABLE = false>
 __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedArgs a, const char* __restrict__ img, int nt, int wpg,
                                                                      int rpw, int n_items) {
@@ -367,13 +372,28 @@ __global__ __launch_bounds__(EE2_THREADS, 1) void edge_embed2_kernel(EdgeEmbedAr
       if (tid < 32) ((unsigned short*)tab.pz)[zr * 32 + tid] = (unsigned short)fd_cvt_pk(0.f + a.bdz[tid], 0.f);
     }
   }
-  for (int item = blockIdx.x * 8 + wave; item < n_items; item += gridDim.x * 8) {
+  Ee2TableMap tmap = {};
+  if constexpr (TABLE) {  // (wave-uniform scalar loads; sample 0 always leads)
+    int n_lead = 0;
+    for (int s = 0; s < a.B; ++s) n_lead += a.leaders[s] == s ? 1 : 0;
+    tmap = ee2_table_map(n_lead < 1 ? 1 : n_lead, nt, a.n_rel);
+  }
+  const int n_it = TABLE ? tmap.n_items : n_items;
+  for (int item = TABLE ? wave * gridDim.x + blockIdx.x : blockIdx.x * 8 + wave; item < n_it; item += gridDim.x * 8) {
     // ---- group (sample b, key tile jt): per-key state of the 32 keys, resident for the whole walk
-    const int per_cc = TABLE ? n_items >> 2 : n_items, cc = TABLE ? item / per_cc : 0, it_cc = item - cc * per_cc;
-    const int grp = it_cc / wpg, part = it_cc - grp * wpg;
-    const int b = grp / nt, jt = grp - b * nt, j0 = jt * 32;
-    const int n_walk = TABLE ? a.n_rel : N, n_keys = TABLE ? nb + 1 : N;  // TABLE: the walk is over rel, the "keys" are bins
-    const int i_first = part * rpw, i_end = (i_first + rpw < n_walk) ? i_first + rpw : n_walk;
+    int cc = 0, b, jt, i_first, i_end;
+    if constexpr (TABLE) {
+      const Ee2TableItem ti = ee2_table_item(tmap, item);
+      cc = ti.cc; jt = ti.jt; i_first = ti.rel0; i_end = ti.rel1;
+      b = 0;
+      for (int s = 0, k = -1; s < a.B; ++s)  // the sample of leader ti.lead
+        if (a.leaders[s] == s && ++k == ti.lead) { b = s; break; }
+    } else {
+      const int grp = item / wpg, part = item - grp * wpg;
+      b = grp / nt; jt = grp - b * nt;
+      i_first = part * rpw; i_end = (i_first + rpw < N) ? i_first + rpw : N;
+    }
+    const int j0 = jt * 32, n_keys = TABLE ? nb + 1 : N;  // TABLE: the walk is over rel, the "keys" are bins
     if (i_first >= i_end) continue;
     const int nvalid = n_keys - j0 < 32 ? n_keys - j0 : 32;
     const bool valid = li < nvalid;
@@ -579,14 +599,84 @@ int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st, int 
   return FDIPT_OK;
 }
 
-// ---- the row table: its launch, and the spread of its records to the pairs
+// ---- the row table: its leaders, its launch, and the spread of its records to the pairs
+// Block b decides a.leaders[b]: the first sample c < b that (1) has every fixed-mask class b has, (2) whose Pi and Pj rows of the
+// representatives (first residues) of b's classes carry the bits of b's, and (3) whose R rows carry the bits of b's; b itself if there
+// is none.  These rows, the sample-free distogram rows and the weights are all a table row is made of, so c's rows ARE b's rows.  Bits
+// are compared, not values (-0 and NaN patterns count).  The relation is transitive, so the first match is itself a leader.
+// (3) is constant along a trajectory and 2.4 MB of reads at c4, so it is decided once, when the R rows are made (fdipt_sample_setup:
+// ee2_rel_leaders_kernel, a.rel_lead[b] = the first sample with b's R rows); the per-step launch compares two integers.
+#define EL_THREADS 1024
+__global__ __launch_bounds__(EL_THREADS) void ee2_rel_leaders_kernel(int n4, const u32x4* __restrict__ rtab, int32_t* __restrict__ rel_lead) {
+  const int tid = threadIdx.x, b = blockIdx.x;
+  int lead = b;
+  for (int c = 0; c < b; ++c) {
+    const u32x4 *rb4 = rtab + (long)b * n4, *rc4 = rtab + (long)c * n4;
+    int same = 1;
+#pragma unroll 4
+    for (int k = tid; k < n4; k += EL_THREADS) {
+      const u32x4 x = rb4[k], y = rc4[k];
+      same &= (x[0] == y[0]) & (x[1] == y[1]) & (x[2] == y[2]) & (x[3] == y[3]);
+    }
+    if (__syncthreads_and(same)) {
+      lead = c;
+      break;
+    }
+  }
+  if (tid == 0) rel_lead[b] = lead;
+}
+int fd_ee2_rel_leaders(int B, long row_floats, const float* rtab, int32_t* rel_lead, hipStream_t st) {
+  if (B < 1 || row_floats < 4 || (row_floats & 3) || row_floats / 4 > 0x7fffffffL || !rtab || !rel_lead) return FDIPT_EINVAL;
+  hipLaunchKernelGGL(ee2_rel_leaders_kernel, dim3(B), dim3(EL_THREADS), 0, st, (int)(row_floats / 4), (const u32x4*)rtab, rel_lead);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
+#define ELS_THREADS 512
+__global__ __launch_bounds__(ELS_THREADS) void ee2_leaders_kernel(EdgeEmbedArgs a) {
+  __shared__ int rep[4];  // first residue of class 0 / 1 of b, then of the candidate (N: the sample has none)
+  const int tid = threadIdx.x, b = blockIdx.x, N = a.N;
+  auto reps = [&](int s, int* out) {
+    if (tid < 2) out[tid] = N;
+    __syncthreads();
+    for (int k = tid; k < N; k += ELS_THREADS) atomicMin(&out[a.fixed_mask[(long)s * N + k] != 0.f ? 1 : 0], k);
+    __syncthreads();
+  };
+  reps(b, rep);
+  const int r0 = rep[0], r1 = rep[1], rl = a.rel_lead[b];
+  int lead = b;
+  for (int c = 0; c < b; ++c) {
+    if (a.rel_lead[c] != rl) continue;  // other R rows (block-uniform)
+    reps(c, rep + 2);
+    const int q0 = rep[2], q1 = rep[3];
+    __syncthreads();  // (the next candidate overwrites them)
+    if ((r0 < N && q0 == N) || (r1 < N && q1 == N)) continue;  // block-uniform
+    int same = 1;
+    if (tid < 4 * ET2_CZ) {  // (class, Pi | Pj, channel)
+      const int cls = tid >> 8, ch = tid & 127, rb = cls ? r1 : r0, rc = cls ? q1 : q0;
+      const unsigned* t = (const unsigned*)((tid >> 7) & 1 ? a.pj : a.pi);
+      if (rb < N) same = t[((long)b * N + rb) * ET2_CZ + ch] == t[((long)c * N + rc) * ET2_CZ + ch];
+    }
+    if (__syncthreads_and(same)) {
+      lead = c;
+      break;
+    }
+  }
+  if (tid == 0) a.leaders[b] = lead;
+}
+const half_t* fd_ee2_table_pz(const void* table, int B, int n_rel, int num_bins) { return ee2_table_of((void*)table, B, n_rel, num_bins).pz; }
+int fd_edge_embed2_leaders(const EdgeEmbedArgs& a, hipStream_t st) {
+  if (!fd_edge_embed2_table_supported(a) || !a.leaders || !a.fixed_mask || !a.pi || !a.pj || !a.rel_lead) return FDIPT_EINVAL;
+  hipLaunchKernelGGL(ee2_leaders_kernel, dim3(a.B), dim3(ELS_THREADS), 0, st, a);
+  FD_CHECK_LAUNCH();
+  return FDIPT_OK;
+}
 int fd_edge_embed2_table_supported(const EdgeEmbedArgs& a) {
   const bool dlds = a.num_bins <= EE2_MAXB_LDS && EE2_LDS_BASE + (a.num_bins + 1) * ET2_CZ * 4 <= EE2_LDS_MAX;
   return a.num_bins >= 3 && dlds && a.H == 8 && a.N % 4 == 0 && (long)a.B * ee2_rows_per_sample(a.n_rel, a.num_bins) < (1L << 24);
 }
 int fd_edge_embed2_table(const EdgeEmbedArgs& a_, const void* img, hipStream_t st, int lo) {
   EdgeEmbedArgs a = a_;
-  if (!fd_edge_embed2_table_supported(a) || !a.table || !a.fixed_mask || !a.wb_img || !a.wdz_img || !a.wdz_img_lo || !a.bdz || a.trace)
+  if (!fd_edge_embed2_table_supported(a) || !a.table || !a.leaders || !a.fixed_mask || !a.wb_img || !a.wdz_img || !a.wdz_img_lo || !a.bdz || a.trace)
     return FDIPT_EINVAL;
   a.pz_out = (half_t*)a.table;  // (any non-null value: the set-up loads the down_z images; the records go to the table)
   const int lds = EE2_LDS_BASE + (a.num_bins + 1) * ET2_CZ * 4;
@@ -599,27 +689,23 @@ int fd_edge_embed2_table(const EdgeEmbedArgs& a_, const void* img, hipStream_t s
       return FDIPT_ELAUNCH;
     attr_dev[kid].set(dev_, 1);
   }
-  // one work item = (class pair, sample, bin tile of 32, range of rpw consecutive rel); a one-class batch (de novo sampling) has a
-  // quarter of the items live, and those should fill the ~2048 waves
-  const int nt = cdiv(a.num_bins + 1, 32), n_groups = a.B * nt, n_waves = 256 * 8;
-  int wpg = n_waves / n_groups < 1 ? 1 : n_waves / n_groups;
-  if (wpg > a.n_rel) wpg = a.n_rel;
-  const int rpw = cdiv(a.n_rel, wpg);
-  wpg = cdiv(a.n_rel, rpw);
-  const int n_items = 4 * n_groups * wpg;
+  // one work item = (class pair, leader, bin tile of 32, range of consecutive rel), laid out by the kernel from the leader count
+  // (ee2_table_map.hpp); a one-class batch (de novo sampling) has a quarter of the items live.  The grid gives each of those a wave of
+  // its own at the leader count that has the most of them
+  const int nt = cdiv(a.num_bins + 1, 32);
   const int cus = a.reserve_cus > 0 && a.reserve_cus < 248 ? (256 - a.reserve_cus) & ~7 : 256;
-  const int live = cdiv(n_groups * wpg, 8), grid = live < cus ? live : cus;
-  hipLaunchKernelGGL(kerns[kid], dim3(grid), dim3(EE2_THREADS), lds, st, a, (const char*)img, nt, wpg, rpw, n_items);
+  const int live = ee2_table_max_live_blocks(a.B, nt, a.n_rel), grid = live < cus ? live : cus;
+  hipLaunchKernelGGL(kerns[kid], dim3(grid), dim3(EE2_THREADS), lds, st, a, (const char*)img, nt, 0, 0, 0);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }
 
-// The spread: a wave takes SP_ROWS consecutive query rows against 32 keys, finds every pair's table row exactly as the pair kernel finds
-// its layer-1 rows (row_ids / Ee2Bins) and copies the row's records: the pair bias into the fragment order ipa_attn3 reads, pair_z into
-// the [row][j / 4][32 d][4 j] image, and (WZ) the z row itself.  a.row_idx, when set, receives the row of every pair.
+// The spread: a wave takes SP_ROWS consecutive query rows against 32 keys, finds every pair's table row (in the rows of the sample's
+// leader) exactly as the pair kernel finds its layer-1 rows (row_ids / Ee2Bins) and copies the row's records: the pair bias into the
+// fragment order ipa_attn3 reads, (WPZ) pair_z into the [row][j / 4][32 d][4 j] image, and (WZ) the z row itself.  a.row_idx, when set, receives the row of every pair.
 #define SP_THREADS 256
 #define SP_ROWS 4
-template <bool WZ>
+template <bool WZ, bool WPZ>
 __global__ __launch_bounds__(SP_THREADS) void ee2_spread_kernel(EdgeEmbedArgs a, int nt, int wpg, int n_items) {
   __shared__ float edg[64];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -633,6 +719,7 @@ __global__ __launch_bounds__(SP_THREADS) void ee2_spread_kernel(EdgeEmbedArgs a,
   for (int item = blockIdx.x * (SP_THREADS / 64) + wave; item < n_items; item += gridDim.x * (SP_THREADS / 64)) {
     const int grp = item / wpg, part = item - grp * wpg;
     const int b = grp / nt, jt = grp - b * nt, j0 = jt * 32;
+    const int lead = a.leaders[b];  // the sample whose rows b's pairs read
     const int i_first = part * SP_ROWS, i_end = (i_first + SP_ROWS < N) ? i_first + SP_ROWS : N;
     const int nvalid = N - j0 < 32 ? N - j0 : 32;
     const bool valid = li < nvalid;
@@ -647,7 +734,7 @@ __global__ __launch_bounds__(SP_THREADS) void ee2_spread_kernel(EdgeEmbedArgs a,
       const float msk = a.res_mask[bi] * mj;
       const int rel = si - sj + a.rel_off;
       const int bin = bins.of_pair(a.sc_ca[bi * 3], a.sc_ca[bi * 3 + 1], a.sc_ca[bi * 3 + 2], cj0, cj1, cj2);
-      const int row = b * tab.rps + (msk != 0.f ? ((2 * fi + fj) * a.n_rel + rel) * (nb + 1) + bin : tab.rps - 1);
+      const int row = lead * tab.rps + (msk != 0.f ? ((2 * fi + fj) * a.n_rel + rel) * (nb + 1) + bin : tab.rps - 1);
       if (a.row_idx && hi == 0 && valid) a.row_idx[bi * N + j] = row;
       {  // pair bias: 32 lanes = 32 consecutive keys of one head (128 B rows), heads 4 hi .. 4 hi + 3
         const f32x4 bv = *(const f32x4*)(tab.bias + (long)row * 8 + 4 * hi);
@@ -657,7 +744,7 @@ __global__ __launch_bounds__(SP_THREADS) void ee2_spread_kernel(EdgeEmbedArgs a,
           for (int r = 0; r < 4; ++r) bo[r * hstride] = bv[r];
         }
       }
-      {  // pair_z: lane (d = li, hi) writes the 4 keys of key group 2 g + hi
+      if constexpr (WPZ) {  // pair_z: lane (d = li, hi) writes the 4 keys of key group 2 g + hi
         half_t* pz_tile = a.pz_out + (bi * (N >> 2) + (j0 >> 2)) * 128;
         const unsigned short* tp = (const unsigned short*)tab.pz + li;
         unsigned short v[16];
@@ -684,11 +771,12 @@ __global__ __launch_bounds__(SP_THREADS) void ee2_spread_kernel(EdgeEmbedArgs a,
   }
 }
 int fd_edge_embed2_spread(const EdgeEmbedArgs& a, hipStream_t st, int write_z) {
-  if (!fd_edge_embed2_table_supported(a) || !a.table || !a.fixed_mask || !a.bias_out || !a.pz_out || (write_z && !a.z_out)) return FDIPT_EINVAL;
+  if (!fd_edge_embed2_table_supported(a) || !a.table || !a.leaders || !a.fixed_mask || !a.bias_out || (write_z && !a.z_out)) return FDIPT_EINVAL;
   const int nt = cdiv(a.N, 32), wpg = cdiv(a.N, SP_ROWS), n_items = a.B * nt * wpg;
   const int grid = cdiv(n_items, SP_THREADS / 64);
-  if (write_z) hipLaunchKernelGGL(ee2_spread_kernel<true>, dim3(grid), dim3(SP_THREADS), 0, st, a, nt, wpg, n_items);
-  else hipLaunchKernelGGL(ee2_spread_kernel<false>, dim3(grid), dim3(SP_THREADS), 0, st, a, nt, wpg, n_items);
+  typedef void (*kern_t)(EdgeEmbedArgs, int, int, int);
+  static const kern_t kerns[4] = {ee2_spread_kernel<false, false>, ee2_spread_kernel<false, true>, ee2_spread_kernel<true, false>, ee2_spread_kernel<true, true>};
+  hipLaunchKernelGGL(kerns[(write_z ? 2 : 0) + (a.pz_out ? 1 : 0)], dim3(grid), dim3(SP_THREADS), 0, st, a, nt, wpg, n_items);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }

@@ -46,6 +46,8 @@ struct EdgeEmbedArgs {
   const float* fixed_mask = nullptr;  // [B,N]: a residue's class is fixed_mask != 0
   void* table = nullptr;              // fd_ee2_table_bytes
   int32_t* row_idx = nullptr;         // [B,N,N] table row of every pair (written by the spread when set)
+  int32_t* leaders = nullptr;         // [B] the sample whose table rows sample b reads (fd_edge_embed2_leaders writes it)
+  const int32_t* rel_lead = nullptr;  // [B] the first sample whose rtab rows carry the bits of sample b's (fd_ee2_rel_leaders, once per setup)
 };
 
 struct AttnArgs {
@@ -88,6 +90,10 @@ struct OPairArgs {
   int off;
   L2Warm warm = {};  // weights of the kernel launched next (common.hpp: L2 warm-up hand-over)
   const half_t* pz = nullptr;  // round 6: pair_z image of this block (fd_pz_bytes) written by the producer of z -> opair_pz_kernel (z, wdz* unused)
+  // ... or (block 0 behind the edge embedder's row table) no image: the table row of every pair [B,N,N] and the rows' pair_z records
+  // [row][32] (fd_ee2_table_pz) -> opair_pzg_kernel gathers the records itself
+  const int32_t* pz_idx = nullptr;
+  const half_t* pz_rows = nullptr;
 };
 
 struct PointsArgs {
@@ -191,10 +197,18 @@ int fd_edge_embed2(const EdgeEmbedArgs& a, const void* img, hipStream_t st, int 
 // The row table of the embedder (models without aatype features): its output for a pair depends on (sample, fixed-mask bits of i and j,
 // rel, bin) only.  fd_edge_embed2_table evaluates every such row once (z row, pair bias, pair_z: a.table), fd_edge_embed2_spread copies
 // the records to the pairs (a.bias_out, a.pz_out and, write_z, a.z_out).  fd_edge_embed2_table_supported: scalars only (plan_forward)
+// The sample enters a row only through the Pi / Pj rows of its class representatives and its R rows, and a batch stepped at one t has
+// the same ones in every sample: fd_edge_embed2_leaders (first of the three launches) writes a.leaders[b] = the first sample b' <= b
+// whose Pi / Pj rows of b's classes and whose R rows are bit-identical to b's (b itself if there is none), on the device, from the
+// call's own inputs (the R rows are compared once, when fdipt_sample_setup makes them: a.rel_lead).  The table launch evaluates the rows
+// of leaders only, the spread points every pair into its leader's rows: both read the one array, so they cannot disagree.  A de novo batch of 8 has one leader, and its live rows (4.8 MB at N = 300) stay in L2.
 size_t fd_ee2_table_bytes(int B, int n_rel, int num_bins);
 int fd_edge_embed2_table_supported(const EdgeEmbedArgs& a);
+int fd_edge_embed2_leaders(const EdgeEmbedArgs& a, hipStream_t st);
+int fd_ee2_rel_leaders(int B, long row_floats, const float* rtab, int32_t* rel_lead, hipStream_t st);  // rtab [B, row_floats]
+const half_t* fd_ee2_table_pz(const void* table, int B, int n_rel, int num_bins);  // the pair_z records [row][32] inside a.table
 int fd_edge_embed2_table(const EdgeEmbedArgs& a, const void* img, hipStream_t st, int lo = 0);
-int fd_edge_embed2_spread(const EdgeEmbedArgs& a, hipStream_t st, int write_z);
+int fd_edge_embed2_spread(const EdgeEmbedArgs& a, hipStream_t st, int write_z);  // a.pz_out = NULL: no pair_z image (o_pair gathers the records)
 
 struct ProjArgs {
   int B, N, H, C, K, PT, Np;  // K = c_s, PT = point columns (3*H*Pq + 3*H*(Pq+Pv)), Np = keys padded to 32

@@ -148,7 +148,8 @@ static bool use_regpair(const FdiptDims* d) {
 // against N^2 pairs.  The static part of the predicate (dims, flags, shape) also decides the workspace region, which holds the four class
 // pairs of a table of up to ee_table_max_rel(N) relative positions (a single chain has 2 N - 1; chain breaks add their gaps).
 // EE_TABLE_CAP: bytes of one class pair's rows of the batch — the spread gathers them, so they should stay cache-resident next to the
-// streams it writes (c4: 39 MB, measured)
+// streams it writes (c4: 39 MB, measured).  Since the rows are shared among the samples of a group (one leader per group,
+// decided on the device: embed_stage) a batch stepped at one t touches one sample's worth of the region; the sizes stay those of B leaders
 #define EE_TABLE_ROW_BYTES 352
 #define EE_TABLE_CAP (64L << 20)
 static int ee_table_max_rel(int N) { return 5 * N / 2; }
@@ -582,9 +583,12 @@ int fdipt_model_prepare(const FdiptDims* d, const float* P, void* derived, fdipt
   return blob_walk(d, iv, L, P, (char*)derived, (hipStream_t)stream);
 }
 
+// `setup`: the R rows [B, n_rel, c_z] f32, then int32 [B]: the first sample whose R rows carry the bits of sample b's (the row table's
+// leader rule reads it every step instead of comparing the rows again: edge_embed2.hip)
+static size_t setup_rel_lead(const FdiptDims* dims, int B, int n_rel) { return al256((size_t)B * n_rel * dims->c_z * 4); }
 size_t fdipt_setup_bytes(const FdiptDims* dims, int B, int N, int n_rel) {
   if (!dims_ok(dims) || B <= 0 || N <= 0 || n_rel <= 0) return 0;
-  return al256((size_t)B * n_rel * dims->c_z * 4);
+  return setup_rel_lead(dims, B, n_rel) + al256((size_t)B * 4);
 }
 
 int fdipt_sample_setup(const FdiptDims* d, const float* P, const void* derived, int B, int N, int n_rel,
@@ -595,15 +599,16 @@ int fdipt_sample_setup(const FdiptDims* d, const float* P, const void* derived, 
   build_inventory(d, iv);
   blob_walk(d, iv, L);
   // R[b, r, :] = W1[:, 2*d1 : 2*d1+E] index_embedding(r - rel_off)   (fp32; constant along the trajectory)
-  return fd_linear(FDIPT_PREC_F32, B * n_rel, d->c_z, d->index_embed, rel_emb, d->index_embed,
-                   (const char*)derived + L.w1r, d->index_embed, nullptr, nullptr, 0, nullptr, 0, (float*)setup, d->c_z,
-                   (hipStream_t)stream);
+  RC(fd_linear(FDIPT_PREC_F32, B * n_rel, d->c_z, d->index_embed, rel_emb, d->index_embed,
+               (const char*)derived + L.w1r, d->index_embed, nullptr, nullptr, 0, nullptr, 0, (float*)setup, d->c_z,
+               (hipStream_t)stream));
+  return fd_ee2_rel_leaders(B, (long)n_rel * d->c_z, (const float*)setup, (int32_t*)((char*)setup + setup_rel_lead(d, B, n_rel)), (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ workspace
 struct WS {
   size_t node_feat, pte, pi, pj, h_a, h_b, node0, node, z, quat, trans, dmask, rot, proj, qp, kp, vp, bias, probs, feats,
-      ipa_out, tf_in, qkv, att, x_a, x_b, ff, e, upd, psi_un, a1, af, qb, kb, vt, pts, seqimg, ipa_parts, e_bf, vpt, r4, a1img, b1img, skip_all, vt_lo, kpf, pz, ee_tab, ee_idx, total;
+      ipa_out, tf_in, qkv, att, x_a, x_b, ff, e, upd, psi_un, a1, af, qb, kb, vt, pts, seqimg, ipa_parts, e_bf, vpt, r4, a1img, b1img, skip_all, vt_lo, kpf, pz, ee_tab, ee_idx, ee_lead, total;
 };
 static void build_ws(const FdiptDims* d, const Inventory& iv, const DLayout& L, int B, int N, WS& w) {
   size_t o = 0;
@@ -647,6 +652,7 @@ static void build_ws(const FdiptDims* d, const Inventory& iv, const DLayout& L, 
   w.pz = take(use_regpair(d) ? fd_pz_bytes(B, N) : 0);  // pair_z image of the current block (round 6: written by the producer of z)
   w.ee_tab = take(ee_table_static(d, B, N) ? fd_ee2_table_bytes(B, ee_table_max_rel(N), d->num_bins) : 0);  // the edge embedder's row table
   w.ee_idx = take(ee_table_static(d, B, N) ? NN * 4 : 0);  // ... and the table row of every pair (block 0's EdgeTransition gathers its z rows)
+  w.ee_lead = take((size_t)B * 4);  // ... and the leader of every sample (int32[B]: whose rows its pairs read; a few bytes, reserved whatever the shape)
   w.total = o;
 }
 
@@ -972,8 +978,14 @@ struct Fwd {
     }
     if (p.ee_table) {  // the distinct rows once, then their records to the pairs
       // z0 itself is never written: its only reader, block 0's EdgeTransition, gathers the rows from the table (edge_transition_stage)
-      ea.fixed_mask = a->fixed_mask; ea.table = W + w.ee_tab; ea.row_idx = (int32_t*)(W + w.ee_idx);
+      // Samples whose layer-1 rows are bit-identical (a batch stepped at one t) share one set of rows: the device decides who leads
+      // (w.ee_lead), the table launch evaluates the leaders' rows, the spread points every pair into its leader's rows.  The region
+      // stays sized for B leaders: the host does not know the grouping
+      ea.fixed_mask = a->fixed_mask; ea.table = W + w.ee_tab; ea.row_idx = (int32_t*)(W + w.ee_idx); ea.leaders = (int32_t*)(W + w.ee_lead);
+      ea.rel_lead = (const int32_t*)((const char*)setup + setup_rel_lead(d, B, a->n_rel));
+      RC(fd_edge_embed2_leaders(ea, st));
       RC(fd_edge_embed2_table(ea, D + (p.x ? L.ee2x : L.ee2), st, p.x));
+      ea.pz_out = nullptr;  // no pair_z image either: block 0's o_pair gathers the records through the row index (ipa_attend)
       RC(fd_edge_embed2_spread(ea, st, 0));
     } else if (p.regpair) RC(fd_edge_embed2(ea, D + (p.x ? L.ee2x : L.ee2), st, p.x));
     else RC(fd_edge_embed(op_precision(d), cz, ea, st));
@@ -1076,7 +1088,10 @@ struct Fwd {
     }
     if (p.pz) {  // (z itself may not have been stored)
       if (!oa.probs_h16) return FDIPT_EINVAL;
-      oa.pz = (const half_t*)(W + w.pz);
+      if (p.ee_table && b == 0) {  // the embedder wrote no image: the records of the (L2-resident) leaders' rows, by row index
+        oa.pz_idx = (const int32_t*)(W + w.ee_idx);
+        oa.pz_rows = fd_ee2_table_pz(W + w.ee_tab, B, a->n_rel, d->num_bins);
+      } else oa.pz = (const half_t*)(W + w.pz);
       return fd_opair_pz(oa, st);
     }
     return fd_opair(op_precision(d), oa, st, p.stream);
@@ -1409,6 +1424,18 @@ int64_t fdipt_embed_table_rows(const FdiptDims* d, int B, int N, int n_rel) {
   blob_walk(d, iv, L);
   const ForwardPlan p = plan_forward(d, iv, L, B, N, OP_ALL, n_rel, false, false);
   return p.ee_table && !p.refused ? (int64_t)n_rel * (d->num_bins + 1) : 0;
+}
+
+int fdipt_embed_table_leaders(const FdiptDims* d, const void* workspace, int B, int N, int n_rel, int32_t* out_dev) {
+  if (!workspace || !out_dev || fdipt_embed_table_rows(d, B, N, n_rel) <= 0) return FDIPT_EINVAL;
+  Inventory iv;
+  DLayout L;
+  WS w;
+  build_inventory(d, iv);
+  blob_walk(d, iv, L);
+  build_ws(d, iv, L, B, N, w);
+  if (hipDeviceSynchronize() != hipSuccess) return FDIPT_ELAUNCH;  // (a diagnostic entry: whatever stream the forward ran on)
+  return hipMemcpy(out_dev, (const char*)workspace + w.ee_lead, (size_t)B * 4, hipMemcpyDeviceToDevice) == hipSuccess ? FDIPT_OK : FDIPT_ELAUNCH;
 }
 
 int fdipt_score_forward(const FdiptDims* d, const float* P, const void* derived, const void* setup,

@@ -122,7 +122,9 @@ int fdipt_model_prepare(const FdiptDims* dims, const float* params_f32, void* de
  *   rel_emb [B,n_rel,index_embed] f32 = get_index_embedding(r - rel_off), r in [0,n_rel) — both evaluated
  *   by the host exactly as the reference does in float32 (framedipt/model/score_network.py:17-38).
  * Produces in `setup` the relative-position part of the first edge-embedder layer
- * (score_network.py:98-105,184-187 restructured: concat-free first layer). */
+ * (score_network.py:98-105,184-187 restructured: concat-free first layer), [B,n_rel,c_z] f32, and behind it int32 [B]: the first
+ * sample whose rows carry the same bits as sample b's (all zero when rel_emb is what is written above; the forward's row table reads
+ * it, see fdipt_embed_table_leaders).  A `setup` is used with the B and n_rel it was made for and is not edited in place. */
 size_t fdipt_setup_bytes(const FdiptDims* dims, int B, int N, int n_rel);
 int fdipt_sample_setup(const FdiptDims* dims, const float* params_f32, const void* derived, int B, int N, int n_rel,
                        const float* rel_emb, void* setup, fdipt_stream_t stream);
@@ -214,6 +216,13 @@ size_t fdipt_forward_workspace_bytes(const FdiptDims* dims, int B, int N);
  * n_rel > 5 N / 2, rows > N * N / 2, or more than 64 MB of rows (352 B each) in the batch.  On that path fixed_mask and res_mask must
  * hold 0 or 1. */
 int64_t fdipt_embed_table_rows(const FdiptDims* dims, int B, int N, int n_rel);
+/* On the table path samples whose first-layer rows carry the same bits share one set of table rows: sample b reads the rows of its
+ * leader, the first sample b' <= b that has every fixed-mask class b has and whose per-class first-layer rows (functions of t_emb[b]
+ * and the class) and relative-position rows (`setup`, compared by fdipt_sample_setup) are bit-identical to b's; b itself where
+ * there is none.  The forward decides this on the device from its own inputs (a batch stepped at one t has the single leader 0; per-sample t makes every sample lead).
+ * Copies the int32 [B] leaders the last forward of this shape left in `workspace` to out_dev (device memory), after a device
+ * synchronisation.  FDIPT_EINVAL where fdipt_embed_table_rows is 0. */
+int fdipt_embed_table_leaders(const FdiptDims* dims, const void* workspace, int B, int N, int n_rel, int32_t* out_dev);
 int fdipt_score_forward(const FdiptDims* dims, const float* params_f32, const void* derived, const void* setup,
                         const FdiptForwardArgs* args, void* workspace, size_t workspace_bytes, fdipt_stream_t stream);
 
