@@ -14,17 +14,25 @@ if [ -n "${FDIPT_CLEAN:-}" ]; then rm -f "$BUILD"/*.o "$OUT/$LIBNAME"; fi
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 # -Wno-inline-asm: the LDS-DMA helpers name m0 (a reserved register hipcc re-materialises before each of its own uses) as clobbered
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result -Wno-inline-asm $EXTRA"
+UNITS="gemm ipa_proj2 pair_mlp edge_embed2 edge_transition3 edge_transition4 attention attention3 pair_bias attention_seq chain rowblock frames select evaluate violations dssp sasa tmscore tmalign mpnn model"
 pids=()
 T0=$SECONDS
 NCOMP=0
-for f in gemm ipa_proj2 pair_mlp edge_embed2 edge_transition3 edge_transition4 attention attention3 pair_bias attention_seq chain rowblock frames select evaluate violations dssp sasa tmscore tmalign mpnn model; do
-  if [ ! -f "$BUILD/$f.o" ] || [ "$HERE/$f.hip" -nt "$BUILD/$f.o" ] || [ "$HERE/common.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/kernels.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/philox.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/horn.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/tmsearch.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/ee2_table_map.hpp" -nt "$BUILD/$f.o" ] || [ "$HERE/../../include/fdipt.h" -nt "$BUILD/$f.o" ]; then
+OBJS=()
+for f in $UNITS; do
+  OBJS+=("$BUILD/$f.o")
+  # stale: no object, or the unit, any header of csrc/ or the C ABI is newer than it
+  stale=
+  for src in "$HERE/$f.hip" "$HERE"/*.hpp "$HERE/../../include/fdipt.h"; do
+    if [ ! -f "$BUILD/$f.o" ] || [ "$src" -nt "$BUILD/$f.o" ]; then stale=1; break; fi
+  done
+  if [ -n "$stale" ]; then
     $HIPCC $FLAGS -c "$HERE/$f.hip" -o "$BUILD/$f.o" &
     pids+=($!)
     NCOMP=$((NCOMP + 1))
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIBNAME" "$BUILD"/{gemm,ipa_proj2,pair_mlp,edge_embed2,edge_transition3,edge_transition4,attention,attention3,pair_bias,attention_seq,chain,rowblock,frames,select,evaluate,violations,dssp,sasa,tmscore,tmalign,mpnn,model}.o
-echo "compiled $NCOMP of 22 units for gfx950 in $((SECONDS - T0)) s: $(cd "$BUILD" && ls *.o | tr '\n' ' ')"
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIBNAME" "${OBJS[@]}"
+echo "compiled $NCOMP of ${#OBJS[@]} units for gfx950 in $((SECONDS - T0)) s: $(cd "$BUILD" && ls *.o | tr '\n' ' ')"
 echo "built $OUT/$LIBNAME"

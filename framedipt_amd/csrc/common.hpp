@@ -334,6 +334,42 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ long long wave_sum_ll(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// The float64 analysis kernels (select, evaluate, violations, sasa) promise sums that do not depend on the batch and repeat bit for
+// bit: this is the one definition of their order.
+#define FD_WAVES (FD_THREADS / FD_WAVE)
+// sum of K values (double or long long) over a block of FD_THREADS, in every thread: butterfly inside a wave, lane 0 stores, then the
+// waves in index order; sh holds FD_WAVES * K values
+template <typename T, int K>
+__device__ __forceinline__ void fd_block_sum(T (&v)[K], T* sh) {
+  const int lane = threadIdx.x & (FD_WAVE - 1), wave = threadIdx.x / FD_WAVE;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if constexpr (std::is_same<T, double>::value) v[k] = wave_sum_d(v[k]);
+    else v[k] = wave_sum_ll(v[k]);
+    if (lane == 0) sh[wave * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    T acc = sh[k];
+#pragma unroll
+    for (int w = 1; w < FD_WAVES; ++w) acc += sh[w * K + k];
+    v[k] = acc;
+  }
+  __syncthreads();
+}
+// the value lane r holds (r wave-uniform), in every lane
+__device__ __forceinline__ double fd_readlane_d(double v, int r) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), r), hi = __builtin_amdgcn_readlane(__double2hiint(v), r);
+  return __hiloint2double(hi, lo);
+}
+// float offset of backbone atom a (BACKBONE_ATOMS order C, N, CA, O) inside a residue's 37 x 3 block
+__device__ __forceinline__ int fd_backbone_off(int a) { return a == 0 ? 6 : a == 1 ? 0 : a == 2 ? 3 : 12; }
 
 #define FD_CHECK_LAUNCH()                                   \
   do {                                                      \

@@ -16,29 +16,8 @@
 #include "common.hpp"
 #include "horn.hpp"
 
-#define EV_WAVES (FD_THREADS / FD_WAVE)
 #define EV_CA_CA 3.80209737096  // residue_constants.ca_ca
 #define EV_RAD2DEG 57.29577951308232
-
-// sum of K values over the block, in every thread: butterfly inside a wave, then the waves in index order
-template <int K>
-__device__ __forceinline__ void ev_block_sum(double (&v)[K], double* sh) {
-  const int lane = threadIdx.x & (FD_WAVE - 1), wave = threadIdx.x / FD_WAVE;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    v[k] = wave_sum_d(v[k]);
-    if (lane == 0) sh[wave * K + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double acc = sh[k];
-#pragma unroll
-    for (int w = 1; w < EV_WAVES; ++w) acc += sh[w * K + k];
-    v[k] = acc;
-  }
-  __syncthreads();
-}
 
 struct EvVec { double x, y, z; };
 __device__ __forceinline__ EvVec ev_load(const float* p) { return {(double)p[0], (double)p[1], (double)p[2]}; }
@@ -77,14 +56,12 @@ __device__ __forceinline__ double ev_signed_error(double a, double b) {
   if (fabs(c2) < fabs(best)) best = c2;
   return best;
 }
-// float offset of backbone atom a (BACKBONE_ATOMS order C, N, CA, O) inside a residue's 37 x 3 block
-__device__ __forceinline__ int ev_atom_off(int a) { return a == 0 ? 6 : a == 1 ? 0 : a == 2 ? 3 : 12; }
 // sum over the four backbone atoms of |x - y|^2 at one row
 __device__ __forceinline__ double ev_row_delta2(const float* x, const float* y) {
   double acc = 0.0;
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
-    const EvVec d = ev_sub(ev_load(x + ev_atom_off(a)), ev_load(y + ev_atom_off(a)));
+    const EvVec d = ev_sub(ev_load(x + fd_backbone_off(a)), ev_load(y + fd_backbone_off(a)));
     acc += ev_dot(d, d);
   }
   return acc;
@@ -117,9 +94,9 @@ __device__ void ev_reference_block(const FdiptEvalArgs& a, int r) {
 }
 
 __global__ __launch_bounds__(FD_THREADS) void evaluate_kernel(FdiptEvalArgs a) {
-  __shared__ double red[EV_WAVES * 9];
+  __shared__ double red[FD_WAVES * 9];
   __shared__ double rot_sh[12];  // R (row-major), then t
-  __shared__ int cnt[EV_WAVES], bad_sh, len_sh, nan_sh;
+  __shared__ int cnt[FD_WAVES], bad_sh, len_sh, nan_sh;
   __shared__ unsigned long long pairs_sh[2];  // pairs at distance > 0, clashes among them
   const int tid = threadIdx.x, lane = tid & (FD_WAVE - 1), wave = tid / FD_WAVE, N = a.N;
   if ((int)blockIdx.x >= a.B) {
@@ -179,7 +156,7 @@ __global__ __launch_bounds__(FD_THREADS) void evaluate_kernel(FdiptEvalArgs a) {
     a.res_bb_rmsd[(long)b * N + i] = v;
   }
   double* region_out = a.region_bb_rmsd + (long)b * a.max_regions;
-  for (int g = wave; g < G; g += EV_WAVES) {  // a wave per region: lane l takes rows first + l, first + l + 64, ...
+  for (int g = wave; g < G; g += FD_WAVES) {  // a wave per region: lane l takes rows first + l, first + l + 64, ...
     const int first = a.region_rows[2 * (g0 + g)], last = a.region_rows[2 * (g0 + g) + 1];
     double acc = 0.0;
     for (int i = first + lane; i <= last; i += FD_WAVE) acc += ev_row_delta2(x + (long)i * 111, y + (long)i * 111);
@@ -233,7 +210,7 @@ __global__ __launch_bounds__(FD_THREADS) void evaluate_kernel(FdiptEvalArgs a) {
     __syncthreads();
     int off = K, tot = 0;
 #pragma unroll
-    for (int v = 0; v < EV_WAVES; ++v) {
+    for (int v = 0; v < FD_WAVES; ++v) {
       if (v < wave) off += cnt[v];
       tot += cnt[v];
     }
@@ -255,9 +232,9 @@ __global__ __launch_bounds__(FD_THREADS) void evaluate_kernel(FdiptEvalArgs a) {
       bond[0] += fabs(dist - EV_CA_CA);
       bond[1] += dist < EV_CA_CA + 0.1 ? 1.0 : 0.0;
     }
-    ev_block_sum(bond, red);
+    fd_block_sum(bond, red);
     unsigned long long n_pos = 0ull, n_clash = 0ull;
-    for (int i = wave; i < K; i += EV_WAVES) {
+    for (int i = wave; i < K; i += FD_WAVES) {
       const EvVec pi = ev_load(ca + 3 * (long)i);
       for (int j = i + 1 + lane; j < K; j += FD_WAVE) {
         const EvVec d = ev_sub(pi, ev_load(ca + 3 * (long)j));
@@ -288,7 +265,7 @@ __global__ __launch_bounds__(FD_THREADS) void evaluate_kernel(FdiptEvalArgs a) {
       cen[6] += 1.0;
     }
   }
-  ev_block_sum(cen, red);
+  fd_block_sum(cen, red);
   const double M = cen[6], inv_m = M > 0.0 ? 1.0 / M : 0.0;
   const EvVec ca_c = {cen[0] * inv_m, cen[1] * inv_m, cen[2] * inv_m}, cb_c = {cen[3] * inv_m, cen[4] * inv_m, cen[5] * inv_m};
   double H[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // H = sum (a - ca)(b - cb)'
@@ -300,7 +277,7 @@ __global__ __launch_bounds__(FD_THREADS) void evaluate_kernel(FdiptEvalArgs a) {
       H[6] += p.z * q.x; H[7] += p.z * q.y; H[8] += p.z * q.z;
     }
   }
-  ev_block_sum(H, red);
+  fd_block_sum(H, red);
   if (tid == 0) {
     double R[9], top, second, scale;
     fd_horn_rotation(H, R, top, second, scale);  // (horn.hpp)
@@ -335,7 +312,7 @@ __global__ __launch_bounds__(FD_THREADS) void evaluate_kernel(FdiptEvalArgs a) {
       dev[1] += d2;
     }
   }
-  ev_block_sum(dev, red);
+  fd_block_sum(dev, red);
   if (tid == 0) {
     a.aligned_mean_dev[b] = dev[0] * inv_m;
     a.aligned_rmsd[b] = sqrt(dev[1] * inv_m);

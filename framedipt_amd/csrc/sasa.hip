@@ -42,15 +42,8 @@ __device__ __forceinline__ SaWs sa_ws(void* base, int B, int b, size_t M) {
   return w;
 }
 
-// the value lane `l` holds (l wave-uniform)
-__device__ __forceinline__ double sa_readlane(double v, int l) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
 __global__ __launch_bounds__(FD_THREADS) void sasa_compact_kernel(FdiptSasaArgs a) {
-  __shared__ int cnt_sh[FD_THREADS / FD_WAVE];
+  __shared__ int cnt_sh[FD_WAVES];
   const int tid = threadIdx.x, lane = tid & (FD_WAVE - 1), wave = tid / FD_WAVE, b = blockIdx.x;
   const long M = (long)a.N * a.atoms, e_base = (long)b * M;
   const SaWs w = sa_ws(a.workspace, a.B, b, (size_t)M);
@@ -67,7 +60,7 @@ __global__ __launch_bounds__(FD_THREADS) void sasa_compact_kernel(FdiptSasaArgs 
     __syncthreads();
     int before = 0, total = 0;
 #pragma unroll
-    for (int v = 0; v < FD_THREADS / FD_WAVE; ++v) {
+    for (int v = 0; v < FD_WAVES; ++v) {
       const int c = cnt_sh[v];
       before += v < wave ? c : 0;
       total += c;
@@ -90,7 +83,7 @@ template <int SLOTS>
 __global__ __launch_bounds__(FD_THREADS) void sasa_points_kernel(FdiptSasaArgs a) {
   const int lane = threadIdx.x & (FD_WAVE - 1), b = blockIdx.y;
   const int n = sa_counts(a.workspace)[b];
-  const long i = (long)blockIdx.x * (FD_THREADS / FD_WAVE) + threadIdx.x / FD_WAVE;
+  const long i = (long)blockIdx.x * FD_WAVES + threadIdx.x / FD_WAVE;
   if (i >= n) return;  // (whole waves leave; the kernel has no barrier)
   const long M = (long)a.N * a.atoms;
   const SaWs w = sa_ws(a.workspace, a.B, b, (size_t)M);
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(FD_THREADS) void sasa_points_kernel(FdiptSasaArgs a
     while (nbrs) {
       const int l = __ffsll((long long)nbrs) - 1;
       nbrs &= nbrs - 1;
-      const double cx = sa_readlane(xj, l), cy = sa_readlane(yj, l), cz = sa_readlane(zj, l), c2 = sa_readlane(r2j, l);
+      const double cx = fd_readlane_d(xj, l), cy = fd_readlane_d(yj, l), cz = fd_readlane_d(zj, l), c2 = fd_readlane_d(r2j, l);
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s) {
         const double dx = px[s] - cx, dy = py[s] - cy, dz = pz[s] - cz;
@@ -166,7 +159,7 @@ extern "C" int fdipt_sample_sasa(const FdiptSasaArgs* a, fdipt_stream_t stream) 
   const hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(sasa_compact_kernel, dim3((unsigned)a->B), dim3(FD_THREADS), 0, s, *a);
   FD_CHECK_LAUNCH();
-  const dim3 grid((unsigned)cdiv(M, FD_THREADS / FD_WAVE), (unsigned)a->B);
+  const dim3 grid((unsigned)cdiv(M, FD_WAVES), (unsigned)a->B);
   if (a->n_points <= 2 * FD_WAVE)
     hipLaunchKernelGGL(sasa_points_kernel<2>, grid, dim3(FD_THREADS), 0, s, *a);
   else

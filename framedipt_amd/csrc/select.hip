@@ -16,27 +16,19 @@
 
 #define SEL_S FDIPT_SELECT_MAX_SAMPLES
 #define SEL_LDG (SEL_S + 1)
-#define SEL_WAVES (FD_THREADS / FD_WAVE)
 
-// float offset of backbone atom a (BACKBONE_ATOMS order C, N, CA, O) inside a residue's 37 x 3 block
-__device__ __forceinline__ int sel_atom_off(int a) { return a == 0 ? 6 : a == 1 ? 0 : a == 2 ? 3 : 12; }
-// the value lane r holds (r wave-uniform), in every lane
-__device__ __forceinline__ double sel_lane(double v, int r) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), r), hi = __builtin_amdgcn_readlane(__double2hiint(v), r);
-  return __hiloint2double(hi, lo);
-}
 // lanes 0 .. S - 1 added in index order
 __device__ __forceinline__ double sel_ordered_sum(double v, int S) {
   double acc = 0.0;
-  for (int r = 0; r < S; ++r) acc += sel_lane(v, r);
+  for (int r = 0; r < S; ++r) acc += fd_readlane_d(v, r);
   return acc;
 }
 // index of the largest (sign = -1) / smallest (sign = +1) of lanes 0 .. S - 1; the lowest index wins on equality (np.argmax / argmin)
 __device__ __forceinline__ int sel_arg_best(double v, int S, double sign) {
-  double best = sign * sel_lane(v, 0);
+  double best = sign * fd_readlane_d(v, 0);
   int idx = 0;
   for (int r = 1; r < S; ++r) {
-    const double x = sign * sel_lane(v, r);
+    const double x = sign * fd_readlane_d(v, r);
     if (x < best) { best = x; idx = r; }
   }
   return idx;
@@ -46,7 +38,7 @@ __global__ __launch_bounds__(FD_THREADS) void select_kernel(FdiptSelectArgs a) {
   __shared__ double Gs[SEL_S * SEL_LDG];
   __shared__ double w_sh[SEL_S], dist_sh[2][SEL_S];
   __shared__ long mbase[SEL_S];  // float offset of every member's atom37 block
-  __shared__ int cnt[SEL_WAVES], hit_sh;
+  __shared__ int cnt[FD_WAVES], hit_sh;
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & (FD_WAVE - 1), wave = tid / FD_WAVE;
   const int N = a.N, L_max = a.L_max;
   const int b0 = a.group_start[g], S = a.group_start[g + 1] - b0;
@@ -74,7 +66,7 @@ __global__ __launch_bounds__(FD_THREADS) void select_kernel(FdiptSelectArgs a) {
       __syncthreads();
       int off = L, tot = 0;
 #pragma unroll
-      for (int v = 0; v < SEL_WAVES; ++v) {
+      for (int v = 0; v < FD_WAVES; ++v) {
         if (v < wave) off += cnt[v];
         tot += cnt[v];
       }
@@ -101,7 +93,7 @@ __global__ __launch_bounds__(FD_THREADS) void select_kernel(FdiptSelectArgs a) {
   // phase 1: mean (np.mean over the sample axis: the samples added in index order, one division)
   for (int m = tid; m < M; m += FD_THREADS) {
     const int l = m / 12, o = m - 12 * l;
-    const long k = (long)res[l] * 111 + sel_atom_off(o / 3) + o % 3;
+    const long k = (long)res[l] * 111 + fd_backbone_off(o / 3) + o % 3;
     double acc = 0.0;
     for (int s = 0; s < S; ++s) acc += (double)x[mbase[s] + k];
     mean[m] = acc / (double)S;
@@ -118,7 +110,7 @@ __global__ __launch_bounds__(FD_THREADS) void select_kernel(FdiptSelectArgs a) {
       const long k0 = (long)res[l] * 111;
 #pragma unroll
       for (int o = 0; o < 12; ++o) {
-        const long k = k0 + sel_atom_off(o / 3) + o % 3;
+        const long k = k0 + fd_backbone_off(o / 3) + o % 3;
         const double vs = (double)xs[k], vr = (double)xr[k], mu = mean[l * 12 + o], d = vs - vr;
         D = fma(d, d, D);
         Gv = fma(vs - mu, vr - mu, Gv);
@@ -148,12 +140,12 @@ __global__ __launch_bounds__(FD_THREADS) void select_kernel(FdiptSelectArgs a) {
       int r = 0;
       for (; r + 4 <= S; r += 4) {  // four LDS reads in flight (the compiler does not unroll around v_readlane); one chain in index order
         const double g0 = Grow[r], g1 = Grow[r + 1], g2 = Grow[r + 2], g3 = Grow[r + 3];
-        gw = fma(g0, sel_lane(w, r), gw);
-        gw = fma(g1, sel_lane(w, r + 1), gw);
-        gw = fma(g2, sel_lane(w, r + 2), gw);
-        gw = fma(g3, sel_lane(w, r + 3), gw);
+        gw = fma(g0, fd_readlane_d(w, r), gw);
+        gw = fma(g1, fd_readlane_d(w, r + 1), gw);
+        gw = fma(g2, fd_readlane_d(w, r + 2), gw);
+        gw = fma(g3, fd_readlane_d(w, r + 3), gw);
       }
-      for (; r < S; ++r) gw = fma(Grow[r], sel_lane(w, r), gw);
+      for (; r < S; ++r) gw = fma(Grow[r], fd_readlane_d(w, r), gw);
       const double wgw = sel_ordered_sum(w * gw, S);
       const double d = sqrt(fmax(gss - 2.0 * gw + wgw, 0.0));
       const unsigned long long zero = __ballot(act && d == 0.0);
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(FD_THREADS) void select_kernel(FdiptSelectArgs a) {
   const int hit = hit_sh;
   for (int m = tid; m < M; m += FD_THREADS) {
     const int l = m / 12, o = m - 12 * l;
-    const long k = (long)res[l] * 111 + sel_atom_off(o / 3) + o % 3;
+    const long k = (long)res[l] * 111 + fd_backbone_off(o / 3) + o % 3;
     const double mu = mean[m];
     double med;
     if (hit >= 0) {
@@ -197,12 +189,12 @@ __global__ __launch_bounds__(FD_THREADS) void select_kernel(FdiptSelectArgs a) {
   }
   __syncthreads();
   // get_closest_index: per sample the sum over atoms of the Euclidean distance to the reference point; a wave per sample
-  for (int s = wave; s < S; s += SEL_WAVES) {
+  for (int s = wave; s < S; s += FD_WAVES) {
     const float* xs = x + mbase[s];
     double pm = 0.0, pd = 0.0;
     for (int j = lane; j < 4 * L; j += FD_WAVE) {
       const int l = j >> 2, at = j & 3;
-      const float* p = xs + (long)res[l] * 111 + sel_atom_off(at);
+      const float* p = xs + (long)res[l] * 111 + fd_backbone_off(at);
       const double *mu = mean + j * 3, *md = median + j * 3;
       const double v0 = (double)p[0], v1 = (double)p[1], v2 = (double)p[2];
       const double a0 = v0 - mu[0], a1 = v1 - mu[1], a2 = v2 - mu[2], c0 = v0 - md[0], c1 = v1 - md[1], c2 = v2 - md[2];

@@ -4,7 +4,7 @@
 // radius of gyration, for B samples, all in float64.
 //
 // Two launches on one stream, nothing between them on the host:
-//   pair kernel    a block serves VI_WAVES rows of one sample, a wave per row i.  The existing rows j of the sample pass through LDS in
+//   pair kernel    a block serves FD_WAVES rows of one sample, a wave per row i.  The existing rows j of the sample pass through LDS in
 //                  tiles of VI_TILE; lane l takes j = l, l + 64, ... ascending, in BOTH directions (index[i] < index[j]: the pair (i, j),
 //                  index[j] < index[i]: the pair (j, i)), so every per-atom sum of row i is formed by this wave alone: each lane's terms
 //                  in ascending j, then a butterfly.  The wave writes row i's per-atom sums and flags, and to the workspace its sum of the
@@ -14,7 +14,6 @@
 // A row that does not exist is skipped; no floating-point atomics: rows appended behind a sample and its batch mates change no bit.
 #include "common.hpp"
 
-#define VI_WAVES (FD_THREADS / FD_WAVE)
 #define VI_TILE FD_THREADS
 
 // openfold/np/residue_constants.py.  van_der_waals_radius by element, in the atom order N, CA, C, CB, O
@@ -58,31 +57,6 @@ __device__ __forceinline__ double vi_radius(int a) { return a == 0 ? VI_R_N : a 
 // the reference's atom14 order of the five atoms (N, CA, C, O, CB) in atom37 columns: the order its within-residue sums run in
 __device__ __forceinline__ int vi_atom14(int k) { return k == 3 ? 4 : k == 4 ? 3 : k; }
 
-__device__ __forceinline__ long long vi_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double vi_wave_sum(double v) { return wave_sum_d(v); }
-// sum of K values over the block, in every thread: butterfly inside a wave, then the waves in index order
-template <typename T, int K>
-__device__ __forceinline__ void vi_block_sum(T (&v)[K], T* sh) {
-  const int lane = threadIdx.x & (FD_WAVE - 1), wave = threadIdx.x / FD_WAVE;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    v[k] = vi_wave_sum(v[k]);
-    if (lane == 0) sh[wave * K + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    T acc = sh[k];
-#pragma unroll
-    for (int w = 1; w < VI_WAVES; ++w) acc += sh[w * K + k];
-    v[k] = acc;
-  }
-  __syncthreads();
-}
 
 // the five atoms of row j of sample b (15 doubles), zero where the row does not keep its coordinates
 __device__ __forceinline__ void vi_load_row(const FdiptViolationArgs& a, long row, double (&x)[15]) {
@@ -101,7 +75,7 @@ __global__ __launch_bounds__(FD_THREADS) void violations_pair_kernel(FdiptViolat
   __shared__ int idx_sh[VI_TILE];
   __shared__ int exists_sh[VI_TILE];
   const int tid = threadIdx.x, lane = tid & (FD_WAVE - 1), wave = tid / FD_WAVE, N = a.N;
-  const int b = blockIdx.x / tiles, i = (blockIdx.x % tiles) * VI_WAVES + wave;
+  const int b = blockIdx.x / tiles, i = (blockIdx.x % tiles) * FD_WAVES + wave;
   const long row0 = (long)b * N;
   const bool mine = i < N && a.res_mask[row0 + (i < N ? i : 0)] != 0.f;  // (the same in every lane of a wave)
   double xi[15];
@@ -168,7 +142,7 @@ __global__ __launch_bounds__(FD_THREADS) void violations_pair_kernel(FdiptViolat
 #pragma unroll
   for (int p = 0; p < 5; ++p) loss[p] = wave_sum_d(loss[p]);
   err = wave_sum_d(err);
-  pairs = vi_wave_sum(pairs);
+  pairs = wave_sum_ll(pairs);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) flags |= __shfl_xor(flags, o, 64);
   if (lane == 0) {
@@ -215,8 +189,8 @@ __device__ __forceinline__ ViBond vi_bond(const double (&x)[15], const double (&
 }
 
 __global__ __launch_bounds__(FD_THREADS) void violations_reduce_kernel(FdiptViolationArgs a) {
-  __shared__ double red_d[VI_WAVES * 8];
-  __shared__ long long red_i[VI_WAVES * 8];
+  __shared__ double red_d[FD_WAVES * 8];
+  __shared__ long long red_i[FD_WAVES * 8];
   const int tid = threadIdx.x, N = a.N, b = blockIdx.x;
   const long row0 = (long)b * N;
   const float* rm = a.res_mask + row0;
@@ -306,8 +280,8 @@ __global__ __launch_bounds__(FD_THREADS) void violations_reduce_kernel(FdiptViol
     a.connections_per_residue_violation_mask[row0 + i] = conn_mask;
     a.total_per_residue_violations_mask[row0 + i] = total;
   }
-  vi_block_sum(fs, red_d);
-  vi_block_sum(is, red_i);
+  fd_block_sum(fs, red_d);
+  fd_block_sum(is, red_i);
   // radius of gyration: the deviations from the centroid, in the same order
   const double atoms = fs[7];
   const double cx = fs[4] / atoms, cy = fs[5] / atoms, cz = fs[6] / atoms;
@@ -322,7 +296,7 @@ __global__ __launch_bounds__(FD_THREADS) void violations_reduce_kernel(FdiptViol
       }
     }
   }
-  vi_block_sum(dev, red_d);
+  fd_block_sum(dev, red_d);
   if (tid == 0) {
     const double bonds = (double)is[0], rows = (double)is[2];
     a.bonds_c_n_loss_mean[b] = fs[0] / (bonds + 1e-6);
@@ -365,7 +339,7 @@ extern "C" int fdipt_sample_violations(const FdiptViolationArgs* a, fdipt_stream
       !a->total_per_residue_violations_mask || !a->clashes_per_atom_loss_sum || !a->clashes_per_atom_clash_mask ||
       !a->within_per_atom_loss_sum || !a->within_per_atom_violations || !a->workspace)
     return FDIPT_EINVAL;
-  const long tiles = cdiv(a->N, VI_WAVES);
+  const long tiles = cdiv(a->N, FD_WAVES);
   if (tiles * a->B > 0x7fffffffL) return FDIPT_ESIZE;
   if (a->workspace_bytes < fdipt_sample_violations_workspace(a->B, a->N)) return FDIPT_ESIZE;
   hipLaunchKernelGGL(violations_pair_kernel, dim3((unsigned)(tiles * a->B)), dim3(FD_THREADS), 0, (hipStream_t)stream, *a, (int)tiles);

@@ -16,11 +16,9 @@ A chain is a run of consecutive rows with ``res_mask != 0`` and one ``chain_idx`
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib, output
+from . import _call, _lib, output
 
 ANGLES = ("phi", "psi", "omega")  # order of the [.., 3, N] arrays
 DICT_ANGLES = ("psi", "omega", "phi")  # key order of the reference's dicts (calc_dihedrals)
@@ -32,24 +30,20 @@ SCALARS = ("bb_rmsd", "ca_ca_bond_dev", "ca_ca_valid_percent", "num_ca_steric_cl
 GEOMETRY_SCALARS = ("ca_ca_bond_dev", "ca_ca_valid_percent", "num_ca_steric_clashes", "ca_steric_clash_percent")
 
 
-def _host(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
 def plan_regions(diffuse_mask, chain_idx):
     """[(chain, first, last)]: the maximal runs of diffused residues per chain in the order of ``get_diffused_region_per_chain``
     (experiments/utils.py:629-687, restated once in framedipt_amd/output.py): chains numbered 0.. in np.unique order, indices local to
     the chain."""
-    chains, starts, ends = output.get_diffused_region_per_chain(_host(diffuse_mask).reshape(-1), _host(chain_idx).reshape(-1))
+    chains, starts, ends = output.get_diffused_region_per_chain(_call.host(diffuse_mask).reshape(-1), _call.host(chain_idx).reshape(-1))
     return [(int(c), int(s), int(e)) for c, s, e in zip(chains, starts, ends)]
 
 
 def region_rows(diffuse_mask, chain_idx, res_mask=None):
     """(regions, rows) of one sample: ``plan_regions`` over the rows of res_mask, and the absolute (first, last) row of every region.
     Raises ValueError for chains the kernel does not serve."""
-    diffuse = _host(diffuse_mask).reshape(-1) != 0
-    chain = _host(chain_idx).reshape(-1)
-    keep = np.ones(len(diffuse), dtype=bool) if res_mask is None else _host(res_mask).reshape(-1) != 0
+    diffuse = _call.host(diffuse_mask).reshape(-1) != 0
+    chain = _call.host(chain_idx).reshape(-1)
+    keep = np.ones(len(diffuse), dtype=bool) if res_mask is None else _call.host(res_mask).reshape(-1) != 0
     if not (len(chain) == len(diffuse) == len(keep)):
         raise ValueError(f"diffuse_mask, chain_idx and res_mask should have one length, got {len(diffuse)}, {len(chain)}, {len(keep)}")
     kept = np.nonzero(keep)[0]
@@ -64,13 +58,6 @@ def region_rows(diffuse_mask, chain_idx, res_mask=None):
     return regions, [(first_row[c] + s, first_row[c] + e) for c, s, e in regions]
 
 
-def _mask(x, shape, what):
-    x = _host(x)
-    if tuple(x.shape) != tuple(shape):
-        raise ValueError(f"{what} {tuple(x.shape)} does not match prot {tuple(shape)}")
-    return np.ascontiguousarray(x != 0, dtype=np.float32)
-
-
 def evaluate_samples(prot, reference, diffuse_mask, chain_idx=None, ref_index=None, res_mask=None, align_mask=None) -> dict:
     """prot [B,N,37,3] and reference [R,N,37,3] float32 (device tensors are used in place, NumPy arrays are uploaded), diffuse_mask
     [B,N]; chain_idx [B,N] (default: one chain), ref_index [B] (default: row 0 for R = 1, row b for R = B), res_mask [B,N] (default:
@@ -81,29 +68,20 @@ def evaluate_samples(prot, reference, diffuse_mask, chain_idx=None, ref_index=No
     sample the lists ``region_bb_rmsd`` ([G_b] float64), ``regions`` ((chain, first, last), chain-local as plan_regions) and
     ``region_rows`` ((first, last) rows).  A NaN dihedral raises ValueError as in the reference; a degenerate alignment (fewer than 3
     aligned rows, a covariance without a unique best rotation) only sets its ``status`` bit."""
-    if len(prot.shape) != 4 or tuple(prot.shape[2:]) != (37, 3):
-        raise ValueError(f"prot should be [B, N, 37, 3], got {tuple(prot.shape)}")
+    b, n, _ = _call.structure_shape(prot, atoms=(37,))
     if len(reference.shape) != 4 or tuple(reference.shape[1:]) != tuple(prot.shape[1:]) or reference.shape[0] < 1:
         raise ValueError(f"reference should be [R, N, 37, 3] with the N of prot {tuple(prot.shape)}, got {tuple(reference.shape)}")
-    b, n, r = int(prot.shape[0]), int(prot.shape[1]), int(reference.shape[0])
-    if b < 1 or n < 1:
-        raise ValueError(f"prot {tuple(prot.shape)}: no samples or no residues")
-    res = np.ones((b, n), dtype=np.float32) if res_mask is None else _mask(res_mask, (b, n), "res_mask")
-    diffuse = _mask(diffuse_mask, (b, n), "diffuse_mask") * res
-    align = res.copy() if align_mask is None else _mask(align_mask, (b, n), "align_mask")
-    if chain_idx is None:
-        chain = np.zeros((b, n), dtype=np.int32)
-    else:
-        chain = _host(chain_idx)
-        if tuple(chain.shape) != (b, n):
-            raise ValueError(f"chain_idx {tuple(chain.shape)} does not match prot {tuple(prot.shape)}")
-        chain = np.ascontiguousarray(np.rint(chain), dtype=np.int32)
+    r = int(reference.shape[0])
+    res = _call.per_row(res_mask, (b, n), "res_mask", "mask", default=1)
+    diffuse = _call.per_row(diffuse_mask, (b, n), "diffuse_mask", "mask") * res
+    align = res.copy() if align_mask is None else _call.per_row(align_mask, (b, n), "align_mask", "mask")
+    chain = _call.per_row(chain_idx, (b, n), "chain_idx", "int", default=0)
     if ref_index is None:
         if r not in (1, b):
             raise ValueError(f"ref_index is needed to map {b} samples to {r} reference structures")
         ref = np.zeros(b, dtype=np.int32) if r == 1 else np.arange(b, dtype=np.int32)
     else:
-        ref = np.ascontiguousarray(_host(ref_index).reshape(-1), dtype=np.int32)
+        ref = np.ascontiguousarray(_call.host(ref_index).reshape(-1), dtype=np.int32)
         if ref.shape[0] != b:
             raise ValueError(f"ref_index should hold one row per sample: {ref.shape[0]} for {b} samples")
         if ((ref < 0) | (ref >= r)).any():
@@ -117,44 +95,20 @@ def evaluate_samples(prot, reference, diffuse_mask, chain_idx=None, ref_index=No
     n_diffused = (diffuse != 0).sum(axis=1).astype(np.int32)
 
     import torch
-    lib = _lib.load()
-
-    def device_array(x, what):
-        if torch.is_tensor(x):
-            _lib.require_cuda(x, "evaluate_samples")
-            if x.dtype != torch.float32:
-                raise ValueError(f"{what} should be float32, got {x.dtype}")
-            return x.contiguous()
-        return None
-
-    x = device_array(prot, "prot")
-    y = device_array(reference, "reference")
-    dev = x.device if x is not None else y.device if y is not None else torch.device("cuda", torch.cuda.current_device())
-    with torch.cuda.device(dev):
-        up = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(dev)  # noqa: E731
-        if x is None:
-            x = up(np.asarray(prot, dtype=np.float32))
-        if y is None:
-            y = up(np.asarray(reference, dtype=np.float32))
-        if y.device != x.device:
-            raise ValueError(f"prot on {x.device}, reference on {y.device}")
-        d_ref, d_diffuse, d_res, d_align, d_chain, d_start = (up(v) for v in (ref, diffuse, res, align, chain, start))
-        d_table = up(table if len(table) else np.zeros((1, 2), dtype=np.int32))
-        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)  # noqa: E731
-        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
-        out = {"res_bb_rmsd": f64(b, n), "region_bb_rmsd": f64(b, max_regions), "bb_rmsd": f64(b), "dihedral": f64(b, 3, n),
-               "gt_dihedral": f64(r, 3, n), "angle_error": f64(b, 3, n), "ca_ca_bond_dev": f64(b), "ca_ca_valid_percent": f64(b),
-               "num_ca_steric_clashes": i32(b), "ca_steric_clash_percent": f64(b), "aligned_mean_dev": f64(b), "aligned_rmsd": f64(b),
-               "rotation": f64(b, 3, 3), "translation": f64(b, 3), "reflection": i32(b), "status": i32(b), "n_diffused": i32(b)}
-        ws_bytes = lib.fdipt_eval_workspace_bytes(b, n)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        p = _lib.ptr
-        args = _lib.EvalArgs(B=b, N=n, R=r, n_regions=len(table), max_regions=max_regions, atom37=p(x), ref37=p(y), ref_index=p(d_ref),
-                             diffuse_mask=p(d_diffuse), res_mask=p(d_res), align_mask=p(d_align), chain_idx=p(d_chain), region_start=p(d_start),
-                             region_rows=p(d_table), ref_index_host=ref.ctypes.data, region_start_host=start.ctypes.data,
-                             workspace=p(ws), workspace_bytes=ws_bytes, **{k: p(v) for k, v in out.items()})
-        _lib.check(lib.fdipt_sample_evaluate(C.byref(args), _lib.stream_ptr()), "fdipt_sample_evaluate")
-        out = {k: v.cpu().numpy() for k, v in out.items()}
+    dev, (x, y) = _call.upload("evaluate_samples", prot=prot, reference=reference)
+    per_sample, per_residue, int_per_sample = ("float64", (b,)), ("float64", (b, n)), ("int32", (b,))
+    outputs = {"res_bb_rmsd": per_residue, "region_bb_rmsd": ("float64", (b, max_regions)), "bb_rmsd": per_sample, "dihedral": ("float64", (b, 3, n)),
+               "gt_dihedral": ("float64", (r, 3, n)), "angle_error": ("float64", (b, 3, n)), "ca_ca_bond_dev": per_sample,
+               "ca_ca_valid_percent": per_sample, "num_ca_steric_clashes": int_per_sample, "ca_steric_clash_percent": per_sample,
+               "aligned_mean_dev": per_sample, "aligned_rmsd": per_sample, "rotation": ("float64", (b, 3, 3)), "translation": ("float64", (b, 3)),
+               "reflection": int_per_sample, "status": int_per_sample, "n_diffused": int_per_sample}
+    inputs = dict(ref_index=ref, diffuse_mask=diffuse, res_mask=res, align_mask=align, chain_idx=chain, region_start=start,
+                  region_rows=table if len(table) else np.zeros((1, 2), dtype=np.int32))
+    out = _call.run("fdipt_sample_evaluate", _lib.EvalArgs, dev,
+                    dict(B=b, N=n, R=r, n_regions=len(table), max_regions=max_regions, ref_index_host=ref.ctypes.data,
+                         region_start_host=start.ctypes.data),
+                    dict(atom37=x, ref37=y, **{k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in inputs.items()}),
+                    outputs, widen=("num_ca_steric_clashes", "reflection", "status"), workspace=("fdipt_eval_workspace_bytes", b, n))
     status, counted = out["status"], out.pop("n_diffused")
     if (status & SKIPPED).any() or not np.array_equal(counted, n_diffused):
         raise _lib.FdiptError(f"fdipt_sample_evaluate: the device counted {counted.tolist()} diffused residues per sample, the host "
@@ -163,8 +117,6 @@ def evaluate_samples(prot, reference, diffuse_mask, chain_idx=None, ref_index=No
         raise ValueError(f"Found NaN values in computed dihedral angles (samples {np.nonzero(status & NAN_DIHEDRAL)[0].tolist()}).")
     per_region = out["region_bb_rmsd"]
     out["region_bb_rmsd"] = [per_region[i, :len(rows[i])].copy() for i in range(b)]
-    for k in ("num_ca_steric_clashes", "reflection", "status"):
-        out[k] = out[k].astype(np.int64)
     out.update(regions=regions, region_rows=rows, ref_index=ref.astype(np.int64))
     return out
 

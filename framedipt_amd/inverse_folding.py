@@ -15,12 +15,11 @@ reference; ``aatype`` arrays are in this project's restype order (``output.RESTY
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 from .output import RESTYPES
 
 ALPHABET = "ACDEFGHIKLMNPQRSTVWYX"
@@ -314,39 +313,21 @@ class ProteinMPNN:
     # ---- inputs
     @staticmethod
     def _inputs(prot, res_mask, chain_mask, residue_index, chain_idx):
-        import torch
         if len(prot.shape) == 3:
             prot = prot[None]
-        if len(prot.shape) != 4 or tuple(prot.shape[2:]) not in ((37, 3), (5, 3)):
-            raise ValueError(f"prot should be [B, N, 37, 3] or [B, N, 5, 3], got {tuple(prot.shape)}")
-        b, n = int(prot.shape[0]), int(prot.shape[1])
-        if b < 1 or n < 1:
-            raise ValueError(f"prot {tuple(prot.shape)}: no backbones or no residues")
+        b, n, _ = _call.structure_shape(prot, items="backbones")
         if n > MAX_ROWS:
             raise ValueError(f"{n} rows: at most {MAX_ROWS}")
-        if torch.is_tensor(prot):
-            _lib.require_cuda(prot, "ProteinMPNN")
-            if prot.dtype != torch.float32:
-                raise ValueError(f"prot should be float32, got {prot.dtype}")
-            dev, x = prot.device, prot.contiguous()
-        else:
-            dev = torch.device("cuda", torch.cuda.current_device())
-            x = torch.from_numpy(np.ascontiguousarray(prot, dtype=np.float32)).to(dev)
+        dev, (x,) = _call.upload("ProteinMPNN", prot=prot)
 
-        def rows(v, default, dtype, what):
-            if v is None:
-                return default
-            v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-            v = v[None] if v.ndim == 1 else v
-            if v.shape != (b, n):
-                raise ValueError(f"{what} {v.shape} should be {(b, n)}")
-            return np.ascontiguousarray(v, dtype=dtype)
+        def rows(v, what, kind, default=None):  # (on the host: the planning of orders, ties and scores reads them; one backbone's [N] serves B = 1)
+            return _call.per_row(v[None] if v is not None and len(v.shape) == 1 else v, (b, n), what, kind, default)
 
-        res_mask = (rows(res_mask, np.ones((b, n), np.float32), np.float32, "res_mask") != 0).astype(np.float32)
-        chain_mask = (rows(chain_mask, np.ones((b, n), np.float32), np.float32, "chain_mask") != 0).astype(np.float32)
-        residue_index = rows(residue_index, np.tile(np.arange(n, dtype=np.int32), (b, 1)), np.int32, "residue_index")
-        chain_idx = rows(chain_idx, np.ones((b, n), np.int32), np.int32, "chain_idx")
-        return dev, x, b, n, res_mask, chain_mask, residue_index, chain_idx
+        residue_index = rows(residue_index, "residue_index", "int")
+        if residue_index is None:
+            residue_index = np.tile(np.arange(n, dtype=np.int32), (b, 1))
+        return (dev, x, b, n, rows(res_mask, "res_mask", "mask", 1), rows(chain_mask, "chain_mask", "mask", 1), residue_index,
+                rows(chain_idx, "chain_idx", "int", 1))
 
     @staticmethod
     def _per_sequence(v, b, m, n, dtype, what):
@@ -379,37 +360,25 @@ class ProteinMPNN:
 
     def _run(self, design, dev, x, b, n, m, res_mask, chain_mask, residue_index, chain_idx, S, order, u=None, omit=None, bias=None, temperature=1.0,
              controls=None, pssm_multi=0.0, unconditional=False):
-        """One call of fdipt_mpnn_design or fdipt_mpnn_score; NumPy outputs.  ``controls``: the optional arrays of FdiptMpnnArgs by field
+        """One call of fdipt_mpnn_design or fdipt_mpnn_score; NumPy outputs, the integer ones as int64.  ``controls``: the optional arrays of FdiptMpnnArgs by field
         name (None = absent).  ``unconditional``: the score entry's mode in which S and order are not read (pass None)."""
         import torch
-        lib = _lib.load()
         if m > MAX_SEQ:
             raise ValueError(f"{m} sequences per backbone: at most {MAX_SEQ}")
-        with torch.cuda.device(dev):
-            dims, k_eff = self.dims(), min(self.k_neighbors, n)
-
-            def up(v):
-                return None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(dev)
-
-            t = {k: up(v) for k, v in (("res_mask", res_mask), ("chain_mask", chain_mask), ("residue_index", residue_index), ("chain_idx", chain_idx),
-                                       ("S", None if S is None else S.astype(np.int32)),
-                                       ("decoding_order", None if order is None else order.astype(np.int32)), ("u", u), ("omit", omit), ("bias", bias))}
-            t.update({k: up(v) for k, v in (controls or {}).items()})
-            out = {"E_idx": torch.zeros((b, n, k_eff), dtype=torch.int32, device=dev), "status": torch.zeros((b,), dtype=torch.int32, device=dev)}
-            if design:
-                out["S_out"] = torch.zeros((b, m, n), dtype=torch.int32, device=dev)
-                out["probs"] = torch.zeros((b, m, n, VOCAB), dtype=torch.float32, device=dev)
-            else:
-                out["log_probs"] = torch.zeros((b, m, n, VOCAB), dtype=torch.float32, device=dev)
-            nbytes = int(lib.fdipt_mpnn_workspace(C.byref(dims), b, n, m))
-            work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            p = _lib.ptr
-            args = _lib.MpnnArgs(B=b, N=n, M=m, atoms=int(x.shape[2]), weights=p(self._weights_on(dev)), prot=p(x), temperature=float(temperature),
-                                 workspace=p(work), workspace_bytes=nbytes, pssm_multi=float(pssm_multi), unconditional=int(bool(unconditional)),
-                                 **{k: p(v) for k, v in t.items()}, **{k: p(v) for k, v in out.items()})
-            fn = lib.fdipt_mpnn_design if design else lib.fdipt_mpnn_score
-            _lib.check(fn(C.byref(dims), C.byref(args), _lib.stream_ptr()), "fdipt_mpnn_design" if design else "fdipt_mpnn_score")
-            return {k: v.cpu().numpy() for k, v in out.items()}
+        inputs = {"res_mask": res_mask, "chain_mask": chain_mask, "residue_index": residue_index, "chain_idx": chain_idx,
+                  "S": None if S is None else S.astype(np.int32), "decoding_order": None if order is None else order.astype(np.int32),
+                  "u": u, "omit": omit, "bias": bias, **(controls or {})}
+        inputs = {k: None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in inputs.items()}
+        outputs = {"E_idx": ("int32", (b, n, min(self.k_neighbors, n))), "status": ("int32", (b,))}
+        if design:
+            outputs.update(S_out=("int32", (b, m, n)), probs=("float32", (b, m, n, VOCAB)))
+        else:
+            outputs["log_probs"] = ("float32", (b, m, n, VOCAB))
+        return _call.run("fdipt_mpnn_design" if design else "fdipt_mpnn_score", _lib.MpnnArgs, dev,
+                         dict(B=b, N=n, M=m, atoms=int(x.shape[2]), temperature=float(temperature), pssm_multi=float(pssm_multi),
+                              unconditional=int(bool(unconditional))),
+                         dict(weights=self._weights_on(dev), prot=x, **inputs), outputs, widen=("E_idx", "status", "S_out"),
+                         workspace=("fdipt_mpnn_workspace", b, n, m), dims=self.dims())
 
     # ---- the two entry points
     def score(self, prot, S, res_mask=None, chain_mask=None, residue_index=None, chain_idx=None, decoding_order=None, seed=None) -> dict:
@@ -433,8 +402,8 @@ class ProteinMPNN:
         self._check_order(order, n)
         out = self._run(False, dev, x, b, n, m, res_mask, chain_mask, residue_index, chain_idx, S, order)
         return {"log_probs": out["log_probs"], "score": scores_of(out["log_probs"], S, (res_mask * chain_mask)[:, None]),
-                "global_score": scores_of(out["log_probs"], S, res_mask[:, None]), "E_idx": out["E_idx"].astype(np.int64), "decoding_order": order,
-                "status": out["status"].astype(np.int64)}
+                "global_score": scores_of(out["log_probs"], S, res_mask[:, None]), "E_idx": out["E_idx"], "decoding_order": order,
+                "status": out["status"]}
 
     def design(self, prot, num_seq: int = 8, temperature: float = 0.1, seed: int = 38, res_mask=None, chain_mask=None, aatype=None,
                residue_index=None, chain_idx=None, omit: str = "X", bias=None, decoding_order=None, u=None, bias_by_res=None, omit_mask=None,
@@ -500,7 +469,7 @@ class ProteinMPNN:
             raise ValueError("tied_beta without tied_positions")
         common = (dev, x, b, n, m, res_mask, chain_mask, residue_index, chain_idx)
         des = self._run(True, *common, S_in, order, u=u, omit=omit_v, bias=bias_v, temperature=temperature, controls=controls, pssm_multi=pssm_multi)
-        S = des["S_out"].astype(np.int64)
+        S = des["S_out"]
         rescored = self._run(False, *common, S, order)
         with np.errstate(invalid="ignore", divide="ignore"):
             recovery = (((S == S_in) * designed[:, None]).sum(-1) / designed.sum(-1)[:, None]).astype(np.float32)
@@ -509,7 +478,7 @@ class ProteinMPNN:
         return {"S": S, "aatype": mpnn_to_aatype(S), "sequences": [[mpnn_to_seq(S[i, j], res_mask[i]) for j in range(m)] for i in range(b)],
                 "probs": des["probs"], "log_probs": rescored["log_probs"], "decoding_order": order, "u": u,
                 "score": scores_of(rescored["log_probs"], S, designed[:, None]), "global_score": scores_of(rescored["log_probs"], S, res_mask[:, None]),
-                "seq_recovery": recovery, "E_idx": des["E_idx"].astype(np.int64), "status": (des["status"] | rescored["status"]).astype(np.int64),
+                "seq_recovery": recovery, "E_idx": des["E_idx"], "status": des["status"] | rescored["status"],
                 "S_input": s_in, "res_mask": res_mask, "chain_mask": chain_mask, "temperature": temperature, "seed": seed, "tie_group": tie_group.astype(np.int64)}
 
     def unconditional_probs(self, prot, res_mask=None, residue_index=None, chain_idx=None) -> dict:
@@ -517,7 +486,7 @@ class ProteinMPNN:
         Returns ``log_probs`` [B,N,21] (0 in rows without res_mask), ``E_idx``, ``status`` [B]."""
         dev, x, b, n, res_mask, chain_mask, residue_index, chain_idx = self._inputs(prot, res_mask, None, residue_index, chain_idx)
         out = self._run(False, dev, x, b, n, 1, res_mask, chain_mask, residue_index, chain_idx, None, None, unconditional=True)
-        return {"log_probs": out["log_probs"][:, 0], "E_idx": out["E_idx"].astype(np.int64), "status": out["status"].astype(np.int64)}
+        return {"log_probs": out["log_probs"][:, 0], "E_idx": out["E_idx"], "status": out["status"]}
 
     def conditional_probs(self, prot, S, res_mask=None, chain_mask=None, residue_index=None, chain_idx=None, backbone_only: bool = False, seed=None,
                           randn=None) -> dict:
@@ -550,7 +519,7 @@ class ProteinMPNN:
                     hot[torch.arange(len(c)), torch.from_numpy(c)] = 1.0
                     order[i, :len(c)] = torch.argsort(((1.0 - hot if backbone_only else hot) + 0.0001) * torch.abs(torch.from_numpy(randn[i]))[None], dim=-1).numpy()
             res = self._run(False, dev, x, b, n, m, res_mask, chain_mask, residue_index, chain_idx, np.repeat(S[:, None], m, axis=1), order)
-            status |= res["status"].astype(np.int64)
+            status |= res["status"]
             for i, c in enumerate(chunk):
                 out[i, c] = res["log_probs"][i, np.arange(len(c)), c]
         return {"log_probs": out, "randn": randn, "status": status}

@@ -13,11 +13,9 @@ numbers are pinned by that contract, a NumPy restatement and closed-form two-ato
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 from .data import features as F
 
 ATOM_RADII = {"N": 1.55, "C": 1.70, "O": 1.52, "S": 1.80}  # Angstrom, by element: the first letter of the atom37 name
@@ -62,11 +60,7 @@ def solvent_accessibility(prot, atom_mask=None, res_mask=None, aatype=None, prob
     (default: ``default_radii``).  All atoms of a sample that exist, of every chain, shield each other.  Returns NumPy arrays:
     ``accessible`` [B,N,A] int64, ``atom_sasa`` [B,N,A], ``residue_sasa`` [B,N], ``rsa`` [B,N] float64, ``n_atoms`` [B] int64 and
     ``total_sasa`` [B] = residue_sasa.sum(1).  The host does not wait for the device before the read-back."""
-    if len(prot.shape) != 4 or tuple(prot.shape[2:]) not in ((37, 3), (5, 3)):
-        raise ValueError(f"prot should be [B, N, 37, 3] or [B, N, 5, 3], got {tuple(prot.shape)}")
-    b, n, n_atoms = int(prot.shape[0]), int(prot.shape[1]), int(prot.shape[2])
-    if b < 1 or n < 1:
-        raise ValueError(f"prot {tuple(prot.shape)}: no samples or no residues")
+    b, n, n_atoms = _call.structure_shape(prot)
     n_points = int(n_points)
     sphere = sphere_points(n_points)
     reach = (default_radii(n_atoms) if radii is None else np.asarray(radii, dtype=np.float64)) + np.float64(probe_radius)
@@ -74,46 +68,20 @@ def solvent_accessibility(prot, atom_mask=None, res_mask=None, aatype=None, prob
         raise ValueError(f"radii should be {n_atoms} positive numbers (with the probe radius added), got {reach!r}")
 
     import torch
-    lib = _lib.load()
-    if torch.is_tensor(prot):
-        _lib.require_cuda(prot, "solvent_accessibility")
-        if prot.dtype != torch.float32:
-            raise ValueError(f"prot should be float32, got {prot.dtype}")
-        dev = prot.device
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-    def on_device(x, shape, what):
-        x = x.to(dev) if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        if tuple(x.shape) != shape:
-            raise ValueError(f"{what} {tuple(x.shape)} does not match prot {tuple(prot.shape)}")
-        return x
-
-    with torch.cuda.device(dev):
-        x = prot.contiguous() if torch.is_tensor(prot) else torch.from_numpy(np.ascontiguousarray(prot, dtype=np.float32)).to(dev)
-        atom = (x != 0).any(-1) if atom_mask is None else on_device(atom_mask, (b, n, n_atoms), "atom_mask") != 0
-        res = torch.ones((b, n), dtype=torch.float32, device=dev) if res_mask is None else (on_device(res_mask, (b, n), "res_mask") != 0).to(torch.float32)
-        if aatype is None:
-            largest = torch.full((b, n), float(MAX_SASA[0]), dtype=torch.float64, device=dev)
-        else:
-            kind = on_device(aatype, (b, n), "aatype")
-            kind = (torch.round(kind) if kind.is_floating_point() else kind).to(torch.int64)
-            table = torch.from_numpy(np.append(MAX_SASA, np.nan)).to(dev)
-            largest = table[torch.where((kind >= 0) & (kind < 20), kind, torch.full_like(kind, 20))]
-        zeros = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
-        out = dict(accessible=zeros(torch.int32, b, n, n_atoms), atom_sasa=zeros(torch.float64, b, n, n_atoms), residue_sasa=zeros(torch.float64, b, n),
-                   rsa=zeros(torch.float64, b, n), n_atoms=zeros(torch.int32, b))
-        ws_bytes = lib.fdipt_sample_sasa_workspace(b, n, n_atoms)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        held = dict(atom_mask=atom.to(torch.uint8).contiguous(), res_mask=res.contiguous(), atom_radius=torch.from_numpy(reach).to(dev),
-                    sphere=torch.from_numpy(sphere).to(dev), max_sasa=largest.contiguous())
-        p = _lib.ptr
-        args = _lib.SasaArgs(B=b, N=n, atoms=n_atoms, n_points=n_points, prot=p(x), workspace=p(ws), workspace_bytes=ws_bytes,
-                             **{k: p(v) for k, v in held.items()}, **{k: p(v) for k, v in out.items()})
-        _lib.check(lib.fdipt_sample_sasa(C.byref(args), _lib.stream_ptr()), "fdipt_sample_sasa")
-        out = {k: v.cpu().numpy() for k, v in out.items()}
-    for k in ("accessible", "n_atoms"):
-        out[k] = out[k].astype(np.int64)
+    dev, (x,) = _call.upload("solvent_accessibility", prot=prot)
+    atom = _call.per_row(atom_mask, (b, n, n_atoms), "atom_mask", dev=dev)
+    atom = (x != 0).any(-1) if atom is None else atom != 0
+    res = _call.per_row(res_mask, (b, n), "res_mask", "mask", default=1, dev=dev)
+    kind = _call.per_row(aatype, (b, n), "aatype", "int", default=0, dev=dev).to(torch.int64)
+    table = torch.from_numpy(np.append(MAX_SASA, np.nan)).to(dev)
+    largest = table[torch.where((kind >= 0) & (kind < 20), kind, torch.full_like(kind, 20))]
+    per_atom = (b, n, n_atoms)
+    out = _call.run("fdipt_sample_sasa", _lib.SasaArgs, dev, dict(B=b, N=n, atoms=n_atoms, n_points=n_points),
+                    dict(prot=x, atom_mask=atom.to(torch.uint8).contiguous(), res_mask=res, atom_radius=torch.from_numpy(reach).to(dev),
+                         sphere=torch.from_numpy(sphere).to(dev), max_sasa=largest.contiguous()),
+                    dict(accessible=("int32", per_atom), atom_sasa=("float64", per_atom), residue_sasa=("float64", (b, n)), rsa=("float64", (b, n)),
+                         n_atoms=("int32", (b,))),
+                    widen=("accessible", "n_atoms"), workspace=("fdipt_sample_sasa_workspace", b, n, n_atoms))
     out["total_sasa"] = out["residue_sasa"].sum(1)
     return out
 

@@ -15,11 +15,9 @@ deposited annotation of three complexes, not by ``md.compute_dssp`` itself.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 
 FRACTIONS = ("non_coil_percent", "coil_percent", "helix_percent", "strand_percent")  # calc_mdtraj_metrics' keys before radius_of_gyration
 COUNTS = ("n_rows", "n_hbonds", "n_bridges", "n_ladders", "status")
@@ -35,46 +33,20 @@ def secondary_structure(prot, res_mask=None, chain_idx=None, aatype=None) -> dic
     the PDB the reference writes.  Returns NumPy arrays: FRACTIONS [B] float64 (NaN without a row or with a status bit), COUNTS [B]
     int64, ``ss`` [B,N] uint8, ``acceptor`` [B,N,2] int64 (row index, -1: none), ``acceptor_energy`` [B,N,2] float64, and ``ss_string``, a
     list of B strings.  The host does not wait for the device before the read-back."""
-    if len(prot.shape) != 4 or tuple(prot.shape[2:]) not in ((37, 3), (5, 3)):
-        raise ValueError(f"prot should be [B, N, 37, 3] or [B, N, 5, 3], got {tuple(prot.shape)}")
-    b, n, n_atoms = int(prot.shape[0]), int(prot.shape[1]), int(prot.shape[2])
-    if b < 1 or n < 1:
-        raise ValueError(f"prot {tuple(prot.shape)}: no samples or no residues")
+    b, n, n_atoms = _call.structure_shape(prot)
 
     import torch
-    lib = _lib.load()
-    if torch.is_tensor(prot):
-        _lib.require_cuda(prot, "secondary_structure")
-        if prot.dtype != torch.float32:
-            raise ValueError(f"prot should be float32, got {prot.dtype}")
-        dev = prot.device
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-    def per_row(x, what):
-        x = x.to(dev) if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        if tuple(x.shape) != (b, n):
-            raise ValueError(f"{what} {tuple(x.shape)} does not match prot {tuple(prot.shape)}")
-        return torch.round(x) if x.is_floating_point() and what != "res_mask" else x
-
-    with torch.cuda.device(dev):
-        x = prot.contiguous() if torch.is_tensor(prot) else torch.from_numpy(np.ascontiguousarray(prot, dtype=np.float32)).to(dev)
-        res = torch.ones((b, n), dtype=torch.float32, device=dev) if res_mask is None else (per_row(res_mask, "res_mask") != 0).to(torch.float32)
-        chain = torch.zeros((b, n), dtype=torch.int32, device=dev) if chain_idx is None else per_row(chain_idx, "chain_idx").to(torch.int32).contiguous()
-        proline = torch.zeros((b, n), dtype=torch.uint8, device=dev) if aatype is None else (per_row(aatype, "aatype") == PRO).to(torch.uint8).contiguous()
-        zeros = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
-        out = {k: zeros(torch.float64, b) for k in FRACTIONS}
-        out.update({k: zeros(torch.int32, b) for k in COUNTS})
-        out.update(ss=zeros(torch.uint8, b, n), acceptor=zeros(torch.int32, b, n, 2), acceptor_energy=zeros(torch.float64, b, n, 2))
-        ws_bytes = lib.fdipt_sample_dssp_workspace(b, n)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        p = _lib.ptr
-        args = _lib.DsspArgs(B=b, N=n, atoms=n_atoms, prot=p(x), res_mask=p(res.contiguous()), chain_idx=p(chain), is_proline=p(proline),
-                             workspace=p(ws), workspace_bytes=ws_bytes, **{k: p(v) for k, v in out.items()})
-        _lib.check(lib.fdipt_sample_dssp(C.byref(args), _lib.stream_ptr()), "fdipt_sample_dssp")
-        out = {k: v.cpu().numpy() for k, v in out.items()}
-    for k in COUNTS + ("acceptor",):
-        out[k] = out[k].astype(np.int64)
+    dev, (x,) = _call.upload("secondary_structure", prot=prot)
+    res = _call.per_row(res_mask, (b, n), "res_mask", "mask", default=1, dev=dev)
+    chain = _call.per_row(chain_idx, (b, n), "chain_idx", "int", default=0, dev=dev)
+    kind = _call.per_row(aatype, (b, n), "aatype", "int", dev=dev)
+    proline = torch.zeros((b, n), dtype=torch.uint8, device=dev) if kind is None else (kind == PRO).to(torch.uint8)
+    outputs = {k: ("float64", (b,)) for k in FRACTIONS}
+    outputs.update({k: ("int32", (b,)) for k in COUNTS})
+    outputs.update(ss=("uint8", (b, n)), acceptor=("int32", (b, n, 2)), acceptor_energy=("float64", (b, n, 2)))
+    out = _call.run("fdipt_sample_dssp", _lib.DsspArgs, dev, dict(B=b, N=n, atoms=n_atoms),
+                    dict(prot=x, res_mask=res, chain_idx=chain, is_proline=proline), outputs, widen=COUNTS + ("acceptor",),
+                    workspace=("fdipt_sample_dssp_workspace", b, n))
     out["ss_string"] = ["".join(LETTERS[c] for c in row.tolist() if c != _lib.DSSP_ABSENT) for row in out["ss"]]
     return out
 

@@ -12,11 +12,9 @@ single sample), the iteration here stops and returns that sample as the median, 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 
 STRATEGIES = ("mean", "median", "mode", "mean_closest", "median_closest")
 BACKBONE_COLUMNS = (2, 0, 1, 4)  # atom37 columns of the reference's BACKBONE_ATOMS order C, N, CA, O
@@ -24,18 +22,14 @@ MAX_SAMPLES = _lib.SELECT_MAX_SAMPLES
 ZERO_DISTANCE, SKIPPED = _lib.SELECT_ZERO_DISTANCE, _lib.SELECT_SKIPPED
 
 
-def _host(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-
-
 def plan_groups(diffuse_mask, groups=None):
     """Host-side plan of a launch: (ids, members, residues) with one entry per group in order of first appearance - the group's id,
     its batch indices in batch order and the indices of its diffused residues.  Raises ValueError for what the kernel cannot serve."""
-    mask = _host(diffuse_mask) != 0
+    mask = _call.host(diffuse_mask) != 0
     if mask.ndim != 2:
         raise ValueError(f"diffuse_mask should be [B, N], got shape {mask.shape}")
     b = mask.shape[0]
-    groups = np.zeros(b, dtype=np.int64) if groups is None else _host(groups).reshape(-1)
+    groups = np.zeros(b, dtype=np.int64) if groups is None else _call.host(groups).reshape(-1)
     if groups.shape[0] != b:
         raise ValueError(f"groups should hold one id per sample: {groups.shape[0]} ids for {b} samples")
     ids, members, residues = [], [], []
@@ -62,57 +56,38 @@ def select_samples(prot, diffuse_mask, groups=None, sigma: float = 30.0, max_ite
     ``weights`` / ``density`` / ``dist_to_mean`` / ``dist_to_median`` [S] float64, ``residues`` [L], ``members`` [S] (batch indices),
     and int arrays [G] ``mode`` / ``mean_closest`` / ``median_closest`` (positions within the group) and ``status``; ``group_ids``
     names the groups in order."""
-    if tuple(prot.shape[2:]) != (37, 3) or len(prot.shape) != 4:
-        raise ValueError(f"prot should be [B, N, 37, 3], got {tuple(prot.shape)}")
-    if tuple(diffuse_mask.shape) != tuple(prot.shape[:2]):
-        raise ValueError(f"diffuse_mask {tuple(diffuse_mask.shape)} does not match prot {tuple(prot.shape)}")
+    b, n, _ = _call.structure_shape(prot, atoms=(37,))
+    mask = _call.per_row(diffuse_mask, (b, n), "diffuse_mask", "mask")
     if not sigma > 0 or max_iterations < 0:
         raise ValueError(f"sigma = {sigma}, max_iterations = {max_iterations}: expected sigma > 0 and max_iterations >= 0")
-    ids, members, residues = plan_groups(diffuse_mask, groups)
-
-    import torch
-    lib = _lib.load()
-    if torch.is_tensor(prot):
-        _lib.require_cuda(prot, "select_samples")
-        if prot.dtype != torch.float32:
-            raise ValueError(f"prot should be float32, got {prot.dtype}")
-        dev, x = prot.device, prot.contiguous()
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device())
-        x = torch.from_numpy(np.ascontiguousarray(prot, dtype=np.float32)).to(dev)
-    b, n = int(x.shape[0]), int(x.shape[1])
+    ids, members, residues = plan_groups(mask, groups)
     n_groups, l_max = len(ids), max(len(r) for r in residues)
     start = np.zeros(n_groups + 1, dtype=np.int32)
     start[1:] = np.cumsum([len(m) for m in members])
     n_diffused = np.array([len(r) for r in residues], dtype=np.int32)
-    with torch.cuda.device(dev):
-        mask = torch.as_tensor(_host(diffuse_mask) != 0, dtype=torch.float32).contiguous().to(dev)
-        d_start, d_member = torch.from_numpy(start).to(dev), torch.from_numpy(np.concatenate(members)).to(dev)
-        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)  # noqa: E731
-        mean, median = f64(n_groups, l_max, 4, 3), f64(n_groups, l_max, 4, 3)
-        per_sample = f64(4, b)  # weights, density, dist_to_mean, dist_to_median
-        index = torch.zeros((n_groups, 3), dtype=torch.int32, device=dev)
-        status, counted = (torch.zeros(n_groups, dtype=torch.int32, device=dev) for _ in range(2))
-        ws_bytes = lib.fdipt_select_workspace_bytes(n_groups, b, l_max)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        p = _lib.ptr
-        args = _lib.SelectArgs(
-            B=b, N=n, G=n_groups, L_max=l_max, atom37=p(x), diffuse_mask=p(mask), group_start=p(d_start), member=p(d_member),
-            group_start_host=start.ctypes.data, n_diffused_host=n_diffused.ctypes.data, sigma=float(sigma),
-            max_iterations=int(max_iterations), mean=p(mean), median=p(median), weights=p(per_sample[0]), density=p(per_sample[1]),
-            dist_to_mean=p(per_sample[2]), dist_to_median=p(per_sample[3]), index=p(index), status=p(status), n_diffused=p(counted),
-            workspace=p(ws), workspace_bytes=ws_bytes)
-        _lib.check(lib.fdipt_sample_select(C.byref(args), _lib.stream_ptr()), "fdipt_sample_select")
-        mean, median, per_sample, index, status, counted = (t.cpu().numpy() for t in (mean, median, per_sample, index, status, counted))
+
+    import torch
+    dev, (x,) = _call.upload("select_samples", prot=prot)
+    centre, per_sample, per_group = ("float64", (n_groups, l_max, 4, 3)), ("float64", (b,)), ("int32", (n_groups,))
+    out = _call.run(
+        "fdipt_sample_select", _lib.SelectArgs, dev,
+        dict(B=b, N=n, G=n_groups, L_max=l_max, group_start_host=start.ctypes.data, n_diffused_host=n_diffused.ctypes.data, sigma=float(sigma),
+             max_iterations=int(max_iterations)),
+        dict(atom37=x, diffuse_mask=torch.from_numpy(mask).to(dev), group_start=torch.from_numpy(start).to(dev),
+             member=torch.from_numpy(np.concatenate(members)).to(dev)),
+        dict(mean=centre, median=centre, weights=per_sample, density=per_sample, dist_to_mean=per_sample, dist_to_median=per_sample,
+             index=("int32", (n_groups, 3)), status=per_group, n_diffused=per_group),
+        widen=("index", "status"), workspace=("fdipt_select_workspace_bytes", n_groups, b, l_max))
+    mean, median, index, status, counted = (out[k] for k in ("mean", "median", "index", "status", "n_diffused"))
     if (status & SKIPPED).any() or not np.array_equal(counted, n_diffused):
         raise _lib.FdiptError(f"fdipt_sample_select: the device counted {counted.tolist()} diffused residues per group, the host "
                               f"{n_diffused.tolist()} (status {status.tolist()})")
     cut = lambda row: [row[start[g]:start[g + 1]].copy() for g in range(n_groups)]  # noqa: E731
     return {"mean": [mean[g, :n_diffused[g]].copy() for g in range(n_groups)],
             "median": [median[g, :n_diffused[g]].copy() for g in range(n_groups)],
-            "weights": cut(per_sample[0]), "density": cut(per_sample[1]), "dist_to_mean": cut(per_sample[2]),
-            "dist_to_median": cut(per_sample[3]), "mode": index[:, 0].astype(np.int64), "mean_closest": index[:, 1].astype(np.int64),
-            "median_closest": index[:, 2].astype(np.int64), "status": status.astype(np.int64), "residues": [r.astype(np.int64) for r in residues],
+            **{k: cut(out[k]) for k in ("weights", "density", "dist_to_mean", "dist_to_median")},
+            "mode": index[:, 0].copy(), "mean_closest": index[:, 1].copy(), "median_closest": index[:, 2].copy(), "status": status,
+            "residues": [r.astype(np.int64) for r in residues],
             "members": [m.astype(np.int64) for m in members], "group_ids": list(ids)}
 
 
@@ -129,7 +104,7 @@ def selected_structure(selection: dict, group: int, strategy: str, prot) -> np.n
     the group's first member with columns C, N, CA, O of the diffused residues replaced (``replace_coords``, sample_selection.py:535;
     CB and everything else stay the first member's, as in the reference)."""
     b = int(selection["members"][group][carrier(selection, group, strategy)])
-    out = np.array(_host(prot[b]), dtype=np.float32)
+    out = np.array(_call.host(prot[b]), dtype=np.float32)
     if strategy in ("mean", "median"):
         out[np.asarray(selection["residues"][group])[:, None], np.array(BACKBONE_COLUMNS)[None, :]] = selection[strategy][group]
     return out

@@ -12,12 +12,10 @@ correspondence score high here and low there.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from .tm_score import CA, all_pairs
+from . import _call, _lib
+from .tm_score import CA, all_pairs  # noqa: F401  (all_pairs: part of this module's interface)
 
 MAX_ROWS = _lib.TMA_MAX_ROWS
 OUTPUTS = ("tm", "tm_a", "tm_b", "rotation", "translation", "alignment", "n_aligned", "rmsd", "d0_a", "d0_b", "init_tm", "init_dp", "best_init", "status")
@@ -38,76 +36,29 @@ def tm_align(prot_a, prot_b=None, mask_a=None, mask_b=None, pairs=None, ref_inde
     (NaN with a status bit), ``rotation`` [P,3,3] and ``translation`` [P,3] (R x + t ~ y, x the first structure), ``alignment`` [P,N_b]
     (the row of the first structure aligned with each row of the second, or -1), ``n_aligned``, ``rmsd``, ``d0_a``, ``d0_b``,
     ``init_tm`` [P,3], ``init_dp`` [P,3], ``best_init``, ``status``, and ``pairs`` [P,2]."""
-    for name, x in (("prot_a", prot_a), ("prot_b", prot_b)):
-        if x is not None and (len(x.shape) != 4 or tuple(x.shape[2:]) not in ((37, 3), (5, 3))):
-            raise ValueError(f"{name} should be [S, N, 37, 3] or [S, N, 5, 3], got {tuple(x.shape)}")
-    s_a, n_a = int(prot_a.shape[0]), int(prot_a.shape[1])
-    if s_a < 1 or n_a < 1:
-        raise ValueError(f"prot_a {tuple(prot_a.shape)}: no structures or no residues")
-    s_b, n_b = (s_a, n_a) if prot_b is None else (int(prot_b.shape[0]), int(prot_b.shape[1]))
-    if s_b < 1 or n_b < 1:
-        raise ValueError(f"prot_b {tuple(prot_b.shape)}: no structures or no residues")
+    s_a, n_a, atoms_a = _call.structure_shape(prot_a, "prot_a", lead="S", items="structures")
+    s_b, n_b, atoms_b = (s_a, n_a, atoms_a) if prot_b is None else _call.structure_shape(prot_b, "prot_b", lead="S", items="structures")
     if prot_b is None and mask_b is not None:
         raise ValueError("mask_b without prot_b: the structures of prot_a carry mask_a")
-    square = prot_b is None and pairs is None and ref_index is None
-    if pairs is not None:
-        pair_list = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-    elif prot_b is None and ref_index is None:
-        pair_list = all_pairs(s_a)
-    else:
-        if ref_index is None:
-            if s_b not in (1, s_a):
-                raise ValueError(f"prot_b holds {s_b} structures for {s_a} samples: give ref_index or pairs")
-            ref_index = np.arange(s_a) if s_b == s_a and s_b > 1 else np.zeros(s_a)
-        pair_list = np.stack([np.arange(s_a), np.asarray(ref_index).reshape(s_a)], axis=1).astype(np.int32)
+    pair_list, square = _call.plan_pairs(s_a, s_b, prot_b is not None, pairs, ref_index)
     n_pairs = len(pair_list)
     shapes = {"rotation": (3, 3), "translation": (3,), "alignment": (n_b,), "init_tm": (3,), "init_dp": (3,)}
-
-    import torch
-    lib = _lib.load()
-    tensors = [x for x in (prot_a, prot_b) if torch.is_tensor(x)]
-    for x in tensors:
-        _lib.require_cuda(x, "tm_align")
-        if x.dtype != torch.float32:
-            raise ValueError(f"prot should be float32, got {x.dtype}")
-    dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
-
-    def structures(x):
-        return x.contiguous() if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-
-    def mask_of(m, s, n, what):
-        if m is None:
-            return torch.ones((s, n), dtype=torch.float32, device=dev)
-        m = m.to(dev) if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m)).to(dev)
-        if tuple(m.shape) != (s, n):
-            raise ValueError(f"{what} {tuple(m.shape)} should be {(s, n)}")
-        return (m != 0).to(torch.float32).contiguous()
-
+    outputs = {k: ("int32" if k in _INTS else "float64", (n_pairs,) + shapes.get(k, ())) for k in OUTPUTS}
     if n_pairs == 0:  # (one structure, all-against-all)
-        out = {k: np.zeros((0,) + shapes.get(k, ()), dtype=np.int64 if k in _INTS else np.float64) for k in OUTPUTS}
+        out = _call.empty_outputs(outputs, _INTS)
     else:
-        with torch.cuda.device(dev):
-            xa = structures(prot_a)
-            xb = None if prot_b is None else structures(prot_b)
-            ma = mask_of(mask_a, s_a, n_a, "mask_a")
-            mb = None if prot_b is None else mask_of(mask_b, s_b, n_b, "mask_b")
-            out = {k: torch.zeros((n_pairs,) + shapes.get(k, ()), dtype=torch.int32 if k in _INTS else torch.float64, device=dev) for k in OUTPUTS}
-            d_pairs = torch.from_numpy(pair_list).to(dev)
-            p = _lib.ptr
-            args = _lib.TmAlignArgs(S=s_a, N_a=n_a, atoms=int(prot_a.shape[2]), ca=CA, S_b=s_b, N_b=n_b,
-                                    atoms_b=int(prot_a.shape[2] if prot_b is None else prot_b.shape[2]), P=n_pairs, prot=p(xa), mask=p(ma),
-                                    prot_b=p(xb), mask_b=p(mb), pairs=p(d_pairs), workspace=None, workspace_bytes=0, **{k: p(v) for k, v in out.items()})
-            _lib.check(lib.fdipt_sample_tm_align(C.byref(args), _lib.stream_ptr()), "fdipt_sample_tm_align")
-            out = {k: v.cpu().numpy() for k, v in out.items()}
-        for k in _INTS:
-            out[k] = out[k].astype(np.int64)
+        import torch
+        dev, (xa, xb) = _call.upload("tm_align", prot_a=prot_a, prot_b=prot_b)
+        out = _call.run("fdipt_sample_tm_align", _lib.TmAlignArgs, dev,
+                        dict(S=s_a, N_a=n_a, atoms=atoms_a, ca=CA, S_b=s_b, N_b=n_b, atoms_b=atoms_b, P=n_pairs),
+                        dict(prot=xa, mask=_call.per_row(mask_a, (s_a, n_a), "mask_a", "mask", default=1, dev=dev), prot_b=xb,
+                             mask_b=None if prot_b is None else _call.per_row(mask_b, (s_b, n_b), "mask_b", "mask", default=1, dev=dev),
+                             pairs=torch.from_numpy(pair_list).to(dev)),
+                        outputs, widen=_INTS)
     out["pairs"] = pair_list.astype(np.int64)
     if square:
-        matrix = np.ones((s_a, s_a), dtype=np.float64)
-        matrix[pair_list[:, 0], pair_list[:, 1]] = matrix[pair_list[:, 1], pair_list[:, 0]] = out["tm_b"]
-        out["matrix"] = matrix
+        out["matrix"] = _call.square_matrix(s_a, pair_list, out["tm_b"])
     return out
-
 
 def tm_metrics(result: dict, p: int) -> dict:
     """The reference's ``{"tm_score": ...}`` entry of pair ``p`` of a ``tm_align`` result: ``calc_tm_score``'s second value, the score

@@ -14,21 +14,15 @@ all-against-all matrix it is a lower bound of TM-align's score, so the diversity
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
+from ._call import all_pairs  # noqa: F401  (part of this module's interface)
 
 CA = 1  # the CA column of atom37 and of the five-atom layout N, CA, C, CB, O
 MAX_ROWS = _lib.TM_MAX_ROWS
 OUTPUTS = ("tm", "rotation", "translation", "n_aligned", "d0", "best_seed", "passes", "status")
-
-
-def all_pairs(b: int) -> np.ndarray:
-    """[b (b - 1) / 2, 2] int32: every i < j, i-major."""
-    i, j = np.triu_indices(b, 1)
-    return np.stack([i, j], axis=1).astype(np.int32)
+_INTS = ("n_aligned", "best_seed", "passes", "status")
 
 
 def tm_scores(prot_a, prot_b=None, mask_a=None, mask_b=None, pairs=None, norm_length=None, ref_index=None) -> dict:
@@ -45,83 +39,32 @@ def tm_scores(prot_a, prot_b=None, mask_a=None, mask_b=None, pairs=None, norm_le
     Returns NumPy arrays per pair: ``tm`` float64 (NaN with a status bit), ``rotation`` [P,3,3] and ``translation`` [P,3] (R x + t ~ y,
     x the first structure), ``n_aligned``, ``best_seed``, ``passes``, ``status`` int64, ``d0`` float64, and ``pairs`` [P,2].  The
     host does not wait for the device before the read-back."""
-    for name, x in (("prot_a", prot_a), ("prot_b", prot_b)):
-        if x is not None and (len(x.shape) != 4 or tuple(x.shape[2:]) not in ((37, 3), (5, 3))):
-            raise ValueError(f"{name} should be [S, N, 37, 3] or [S, N, 5, 3], got {tuple(x.shape)}")
-    s_a, n = int(prot_a.shape[0]), int(prot_a.shape[1])
-    if s_a < 1 or n < 1:
-        raise ValueError(f"prot_a {tuple(prot_a.shape)}: no structures or no residues")
-    if prot_b is not None and int(prot_b.shape[1]) != n:
+    s_a, n, atoms_a = _call.structure_shape(prot_a, "prot_a", lead="S", items="structures")
+    s_b, n_b, atoms_b = (s_a, n, atoms_a) if prot_b is None else _call.structure_shape(prot_b, "prot_b", lead="S", items="structures")
+    if n_b != n:
         raise ValueError(f"prot_b {tuple(prot_b.shape)} does not have the {n} rows of prot_a")
-    s_b = s_a if prot_b is None else int(prot_b.shape[0])
-    square = prot_b is None and pairs is None and ref_index is None
-    if pairs is not None:
-        pair_list = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-    elif prot_b is None and ref_index is None:
-        pair_list = all_pairs(s_a)
-    else:
-        if ref_index is None:
-            if s_b not in (1, s_a):
-                raise ValueError(f"prot_b holds {s_b} structures for {s_a} samples: give ref_index or pairs")
-            ref_index = np.arange(s_a) if s_b == s_a and s_b > 1 else np.zeros(s_a)
-        pair_list = np.stack([np.arange(s_a), np.asarray(ref_index).reshape(s_a)], axis=1).astype(np.int32)
+    if prot_b is None and mask_b is not None:
+        raise ValueError("mask_b without prot_b: the structures of prot_a carry mask_a")
+    pair_list, square = _call.plan_pairs(s_a, s_b, prot_b is not None, pairs, ref_index)
     n_pairs = len(pair_list)
     if norm_length is not None:
         norm_length = np.broadcast_to(np.asarray(norm_length, dtype=np.int32), (n_pairs,)).copy()
-    empty = {"tm": np.zeros(0), "rotation": np.zeros((0, 3, 3)), "translation": np.zeros((0, 3)), "d0": np.zeros(0),
-             **{k: np.zeros(0, dtype=np.int64) for k in ("n_aligned", "best_seed", "passes", "status")}}
-
-    import torch
-    lib = _lib.load()
-    tensors = [x for x in (prot_a, prot_b) if torch.is_tensor(x)]
-    for x in tensors:
-        _lib.require_cuda(x, "tm_scores")
-        if x.dtype != torch.float32:
-            raise ValueError(f"prot should be float32, got {x.dtype}")
-    dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
-
-    def structures(x):
-        return x.contiguous() if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-
-    def mask_of(m, s, what):
-        if m is None:
-            return torch.ones((s, n), dtype=torch.float32, device=dev)
-        m = m.to(dev) if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m)).to(dev)
-        if tuple(m.shape) != (s, n):
-            raise ValueError(f"{what} {tuple(m.shape)} should be {(s, n)}")
-        return (m != 0).to(torch.float32).contiguous()
-
+    shapes = {"rotation": (3, 3), "translation": (3,)}
+    outputs = {k: ("int32" if k in _INTS else "float64", (n_pairs,) + shapes.get(k, ())) for k in OUTPUTS}
     if n_pairs == 0:  # (one structure, all-against-all)
-        out = empty
+        out = _call.empty_outputs(outputs, _INTS)
     else:
-        with torch.cuda.device(dev):
-            xa = structures(prot_a)
-            xb = None if prot_b is None else structures(prot_b)
-            ma = mask_of(mask_a, s_a, "mask_a")
-            mb = None if prot_b is None else mask_of(mask_b, s_b, "mask_b")
-            if prot_b is None and mask_b is not None:
-                raise ValueError("mask_b without prot_b: the structures of prot_a carry mask_a")
-            zeros = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
-            out = dict(tm=zeros(torch.float64, n_pairs), rotation=zeros(torch.float64, n_pairs, 3, 3), translation=zeros(torch.float64, n_pairs, 3),
-                       n_aligned=zeros(torch.int32, n_pairs), d0=zeros(torch.float64, n_pairs), best_seed=zeros(torch.int32, n_pairs),
-                       passes=zeros(torch.int32, n_pairs), status=zeros(torch.int32, n_pairs))
-            d_pairs = torch.from_numpy(pair_list).to(dev)
-            d_norm = None if norm_length is None else torch.from_numpy(norm_length).to(dev)
-            p = _lib.ptr
-            args = _lib.TmArgs(S=s_a, N=n, atoms=int(prot_a.shape[2]), ca=CA, S_b=s_b, atoms_b=int(prot_a.shape[2] if prot_b is None else prot_b.shape[2]),
-                               P=n_pairs, prot=p(xa), mask=p(ma), prot_b=p(xb), mask_b=p(mb), pairs=p(d_pairs), norm_length=p(d_norm),
-                               workspace=None, workspace_bytes=0, **{k: p(v) for k, v in out.items()})
-            _lib.check(lib.fdipt_sample_tm_score(C.byref(args), _lib.stream_ptr()), "fdipt_sample_tm_score")
-            out = {k: v.cpu().numpy() for k, v in out.items()}
-        for k in ("n_aligned", "best_seed", "passes", "status"):
-            out[k] = out[k].astype(np.int64)
+        import torch
+        dev, (xa, xb) = _call.upload("tm_scores", prot_a=prot_a, prot_b=prot_b)
+        out = _call.run("fdipt_sample_tm_score", _lib.TmArgs, dev, dict(S=s_a, N=n, atoms=atoms_a, ca=CA, S_b=s_b, atoms_b=atoms_b, P=n_pairs),
+                        dict(prot=xa, mask=_call.per_row(mask_a, (s_a, n), "mask_a", "mask", default=1, dev=dev), prot_b=xb,
+                             mask_b=None if prot_b is None else _call.per_row(mask_b, (s_b, n), "mask_b", "mask", default=1, dev=dev),
+                             pairs=torch.from_numpy(pair_list).to(dev), norm_length=None if norm_length is None else torch.from_numpy(norm_length).to(dev)),
+                        outputs, widen=_INTS)
     out["pairs"] = pair_list.astype(np.int64)
     if square:
-        matrix = np.ones((s_a, s_a), dtype=np.float64)
-        matrix[pair_list[:, 0], pair_list[:, 1]] = matrix[pair_list[:, 1], pair_list[:, 0]] = out["tm"]
-        out["matrix"] = matrix
+        out["matrix"] = _call.square_matrix(s_a, pair_list, out["tm"])
     return out
-
 
 def tm_metrics(result: dict, p: int) -> dict:
     """The reference's ``{"tm_score": ...}`` entry (protein_metrics, the self-consistency table) of pair ``p`` of a ``tm_scores`` result."""

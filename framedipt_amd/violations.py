@@ -20,7 +20,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 
 SCALARS = ("bonds_c_n_loss_mean", "angles_ca_c_n_loss_mean", "angles_c_n_ca_loss_mean", "clashes_mean_loss",
            "violations_extreme_ca_ca_distance", "violations_between_residue_bond", "violations_between_residue_clash",
@@ -58,61 +58,25 @@ def structural_violations(prot, diffuse_mask=None, res_mask=None, residue_index=
     their masks uint8.  The host does not wait for the device before the read-back."""
     if atoms not in ("diffused", "all"):
         raise ValueError(f"atoms should be 'diffused' or 'all', got {atoms!r}")
-    if len(prot.shape) != 4 or tuple(prot.shape[2:]) not in ((37, 3), (5, 3)):
-        raise ValueError(f"prot should be [B, N, 37, 3] or [B, N, 5, 3], got {tuple(prot.shape)}")
-    b, n, n_atoms = int(prot.shape[0]), int(prot.shape[1]), int(prot.shape[2])
-    if b < 1 or n < 1:
-        raise ValueError(f"prot {tuple(prot.shape)}: no samples or no residues")
+    b, n, n_atoms = _call.structure_shape(prot)
 
     import torch
-    lib = _lib.load()
-    if torch.is_tensor(prot):
-        _lib.require_cuda(prot, "structural_violations")
-        if prot.dtype != torch.float32:
-            raise ValueError(f"prot should be float32, got {prot.dtype}")
-        dev = prot.device
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-    def mask(x, what):
-        if x is None:
-            return torch.ones((b, n), dtype=torch.float32, device=dev)
-        x = x.to(dev) if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        if tuple(x.shape) != (b, n):
-            raise ValueError(f"{what} {tuple(x.shape)} does not match prot {tuple(prot.shape)}")
-        return (x != 0).to(torch.float32)
-
-    with torch.cuda.device(dev):
-        x = prot.contiguous() if torch.is_tensor(prot) else torch.from_numpy(np.ascontiguousarray(prot, dtype=np.float32)).to(dev)
-        res = mask(res_mask, "res_mask")
-        nonzero = (x[:, :, :5] != 0).flatten(2).any(dim=-1).to(torch.float32)  # (protein_metrics :149 on the atoms that exist)
-        keep = (nonzero if atoms == "all" else nonzero * mask(diffuse_mask, "diffuse_mask")).contiguous()
-        if residue_index is None:
-            index = torch.arange(n, dtype=torch.int32, device=dev).repeat(b, 1)
-        else:
-            index = residue_index.to(dev) if torch.is_tensor(residue_index) else torch.from_numpy(np.ascontiguousarray(residue_index)).to(dev)
-            if tuple(index.shape) != (b, n):
-                raise ValueError(f"residue_index {tuple(index.shape)} does not match prot {tuple(prot.shape)}")
-            if index.is_floating_point():
-                index = torch.round(index)
-            index = index.to(torch.int32).contiguous()
-        zeros = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
-        out = {k: zeros(torch.float64, b) for k in SCALARS}
-        out.update(num_residue_violations=zeros(torch.int32, b), n_clash_pairs=zeros(torch.int64, b))
-        out.update({k: zeros(torch.float64, b, n) for k in PER_RESIDUE})
-        out.update({k: zeros(torch.uint8, b, n) for k in PER_RESIDUE_MASKS})
-        out.update({k: zeros(torch.float64, b, n, 5) for k in PER_ATOM})
-        out.update({k: zeros(torch.uint8, b, n, 5) for k in PER_ATOM_MASKS})
-        ws_bytes = lib.fdipt_sample_violations_workspace(b, n)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        p = _lib.ptr
-        args = _lib.ViolationArgs(B=b, N=n, atoms=n_atoms, prot=p(x), res_mask=p(res), keep_mask=p(keep), residue_index=p(index),
-                                  workspace=p(ws), workspace_bytes=ws_bytes, **{k: p(v) for k, v in out.items()})
-        _lib.check(lib.fdipt_sample_violations(C.byref(args), _lib.stream_ptr()), "fdipt_sample_violations")
-        out = {k: v.cpu().numpy() for k, v in out.items()}
-    out["num_residue_violations"] = out["num_residue_violations"].astype(np.int64)
-    return out
-
+    dev, (x,) = _call.upload("structural_violations", prot=prot)
+    res = _call.per_row(res_mask, (b, n), "res_mask", "mask", default=1, dev=dev)
+    nonzero = (x[:, :, :5] != 0).flatten(2).any(dim=-1).to(torch.float32)  # (protein_metrics :149 on the atoms that exist)
+    keep = nonzero if atoms == "all" else nonzero * _call.per_row(diffuse_mask, (b, n), "diffuse_mask", "mask", default=1, dev=dev)
+    index = _call.per_row(residue_index, (b, n), "residue_index", "int", dev=dev)
+    if index is None:
+        index = torch.arange(n, dtype=torch.int32, device=dev).repeat(b, 1)
+    outputs = {k: ("float64", (b,)) for k in SCALARS}
+    outputs.update(num_residue_violations=("int32", (b,)), n_clash_pairs=("int64", (b,)))
+    outputs.update({k: ("float64", (b, n)) for k in PER_RESIDUE})
+    outputs.update({k: ("uint8", (b, n)) for k in PER_RESIDUE_MASKS})
+    outputs.update({k: ("float64", (b, n, 5)) for k in PER_ATOM})
+    outputs.update({k: ("uint8", (b, n, 5)) for k in PER_ATOM_MASKS})
+    return _call.run("fdipt_sample_violations", _lib.ViolationArgs, dev, dict(B=b, N=n, atoms=n_atoms),
+                     dict(prot=x, res_mask=res, keep_mask=keep.contiguous(), residue_index=index), outputs, widen=("num_residue_violations",),
+                     workspace=("fdipt_sample_violations_workspace", b, n))
 
 def violation_metrics(result: dict, b: int) -> dict:
     """The flat ``metrics_dict`` entries of ``protein_metrics`` for sample ``b``: METRIC_KEYS as Python floats."""
