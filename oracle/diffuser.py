@@ -1,7 +1,8 @@
 """ORACLE (test infrastructure, not product code): SE(3) diffuser in NumPy.
 
 CPU restatement of ``framedipt/diffusion/{so3,r3,se3}_diffuser.py`` for the
-functions on the sampler path.
+functions on the sampler path and
+on the confidence walk (row f4: ``forward``, ``step_log_prob_terms``, ``prior_log_prob``).
 Randomness is the global legacy ``np.random`` stream, consumed in the
 reference's order (SURVEY.md section 0 finding 10).  IGSO(3) table rows are computed on
 demand (the reference builds all 1000 rows at start-up, ``so3_diffuser.py:235-283``).
@@ -59,6 +60,25 @@ def torch_score_mixed(vec_f32: np.ndarray, sigma: float, eps: float = 1e-6, L: i
     ds = (w * num.astype(np.float64) / den.astype(np.float64)).sum(-1)
     sc = ds / (f + 1e-4)
     return sc[..., None] * vec.astype(np.float64) / omega.astype(np.float64)[..., None]
+
+
+def align_rotvec(inputs, targets):
+    """so3_diffuser.py:99-119: the rotation vector of ``inputs`` on the side of the ``targets`` axis — kept where the axes' dot product
+    is positive, otherwise (-axis, 2 pi - angle), the same rotation.  -> (aligned [*,3], dot [*]).  A zero vector gives NaN (0 / 0) and
+    a zero dot product gives 0, as NumPy does there."""
+    dtype = inputs.dtype.type
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ang = np.linalg.norm(inputs, axis=-1, keepdims=True)
+        axis = inputs / ang
+        dot = np.sum(targets / np.linalg.norm(targets, axis=-1, keepdims=True) * axis, axis=-1)
+        sign = np.sign(dot)[..., None]
+        return axis * sign * np.where(sign > 0, ang, 2 * dtype(np.pi) - ang), dot
+
+
+def normal_log_prob(x, mu, std):
+    """torch.distributions.Normal(mu, std).log_prob(x), in the type of ``x``."""
+    d = x - mu
+    return -(d * d) / (2 * std * std) - np.log(std) - np.log(np.sqrt(2 * x.dtype.type(np.pi)))
 
 
 class SO3Diffuser:
@@ -126,6 +146,13 @@ class SO3Diffuser:
             sig = self.discrete_sigma[self.t_to_idx(np.float64(F32(t[b])))]
             out[b] = torch_score_mixed(vec_f32[b], sig)
         return out
+
+    def coef_as(self, t, dtype=np.float64):
+        """``diffusion_coef`` with the schedule's float64 constants and ``t`` taken into ``dtype`` first (float64: the same value)."""
+        t = dtype(t)
+        emax, emin = np.exp(dtype(self.max_sigma)), np.exp(dtype(self.min_sigma))
+        sig = np.log(t * emax + (1 - t) * emin)
+        return np.sqrt(2 * (emax - emin) * sig / np.exp(sig))
 
     def reverse(self, rot_t, score_t, t, dt, noise_scale=1.0, z=None, orthogonalize=False):
         """so3_diffuser.py:569-602."""
@@ -271,6 +298,100 @@ class SE3Diffuser:
             rv1 = m * rv1 + (1 - m) * rv
         rot, tr1 = self._assemble(rv1, tr1)
         return rot, tr1.astype(F32)
+
+    # ------------------------------------------------ forward noising and the step log-probabilities (the confidence walk)
+    # The state between steps is (float32 rotation matrices, float32 translations): what _assemble leaves and _extract reads.
+    @staticmethod
+    def _mask_col(diffuse_mask, dtype):
+        return None if diffuse_mask is None else np.asarray(diffuse_mask).astype(dtype)[..., None]
+
+    def forward(self, rot_f32, trans_f32, t_1, dt, diffuse_mask, z_rot, z_trans, noise_scale=1.0, dtype=np.float64):
+        """se3_diffuser.py:50-95 with r3_diffuser.py:122-161 (center=False) and so3_diffuser.py:408-443, the N(0,1) draws given:
+        x_t ~ q(x_t | x_{t-1}).  rot [*,N,3,3] f32, trans [*,N,3] f32, mask [*,N] or None, z [*,N,3].
+        -> (rot f32, trans f32, rot64 = the matrices before the float32 cast).  ``dtype``: arithmetic of the rotation part."""
+        so3, r3 = self._so3_diffuser, self._r3_diffuser
+        cs = r3._conf.coordinate_scaling
+        m = self._mask_col(diffuse_mask, np.float64)
+        x0 = np.asarray(trans_f32, dtype=F32).astype(np.float64)
+        x = x0 * cs
+        bt = r3.b_t(t_1)
+        pert = (-0.5 * bt * x) * dt + np.sqrt(bt) * np.sqrt(dt) * (noise_scale * np.asarray(z_trans, dtype=np.float64))
+        if m is not None:
+            pert = pert * m
+        xt = (x + pert) / cs
+        if m is not None:
+            xt = m * xt + (1 - m) * x0
+        md = self._mask_col(diffuse_mask, dtype)
+        rot_f32 = np.asarray(rot_f32, dtype=F32)
+        rv1 = fr.scipy_from_matrix_as_rotvec(rot_f32, dtype=dtype)
+        p = so3.coef_as(t_1, dtype) * np.sqrt(dtype(dt)) * (dtype(noise_scale) * np.asarray(z_rot).astype(dtype))
+        if md is not None:
+            p = p * md
+        rvt = fr.compose_rotvec(rv1.reshape(-1, 3), p.reshape(-1, 3), dtype=dtype).reshape(rv1.shape)
+        if md is not None:
+            rvt = md * rvt + (1 - md) * rv1
+        rot64 = fr.scipy_from_rotvec_as_matrix(rvt, dtype)
+        return rot64.astype(F32), xt.astype(F32), rot64
+
+    def step_log_prob_terms(self, rot_t, trans_t, rot_1, trans_1, rot_score, trans_score, diffuse_mask, t, t_1, dt,
+                            dtype=np.float64, info=None):
+        """One step of the confidence walk: log p(x_{t-1} | x_t) under the scores at t and log q(x_t | x_{t-1}), translation and
+        rotation terms apart (se3_diffuser.py:97-196; r3_diffuser.py:163-260; so3_diffuser.py:466-567; r3_utils.py:10-42).
+
+        rot [B,N,3,3] f32, trans [B,N,3] f32, rot_score f64 / trans_score f32 [B,N,3] or both None, mask [B,N] or None.
+        -> (sums [B,4], rows [B,N,4]) in ``dtype``: columns backward trans, backward rot, forward trans, forward rot; ``rows`` holds each
+        residue's term (its three components added), 0 where ``mask == 0``; ``sums = rows.sum(1)``.  Without scores columns 0 and 1 are
+        0.  The mask enters three ways: rows with ``mask != 0`` are summed (``.bool()``), the forward translation mean and the rotation
+        drift are multiplied by its value, the backward translation mean is not (r3_diffuser.py:251-252 casts the mask to bool first).
+        ``info``: a dict that receives dot_backward / dot_forward (the align dot products), mu (the backward rotation mean), rv_t and
+        rv_1 (the rotation vectors of the two states) and selected (mask != 0)."""
+        if (rot_score is None) != (trans_score is None):
+            raise ValueError("step_log_prob_terms: the two scores go together")
+        so3, r3 = self._so3_diffuser, self._r3_diffuser
+        cs, sdt = dtype(r3._conf.coordinate_scaling), np.sqrt(dtype(dt))
+        rot_t, rot_1 = np.asarray(rot_t, dtype=F32), np.asarray(rot_1, dtype=F32)
+        B, N = rot_t.shape[:2]
+        sel = np.ones((B, N), dtype=bool) if diffuse_mask is None else np.asarray(diffuse_mask) != 0
+        m = dtype(1) if diffuse_mask is None else self._mask_col(diffuse_mask, dtype)
+        bt, bt1 = (dtype(r3.min_b) + dtype(s) * (dtype(r3.max_b) - dtype(r3.min_b)) for s in (t, t_1))
+        g, g1 = so3.coef_as(t, dtype), so3.coef_as(t_1, dtype)
+        xt, x1 = np.asarray(trans_t, dtype=F32).astype(dtype) * cs, np.asarray(trans_1, dtype=F32).astype(dtype) * cs
+        rvt = fr.scipy_from_matrix_as_rotvec(rot_t, dtype=dtype)
+        rv1 = fr.scipy_from_matrix_as_rotvec(rot_1, dtype=dtype)
+        rows = np.zeros((B, N, 4), dtype=dtype)
+        dot_b = mu_r = None
+        if rot_score is not None:
+            f = -0.5 * bt * xt
+            mu = xt - (f - bt * np.asarray(trans_score, dtype=F32).astype(dtype)) * dtype(dt)
+            rows[..., 0] = normal_log_prob(x1, mu, np.sqrt(bt) * sdt).sum(-1)
+            drift = g * g * np.asarray(rot_score).astype(dtype) * dtype(dt) * m
+            mu_r = fr.compose_rotvec(rvt.reshape(-1, 3), drift.reshape(-1, 3), dtype=dtype).reshape(rvt.shape)
+            al, dot_b = align_rotvec(rv1, mu_r)
+            rows[..., 1] = normal_log_prob(al, mu_r, g * sdt).sum(-1)
+        muf = (x1 + (-0.5 * bt1 * x1) * dtype(dt)) * m
+        rows[..., 2] = normal_log_prob(xt, muf, np.sqrt(bt1) * sdt).sum(-1)
+        al, dot_f = align_rotvec(rvt, rv1)
+        rows[..., 3] = normal_log_prob(al, rv1, g1 * sdt).sum(-1)
+        rows = np.where(sel[..., None], rows, dtype(0))  # torch.masked_select: an unselected row (NaN after align, if its vector is 0) leaves
+        if info is not None:
+            info.update(dot_backward=dot_b, dot_forward=dot_f, mu=mu_r, rv_t=rvt, rv_1=rv1, selected=sel)
+        return rows.sum(axis=1), rows
+
+    def prior_log_prob(self, trans_T_f32, diffuse_mask, dtype=np.float64):
+        """The terminal term of the confidence score (experiments/utils.py:846-866): the standard-normal log density of the scaled x_T
+        translations over the diffused residues, element by element in float32 as torch has it there, and log(1 / pi^2) per unit of the
+        mask's sum.  trans [B,N,3] f32, mask [B,N] or None -> (out [B,2] in ``dtype`` = {trans, rot}, terms [B,N,3] f32, 0 where
+        ``mask == 0``)."""
+        x = np.asarray(trans_T_f32, dtype=F32) * F32(self._r3_diffuser._conf.coordinate_scaling)
+        terms = -(x * x) / F32(2) - F32(0.91893853320467274178)
+        B, N = x.shape[:2]
+        if diffuse_mask is None:
+            n_diffused = np.full(B, N, dtype=dtype)
+        else:
+            terms = np.where((np.asarray(diffuse_mask) != 0)[..., None], terms, F32(0))
+            n_diffused = np.asarray(diffuse_mask).astype(dtype).sum(axis=-1)
+        out = np.stack([terms.astype(dtype).sum(axis=(1, 2)), np.log(1 / dtype(np.pi) ** 2) * n_diffused], axis=-1)
+        return out, terms
 
     def calc_rot_score(self, quats_t, quats_0, t):
         """se3_diffuser.py:281-292 (float32 quaternion algebra, float64 score)."""

@@ -161,9 +161,13 @@ def quat_to_rotvec(quat: np.ndarray, eps: float = 1e-6) -> np.ndarray:
 
 
 # ------------------------------------------------ SciPy Rotation conventions
-def scipy_from_rotvec_as_matrix(rv: np.ndarray) -> np.ndarray:
-    """Rotation.from_rotvec(rv).as_matrix() (SciPy _rotation.pyx), float64."""
-    rv = np.asarray(rv, dtype=np.float64)
+def scipy_from_rotvec_as_matrix(rv: np.ndarray, dtype=np.float64) -> np.ndarray:
+    """Rotation.from_rotvec(rv).as_matrix() (SciPy _rotation.pyx), float64.
+
+    ``dtype`` (here and on the three functions below): the arithmetic type, float64 as SciPy has it; ``np.longdouble`` evaluates the
+    same formulas with a wider significand, which is how the tests measure the rounding error of the float64 chain itself.
+    """
+    rv = np.asarray(rv, dtype=dtype)
     th = np.linalg.norm(rv, axis=-1)
     th2 = th * th
     small = th <= 1e-3
@@ -172,7 +176,7 @@ def scipy_from_rotvec_as_matrix(rv: np.ndarray) -> np.ndarray:
     x, y, z = (scale * rv[..., i] for i in range(3))
     w = np.cos(th / 2)
     # SciPy normalises in from_rotvec? No: the quaternion is unit by construction.
-    r = np.empty(rv.shape[:-1] + (3, 3))
+    r = np.empty(rv.shape[:-1] + (3, 3), dtype=dtype)
     x2, y2, z2, w2 = x * x, y * y, z * z, w * w
     xy, zw, xz, yw, yz, xw = x * y, z * w, x * z, y * w, y * z, x * w
     r[..., 0, 0] = x2 - y2 - z2 + w2
@@ -187,20 +191,20 @@ def scipy_from_rotvec_as_matrix(rv: np.ndarray) -> np.ndarray:
     return r
 
 
-def markley_quat(m: np.ndarray):
+def markley_quat(m: np.ndarray, dtype=np.float64):
     """Rotation.from_matrix of SciPy 1.7.3 up to the quaternion: (q [*,4] scalar-last, unit, sign as computed; branch [*]).
 
     branch = argmax(m00, m11, m22, trace), the first maximum on ties (NumPy's argmax, as SciPy calls it); 3 = the trace branch.
     """
-    m = np.asarray(m, dtype=np.float64)
+    m = np.asarray(m, dtype=dtype)
     shp = m.shape[:-2]
     m = m.reshape(-1, 3, 3)
     n = m.shape[0]
-    dec = np.empty((n, 4))
+    dec = np.empty((n, 4), dtype=dtype)
     dec[:, 0], dec[:, 1], dec[:, 2] = m[:, 0, 0], m[:, 1, 1], m[:, 2, 2]
     dec[:, 3] = dec[:, 0] + dec[:, 1] + dec[:, 2]
     ch = dec.argmax(axis=1)
-    q = np.empty((n, 4))  # scalar-last
+    q = np.empty((n, 4), dtype=dtype)  # scalar-last
     idx = np.nonzero(ch != 3)[0]
     i = ch[idx]
     j = (i + 1) % 3
@@ -218,13 +222,13 @@ def markley_quat(m: np.ndarray):
     return q.reshape(shp + (4,)), ch.reshape(shp)
 
 
-def scipy_from_matrix_as_rotvec(m: np.ndarray, orthogonalize: bool = False) -> np.ndarray:
+def scipy_from_matrix_as_rotvec(m: np.ndarray, orthogonalize: bool = False, dtype=np.float64) -> np.ndarray:
     """Rotation.from_matrix(m).as_rotvec(): Markley quaternion, then log map (float64).
 
     ``orthogonalize=True`` adds the SVD projection SciPy >= 1.8 applies first
     (the oracle container has 1.15.3; the reference pins 1.7.3 which does not).
     """
-    m = np.asarray(m, dtype=np.float64)
+    m = np.asarray(m, dtype=dtype)
     if orthogonalize:
         u, _, vt = np.linalg.svd(m)
         det = np.linalg.det(u @ vt)
@@ -232,7 +236,7 @@ def scipy_from_matrix_as_rotvec(m: np.ndarray, orthogonalize: bool = False) -> n
         u[..., :, 2] *= det[..., None]
         m = u @ vt
     shp = m.shape[:-2]
-    q, _ = markley_quat(m)
+    q, _ = markley_quat(m, dtype)
     q = q.reshape(-1, 4)
     q = np.where(q[:, 3:4] < 0, -q, q)
     ang = 2 * np.arctan2(np.linalg.norm(q[:, :3], axis=1), q[:, 3])
@@ -243,10 +247,10 @@ def scipy_from_matrix_as_rotvec(m: np.ndarray, orthogonalize: bool = False) -> n
     return (scale[:, None] * q[:, :3]).reshape(shp + (3,))
 
 
-def compose_rotvec(r1: np.ndarray, r2: np.ndarray, orthogonalize: bool = False) -> np.ndarray:
+def compose_rotvec(r1: np.ndarray, r2: np.ndarray, orthogonalize: bool = False, dtype=np.float64) -> np.ndarray:
     """framedipt/data/transforms.py:33-46: log(exp(r1) exp(r2))."""
-    c = np.einsum("...ij,...jk->...ik", scipy_from_rotvec_as_matrix(r1), scipy_from_rotvec_as_matrix(r2))
-    return scipy_from_matrix_as_rotvec(c, orthogonalize)
+    c = np.einsum("...ij,...jk->...ik", scipy_from_rotvec_as_matrix(r1, dtype), scipy_from_rotvec_as_matrix(r2, dtype))
+    return scipy_from_matrix_as_rotvec(c, orthogonalize, dtype)
 
 
 # ------------------------------------------------ geomstats-fork SO(3) maps

@@ -46,8 +46,8 @@ def test_forward_noising_and_step_log_probs_teacher_forced(name):
                                      dev(G["step_trans_score"][i][None].astype(np.float32)), mask, float(G["step_t"][i]), float(t_1),
                                      dt).cpu().numpy()[0]
         lpb, lpf = float(G["step_lp_backward"][i]), float(G["step_lp_forward"][i])
-        assert abs(out[0] + out[1] - lpb) <= 2e-5 * max(abs(lpb), 1.0), (i, out, lpb)
-        assert abs(out[2] + out[3] - lpf) <= 2e-5 * max(abs(lpf), 1.0), (i, out, lpf)
+        assert abs(out[0] + out[1] - lpb) <= 1e-6 * max(abs(lpb), 1.0), (i, out, lpb)
+        assert abs(out[2] + out[3] - lpf) <= 1e-6 * max(abs(lpf), 1.0), (i, out, lpf)
         rot, trans = rt, tt
 
 

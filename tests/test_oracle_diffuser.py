@@ -60,6 +60,35 @@ def test_sample_ref_stream():
     np.testing.assert_allclose(trans.astype(np.float32), X["inpaint_trans"], atol=1e-5)
 
 
+def test_confidence_walk_steps_teacher_forced():
+    """forward / step_log_prob_terms on every step of the two recorded confidence walks, from the reference's own state, noise and
+    scores: x_t at the bounds the device path is held to, the two log-probabilities at 1e-6 of max(|lp|, 1).  The records went through
+    the reference's float32 torch tensors, which the float64 restatement does not imitate; the largest deviation is printed."""
+    worst = dict(rot=0.0, trans=0.0, lp=0.0)
+    for name in ("small_denovo_n24_T6", "full_inpaint_n40_T5"):
+        C = load_golden(f"conf_{name}.npz")
+        d = od.SE3Diffuser((config.small_config(False) if name.startswith("small") else config.base_config(True)).diffuser)
+        dm = C["diffuse_mask"][None]
+        dt = 1.0 / int(C["num_t"])
+        rot, trans = fr.quat_to_rot(C["x0"][None, :, :4]), C["x0"][None, :, 4:]
+        for i, t_1 in enumerate(C["step_t_1"]):
+            ro, to, _ = d.forward(rot, trans, float(t_1), dt, dm, C["noise_tape"][2 * i + 1][None], C["noise_tape"][2 * i][None])
+            np.testing.assert_allclose(ro[0], C["step_rot"][i], atol=2e-6, err_msg=f"{name} rot step {i}")
+            np.testing.assert_allclose(to[0], C["step_trans"][i], rtol=1e-6, atol=2e-6, err_msg=f"{name} trans step {i}")
+            worst["rot"] = max(worst["rot"], np.abs(ro[0] - C["step_rot"][i]).max())
+            worst["trans"] = max(worst["trans"], np.abs(to[0] - C["step_trans"][i]).max())
+            rt, tt = C["step_rot"][i][None], C["step_trans"][i][None]
+            out, _ = d.step_log_prob_terms(rt, tt, rot, trans, C["step_rot_score"][i][None], C["step_trans_score"][i][None], dm,
+                                           float(C["step_t"][i]), float(t_1), dt)
+            for got, key in ((out[0, 0] + out[0, 1], "step_lp_backward"), (out[0, 2] + out[0, 3], "step_lp_forward")):
+                lp = float(C[key][i])
+                rel = abs(got - lp) / max(abs(lp), 1.0)
+                worst["lp"] = max(worst["lp"], rel)
+                assert rel <= 1e-6, (name, i, key, got, lp)
+            rot, trans = rt, tt
+    print("confidence walk vs the records: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+
+
 def test_reverse_steps_teacher_forced():
     d = _diff()
     for name in ("traj_small_denovo_n16_T10.npz", "traj_small_inpaint_n24_T10.npz", "traj_full_denovo_n64_T20.npz"):
