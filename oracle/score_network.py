@@ -47,6 +47,14 @@ def softplus(x):
     return np.log1p(np.exp(x))
 
 
+IPA_ROUND16 = ("z", "qk", "pair_bias", "opair")  # rounding hooks of ScoreNetwork.ipa(dtype=float64): see _ipa_f64
+
+
+def rnd16(x):
+    """Round to the nearest fp16 value (ties to even, as the device conversion), kept in float64."""
+    return np.asarray(x).astype(np.float16).astype(np.float64)
+
+
 # exp(-k ln(1e4)/15), k=0..15 exactly as torch float32 evaluates it (score_network.py:49-53); pinned by
 # tests/golden/ops.npz["timestep_freqs"].  t*1e4*freq reaches 1e4 rad in float32, so a 1-ulp difference in a
 # frequency moves sin/cos by 1e-4: the constants are part of the reference's behaviour.
@@ -148,8 +156,15 @@ class ScoreNetwork:
         return node, edge
 
     # ------------------------------------------------------------------ IPA
-    def ipa(self, b, s, z, quat, trans, mask):
-        """ipa_pytorch.py:170-329. quat/trans [B,N,*] (trans in scaled units)."""
+    def ipa(self, b, s, z, quat, trans, mask, dtype=F32, round16=(), aux=False, slab=32):
+        """ipa_pytorch.py:170-329. quat/trans [B,N,*] (trans in scaled units).
+
+        ``dtype=np.float64``: the float64 restatement (``_ipa_f64``) from the same float32 weights and inputs; ``round16`` names the
+        operands it rounds to fp16 (``IPA_ROUND16``); ``aux=True`` returns ``(out, {"logits", "weights", "feats"})``.  The defaults are the
+        float32 arithmetic every caller had before the switch existed."""
+        if np.dtype(dtype) == np.float64:
+            return self._ipa_f64(b, s, z, quat, trans, mask, frozenset(round16), aux, slab)
+        assert np.dtype(dtype) == F32 and not round16 and not aux, "rounding hooks and the auxiliary outputs belong to the float64 restatement"
         ic = self.mc.ipa
         H, C, Pq, Pv = ic.no_heads, ic.c_hidden, ic.no_qk_points, ic.no_v_points
         B, N, _ = s.shape
@@ -190,8 +205,78 @@ class ScoreNetwork:
         o_pair = np.matmul(a.transpose(0, 2, 1, 3), pair_z).reshape(B, N, -1).astype(F32, copy=False)
         feats = np.concatenate([o, o_pt[..., 0], o_pt[..., 1], o_pt[..., 2], o_norm, o_pair], axis=-1)
         if self.trace is not None:
-            self.trace[f"ipa_{b}_feats"] = feats
+            self.trace[f"ipa_{b}_feats"], self.trace[f"ipa_{b}_weights"] = feats, a
         return self._lin(p + "linear_out", feats.astype(F32, copy=False))
+
+    def _ipa_f64(self, b, s, z, quat, trans, mask, r16, aux, slab):
+        """The same module with every product, the softmax and the frame maps in float64, from the float32 weights and inputs.  Query rows
+        go in slabs of ``slab``, so the largest temporaries are [slab,N,H,Pq,3] and [slab,N,c_z] (z itself is never copied whole).
+
+        ``r16`` (subset of ``IPA_ROUND16``) rounds to fp16 the operands the half-precision mode of the HIP module carries as ONE fp16 value
+        (csrc/attention3.hip header); operands it carries as hi + lo parts (node rows, point logits, P V, value points,
+        down_z weights) are left alone:
+          "z"          the pair representation as stored
+          "qk"         Q (pre-scaled by sqrt(1/(3C)), as the projection writes it) and K of Q K^T
+          "pair_bias"  both operands of linear_b(z): z and sqrt(1/3) W_b
+          "opair"      the pass-over-z o_pair: the attention weights and z of sum_j a z"""
+        F64 = np.float64
+        assert r16 <= set(IPA_ROUND16), sorted(r16 - set(IPA_ROUND16))
+        ic = self.mc.ipa
+        H, C, Pq, Pv = ic.no_heads, ic.c_hidden, ic.no_qk_points, ic.no_v_points
+        B, N, _ = s.shape
+        p = f"score_model.trunk.ipa_{b}."
+        W = lambda n: self.sd[p + n].astype(F64)  # noqa: E731
+        lin = lambda n, x: x @ W(n + ".weight").T + W(n + ".bias")  # noqa: E731
+        s, quat, trans, mask = (np.asarray(x).astype(F64) for x in (s, quat, trans, mask))  # (float64 inputs are taken as they are)
+        rot = fr.quat_to_rot(quat)
+        q = lin("linear_q", s).reshape(B, N, H, C) * math.sqrt(1.0 / (3 * C))
+        kv = lin("linear_kv", s).reshape(B, N, H, 2 * C)
+        k, v = kv[..., :C], kv[..., C:]
+        if "qk" in r16:
+            q, k = rnd16(q), rnd16(k)
+
+        def pts(name, n_pts):
+            x = np.stack(np.split(lin(name, s), 3, axis=-1), axis=-1)
+            return fr.rigid_apply(rot[:, :, None], trans[:, :, None], x).reshape(B, N, H, n_pts, 3)
+
+        q_pts = pts("linear_q_points", Pq)
+        kv_pts = pts("linear_kv_points", Pq + Pv)
+        k_pts, v_pts = kv_pts[..., :Pq, :], kv_pts[..., Pq:, :]
+        wb, bb = W("linear_b.weight") * math.sqrt(1.0 / 3), W("linear_b.bias") * math.sqrt(1.0 / 3)
+        if "pair_bias" in r16:
+            wb = rnd16(wb)
+        hw = np.log1p(np.exp(W("head_weights"))) * math.sqrt(1.0 / (3 * (Pq * 9.0 / 2)))  # [H]
+        wdz, bdz = W("down_z.weight"), W("down_z.bias")
+        logits, o_pair = np.empty((B, H, N, N), dtype=F64), np.empty((B, N, H, wdz.shape[0]), dtype=F64)
+        att = np.empty_like(logits)
+        for bi in range(B):
+            for i0 in range(0, N, slab):
+                sl = slice(i0, min(N, i0 + slab))
+                zs = np.asarray(z[bi, sl], dtype=F32).astype(F64)  # [m,N,c_z]
+                if r16 & {"z", "pair_bias", "opair"} and z.dtype != np.float16:
+                    z16 = rnd16(zs)
+                    zs = z16 if "z" in r16 else zs
+                else:
+                    z16 = zs
+                a = np.matmul(q[bi, sl].transpose(1, 0, 2), k[bi].transpose(1, 2, 0))  # [H,m,N]
+                a += ((z16 if "pair_bias" in r16 else zs) @ wb.T + bb).transpose(2, 0, 1)
+                d = q_pts[bi, sl, None] - k_pts[bi, None]  # [m,N,H,Pq,3]
+                a += (((d * d).sum(-1) * hw[:, None]).sum(-1) * -0.5).transpose(2, 0, 1)
+                a += 1e5 * (mask[bi, sl, None] * mask[bi, None, :] - 1)
+                logits[bi, :, sl] = a
+                e = np.exp(a - a.max(-1, keepdims=True))
+                w = e / e.sum(-1, keepdims=True)
+                att[bi, :, sl] = w
+                pz = (z16 if "opair" in r16 else zs) @ wdz.T + bdz  # [m,N,c_z/4]
+                o_pair[bi, sl] = np.matmul((rnd16(w) if "opair" in r16 else w).transpose(1, 0, 2), pz)
+        o = np.matmul(att, v.transpose(0, 2, 1, 3)).transpose(0, 2, 1, 3).reshape(B, N, H * C)
+        o_pt = np.matmul(att, v_pts.transpose(0, 2, 1, 3, 4).reshape(B, H, N, Pv * 3)).transpose(0, 2, 1, 3).reshape(B, N, H, Pv, 3)
+        o_pt = fr.rigid_invert_apply(rot[:, :, None, None], trans[:, :, None, None], o_pt)
+        o_norm = np.sqrt((o_pt**2).sum(-1) + 1e-8).reshape(B, N, H * Pv)
+        o_pt = o_pt.reshape(B, N, H * Pv, 3)
+        feats = np.concatenate([o, o_pt[..., 0], o_pt[..., 1], o_pt[..., 2], o_norm, o_pair.reshape(B, N, -1)], axis=-1)
+        out = lin("linear_out", feats)
+        return (out, {"logits": logits, "weights": att, "feats": feats}) if aux else out
 
     def seq_tfmr(self, b, x, mask):
         """nn.TransformerEncoder(post-norm, ReLU, dropout 0), ipa_pytorch.py:433-443,536-538."""

@@ -120,3 +120,36 @@ def test_torch_cpu_port_matches_the_numpy_oracle(tables):
     for k in ("rigids", "psi", "trans_score", "atom37"):
         np.testing.assert_allclose(b[k], a[k], atol=2e-4, err_msg=k)
     np.testing.assert_allclose(b["atom37"], G["out_atom37"], atol=5e-4)
+
+
+# measured deviation of the float32 oracle from its float64 restatement on the N = 64 golden, worst of the four blocks:
+# max |a - b| / max |b| of the module output, of the concatenated features and of the attention weights
+IPA_F64_MEASURED = {"out": 6.61e-7, "feats": 4.39e-7, "weights": 4.72e-7}
+
+
+def test_ipa_float64_restatement_against_the_float32_oracle(tables):
+    """ScoreNetwork.ipa(dtype=float64) (the restatement tests/test_gpu_ipa_attention_edges.py holds the kernels to) against the float32
+    arithmetic of the same method on the inputs every block of the N = 64 golden's forward sees: module output, features and attention
+    weights within 4 x the measured deviation."""
+    G = load_golden("fwd_full_denovo_n64.npz")
+    model, _ = _model("full_denovo_n64", G, tables)
+    worst = dict.fromkeys(IPA_F64_MEASURED, 0.0)
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())  # noqa: E731
+
+    class Both(ScoreNetwork):
+        def ipa(self, b, s, z, quat, trans, mask):
+            out = super().ipa(b, s, z, quat, trans, mask)
+            o64, aux = super().ipa(b, s, z, quat, trans, mask, dtype=np.float64, aux=True)
+            sl = super().ipa(b, s, z, quat, trans, mask, dtype=np.float64, slab=7)  # (ragged slabs give the same rows)
+            np.testing.assert_allclose(sl, o64, rtol=0, atol=1e-12 * np.abs(o64).max())
+            assert o64.dtype == np.float64 and out.dtype == np.float32
+            for k, a, r in (("out", out, o64), ("feats", self.trace[f"ipa_{b}_feats"], aux["feats"]), ("weights", self.trace[f"ipa_{b}_weights"], aux["weights"])):
+                worst[k] = max(worst[k], rel(a, r))
+            return out
+
+    model.__class__ = Both
+    model.trace = {}
+    model(_feats(G))
+    print("float32 oracle against the float64 restatement, N = 64, worst block:", {k: f"{v:.2e}" for k, v in worst.items()})
+    for k, v in worst.items():
+        assert v <= 4 * IPA_F64_MEASURED[k], (k, v)
