@@ -1,5 +1,6 @@
 // mpnn.hip — inverse folding on the device (include/fdipt.h, "inverse folding"): the vanilla full-backbone
-// ProteinMPNN, inference only, float32 throughout.
+// ProteinMPNN and (dims->ca_only, section 7.12) its CA-only sibling, which differs in the feature kernel alone; inference only,
+// float32 throughout.
 //
 // Every matmul-shaped step has the same shape: the (up to 64) edges of ONE row are the rows of a 64 x IN activation tile in LDS, and
 // the tile goes through a [IN][128] weight (stored transposed in the image) on v_mfma_f32_32x32x2_f32: wave w owns output columns
@@ -9,6 +10,8 @@
 //
 //   mpnn_features_kernel   block per row: CA distances to all columns, the K_eff smallest by (distance, index) through a rank count in
 //                          LDS, 16 positional + 25 x 16 RBF inputs, edge_embedding, norm_edges, W_e -> h_E
+//   mpnn_ca_features_kernel  the same block for the CA-only model: the same neighbours (mp_neighbours), 16 positional + 9 x 16 RBF inputs
+//                          over the array-shifted traces + 7 orientation inputs (dU, Q) from the frames of the row and its neighbours
 //   mpnn_enc_kernel<false> block per row: [h_V_i, h_E_ij, h_V_j] -> W1, W2, W3 (GELU), masked sum / 30, LN, FFN, LN, mask -> new h_V
 //   mpnn_enc_kernel<true>  block per row: the same gather on the new h_V -> W11, W12, W13, + h_E, LN -> h_E (in place: a row's own edges)
 //   mpnn_order_kernel      block per sequence: the decoding step of every row (the inverse of decoding_order)
@@ -40,6 +43,9 @@ constexpr long D_W1 = 0, D_B1 = D_W1 + 512 * 128, D_W2 = D_B1 + 128, D_B2 = D_W2
                D_LN2G = D_BOUT + 128, D_LN2B = D_LN2G + 128, D_SIZE = D_LN2B + 128;
 constexpr long OUT_W = DEC0 + 3 * D_SIZE, OUT_B = OUT_W + 128 * MP_V, TOTAL = OUT_B + MP_V;
 static_assert(TOTAL == 1660485, "the parameter count of the vanilla model");
+// The CA-only image is the same table with 167 rows of edge_embedding: every offset past EDGE_W lies CA_SHIFT lower (MpCtx::W).
+constexpr long EDGE_IN = 416, EDGE_IN_CA = 167, CA_SHIFT = (EDGE_IN - EDGE_IN_CA) * 128;
+static_assert(TOTAL - CA_SHIFT == 1628613, "the parameter count of the CA-only model, its five unread parameters left out");
 }  // namespace mpw
 
 // what every kernel needs: the caller's arguments and the workspace carved up
@@ -50,6 +56,9 @@ struct MpCtx {
   float* hV[2];   // [B,N,128] ping / pong of the encoder; the encoder's result ends in hV[1]
   float* stack;   // [3][B,M,N,128]: the decoder layers' outputs per sequence
   int32_t* pos;   // [B,M,N]: the decoding step of a row (the inverse of decoding_order)
+  long shift;     // 0, or mpw::CA_SHIFT for the CA-only image
+  // the image at an offset of the table past EDGE_W (every matrix and vector but the positional ones and edge_embedding itself)
+  __device__ __forceinline__ const float* W(long off) const { return a.weights + (off - shift); }
 };
 
 struct MpAcc { f32x16 t[2]; };
@@ -180,25 +189,23 @@ __device__ __forceinline__ void mp_atoms(const float* __restrict__ row, float* o
   for (int d = 0; d < 3; ++d) out[12 + d] = -0.58273431f * a[d] + 0.56802827f * b[d] - 0.54067466f * cc[d] + ca[d];
 }
 
-__global__ __launch_bounds__(FD_THREADS) void mpnn_features_kernel(MpCtx x) {
-  __shared__ float tile[MP_ROWS * MP_LD];
-  __shared__ float dist[FDIPT_MPNN_MAX_ROWS];
-  __shared__ float nb[MP_ROWS * 15], me[15], red[FD_THREADS / FD_WAVE], dnb[MP_ROWS];
-  __shared__ int sel[MP_ROWS], posd[MP_ROWS], flag;
+// The neighbours of row i of backbone b, for both feature kernels.  ca: the CA of the backbone's row 0, stride: floats per row of prot.
+// Leaves in LDS sel[k] (the column of slot k < K, nearest first, ties to the lower column), dnb[k] (its adjusted distance) and posd[k]
+// (its positional class), writes E_idx and the row's share of status, and ends on a barrier.  dist: FDIPT_MPNN_MAX_ROWS floats, red: one
+// per wave.
+__device__ __forceinline__ void mp_neighbours(const MpCtx& x, const float* __restrict__ ca, int stride, long b, int i, float* dist, float* red,
+                                              float* dnb, int* sel, int* posd, int* flag) {
   const FdiptMpnnArgs& a = x.a;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = a.N, K = x.K, i = blockIdx.x, A3 = a.atoms * 3;
-  const long b = blockIdx.y, bi = b * N + i;
-  const float* __restrict__ W = a.weights;
-  const float* prot = a.prot + b * N * A3;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = a.N, K = x.K;
+  const long bi = b * N + i;
   const float mi = a.res_mask[bi];
   if (tid < MP_ROWS) sel[tid] = tid < K ? tid : 0;  // in range whatever the distances are (NaN coordinates)
-  if (tid == 0) flag = 0;
-  if (tid < MP_H) x.hV[0][bi * MP_H + tid] = 0.f;
+  if (tid == 0) *flag = 0;
   // D = mask_2D sqrt(|dCA|^2 + 1e-6), D_adjust = D + (1 - mask_2D) max_j D
-  const float cx = prot[i * A3 + 3], cy = prot[i * A3 + 4], cz = prot[i * A3 + 5];
+  const float cx = ca[i * stride], cy = ca[i * stride + 1], cz = ca[i * stride + 2];
   float mx = 0.f;
   for (int j = tid; j < N; j += FD_THREADS) {
-    const float dx = prot[j * A3 + 3] - cx, dy = prot[j * A3 + 4] - cy, dz = prot[j * A3 + 5] - cz;
+    const float dx = ca[j * stride] - cx, dy = ca[j * stride + 1] - cy, dz = ca[j * stride + 2] - cz;
     const float d = mi * a.res_mask[b * N + j] * sqrtf(dx * dx + dy * dy + dz * dz + 1e-6f);
     dist[j] = d, mx = fmaxf(mx, d);
   }
@@ -219,19 +226,54 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_features_kernel(MpCtx x) {
     if (r < K && dj == dj) sel[r] = j;
   }
   __syncthreads();
-  if (tid == 0) mp_atoms(prot + i * A3, me);
   if (tid < K) {
     const int j = sel[tid];
-    mp_atoms(prot + j * A3, nb + tid * 15);
     dnb[tid] = dist[j];
     a.E_idx[bi * K + tid] = j;
     const int same = a.chain_idx[bi] == a.chain_idx[b * N + j];
     const int off = a.residue_index[bi] - a.residue_index[b * N + j];
     posd[tid] = same ? min(max(off + 32, 0), 64) : 65;
-    if (mi != 0.f && a.res_mask[b * N + j] == 0.f) flag = 1;
+    if (mi != 0.f && a.res_mask[b * N + j] == 0.f) *flag = 1;
   }
   __syncthreads();
-  if (tid == 0 && flag) atomicOr(a.status + b, FDIPT_MPNN_MASKED_NEIGHBOR);
+  if (tid == 0 && *flag) atomicOr(a.status + b, FDIPT_MPNN_MASKED_NEIGHBOR);
+}
+
+// norm_edges and W_e over the edge_embedding outputs in the accumulators -> h_E: the tail of both feature kernels
+__device__ __forceinline__ void mp_edge_tail(const MpCtx& x, MpAcc& c, float* tile, long bi, int tid) {
+  const int lane = tid & 63, wave = tid >> 6, K = x.K;
+  __syncthreads();
+  mp_store(c, tile, wave, lane, [](float v, int) { return v; });
+  __syncthreads();
+  for (int k = wave; k < K; k += FD_THREADS / FD_WAVE) mp_ln(tile + k * MP_LD, x.W(mpw::EDGE_G), x.W(mpw::EDGE_B), lane);
+  __syncthreads();
+  mp_zero(c);
+  mp_mma(c, tile, x.W(mpw::WE_W), MP_H, wave, lane);
+  const int col = wave * 32 + (lane & 31);
+  const float bias = x.W(mpw::WE_B)[col];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int k = t * 32 + c_row(r, lane);
+      if (k < K) x.hE[(bi * K + k) * MP_H + col] = c.t[t][r] + bias;
+    }
+}
+
+__global__ __launch_bounds__(FD_THREADS) void mpnn_features_kernel(MpCtx x) {
+  __shared__ float tile[MP_ROWS * MP_LD];
+  __shared__ float dist[FDIPT_MPNN_MAX_ROWS];
+  __shared__ float nb[MP_ROWS * 15], me[15], red[FD_THREADS / FD_WAVE], dnb[MP_ROWS];
+  __shared__ int sel[MP_ROWS], posd[MP_ROWS], flag;
+  const FdiptMpnnArgs& a = x.a;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = a.N, K = x.K, i = blockIdx.x, A3 = a.atoms * 3;
+  const long b = blockIdx.y, bi = b * N + i;
+  const float* __restrict__ W = a.weights;
+  const float* prot = a.prot + b * N * A3;
+  if (tid < MP_H) x.hV[0][bi * MP_H + tid] = 0.f;
+  mp_neighbours(x, prot + 3, A3, b, i, dist, red, dnb, sel, posd, &flag);
+  if (tid == 0) mp_atoms(prot + i * A3, me);
+  if (tid < K) mp_atoms(prot + sel[tid] * A3, nb + tid * 15);
   // edge_embedding over the 416 inputs: 16 positional, then 25 pairs x 16 RBF centres
   MpAcc c;
   mp_zero(c);
@@ -264,22 +306,133 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_features_kernel(MpCtx x) {
     __syncthreads();
     mp_mma(c, tile, W + mpw::EDGE_W + (long)f0 * MP_H, kw, wave, lane);
   }
-  __syncthreads();
-  mp_store(c, tile, wave, lane, [](float v, int) { return v; });
-  __syncthreads();
-  for (int k = wave; k < K; k += FD_THREADS / FD_WAVE) mp_ln(tile + k * MP_LD, W + mpw::EDGE_G, W + mpw::EDGE_B, lane);
-  __syncthreads();
+  mp_edge_tail(x, c, tile, bi, tid);
+}
+
+// ---- the CA-only features
+// x0 y0 + x1 y1 + x2 y2 in ONE order of operations, so that swapping the operands gives the same bits: the self edge's R is symmetric
+__device__ __forceinline__ float mp_dot3(float x0, float y0, float x1, float y1, float x2, float y2) { return fmaf(x2, y2, fmaf(x1, y1, x0 * y0)); }
+// v / max(|v|, 1e-12)
+__device__ __forceinline__ void mp_unit(float* v) {
+  const float s = 1.f / fmaxf(sqrtf(mp_dot3(v[0], v[0], v[1], v[1], v[2], v[2])), 1e-12f);
+  v[0] *= s, v[1] *= s, v[2] *= s;
+}
+// the kept unit step q - p: the zero vector unless 3.6 < |q - p| < 4.0
+__device__ __forceinline__ void mp_step(const float* p, const float* q, float* u) {
+  u[0] = q[0] - p[0], u[1] = q[1] - p[1], u[2] = q[2] - p[2];
+  const float len = sqrtf(mp_dot3(u[0], u[0], u[1], u[1], u[2], u[2]));
+  if (!(len > 3.6f && len < 4.0f)) u[0] = u[1] = u[2] = 0.f;
+  mp_unit(u);
+}
+// The three shifted traces of row r into t[9] (Ca[r-1], Ca[r], Ca[r+1]; rows -1 and N are the zero vector) and its frame O[9] (rows
+// o_1, n_2, o_1 x n_2; zero at row 0 and at rows N-2, N-1).  No read outside [0, N).
+__device__ __forceinline__ void mp_ca_row(const float* __restrict__ ca, int stride, int N, int r, float* t, float* O) {
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const int q = r - 1 + s;
+    const bool in = q >= 0 && q < N;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) t[3 * s + d] = in ? ca[(long)q * stride + d] : 0.f;
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) O[e] = 0.f;
+  if (r < 1 || r > N - 3) return;  // (rows r-1 and r+1 exist here)
+  float u2[3], u1[3];
+  mp_step(t, t + 3, u2);      // the step into the row
+  mp_step(t + 3, t + 6, u1);  // the step out of it
+  float* o1 = O;
+  float* n2 = O + 3;
+  float* o3 = O + 6;
+  o1[0] = u2[0] - u1[0], o1[1] = u2[1] - u1[1], o1[2] = u2[2] - u1[2];
+  mp_unit(o1);
+  n2[0] = u2[1] * u1[2] - u2[2] * u1[1], n2[1] = u2[2] * u1[0] - u2[0] * u1[2], n2[2] = u2[0] * u1[1] - u2[1] * u1[0];
+  mp_unit(n2);
+  o3[0] = o1[1] * n2[2] - o1[2] * n2[1], o3[1] = o1[2] * n2[0] - o1[0] * n2[2], o3[2] = o1[0] * n2[1] - o1[1] * n2[0];
+}
+// (A of row i, B of neighbour j) of the nine RBF blocks: 0 = the row before, 1 = the row, 2 = the row after
+__device__ __constant__ signed char mp_ca_pair_a[9] = {1, 0, 2, 0, 0, 1, 1, 2, 2};
+__device__ __constant__ signed char mp_ca_pair_b[9] = {1, 0, 2, 1, 2, 0, 2, 0, 1};
+
+__global__ __launch_bounds__(FD_THREADS) void mpnn_ca_features_kernel(MpCtx x) {
+  __shared__ float tile[MP_ROWS * MP_LD];
+  __shared__ float dist[FDIPT_MPNN_MAX_ROWS];
+  __shared__ float nb[MP_ROWS * 9], of[MP_ROWS * 7], me[9], Oi[9], red[FD_THREADS / FD_WAVE], dnb[MP_ROWS];
+  __shared__ int sel[MP_ROWS], posd[MP_ROWS], flag;
+  const FdiptMpnnArgs& a = x.a;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = a.N, K = x.K, i = blockIdx.x, A3 = a.atoms * 3;
+  const long b = blockIdx.y, bi = b * N + i;
+  const float* __restrict__ W = a.weights;
+  const float* ca = a.prot + b * N * A3 + (a.atoms == 1 ? 0 : 3);  // the trace alone, or atom 1 of either layout
+  if (tid < MP_H) x.hV[0][bi * MP_H + tid] = 0.f;
+  if (tid == 0) mp_ca_row(ca, A3, N, i, me, Oi);
+  mp_neighbours(x, ca, A3, b, i, dist, red, dnb, sel, posd, &flag);  // (its barriers publish me and Oi)
+  if (tid < K) {
+    // the orientation inputs of slot tid: dU = unit(O_i (Ca_j - Ca_i)), Q of R = O_i^T O_j
+    float Oj[9], dU[3], R[9], q[4];
+    mp_ca_row(ca, A3, N, sel[tid], nb + tid * 9, Oj);
+    if (sel[tid] == i)  // the self edge: the very values of O_i, so that R_ab and R_ba are the same operations on swapped operands
+      for (int e = 0; e < 9; ++e) Oj[e] = Oi[e];
+    const float* pj = nb + tid * 9 + 3;
+    const float dx = pj[0] - me[3], dy = pj[1] - me[4], dz = pj[2] - me[5];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) dU[r] = mp_dot3(Oi[3 * r], dx, Oi[3 * r + 1], dy, Oi[3 * r + 2], dz);
+    mp_unit(dU);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int s = 0; s < 3; ++s) R[3 * r + s] = mp_dot3(Oi[r], Oj[s], Oi[3 + r], Oj[3 + s], Oi[6 + r], Oj[6 + s]);
+    const float anti[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+    const float diag[3] = {R[0] - R[4] - R[8], -R[0] + R[4] - R[8], -R[0] - R[4] + R[8]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) q[r] = (anti[r] > 0.f ? 1.f : anti[r] < 0.f ? -1.f : 0.f) * (0.5f * sqrtf(fabsf(1.f + diag[r])));
+    q[3] = sqrtf(fmaxf(1.f + (R[0] + R[4] + R[8]), 0.f)) / 2.f;
+    const float s = 1.f / fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
+    float* o = of + tid * 7;
+    o[0] = dU[0], o[1] = dU[1], o[2] = dU[2], o[3] = q[0] * s, o[4] = q[1] * s, o[5] = q[2] * s, o[6] = q[3] * s;
+  }
+  // edge_embedding over the 167 inputs: 16 positional, 9 pairs x 16 RBF centres, dU and Q; the second chunk is 39 columns and a zero one
+  MpAcc c;
   mp_zero(c);
-  mp_mma(c, tile, W + mpw::WE_W, MP_H, wave, lane);
-  const int col = wave * 32 + (lane & 31);
-  const float bias = W[mpw::WE_B + col];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int k = t * 32 + c_row(r, lane);
-      if (k < K) x.hE[(bi * K + k) * MP_H + col] = c.t[t][r] + bias;
+  for (int f0 = 0; f0 < (int)mpw::EDGE_IN_CA; f0 += MP_H) {
+    const int kw = min(MP_H, ((int)mpw::EDGE_IN_CA - f0 + 1) & ~1);  // 128, then 40
+    __syncthreads();
+    for (int e = tid; e < MP_ROWS * kw; e += FD_THREADS) {
+      const int k = e / kw, f = f0 + e % kw;
+      float v = 0.f;
+      if (k < K && f < (int)mpw::EDGE_IN_CA) {
+        if (f < 16) {
+          v = W[mpw::POS_W + posd[k] * 16 + f] + W[mpw::POS_B + f];
+        } else if (f < 160) {
+          const int p = (f - 16) >> 4, ce = (f - 16) & 15;
+          float d;
+          if (p == 0) {
+            d = dnb[k];
+          } else {
+            const float* pa = me + 3 * mp_ca_pair_a[p];
+            const float* pb = nb + k * 9 + 3 * mp_ca_pair_b[p];
+            const float dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
+            d = sqrtf(dx * dx + dy * dy + dz * dz + 1e-6f);
+          }
+          const float z = (d - (2.f + ce * (20.f / 15.f))) / 1.25f;
+          v = expf(-z * z);
+        } else {
+          v = of[k * 7 + (f - 160)];
+        }
+      }
+      tile[k * MP_LD + (f - f0)] = v;
     }
+    __syncthreads();
+    // an even number of whole steps, then (167 is odd) one step whose second weight row does not exist: its operand is the zero column
+    const int whole = min(kw, ((int)mpw::EDGE_IN_CA - f0) & ~1);
+    mp_mma(c, tile, W + mpw::EDGE_W + (long)f0 * MP_H, whole, wave, lane);
+    if (whole < kw) {
+      const int li = lane & 31, hi = lane >> 5;
+      const float bw = hi ? 0.f : W[mpw::EDGE_W + (long)(f0 + whole) * MP_H + wave * 32 + li];
+      c.t[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(tile[li * MP_LD + whole + hi], bw, c.t[0], 0, 0, 0);
+      c.t[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(tile[(li + 32) * MP_LD + whole + hi], bw, c.t[1], 0, 0, 0);
+    }
+  }
+  mp_edge_tail(x, c, tile, bi, tid);
 }
 
 // ------------------------------------------------------------------------------------------------ encoder
@@ -291,7 +444,7 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_enc_kernel(MpCtx x, int layer
   const FdiptMpnnArgs& a = x.a;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = a.N, K = x.K, i = blockIdx.x;
   const long b = blockIdx.y, bi = b * N + i;
-  const float* __restrict__ W = a.weights + mpw::ENC0 + layer * mpw::E_SIZE;
+  const float* __restrict__ W = x.W(mpw::ENC0 + layer * mpw::E_SIZE);
   const float* hV = x.hV[src] + b * N * MP_H;  // node update: the layer's input; edge update: the layer's new h_V
   float* hE = x.hE + bi * K * MP_H;
   const float mi = a.res_mask[bi];
@@ -330,8 +483,8 @@ __device__ __forceinline__ void mp_dec_layer(const MpCtx& x, int layer, long b, 
                                              const int* before, const int* lettered, int tid, L&& letter) {
   const FdiptMpnnArgs& a = x.a;
   const int N = a.N, K = x.K;
-  const float* __restrict__ W = a.weights + mpw::DEC0 + layer * mpw::D_SIZE;
-  const float* Ws = a.weights + mpw::WS;
+  const float* __restrict__ W = x.W(mpw::DEC0 + layer * mpw::D_SIZE);
+  const float* Ws = x.W(mpw::WS);
   const float* hE = x.hE + (b * N + i) * K * MP_H;
   const float* enc = x.hV[1] + b * N * MP_H;
   const long BMN = (long)a.B * a.M * N;
@@ -349,10 +502,12 @@ __device__ __forceinline__ void mp_dec_layer(const MpCtx& x, int layer, long b, 
 }
 
 // logits[a] = W_out vi + b into lg[21] (LDS)
-__device__ __forceinline__ void mp_logits(const float* __restrict__ W, const float* vi, float* lg, int tid) {
+__device__ __forceinline__ void mp_logits(const MpCtx& x, const float* vi, float* lg, int tid) {
+  const float* __restrict__ Wo = x.W(mpw::OUT_W);
+  const float* __restrict__ bo = x.W(mpw::OUT_B);
   if (tid < MP_V) {
-    float s = W[mpw::OUT_B + tid];
-    for (int k = 0; k < MP_H; ++k) s += vi[k] * W[mpw::OUT_W + k * MP_V + tid];
+    float s = bo[tid];
+    for (int k = 0; k < MP_H; ++k) s += vi[k] * Wo[k * MP_V + tid];
     lg[tid] = s;
   }
   __syncthreads();
@@ -395,7 +550,7 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_score_kernel(MpCtx x, int lay
   __syncthreads();
   mp_dec_layer(x, layer, b, bm, i, tile, vi, hid, sel, before, before, tid, [&](int j) { return mp_letter(S[j]); });
   if (layer != 2) return;
-  mp_logits(a.weights, vi, lg, tid);
+  mp_logits(x, vi, lg, tid);
   if (tid == 0) {
     float mx = lg[0], s = 0.f;
     for (int q = 1; q < MP_V; ++q) mx = fmaxf(mx, lg[q]);
@@ -421,7 +576,6 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_design_kernel(MpCtx x) {
   const long BMN = (long)a.B * a.M * N;
   const int* pos = x.pos + bm * N;
   const int* order = a.decoding_order + bm * N;
-  const float* __restrict__ W = a.weights;
   for (int j = tid; j < N; j += FD_THREADS) S[j] = (unsigned char)mp_letter(a.S[bm * N + j]), known[j] = a.res_mask[b * N + j] == 0.f;
   __syncthreads();
   // the tie id of step s: -1 for an untied row and for a step that decodes nothing (past the end, out of range, named twice, no res_mask)
@@ -460,7 +614,7 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_design_kernel(MpCtx x) {
       __threadfence();  // the row of the stack is read back by later steps of this block
       __syncthreads();
     }
-    mp_logits(W, vi, lg, tid);
+    mp_logits(x, vi, lg, tid);
     if (tied) {
       if (tid < MP_V) acc[tid] += a.tied_beta[bi] * (lg[tid] / a.temperature) / (float)(gend - t0);
       __syncthreads();
@@ -538,10 +692,12 @@ __global__ __launch_bounds__(FD_THREADS) void mpnn_design_kernel(MpCtx x) {
 // ------------------------------------------------------------------------------------------------ host
 static bool mp_dims_ok(const FdiptMpnnDims* d) {
   return d && d->hidden == MP_H && d->enc_layers == 3 && d->dec_layers == 3 && d->vocab == MP_V && d->k_neighbors >= 1 &&
-         d->k_neighbors <= FDIPT_MPNN_MAX_NEIGHBORS;
+         d->k_neighbors <= FDIPT_MPNN_MAX_NEIGHBORS && (d->ca_only == 0 || d->ca_only == 1);
 }
 
-extern "C" int64_t fdipt_mpnn_weights_floats(const FdiptMpnnDims* dims) { return mp_dims_ok(dims) ? (int64_t)mpw::TOTAL : FDIPT_EINVAL; }
+extern "C" int64_t fdipt_mpnn_weights_floats(const FdiptMpnnDims* dims) {
+  return mp_dims_ok(dims) ? (int64_t)(mpw::TOTAL - (dims->ca_only ? mpw::CA_SHIFT : 0)) : FDIPT_EINVAL;
+}
 
 // h_E, the encoder's two h_V, the three decoder outputs per sequence (floats), then the decoding steps (i32)
 extern "C" size_t fdipt_mpnn_workspace(const FdiptMpnnDims* dims, int B, int N, int M) {
@@ -551,7 +707,9 @@ extern "C" size_t fdipt_mpnn_workspace(const FdiptMpnnDims* dims, int B, int N, 
 }
 
 static int mp_prepare(const FdiptMpnnDims* dims, const FdiptMpnnArgs* a, bool design, MpCtx& x) {
-  if (!a || !mp_dims_ok(dims) || a->B < 1 || a->N < 1 || a->M < 1 || (a->atoms != 37 && a->atoms != 5)) return FDIPT_EINVAL;
+  if (!a || !mp_dims_ok(dims) || a->B < 1 || a->N < 1 || a->M < 1) return FDIPT_EINVAL;
+  if (a->atoms != 37 && a->atoms != 5 && !(dims->ca_only && a->atoms == 1)) return FDIPT_EINVAL;
+  if (dims->ca_only && a->N < 3) return FDIPT_EINVAL;  // the frames need three rows (the reference raises)
   if (!a->weights || !a->prot || !a->res_mask || !a->residue_index || !a->chain_idx || !a->E_idx || !a->status) return FDIPT_EINVAL;
   if ((design || !a->unconditional) && (!a->S || !a->decoding_order)) return FDIPT_EINVAL;
   if (design ? (!a->chain_mask || !a->u || !a->omit || !a->bias || !a->S_out || !a->probs || !(a->temperature > 0.f)) : !a->log_probs) return FDIPT_EINVAL;
@@ -562,6 +720,7 @@ static int mp_prepare(const FdiptMpnnDims* dims, const FdiptMpnnArgs* a, bool de
   if (design) x.a.unconditional = 0;
   else if (x.a.unconditional) x.a.decoding_order = nullptr, x.a.S = nullptr;
   x.K = dims->k_neighbors < a->N ? dims->k_neighbors : a->N;
+  x.shift = dims->ca_only ? mpw::CA_SHIFT : 0;
   const size_t bn = (size_t)a->B * a->N;
   x.hE = (float*)a->workspace;
   x.hV[0] = x.hE + bn * x.K * MP_H;
@@ -575,7 +734,8 @@ static int mp_prepare(const FdiptMpnnDims* dims, const FdiptMpnnArgs* a, bool de
 static int mp_encode(const MpCtx& x, hipStream_t s) {
   const dim3 rows((unsigned)x.a.N, (unsigned)x.a.B);
   if (hipMemsetAsync(x.a.status, 0, sizeof(int32_t) * x.a.B, s) != hipSuccess) return FDIPT_ELAUNCH;
-  hipLaunchKernelGGL(mpnn_features_kernel, rows, dim3(FD_THREADS), 0, s, x);
+  if (x.shift) hipLaunchKernelGGL(mpnn_ca_features_kernel, rows, dim3(FD_THREADS), 0, s, x);
+  else hipLaunchKernelGGL(mpnn_features_kernel, rows, dim3(FD_THREADS), 0, s, x);
   FD_CHECK_LAUNCH();
   for (int l = 0; l < 3; ++l) {
     const int src = l & 1;  // 0 -> 1, 1 -> 0, 0 -> 1

@@ -6,8 +6,11 @@ ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward and .sample) runs on th
 ``fdipt_mpnn_design`` (csrc/mpnn.hip, ABI in include/fdipt.h); DESIGN.md section 7.10 is the contract.  Inference only, float32.
 Section 7.11 adds what the vendored ProteinMPNN offers beyond that subprocess: the per-row controls of ``sample`` (``bias_by_res``,
 ``omit_AA_mask``, the two PSSM stages), tied positions (``tied_sample``; ``tied_positions_from_chains`` for homo-oligomers) and the two
-probability modes ``unconditional_probs`` and ``conditional_probs`` with ``native_scores``.  ``ca_only`` is not built, nor are tied
-groups with a masked or fixed member (``tie_groups`` refuses them).
+probability modes ``unconditional_probs`` and ``conditional_probs`` with ``native_scores``.  Section 7.12 is the CA-only model
+(``CA_ProteinFeatures``, ``ProteinMPNN(ca_only=True)`` of the reference): ``ProteinMPNN(ca_only=True)`` here reads only the CA trace, and
+everything after the features - encoder, decoder, controls, ties, probability modes - is the same code.  No trained CA checkpoint was
+available when this was built: parity is claimed against the reference's code with synthetic parameters.  Not built: tied groups with a
+masked or fixed member (``tie_groups`` refuses them).
 
 Two alphabets meet here.  ``S`` arrays, ``probs`` and ``log_probs`` are in the MODEL's alphabet ``ACDEFGHIKLMNPQRSTVWYX``, as in the
 reference; ``aatype`` arrays are in this project's restype order (``output.RESTYPES``, 20 = unknown).  ``aatype_to_mpnn`` and
@@ -24,6 +27,7 @@ from .output import RESTYPES
 
 ALPHABET = "ACDEFGHIKLMNPQRSTVWYX"
 VOCAB, HIDDEN, LAYERS = 21, 128, 3
+EDGE_IN, EDGE_IN_CA = 416, 167   # the inputs of features.edge_embedding: 16 + 25 x 16, and 16 + 9 x 16 + 7 for the CA-only model
 MAX_ROWS, MAX_SEQ, MAX_NEIGHBORS = _lib.MPNN_MAX_ROWS, _lib.MPNN_MAX_SEQ, _lib.MPNN_MAX_NEIGHBORS
 MASKED_NEIGHBOR, NO_LETTER = _lib.MPNN_MASKED_NEIGHBOR, _lib.MPNN_NO_LETTER
 _TO_MPNN = np.array([ALPHABET.index(c) for c in RESTYPES] + [20], dtype=np.int64)       # restype index -> model letter
@@ -70,12 +74,23 @@ def _layer_shapes(prefix, w1_in, edge_update):
     return out
 
 
-def param_shapes() -> "OrderedDict[str, tuple]":
-    """The reference's parameter names and shapes (vanilla model: hidden 128, 3 + 3 layers), in a fixed order."""
+# the parameters of a CA-only state dict that the reference's forward never reads (departure c)
+CA_UNREAD = ("features.node_embedding.weight", "features.norm_nodes.weight", "features.norm_nodes.bias", "W_v.weight", "W_v.bias")
+
+
+def param_shapes(ca_only: bool = False) -> "OrderedDict[str, tuple]":
+    """The reference's parameter names and shapes (hidden 128, 3 + 3 layers), in a fixed order: the vanilla model, or with ``ca_only``
+    the CA-only one - 167 edge inputs and the five parameters of ``CA_UNREAD``."""
     s = OrderedDict()
     s["features.embeddings.linear.weight"], s["features.embeddings.linear.bias"] = (16, 66), (16,)
-    s["features.edge_embedding.weight"] = (HIDDEN, 416)
+    if ca_only:
+        s["features.node_embedding.weight"] = (HIDDEN, 3)
+    s["features.edge_embedding.weight"] = (HIDDEN, EDGE_IN_CA if ca_only else EDGE_IN)
+    if ca_only:
+        s["features.norm_nodes.weight"], s["features.norm_nodes.bias"] = (HIDDEN,), (HIDDEN,)
     s["features.norm_edges.weight"], s["features.norm_edges.bias"] = (HIDDEN,), (HIDDEN,)
+    if ca_only:
+        s["W_v.weight"], s["W_v.bias"] = (HIDDEN, HIDDEN), (HIDDEN,)
     s["W_e.weight"], s["W_e.bias"] = (HIDDEN, HIDDEN), (HIDDEN,)
     s["W_s.weight"] = (VOCAB, HIDDEN)
     for l in range(LAYERS):
@@ -86,14 +101,15 @@ def param_shapes() -> "OrderedDict[str, tuple]":
     return s
 
 
-def synthetic_state_dict(seed: int, k: int = 48) -> "OrderedDict[str, np.ndarray]":
+def synthetic_state_dict(seed: int, k: int = 48, ca_only: bool = False) -> "OrderedDict[str, np.ndarray]":
     """Synthetic float32 parameters under the reference's names from ``np.random.default_rng((seed, k))``, drawn in the order of
     ``param_shapes``: Xavier-uniform matrices (the reference's initialisation), biases uniform in +-0.1, LayerNorm gains 1 + 0.1 n and
     shifts 0.1 n - nothing is zero or one, so that a swapped gain, shift or bias shows.  ``k`` does not change a shape; it enters the
-    stream so that models of different K differ."""
-    rng = np.random.default_rng((int(seed), int(k)))
+    stream so that models of different K differ.  ``ca_only``: the CA-only model from ``np.random.default_rng((seed, k, 1))`` in the
+    order of ``param_shapes(ca_only=True)``, the five unread parameters included (the reference's strict ``load_state_dict`` wants them)."""
+    rng = np.random.default_rng((int(seed), int(k), 1) if ca_only else (int(seed), int(k)))
     sd = OrderedDict()
-    for name, shape in param_shapes().items():
+    for name, shape in param_shapes(ca_only).items():
         if len(shape) == 2:
             bound = np.sqrt(6.0 / (shape[0] + shape[1]))
             v = rng.uniform(-bound, bound, size=shape)
@@ -127,18 +143,28 @@ def _image_order():
     return order + linear("W_out")
 
 
-def pack_image(sd) -> np.ndarray:
-    """The packed float32 weight image of a state dict under the reference's names (tensors or arrays)."""
-    shapes = param_shapes()
-    missing = [n for n in shapes if n not in sd]
+def is_ca_state_dict(sd) -> bool:
+    """Does a state dict hold the CA-only model?  It is known by the 167 columns of ``features.edge_embedding.weight``."""
+    w = sd.get("features.edge_embedding.weight") if hasattr(sd, "get") else None
+    return w is not None and len(w.shape) == 2 and int(w.shape[1]) == EDGE_IN_CA
+
+
+def pack_image(sd, ca_only=None) -> np.ndarray:
+    """The packed float32 weight image of a state dict under the reference's names (tensors or arrays).  ``ca_only``: which model the
+    dict must hold; None: whichever its ``features.edge_embedding.weight`` says (``is_ca_state_dict``).  The image of a CA-only model is
+    the same table with 167 rows of edge_embedding; the five parameters its forward never reads may be present and are dropped."""
+    ca_only = is_ca_state_dict(sd) if ca_only is None else bool(ca_only)
+    what = "CA-only" if ca_only else "vanilla"
+    shapes = param_shapes(ca_only)
+    missing = [n for n in shapes if n not in sd and n not in CA_UNREAD]
     if missing:
-        raise ValueError(f"state dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''}: the vanilla full-backbone model is the one built")
+        raise ValueError(f"state dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''} of the {what} model")
     parts = []
     for name, transposed in _image_order():
         v = sd[name]
         v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
         if tuple(v.shape) != shapes[name]:
-            raise ValueError(f"{name}: shape {tuple(v.shape)}, the vanilla model has {shapes[name]} (ca_only and other widths are not built)")
+            raise ValueError(f"{name}: shape {tuple(v.shape)}, the {what} model has {shapes[name]} (other widths are not built)")
         parts.append(np.ascontiguousarray(v.T if transposed else v, dtype=np.float32).reshape(-1))
     return np.concatenate(parts)
 
@@ -253,11 +279,13 @@ def _fmt(x):
 def fasta_records(result: dict, b: int, name: str, model_name: str = "synthetic") -> str:
     """The reference's ``seqs/<name>.fa`` for backbone ``b`` of a ``design`` result (protein_mpnn_run.py:348, 367): the input sequence
     first, then one record per designed sequence with the four-decimal score, global_score and seq_recovery.  The first record's score
-    fields are those of the input sequence where the result carries them (``native_score``, ``native_global_score``), NaN otherwise."""
+    fields are those of the input sequence where the result carries them (``native_score``, ``native_global_score``), NaN otherwise.
+    The result of a CA-only model (``ca_only`` set) names its model as ``CA_model_name=``, as protein_mpnn_run.py:344-348 does."""
     chain = result["chain_mask"][b] * result["res_mask"][b]
-    lines = [">{}, score={}, global_score={}, fixed_chains={}, designed_chains={}, model_name={}, git_hash={}, seed={}".format(
+    lines = [">{}, score={}, global_score={}, fixed_chains={}, designed_chains={}, {}={}, git_hash={}, seed={}".format(
         name, _fmt(result.get("native_score", np.full(len(result["S"]), np.nan))[b]),
-        _fmt(result.get("native_global_score", np.full(len(result["S"]), np.nan))[b]), [], ["A"], model_name, "unknown", result["seed"]),
+        _fmt(result.get("native_global_score", np.full(len(result["S"]), np.nan))[b]), [], ["A"],
+        "CA_model_name" if result.get("ca_only") else "model_name", model_name, "unknown", result["seed"]),
         mpnn_to_seq(result["S_input"][b], chain)]
     for m in range(result["S"].shape[1]):
         lines.append(">T={}, sample={}, score={}, global_score={}, seq_recovery={}".format(
@@ -267,29 +295,37 @@ def fasta_records(result: dict, b: int, name: str, model_name: str = "synthetic"
 
 
 class ProteinMPNN:
-    """The vanilla ProteinMPNN (hidden 128, 3 + 3 layers, vocabulary 21) with ``k_neighbors`` neighbours per row."""
+    """ProteinMPNN (hidden 128, 3 + 3 layers, vocabulary 21) with ``k_neighbors`` neighbours per row: the vanilla full-backbone model, or
+    with ``ca_only`` the CA-only one, whose features read nothing but the CA trace."""
 
-    def __init__(self, k_neighbors: int = 48):
+    def __init__(self, k_neighbors: int = 48, ca_only: bool = False):
         if not 1 <= int(k_neighbors) <= MAX_NEIGHBORS:
             raise ValueError(f"k_neighbors {k_neighbors} outside 1 .. {MAX_NEIGHBORS}")
         self.k_neighbors = int(k_neighbors)
+        self.ca_only = bool(ca_only)
         self.noise_level = None
         self.source = None      # "synthetic(seed)" or the checkpoint's path
         self.image = None       # the packed float32 image (NumPy)
         self._device_image = {}
 
     def dims(self):
-        return _lib.MpnnDims(hidden=HIDDEN, enc_layers=LAYERS, dec_layers=LAYERS, vocab=VOCAB, k_neighbors=self.k_neighbors)
+        return _lib.MpnnDims(hidden=HIDDEN, enc_layers=LAYERS, dec_layers=LAYERS, vocab=VOCAB, k_neighbors=self.k_neighbors, ca_only=int(self.ca_only))
 
     # ---- parameters
     def load_state_dict(self, sd):
-        self.image = pack_image(sd)
+        """A state dict under the reference's names.  A CA-only model is known by its 167-column ``features.edge_embedding.weight``;
+        ValueError where that disagrees with the ``ca_only`` this object was built with."""
+        if is_ca_state_dict(sd) != self.ca_only:
+            raise ValueError("the state dict holds the {} model (features.edge_embedding.weight has {} columns) but this is ProteinMPNN(ca_only={})".format(
+                "CA-only" if not self.ca_only else "vanilla full-backbone", int(sd["features.edge_embedding.weight"].shape[1])
+                if "features.edge_embedding.weight" in sd else "no", self.ca_only))
+        self.image = pack_image(sd, self.ca_only)
         self._device_image = {}
         return self
 
     def load_synthetic(self, seed: int = 0):
         self.source = f"synthetic({seed})"
-        return self.load_state_dict(synthetic_state_dict(seed, self.k_neighbors))
+        return self.load_state_dict(synthetic_state_dict(seed, self.k_neighbors, self.ca_only))
 
     def load_checkpoint(self, path):
         """A ``.pt`` file in the layout of protein_mpnn_run.py:160-168: ``model_state_dict``, ``num_edges`` (K), ``noise_level``."""
@@ -311,13 +347,17 @@ class ProteinMPNN:
         return self._device_image[key]
 
     # ---- inputs
-    @staticmethod
-    def _inputs(prot, res_mask, chain_mask, residue_index, chain_idx):
-        if len(prot.shape) == 3:
+    def _inputs(self, prot, res_mask, chain_mask, residue_index, chain_idx):
+        shape = tuple(prot.shape)
+        if self.ca_only and (len(shape) == 2 or (len(shape) == 3 and shape[1] not in (37, 5, 1))) and shape[-1] == 3:
+            prot = prot[None, :, None] if len(shape) == 2 else prot[:, :, None]  # a CA trace [N,3] or [B,N,3] as [B,N,1,3]
+        elif len(shape) == 3:
             prot = prot[None]
-        b, n, _ = _call.structure_shape(prot, items="backbones")
+        b, n, _ = _call.structure_shape(prot, atoms=(37, 5, 1) if self.ca_only else (37, 5), items="backbones")
         if n > MAX_ROWS:
             raise ValueError(f"{n} rows: at most {MAX_ROWS}")
+        if self.ca_only and n < 3:
+            raise ValueError(f"{n} rows: the CA-only model needs at least 3")
         dev, (x,) = _call.upload("ProteinMPNN", prot=prot)
 
         def rows(v, what, kind, default=None):  # (on the host: the planning of orders, ties and scores reads them; one backbone's [N] serves B = 1)
@@ -383,7 +423,8 @@ class ProteinMPNN:
     # ---- the two entry points
     def score(self, prot, S, res_mask=None, chain_mask=None, residue_index=None, chain_idx=None, decoding_order=None, seed=None) -> dict:
         """Teacher-forced log-probabilities (``forward(..., use_input_decoding_order=True)``).  prot [B,N,37|5,3] float32 (device tensor
-        or NumPy; a single [N,..] backbone gains B = 1); S [B,N] or [B,M,N] model letters; decoding_order [B,M,N] / [B,N] or None: drawn
+        or NumPy; a single [N,..] backbone gains B = 1; a CA-only model reads atom 1 of either layout and also takes the CA trace alone
+        as [B,N,3], [N,3] or [B,N,1,3] - a 3-D array whose middle extent is 37, 5 or 1 is one backbone [N,atoms,3]); S [B,N] or [B,M,N] model letters; decoding_order [B,M,N] / [B,N] or None: drawn
         as the reference draws it from ``torch.Generator().manual_seed(seed)``.  Returns ``log_probs`` [B,M,N,21] (0 in rows without
         res_mask), ``score`` and ``global_score`` [B,M], ``E_idx`` [B,N,K_eff], ``decoding_order``, ``status`` [B]."""
         import torch
@@ -479,7 +520,8 @@ class ProteinMPNN:
                 "probs": des["probs"], "log_probs": rescored["log_probs"], "decoding_order": order, "u": u,
                 "score": scores_of(rescored["log_probs"], S, designed[:, None]), "global_score": scores_of(rescored["log_probs"], S, res_mask[:, None]),
                 "seq_recovery": recovery, "E_idx": des["E_idx"], "status": des["status"] | rescored["status"],
-                "S_input": s_in, "res_mask": res_mask, "chain_mask": chain_mask, "temperature": temperature, "seed": seed, "tie_group": tie_group.astype(np.int64)}
+                "S_input": s_in, "res_mask": res_mask, "chain_mask": chain_mask, "temperature": temperature, "seed": seed, "tie_group": tie_group.astype(np.int64),
+                "ca_only": self.ca_only}
 
     def unconditional_probs(self, prot, res_mask=None, residue_index=None, chain_idx=None) -> dict:
         """``unconditional_probs`` of the reference: the decoder with no neighbour counted as decoded, what the backbone alone says.

@@ -565,7 +565,7 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
 
 
 def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, seq_per_sample: int = 8, weights=None, temperature: float = 0.1,
-               seed: int = 38, max_batch: int = 16, omit_aas: str = "X"):
+               seed: int = 38, max_batch: int = 16, omit_aas: str = "X", ca_only: bool = False):
     """Rank 0, after the gather (``--design``; framedipt_amd/inverse_folding.py): ``seq_per_sample`` ProteinMPNN sequences per sample at the
     reference's settings (``--sampling_temp 0.1 --seed 38``, X omitted), what experiments/inference.py:run_protein_mpnn starts a subprocess
     for.  De novo runs design every row; inpainting runs design the diffused rows with the context fixed to its true residue types.
@@ -573,9 +573,11 @@ def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, 
     the output: such sequences exercise the path and mean nothing).  Writes ``seqs/<sample>.fa`` in the reference's FASTA layout and
     ``design.json``.  ``omit_aas`` (``--omit-aas``): the letters never drawn.  Inpainting runs add ``native_conditional_score`` per sample:
     the mean negative conditional log-probability (``conditional_probs``: every other letter given) of the TRUE letters of the diffused
-    rows on the sampled backbone.  Returns the summary written."""
+    rows on the sampled backbone.  ``ca_only`` (``--ca-only``): the CA-only model (``weights`` must then be a CA
+    checkpoint), which reads the CA trace of the samples alone; the same files, the FASTA header says ``CA_model_name=``.  Returns the
+    summary written."""
     from . import inverse_folding
-    model = inverse_folding.ProteinMPNN()
+    model = inverse_folding.ProteinMPNN(ca_only=ca_only)
     model = model.load_checkpoint(weights) if weights else model.load_synthetic(0)
     os.makedirs(os.path.join(out_dir, "seqs"), exist_ok=True)
     by_length = {}
@@ -610,7 +612,7 @@ def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, 
                                  "fasta": fasta}
                 if native is not None:
                     samples[stem]["native_conditional_score"] = float(native[b])
-    summary = {"weights": model.source, "synthetic": not weights, "k_neighbors": model.k_neighbors, "temperature": temperature, "seed": seed,
+    summary = {"weights": model.source, "synthetic": not weights, "ca_only": model.ca_only, "k_neighbors": model.k_neighbors, "temperature": temperature, "seed": seed,
                "seq_per_sample": seq_per_sample, "omit": omit_aas, "samples": samples}
     with open(os.path.join(out_dir, "design.json"), "w") as f:
         json.dump(summary, f, indent=1)
@@ -737,6 +739,7 @@ def main():
                     "every row, inpainting runs the diffused rows with the context fixed")
     ap.add_argument("--seq-per-sample", type=int, default=8, help="--design: sequences per sample (the reference's inference.samples.seq_per_sample)")
     ap.add_argument("--omit-aas", default="X", help="--design: the letters never drawn (ProteinMPNN's --omit_AAs)")
+    ap.add_argument("--ca-only", action="store_true", help="--design: the CA-only ProteinMPNN (reads the CA trace alone; --mpnn-weights must then be a CA checkpoint)")
     ap.add_argument("--mpnn-weights", default=None, help="--design: a ProteinMPNN checkpoint (.pt with model_state_dict, num_edges, noise_level); default: "
                     "SYNTHETIC parameters, stated as such in the output")
     ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score, --tm-align: the TM-score threshold of the clusters (reference default)")
@@ -894,8 +897,8 @@ def main():
             print(f"structural alignments of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
         if a.design:
             t1 = time.perf_counter()
-            done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights, omit_aas=a.omit_aas)
-            print(f"{a.seq_per_sample} sequence(s) for each of {len(done['samples'])} sample(s) with {'SYNTHETIC ProteinMPNN parameters' if done['synthetic'] else done['weights']} "
+            done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights, omit_aas=a.omit_aas, ca_only=a.ca_only)
+            print(f"{a.seq_per_sample} sequence(s) for each of {len(done['samples'])} sample(s) with {'SYNTHETIC ' if done['synthetic'] else ''}{'CA-only ' if done['ca_only'] else ''}ProteinMPNN parameters{'' if done['synthetic'] else ' of ' + str(done['weights'])} "
                   f"in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/seqs/<sample>.fa, design.json", flush=True)
     if world > 1:
         dist.destroy_process_group()

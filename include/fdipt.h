@@ -729,8 +729,16 @@ int fdipt_sample_tm_align(const FdiptTmAlignArgs* args, fdipt_stream_t stream);
  *       dense.W_in^T [128][512], b [512]; dense.W_out^T [512][128], b [128]; norm2 weight, bias;
  *       W11^T [384][128], b; W12^T [128][128], b; W13^T [128][128], b; norm3 weight, bias
  *   decoder_layers.l, l = 0 .. 2:  W1^T [512][128], b; W2^T, b; W3^T, b; norm1; dense.W_in^T, b; dense.W_out^T, b; norm2
- *   W_out.weight^T [128][21], W_out.bias [21] */
-#define FDIPT_MPNN_MAX_ROWS 2048      /* N beyond: FDIPT_ESIZE                                                                       */
+ *   W_out.weight^T [128][21], W_out.bias [21]
+ *
+ * FdiptMpnnDims.ca_only = 1 is the CA-only model (CA_ProteinFeatures, ProteinMPNN(ca_only=True)): the same
+ * model after features that read nothing but the CA trace.  The edge inputs are 167 columns (16 positional, 9 x 16 RBF over the
+ * array-shifted traces, 7 orientation values), the image is the same table with features.edge_embedding.weight^T [167][128], so
+ * fdipt_mpnn_weights_floats is 1 628 613 = 1 660 485 - 249 x 128; the five parameters the reference's forward never reads
+ * (features.node_embedding, features.norm_nodes, W_v) are not in it.  prot may then also be the trace alone, atoms = 1: [B,N,3]; with
+ * 37 or 5 atoms the kernel reads atom 1.  N < 3 is FDIPT_EINVAL (the reference raises there).  E_idx, the workspace and every other
+ * argument are as for the vanilla model. */
+#define FDIPT_MPNN_MAX_ROWS 2048     /* N beyond: FDIPT_ESIZE                                                                       */
 #define FDIPT_MPNN_MAX_SEQ 64         /* M beyond: FDIPT_ESIZE                                                                       */
 #define FDIPT_MPNN_MAX_NEIGHBORS 64   /* k_neighbors outside 1 .. 64: FDIPT_EINVAL                                                   */
 #define FDIPT_MPNN_MASKED_NEIGHBOR 1  /* status: a row with res_mask set has a neighbour without; no parity with the reference there */
@@ -738,11 +746,13 @@ int fdipt_sample_tm_align(const FdiptTmAlignArgs* args, fdipt_stream_t stream);
 typedef struct FdiptMpnnDims {
   int32_t hidden, enc_layers, dec_layers, vocab; /* 128, 3, 3, 21: anything else is FDIPT_EINVAL                                    */
   int32_t k_neighbors;                /* K, the checkpoint's num_edges; a row takes K_eff = min(K, N) neighbours                     */
+  int32_t ca_only;                    /* 0 = the vanilla model (a caller that never names it), 1 = the CA-only one; else FDIPT_EINVAL */
 } FdiptMpnnDims;
 /* floats of the weight image; FDIPT_EINVAL for dims the kernels are not built for */
 int64_t fdipt_mpnn_weights_floats(const FdiptMpnnDims* dims);
 typedef struct FdiptMpnnArgs {
-  int32_t B, N, M, atoms;             /* backbones, rows, sequences per backbone, atoms per row of prot: 37 or 5 (N, CA, C, CB, O)   */
+  int32_t B, N, M, atoms;             /* backbones, rows, sequences per backbone, atoms per row of prot: 37 or 5 (N, CA, C, CB, O);  */
+                                      /* with dims->ca_only also 1: the CA trace                                                     */
   const float* weights;               /* f32 [fdipt_mpnn_weights_floats]                                                             */
   const float* prot;                  /* [B,N,atoms,3] f32: N, CA, C at 0, 1, 2 and O at 4 in both layouts; CB is rebuilt            */
   const float* res_mask;              /* [B,N] f32                                                                                   */
@@ -779,7 +789,8 @@ typedef struct FdiptMpnnArgs {
                                       /* decoding_order are not read and may be NULL                                                 */
 } FdiptMpnnArgs;
 size_t fdipt_mpnn_workspace(const FdiptMpnnDims* dims, int B, int N, int M);
-/* FDIPT_EINVAL: a null pointer the entry reads or writes, unsupported dims, B, N or M < 1, atoms not 37 or 5, temperature <= 0
+/* FDIPT_EINVAL: a null pointer the entry reads or writes, unsupported dims, B, N or M < 1, atoms not 37 or 5 (ca_only: or 1), N < 3
+ * with ca_only, temperature <= 0
  * (design), pssm_bias or pssm_log_odds_mask without pssm_coef (design), tie_group without tied_beta (design).  FDIPT_ESIZE: N >
  * FDIPT_MPNN_MAX_ROWS, M > FDIPT_MPNN_MAX_SEQ, workspace too small.  All before any launch. */
 int fdipt_mpnn_score(const FdiptMpnnDims* dims, const FdiptMpnnArgs* args, fdipt_stream_t stream);

@@ -5,9 +5,11 @@ sequences, the time between device-side events around each C entry, and the time
 work in eager mode, float32, on the same GPU - the stand-in for what the reference's subprocess computes, without its PDB parsing - with
 the number of letters in which the two disagree (float32 rounding next to a boundary of a cumulative distribution; not a parity claim).
 One run; no threshold is attached to these times.  ``--tied``: the same load as a 3 x 100 homo-trimer, row r of the three chains tied
-(DESIGN.md section 7.11); the restatement is then not run.
+(DESIGN.md section 7.11); the restatement is then not run.  ``--ca-only``: the CA-only model on the same traces,
+given as [B,N,3], and the vanilla model's design and score calls next to it in the same run (``vanilla``); the restatement is that of
+tests/mpnn_ca_ref.py.
 
-    python tools/mpnn_wall.py [out.json] [--restatement-sequences K] [--tied]
+    python tools/mpnn_wall.py [out.json] [--restatement-sequences K] [--tied] [--ca-only]
 """
 import argparse
 import json
@@ -21,6 +23,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import mpnn_ca_ref as mc  # noqa: E402
 import mpnn_ref as mr  # noqa: E402
 
 from framedipt_amd import _lib  # noqa: E402
@@ -31,6 +34,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?", default=None)
 ap.add_argument("--restatement-sequences", type=int, default=B * M, help="time the restatement on the first K sequences and scale")
 ap.add_argument("--tied", action="store_true", help="three chains of 100 rows, row r of every chain tied")
+ap.add_argument("--ca-only", action="store_true", help="the CA-only model on the CA traces, the vanilla model beside it")
 cli = ap.parse_args()
 n_restatement = 0 if cli.tied else cli.restatement_sequences
 
@@ -56,11 +60,11 @@ lib.fdipt_mpnn_design, lib.fdipt_mpnn_score = timed("fdipt_mpnn_design"), timed(
 
 rng = np.random.default_rng(0)
 prot = np.stack([mr.backbone(rng, N) for _ in range(B)])
-d_prot = torch.from_numpy(prot).cuda()
-model = inv.ProteinMPNN(K).load_synthetic(mr.WEIGHT_SEED)
+d_prot = torch.from_numpy(np.ascontiguousarray(prot[:, :, 1]) if cli.ca_only else prot).cuda()
+model = inv.ProteinMPNN(K, ca_only=cli.ca_only).load_synthetic(mr.WEIGHT_SEED)
 torch.cuda.synchronize()
 
-out = {"backbones": B, "rows": N, "sequences_per_backbone": M, "k_neighbors": K, "temperature": T, "tied": cli.tied}
+out = {"backbones": B, "rows": N, "sequences_per_backbone": M, "k_neighbors": K, "temperature": T, "tied": cli.tied, "ca_only": cli.ca_only}
 chains = {}
 if cli.tied:
     chains = {"chain_idx": np.tile(np.repeat([1, 2, 3], N // 3), (B, 1)), "residue_index": np.tile(np.arange(N // 3), (B, 3))}
@@ -81,10 +85,25 @@ torch.cuda.synchronize()
 out["score"] = {"first_call_wall_s": walls[0], "call_wall_s": walls[1:], "equals_design_rescoring": bool(np.array_equal(sc["log_probs"], des["log_probs"]))}
 # design() launches the design entry and then the score entry (its rescoring); score() the score entry alone
 out["device_ms"] = {name: [start.elapsed_time(stop) for start, stop in evs] for name, evs in events.items()}
+if cli.ca_only:  # the vanilla model on the full backbones of the same traces, after the CA-only calls, for the comparison of section 7.12
+    for evs in events.values():
+        evs.clear()
+    vanilla, d_full, walls = inv.ProteinMPNN(K).load_synthetic(mr.WEIGHT_SEED), torch.from_numpy(prot).cuda(), {"design": [], "score": []}
+    for _ in range(3):
+        t0 = time.perf_counter()
+        vdes = vanilla.design(d_full, num_seq=M, temperature=T, seed=38, **chains)
+        walls["design"].append(time.perf_counter() - t0)
+    for _ in range(3):
+        t0 = time.perf_counter()
+        vanilla.score(d_full, vdes["S"], decoding_order=vdes["decoding_order"], **{k: v for k, v in chains.items() if k != "tied_positions"})
+        walls["score"].append(time.perf_counter() - t0)
+    torch.cuda.synchronize()
+    out["vanilla"] = {"design_call_wall_s": walls["design"][1:], "score_call_wall_s": walls["score"][1:],
+                      "device_ms": {name: [start.elapsed_time(stop) for start, stop in evs] for name, evs in events.items()}}
 print(json.dumps(out), flush=True)
 
 # the torch restatement, eager, float32, on the same GPU: encoder once per backbone, then per sequence the design loop and its rescoring
-sd = inv.synthetic_state_dict(mr.WEIGHT_SEED, K)
+sd = inv.synthetic_state_dict(mr.WEIGHT_SEED, K, ca_only=cli.ca_only)
 ref = mr.Model(sd, K, torch.float32, "cuda")
 ones, index = np.ones(N, np.float32), np.arange(N)
 omit = np.array([0.0] * 20 + [1.0], np.float32)
@@ -96,7 +115,7 @@ with torch.no_grad():
             break
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        enc = mr.encode(ref, prot[b], ones, index, ones)
+        enc = mc.encode_ca(ref, prot[b][:, 1], ones, index, ones) if cli.ca_only else mr.encode(ref, prot[b], ones, index, ones)
         torch.cuda.synchronize()
         t_enc += time.perf_counter() - t0
         for m in range(M):
