@@ -295,6 +295,70 @@ def run_violations(out_dir: str, records, gathered: dict):
     return summary
 
 
+def run_lddt(out_dir: str, records, gathered: dict, inpainting: bool = False, selected=None):
+    """Rank 0, after the gather (``--lddt``; framedipt_amd/lddt.py).  Inpainting runs: per structure name every sample - and, with
+    ``selected`` (what ``run_selection`` kept), the five selected structures - against the ground truth (``gt`` of a gathered entry) in
+    the atom sets ``ca`` and ``backbone``, score_mask = the diffused rows that exist, the context as environment.  Writes ``lddt.json``
+    (per sample the flat metrics and the per-residue arrays of the diffused rows) and ``lddt.csv`` (one row per sample: pdb_name, sample,
+    lddt_ca, lddt_bb, drmsd, fape, region_fape); a structure without ground truth is listed as skipped.  De novo runs: per sample length
+    one all-against-all call on the CA atoms: ``pairwise_lddt_ca_length_<L>.npy`` (row = model, column = reference) and
+    ``consistency.json`` with every sample's mean off-diagonal lDDT and its ``consensus`` profile.  Returns the summary written."""
+    import csv
+
+    from . import lddt, selection
+    if not inpainting:
+        by_length = {}
+        for r in sorted(records, key=lambda x: x["item"]):
+            by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+        summary = {"atoms": "ca", "lengths": []}
+        for length in sorted(by_length):
+            rs = by_length[length]
+            prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
+            mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+            res = lddt.local_accuracy(prot, atoms="ca", res_mask=mask)
+            np.save(os.path.join(out_dir, f"pairwise_lddt_ca_length_{length}.npy"), res["matrix"])
+            summary["lengths"].append({"length": length, "samples": [
+                {"pdb_name": r["name"], "sample": r["sample_i"], "mean_lddt": float(np.delete(res["matrix"][s], s).mean()) if len(rs) > 1 else None,
+                 "consensus": res["consensus"][s].tolist()} for s, r in enumerate(rs)]})
+        with open(os.path.join(out_dir, "consistency.json"), "w") as f:
+            json.dump(summary, f, indent=1)
+        return summary
+    columns = ["lddt_ca", "lddt_bb", "drmsd", "fape", "region_fape"]
+    summary, table = {"atoms": ["ca", "backbone"], "score_mask": "diffused rows", "samples": [], "skipped": []}, []
+    for g, (name, rs) in enumerate(group_records_by_name(records).items()):
+        items = [gathered[r["item"]] for r in rs]
+        truth = next((it["gt"] for it in items if "gt" in it), None)
+        if truth is None:
+            summary["skipped"].append(str(name))
+            continue
+        n = items[0]["prot"].shape[0]
+        labels, structures, sources = [str(r["sample_i"]) for r in rs], [it["prot"] for it in items], list(items)
+        if selected is not None:
+            labels += list(selection.STRATEGIES)
+            structures += [selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n] for strategy in selection.STRATEGIES]
+            sources += [items[0]] * len(selection.STRATEGIES)
+        prot = np.stack(structures).astype(np.float32)
+        res_mask = np.stack([np.ones(n, dtype=np.float32) if it.get("res_mask") is None else it["res_mask"] for it in sources]).astype(np.float32)
+        score = np.stack([it["diffused"] for it in sources]).astype(np.float32) * res_mask
+        reference = np.asarray(truth, dtype=np.float32)[None]
+        ca = lddt.local_accuracy(prot, reference, atoms="ca", res_mask=res_mask, score_mask=score)
+        bb = lddt.local_accuracy(prot, reference, atoms="backbone", res_mask=res_mask, score_mask=score)
+        for s, label in enumerate(labels):
+            rows = np.flatnonzero(score[s])
+            values = {**lddt.lddt_metrics(ca, s), "lddt_bb": lddt.lddt_metrics(bb, s)["lddt_bb"]}
+            summary["samples"].append({"pdb_name": str(name), "sample": label, **{k: values[k] for k in columns}, "status": int(ca["status"][s] | bb["status"][s]),
+                                       "rows": rows.tolist(), "res_lddt_ca": ca["res_lddt"][s][rows].tolist(), "res_lddt_bb": bb["res_lddt"][s][rows].tolist(),
+                                       "res_fape": ca["res_fape"][s][rows].tolist()})
+            table.append({"pdb_name": str(name), "sample": label, **{k: repr(values[k]) for k in columns}})
+    with open(os.path.join(out_dir, "lddt.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "lddt.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample"] + columns)
+        w.writeheader()
+        w.writerows(table)
+    return summary
+
+
 def run_secondary_structure(out_dir: str, records, gathered: dict):
     """Rank 0, after the gather (``--secondary-structure``): one ``secondary_structure.secondary_structure`` call over every sample of the
     run with its res_mask, chain_idx and aatype (a proline donates no hydrogen bond); shorter samples are padded with res_mask = 0
@@ -734,6 +798,11 @@ def main():
                     "a TM-align style search, this project's own contract; no parity with tmtools is claimed).  De novo runs: all-against-all per sample "
                     "length, the larger of the searched and the fixed score: pairwise_tm_score_aligned_length_<L>.npy, diversity_aligned.json, "
                     "diversity_aligned.csv.  Inpainting runs: the aligned matrix per structure: tm_align.json")
+    ap.add_argument("--lddt", action="store_true", help="after the run, rank 0 computes the superposition-free accuracy scores on its GPU (framedipt_amd/lddt.py: "
+                    "lDDT, dRMSD and backbone FAPE).  Inpainting runs: every sample (and with --select the five selected structures) against the ground "
+                    "truth on the CA and the backbone atoms, scored over the diffused rows with the context as environment: lddt.json and lddt.csv.  "
+                    "De novo runs: all-against-all CA lDDT per sample length: pairwise_lddt_ca_length_<L>.npy and consistency.json (per sample the mean "
+                    "lDDT against the others and the per-residue consensus)")
     ap.add_argument("--design", action="store_true", help="after the run, rank 0 designs sequences for every sample on its GPU (framedipt_amd/inverse_folding.py: "
                     "ProteinMPNN at T = 0.1, seed 38, X omitted, as the reference's run_protein_mpnn): seqs/<sample>.fa and design.json.  De novo runs design "
                     "every row, inpainting runs the diffused rows with the context fixed")
@@ -836,9 +905,9 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt else None
     ground_truth = None
-    if (a.evaluate or a.sasa or a.tm_score) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
+    if (a.evaluate or a.sasa or a.tm_score or a.lddt) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
             build = lambda: inference.get_atom_positions_from_rigids(net, feats["rigids_0"], feats["torsion_angles_sin_cos"][..., 2, :], feats["aatype"])[0]  # noqa: E731
             return one_gpu_turn(build) if one_gpu and world > 1 else build()
@@ -849,7 +918,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -858,7 +927,7 @@ def main():
                                                                 **({} if a.keep == "all" else {"keep": a.keep})})
         print(f"{sum(r['n_res'] for r in allrecs) * a.num_t / el:.0f} residue*steps/s (incl. model set-up and file output)")
         print(f"{len(ds)} samples on {world} GPU(s) in {el:.1f} s -> {a.out_dir}/manifest.json", flush=True)
-        selected = {} if a.select and a.evaluate else None
+        selected = {} if a.select and (a.evaluate or a.lddt) else None
         if a.select:
             t1 = time.perf_counter()
             done = run_selection(a.out_dir, allrecs, gathered, reference_layout=inp, sigma=a.select_sigma, max_iterations=a.select_iterations, keep=selected)
@@ -895,6 +964,12 @@ def main():
             what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_align.json" if inp else \
                 f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity_aligned.json, diversity_aligned.csv, pairwise_tm_score_aligned_length_<L>.npy"
             print(f"structural alignments of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
+        if a.lddt:
+            t1 = time.perf_counter()
+            done = run_lddt(a.out_dir, allrecs, gathered, inpainting=inp, selected=selected if inp else None)
+            what = f"{len(done['samples'])} structure(s) -> {a.out_dir}/lddt.json, lddt.csv" if inp else \
+                f"{len(done['lengths'])} length(s) -> {a.out_dir}/consistency.json, pairwise_lddt_ca_length_<L>.npy"
+            print(f"lDDT, dRMSD and FAPE of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
         if a.design:
             t1 = time.perf_counter()
             done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights, omit_aas=a.omit_aas, ca_only=a.ca_only)

@@ -713,6 +713,66 @@ size_t fdipt_sample_tm_align_workspace(int S, int N_a, int N_b, int P);
  * FDIPT_TMA_MAX_ROWS. */
 int fdipt_sample_tm_align(const FdiptTmAlignArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- superposition-free accuracy (opt-in) */
+/* lDDT (Mariani et al. 2013; openfold/utils/loss.py lddt :382, lddt_ca :438), dRMSD (compute_drmsd :1518) and backbone FAPE (compute_fape
+ * :76 as backbone_loss :152 calls it: clamp 10, unit 10, eps 1e-4) of P ordered pairs (model structure a, reference structure b) in row
+ * correspondence, float32 coordinates widened, all arithmetic float64 with contraction off, in two launches on one stream.  The
+ * contract is DESIGN.md section 7.13.
+ * A row exists where res_mask[a] != 0; a row that does not exist is skipped everywhere.  A score row (score_mask[a] != 0 and it exists)
+ * has its scores reported and enters the pair's numbers; partners, points and frames are always all existing rows.  An atom takes part
+ * where it exists in both structures: atom_mask != 0, or without a mask any non-zero coordinate.
+ * Atom set (mode): CA = column 1 (column 0 of a CA trace, atoms = 1); BACKBONE = N, CA, C, O = columns 0, 1, 2, 4 of atom37 and of the
+ * five-atom layout; ALL = the 37 columns of atom37.  A = 1, 4, 37 atoms per row.
+ * lDDT: the atom pair (u, v) of rows (i, j) is scored where d_b = sqrt(1e-10 + |x_u - x_v|^2) of the reference < cutoff, both take part,
+ * u != v, and i != j in the multi-atom sets unless same_residue (then it is the reference's lddt on the flattened atom list).  Per atom
+ * u the integers c (scored pairs) and n_t (scored pairs with |d_b - d_a| < t; t = 0.5, 1, 2, 4); score = (1 / (1e-10 + c)) * (1e-10 +
+ * 0.25 (n_0.5 + n_1 + n_2 + n_4)) per atom, per row (its atoms' integers summed) and per pair (the score rows' summed, int64).
+ * dRMSD: over the CA atoms that take part of the score rows, n of them: sqrt(sum_{i != j} (d_a - d_b)^2 / (n (n - 1))), plain
+ * distances, 0 for n <= 1 (compute_drmsd on these rows without its mask argument).
+ * FAPE: frame i = from_3_points(C, CA, N, eps 1e-8) with the first and third column negated (data_transforms.atom37_to_frames, group
+ * 0) of every existing row whose N, CA and C take part, for both structures; points = the CA atoms that take part of all existing
+ * rows; e_ij = min(sqrt(|R_i^T (x_j - t_i) - G_i^T (y_j - u_i)|^2 + 1e-4), 10) / 10; fape = sum_i (sum_j e_ij / (1e-4 + n_frames)) /
+ * (1e-4 + n_points); res_fape[i] = sum_j e_ij / (1e-4 + n_points); region_fape = the mean of res_fape over the score rows with a frame.
+ * Every sum runs in a fixed order that depends on the pair's own rows only; no floating-point atomics. */
+#define FDIPT_LDDT_CA 0
+#define FDIPT_LDDT_BACKBONE 1
+#define FDIPT_LDDT_ALL 2
+#define FDIPT_LDDT_TILE 256          /* partner rows per LDS tile of the CA and BACKBONE sets                                       */
+#define FDIPT_LDDT_TILE_ALL 64       /* ... of the ALL set                                                                          */
+#define FDIPT_LDDT_NO_PARTNER 1      /* status: a score row has no scored pair (c = 0): its lDDT is the reference's eps / eps = 1   */
+#define FDIPT_LDDT_NO_FRAME 2        /* status: no row has a frame (a CA trace among them): fape, res_fape, region_fape are 0       */
+#define FDIPT_LDDT_SKIPPED 4         /* status: a structure index of the pair is out of range; every output of the pair is 0        */
+typedef struct FdiptLddtArgs {
+  int32_t S, N, atoms;               /* model structures, rows, atoms per row of prot: 37, 5 or 1 (a CA trace)                      */
+  int32_t S_b, atoms_b;              /* of prot_b (ignored where prot_b is NULL)                                                    */
+  int32_t P, mode, same_residue;     /* pairs; FDIPT_LDDT_CA / BACKBONE / ALL; 1: atom pairs inside a row are scored too            */
+  double cutoff;                     /* inclusion radius on the reference's distances (15)                                          */
+  const float* prot;                 /* [S,N,atoms,3] f32                                                                           */
+  const float* prot_b;               /* [S_b,N,atoms_b,3] f32 or NULL: the reference structure of a pair comes from here, else from prot */
+  const float* res_mask;             /* [S,N] f32                                                                                   */
+  const float* score_mask;           /* [S,N] f32                                                                                   */
+  const uint8_t* atom_mask_a;        /* [S,N,atoms] u8 or NULL                                                                      */
+  const uint8_t* atom_mask_b;        /* [S_b,N,atoms_b] u8 ([S,N,atoms] without prot_b) or NULL                                     */
+  const int32_t* pairs;              /* [P,2] i32: (model: index into prot, reference: index into prot_b or prot)                   */
+  /* outputs */
+  double* lddt;                      /* [P] f64                                                                                     */
+  double* res_lddt;                  /* [P,N] f64; 0 at rows that are no score rows                                                 */
+  int32_t* n_scored;                 /* [P,N] i32: c of the row                                                                     */
+  int32_t* n_passed;                 /* [P,N,4] i32: n_0.5, n_1, n_2, n_4 of the row                                                */
+  double* atom_lddt;                 /* [P,N,A] f64 or NULL: per atom of the score rows (an atom without a scored pair: eps / eps)  */
+  double* drmsd;                     /* [P] f64                                                                                     */
+  double* fape;                      /* [P] f64                                                                                     */
+  double* res_fape;                  /* [P,N] f64; 0 where the row has no frame                                                     */
+  double* region_fape;               /* [P] f64; 0 where no score row has a frame                                                   */
+  int32_t* status;                   /* [P] i32: FDIPT_LDDT_* bits                                                                  */
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptLddtArgs;
+size_t fdipt_sample_lddt_workspace(int P, int N);
+/* FDIPT_EINVAL: a null pointer, S, N or P < 1, a layout or mode outside the above, ALL without atom37 in both structures, a cutoff that
+ * is not positive.  FDIPT_ESIZE: workspace too small, more row tiles than a grid holds, N A A beyond an int32 row counter. */
+int fdipt_sample_lddt(const FdiptLddtArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- inverse folding (opt-in) */
 /* The vanilla full-backbone ProteinMPNN (ProteinMPNN/protein_mpnn_utils.py: ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward
  * and .sample), inference only, float32 throughout; the contract is DESIGN.md section 7.10.  Letters are in the MODEL's alphabet
