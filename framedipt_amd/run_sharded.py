@@ -359,6 +359,76 @@ def run_lddt(out_dir: str, records, gathered: dict, inpainting: bool = False, se
     return summary
 
 
+def write_gdt(out_dir: str, structures: dict, skipped=()):
+    """``structures``: name -> {"samples": [labels], "n_scored": [S], "fixed" and "search": {"gdt_ts": [S], "gdt_ha": [S]} (no
+    superposition: the frame of the fixed context; the searched superposition per cutoff), "counts_fixed" and "counts": [S,5], "status":
+    [S]}.  Writes ``gdt.json`` (all of it, with the names in ``skipped``) and ``gdt.csv`` (one row per sample: pdb_name, sample,
+    n_scored, gdt_ts_fixed, gdt_ha_fixed, gdt_ts, gdt_ha).  Returns the summary written to ``gdt.json``."""
+    import csv
+
+    from . import gdt
+    number = lambda v: None if v != v else float(v)  # noqa: E731  (NaN: a status bit)
+    summary = {"cutoffs": list(gdt.CUTOFFS), "rows": "diffused rows that exist", "superposition": "search: DESIGN.md section 7.14 (no parity with LGA is claimed)",
+               "structures": {}, "skipped": [str(n) for n in skipped]}
+    table = []
+    for name, e in structures.items():
+        summary["structures"][name] = {"samples": list(e["samples"]), "n_scored": [int(v) for v in e["n_scored"]],
+                                       "gdt_ts_fixed": [number(v) for v in e["fixed"]["gdt_ts"]], "gdt_ha_fixed": [number(v) for v in e["fixed"]["gdt_ha"]],
+                                       "gdt_ts": [number(v) for v in e["search"]["gdt_ts"]], "gdt_ha": [number(v) for v in e["search"]["gdt_ha"]],
+                                       "counts_fixed": np.asarray(e["counts_fixed"]).tolist(), "counts": np.asarray(e["counts"]).tolist(),
+                                       "status": [int(v) for v in e["status"]]}
+        table += [{"pdb_name": name, "sample": label, "n_scored": int(e["n_scored"][s]), "gdt_ts_fixed": repr(float(e["fixed"]["gdt_ts"][s])),
+                   "gdt_ha_fixed": repr(float(e["fixed"]["gdt_ha"][s])), "gdt_ts": repr(float(e["search"]["gdt_ts"][s])), "gdt_ha": repr(float(e["search"]["gdt_ha"][s]))}
+                  for s, label in enumerate(e["samples"])]
+    with open(os.path.join(out_dir, "gdt.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "gdt.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "n_scored", "gdt_ts_fixed", "gdt_ha_fixed", "gdt_ts", "gdt_ha"])
+        w.writeheader()
+        w.writerows(table)
+    return summary
+
+
+def run_gdt(out_dir: str, records, gathered: dict, inpainting: bool = False, selected=None):
+    """Rank 0, after the gather (``--gdt``; framedipt_amd/gdt.py).  Inpainting runs: per structure name every sample - and, with
+    ``selected`` (what ``run_selection`` kept), the five selected structures - against the ground truth (``gt`` of a gathered entry) over
+    the diffused rows that exist, without a superposition and with the searched one, then ``write_gdt``; a structure without ground
+    truth is listed as skipped.  De novo runs: per sample length one all-against-all searched call:
+    ``pairwise_gdt_ts_length_<L>.npy``.  Returns the summary written (de novo: {"lengths": [...]})."""
+    from . import gdt, selection
+    if not inpainting:
+        by_length = {}
+        for r in sorted(records, key=lambda x: x["item"]):
+            by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+        for length in sorted(by_length):
+            rs = by_length[length]
+            prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
+            mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+            np.save(os.path.join(out_dir, f"pairwise_gdt_ts_length_{length}.npy"), gdt.gdt_scores(prot, mask_a=mask)["matrix_ts"])
+        return {"lengths": sorted(by_length)}
+    structures, skipped = {}, []
+    for g, (name, rs) in enumerate(group_records_by_name(records).items()):
+        items = [gathered[r["item"]] for r in rs]
+        truth = next((it["gt"] for it in items if "gt" in it), None)
+        if truth is None:
+            skipped.append(str(name))
+            continue
+        n = items[0]["prot"].shape[0]
+        labels, models, sources = [str(r["sample_i"]) for r in rs], [it["prot"] for it in items], list(items)
+        if selected is not None:
+            labels += list(selection.STRATEGIES)
+            models += [selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n] for strategy in selection.STRATEGIES]
+            sources += [items[0]] * len(selection.STRATEGIES)
+        prot = np.stack(models).astype(np.float32)
+        mask = np.stack([it["diffused"] * (1 if it.get("res_mask") is None else it["res_mask"]) for it in sources]).astype(np.float32)
+        reference = np.asarray(truth, dtype=np.float32)[None]
+        fixed = gdt.gdt_scores(prot, reference, mask_a=mask, superpose="none")
+        search = gdt.gdt_scores(prot, reference, mask_a=mask, superpose="search")
+        structures[str(name)] = {"samples": labels, "n_scored": search["n_scored"], "fixed": fixed, "search": search, "counts_fixed": fixed["counts"],
+                                 "counts": search["counts"], "status": fixed["status"] | search["status"]}
+    return write_gdt(out_dir, structures, skipped)
+
+
 def run_secondary_structure(out_dir: str, records, gathered: dict):
     """Rank 0, after the gather (``--secondary-structure``): one ``secondary_structure.secondary_structure`` call over every sample of the
     run with its res_mask, chain_idx and aatype (a proline donates no hydrogen bond); shorter samples are padded with res_mask = 0
@@ -803,6 +873,10 @@ def main():
                     "truth on the CA and the backbone atoms, scored over the diffused rows with the context as environment: lddt.json and lddt.csv.  "
                     "De novo runs: all-against-all CA lDDT per sample length: pairwise_lddt_ca_length_<L>.npy and consistency.json (per sample the mean "
                     "lDDT against the others and the per-residue consensus)")
+    ap.add_argument("--gdt", action="store_true", help="after the run, rank 0 computes GDT-TS and GDT-HA on its GPU (framedipt_amd/gdt.py).  Inpainting runs: every "
+                    "sample (and with --select the five selected structures) against the ground truth over the diffused rows that exist, without a "
+                    "superposition (the frame of the fixed context) and with the searched one: gdt.json and gdt.csv.  De novo runs: all-against-all searched "
+                    "GDT-TS per sample length: pairwise_gdt_ts_length_<L>.npy")
     ap.add_argument("--design", action="store_true", help="after the run, rank 0 designs sequences for every sample on its GPU (framedipt_amd/inverse_folding.py: "
                     "ProteinMPNN at T = 0.1, seed 38, X omitted, as the reference's run_protein_mpnn): seqs/<sample>.fa and design.json.  De novo runs design "
                     "every row, inpainting runs the diffused rows with the context fixed")
@@ -905,9 +979,9 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt else None
     ground_truth = None
-    if (a.evaluate or a.sasa or a.tm_score or a.lddt) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
+    if (a.evaluate or a.sasa or a.tm_score or a.lddt or a.gdt) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
             build = lambda: inference.get_atom_positions_from_rigids(net, feats["rigids_0"], feats["torsion_angles_sin_cos"][..., 2, :], feats["aatype"])[0]  # noqa: E731
             return one_gpu_turn(build) if one_gpu and world > 1 else build()
@@ -918,7 +992,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -927,7 +1001,7 @@ def main():
                                                                 **({} if a.keep == "all" else {"keep": a.keep})})
         print(f"{sum(r['n_res'] for r in allrecs) * a.num_t / el:.0f} residue*steps/s (incl. model set-up and file output)")
         print(f"{len(ds)} samples on {world} GPU(s) in {el:.1f} s -> {a.out_dir}/manifest.json", flush=True)
-        selected = {} if a.select and (a.evaluate or a.lddt) else None
+        selected = {} if a.select and (a.evaluate or a.lddt or a.gdt) else None
         if a.select:
             t1 = time.perf_counter()
             done = run_selection(a.out_dir, allrecs, gathered, reference_layout=inp, sigma=a.select_sigma, max_iterations=a.select_iterations, keep=selected)
@@ -970,6 +1044,12 @@ def main():
             what = f"{len(done['samples'])} structure(s) -> {a.out_dir}/lddt.json, lddt.csv" if inp else \
                 f"{len(done['lengths'])} length(s) -> {a.out_dir}/consistency.json, pairwise_lddt_ca_length_<L>.npy"
             print(f"lDDT, dRMSD and FAPE of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
+        if a.gdt:
+            t1 = time.perf_counter()
+            done = run_gdt(a.out_dir, allrecs, gathered, inpainting=inp, selected=selected if inp else None)
+            what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/gdt.json, gdt.csv" if inp else \
+                f"{len(done['lengths'])} length(s) -> {a.out_dir}/pairwise_gdt_ts_length_<L>.npy"
+            print(f"GDT-TS and GDT-HA of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
         if a.design:
             t1 = time.perf_counter()
             done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights, omit_aas=a.omit_aas, ca_only=a.ca_only)

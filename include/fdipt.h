@@ -773,6 +773,59 @@ size_t fdipt_sample_lddt_workspace(int P, int N);
  * is not positive.  FDIPT_ESIZE: workspace too small, more row tiles than a grid holds, N A A beyond an int32 row counter. */
 int fdipt_sample_lddt(const FdiptLddtArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- GDT-TS / GDT-HA (opt-in) */
+/* The global distance test (openfold/utils/validation_metrics.py gdt, gdt_ts, gdt_ha) of P pairs (model, reference) in row
+ * correspondence, in float64 with contraction off, in one launch of a block per pair.  The contract is DESIGN.md section 7.14.
+ * x, y: the CA atoms of the rows where both structures' masks are set, in ascending row order, float32 widened; n their number;
+ * L = norm_length of the pair where given and > 0, else n.  Cutoffs c = (0.5, 1, 2, 4, 8) Angstrom; under a transform T,
+ * count_k(T) = #{i : |T x_i - y_i|^2 <= c_k^2}.  gdt_ts = (count_1 + count_2 + count_3 + count_4) / (4 L), gdt_ha = (count_0 + count_1 +
+ * count_2 + count_3) / (4 L), the integers summed first, one division.
+ * mode NONE: T the identity (the reference's gdt on the raw coordinates; n >= 1).  GLOBAL: the least-squares superposition of all n
+ * rows (Horn, proper rotation), one T for every cutoff (superimpose, then gdt; n >= 3).  SEARCH (n >= 3): per cutoff the largest count
+ * over every transform the search visits.  A work item is (refinement cutoff k, seed), numbered k * n_seeds + seed; the seeds are those
+ * of the TM-score block above with every start.  A pass of an item: superpose the current set (first the seed's fragment), form the five
+ * counts under the transform, select the rows with d^2 < cut^2, cut = c_k (+ 0.5 while fewer than 3 rows are inside and n > 3, up to
+ * 10^4); the item ends where the set equals the set just superposed or after 21 passes.  Every pass offers its five counts; the winner
+ * of cutoff j is the largest count_j, then the lowest item number, then the earliest pass.  Seed 0 starts from all rows: a searched count
+ * is never below the GLOBAL one.  This search is the project's own; NO parity with the LGA program is claimed.
+ * Every output of a pair depends on that pair's masked rows only. */
+#define FDIPT_GDT_NONE 0
+#define FDIPT_GDT_GLOBAL 1
+#define FDIPT_GDT_SEARCH 2
+#define FDIPT_GDT_CUTOFFS 5
+#define FDIPT_GDT_TOO_SHORT 1        /* status: n < 1 (NONE) or n < 3; scores NaN                                                   */
+#define FDIPT_GDT_SKIPPED 2          /* status: a structure index of the pair is out of range; scores NaN                           */
+#define FDIPT_GDT_NOT_FINITE 4       /* status: a coordinate of a scored row is not finite, nothing is counted; scores NaN          */
+typedef struct FdiptGdtArgs {
+  int32_t S, N, atoms, ca;           /* structures, rows, atoms per row of prot: 37 or 5; the CA column (1 in both layouts)         */
+  int32_t S_b, atoms_b;              /* of prot_b (ignored where prot_b is NULL)                                                    */
+  int32_t P, mode;                   /* pairs; FDIPT_GDT_NONE / GLOBAL / SEARCH                                                     */
+  const float* prot;                 /* [S,N,atoms,3] f32                                                                           */
+  const float* mask;                 /* [S,N] f32                                                                                   */
+  const float* prot_b;               /* [S_b,N,atoms_b,3] f32 or NULL: the second structure of a pair comes from here, else from prot */
+  const float* mask_b;               /* [S_b,N] f32 (with prot_b)                                                                   */
+  const int32_t* pairs;              /* [P,2] i32: (index into prot, index into prot_b or prot); x is the first, y the second       */
+  const int32_t* norm_length;        /* [P] i32 or NULL: L of the pair where > 0                                                    */
+  /* outputs: [P] */
+  double* gdt_ts;                    /* f64; NaN with a status bit                                                                  */
+  double* gdt_ha;                    /* f64; NaN with a status bit                                                                  */
+  int32_t* counts;                   /* [P,5] i32: count_j under cutoff j's winning transform; 0 with a status bit                  */
+  int32_t* n_scored;                 /* i32: n                                                                                      */
+  double* rotation;                  /* [P,5,3,3] f64: R x + t ~ y per cutoff; the identity in NONE and with a status bit           */
+  double* translation;               /* [P,5,3] f64                                                                                 */
+  int32_t* best_item;                /* [P,5] i32: the winning item per cutoff; -1 outside SEARCH and with a status bit             */
+  int32_t* best_pass;                /* [P,5] i32: its pass, from 0; -1 likewise                                                    */
+  int32_t* passes;                   /* i32: superpositions over all items of the search (1 in GLOBAL, 0 in NONE)                   */
+  int32_t* res_within;               /* [P,N] i32: bit j set where the row is scored and within c_j under cutoff j's transform      */
+  int32_t* status;                   /* i32: FDIPT_GDT_* bits                                                                       */
+  void* workspace;                   /* may be NULL: fdipt_sample_gdt_workspace is 0 (the search lives in LDS and registers)        */
+  size_t workspace_bytes;
+} FdiptGdtArgs;
+size_t fdipt_sample_gdt_workspace(int S, int N, int P);
+/* FDIPT_EINVAL: a null pointer, S, N or P < 1, atoms not 37 or 5, ca outside 0 .. 4, a mode outside the above.  FDIPT_ESIZE: N >
+ * FDIPT_TM_MAX_ROWS. */
+int fdipt_sample_gdt(const FdiptGdtArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- inverse folding (opt-in) */
 /* The vanilla full-backbone ProteinMPNN (ProteinMPNN/protein_mpnn_utils.py: ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward
  * and .sample), inference only, float32 throughout; the contract is DESIGN.md section 7.10.  Letters are in the MODEL's alphabet
