@@ -698,6 +698,52 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
     return write_tm_align_table(out_dir, structures, skipped)
 
 
+def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1, inpainting: bool = False):
+    """Rank 0, after the gather (``--novelty SET.npz``; framedipt_amd/structure_search.py).  De novo runs only: every final sample is
+    searched in the structure set, one ``search`` call per sample length, the samples compacted to their set rows (``compact_rows``).
+    The reference (evaluation/eval_denovo.py:plot_novelty) searches the ESMFold refold of a sample with foldseek; here the query is
+    the sample itself and the search is this project's own (no parity with foldseek is claimed) - both are said
+    in the output.  Writes ``novelty.json`` (per sample pdbTM, the hit's name, tm_t, n_aligned, the counts and with top_k > 1 every hit)
+    and ``novelty.csv`` (length, sample, pdbTM, hit).  A length beyond the search's row limit is recorded as skipped.  Inpainting runs
+    are refused: a redesigned loop in a fixed context is not novel by construction.  Returns the summary written."""
+    if inpainting:
+        raise ValueError("--novelty is for de novo runs: a redesigned region inside a fixed context is not novel by construction")
+    import csv
+
+    from . import structure_search
+    db = structure_search.StructureSet.load(set_path)
+    by_length = {}
+    for r in records:
+        by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+    samples, skipped = [], []
+    for length, rs in by_length.items():
+        prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
+        mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+        rows, rows_mask = compact_rows(prot, mask)
+        if rows.shape[1] > structure_search.MAX_ROWS:
+            skipped.append(length)
+            continue
+        res = structure_search.search(rows, db, mask=rows_mask, top_k=top_k)
+        for q, r in enumerate(rs):
+            entry = {"length": length, "sample": r["sample_i"], **structure_search.novelty_metrics(res, q),
+                     **{k: int(res[k][q]) for k in ("n_scored", "n_pruned", "n_skipped")}}
+            if top_k > 1:
+                entry["hits"] = [{"hit": res["names"][q][j], "tm_q": float(res["tm_q"][q, j]), "tm_t": float(res["tm_t"][q, j]),
+                                  "n_aligned": int(res["n_aligned"][q, j])} for j in range(top_k) if res["hit"][q, j] >= 0]
+            samples.append(entry)
+    summary = {"set": str(set_path), "entries": len(db), "top_k": int(top_k),
+               "query": "the sample itself (the reference searches the ESMFold refold of a sample)",
+               "search": "the alignment search of DESIGN.md sections 7.9 and 7.15, pdbTM normalised by the sample's rows; no parity with foldseek is claimed",
+               "samples": samples, "skipped_lengths": sorted(skipped)}
+    with open(os.path.join(out_dir, "novelty.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "novelty.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["length", "sample", "pdbTM", "hit"])
+        w.writeheader()
+        w.writerows({"length": e["length"], "sample": e["sample"], "pdbTM": repr(e["pdbTM"]), "hit": e["hit"]} for e in samples)
+    return summary
+
+
 def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, seq_per_sample: int = 8, weights=None, temperature: float = 0.1,
                seed: int = 38, max_batch: int = 16, omit_aas: str = "X", ca_only: bool = False):
     """Rank 0, after the gather (``--design``; framedipt_amd/inverse_folding.py): ``seq_per_sample`` ProteinMPNN sequences per sample at the
@@ -885,6 +931,11 @@ def main():
     ap.add_argument("--ca-only", action="store_true", help="--design: the CA-only ProteinMPNN (reads the CA trace alone; --mpnn-weights must then be a CA checkpoint)")
     ap.add_argument("--mpnn-weights", default=None, help="--design: a ProteinMPNN checkpoint (.pt with model_state_dict, num_edges, noise_level); default: "
                     "SYNTHETIC parameters, stated as such in the output")
+    ap.add_argument("--novelty", default=None, metavar="SET.npz", help="de novo runs: after the run, rank 0 searches every final sample in the structure set "
+                    "(framedipt_amd/structure_search.py: StructureSet.save) on its GPU and keeps the largest TM-score of the hits, the reference's pdbTM: "
+                    "novelty.json, novelty.csv.  The query is the sample itself, not an ESMFold refold, and the search is this project's own: no parity "
+                    "with foldseek is claimed.  Refused in inpainting runs")
+    ap.add_argument("--novelty-top-k", type=int, default=1, help="--novelty: hits kept per sample (1 .. 64)")
     ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score, --tm-align: the TM-score threshold of the clusters (reference default)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
@@ -893,6 +944,10 @@ def main():
             a.keep = int(a.keep)
         except ValueError:
             ap.error(f"--keep {a.keep}: expected all, last or an integer stride")
+    if a.novelty and a.download_dir is not None:
+        ap.error("--novelty is for de novo runs: a redesigned region inside a fixed context is not novel by construction")
+    if a.novelty and not 1 <= a.novelty_top_k <= 64:
+        ap.error(f"--novelty-top-k {a.novelty_top_k}: expected 1 .. 64")
 
     import torch
     import torch.distributed as dist
@@ -979,7 +1034,7 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt or a.novelty else None
     ground_truth = None
     if (a.evaluate or a.sasa or a.tm_score or a.lddt or a.gdt) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
@@ -992,7 +1047,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt or a.novelty:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -1050,6 +1105,11 @@ def main():
             what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/gdt.json, gdt.csv" if inp else \
                 f"{len(done['lengths'])} length(s) -> {a.out_dir}/pairwise_gdt_ts_length_<L>.npy"
             print(f"GDT-TS and GDT-HA of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
+        if a.novelty:
+            t1 = time.perf_counter()
+            done = run_novelty(a.out_dir, allrecs, gathered, a.novelty, top_k=a.novelty_top_k, inpainting=inp)
+            print(f"novelty of {len(done['samples'])} sample(s) against {done['entries']} structure(s) in {time.perf_counter() - t1:.2f} s -> "
+                  f"{a.out_dir}/novelty.json, novelty.csv", flush=True)
         if a.design:
             t1 = time.perf_counter()
             done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights, omit_aas=a.omit_aas, ca_only=a.ca_only)

@@ -713,6 +713,73 @@ size_t fdipt_sample_tm_align_workspace(int S, int N_a, int N_b, int P);
  * FDIPT_TMA_MAX_ROWS. */
 int fdipt_sample_tm_align(const FdiptTmAlignArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- structure search (opt-in) */
+/* The novelty of samples: for each of Q queries, the top_k entries of a packed, ragged set of D CA traces under the alignment search of
+ * the block above (the pair is (query, entry): tm_q is its tm_a, tm_t its tm_b), exactly what that search gives for every pair - bit
+ * for bit, csrc/tmalign_body.hpp is the one body.  The contract is DESIGN.md section 7.15.  No parity with foldseek is claimed.
+ * The caller plans the work: plan_entries lists entry indices bucket by bucket, bucket b being plan_entries[bucket_start[b] ..
+ * bucket_start[b + 1]) with every entry of at most bucket_cap[b] rows.  Per bucket, in the order given: one launch of a block per
+ * (query, entry) whose LDS is sized for (N_q, bucket_cap[b]), writing the pair's scores into the [Q,D] arrays; then one launch that
+ * folds the bucket into each query's running list of the top_k (ranked score descending, entry index ascending; a score that is NaN
+ * or below min_score never enters) and sets the query's floor = max(min_score, the top_k-th ranked score held), min_score while fewer
+ * are held.  With prune, a block whose bound - min(n1, n2) / n1 for FDIPT_SEARCH_RANK_QUERY, min(n1, n2) / n2 for ..._TARGET, a score
+ * being a sum of min(n1, n2) terms of at most 1 - is STRICTLY below the floor leaves with FDIPT_SEARCH_PRUNED.  The floor changes
+ * between launches only: a call is deterministic for a given plan.  An entry that no bucket lists keeps NaN scores; one of more than
+ * FDIPT_TMA_MAX_ROWS rows is marked FDIPT_SEARCH_TOO_LONG.  With details the Q x top_k hits run once more with every output. */
+#define FDIPT_SEARCH_MAX_K 64
+#define FDIPT_SEARCH_PRUNED 16       /* pair status: not scored, its length bound lies strictly below the query's floor             */
+#define FDIPT_SEARCH_TOO_LONG 32     /* pair status: the entry has more than FDIPT_TMA_MAX_ROWS rows; skipped                        */
+#define FDIPT_SEARCH_RANK_QUERY 0    /* rank_by: tm_q, the score normalised by the query's rows                                      */
+#define FDIPT_SEARCH_RANK_TARGET 1   /* rank_by: tm_t, the score normalised by the entry's rows                                      */
+typedef struct FdiptSearchArgs {
+  int32_t Q, N_q, atoms, ca;         /* queries, rows, atoms per row of prot: 37 or 5; the CA column (1 in both layouts)            */
+  int32_t D;                         /* entries of the set                                                                          */
+  int32_t top_k, rank_by, prune, details;
+  int32_t n_buckets;                 /* launches of the score pass (0: nothing is scored)                                           */
+  int32_t detail_cap;                /* details: rows of `alignment` per hit and the N_b of the detail launch; >= every listed entry */
+  int64_t R;                         /* rows of db_ca                                                                               */
+  double min_score;
+  const float* prot;                 /* [Q,N_q,atoms,3] f32                                                                         */
+  const float* mask;                 /* [Q,N_q] f32                                                                                 */
+  const float* db_ca;                /* [R,3] f32: the CA atoms of all entries, packed                                              */
+  const int64_t* db_offsets;         /* [D+1] i64, device: entry e is rows db_offsets[e] .. db_offsets[e + 1]                       */
+  const int32_t* plan_entries;       /* [bucket_start[n_buckets]] i32, device                                                       */
+  const int32_t* bucket_start;       /* [n_buckets + 1] i32, HOST memory, ascending from 0                                          */
+  const int32_t* bucket_cap;         /* [n_buckets] i32, HOST memory, each 1 .. FDIPT_TMA_MAX_ROWS                                  */
+  /* outputs per hit: [Q,top_k] */
+  int32_t* hit;                      /* i32: entry index, -1 where fewer than top_k entries qualify                                 */
+  double* tm_q;                      /* f64; NaN where hit is -1                                                                    */
+  double* tm_t;
+  int32_t* n_aligned;
+  double* rmsd;
+  int32_t* status;                   /* i32: FDIPT_TMA_* bits of the hit's pair; 0 where hit is -1                                  */
+  /* outputs per query: [Q] */
+  int32_t* n_scored;                 /* pairs a block scored or refused (D - n_pruned - n_skipped - entries no bucket lists)       */
+  int32_t* n_pruned;
+  int32_t* n_skipped;                /* entries beyond the row limit                                                                */
+  double* pdb_tm;                    /* f64: the ranked score of hit 0; NaN without a hit                                           */
+  /* outputs per pair: [Q,D] */
+  double* scores_q;                  /* f64; NaN where not scored                                                                   */
+  double* scores_t;
+  int32_t* pair_n_aligned;
+  double* pair_rmsd;
+  int32_t* pair_status;              /* i32: FDIPT_TMA_* and FDIPT_SEARCH_* bits                                                    */
+  /* outputs of the detail pass: [Q,top_k], NULL without details */
+  double* detail_tm_q;               /* f64: the detail pass's own scores (equal to tm_q, tm_t bit for bit)                         */
+  double* detail_tm_t;
+  double* rotation;                  /* [Q,top_k,3,3] f64                                                                           */
+  double* translation;               /* [Q,top_k,3] f64                                                                             */
+  int32_t* alignment;                /* [Q,top_k,detail_cap] i32: the query row aligned with each entry row, or -1                  */
+  int32_t* best_init;
+  void* workspace;                   /* fdipt_structure_search_workspace bytes: the ranked scores of the lists, the floors, and the */
+  size_t workspace_bytes;            /* detail pass's outputs nobody asked for                                                      */
+} FdiptSearchArgs;
+size_t fdipt_structure_search_workspace(int Q, int top_k, int details);
+/* FDIPT_EINVAL: a null pointer, Q, N_q or D < 1, atoms not 37 or 5, ca outside 0 .. 4, top_k outside 1 .. FDIPT_SEARCH_MAX_K, a rank_by
+ * that is none of the two, a plan that is not ascending or a cap outside 1 .. FDIPT_TMA_MAX_ROWS, details with detail_cap outside that
+ * range.  FDIPT_ESIZE: N_q > FDIPT_TMA_MAX_ROWS, Q x D or Q x top_k x detail_cap >= 2^31, workspace too small. */
+int fdipt_structure_search(const FdiptSearchArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- superposition-free accuracy (opt-in) */
 /* lDDT (Mariani et al. 2013; openfold/utils/loss.py lddt :382, lddt_ca :438), dRMSD (compute_drmsd :1518) and backbone FAPE (compute_fape
  * :76 as backbone_loss :152 calls it: clamp 10, unit 10, eps 1e-4) of P ordered pairs (model structure a, reference structure b) in row
