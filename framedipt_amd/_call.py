@@ -94,11 +94,12 @@ def empty_outputs(spec: dict, widen=()) -> dict:
     return {k: np.zeros(tuple(shape), dtype=np.int64 if k in widen else dtype) for k, (dtype, shape) in spec.items()}
 
 
-def run(name: str, struct, dev, scalars: dict, inputs: dict, outputs: dict, widen=(), workspace=None, dims=None) -> dict:
+def run(name: str, struct, dev, scalars: dict, inputs: dict, outputs: dict, widen=(), workspace=None, dims=None, extra=()) -> dict:
     """One call of the C entry ``name`` on the current stream of ``dev``.  ``struct``: its args struct, filled from ``scalars`` (plain
     fields: sizes, numbers, host pointers), ``inputs`` (device tensors or None, by field name) and zeroed outputs allocated from
     ``outputs`` ({name: (dtype name, shape)}).  ``workspace``: (size function, *its arguments), sized and allocated here, or None for an
     entry that takes none.  ``dims``: a struct both functions take by reference as their first argument (the inverse-folding model).
+    ``extra``: plain arguments the entry takes between its args struct and the stream.
     Returns the outputs as NumPy arrays, those named in ``widen`` as int64."""
     import torch
     lib = _lib.load()
@@ -109,7 +110,7 @@ def run(name: str, struct, dev, scalars: dict, inputs: dict, outputs: dict, wide
         work = None if workspace is None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
         args = struct(workspace=_lib.ptr(work), workspace_bytes=nbytes, **scalars, **{k: _lib.ptr(v) for k, v in inputs.items()},
                       **{k: _lib.ptr(v) for k, v in out.items()})
-        _lib.check(getattr(lib, name)(*lead, C.byref(args), _lib.stream_ptr()), name)
+        _lib.check(getattr(lib, name)(*lead, C.byref(args), *extra, _lib.stream_ptr()), name)
         return to_numpy(out, widen)
 
 

@@ -13,6 +13,8 @@
 //            doubles, nothing depends on block scheduling
 //   finish   a block per query: the hits' numbers gathered from the pair arrays, the counts from the statuses
 //   detail   a block per hit with every output of the body on
+// fdipt_structure_search_inits with FDIPT_TMA_INITS_ALL: the score and detail launches are ss_score5_kernel and ss_detail5_kernel, the same blocks with the body's
+// INITS5 switch on, and the workspace's init_tm and init_dp hold five entries per hit.
 // Contraction into fused multiply-adds is off in this unit, as in tmalign.hip.
 #include "common.hpp"
 
@@ -28,7 +30,7 @@
 struct SsWork {
   size_t top_score, floor, tm, rmsd, d0_a, d0_b, init_tm, n_aligned, status, init_dp, total;
 };
-static inline SsWork ss_work(int Q, int k, int details) {
+static inline SsWork ss_work(int Q, int k, int details, int inits = 3) {
   SsWork w;
   const size_t qk = (size_t)Q * k;
   size_t o = 0;
@@ -40,10 +42,10 @@ static inline SsWork ss_work(int Q, int k, int details) {
     w.rmsd = o, o += qk * 8;
     w.d0_a = o, o += qk * 8;
     w.d0_b = o, o += qk * 8;
-    w.init_tm = o, o += qk * 3 * 8;
+    w.init_tm = o, o += qk * inits * 8;
     w.n_aligned = o, o += qk * 4;
     w.status = o, o += qk * 4;
-    w.init_dp = o, o += qk * 3 * 4;
+    w.init_dp = o, o += qk * inits * 4;
   }
   w.total = (o + 7) / 8 * 8;
   return w;
@@ -75,7 +77,8 @@ struct SsBound {
   }
 };
 
-__global__ __launch_bounds__(FD_THREADS) void ss_score_kernel(FdiptSearchArgs a, const double* floor, int start, int count, int cap) {
+template <bool INITS5>
+__device__ __forceinline__ void ss_score_block(const FdiptSearchArgs& a, const double* floor, int start, int count, int cap) {
   extern __shared__ double tma_sh[];
   __shared__ int cnt_sh[FD_THREADS / FD_WAVE], next_sh, passes_sh, count_sh;
   const int q = blockIdx.x / count, e = a.plan_entries[start + blockIdx.x % count];
@@ -89,7 +92,14 @@ __global__ __launch_bounds__(FD_THREADS) void ss_score_kernel(FdiptSearchArgs a,
   }
   const TmaSource A{a.prot + ((long)q * a.N_q * a.atoms + a.ca) * 3, a.mask + (long)q * a.N_q, (long)a.atoms * 3, a.N_q};
   const TmaSource B{a.db_ca + r0 * 3, nullptr, 3, (int)(r1 - r0)};
-  tma_pair<false, false>(A, B, a.N_q, cap, o, p, tma_sh, cnt_sh, &next_sh, &passes_sh, &count_sh, SsBound{floor + q, a.rank_by, a.prune});
+  tma_pair<false, false, INITS5>(A, B, a.N_q, cap, o, p, tma_sh, cnt_sh, &next_sh, &passes_sh, &count_sh, SsBound{floor + q, a.rank_by, a.prune});
+}
+
+__global__ __launch_bounds__(FD_THREADS) void ss_score_kernel(FdiptSearchArgs a, const double* floor, int start, int count, int cap) {
+  ss_score_block<false>(a, floor, start, count, cap);
+}
+__global__ __launch_bounds__(FD_THREADS) void ss_score5_kernel(FdiptSearchArgs a, const double* floor, int start, int count, int cap) {
+  ss_score_block<true>(a, floor, start, count, cap);
 }
 
 // (s, e) ranks before (t, f): the order of the hits
@@ -162,12 +172,13 @@ __global__ __launch_bounds__(FD_THREADS) void ss_finish_kernel(FdiptSearchArgs a
   }
 }
 
-__global__ __launch_bounds__(FD_THREADS) void ss_detail_kernel(FdiptSearchArgs a, TmaOut o) {
+template <bool INITS5>
+__device__ __forceinline__ void ss_detail_block(const FdiptSearchArgs& a, const TmaOut& o) {
   extern __shared__ double tma_sh[];
   __shared__ int cnt_sh[FD_THREADS / FD_WAVE], next_sh, passes_sh, count_sh;
   const long p = blockIdx.x;
   const int q = (int)(p / a.top_k), e = a.hit[p], cap = a.detail_cap;
-  tma_clear<true>(o, p, cap);
+  tma_clear<true, INITS5>(o, p, cap);
   if (e < 0 || e >= a.D) {  // no hit: NaN scores, the identity, nothing aligned
     tma_leave<true>(o, p, 0, 0, 0.0, 0.0, -1);
     return;
@@ -179,15 +190,18 @@ __global__ __launch_bounds__(FD_THREADS) void ss_detail_kernel(FdiptSearchArgs a
   }
   const TmaSource A{a.prot + ((long)q * a.N_q * a.atoms + a.ca) * 3, a.mask + (long)q * a.N_q, (long)a.atoms * 3, a.N_q};
   const TmaSource B{a.db_ca + r0 * 3, nullptr, 3, (int)(r1 - r0)};
-  tma_pair<true, false>(A, B, a.N_q, cap, o, p, tma_sh, cnt_sh, &next_sh, &passes_sh, &count_sh, TmaNoEarly());
+  tma_pair<true, false, INITS5>(A, B, a.N_q, cap, o, p, tma_sh, cnt_sh, &next_sh, &passes_sh, &count_sh, TmaNoEarly());
 }
+
+__global__ __launch_bounds__(FD_THREADS) void ss_detail_kernel(FdiptSearchArgs a, TmaOut o) { ss_detail_block<false>(a, o); }
+__global__ __launch_bounds__(FD_THREADS) void ss_detail5_kernel(FdiptSearchArgs a, TmaOut o) { ss_detail_block<true>(a, o); }
 
 extern "C" size_t fdipt_structure_search_workspace(int Q, int top_k, int details) {
   if (Q < 1 || top_k < 1) return 0;
-  return ss_work(Q, top_k, details).total;
+  return ss_work(Q, top_k, details, 5).total;  // (sized for either mode: 32 bytes per hit more than the default needs)
 }
 
-extern "C" int fdipt_structure_search(const FdiptSearchArgs* a, fdipt_stream_t stream) {
+extern "C" int fdipt_structure_search_inits(const FdiptSearchArgs* a, int32_t inits, fdipt_stream_t stream) {
   if (!a || a->Q < 1 || a->N_q < 1 || a->D < 1 || (a->atoms != 37 && a->atoms != 5) || a->ca < 0 || a->ca >= 5) return FDIPT_EINVAL;
   if (a->top_k < 1 || a->top_k > SS_MAX_K || (a->rank_by != FDIPT_SEARCH_RANK_QUERY && a->rank_by != FDIPT_SEARCH_RANK_TARGET) || a->n_buckets < 0 || a->R < 0)
     return FDIPT_EINVAL;
@@ -200,19 +214,23 @@ extern "C" int fdipt_structure_search(const FdiptSearchArgs* a, fdipt_stream_t s
   if (a->details && (!a->detail_tm_q || !a->detail_tm_t || !a->rotation || !a->translation || !a->alignment || !a->best_init || a->detail_cap < 1 ||
                      a->detail_cap > TMA_MAX_ROWS))
     return FDIPT_EINVAL;
+  if (inits != FDIPT_TMA_INITS_DEFAULT && inits != FDIPT_TMA_INITS_ALL) return FDIPT_EINVAL;
   if (a->N_q > TMA_MAX_ROWS) return FDIPT_ESIZE;
+  const bool five = inits == FDIPT_TMA_INITS_ALL;
   const long limit = 0x7fffffffL;
   if ((long)a->Q * a->D >= limit || (a->details && (long)a->Q * a->top_k * a->detail_cap >= limit)) return FDIPT_ESIZE;
   for (int b = 0; b < a->n_buckets; ++b)
     if ((long)a->Q * (a->bucket_start[b + 1] - a->bucket_start[b]) >= limit) return FDIPT_ESIZE;
-  const SsWork w = ss_work(a->Q, a->top_k, a->details);
-  if (!a->workspace || a->workspace_bytes < w.total) return FDIPT_ESIZE;
+  const SsWork w = ss_work(a->Q, a->top_k, a->details, five ? 5 : 3);
+  if (!a->workspace || a->workspace_bytes < fdipt_structure_search_workspace(a->Q, a->top_k, a->details)) return FDIPT_ESIZE;
   static FdPerDevice attr_dev;
   const int dev_ = fd_device();
   if (!attr_dev.get(dev_)) {  // up to 131 KB, more than the default 64 KB of dynamic LDS
-    const int most = (int)tma_layout(TMA_MAX_ROWS, TMA_MAX_ROWS).total;
+    const int most = (int)tma_layout(TMA_MAX_ROWS, TMA_MAX_ROWS).total, most5 = (int)tma_layout(TMA_MAX_ROWS, TMA_MAX_ROWS, true).total;
     if (hipFuncSetAttribute((const void*)ss_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
-        hipFuncSetAttribute((const void*)ss_detail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
+        hipFuncSetAttribute((const void*)ss_detail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+        hipFuncSetAttribute((const void*)ss_score5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most5) != hipSuccess ||
+        hipFuncSetAttribute((const void*)ss_detail5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most5) != hipSuccess)
       return FDIPT_ELAUNCH;
     attr_dev.set(dev_, 1);
   }
@@ -226,8 +244,10 @@ extern "C" int fdipt_structure_search(const FdiptSearchArgs* a, fdipt_stream_t s
   for (int b = 0; b < a->n_buckets; ++b) {
     const int start = a->bucket_start[b], count = a->bucket_start[b + 1] - start, cap = a->bucket_cap[b];
     if (count == 0) continue;
-    hipLaunchKernelGGL(ss_score_kernel, dim3((unsigned)((long)a->Q * count)), dim3(FD_THREADS), tma_layout(a->N_q, cap).total, st, *a, (const double*)floor, start,
-                       count, cap);
+    const dim3 grid((unsigned)((long)a->Q * count));
+    const size_t lds = tma_layout(a->N_q, cap, five).total;
+    if (five) hipLaunchKernelGGL(ss_score5_kernel, grid, dim3(FD_THREADS), lds, st, *a, (const double*)floor, start, count, cap);
+    else hipLaunchKernelGGL(ss_score_kernel, grid, dim3(FD_THREADS), lds, st, *a, (const double*)floor, start, count, cap);
     FD_CHECK_LAUNCH();
     hipLaunchKernelGGL(ss_merge_kernel, dim3((unsigned)a->Q), dim3(FD_THREADS), 0, st, *a, top_score, floor, start, count);
     FD_CHECK_LAUNCH();
@@ -238,8 +258,15 @@ extern "C" int fdipt_structure_search(const FdiptSearchArgs* a, fdipt_stream_t s
     const TmaOut o{(double*)(work + w.tm), a->detail_tm_q, a->detail_tm_t, a->rotation, a->translation, (double*)(work + w.rmsd), (double*)(work + w.d0_a),
                    (double*)(work + w.d0_b), (double*)(work + w.init_tm), a->alignment, (int*)(work + w.n_aligned), (int*)(work + w.init_dp), a->best_init,
                    (int*)(work + w.status), a->detail_cap};
-    hipLaunchKernelGGL(ss_detail_kernel, dim3((unsigned)((long)a->Q * a->top_k)), dim3(FD_THREADS), tma_layout(a->N_q, a->detail_cap).total, st, *a, o);
+    const dim3 grid((unsigned)((long)a->Q * a->top_k));
+    const size_t lds = tma_layout(a->N_q, a->detail_cap, five).total;
+    if (five) hipLaunchKernelGGL(ss_detail5_kernel, grid, dim3(FD_THREADS), lds, st, *a, o);
+    else hipLaunchKernelGGL(ss_detail_kernel, grid, dim3(FD_THREADS), lds, st, *a, o);
     FD_CHECK_LAUNCH();
   }
   return FDIPT_OK;
+}
+
+extern "C" int fdipt_structure_search(const FdiptSearchArgs* a, fdipt_stream_t stream) {
+  return fdipt_structure_search_inits(a, FDIPT_TMA_INITS_DEFAULT, stream);
 }

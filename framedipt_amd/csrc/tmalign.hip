@@ -13,6 +13,8 @@
 //             barrier per diagonal).  Two bits of direction per cell, 16 cells of one row per word, so no two threads share a word;
 //             the traceback is one thread's walk over the words
 //   Search    tmsearch.hpp over the gathered pairs; its masks share their LDS with the directions (never live at the same time)
+// inits = FDIPT_TMA_INITS_ALL launches tm_align5_kernel, the same block with the body's INITS5 switch on: behind I1 - I3 the candidates of
+// I4 one after another on the whole block (a fragment superposition by one thread, DP, gather, Fast by one thread), then I5 as I1.
 // Contraction into fused multiply-adds is off in this unit: the sums are compared with a NumPy evaluation in the same order.
 #include "common.hpp"
 
@@ -22,13 +24,14 @@
 #include "tmsearch.hpp"
 #include "tmalign_body.hpp"
 
-__global__ __launch_bounds__(FD_THREADS) void tm_align_kernel(FdiptTmAlignArgs a) {
+template <bool INITS5>
+__device__ __forceinline__ void tm_align_block(const FdiptTmAlignArgs a) {
   extern __shared__ double tma_sh[];
   __shared__ int cnt_sh[FD_THREADS / FD_WAVE], next_sh, passes_sh, count_sh;
   const int Na = a.N_a, Nb = a.N_b;
   const long p = blockIdx.x;
   const TmaOut o{a.tm, a.tm_a, a.tm_b, a.rotation, a.translation, a.rmsd, a.d0_a, a.d0_b, a.init_tm, a.alignment, a.n_aligned, a.init_dp, a.best_init, a.status, Nb};
-  tma_clear<true>(o, p, Nb);
+  tma_clear<true, INITS5>(o, p, Nb);
 
   const int ia = a.pairs[2 * p], ib = a.pairs[2 * p + 1];
   const int Sb = a.prot_b ? a.S_b : a.S;
@@ -39,8 +42,11 @@ __global__ __launch_bounds__(FD_THREADS) void tm_align_kernel(FdiptTmAlignArgs a
   const TmaSource A{a.prot + ((long)ia * Na * a.atoms + a.ca) * 3, a.mask + (long)ia * Na, (long)a.atoms * 3, Na};
   const TmaSource B{a.prot_b ? a.prot_b + ((long)ib * Nb * a.atoms_b + a.ca) * 3 : a.prot + ((long)ib * Nb * a.atoms + a.ca) * 3,
                     (a.prot_b ? a.mask_b : a.mask) + (long)ib * Nb, (long)(a.prot_b ? a.atoms_b : a.atoms) * 3, Nb};
-  tma_pair<true, true>(A, B, Na, Nb, o, p, tma_sh, cnt_sh, &next_sh, &passes_sh, &count_sh, TmaNoEarly());
+  tma_pair<true, true, INITS5>(A, B, Na, Nb, o, p, tma_sh, cnt_sh, &next_sh, &passes_sh, &count_sh, TmaNoEarly());
 }
+
+__global__ __launch_bounds__(FD_THREADS) void tm_align_kernel(FdiptTmAlignArgs a) { tm_align_block<false>(a); }
+__global__ __launch_bounds__(FD_THREADS) void tm_align5_kernel(FdiptTmAlignArgs a) { tm_align_block<true>(a); }
 
 extern "C" size_t fdipt_sample_tm_align_workspace(int S, int N_a, int N_b, int P) {
   (void)S, (void)N_a, (void)N_b, (void)P;  // the search lives in LDS and registers; the entry keeps the arguments for a later layout
@@ -54,18 +60,23 @@ extern "C" int fdipt_sample_tm_align(const FdiptTmAlignArgs* a, fdipt_stream_t s
     return FDIPT_EINVAL;
   if (a->prot_b && (!a->mask_b || a->S_b < 1 || (a->atoms_b != 37 && a->atoms_b != 5))) return FDIPT_EINVAL;
   if (!a->prot_b && a->N_b != a->N_a) return FDIPT_EINVAL;
+  if (a->inits != FDIPT_TMA_INITS_DEFAULT && a->inits != FDIPT_TMA_INITS_ALL) return FDIPT_EINVAL;
   if (a->N_a > TMA_MAX_ROWS || a->N_b > TMA_MAX_ROWS) return FDIPT_ESIZE;
   if (a->workspace_bytes < fdipt_sample_tm_align_workspace(a->S, a->N_a, a->N_b, a->P)) return FDIPT_ESIZE;
-  const size_t lds = tma_layout(a->N_a, a->N_b).total;
+  const bool five = a->inits == FDIPT_TMA_INITS_ALL;
+  const size_t lds = tma_layout(a->N_a, a->N_b, five).total;
   static FdPerDevice attr_dev;
   const int dev_ = fd_device();
-  if (!attr_dev.get(dev_)) {  // 512 x 512: 131 KB, more than the default 64 KB of dynamic LDS
+  if (!attr_dev.get(dev_)) {  // 512 x 512: 131 KB (132 KB with the five starts), more than the default 64 KB of dynamic LDS
     if (hipFuncSetAttribute((const void*)tm_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tma_layout(TMA_MAX_ROWS, TMA_MAX_ROWS).total) !=
-        hipSuccess)
+            hipSuccess ||
+        hipFuncSetAttribute((const void*)tm_align5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)tma_layout(TMA_MAX_ROWS, TMA_MAX_ROWS, true).total) != hipSuccess)
       return FDIPT_ELAUNCH;
     attr_dev.set(dev_, 1);
   }
-  hipLaunchKernelGGL(tm_align_kernel, dim3((unsigned)a->P), dim3(FD_THREADS), lds, (hipStream_t)stream, *a);
+  if (five) hipLaunchKernelGGL(tm_align5_kernel, dim3((unsigned)a->P), dim3(FD_THREADS), lds, (hipStream_t)stream, *a);
+  else hipLaunchKernelGGL(tm_align_kernel, dim3((unsigned)a->P), dim3(FD_THREADS), lds, (hipStream_t)stream, *a);
   FD_CHECK_LAUNCH();
   return FDIPT_OK;
 }

@@ -5,7 +5,12 @@
 // chosen by a mask with an atom stride, else every row of a packed CA array) and by which outputs are written (FULL: all of
 // FdiptTmAlignArgs; else tm_a, tm_b, n_aligned, rmsd and status), and it asks `early(n1, n2)` for status bits to leave with once both
 // row counts are known (the length bound of the structure search).  The layout is sized by the launch's (Na, Nb); the traces hold
-// A.rows <= Na and B.rows <= Nb rows.  An including unit turns contraction off and includes common.hpp, horn.hpp and tmsearch.hpp first.
+// A.rows <= Na and B.rows <= Nb rows.  INITS5 (a third switch, false in every instantiation of the default mode, which it leaves
+// unchanged) adds the two fragment starts of section 7.9's addendum behind I1 - I3: I4, the best of a grid of local superpositions
+// (candidates one after another on the whole block: one thread's tma_superpose of the fragment, tma_dp, tma_gather, one thread's
+// tma_fast), and I5, I1's thread-per-offset walk over the shorter of the two traces' longest unbroken runs; init_tm and init_dp then
+// hold five entries per pair and the layout one more map.  An including unit turns contraction off and includes common.hpp, horn.hpp
+// and tmsearch.hpp first.
 #pragma once
 
 #define TMA_MAX_ROWS FDIPT_TMA_MAX_ROWS
@@ -15,6 +20,9 @@
 #define TMA_SEC_T 1
 #define TMA_SEC_H 2
 #define TMA_SEC_E 3
+#define TMA_FRAG_C0 4.25    // Angstrom: the first cut of Frag
+#define TMA_FRAG_GROWTH 1.1
+#define TMA_FRAG_ROUNDS 64
 
 __host__ __device__ inline int tma_dir_stride(int Nb) { return ((Nb + 15) / 16) | 1; }  // words per row, odd: rows spread over the banks
 
@@ -23,7 +31,8 @@ struct TmaLayout {
   int K;
 };
 // doubles first, then the region the directions and the search's masks share, then shorts, then bytes
-__host__ __device__ inline TmaLayout tma_layout(int Na, int Nb) {
+// (`five`: the layout of INITS5, one more map of Nb shorts for I4's best candidate)
+__host__ __device__ inline TmaLayout tma_layout(int Na, int Nb, bool five = false) {
   TmaLayout l;
   l.K = Na < Nb ? Na : Nb;
   size_t o = 0;
@@ -34,7 +43,7 @@ __host__ __device__ inline TmaLayout tma_layout(int Na, int Nb) {
   l.slots = o, o += (size_t)3 * sizeof(TmTransform) + 8;
   const size_t dirs = (size_t)Na * tma_dir_stride(Nb) * 4, search = tm_search_lds_bytes(l.K);
   l.shared = o, o += ((dirs > search ? dirs : search) + 7) / 8 * 8;
-  l.map = o, o += (size_t)2 * Nb * 2;
+  l.map = o, o += (size_t)(five ? 3 : 2) * Nb * 2;
   l.rows = o, o += (size_t)(Na + Nb) * 2;
   l.bytes = o, o += (size_t)2 * (Na + 1) + Na + Nb;
   l.total = (o + 7) / 8 * 8;
@@ -155,6 +164,35 @@ __device__ __forceinline__ int tma_sec_of(const TmaTrace& t, int i, int n) {
     e = e && (ec[k] - 1.42) * (ec[k] - 1.42) < v[k] && v[k] < (ec[k] + 1.42) * (ec[k] + 1.42);
   }
   return h ? TMA_SEC_H : e ? TMA_SEC_E : v[2] < 64.0 ? TMA_SEC_T : TMA_SEC_C;
+}
+
+// I4's step between fragment starts on a trace of n rows
+__device__ __forceinline__ int tma_jump(int n) {
+  const int j = n > 250 ? 45 : n > 200 ? 35 : n > 150 ? 25 : 15;
+  return j < n / 3 ? j : n / 3;
+}
+
+// Frag by one thread: out[0], out[1] = the first row and the rows of the longest run of the trace whose successive squared distances lie
+// strictly below c^2, the first among equals; c grows by one multiplication per round until the run has min(4, n / 3) rows, and after
+// TMA_FRAG_ROUNDS rounds the run is the whole trace
+__device__ __forceinline__ void tma_frag(const TmaTrace& t, int n, int* out) {
+  const int need = n / 3 < 4 ? n / 3 : 4;
+  double c = TMA_FRAG_C0;
+  int start = 0, rows = n;
+  for (int round = 0; round < TMA_FRAG_ROUNDS; ++round) {
+    int best_s = 0, best_r = 1, s0 = 0;
+    for (int i = 1; i < n; ++i) {
+      const double dx = t.x[i] - t.x[i - 1], dy = t.y[i] - t.y[i - 1], dz = t.z[i] - t.z[i - 1];
+      if (!(dx * dx + dy * dy + dz * dz < c * c)) s0 = i;
+      if (i - s0 + 1 > best_r) best_s = s0, best_r = i - s0 + 1;
+    }
+    if (best_r >= need) {
+      start = best_s, rows = best_r;
+      break;
+    }
+    c = c * TMA_FRAG_GROWTH;
+  }
+  out[0] = start, out[1] = rows;
 }
 
 struct TmaShared {
@@ -283,11 +321,12 @@ struct TmaNoEarly {
 };
 
 // Prepares the outputs of pair p as the search's first lines do (FULL only): what a block that returns before tma_pair leaves behind.
-template <bool FULL>
+template <bool FULL, bool INITS5 = false>
 __device__ __forceinline__ void tma_clear(const TmaOut& o, long p, int Nb_rows) {
+  constexpr int NI = INITS5 ? 5 : 3;
   if constexpr (FULL) {
     for (int j = threadIdx.x; j < Nb_rows; j += FD_THREADS) o.alignment[p * o.align_stride + j] = -1;
-    if (threadIdx.x < 3) o.init_tm[p * 3 + threadIdx.x] = -1.0, o.init_dp[p * 3 + threadIdx.x] = 0;
+    if (threadIdx.x < NI) o.init_tm[p * NI + threadIdx.x] = -1.0, o.init_dp[p * NI + threadIdx.x] = 0;
   }
 }
 
@@ -307,13 +346,14 @@ __device__ __forceinline__ void tma_leave(const TmaOut& o, long p, int status, i
   }
 }
 
-// The search of one pair by the whole block.  `tma_sh`: tma_layout(Na, Nb).total bytes of LDS, 8-byte aligned; cnt_sh: FD_THREADS /
-// FD_WAVE ints; next_sh, passes_sh, count_sh: one int each.  The caller has run tma_clear.
-template <bool FULL, bool MASK_B, class Early>
+// The search of one pair by the whole block.  `tma_sh`: tma_layout(Na, Nb, INITS5).total bytes of LDS, 8-byte aligned; cnt_sh:
+// FD_THREADS / FD_WAVE ints; next_sh, passes_sh, count_sh: one int each.  The caller has run tma_clear<FULL, INITS5>.
+template <bool FULL, bool MASK_B, bool INITS5, class Early>
 __device__ __forceinline__ void tma_pair(const TmaSource& A, const TmaSource& B, int Na, int Nb, const TmaOut& o, long p, double* tma_sh, int* cnt_sh,
                                          int* next_sh, int* passes_sh, int* count_sh, Early early) {
   const int tid = threadIdx.x;
-  const TmaLayout lay = tma_layout(Na, Nb);
+  constexpr int NI = INITS5 ? 5 : 3;
+  const TmaLayout lay = tma_layout(Na, Nb, INITS5);
   char* base = (char*)tma_sh;
   double *xx = (double*)(base + lay.x), *yy = (double*)(base + lay.y), *pp = (double*)(base + lay.pairs);
   TmTransform* slots = (TmTransform*)(base + lay.slots);  // 0: the running transform, 1: the best alignment's, 2: T0 of I3
@@ -416,7 +456,7 @@ __device__ __forceinline__ void tma_pair(const TmaSource& A, const TmaSource& B,
 
   double best_tm = -1.0;
   int best_init = -1;
-  for (int which = 0; which < 3; ++which) {
+  for (int which = 0; which < NI; ++which) {
     // ---- the initial alignment into the map
     int k;
     if (which == 0) {
@@ -424,9 +464,87 @@ __device__ __forceinline__ void tma_pair(const TmaSource& A, const TmaSource& B,
       __syncthreads();
     } else if (which == 1) {
       tma_dp(sh, slots, 0.0, 1.0, -1.0, count_sh);
-    } else {
+    } else if (!INITS5 || which == 2) {
       const double d01 = d0s + 1.5;
       tma_dp(sh, slots + 2, d01 * d01, 0.5, -1.0, count_sh);
+    }
+    if constexpr (INITS5) {
+      if (which == 3) {
+        // ---- I4: the candidates (length, i, j) one after another; slot 0 holds the fragment's transform, best_map + Nb the best map
+        short* map4 = best_map + Nb;
+        const double d01 = d0s + 1.5;
+        const int ja = tma_jump(n1), jb = tma_jump(n2);
+        double best_f = -1.0;
+        bool have = false;
+        for (int pass = 0; pass < 2; ++pass) {
+          const int l = pass == 0 ? (Ls / 3 < 20 ? Ls / 3 : 20) : (Ls / 2 < 100 ? Ls / 2 : 100);
+          if (l < 3) continue;
+          for (int i = 0; i + l <= n1; i += ja)
+            for (int j = 0; j + l <= n2; j += jb) {
+              if (tid == 0) {
+                TmTransform T;
+                tma_superpose(sh.X, sh.Y, i - j, j, j + l, false, slots[1], 0.0, T);
+                slots[0] = T;
+              }
+              __syncthreads();
+              int kc = tma_dp(sh, slots, d01 * d01, 0.0, 0.0, count_sh);
+              if (kc < 3) continue;
+              kc = tma_gather(sh, map, false, slots, 0.0, cnt_sh);
+              if (tid == 0) {
+                TmTransform T;
+                *s_sh = tma_fast(sh.PA, sh.PB, 0, 0, kc, d0ssq, ds, T);
+              }
+              __syncthreads();
+              const double f = *s_sh;
+              if (!have || f > best_f) {  // the first in candidate order among equals
+                have = true, best_f = f;
+                for (int r = tid; r < n2; r += FD_THREADS) map4[r] = map[r];
+              }
+              __syncthreads();  // (the score is read; the next candidate writes it and the map)
+            }
+        }
+        if (!have) continue;
+        for (int r = tid; r < n2; r += FD_THREADS) map[r] = map4[r];
+        __syncthreads();
+      } else if (which == 4) {
+        // ---- I5: Frag of both traces by one thread each, then I1's walk over the donor's fragment
+        int* frag_sh = (int*)shared;
+        if (tid == 0) tma_frag(sh.X, n1, frag_sh);
+        if (tid == FD_WAVE) tma_frag(sh.Y, n2, frag_sh + 2);
+        __syncthreads();
+        const int sx = frag_sh[0], Lx = frag_sh[1], sy = frag_sh[2], Ly = frag_sh[3];
+        __syncthreads();  // (the reduction's arrays lie there)
+        const bool from_x = Lx < Ly || (Lx == Ly && n1 <= n2);
+        const int L = Lx < Ly ? Lx : Ly, other = from_x ? n2 : n1;
+        int r0 = from_x ? sx : sy, r1 = r0 + L;  // the fragment: rows r0 .. r1 - 1 of the donor
+        if (L == Ls) r1 = r0 + (89 * Ls) / 100 + 1, r0 += Ls / 10;
+        const int fifths = (2 * (L < other ? L : other)) / 5, mn = fifths > 3 ? fifths : 3;
+        const int xa = from_x ? r0 : 0, xb = from_x ? r1 : n1, ya = from_x ? 0 : r0, yb = from_x ? n2 : r1;
+        const int k5_lo = xa - yb + 1, n5_off = xb - ya - k5_lo;  // every offset with a pair
+        double mine = -1.0;
+        int mine_k = 0x7fffffff;
+        TmTransform T;
+        for (int oo = tid; oo < n5_off; oo += FD_THREADS) {
+          const int kk = k5_lo + oo, j0 = ya > xa - kk ? ya : xa - kk, j1 = yb < xb - kk ? yb : xb - kk;
+          if (j1 - j0 < mn) continue;
+          const double f = tma_fast(sh.X, sh.Y, kk, j0, j1, d0ssq, ds, T);
+          if (f > mine) mine = f, mine_k = kk;
+        }
+        double* red_s = (double*)shared;
+        int* red_k = (int*)(red_s + FD_THREADS);
+        red_s[tid] = mine, red_k[tid] = mine_k;
+        __syncthreads();
+        int owner = 0;
+        for (int t = 1; t < FD_THREADS; ++t)
+          if (red_s[t] > red_s[owner] || (red_s[t] == red_s[owner] && red_k[t] < red_k[owner])) owner = t;
+        const double f5 = red_s[owner];
+        const int k5 = red_k[owner];
+        __syncthreads();
+        if (!(f5 >= 0.0)) continue;  // no offset qualifies
+        const int j0 = ya > xa - k5 ? ya : xa - k5, j1 = yb < xb - k5 ? yb : xb - k5;
+        for (int j = tid; j < n2; j += FD_THREADS) map[j] = (short)(j >= j0 && j < j1 ? j + k5 : -1);
+        __syncthreads();
+      }
     }
     k = tma_gather(sh, map, false, slots, 0.0, cnt_sh);
     if (which == 1 && k >= 3) {  // F2 and T2 by one thread; T0 = T2 where F2 leads
@@ -457,7 +575,7 @@ __device__ __forceinline__ void tma_pair(const TmaSource& A, const TmaSource& B,
         __syncthreads();
         const double tm = *s_sh / (double)Ls;
         if constexpr (FULL)
-          if (round < 0 && tid == 0) o.init_tm[p * 3 + which] = tm;
+          if (round < 0 && tid == 0) o.init_tm[p * NI + which] = tm;
         if (tm > best_tm) {
           best_tm = tm, best_init = which;
           for (int j = tid; j < n2; j += FD_THREADS) best_map[j] = map[j];
@@ -475,7 +593,7 @@ __device__ __forceinline__ void tma_pair(const TmaSource& A, const TmaSource& B,
       }
     }
     if constexpr (FULL)
-      if (tid == 0) o.init_dp[p * 3 + which] = dps;
+      if (tid == 0) o.init_dp[p * NI + which] = dps;
   }
 
   // ---- final: drop the pairs beyond d8, score per normalisation length

@@ -601,7 +601,7 @@ def run_tm_score(out_dir: str, records, gathered: dict, inpainting: bool = False
     return write_tm_table(out_dir, structures)
 
 
-def write_diversity_aligned(out_dir: str, aligned: dict, fixed: dict, tm_score_th: float = 0.5, skipped=()):
+def write_diversity_aligned(out_dir: str, aligned: dict, fixed: dict, tm_score_th: float = 0.5, skipped=(), inits: str = "default"):
     """``aligned``: sample length -> matrix [S,S] of ``tm_align`` (entry (i, j) = ``tm_b``, mirrored); ``fixed``: the matrix of ``tm_scores``
     of the same samples.  Both are scores of a valid alignment under the same normalisation, so the larger is the tighter lower bound of
     the optimum: ``fmax(aligned, fixed)`` - where one of the two is NaN (a status bit), the other - is written as
@@ -609,12 +609,13 @@ def write_diversity_aligned(out_dir: str, aligned: dict, fixed: dict, tm_score_t
     clustered into ``diversity_aligned.json`` / ``diversity_aligned.csv``.  Per length the json records ``fixed_won``, the pairs i < j
     where the fixed correspondence scored above the search or the search gave no score, and ``nan_pairs``, the pairs without either
     score: a length with such pairs is written but not clustered (``clusters`` and ``diversity`` null).  ``skipped``: lengths beyond the
-    row limit of the search.  Returns the summary written to ``diversity_aligned.json``."""
+    row limit of the search; ``inits``: the search's mode (``--tm-inits``), recorded.  Returns the summary written to
+    ``diversity_aligned.json``."""
     import csv
 
     from . import tm_score
     summary = {"tm_score_th": tm_score_th, "alignment": "searched (DESIGN.md section 7.9; no parity with tmtools.tm_align is claimed), "
-               "the fixed row-by-row score where it is larger", "lengths": [], "skipped_lengths": [int(v) for v in skipped]}
+               "the fixed row-by-row score where it is larger", "inits": str(inits), "lengths": [], "skipped_lengths": [int(v) for v in skipped]}
     for length in sorted(aligned):
         a, f = np.asarray(aligned[length], dtype=np.float64), np.asarray(fixed[length], dtype=np.float64)
         matrix = np.fmax(a, f)
@@ -636,12 +637,12 @@ def write_diversity_aligned(out_dir: str, aligned: dict, fixed: dict, tm_score_t
     return summary
 
 
-def write_tm_align_table(out_dir: str, structures: dict, skipped=None):
+def write_tm_align_table(out_dir: str, structures: dict, skipped=None, inits: str = "default"):
     """``structures``: name -> {"samples": [labels], "rows": the most rows any sample of the structure was aligned over, "matrix": [S,S] of
     ``tm_align`` among the structure's samples over the diffused rows}; ``skipped``: name -> rows, the structures with more diffused rows
-    than the search takes.  Writes ``tm_align.json``.  Returns the summary written."""
+    than the search takes; ``inits``: the search's mode, recorded.  Writes ``tm_align.json``.  Returns the summary written."""
     number = lambda v: None if v != v else float(v)  # noqa: E731  (NaN: a status bit)
-    summary = {"alignment": "searched over the diffused rows (DESIGN.md section 7.9)", "structures": {
+    summary = {"alignment": "searched over the diffused rows (DESIGN.md section 7.9)", "inits": str(inits), "structures": {
         name: {"samples": list(e["samples"]), "rows": int(e["rows"]), "matrix": [[number(v) for v in row] for row in np.asarray(e["matrix"], dtype=np.float64)]}
         for name, e in structures.items()}, "skipped_structures": {str(k): int(v) for k, v in (skipped or {}).items()}}
     with open(os.path.join(out_dir, "tm_align.json"), "w") as f:
@@ -663,13 +664,15 @@ def compact_rows(prot, mask):
     return out, out_mask
 
 
-def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False, tm_score_th: float = 0.5):
+def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False, tm_score_th: float = 0.5, inits: str = "default"):
     """Rank 0, after the gather (``--tm-align``; framedipt_amd/tm_align.py).  De novo runs: per sample length one all-against-all
     ``tm_align`` call and one ``tm_scores`` call, then ``write_diversity_aligned``.  Inpainting runs: the aligned matrix among the samples
     of every structure name over the diffused rows that exist, ``write_tm_align_table`` (the sample-against-ground-truth number stays the
     fixed one of ``--tm-score``).  The samples go to the search compacted to their set rows (``compact_rows``): its row limit then
-    applies to those rows, not to the complex.  What still exceeds it is recorded as skipped.  Returns the summary written."""
+    applies to those rows, not to the complex.  What still exceeds it is recorded as skipped.  ``inits``: the initial alignments of the
+    search (``--tm-inits``), recorded in either file.  Returns the summary written."""
     from . import tm_align, tm_score
+    tm_align.check_inits(inits)
     if not inpainting:
         by_length = {}
         for r in records:
@@ -682,9 +685,9 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
             if rows.shape[1] > tm_align.MAX_ROWS:
                 skipped.append(length)
                 continue
-            aligned[length] = tm_align.tm_align(rows, mask_a=rows_mask)["matrix"]
+            aligned[length] = tm_align.tm_align(rows, mask_a=rows_mask, inits=inits)["matrix"]
             fixed[length] = tm_score.tm_scores(prot, mask_a=mask)["matrix"]
-        return write_diversity_aligned(out_dir, aligned, fixed, tm_score_th, skipped)
+        return write_diversity_aligned(out_dir, aligned, fixed, tm_score_th, skipped, inits)
     structures, skipped = {}, {}
     for name, rs in group_records_by_name(records).items():
         items = [gathered[r["item"]] for r in rs]
@@ -694,18 +697,19 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
         if rows.shape[1] > tm_align.MAX_ROWS:
             skipped[str(name)] = rows.shape[1]
             continue
-        structures[str(name)] = {"samples": [str(r["sample_i"]) for r in rs], "rows": rows.shape[1], "matrix": tm_align.tm_align(rows, mask_a=rows_mask)["matrix"]}
-    return write_tm_align_table(out_dir, structures, skipped)
+        structures[str(name)] = {"samples": [str(r["sample_i"]) for r in rs], "rows": rows.shape[1], "matrix": tm_align.tm_align(rows, mask_a=rows_mask, inits=inits)["matrix"]}
+    return write_tm_align_table(out_dir, structures, skipped, inits)
 
 
-def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1, inpainting: bool = False):
+def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1, inpainting: bool = False, inits: str = "default"):
     """Rank 0, after the gather (``--novelty SET.npz``; framedipt_amd/structure_search.py).  De novo runs only: every final sample is
     searched in the structure set, one ``search`` call per sample length, the samples compacted to their set rows (``compact_rows``).
     The reference (evaluation/eval_denovo.py:plot_novelty) searches the ESMFold refold of a sample with foldseek; here the query is
     the sample itself and the search is this project's own (no parity with foldseek is claimed) - both are said
     in the output.  Writes ``novelty.json`` (per sample pdbTM, the hit's name, tm_t, n_aligned, the counts and with top_k > 1 every hit)
     and ``novelty.csv`` (length, sample, pdbTM, hit).  A length beyond the search's row limit is recorded as skipped.  Inpainting runs
-    are refused: a redesigned loop in a fixed context is not novel by construction.  Returns the summary written."""
+    are refused: a redesigned loop in a fixed context is not novel by construction.  ``inits``: the initial alignments of the search
+    (``--tm-inits``), recorded in ``novelty.json``.  Returns the summary written."""
     if inpainting:
         raise ValueError("--novelty is for de novo runs: a redesigned region inside a fixed context is not novel by construction")
     import csv
@@ -723,7 +727,7 @@ def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1,
         if rows.shape[1] > structure_search.MAX_ROWS:
             skipped.append(length)
             continue
-        res = structure_search.search(rows, db, mask=rows_mask, top_k=top_k)
+        res = structure_search.search(rows, db, mask=rows_mask, top_k=top_k, inits=inits)
         for q, r in enumerate(rs):
             entry = {"length": length, "sample": r["sample_i"], **structure_search.novelty_metrics(res, q),
                      **{k: int(res[k][q]) for k in ("n_scored", "n_pruned", "n_skipped")}}
@@ -731,7 +735,7 @@ def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1,
                 entry["hits"] = [{"hit": res["names"][q][j], "tm_q": float(res["tm_q"][q, j]), "tm_t": float(res["tm_t"][q, j]),
                                   "n_aligned": int(res["n_aligned"][q, j])} for j in range(top_k) if res["hit"][q, j] >= 0]
             samples.append(entry)
-    summary = {"set": str(set_path), "entries": len(db), "top_k": int(top_k),
+    summary = {"set": str(set_path), "entries": len(db), "top_k": int(top_k), "inits": str(inits),
                "query": "the sample itself (the reference searches the ESMFold refold of a sample)",
                "search": "the alignment search of DESIGN.md sections 7.9 and 7.15, pdbTM normalised by the sample's rows; no parity with foldseek is claimed",
                "samples": samples, "skipped_lengths": sorted(skipped)}
@@ -935,6 +939,9 @@ def main():
                     "(framedipt_amd/structure_search.py: StructureSet.save) on its GPU and keeps the largest TM-score of the hits, the reference's pdbTM: "
                     "novelty.json, novelty.csv.  The query is the sample itself, not an ESMFold refold, and the search is this project's own: no parity "
                     "with foldseek is claimed.  Refused in inpainting runs")
+    ap.add_argument("--tm-inits", choices=("default", "all"), default="default", help="--tm-align and --novelty: the initial alignments of the search; "
+                    "all adds a local-superposition and a fragment-threading start (DESIGN.md section 7.9), for pairs that share a motif the three "
+                    "default ones cannot see; recorded in diversity_aligned.json, tm_align.json and novelty.json")
     ap.add_argument("--novelty-top-k", type=int, default=1, help="--novelty: hits kept per sample (1 .. 64)")
     ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score, --tm-align: the TM-score threshold of the clusters (reference default)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
@@ -1089,7 +1096,7 @@ def main():
             print(f"TM-scores of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
         if a.tm_align:
             t1 = time.perf_counter()
-            done = run_tm_align(a.out_dir, allrecs, gathered, inpainting=inp, tm_score_th=a.tm_score_th)
+            done = run_tm_align(a.out_dir, allrecs, gathered, inpainting=inp, tm_score_th=a.tm_score_th, inits=a.tm_inits)
             what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_align.json" if inp else \
                 f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity_aligned.json, diversity_aligned.csv, pairwise_tm_score_aligned_length_<L>.npy"
             print(f"structural alignments of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
@@ -1107,7 +1114,7 @@ def main():
             print(f"GDT-TS and GDT-HA of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
         if a.novelty:
             t1 = time.perf_counter()
-            done = run_novelty(a.out_dir, allrecs, gathered, a.novelty, top_k=a.novelty_top_k, inpainting=inp)
+            done = run_novelty(a.out_dir, allrecs, gathered, a.novelty, top_k=a.novelty_top_k, inpainting=inp, inits=a.tm_inits)
             print(f"novelty of {len(done['samples'])} sample(s) against {done['entries']} structure(s) in {time.perf_counter() - t1:.2f} s -> "
                   f"{a.out_dir}/novelty.json, novelty.csv", flush=True)
         if a.design:

@@ -4,7 +4,7 @@
 TM-score of the hits (``pdbTM``).  ``search`` is that quantity under this project's own alignment search (DESIGN.md sections 7.9 and
 7.15): for every query the ``top_k`` entries of a ``StructureSet`` by TM-score, exactly what a brute-force ``tm_align`` over all entries
 returns, bit for bit.  **No parity with foldseek is claimed**, and there is no prefilter: every pair is scored unless its length bound
-shows that it cannot enter the result.  One call of ``fdipt_structure_search`` (csrc/structsearch.hip, ABI in include/fdipt.h): the
+shows that it cannot enter the result.  One call of ``fdipt_structure_search_inits`` (csrc/structsearch.hip, ABI in include/fdipt.h): the
 entries stay packed (no padding to the longest), the score pass is launched bucket by bucket of entry length so that every block asks
 for the LDS of its bucket's cap, the top-k lists are merged on the device after every bucket, and the hits run once more for their
 transforms and alignments.
@@ -18,6 +18,7 @@ import os
 import numpy as np
 
 from . import _call, _lib
+from .tm_align import INITS, check_inits
 from .tm_score import CA
 
 MAX_ROWS = _lib.TMA_MAX_ROWS
@@ -171,12 +172,13 @@ def bound(n1, n2, rank_by: str = "query"):
 
 
 def search(prot, db: StructureSet, mask=None, top_k: int = 1, rank_by: str = "query", min_score: float = 0.0, prune: bool = True, details: bool = True,
-           return_scores: bool = False) -> dict:
+           return_scores: bool = False, inits: str = "default") -> dict:
     """prot [Q,N_q,37,3] or [Q,N_q,5,3] float32, a device tensor (used in place) or a NumPy array (uploaded); ``mask`` [Q,N_q] (default:
     ones): the rows of each query.  The pair is (query, entry): ``tm_q`` is ``tm_a`` of ``tm_align``, normalised by the query's rows -
     the usual ``pdbTM`` - and ``tm_t`` is ``tm_b``, normalised by the entry's.  ``rank_by``: ``"query"`` or ``"target"``, the score the
     hits are ordered by: ranked score descending, then entry index ascending; NaN never ranks; hits below ``min_score`` are not returned.
     ``prune``: skip a pair whose length bound lies strictly below what the query's list already holds - the result is the same.
+    ``inits``: the initial alignments of every pair's search, ``"default"`` or ``"all"`` as in ``tm_align``.
 
     Returns NumPy arrays: ``hit`` [Q,k] (entry index, -1 where fewer than k entries qualify), ``tm_q``, ``tm_t`` (NaN there),
     ``n_aligned``, ``rmsd``, ``status`` [Q,k] as in ``tm_align``; ``n_scored``, ``n_pruned``, ``n_skipped`` [Q] (pairs a block scored or
@@ -186,6 +188,7 @@ def search(prot, db: StructureSet, mask=None, top_k: int = 1, rank_by: str = "qu
     hit) and ``detail_tm_q`` / ``detail_tm_t``, the detail pass's own scores.  With ``return_scores``: ``scores_q`` / ``scores_t`` [Q,D]
     (NaN where pruned or skipped) and ``pair_status`` [Q,D] (``PRUNED``, ``TOO_LONG`` and the ``tm_align`` bits)."""
     n_q, rows, atoms = _call.structure_shape(prot, "prot", lead="Q", items="queries")
+    check_inits(inits)
     if not isinstance(db, StructureSet):
         raise ValueError("db should be a StructureSet")
     if len(db) < 1:
@@ -212,10 +215,10 @@ def search(prot, db: StructureSet, mask=None, top_k: int = 1, rank_by: str = "qu
                    bucket_start=work["bucket_start"].ctypes.data_as(C.c_void_p), bucket_cap=work["bucket_cap"].ctypes.data_as(C.c_void_p))
     if not details:
         scalars.update({k: None for k in detail})
-    out = _call.run("fdipt_structure_search", _lib.SearchArgs, dev, scalars,
+    out = _call.run("fdipt_structure_search_inits", _lib.SearchArgs, dev, scalars,
                     dict(prot=x, mask=_call.per_row(mask, (n_q, rows), "mask", "mask", default=1, dev=dev), db_ca=ca, db_offsets=offsets,
                          plan_entries=torch.from_numpy(work["entries"]).to(dev) if len(work["entries"]) else None),
-                    outputs, widen=_INTS, workspace=("fdipt_structure_search_workspace", n_q, top_k, int(bool(details))))
+                    outputs, widen=_INTS, workspace=("fdipt_structure_search_workspace", n_q, top_k, int(bool(details))), extra=(INITS[inits],))
     if details:
         hits = out["hit"]
         longest = int(db.lengths[hits[hits >= 0]].max()) if (hits >= 0).any() else 0
@@ -226,7 +229,7 @@ def search(prot, db: StructureSet, mask=None, top_k: int = 1, rank_by: str = "qu
             del out[k]
     else:
         del out["pair_n_aligned"], out["pair_rmsd"]
-    out["rank_by"] = rank_by
+    out["rank_by"], out["inits"] = rank_by, inits
     return out
 
 

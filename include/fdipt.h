@@ -675,12 +675,17 @@ int fdipt_sample_tm_score(const FdiptTmArgs* args, fdipt_stream_t stream);
  * under the better of their two transforms.  Each is scored by the seed search of the TM-score block above (fragment starts 40 apart,
  * pairs beyond d8 not scored) and iterated: dynamic programme on d0s^2 / (d0s^2 + d^2) under the search's transform with gap penalty
  * -0.6 then 0, up to 30 times each, until the score settles.  The best alignment loses its pairs beyond d8 and is scored by the full
- * search (start step 1, no d8) once per normalisation length.  Every output of a pair depends on that pair's masked rows only. */
+ * search (start step 1, no d8) once per normalisation length.  Every output of a pair depends on that pair's masked rows only.
+ * inits = FDIPT_TMA_INITS_ALL (opt-in; the default mode keeps every bit) runs two more initial alignments behind I1 - I3 through the same
+ * iteration: I4, the best of a grid of local superpositions of fragment pairs, each extended by a dynamic programme and ranked by the fast
+ * score, and I5, the best gapless threading of the longest unbroken run of the trace whose run is shorter (section 7.9's addendum). */
 #define FDIPT_TMA_MAX_ROWS 512       /* N_a or N_b beyond: FDIPT_ESIZE (the traces and the programme's directions live in LDS)       */
 #define FDIPT_TMA_TOO_SHORT 1        /* status: n1 < 5 or n2 < 5, no search; tm = NaN                                               */
 #define FDIPT_TMA_SKIPPED 2          /* status: a structure index of the pair is out of range; tm = NaN                             */
 #define FDIPT_TMA_NOT_FINITE 4       /* status: a coordinate of a set row is not finite, no search; tm = NaN                        */
 #define FDIPT_TMA_NO_ALIGNMENT 8     /* status: fewer than 3 pairs of the best alignment lie within d8; tm = NaN                    */
+#define FDIPT_TMA_INITS_DEFAULT 0    /* inits: I1, I2, I3; init_tm and init_dp hold 3 entries per pair                              */
+#define FDIPT_TMA_INITS_ALL 1        /* inits: I1 .. I5; init_tm and init_dp hold 5 entries per pair                                */
 typedef struct FdiptTmAlignArgs {
   int32_t S, N_a, atoms, ca;         /* structures, rows, atoms per row of prot: 37 or 5; the CA column (1 in both layouts)         */
   int32_t S_b, N_b, atoms_b;         /* of prot_b (where prot_b is NULL: S_b and atoms_b ignored, N_b = N_a)                        */
@@ -701,16 +706,19 @@ typedef struct FdiptTmAlignArgs {
   double* rmsd;                      /* f64: of the aligned pairs under the returned transform                                      */
   double* d0_a;                      /* f64: d0(n1)                                                                                 */
   double* d0_b;                      /* f64: d0(n2)                                                                                 */
-  double* init_tm;                   /* [P,3] f64: S / Ls of each initial alignment before its iteration; -1 where it was skipped   */
-  int32_t* init_dp;                  /* [P,3] i32: dynamic programmes of each initial alignment's iteration                         */
-  int32_t* best_init;                /* i32: the initial alignment whose iteration gave the result; -1 with a status bit before it  */
+  double* init_tm;                   /* [P,3] f64 ([P,5] with FDIPT_TMA_INITS_ALL): S / Ls of each initial alignment before its     */
+                                     /* iteration; -1 where it was skipped                                                          */
+  int32_t* init_dp;                  /* [P,3] i32 ([P,5] with FDIPT_TMA_INITS_ALL): dynamic programmes of each one's iteration      */
+  int32_t* best_init;                /* i32: the initial alignment whose iteration gave the result (0 .. 2, 0 .. 4 with             */
+                                     /* FDIPT_TMA_INITS_ALL); -1 with a status bit before it                                        */
   int32_t* status;                   /* i32: FDIPT_TMA_* bits                                                                       */
   void* workspace;                   /* may be NULL: fdipt_sample_tm_align_workspace is 0 (the search lives in LDS and registers)   */
   size_t workspace_bytes;
+  int32_t inits;                     /* FDIPT_TMA_INITS_DEFAULT or FDIPT_TMA_INITS_ALL (last: the fields before it keep their place) */
 } FdiptTmAlignArgs;
 size_t fdipt_sample_tm_align_workspace(int S, int N_a, int N_b, int P);
-/* FDIPT_EINVAL: a null pointer, S, N_a, N_b or P < 1, atoms not 37 or 5, ca outside 0 .. 4.  FDIPT_ESIZE: N_a or N_b >
- * FDIPT_TMA_MAX_ROWS. */
+/* FDIPT_EINVAL: a null pointer, S, N_a, N_b or P < 1, atoms not 37 or 5, ca outside 0 .. 4, inits none of the two.  FDIPT_ESIZE: N_a
+ * or N_b > FDIPT_TMA_MAX_ROWS. */
 int fdipt_sample_tm_align(const FdiptTmAlignArgs* args, fdipt_stream_t stream);
 
 /* ---------------------------------------------------------------- structure search (opt-in) */
@@ -779,6 +787,10 @@ size_t fdipt_structure_search_workspace(int Q, int top_k, int details);
  * that is none of the two, a plan that is not ascending or a cap outside 1 .. FDIPT_TMA_MAX_ROWS, details with detail_cap outside that
  * range.  FDIPT_ESIZE: N_q > FDIPT_TMA_MAX_ROWS, Q x D or Q x top_k x detail_cap >= 2^31, workspace too small. */
 int fdipt_structure_search(const FdiptSearchArgs* args, fdipt_stream_t stream);
+/* The same search with the initial alignments of every pair's search chosen, score and detail launches alike: inits is
+ * FDIPT_TMA_INITS_DEFAULT (fdipt_structure_search itself) or FDIPT_TMA_INITS_ALL; anything else is FDIPT_EINVAL.  FdiptSearchArgs keeps
+ * its layout: the mode is an argument of the entry, not a field.  The workspace of fdipt_structure_search_workspace serves both modes. */
+int fdipt_structure_search_inits(const FdiptSearchArgs* args, int32_t inits, fdipt_stream_t stream);
 
 /* ---------------------------------------------------------------- superposition-free accuracy (opt-in) */
 /* lDDT (Mariani et al. 2013; openfold/utils/loss.py lddt :382, lddt_ca :438), dRMSD (compute_drmsd :1518) and backbone FAPE (compute_fape

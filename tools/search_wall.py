@@ -10,8 +10,13 @@ One warm-up round, then ROUNDS rounds that alternate the three calls (device ten
 clock is read).  Prints every time, the median and the range per call, the ratio of the unpruned search to the padded call with the
 run-to-run spread next to it, the pruned share, and checks that the three agree on every query's best hit bit for bit.
 
-    python tools/search_wall.py [out.json]
+``--inits all`` runs the three calls in the five-start mode ("The two fragment starts").  ``--inits both``
+alternates ``search(prune=False)`` of the two modes instead (each between device-side events as well) and counts the pairs whose
+score rose.  ``--rounds`` sets the timed rounds.
+
+    python tools/search_wall.py [out.json] [--inits {default,all,both}] [--rounds K]
 """
+import argparse
 import json
 import os
 import sys
@@ -25,7 +30,12 @@ sys.path.insert(0, ROOT)
 
 from framedipt_amd import structure_search as ss, tm_align  # noqa: E402
 
-ROUNDS, N_Q, ROWS, N_DB = 4, 8, 300, 2048
+ap = argparse.ArgumentParser()
+ap.add_argument("out", nargs="?", default=None)
+ap.add_argument("--inits", choices=("default", "all", "both"), default="default")
+ap.add_argument("--rounds", type=int, default=4)
+opt = ap.parse_args()
+ROUNDS, N_Q, ROWS, N_DB = opt.rounds, 8, 300, 2048
 rng = np.random.default_rng(2048)
 
 
@@ -73,25 +83,52 @@ for e, t in enumerate(entries):
 pairs = np.array([[q, e] for q in range(N_Q) for e in range(N_DB)], dtype=np.int32)
 d_queries = torch.from_numpy(np.stack([five_atoms(q) for q in queries])).cuda()
 d_padded, d_padded_mask = torch.from_numpy(padded).cuda(), torch.from_numpy(padded_mask).cuda()
-calls = {"search": lambda: ss.search(d_queries, db, prune=False, return_scores=True),
-         "search_pruned_0.5": lambda: ss.search(d_queries, db, prune=True, min_score=0.5, return_scores=True),
-         "tm_align_padded": lambda: tm_align.tm_align(d_queries, d_padded, None, d_padded_mask, pairs=pairs)}
-walls, results = {k: [] for k in calls}, {}
+mode = "default" if opt.inits == "both" else opt.inits
+calls = {"search": lambda: ss.search(d_queries, db, prune=False, return_scores=True, inits=mode),
+         "search_pruned_0.5": lambda: ss.search(d_queries, db, prune=True, min_score=0.5, return_scores=True, inits=mode),
+         "tm_align_padded": lambda: tm_align.tm_align(d_queries, d_padded, None, d_padded_mask, pairs=pairs, inits=mode)}
+if opt.inits == "both":
+    calls = {"search": calls["search"], "search_all": lambda: ss.search(d_queries, db, prune=False, return_scores=True, inits="all")}
+walls, device_ms, results = {k: [] for k in calls}, {k: [] for k in calls}, {}
 for r in range(ROUNDS + 1):  # round 0 warms every shape up
     for name, call in calls.items():
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        start.record()
         results[name] = call()
+        stop.record()
         torch.cuda.synchronize()
         if r:
             walls[name].append(time.perf_counter() - t0)
+            device_ms[name].append(start.elapsed_time(stop))
         print(f"round {r} {name}: {time.perf_counter() - t0:.3f} s", flush=True)
 
 work = ss.plan(db.lengths)
 out = {"queries": N_Q, "rows": ROWS, "entries": N_DB, "pairs": len(pairs), "entry_rows": {"min": int(db.lengths.min()), "mean": float(db.lengths.mean()), "max": longest},
        "rounds": ROUNDS, "buckets": {int(c): int(e - s) for c, s, e in zip(work["bucket_cap"], work["bucket_start"][:-1], work["bucket_start"][1:])}}
 for name, w in walls.items():
-    out[name] = {"wall_s": w, "median_s": float(np.median(w)), "min_s": min(w), "max_s": max(w), "spread": (max(w) - min(w)) / float(np.median(w))}
+    out[name] = {"wall_s": w, "median_s": float(np.median(w)), "min_s": min(w), "max_s": max(w), "spread": (max(w) - min(w)) / float(np.median(w)),
+                 "between_events_ms": device_ms[name]}
+out["inits"] = opt.inits
+if opt.inits == "both":
+    plain, five = results["search"], results["search_all"]
+    out["all_over_default"] = out["search_all"]["median_s"] / out["search"]["median_s"]
+    out["tm_q_rose"], out["tm_q_fell"] = int((five["scores_q"] > plain["scores_q"]).sum()), int((five["scores_q"] < plain["scores_q"]).sum())
+    out["tm_t_rose"], out["tm_t_fell"] = int((five["scores_t"] > plain["scores_t"]).sum()), int((five["scores_t"] < plain["scores_t"]).sum())
+    out["largest_rise_tm_q"] = float(np.nanmax(five["scores_q"] - plain["scores_q"]))
+    out["pdb_tm"], out["pdb_tm_all"] = plain["pdb_tm"].tolist(), five["pdb_tm"].tolist()
+    out["best_hit_changed"] = int((plain["hit"][:, 0] != five["hit"][:, 0]).sum())
+    for m in ("default", "all"):  # the programmes per pair and the winners: one padded tm_align call per mode (the score pass returns neither)
+        dense = tm_align.tm_align(d_queries, d_padded, None, d_padded_mask, pairs=pairs, inits=m)
+        out[f"dp_per_pair_{m}"] = {"mean": float(dense["init_dp"].sum(1).mean()), "min": int(dense["init_dp"].sum(1).min()), "max": int(dense["init_dp"].sum(1).max())}
+        out[f"best_init_counts_{m}"] = np.bincount(dense["best_init"][dense["best_init"] >= 0], minlength=tm_align.N_INITS[m]).tolist()
+        out[f"scores_equal_the_padded_call_{m}"] = bool(np.array_equal((plain if m == "default" else five)["scores_t"], dense["tm_b"].reshape(N_Q, N_DB), equal_nan=True))
+    print(json.dumps(out), flush=True)
+    if opt.out:
+        with open(opt.out, "w") as f:
+            json.dump(out, f, indent=1)
+    sys.exit(0)
 out["search_over_padded"] = out["search"]["median_s"] / out["tm_align_padded"]["median_s"]
 out["pruned_over_search"] = out["search_pruned_0.5"]["median_s"] / out["search"]["median_s"]
 plain, pruned, dense = results["search"], results["search_pruned_0.5"], results["tm_align_padded"]
@@ -106,7 +143,7 @@ same_hits = np.array_equal(np.where(strong, plain["hit"][:, 0], -1), pruned["hit
 out["scores_equal_the_padded_call"], out["pruned_hits_equal_the_unpruned"] = bool(same_scores), bool(same_hits)
 out["pdb_tm"] = plain["pdb_tm"].tolist()
 print(json.dumps(out), flush=True)
-if len(sys.argv) > 1:
-    with open(sys.argv[1], "w") as f:
+if opt.out:
+    with open(opt.out, "w") as f:
         json.dump(out, f, indent=1)
 sys.exit(0 if same_scores and same_hits else 1)
