@@ -135,6 +135,44 @@ def plan_pairs(s_a: int, s_b: int, has_b: bool, pairs, ref_index):
     return np.stack([np.arange(s_a), np.asarray(ref_index).reshape(s_a)], axis=1).astype(np.int32), False
 
 
+def check_map(alignment, n_pairs: int, n_b: int, n_a: int):
+    """The row map of a mapped entry, ``[N_b]`` (one map for every pair) or ``[P, N_b]``, checked without torch or the library: a NumPy
+    array (or a list) comes back as int32 ``[P, N_b]`` after ``row_map.validate`` - a bad map raises here; a device tensor is checked
+    for its shape and integer dtype only and comes back as it is: the device judges it (the ``MAP_*`` status bits)."""
+    from . import row_map
+    if hasattr(alignment, "detach"):
+        shape, integer = tuple(alignment.shape), not (alignment.is_floating_point() or alignment.is_complex())
+    else:
+        alignment = np.asarray(alignment)
+        shape, integer = alignment.shape, np.issubdtype(alignment.dtype, np.integer)
+    if shape not in ((n_b,), (n_pairs, n_b)) or not integer:
+        raise ValueError(f"alignment should be integers [{n_b}] (the reference's rows) or [{n_pairs}, {n_b}] (per pair), got "
+                         f"{'integers' if integer else 'non-integers'} {tuple(shape)}")
+    if hasattr(alignment, "detach"):
+        return alignment
+    return np.broadcast_to(row_map.validate(alignment, n_a), (n_pairs, n_b)).copy()
+
+
+def upload_map(alignment, n_pairs: int, n_b: int, dev):
+    """What ``check_map`` returned as a contiguous int32 tensor [P, N_b] on ``dev``."""
+    import torch
+    x = alignment.to(dev) if torch.is_tensor(alignment) else torch.from_numpy(alignment).to(dev)
+    return x.to(torch.int32).expand(n_pairs, n_b).contiguous()
+
+
+def run_mapped(name: str, struct, dev, scalars: dict, inputs: dict, outputs: dict, row_map: dict, widen=(), workspace=None) -> dict:
+    """``run`` for an entry that takes a ``RowMap`` behind its args struct: ``row_map`` holds the struct's plain fields and its device
+    inputs; ``n_covered`` and ``n_reference`` [P] are allocated here and come back with the outputs (int64)."""
+    import torch
+    n_pairs = int(row_map["map"].shape[0])
+    with torch.cuda.device(dev):
+        counts = zeros_on(dev, {"n_covered": ("int32", (n_pairs,)), "n_reference": ("int32", (n_pairs,))})
+        rm = _lib.RowMap(**{k: _lib.ptr(v) if torch.is_tensor(v) or v is None else v for k, v in row_map.items()}, **{k: _lib.ptr(v) for k, v in counts.items()})
+        out = run(name, struct, dev, scalars, inputs, outputs, widen=widen, workspace=workspace, extra=(C.byref(rm),))
+        out.update(to_numpy(counts, widen=tuple(counts)))
+    return out
+
+
 def square_matrix(s: int, pair_list, values) -> np.ndarray:
     """[s,s] float64 with a unit diagonal and ``values`` at the pairs of ``pair_list``, mirrored."""
     matrix = np.ones((s, s), dtype=np.float64)

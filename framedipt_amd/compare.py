@@ -1,0 +1,47 @@
+"""Accuracy of a model against a reference whose rows do not correspond: align first, then score through the alignment.
+
+``aligned_accuracy`` runs the alignment search (``tm_align.tm_align``), hands its ``alignment`` - the row of the model aligned with each
+row of the reference, or -1 - to the two mapped accuracy entries (``lddt.local_accuracy`` and ``gdt.gdt_scores`` with ``alignment=``;
+DESIGN.md section 7.16) and returns one dict.  The reference owns the rows: every per-row output has the reference's N_b rows, lDDT
+under ``coverage="penalise"`` charges the reference rows the model has no partner for, and GDT is divided by the reference's rows.
+For a correspondence known beforehand - residue numbers, a deletion - build the map with ``row_map`` and call the two entries directly.
+"""
+from __future__ import annotations
+
+from . import gdt, lddt, tm_align
+
+_LDDT_KEYS = ("lddt", "res_lddt", "n_scored", "n_passed", "drmsd", "fape", "res_fape", "region_fape", "n_covered", "n_reference", "coverage")
+_GDT_KEYS = ("gdt_ts", "gdt_ha", "counts", "res_within", "rotation", "translation")
+
+
+def aligned_accuracy(prot_a, prot_b, mask_a=None, mask_b=None, pairs=None, ref_index=None, inits: str = "default", atoms: str = "ca",
+                     coverage: str = "penalise", superpose: str = "search") -> dict:
+    """prot_a [S,N_a,37,3] or [S,N_a,5,3]: the models; prot_b [S_b,N_b,37 or 5,3]: the references (device tensors or NumPy arrays, as
+    ``tm_align`` takes them); mask_a [S,N_a], mask_b [S_b,N_b]: the rows of each structure; ``pairs`` / ``ref_index``: as ``tm_align``
+    plans them (default: model i against reference i, or against the one reference).  ``inits``: the search's initial alignments;
+    ``atoms`` / ``coverage``: the lDDT atom set and switch; ``superpose``: the GDT mode.
+
+    Returns per pair ``tm`` (normalised by the reference), ``tm_a``, ``tm_b``, ``rmsd``, ``n_aligned``, ``alignment`` [P,N_b] and the
+    search's ``rotation`` / ``translation`` as ``tm_rotation`` / ``tm_translation``; the lDDT outputs ``lddt``, ``res_lddt`` [P,N_b],
+    ``n_scored``, ``n_passed``, ``drmsd``, ``fape``, ``res_fape``, ``region_fape``, ``n_covered``, ``n_reference``, ``coverage``; the GDT
+    outputs ``gdt_ts``, ``gdt_ha`` (divided by the reference's masked rows), ``counts``, ``res_within`` [P,N_b], ``rotation``,
+    ``translation`` [P,5,...]; the three status words ``tm_status``, ``lddt_status``, ``gdt_status``; ``pairs`` and ``atoms``."""
+    if prot_b is None:
+        raise ValueError("aligned_accuracy scores models against references: prot_b is required")
+    found = tm_align.tm_align(prot_a, prot_b, mask_a=mask_a, mask_b=mask_b, pairs=pairs, ref_index=ref_index, inits=inits)
+    pair_list, maps = found["pairs"], found["alignment"].astype("int32")
+    local = lddt.local_accuracy(prot_a, prot_b, atoms=atoms, res_mask=mask_a, res_mask_b=mask_b, pairs=pair_list, alignment=maps, coverage=coverage)
+    glob = gdt.gdt_scores(prot_a, prot_b, mask_a=mask_a, mask_b=mask_b, pairs=pair_list, alignment=maps, norm_length="reference", superpose=superpose)
+    out = {k: found[k] for k in ("tm", "tm_a", "tm_b", "rmsd", "n_aligned", "alignment", "pairs")}
+    out.update(tm_rotation=found["rotation"], tm_translation=found["translation"], tm_status=found["status"])
+    out.update({k: local[k] for k in _LDDT_KEYS})
+    out.update({k: glob[k] for k in _GDT_KEYS})
+    out.update(lddt_status=local["status"], gdt_status=glob["status"], atoms=atoms, coverage_mode=coverage, superpose=superpose)
+    return out
+
+
+def aligned_metrics(result: dict, p: int) -> dict:
+    """The flat entries of pair ``p`` for a metrics table, as Python numbers."""
+    return {"tm_score": float(result["tm"][p]), lddt.METRIC_NAMES[result["atoms"]]: float(result["lddt"][p]), "gdt_ts": float(result["gdt_ts"][p]),
+            "gdt_ha": float(result["gdt_ha"][p]), "drmsd": float(result["drmsd"][p]), "n_aligned": int(result["n_aligned"][p]),
+            "n_covered": int(result["n_covered"][p]), "n_reference": int(result["n_reference"][p]), "coverage": float(result["coverage"][p])}

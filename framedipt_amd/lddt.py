@@ -12,7 +12,9 @@ it has hinged as a whole against its context - and they mean something for the c
 ``local_accuracy`` is one call of ``fdipt_sample_lddt`` (csrc/lddt.hip, contract in include/fdipt.h and DESIGN.md section 7.13) for any
 number of ordered pairs, all in float64.  With one array every ordered pair is scored - lDDT is not symmetric, the reference structure
 chooses the scored distances - and ``consensus`` is the per-residue mean over the other samples as references: where the samples of a
-run agree.
+run agree.  With ``alignment=`` the rows of the reference need not be those of the model: ``fdipt_sample_lddt_mapped``
+(csrc/lddt_mapped.hip) reads the model through a row map (``row_map`` builds maps, ``compare.aligned_accuracy``
+takes them from ``tm_align``).
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
 PER_PAIR = ("lddt", "drmsd", "fape", "region_fape")
 PER_ROW = ("res_lddt", "res_fape")
 METRIC_NAMES = {"ca": "lddt_ca", "backbone": "lddt_bb", "all": "lddt_all"}
+COVERAGE = {"ignore": _lib.MAP_IGNORE, "penalise": _lib.MAP_PENALISE}
 
 
 def _shape(x, what: str):
@@ -48,7 +51,8 @@ def ordered_pairs(s: int) -> np.ndarray:
 
 
 def local_accuracy(prot_a, prot_b=None, atoms: str = "ca", res_mask=None, score_mask=None, atom_mask_a=None, atom_mask_b=None, pairs=None,
-                   ref_index=None, cutoff: float = 15.0, same_residue: bool = False, per_atom: bool = False) -> dict:
+                   ref_index=None, cutoff: float = 15.0, same_residue: bool = False, per_atom: bool = False, alignment=None,
+                   coverage: str = "ignore", res_mask_b=None) -> dict:
     """prot_a [S,N,37,3], [S,N,5,3] or a CA trace [S,N,3] float32, a device tensor (used in place:
     ``inference_fn(..., return_device=True)["prot_traj"][0]``) or a NumPy array (uploaded): the models; prot_b [S_b,N,...] likewise or
     None: the references.  ``atoms``: "ca", "backbone" (N, CA, C, O) or "all" (atom37 in both).  res_mask [S,N] (default: ones): the
@@ -67,9 +71,25 @@ def local_accuracy(prot_a, prot_b=None, atoms: str = "ca", res_mask=None, score_
     Returns NumPy arrays: ``lddt``, ``drmsd``, ``fape``, ``region_fape`` [P] float64, ``res_lddt``, ``res_fape`` [P,N] float64,
     ``n_scored`` [P,N] and ``n_passed`` [P,N,4] int64, ``status`` [P] int64 (``_lib.LDDT_*`` bits), ``pairs`` [P,2], ``atoms``.  A CA
     trace has no frames: the FAPE outputs are zero with ``LDDT_NO_FRAME`` set.  The host does not wait for the device before the
-    read-back."""
+    read-back.
+
+    ``alignment`` (int [N_b], or [P,N_b] per pair; NumPy or a device tensor): the rows of prot_b need not be those of prot_a - entry j is
+    the row of the model that corresponds to row j of the reference, or -1 (``tm_align(...)["alignment"]``, ``row_map``); DESIGN.md
+    section 7.16.  prot_b is then required and may have any row count; every per-row output has its N_b rows; ``score_mask`` is
+    [S_b,N_b] and ``res_mask_b`` [S_b,N_b] (default: ones) says which reference rows exist, ``res_mask`` [S,N_a] which model rows do.
+    ``coverage``: "ignore" - an atom takes part where it exists in the reference and its row has a present partner in the model, so
+    the numbers are those of the un-mapped call on the gathered model - or "penalise" - every atom pair of the reference within the
+    cutoff is scored and passes only where the model has both atoms, so a row without a partner scores eps / (eps + c); dRMSD and FAPE
+    are the same under both.  The result gains ``n_covered``, ``n_reference`` [P] int64 and ``coverage`` [P], their ratio (0 for no
+    reference row).  A NumPy map with an entry outside -1 .. N_a - 1 or a model row used twice raises; for a device tensor the pair's
+    ``status`` carries ``MAP_OUT_OF_RANGE`` / ``MAP_DUPLICATE`` and its outputs are zero."""
     if atoms not in MODES:
         raise ValueError(f"atoms should be 'ca', 'backbone' or 'all', got {atoms!r}")
+    if alignment is not None:
+        return _mapped_accuracy(prot_a, prot_b, atoms, res_mask, score_mask, atom_mask_a, atom_mask_b, pairs, ref_index, cutoff, same_residue, per_atom,
+                                alignment, coverage, res_mask_b)
+    if coverage != "ignore" or res_mask_b is not None:
+        raise ValueError("coverage and res_mask_b belong to a call with an alignment")
     s_a, n, atoms_a = _shape(prot_a, "prot_a")
     s_b, n_b, atoms_b = (s_a, n, atoms_a) if prot_b is None else _shape(prot_b, "prot_b")
     if n_b != n:
@@ -125,6 +145,62 @@ def local_accuracy(prot_a, prot_b=None, atoms: str = "ca", res_mask=None, score_
         out["matrix"][pair_list[:, 0], pair_list[:, 1]] = out["lddt"]
         out["drmsd_matrix"][pair_list[:, 0], pair_list[:, 1]] = out["drmsd"]
         out["consensus"] = consensus(out["res_lddt"], pair_list, s_a)
+    return out
+
+
+def _mapped_accuracy(prot_a, prot_b, atoms, res_mask, score_mask, atom_mask_a, atom_mask_b, pairs, ref_index, cutoff, same_residue, per_atom, alignment,
+                     coverage, res_mask_b) -> dict:
+    """``local_accuracy`` with an alignment: one call of ``fdipt_sample_lddt_mapped``."""
+    if coverage not in COVERAGE:
+        raise ValueError(f"coverage should be 'ignore' or 'penalise', got {coverage!r}")
+    if prot_b is None:
+        raise ValueError("an alignment maps the rows of prot_b to those of prot_a: prot_b is required")
+    s_a, n_a, atoms_a = _shape(prot_a, "prot_a")
+    s_b, n_b, atoms_b = _shape(prot_b, "prot_b")
+    for what, layout in (("prot_a", atoms_a), ("prot_b", atoms_b)):
+        if (atoms == "all" and layout != 37) or (atoms == "backbone" and layout == 1):
+            raise ValueError(f"atoms={atoms!r} needs {'atom37' if atoms == 'all' else 'the backbone atoms'}: {what} holds {layout} atom(s) per row")
+    if not cutoff > 0:
+        raise ValueError(f"cutoff should be positive, got {cutoff}")
+    pair_list, _ = _call.plan_pairs(s_a, s_b, True, pairs, ref_index)
+    n_pairs, k = len(pair_list), SET_ATOMS[atoms]
+    checks = (("res_mask", res_mask, (s_a, n_a)), ("res_mask_b", res_mask_b, (s_b, n_b)), ("score_mask", score_mask, (s_b, n_b)),
+              ("atom_mask_a", atom_mask_a, (s_a, n_a, atoms_a)), ("atom_mask_b", atom_mask_b, (s_b, n_b, atoms_b)))
+    for what, x, shape in checks:
+        if x is not None and tuple(x.shape if hasattr(x, "shape") else np.shape(x)) != shape:
+            raise ValueError(f"{what} {tuple(x.shape if hasattr(x, 'shape') else np.shape(x))} does not match its structure: expected {shape}")
+    alignment = _call.check_map(alignment, n_pairs, n_b, n_a)
+    ints = ("n_scored", "n_passed", "status")
+    outputs = {key: ("float64", (n_pairs,)) for key in PER_PAIR}
+    outputs.update({key: ("float64", (n_pairs, n_b)) for key in PER_ROW})
+    outputs.update(n_scored=("int32", (n_pairs, n_b)), n_passed=("int32", (n_pairs, n_b, 4)), status=("int32", (n_pairs,)))
+    if per_atom:
+        outputs["atom_lddt"] = ("float64", (n_pairs, n_b, k))
+    if n_pairs == 0:
+        out = _call.empty_outputs(outputs, ints)
+        out.update(n_covered=np.zeros(0, dtype=np.int64), n_reference=np.zeros(0, dtype=np.int64))
+    else:
+        import torch
+        dev, (xa, xb) = _call.upload("local_accuracy", prot_a=prot_a, prot_b=prot_b)
+
+        def atom_mask(x, shape, what):
+            m = _call.per_row(x, shape, what, "mask", dev=dev)
+            return None if m is None else m.to(torch.uint8).contiguous()
+
+        out = _call.run_mapped("fdipt_sample_lddt_mapped", _lib.LddtArgs, dev,
+                               dict(S=s_a, N=n_b, atoms=atoms_a, S_b=s_b, atoms_b=atoms_b, P=n_pairs, mode=MODES[atoms], same_residue=int(bool(same_residue)),
+                                    cutoff=float(cutoff)),
+                               dict(prot=xa, prot_b=xb, res_mask=_call.per_row(res_mask, (s_a, n_a), "res_mask", "mask", default=1, dev=dev),
+                                    atom_mask_a=atom_mask(atom_mask_a, (s_a, n_a, atoms_a), "atom_mask_a"),
+                                    atom_mask_b=atom_mask(atom_mask_b, (s_b, n_b, atoms_b), "atom_mask_b"), pairs=torch.from_numpy(pair_list).to(dev)),
+                               outputs,
+                               dict(N_a=n_a, coverage=COVERAGE[coverage], map=_call.upload_map(alignment, n_pairs, n_b, dev),
+                                    res_mask_b=_call.per_row(res_mask_b, (s_b, n_b), "res_mask_b", "mask", default=1, dev=dev),
+                                    score_mask_b=_call.per_row(score_mask, (s_b, n_b), "score_mask", "mask", default=1, dev=dev)),
+                               widen=ints, workspace=("fdipt_sample_lddt_mapped_workspace", n_pairs, n_b))
+    out["coverage"] = np.divide(out["n_covered"], out["n_reference"], out=np.zeros(n_pairs), where=out["n_reference"] > 0)
+    out["pairs"] = pair_list.astype(np.int64)
+    out["atoms"] = atoms
     return out
 
 

@@ -701,7 +701,7 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
     return write_tm_align_table(out_dir, structures, skipped, inits)
 
 
-def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1, inpainting: bool = False, inits: str = "default"):
+def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1, inpainting: bool = False, inits: str = "default", accuracy: bool = False):
     """Rank 0, after the gather (``--novelty SET.npz``; framedipt_amd/structure_search.py).  De novo runs only: every final sample is
     searched in the structure set, one ``search`` call per sample length, the samples compacted to their set rows (``compact_rows``).
     The reference (evaluation/eval_denovo.py:plot_novelty) searches the ESMFold refold of a sample with foldseek; here the query is
@@ -709,7 +709,10 @@ def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1,
     in the output.  Writes ``novelty.json`` (per sample pdbTM, the hit's name, tm_t, n_aligned, the counts and with top_k > 1 every hit)
     and ``novelty.csv`` (length, sample, pdbTM, hit).  A length beyond the search's row limit is recorded as skipped.  Inpainting runs
     are refused: a redesigned loop in a fixed context is not novel by construction.  ``inits``: the initial alignments of the search
-    (``--tm-inits``), recorded in ``novelty.json``.  Returns the summary written."""
+    (``--tm-inits``), recorded in ``novelty.json``.  ``accuracy`` (``--novelty-accuracy``): also lDDT-CA and GDT of every sample against
+    each of its hits through the hit's alignment (``structure_search.hit_accuracy``), written to
+    ``novelty_accuracy.json`` / ``.csv`` - ``novelty.json`` and ``novelty.csv`` hold what they hold without it.  Returns the summary
+    written."""
     if inpainting:
         raise ValueError("--novelty is for de novo runs: a redesigned region inside a fixed context is not novel by construction")
     import csv
@@ -719,7 +722,7 @@ def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1,
     by_length = {}
     for r in records:
         by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
-    samples, skipped = [], []
+    samples, skipped, accurate = [], [], []
     for length, rs in by_length.items():
         prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
         mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
@@ -728,6 +731,10 @@ def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1,
             skipped.append(length)
             continue
         res = structure_search.search(rows, db, mask=rows_mask, top_k=top_k, inits=inits)
+        if accuracy:
+            acc = structure_search.hit_accuracy(res, rows, db, mask=rows_mask)
+            accurate += [{"length": length, "sample": r["sample_i"], "rank": j, "hit": res["names"][q][j], **structure_search.hit_accuracy_metrics(acc, q, j)}
+                         for q, r in enumerate(rs) for j in range(top_k) if res["hit"][q, j] >= 0]
         for q, r in enumerate(rs):
             entry = {"length": length, "sample": r["sample_i"], **structure_search.novelty_metrics(res, q),
                      **{k: int(res[k][q]) for k in ("n_scored", "n_pruned", "n_skipped")}}
@@ -745,6 +752,15 @@ def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1,
         w = csv.DictWriter(f, fieldnames=["length", "sample", "pdbTM", "hit"])
         w.writeheader()
         w.writerows({"length": e["length"], "sample": e["sample"], "pdbTM": repr(e["pdbTM"]), "hit": e["hit"]} for e in samples)
+    if accuracy:
+        with open(os.path.join(out_dir, "novelty_accuracy.json"), "w") as f:
+            json.dump({"set": str(set_path), "top_k": int(top_k), "atoms": "ca", "coverage": "penalise", "superpose": "search",
+                       "reference": "the hit: lDDT charges the hit's rows the sample has no partner for, GDT is divided by the hit's rows",
+                       "hits": accurate}, f, indent=1)
+        with open(os.path.join(out_dir, "novelty_accuracy.csv"), "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=["length", "sample", "rank", "hit", "lddt_ca", "gdt_ts", "gdt_ha", "n_covered", "n_reference"], extrasaction="ignore")
+            w.writeheader()
+            w.writerows({**e, **{k: repr(e[k]) for k in ("lddt_ca", "gdt_ts", "gdt_ha")}} for e in accurate)
     return summary
 
 
@@ -943,6 +959,8 @@ def main():
                     "all adds a local-superposition and a fragment-threading start (DESIGN.md section 7.9), for pairs that share a motif the three "
                     "default ones cannot see; recorded in diversity_aligned.json, tm_align.json and novelty.json")
     ap.add_argument("--novelty-top-k", type=int, default=1, help="--novelty: hits kept per sample (1 .. 64)")
+    ap.add_argument("--novelty-accuracy", action="store_true", help="--novelty: also lDDT-CA and GDT-TS / GDT-HA of every sample against each of its hits, "
+                    "through the hit's alignment -> novelty_accuracy.json, novelty_accuracy.csv (novelty.json and novelty.csv do not change)")
     ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score, --tm-align: the TM-score threshold of the clusters (reference default)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
     a = ap.parse_args()
@@ -953,6 +971,8 @@ def main():
             ap.error(f"--keep {a.keep}: expected all, last or an integer stride")
     if a.novelty and a.download_dir is not None:
         ap.error("--novelty is for de novo runs: a redesigned region inside a fixed context is not novel by construction")
+    if a.novelty_accuracy and not a.novelty:
+        ap.error("--novelty-accuracy needs --novelty SET.npz")
     if a.novelty and not 1 <= a.novelty_top_k <= 64:
         ap.error(f"--novelty-top-k {a.novelty_top_k}: expected 1 .. 64")
 
@@ -1114,7 +1134,7 @@ def main():
             print(f"GDT-TS and GDT-HA of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
         if a.novelty:
             t1 = time.perf_counter()
-            done = run_novelty(a.out_dir, allrecs, gathered, a.novelty, top_k=a.novelty_top_k, inpainting=inp, inits=a.tm_inits)
+            done = run_novelty(a.out_dir, allrecs, gathered, a.novelty, top_k=a.novelty_top_k, inpainting=inp, inits=a.tm_inits, accuracy=a.novelty_accuracy)
             print(f"novelty of {len(done['samples'])} sample(s) against {done['entries']} structure(s) in {time.perf_counter() - t1:.2f} s -> "
                   f"{a.out_dir}/novelty.json, novelty.csv", flush=True)
         if a.design:

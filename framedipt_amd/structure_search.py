@@ -239,3 +239,48 @@ def novelty_metrics(result: dict, q: int, db: StructureSet = None) -> dict:
     e = int(result["hit"][q, 0])
     name = None if e < 0 else result["names"][q][0] if "names" in result else db.names[e] if db is not None else str(e)
     return {"pdbTM": float(result["pdb_tm"][q]), "hit": name, "tm_t": float(result["tm_t"][q, 0]), "n_aligned": int(result["n_aligned"][q, 0])}
+
+
+def hit_accuracy(result: dict, prot, db: StructureSet, mask=None, atoms: str = "ca", coverage: str = "penalise", superpose: str = "search") -> dict:
+    """Is a query locally the same fold as its hits?  lDDT-CA and GDT of every query of a ``search`` result (``details=True``) against
+    each of its hits, through the hit's ``alignment`` (``lddt.local_accuracy`` and ``gdt.gdt_scores`` with ``alignment=``; DESIGN.md
+    section 7.16): the hit is the reference, so ``coverage="penalise"`` charges the entry rows the query has no partner for, and GDT is
+    normalised by the hit's rows.  ``prot`` / ``mask``: what ``search`` was given.  The hits' traces are gathered from the set into one
+    padded [Q * top_k, L, 3] array.  A structure set holds CA traces: ``atoms`` is "ca".
+
+    Returns [Q,k] arrays - ``lddt``, ``gdt_ts``, ``gdt_ha`` float64 (NaN without a hit), ``n_covered``, ``n_reference`` int64,
+    ``coverage`` - and ``res_lddt`` [Q,k,L] float64, ``res_within`` [Q,k,L] int32, ``lddt_status``, ``gdt_status`` [Q,k]."""
+    if atoms != "ca":
+        raise ValueError(f"a structure set holds CA traces: atoms should be 'ca', got {atoms!r}")
+    if "alignment" not in result:
+        raise ValueError("hit_accuracy needs the alignments of the hits: search(..., details=True)")
+    from . import gdt, lddt
+    hits, alignment = np.asarray(result["hit"]), np.asarray(result["alignment"])
+    n_q, top_k, rows = alignment.shape
+    if rows == 0:  # (no query has a hit)
+        nan, zero = np.full((n_q, top_k), np.nan), np.zeros((n_q, top_k), dtype=np.int64)
+        return {"lddt": nan, "gdt_ts": nan.copy(), "gdt_ha": nan.copy(), "n_covered": zero, "n_reference": zero.copy(), "coverage": zero.astype(np.float64),
+                "res_lddt": np.zeros((n_q, top_k, 0)), "res_within": np.zeros((n_q, top_k, 0), dtype=np.int32), "lddt_status": zero.copy(), "gdt_status": zero.copy()}
+    ref, ref_mask = np.zeros((n_q * top_k, rows, 3), dtype=np.float32), np.zeros((n_q * top_k, rows), dtype=np.float32)
+    for p, e in enumerate(hits.reshape(-1)):
+        if e >= 0:
+            trace = db.entry(int(e))
+            ref[p, :len(trace)], ref_mask[p, :len(trace)] = trace, 1
+    maps = np.where(ref_mask != 0, alignment.reshape(n_q * top_k, rows), -1).astype(np.int32)
+    pairs = np.stack([np.repeat(np.arange(n_q), top_k), np.arange(n_q * top_k)], axis=1).astype(np.int32)
+    ca = prot if tuple(prot.shape[2:]) == (3,) else prot[:, :, CA]  # (a trace for the GDT entry: a CA trace goes with a CA trace)
+    local = lddt.local_accuracy(ca, ref, atoms="ca", res_mask=mask, res_mask_b=ref_mask, pairs=pairs, alignment=maps, coverage=coverage)
+    glob = gdt.gdt_scores(ca, ref, mask_a=mask, mask_b=ref_mask, pairs=pairs, alignment=maps, norm_length="reference", superpose=superpose)
+    miss = (hits < 0)
+    shape = (n_q, top_k)
+    out = {"lddt": np.where(miss, np.nan, local["lddt"].reshape(shape)), "gdt_ts": glob["gdt_ts"].reshape(shape), "gdt_ha": glob["gdt_ha"].reshape(shape),
+           "n_covered": local["n_covered"].reshape(shape), "n_reference": local["n_reference"].reshape(shape), "coverage": local["coverage"].reshape(shape),
+           "res_lddt": local["res_lddt"].reshape(shape + (rows,)), "res_within": glob["res_within"].reshape(shape + (rows,)),
+           "lddt_status": local["status"].reshape(shape), "gdt_status": glob["status"].reshape(shape)}
+    return out
+
+
+def hit_accuracy_metrics(accuracy: dict, q: int, k: int = 0) -> dict:
+    """The flat entries of hit ``k`` of query ``q`` of a ``hit_accuracy`` result, as Python numbers."""
+    return {"lddt_ca": float(accuracy["lddt"][q, k]), "gdt_ts": float(accuracy["gdt_ts"][q, k]), "gdt_ha": float(accuracy["gdt_ha"][q, k]),
+            "n_covered": int(accuracy["n_covered"][q, k]), "n_reference": int(accuracy["n_reference"][q, k]), "coverage": float(accuracy["coverage"][q, k])}

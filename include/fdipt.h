@@ -905,6 +905,50 @@ size_t fdipt_sample_gdt_workspace(int S, int N, int P);
  * FDIPT_TM_MAX_ROWS. */
 int fdipt_sample_gdt(const FdiptGdtArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- accuracy through a row map (opt-in) */
+/* The two accuracy entries above for structures whose rows do NOT correspond: a pair p is (model ia of prot [S,N_a,atoms,3], reference
+ * ib of prot_b [S_b,N_b,atoms_b,3]) with a row map m = map[p,:], int32 [N_b]: m[j] is the model row that corresponds to reference row j,
+ * or -1 - the layout of FdiptTmAlignArgs.alignment and of FdiptSearchArgs.alignment.  N_a and N_b are independent; every per-row output
+ * has N_b rows: the reference owns the rows, as it owns the distances in lDDT.  The contract is DESIGN.md section 7.16.
+ * In both entries args->N is N_b, args->prot_b is required, and what args says about the model ([S,N,...]: prot, res_mask, atom_mask_a,
+ * mask) has N_a rows; FdiptLddtArgs.score_mask is not read.
+ * Reference row j EXISTS where res_mask_b[ib,j] != 0 (GDT: mask_b[ib,j]).  It is COVERED where it exists, 0 <= m[j] < N_a and
+ * res_mask[ia,m[j]] != 0 (GDT: mask[ia,m[j]]).  A model atom of a covered row is present by the rule of the un-mapped entry (atom_mask_a,
+ * or any non-zero coordinate).  The map need not be monotone; it must be injective on its non-negative entries.
+ * The gathered model G(p): row j is model row m[j] where covered, absent (no atom present) elsewhere.
+ * lDDT, coverage FDIPT_MAP_IGNORE: an atom takes part where it exists in the reference and is present in G; every output is bit for bit
+ * what fdipt_sample_lddt returns on G with absent atoms masked off, res_mask = the reference's existing rows and score_mask =
+ * score_mask_b[ib].  FDIPT_MAP_PENALISE (OpenFold's lddt where only the true mask is known): the atom pair (u, v) is scored, and counted
+ * in c, where both atoms exist IN THE REFERENCE and d_b < cutoff (and u != v, and the same-residue rule); it passes threshold t only if
+ * both atoms are present in G and |d_b - d_a| < t.  An uncovered row therefore scores eps / (eps + c).  The integers equal those of
+ * fdipt_sample_lddt on G with every absent atom placed at a far, distinct point and marked present: that construction is the test
+ * oracle.  drmsd and the FAPE outputs are the same under both switches (coverage has no meaning for them).
+ * GDT: x, y are the CA atoms of (model row m[j], reference row j) for ascending j over the covered rows; n their number; everything after
+ * the load is fdipt_sample_gdt in its three modes, every output bit for bit that entry's on G; res_within is [P,N_b]; L = n without a
+ * norm_length.  N_a and N_b are each limited to FDIPT_TM_MAX_ROWS.  A CA trace (atoms = 1, ca = 0) is accepted for either structure.
+ * Status bits of the map, shared by both entries (outside the bits each entry uses itself): either zeroes the pair's outputs (lDDT) or
+ * makes them NaN (GDT) exactly as that entry's SKIPPED does, and changes no bit of another pair.  n_covered and n_reference are 0 then. */
+#define FDIPT_MAP_IGNORE 0
+#define FDIPT_MAP_PENALISE 1
+#define FDIPT_MAP_OUT_OF_RANGE 8     /* status: an entry of the pair's map is < -1 or >= N_a                                        */
+#define FDIPT_MAP_DUPLICATE 16       /* status: two reference rows of the pair map to the same model row                            */
+typedef struct FdiptRowMap {
+  int32_t N_a, coverage;             /* rows of prot; FDIPT_MAP_IGNORE / FDIPT_MAP_PENALISE (lDDT only)                             */
+  const int32_t* map;                /* [P,args->N] i32                                                                             */
+  const float* res_mask_b;           /* [S_b,args->N] f32: the reference's existing rows (lDDT; GDT reads args->mask_b)             */
+  const float* score_mask_b;         /* [S_b,args->N] f32: the score rows, in reference rows (lDDT)                                 */
+  int32_t* n_covered;                /* [P] i32: covered rows                                                                       */
+  int32_t* n_reference;              /* [P] i32: existing reference rows                                                            */
+} FdiptRowMap;
+/* fdipt_sample_lddt_workspace(P, N_b) plus the verdicts on the maps */
+size_t fdipt_sample_lddt_mapped_workspace(int P, int N_b);
+/* Three launches on one stream: the verdicts on the maps (and n_covered, n_reference), then fdipt_sample_lddt's two.  FDIPT_EINVAL: as
+ * fdipt_sample_lddt, a null pointer in map, N_a < 1, a coverage outside the two, no prot_b.  FDIPT_ESIZE: as fdipt_sample_lddt. */
+int fdipt_sample_lddt_mapped(const FdiptLddtArgs* args, const FdiptRowMap* row_map, fdipt_stream_t stream);
+/* One launch.  FDIPT_EINVAL: as fdipt_sample_gdt (atoms 37, 5 or 1; ca below atoms), a null map, n_covered or n_reference, N_a < 1, no
+ * prot_b.  FDIPT_ESIZE: N_a or N_b > FDIPT_TM_MAX_ROWS. */
+int fdipt_sample_gdt_mapped(const FdiptGdtArgs* args, const FdiptRowMap* row_map, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- inverse folding (opt-in) */
 /* The vanilla full-backbone ProteinMPNN (ProteinMPNN/protein_mpnn_utils.py: ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward
  * and .sample), inference only, float32 throughout; the contract is DESIGN.md section 7.10.  Letters are in the MODEL's alphabet
