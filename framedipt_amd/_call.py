@@ -1,5 +1,5 @@
 """The one call path of the sample-analysis entries (selection, evaluation, violations, secondary_structure, sasa, tm_score, tm_align,
-inverse_folding): shape checks, device choice and upload, optional per-row inputs, output buffers, the C call and the read-back.
+inverse_folding, seq_align): shape checks, device choice and upload, optional per-row inputs, output buffers, the C call and the read-back.
 
 ``structure_shape``, ``per_row`` on the host (``dev`` None), ``plan_pairs`` and ``square_matrix`` need neither torch nor the built
 library: an entry raises its shape errors before either is touched.

@@ -5,10 +5,12 @@ row of the reference, or -1 - to the two mapped accuracy entries (``lddt.local_a
 DESIGN.md section 7.16) and returns one dict.  The reference owns the rows: every per-row output has the reference's N_b rows, lDDT
 under ``coverage="penalise"`` charges the reference rows the model has no partner for, and GDT is divided by the reference's rows.
 For a correspondence known beforehand - residue numbers, a deletion - build the map with ``row_map`` and call the two entries directly.
+``sequence_aligned_accuracy`` takes the map from the sequences instead (``seq_align.chain_row_map``: a global alignment per chain, what the
+reference's ``framedipt/protein/align.py`` does before it superposes).
 """
 from __future__ import annotations
 
-from . import gdt, lddt, tm_align
+from . import gdt, lddt, seq_align, tm_align
 
 _LDDT_KEYS = ("lddt", "res_lddt", "n_scored", "n_passed", "drmsd", "fape", "res_fape", "region_fape", "n_covered", "n_reference", "coverage")
 _GDT_KEYS = ("gdt_ts", "gdt_ha", "counts", "res_within", "rotation", "translation")
@@ -37,6 +39,34 @@ def aligned_accuracy(prot_a, prot_b, mask_a=None, mask_b=None, pairs=None, ref_i
     out.update({k: local[k] for k in _LDDT_KEYS})
     out.update({k: glob[k] for k in _GDT_KEYS})
     out.update(lddt_status=local["status"], gdt_status=glob["status"], atoms=atoms, coverage_mode=coverage, superpose=superpose)
+    return out
+
+
+def sequence_aligned_accuracy(prot_a, aatype_a, prot_b, aatype_b, chain_a=None, chain_b=None, chain_pairs=None, mask_a=None, mask_b=None,
+                              pairs=None, ref_index=None, atoms: str = "ca", coverage: str = "penalise", superpose: str = "search", **scoring) -> dict:
+    """prot_a [S,N_a,37 or 5,3]: the models, which share the residue types aatype_a [N_a] and the chain labels chain_a [N_a]; prot_b
+    [S_b,N_b,37 or 5,3]: the references with aatype_b [N_b], chain_b [N_b].  The rows are matched by ``seq_align.chain_row_map`` (chains
+    with equal labels, or ``chain_pairs``; ``scoring``: its ``matrix``, ``open_gap``, ``extend_gap``), and the one map serves every pair of
+    ``local_accuracy(..., alignment=, coverage=)`` and ``gdt_scores(..., alignment=, norm_length="reference")``.
+
+    Returns ``alignment`` [N_b], ``chains`` and per chain pair ``score``, ``identity``, ``identity_b``, ``n_identical``, ``n_aligned``,
+    ``seq_status``; per pair of structures the lDDT and GDT outputs of ``aligned_accuracy`` (``lddt``, ``res_lddt`` [P,N_b], ``gdt_ts``,
+    ``gdt_ha``, ``n_covered``, ...), ``lddt_status``, ``gdt_status``; ``atoms``, ``coverage_mode``, ``superpose``."""
+    if prot_b is None:
+        raise ValueError("sequence_aligned_accuracy scores models against references: prot_b is required")
+    n_a, n_b = int(prot_a.shape[1]), int(prot_b.shape[1])
+    for what, aatype, n in (("aatype_a", aatype_a, n_a), ("aatype_b", aatype_b, n_b)):
+        if len(aatype) != n:
+            raise ValueError(f"{what} holds {len(aatype)} letters for {n} rows")
+    found = seq_align.chain_row_map(aatype_a, chain_a, aatype_b, chain_b, chain_pairs=chain_pairs, **scoring)
+    m = found["alignment"]
+    local = lddt.local_accuracy(prot_a, prot_b, atoms=atoms, res_mask=mask_a, res_mask_b=mask_b, pairs=pairs, ref_index=ref_index, alignment=m, coverage=coverage)
+    glob = gdt.gdt_scores(prot_a, prot_b, mask_a=mask_a, mask_b=mask_b, pairs=pairs, ref_index=ref_index, alignment=m, norm_length="reference", superpose=superpose)
+    out = {k: found[k] for k in ("alignment", "chains", "score", "identity", "identity_b", "n_identical", "n_aligned")}
+    out.update({k: local[k] for k in _LDDT_KEYS})
+    out.update({k: glob[k] for k in _GDT_KEYS})
+    out.update(seq_status=found["status"], lddt_status=local["status"], gdt_status=glob["status"], pairs=local["pairs"], atoms=atoms, coverage_mode=coverage,
+               superpose=superpose)
     return out
 
 

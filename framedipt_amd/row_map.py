@@ -3,8 +3,10 @@ section 7.16), in NumPy on the host.  A map is int32 ``[N_b]``: entry j is the r
 of the reference (structure b), or -1 - the layout of ``tm_align(...)["alignment"]`` and of ``structure_search``'s.  A map need not be
 monotone; it must be injective on its non-negative entries.
 
-``from_residue_numbers`` is this project's counterpart of the reference's ``framedipt/protein/align.py``: correspondence by residue
-identity, before any superposition.
+``from_residue_numbers`` is this project's counterpart of the reference's ``framedipt/protein/align.py`` by numbering: correspondence
+by residue identity, before any superposition.  It is that file's counterpart only while the two structures number their residues alike;
+``seq_align.chain_row_map`` is the counterpart by sequence (a global alignment per chain on the device, what that file itself does) and
+returns a map of the same layout.  This module stays pure NumPy.
 """
 from __future__ import annotations
 

@@ -812,11 +812,56 @@ def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, 
                                  "fasta": fasta}
                 if native is not None:
                     samples[stem]["native_conditional_score"] = float(native[b])
+                gathered[r["item"]]["designed_sequences"] = list(res["sequences"][b])  # what --seq-diversity compares
     summary = {"weights": model.source, "synthetic": not weights, "ca_only": model.ca_only, "k_neighbors": model.k_neighbors, "temperature": temperature, "seed": seed,
                "seq_per_sample": seq_per_sample, "omit": omit_aas, "samples": samples}
     with open(os.path.join(out_dir, "design.json"), "w") as f:
         json.dump(summary, f, indent=1)
     return summary
+
+
+def write_seq_diversity(out_dir: str, owners, matrix, scoring: dict):
+    """``pairwise_seq_identity.npy`` (``matrix`` [Q,Q]: ``identity_short`` of every pair of designed sequences, unit diagonal) and
+    ``seq_diversity.json``: ``owners`` [(sample stem, index among the sample's sequences)] in the matrix's order, the mean off-diagonal
+    identity, per sample the largest identity of one of its sequences to a sequence of ANOTHER sample (None for a lone sample), and the
+    scoring parameters.  Returns the summary written."""
+    matrix = np.asarray(matrix, dtype=np.float64)
+    q = len(owners)
+    stems = [o[0] for o in owners]
+    other = np.array([[a != b for b in stems] for a in stems], dtype=bool).reshape(q, q)
+    nearest = {}
+    for stem in dict.fromkeys(stems):
+        rows = np.array([o == stem for o in stems])
+        block = matrix[rows][:, ~rows]
+        nearest[stem] = float(block.max()) if block.size else None
+    off = ~np.eye(q, dtype=bool)
+    summary = {"n_sequences": q, "sequences": [{"sample": stem, "index": int(k)} for stem, k in owners],
+               "mean_identity": float(matrix[off].mean()) if q > 1 else None,
+               "mean_identity_between_samples": float(matrix[other].mean()) if other.any() else None,
+               "max_identity_to_other_sample": nearest, "identity": "n_identical / min(len_a, len_b)", "scoring": scoring,
+               "matrix": "pairwise_seq_identity.npy"}
+    np.save(os.path.join(out_dir, "pairwise_seq_identity.npy"), matrix)
+    with open(os.path.join(out_dir, "seq_diversity.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    return summary
+
+
+def run_seq_diversity(out_dir: str, records, gathered: dict, matrix="blosum62", open_gap: float = -10.0, extend_gap: float = -0.5):
+    """Rank 0, after ``run_design`` (``--design --seq-diversity``, de novo runs; framedipt_amd/seq_align.py): every designed sequence of
+    every sample (``designed_sequences`` of the gathered entries, which ``run_design`` leaves there) against every other in ONE
+    score-only launch of the global alignment - the lengths may differ - then ``write_seq_diversity``."""
+    from . import seq_align
+    owners, seqs = [], []
+    for r in records:
+        stem = os.path.splitext(r["file"])[0].replace(os.sep, "_")
+        for k, seq in enumerate(gathered[r["item"]].get("designed_sequences") or ()):
+            owners.append((stem, k))
+            seqs.append(seq)
+    if not seqs:
+        raise ValueError("--seq-diversity needs designed sequences: run_design has left none on the gathered entries")
+    found = seq_align.align_sequences(seqs, matrix=matrix, open_gap=open_gap, extend_gap=extend_gap, traceback=False)
+    scoring = {"matrix": matrix if isinstance(matrix, str) else "custom", "open_gap": float(open_gap), "extend_gap": float(extend_gap), "mode": "global"}
+    return write_seq_diversity(out_dir, owners, found["matrix"], scoring)
 
 
 def reference_layout_writer(out_dir: str, net, final_only: bool):
@@ -951,6 +996,9 @@ def main():
     ap.add_argument("--ca-only", action="store_true", help="--design: the CA-only ProteinMPNN (reads the CA trace alone; --mpnn-weights must then be a CA checkpoint)")
     ap.add_argument("--mpnn-weights", default=None, help="--design: a ProteinMPNN checkpoint (.pt with model_state_dict, num_edges, noise_level); default: "
                     "SYNTHETIC parameters, stated as such in the output")
+    ap.add_argument("--seq-diversity", action="store_true", help="--design, de novo runs: rank 0 then aligns all designed sequences of all samples all-against-all on "
+                    "its GPU (framedipt_amd/seq_align.py: global alignment, BLOSUM62, open -10, extend -0.5, score only) and writes pairwise_seq_identity.npy "
+                    "and seq_diversity.json")
     ap.add_argument("--novelty", default=None, metavar="SET.npz", help="de novo runs: after the run, rank 0 searches every final sample in the structure set "
                     "(framedipt_amd/structure_search.py: StructureSet.save) on its GPU and keeps the largest TM-score of the hits, the reference's pdbTM: "
                     "novelty.json, novelty.csv.  The query is the sample itself, not an ESMFold refold, and the search is this project's own: no parity "
@@ -973,6 +1021,8 @@ def main():
         ap.error("--novelty is for de novo runs: a redesigned region inside a fixed context is not novel by construction")
     if a.novelty_accuracy and not a.novelty:
         ap.error("--novelty-accuracy needs --novelty SET.npz")
+    if a.seq_diversity and (not a.design or a.download_dir is not None):
+        ap.error("--seq-diversity compares the designed sequences of a de novo run: it needs --design and no --download-dir")
     if a.novelty and not 1 <= a.novelty_top_k <= 64:
         ap.error(f"--novelty-top-k {a.novelty_top_k}: expected 1 .. 64")
 
@@ -1142,6 +1192,11 @@ def main():
             done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights, omit_aas=a.omit_aas, ca_only=a.ca_only)
             print(f"{a.seq_per_sample} sequence(s) for each of {len(done['samples'])} sample(s) with {'SYNTHETIC ' if done['synthetic'] else ''}{'CA-only ' if done['ca_only'] else ''}ProteinMPNN parameters{'' if done['synthetic'] else ' of ' + str(done['weights'])} "
                   f"in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/seqs/<sample>.fa, design.json", flush=True)
+            if a.seq_diversity:
+                t1 = time.perf_counter()
+                done = run_seq_diversity(a.out_dir, allrecs, gathered)
+                print(f"sequence identity of {done['n_sequences']} designed sequence(s), all against all, in {time.perf_counter() - t1:.2f} s -> "
+                      f"{a.out_dir}/pairwise_seq_identity.npy, seq_diversity.json", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -949,6 +949,65 @@ int fdipt_sample_lddt_mapped(const FdiptLddtArgs* args, const FdiptRowMap* row_m
  * prot_b.  FDIPT_ESIZE: N_a or N_b > FDIPT_TM_MAX_ROWS. */
 int fdipt_sample_gdt_mapped(const FdiptGdtArgs* args, const FdiptRowMap* row_map, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- sequence alignment (opt-in) */
+/* Global alignment with affine gaps (Gotoh, three states) of P pairs of sequences, a wave per pair: the correspondence
+ * framedipt/protein/align.py:get_shared_residues_info takes from Bio.Align.PairwiseAligner (mode global, BLOSUM62, open -10, extend
+ * -0.5), as a producer of the row map above.  The contract is DESIGN.md section 7.17.  Letters are aatype in restype order
+ * ARNDCQEGHILKMFPSTWYV, 0 .. 19, and 20 = X.  All arithmetic is int32 in HALF units: table [21,21] holds twice the substitution score,
+ * open_gap and extend_gap twice the penalties (<= 0); a gap of k positions costs open + (k - 1) extend, end gaps as inner gaps.  With i
+ * over a (length la) and j over b (length lb), T the table, o and e the penalties:
+ *   M[i,j] = max(M, X, Y)[i-1,j-1] + T[a_i,b_j]
+ *   X[i,j] = max(M[i-1,j] + o, X[i-1,j] + e, Y[i-1,j] + o)      a_i against a gap
+ *   Y[i,j] = max(M[i,j-1] + o, X[i,j-1] + o, Y[i,j-1] + e)      b_j against a gap
+ * M[0,0] = 0, X[i,0] = o + (i - 1) e, Y[0,j] = o + (j - 1) e, every other state of row 0 and column 0 is unreachable.  score = max(M, X,
+ * Y)[la,lb].  Tie rule: in each maximum the first of M, X, Y wins among equals; the path is the one those choices record, walked back
+ * from [la,lb].  |table entries| and |penalties| are limited to 8192 half units: the int32 sums then cannot wrap.
+ * Counts of the path: n_aligned (M steps), n_identical (M steps with a_i == b_j and neither X), n_gaps_a (Y steps: gap positions in a),
+ * n_gaps_b (X steps), n_gap_runs (maximal runs of X steps and of Y steps; an X run next to a Y run counts twice).
+ * traceback != 0: a direction byte per cell goes to a workspace slab of max_len_a x max_len_b bytes per persistent wave and one lane walks
+ * the path back; alignment is written.  traceback == 0: no slab; the counts ride through the recurrence under the same tie rule, every
+ * output but alignment (not touched, may be NULL) is the same number.  Waves take pairs w, w + W, ...; W follows from workspace_bytes and
+ * no output depends on it. */
+#define FDIPT_SEQ_MAX_ROWS 2048      /* max_len_a or max_len_b beyond: FDIPT_ESIZE                                                   */
+#define FDIPT_SEQ_LETTERS 21
+#define FDIPT_SEQ_MAX_HALF_UNITS 8192 /* |table entry|, |open_gap|, |extend_gap| beyond: FDIPT_EINVAL (penalties), the caller's check (table) */
+#define FDIPT_SEQ_EMPTY 1            /* status: a length of 0; the outputs are zero and the map is -1                               */
+#define FDIPT_SEQ_BAD_LETTER 2       /* status: a letter outside 0 .. 20 inside a length; scored as X                               */
+#define FDIPT_SEQ_SKIPPED 4          /* status: a sequence index of the pair is out of range, or a device length is negative or beyond
+                                        max_len / the padded width; the outputs are zero and the map is -1                          */
+typedef struct FdiptSeqAlignArgs {
+  int32_t S_a, N_a;                  /* sequences and padded width of seq_a                                                         */
+  int32_t S_b, N_b;                  /* of seq_b (where seq_b is NULL: ignored, seq_a and len_a serve both sides)                   */
+  int32_t P;                         /* pairs                                                                                       */
+  int32_t max_len_a, max_len_b;      /* host-known: the largest length on each side; they size the LDS and the slabs                */
+  int32_t open_gap, extend_gap;      /* half units, <= 0                                                                            */
+  int32_t traceback;                 /* 0: score and counts only                                                                    */
+  const int32_t* seq_a;              /* [S_a,N_a] i32: letters; beyond a sequence's length nothing is read                          */
+  const int32_t* len_a;              /* [S_a] i32                                                                                   */
+  const int32_t* seq_b;              /* [S_b,N_b] i32 or NULL                                                                       */
+  const int32_t* len_b;              /* [S_b] i32 (with seq_b)                                                                      */
+  const int32_t* pairs;              /* [P,2] i32: (index into seq_a, index into seq_b or seq_a)                                    */
+  const int32_t* table;              /* [21,21] i32: twice the substitution score, row = letter of a                                */
+  /* outputs: [P] i32 */
+  int32_t* score;                    /* half units                                                                                  */
+  int32_t* n_aligned;
+  int32_t* n_identical;
+  int32_t* n_gaps_a;
+  int32_t* n_gaps_b;
+  int32_t* n_gap_runs;
+  int32_t* alignment;                /* [P,N_b] i32 (traceback): the row of a aligned with each row of b, or -1; monotone            */
+  int32_t* status;                   /* FDIPT_SEQ_* bits                                                                            */
+  void* workspace;                   /* traceback: the slabs; else may be NULL                                                      */
+  size_t workspace_bytes;
+} FdiptSeqAlignArgs;
+/* traceback: W slabs of max_len_a x max_len_b bytes, W = the launch's persistent waves (at most P), lowered until the slabs fit
+ * max_workspace_bytes, and at least one; else 0 */
+size_t fdipt_seq_align_workspace_bytes(int P, int max_len_a, int max_len_b, int traceback, size_t max_workspace_bytes);
+/* One launch.  FDIPT_EINVAL: a null pointer the mode reads or writes, S_a, N_a or P < 1 (S_b, N_b with seq_b), a max_len < 0 or beyond
+ * its padded width, a penalty > 0 or < -FDIPT_SEQ_MAX_HALF_UNITS.  FDIPT_ESIZE: a max_len > FDIPT_SEQ_MAX_ROWS, traceback with a
+ * workspace below one slab. */
+int fdipt_seq_align(const FdiptSeqAlignArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- inverse folding (opt-in) */
 /* The vanilla full-backbone ProteinMPNN (ProteinMPNN/protein_mpnn_utils.py: ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward
  * and .sample), inference only, float32 throughout; the contract is DESIGN.md section 7.10.  Letters are in the MODEL's alphabet
