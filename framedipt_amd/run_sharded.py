@@ -359,6 +359,55 @@ def run_lddt(out_dir: str, records, gathered: dict, inpainting: bool = False, se
     return summary
 
 
+def run_interface(out_dir: str, records, gathered: dict, inpainting: bool = False, selected=None, atoms: str = "cb"):
+    """Rank 0, after the gather (``--interface``; framedipt_amd/interface.py).  Inpainting runs: per structure name every sample - and,
+    with ``selected`` (what ``run_selection`` kept), the five selected structures - against the ground truth (``gt`` of a gathered entry)
+    on ``loop_sides``: per chain with diffused rows one interface, the ligand that chain's diffused rows, the receptor every row of the
+    other chains - does the redesigned loop touch its partners where the native loop does.  Writes ``interface.json`` (per sample and
+    chain the flat metrics of ``interface_metrics`` and the per-row contact counts of the ligand rows) and ``interface.csv`` (one row per
+    sample and chain); a structure without ground truth, without a second chain or without diffused rows is listed as skipped.  De novo
+    runs have no reference complex: the flag is refused.  Returns the summary written."""
+    import csv
+
+    from . import interface, selection
+    if not inpainting:
+        raise SystemExit("--interface scores the samples of an inpainting run against their ground-truth complex; a de novo run has none")
+    columns = ["n_native", "n_model", "n_shared", "n_interface_rows", "fnat", "fnonnat", "irmsd", "lrmsd", "dockq", "capri_class", "status"]
+    summary = {"atoms": atoms, "contact_cutoff": interface.CONTACT_CUTOFF[atoms], "interface_cutoff": 10.0, "sides": "ligand: the diffused rows of a chain; receptor: the other chains",
+               "contract": "DESIGN.md section 7.18 (no parity with the DockQ program is claimed)", "samples": [], "skipped": []}
+    table = []
+    for g, (name, rs) in enumerate(group_records_by_name(records).items()):
+        items = [gathered[r["item"]] for r in rs]
+        truth = next((it["gt"] for it in items if "gt" in it), None)
+        n = items[0]["prot"].shape[0]
+        chain = np.zeros(n) if items[0].get("chain_idx") is None else np.rint(np.asarray(items[0]["chain_idx"]))
+        sides, chains = interface.loop_sides(np.asarray(items[0]["diffused"]) != 0, chain)
+        if truth is None or len(sides) == 0 or not (sides == interface.RECEPTOR).any():
+            summary["skipped"].append(str(name))
+            continue
+        labels, structures, sources = [str(r["sample_i"]) for r in rs], [it["prot"] for it in items], list(items)
+        if selected is not None:
+            labels += list(selection.STRATEGIES)
+            structures += [selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n] for strategy in selection.STRATEGIES]
+            sources += [items[0]] * len(selection.STRATEGIES)
+        res_mask = np.stack([np.ones(n, dtype=np.float32) if it.get("res_mask") is None else it["res_mask"] for it in sources]).astype(np.float32)
+        res = interface.interface_accuracy(np.stack(structures).astype(np.float32), np.asarray(truth, dtype=np.float32)[None], sides, atoms=atoms, res_mask=res_mask)
+        for s, label in enumerate(labels):
+            for k, c in enumerate(chains):
+                rows = np.flatnonzero(sides[k] == interface.LIGAND)
+                values = interface.interface_metrics(res, s, k)
+                summary["samples"].append({"pdb_name": str(name), "sample": label, "chain": int(c), **values, "ligand_rows": rows.tolist(),
+                                           **{key: res[key][s, k][rows].tolist() for key in ("res_native", "res_model", "res_shared")}})
+                table.append({"pdb_name": str(name), "sample": label, "chain": int(c), **{key: "" if values[key] is None else repr(values[key]) for key in columns}})
+    with open(os.path.join(out_dir, "interface.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    with open(os.path.join(out_dir, "interface.csv"), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "chain"] + columns)
+        w.writeheader()
+        w.writerows(table)
+    return summary
+
+
 def write_gdt(out_dir: str, structures: dict, skipped=()):
     """``structures``: name -> {"samples": [labels], "n_scored": [S], "fixed" and "search": {"gdt_ts": [S], "gdt_ha": [S]} (no
     superposition: the frame of the fixed context; the searched superposition per cutoff), "counts_fixed" and "counts": [S,5], "status":
@@ -984,6 +1033,12 @@ def main():
                     "truth on the CA and the backbone atoms, scored over the diffused rows with the context as environment: lddt.json and lddt.csv.  "
                     "De novo runs: all-against-all CA lDDT per sample length: pairwise_lddt_ca_length_<L>.npy and consistency.json (per sample the mean "
                     "lDDT against the others and the per-residue consensus)")
+    ap.add_argument("--interface", action="store_true", help="after the run, rank 0 computes the interface accuracy on its GPU (framedipt_amd/interface.py: contacts, "
+                    "fnat, fnonnat, iRMSD, LRMSD, DockQ; DESIGN.md section 7.18, no parity with the DockQ program is claimed).  Inpainting runs: every sample - and "
+                    "with --select the five selected structures - against the ground truth, the ligand the diffused rows of a chain, the receptor the other "
+                    "chains: interface.json and interface.csv.  De novo runs have no reference complex: the flag is refused")
+    ap.add_argument("--interface-atoms", default="cb", choices=["ca", "cb", "backbone", "all"], help="the atom set of --interface (default cb: CB within 8 A, CA where "
+                    "a row has no CB; backbone and all: 5 A)")
     ap.add_argument("--gdt", action="store_true", help="after the run, rank 0 computes GDT-TS and GDT-HA on its GPU (framedipt_amd/gdt.py).  Inpainting runs: every "
                     "sample (and with --select the five selected structures) against the ground truth over the diffused rows that exist, without a "
                     "superposition (the frame of the fixed context) and with the searched one: gdt.json and gdt.csv.  De novo runs: all-against-all searched "
@@ -1019,6 +1074,8 @@ def main():
             ap.error(f"--keep {a.keep}: expected all, last or an integer stride")
     if a.novelty and a.download_dir is not None:
         ap.error("--novelty is for de novo runs: a redesigned region inside a fixed context is not novel by construction")
+    if a.interface and a.download_dir is None:
+        ap.error("--interface scores the samples of an inpainting run against their ground-truth complex: a de novo run has none (give --download-dir)")
     if a.novelty_accuracy and not a.novelty:
         ap.error("--novelty-accuracy needs --novelty SET.npz")
     if a.seq_diversity and (not a.design or a.download_dir is not None):
@@ -1111,9 +1168,9 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt or a.novelty else None
+    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt or a.interface or a.novelty else None
     ground_truth = None
-    if (a.evaluate or a.sasa or a.tm_score or a.lddt or a.gdt) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
+    if (a.evaluate or a.sasa or a.tm_score or a.lddt or a.gdt or a.interface) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
             build = lambda: inference.get_atom_positions_from_rigids(net, feats["rigids_0"], feats["torsion_angles_sin_cos"][..., 2, :], feats["aatype"])[0]  # noqa: E731
             return one_gpu_turn(build) if one_gpu and world > 1 else build()
@@ -1124,7 +1181,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt or a.novelty:  # (every rank takes part in the gather; rank 0 receives)
+    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt or a.interface or a.novelty:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -1133,7 +1190,7 @@ def main():
                                                                 **({} if a.keep == "all" else {"keep": a.keep})})
         print(f"{sum(r['n_res'] for r in allrecs) * a.num_t / el:.0f} residue*steps/s (incl. model set-up and file output)")
         print(f"{len(ds)} samples on {world} GPU(s) in {el:.1f} s -> {a.out_dir}/manifest.json", flush=True)
-        selected = {} if a.select and (a.evaluate or a.lddt or a.gdt) else None
+        selected = {} if a.select and (a.evaluate or a.lddt or a.gdt or a.interface) else None
         if a.select:
             t1 = time.perf_counter()
             done = run_selection(a.out_dir, allrecs, gathered, reference_layout=inp, sigma=a.select_sigma, max_iterations=a.select_iterations, keep=selected)
@@ -1182,6 +1239,11 @@ def main():
             what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/gdt.json, gdt.csv" if inp else \
                 f"{len(done['lengths'])} length(s) -> {a.out_dir}/pairwise_gdt_ts_length_<L>.npy"
             print(f"GDT-TS and GDT-HA of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
+        if a.interface:
+            t1 = time.perf_counter()
+            done = run_interface(a.out_dir, allrecs, gathered, inpainting=inp, selected=selected, atoms=a.interface_atoms)
+            print(f"interface accuracy of {len(done['samples'])} (structure, chain) entr(ies) in {time.perf_counter() - t1:.2f} s -> "
+                  f"{a.out_dir}/interface.json, interface.csv", flush=True)
         if a.novelty:
             t1 = time.perf_counter()
             done = run_novelty(a.out_dir, allrecs, gathered, a.novelty, top_k=a.novelty_top_k, inpainting=inp, inits=a.tm_inits, accuracy=a.novelty_accuracy)

@@ -1008,6 +1008,90 @@ size_t fdipt_seq_align_workspace_bytes(int P, int max_len_a, int max_len_b, int 
  * workspace below one slab. */
 int fdipt_seq_align(const FdiptSeqAlignArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- interface accuracy (opt-in) */
+/* Contacts across an interface, fnat, fnonnat, interface RMSD, ligand RMSD and DockQ (Basu & Wallner 2016: the formula, not the
+ * program) of P pairs (model structure a, reference structure b) in row correspondence, each on the I interfaces of the call; float32
+ * coordinates widened, all arithmetic float64 with contraction off, three launches on one stream.  The contract is DESIGN.md section
+ * 7.18.
+ * A row takes part where res_mask of the model AND of the reference is set.  sides[k,i] says what row i is in interface k: 0 neither,
+ * FDIPT_IFACE_RECEPTOR, FDIPT_IFACE_LIGAND (anything else counts as 0).  An atom takes part where it exists in BOTH structures:
+ * atom_mask != 0, or without a mask any non-zero coordinate.
+ * Atom set (mode): CA = column 1 (column 0 of a CA trace, atoms = 1); CB = column 3 where it takes part, else column 1; BACKBONE = N,
+ * CA, C, CB, O = columns 0 .. 4 of atom37 and of the five-atom layout; ALL = the 37 columns of atom37.
+ * Residue pair (i receptor, j ligand) is a contact of a structure where some pair of atoms that take part has (dx dx + dy dy) + dz dz
+ * <= contact_cutoff^2 in it; n_native counts the reference's contacts, n_model the model's, n_shared those of both.  A row of either
+ * side is an interface row where, in the reference, some such atom pair across the sides is within interface_cutoff.  fnat = n_shared
+ * / n_native (0 for n_native = 0), fnonnat = (n_model - n_shared) / n_model (0 for n_model = 0).
+ * RMSD atoms: N, CA, C, O = columns 0, 1, 2, 4 where both layouts have them and mode is not CA, else CA alone; an atom is used where
+ * it exists in both structures.  irmsd: the RMSD atoms of the interface rows after their own least-squares superposition (Horn, proper
+ * rotation).  lrmsd: the RMSD atoms of the ligand rows under the superposition of the RMSD atoms of the receptor rows.  Both transforms
+ * are R x + t ~ y, x the model.  dockq = (fnat + 1 / (1 + (irmsd / 1.5)^2) + 1 / (1 + (lrmsd / 8.5)^2)) / 3.
+ * The integers are exact and order-free (integer atomics); every floating-point sum runs in a fixed order that depends on the pair's
+ * own rows only.  Pruning (default) skips a residue pair of a structure only where |CA_i - CA_j| - reach_i - reach_j exceeds the
+ * cutoff that structure is tested against by a relative 1e-6, reach the largest distance from the row's CA to one of its atoms that
+ * take part: no output bit depends on it. */
+#define FDIPT_IFACE_CA 0
+#define FDIPT_IFACE_CB 1
+#define FDIPT_IFACE_BACKBONE 2
+#define FDIPT_IFACE_ALL 3
+#define FDIPT_IFACE_RECEPTOR 1       /* values of sides                                                                             */
+#define FDIPT_IFACE_LIGAND 2
+#define FDIPT_IFACE_MAX_ROWS 2048    /* N beyond: FDIPT_ESIZE                                                                       */
+#define FDIPT_IFACE_MAX_INTERFACES 64 /* I beyond: FDIPT_ESIZE                                                                      */
+#define FDIPT_IFACE_ROWS 64          /* receptor rows a block of the contact pass serves                                            */
+#define FDIPT_IFACE_TILE 256         /* ligand rows per LDS tile of the CA, CB and BACKBONE sets                                    */
+#define FDIPT_IFACE_TILE_ALL 64      /* ... of the ALL set                                                                          */
+#define FDIPT_IFACE_NO_PRUNE 1       /* flags: every residue pair across the sides is evaluated                                     */
+#define FDIPT_IFACE_NO_NATIVE_CONTACT 1 /* status: n_native = 0: fnat is 0, irmsd and dockq NaN                                     */
+#define FDIPT_IFACE_TOO_FEW_ATOMS 2  /* status: a superposition has fewer than 3 atoms: its RMSD and dockq are NaN, its transform 0 */
+#define FDIPT_IFACE_DEGENERATE 4     /* status: the eigenvalue gap of a superposition is within rounding (1e-9 of the matrix)       */
+#define FDIPT_IFACE_EMPTY_SIDE 8     /* status: no row takes part on one of the sides                                               */
+#define FDIPT_IFACE_NOT_FINITE 16    /* status: a sum over RMSD atoms is not finite: that RMSD and dockq are NaN                    */
+#define FDIPT_IFACE_SKIPPED 32       /* status: a structure index of the pair is out of range: integers and fractions 0, RMSDs and  */
+                                     /* dockq NaN, transforms 0                                                                     */
+typedef struct FdiptInterfaceArgs {
+  int32_t S, N, atoms;               /* model structures, rows, atoms per row of prot: 37, 5 or 1 (a CA trace)                      */
+  int32_t S_b, atoms_b;              /* of prot_b (ignored where prot_b is NULL)                                                    */
+  int32_t P, I, mode, flags;         /* pairs, interfaces, FDIPT_IFACE_CA / CB / BACKBONE / ALL, FDIPT_IFACE_NO_PRUNE or 0          */
+  double contact_cutoff;             /* > 0                                                                                         */
+  double interface_cutoff;           /* > 0                                                                                         */
+  const float* prot;                 /* [S,N,atoms,3] f32                                                                           */
+  const float* prot_b;               /* [S_b,N,atoms_b,3] f32 or NULL: the reference of a pair comes from here, else from prot      */
+  const float* res_mask;             /* [S,N] f32                                                                                   */
+  const float* res_mask_b;           /* [S_b,N] f32 (with prot_b; without it res_mask serves both)                                  */
+  const uint8_t* atom_mask_a;        /* [S,N,atoms] u8 or NULL                                                                      */
+  const uint8_t* atom_mask_b;        /* [S_b,N,atoms_b] u8 ([S,N,atoms] without prot_b) or NULL                                     */
+  const int32_t* pairs;              /* [P,2] i32: (model: index into prot, reference: index into prot_b or prot)                   */
+  const int32_t* sides;              /* [I,N] i32                                                                                   */
+  /* outputs */
+  int32_t* n_native;                 /* [P,I] i32                                                                                   */
+  int32_t* n_model;                  /* [P,I] i32                                                                                   */
+  int32_t* n_shared;                 /* [P,I] i32                                                                                   */
+  int32_t* n_interface_rows;         /* [P,I] i32                                                                                   */
+  int32_t* res_native;               /* [P,I,N] i32: the reference's contacts the row is part of                                    */
+  int32_t* res_model;                /* [P,I,N] i32                                                                                 */
+  int32_t* res_shared;               /* [P,I,N] i32                                                                                 */
+  int32_t* interface_rows;           /* [P,I,N] i32: 1 = an interface row                                                           */
+  double* fnat;                      /* [P,I] f64                                                                                   */
+  double* fnonnat;                   /* [P,I] f64                                                                                   */
+  double* irmsd;                     /* [P,I] f64                                                                                   */
+  double* lrmsd;                     /* [P,I] f64                                                                                   */
+  double* dockq;                     /* [P,I] f64                                                                                   */
+  double* interface_rotation;        /* [P,I,3,3] f64: the superposition of irmsd                                                   */
+  double* interface_translation;     /* [P,I,3] f64                                                                                 */
+  double* receptor_rotation;         /* [P,I,3,3] f64: the superposition of lrmsd                                                   */
+  double* receptor_translation;      /* [P,I,3] f64                                                                                 */
+  int32_t* status;                   /* [P,I] i32: FDIPT_IFACE_* bits                                                               */
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptInterfaceArgs;
+/* per pair and row: the atoms that take part, and the row's reach in both structures */
+size_t fdipt_sample_interface_workspace(int P, int N);
+/* FDIPT_EINVAL: a null pointer, S, N, P or I < 1, a layout or mode outside the above, ALL without atom37 in both structures, CB or
+ * BACKBONE with a CA trace, a cutoff that is not positive, unknown flags.  FDIPT_ESIZE: N > FDIPT_IFACE_MAX_ROWS, I >
+ * FDIPT_IFACE_MAX_INTERFACES, workspace too small, more blocks than a grid holds.  All before any launch. */
+int fdipt_sample_interface(const FdiptInterfaceArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- inverse folding (opt-in) */
 /* The vanilla full-backbone ProteinMPNN (ProteinMPNN/protein_mpnn_utils.py: ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward
  * and .sample), inference only, float32 throughout; the contract is DESIGN.md section 7.10.  Letters are in the MODEL's alphabet
