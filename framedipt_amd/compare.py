@@ -10,7 +10,9 @@ reference's ``framedipt/protein/align.py`` does before it superposes; DESIGN.md 
 """
 from __future__ import annotations
 
-from . import gdt, lddt, seq_align, tm_align
+import numpy as np
+
+from . import gdt, interface, lddt, seq_align, tm_align
 
 _LDDT_KEYS = ("lddt", "res_lddt", "n_scored", "n_passed", "drmsd", "fape", "res_fape", "region_fape", "n_covered", "n_reference", "coverage")
 _GDT_KEYS = ("gdt_ts", "gdt_ha", "counts", "res_within", "rotation", "translation")
@@ -67,6 +69,38 @@ def sequence_aligned_accuracy(prot_a, aatype_a, prot_b, aatype_b, chain_a=None, 
     out.update({k: glob[k] for k in _GDT_KEYS})
     out.update(seq_status=found["status"], lddt_status=local["status"], gdt_status=glob["status"], pairs=local["pairs"], atoms=atoms, coverage_mode=coverage,
                superpose=superpose)
+    return out
+
+
+def sequence_aligned_interface(prot_a, aatype_a, prot_b, aatype_b, chain_a, chain_b, chain_pairs=None, interfaces=None, atoms: str = "cb",
+                               coverage: str = "penalise", mask_a=None, mask_b=None, atom_mask_a=None, atom_mask_b=None, pairs=None, ref_index=None,
+                               contact_cutoff=None, interface_cutoff: float = 10.0, prune: bool = True, **scoring) -> dict:
+    """The docking question for a model from another tool, or a ground truth read from its own file: prot_a [S,N_a,...] are the models
+    with residue types aatype_a [N_a] and chain labels chain_a [N_a]; prot_b [S_b,N_b,...] the references with aatype_b, chain_b [N_b].
+    The rows are matched by ``seq_align.chain_row_map`` (chains with equal labels, or ``chain_pairs`` [(label_a, label_b)]; ``scoring``:
+    its ``matrix``, ``open_gap``, ``extend_gap``) - the model may store its chains in another order, the map is then not monotone -, the
+    interfaces are ``interface.chain_sides(chain_b, interfaces)`` (``interfaces``: pairs of the REFERENCE's chain labels; default: every
+    pair), and ``interface.interface_accuracy(..., alignment=, coverage=)`` scores every pair of structures in one call.  The sibling of
+    ``sequence_aligned_accuracy``; no parity with the DockQ program is claimed.
+
+    Returns ``alignment`` [N_b], ``chains`` and per chain pair ``score``, ``identity``, ``identity_b``, ``n_identical``, ``n_aligned``,
+    ``seq_status``; every output of ``interface_accuracy`` with an alignment (``dockq``, ``fnat`` [P,I], ``n_covered``,
+    ``n_interface_covered``, ...); ``sides`` [I,N_b], ``labels`` [I,2] (receptor, ligand: the reference's chain labels) and
+    ``global_dockq`` [P] (``interface.global_dockq``: this project's own summary)."""
+    if prot_b is None:
+        raise ValueError("sequence_aligned_interface scores models against references: prot_b is required")
+    n_a, n_b = int(prot_a.shape[1]), int(prot_b.shape[1])
+    for what, x, n in (("aatype_a", aatype_a, n_a), ("aatype_b", aatype_b, n_b), ("chain_a", chain_a, n_a), ("chain_b", chain_b, n_b)):
+        if x is None or len(x) != n:
+            raise ValueError(f"{what} should hold one entry for each of the {n} rows" + ("" if x is None else f", got {len(x)}"))
+    sides, labels = interface.chain_sides(chain_b, interfaces)
+    found = seq_align.chain_row_map(aatype_a, chain_a, aatype_b, chain_b, chain_pairs=chain_pairs, **scoring)
+    out = interface.interface_accuracy(prot_a, prot_b, sides, atoms=atoms, res_mask=mask_a, res_mask_b=mask_b, atom_mask_a=atom_mask_a, atom_mask_b=atom_mask_b,
+                                       pairs=pairs, ref_index=ref_index, contact_cutoff=contact_cutoff, interface_cutoff=interface_cutoff, prune=prune,
+                                       alignment=found["alignment"], coverage=coverage)
+    out.update({k: found[k] for k in ("alignment", "chains", "score", "identity", "identity_b", "n_identical", "n_aligned")})
+    out.update(seq_status=found["status"], sides=sides, labels=labels)
+    out["global_dockq"] = np.array([interface.global_dockq(out, p) for p in range(len(out["pairs"]))], dtype=np.float64)
     return out
 
 

@@ -11,6 +11,10 @@ up to ``MAX_INTERFACES`` interfaces, all in float64; DESIGN.md section 7.18 is t
 pinned by its NumPy restatement (tests/interface_ref.py): no parity with the DockQ program is claimed.  An interface is a row of
 ``sides`` (0 neither, 1 receptor, 2 ligand): ``chain_sides`` builds one per chain pair, ``loop_sides`` one per chain with diffused rows -
 the inpainting question.
+
+With ``alignment=`` the rows of the reference need not be those of the model: ``fdipt_sample_interface_mapped``
+(csrc/interface_mapped.hip) reads the model through a row map, and ``coverage="penalise"`` charges the model
+for the reference rows it lacks.  ``compare.sequence_aligned_interface`` takes the map from the sequences.
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ PER_INTERFACE_INTS = ("n_native", "n_model", "n_shared", "n_interface_rows", "st
 PER_INTERFACE = ("fnat", "fnonnat", "irmsd", "lrmsd", "dockq")
 PER_ROW = ("res_native", "res_model", "res_shared", "interface_rows")
 TRANSFORMS = {"interface_rotation": (3, 3), "interface_translation": (3,), "receptor_rotation": (3, 3), "receptor_translation": (3,)}
+COVERAGE = {"ignore": _lib.MAP_IGNORE, "penalise": _lib.MAP_PENALISE}
 CAPRI_BOUNDS = (0.23, 0.49, 0.80)  # DockQ at which the class becomes acceptable, medium, high
 
 
@@ -86,7 +91,8 @@ def loop_sides(diffuse_mask, chain_idx, partner: str = "other_chains"):
 
 
 def interface_accuracy(prot_a, prot_b=None, sides=None, atoms: str = "cb", res_mask=None, res_mask_b=None, atom_mask_a=None, atom_mask_b=None,
-                       pairs=None, ref_index=None, contact_cutoff=None, interface_cutoff: float = 10.0, prune: bool = True) -> dict:
+                       pairs=None, ref_index=None, contact_cutoff=None, interface_cutoff: float = 10.0, prune: bool = True, alignment=None,
+                       coverage: str = "ignore") -> dict:
     """prot_a [S,N,37,3], [S,N,5,3] or a CA trace [S,N,3] float32, a device tensor (used in place) or a NumPy array (uploaded): the
     models; prot_b [S_b,N,...] likewise or None: the references.  ``sides`` int [I,N] (or [N]): 0 neither, 1 receptor, 2 ligand, one row
     per interface, shared by every pair.  ``atoms``: "ca", "cb" (CB where both structures have it, else CA), "backbone" (N, CA, C, CB, O)
@@ -105,11 +111,29 @@ def interface_accuracy(prot_a, prot_b=None, sides=None, atoms: str = "cb", res_m
     ``fnat``, ``fnonnat``, ``irmsd``, ``lrmsd``, ``dockq`` [P,I] float64 (NaN with a status bit), ``res_native``, ``res_model``,
     ``res_shared`` [P,I,N] int64, ``interface_rows`` [P,I,N] bool, ``interface_rotation`` [P,I,3,3] and ``interface_translation`` [P,I,3]
     (R x + t ~ y, x the model: the superposition of irmsd), ``receptor_rotation`` and ``receptor_translation`` (of lrmsd), ``pairs``
-    [P,2], ``atoms`` and the two cutoffs."""
+    [P,2], ``atoms`` and the two cutoffs.
+
+    ``alignment`` (int [N_b], or [P,N_b] per pair; NumPy or a device tensor): the rows of prot_b [S_b,N_b,...] need not be those of prot_a
+    [S,N_a,...] - entry j is the row of the model that corresponds to row j of the reference, or -1 (``seq_align.chain_row_map``,
+    ``row_map``, ``tm_align(...)["alignment"]``); the map need not be monotone (the model may store its chains in another order).  One
+    call of ``fdipt_sample_interface_mapped``, DESIGN.md section 7.19.  The reference owns the rows: ``sides`` is [I,N_b], res_mask_b
+    [S_b,N_b], every per-row output [P,I,N_b]; res_mask and atom_mask_a stay in the model's rows.  ``coverage``: "ignore" - a row takes part
+    where it has a partner in the model, and the result is bit for bit that of the call without ``alignment`` on the gathered model;
+    "penalise" - the native contacts and the interface rows are the reference's own, a model contact needs both rows in the model, so a
+    missing residue costs fnat every native contact it is part of, and irmsd / lrmsd run over the rows the model has.  The result gains
+    ``n_covered``, ``n_reference`` [P] int64, ``coverage`` [P] (their ratio, 0 for no reference row), ``n_interface_covered`` [P,I] (the
+    interface rows that entered irmsd) and ``coverage_mode``.  A NumPy map that is out of range or uses a model row twice raises
+    (``row_map.validate``); a device map sets ``_lib.IFACE_MAP_OUT_OF_RANGE`` / ``_lib.IFACE_MAP_DUPLICATE`` in ``status`` on every
+    interface of its pair, whose outputs are those of a skipped pair."""
     if atoms not in MODES:
         raise ValueError(f"atoms should be 'ca', 'cb', 'backbone' or 'all', got {atoms!r}")
     if sides is None:
         raise ValueError("sides is required: chain_sides(chain_idx) or loop_sides(diffuse_mask, chain_idx) build it")
+    if alignment is not None:
+        return _mapped_interface(prot_a, prot_b, sides, atoms, res_mask, res_mask_b, atom_mask_a, atom_mask_b, pairs, ref_index, contact_cutoff,
+                                 interface_cutoff, prune, alignment, coverage)
+    if coverage != "ignore":
+        raise ValueError(f"coverage={coverage!r} belongs to a call with an alignment")
     s_a, n, atoms_a = _shape(prot_a, "prot_a")
     s_b, n_b, atoms_b = (s_a, n, atoms_a) if prot_b is None else _shape(prot_b, "prot_b")
     if n_b != n:
@@ -171,6 +195,80 @@ def interface_accuracy(prot_a, prot_b=None, sides=None, atoms: str = "cb", res_m
             out[name] = np.tile(np.eye(s_a), (n_if, 1, 1))
             out[name][:, pair_list[:, 0], pair_list[:, 1]] = out[key].T
     return out
+
+
+def _mapped_interface(prot_a, prot_b, sides, atoms, res_mask, res_mask_b, atom_mask_a, atom_mask_b, pairs, ref_index, contact_cutoff, interface_cutoff, prune,
+                      alignment, coverage) -> dict:
+    """``interface_accuracy`` with an alignment: one call of ``fdipt_sample_interface_mapped``."""
+    if coverage not in COVERAGE:
+        raise ValueError(f"coverage should be 'ignore' or 'penalise', got {coverage!r}")
+    if prot_b is None:
+        raise ValueError("alignment maps the rows of prot_b to those of prot_a: prot_b is required")
+    s_a, n_a, atoms_a = _shape(prot_a, "prot_a")
+    s_b, n_b, atoms_b = _shape(prot_b, "prot_b")
+    for what, layout in (("prot_a", atoms_a), ("prot_b", atoms_b)):
+        if (atoms == "all" and layout != 37) or (atoms in ("cb", "backbone") and layout == 1):
+            raise ValueError(f"atoms={atoms!r} needs {'atom37' if atoms == 'all' else 'the backbone atoms'}: {what} holds {layout} atom(s) per row")
+    contact_cutoff = CONTACT_CUTOFF[atoms] if contact_cutoff is None else float(contact_cutoff)
+    if not contact_cutoff > 0 or not interface_cutoff > 0:
+        raise ValueError(f"the cutoffs should be positive, got contact_cutoff={contact_cutoff}, interface_cutoff={interface_cutoff}")
+    sides_host = sides if hasattr(sides, "detach") else np.asarray(sides)
+    sides_shape = tuple(sides_host.shape)
+    if len(sides_shape) == 1:
+        sides_shape = (1,) + sides_shape
+    if len(sides_shape) != 2 or sides_shape[1] != n_b or sides_shape[0] < 1:
+        raise ValueError(f"sides should be [I, {n_b}] (or [{n_b}]) with I >= 1 - with an alignment the rows of prot_b, the reference -, got "
+                         f"{tuple(sides_host.shape)}")
+    n_if = sides_shape[0]
+    pair_list, _ = _call.plan_pairs(s_a, s_b, True, pairs, ref_index)
+    n_pairs = len(pair_list)
+    checks = (("res_mask", res_mask, (s_a, n_a)), ("res_mask_b", res_mask_b, (s_b, n_b)), ("atom_mask_a", atom_mask_a, (s_a, n_a) + (() if atoms_a == 1 else (atoms_a,))),
+              ("atom_mask_b", atom_mask_b, (s_b, n_b) + (() if atoms_b == 1 else (atoms_b,))))
+    for what, x, shape in checks:
+        if x is not None and tuple(x.shape if hasattr(x, "shape") else np.shape(x)) != shape:
+            raise ValueError(f"{what} {tuple(x.shape if hasattr(x, 'shape') else np.shape(x))} does not match its structure: expected {shape}")
+    alignment = _call.check_map(alignment, n_pairs, n_b, n_a)
+    ints = PER_INTERFACE_INTS + PER_ROW[:3] + ("n_interface_covered",)
+    outputs = {key: ("int32", (n_pairs, n_if)) for key in PER_INTERFACE_INTS + ("n_interface_covered",)}
+    outputs.update({key: ("float64", (n_pairs, n_if)) for key in PER_INTERFACE})
+    outputs.update({key: ("int32", (n_pairs, n_if, n_b)) for key in PER_ROW})
+    outputs.update({key: ("float64", (n_pairs, n_if) + shape) for key, shape in TRANSFORMS.items()})
+    if n_pairs == 0:
+        out = _call.empty_outputs(outputs, ints)
+        out.update(n_covered=np.zeros(0, dtype=np.int64), n_reference=np.zeros(0, dtype=np.int64))
+    else:
+        import torch
+        dev, (xa, xb) = _call.upload("interface_accuracy", prot_a=prot_a, prot_b=prot_b)
+
+        def atom_mask(x, shape, what):
+            m = _call.per_row(x, shape, what, "mask", dev=dev)
+            return None if m is None else m.to(torch.uint8).contiguous()
+
+        mask_b = _call.per_row(res_mask_b, (s_b, n_b), "res_mask_b", "mask", default=1, dev=dev)
+        out = _call.run_mapped("fdipt_sample_interface_mapped", _lib.InterfaceArgs, dev,
+                               dict(S=s_a, N=n_b, atoms=atoms_a, S_b=s_b, atoms_b=atoms_b, P=n_pairs, I=n_if, mode=MODES[atoms],
+                                    flags=0 if prune else _lib.IFACE_NO_PRUNE, contact_cutoff=contact_cutoff, interface_cutoff=float(interface_cutoff)),
+                               dict(prot=xa, prot_b=xb, res_mask=_call.per_row(res_mask, (s_a, n_a), "res_mask", "mask", default=1, dev=dev), res_mask_b=mask_b,
+                                    atom_mask_a=atom_mask(atom_mask_a, checks[2][2], "atom_mask_a"), atom_mask_b=atom_mask(atom_mask_b, checks[3][2], "atom_mask_b"),
+                                    pairs=torch.from_numpy(pair_list).to(dev), sides=_call.per_row(sides_host.reshape(n_if, n_b), (n_if, n_b), "sides", "int", dev=dev)),
+                               outputs,
+                               dict(N_a=n_a, coverage=COVERAGE[coverage], map=_call.upload_map(alignment, n_pairs, n_b, dev), res_mask_b=mask_b, score_mask_b=None),
+                               widen=ints, workspace=("fdipt_sample_interface_mapped_workspace", n_pairs, n_b))
+    out["interface_rows"] = out["interface_rows"] != 0
+    out["coverage"] = np.divide(out["n_covered"], out["n_reference"], out=np.zeros(n_pairs), where=out["n_reference"] > 0)
+    out.update(pairs=pair_list.astype(np.int64), atoms=atoms, contact_cutoff=contact_cutoff, interface_cutoff=float(interface_cutoff), coverage_mode=coverage)
+    return out
+
+
+def global_dockq(result: dict, p: int) -> float:
+    """This project's own one-number summary of pair ``p`` (NOT the DockQ program's global score): the mean of ``dockq[p]`` over the
+    interfaces that have a native contact (``n_native > 0``).  Under ``coverage="penalise"`` (``result["coverage_mode"]``) an interface
+    whose DockQ is NaN - the model lacks the rows of a superposition - counts as 0; otherwise (``"ignore"``, or a call without an
+    alignment) it is left out.  NaN where no interface has a native contact, or none is left."""
+    dockq = np.asarray(result["dockq"], dtype=np.float64)[p].reshape(-1)
+    dockq = dockq[np.asarray(result["n_native"])[p].reshape(-1) > 0]
+    dockq = np.nan_to_num(dockq, nan=0.0) if result.get("coverage_mode", "ignore") == "penalise" else dockq[~np.isnan(dockq)]
+    return float(dockq.mean()) if dockq.size else float("nan")
 
 
 def interface_metrics(result: dict, p: int, k: int) -> dict:

@@ -933,7 +933,7 @@ int fdipt_sample_gdt(const FdiptGdtArgs* args, fdipt_stream_t stream);
 #define FDIPT_MAP_OUT_OF_RANGE 8     /* status: an entry of the pair's map is < -1 or >= N_a                                        */
 #define FDIPT_MAP_DUPLICATE 16       /* status: two reference rows of the pair map to the same model row                            */
 typedef struct FdiptRowMap {
-  int32_t N_a, coverage;             /* rows of prot; FDIPT_MAP_IGNORE / FDIPT_MAP_PENALISE (lDDT only)                             */
+  int32_t N_a, coverage;             /* rows of prot; FDIPT_MAP_IGNORE / FDIPT_MAP_PENALISE (lDDT, interface)                       */
   const int32_t* map;                /* [P,args->N] i32                                                                             */
   const float* res_mask_b;           /* [S_b,args->N] f32: the reference's existing rows (lDDT; GDT reads args->mask_b)             */
   const float* score_mask_b;         /* [S_b,args->N] f32: the score rows, in reference rows (lDDT)                                 */
@@ -1084,6 +1084,7 @@ typedef struct FdiptInterfaceArgs {
   int32_t* status;                   /* [P,I] i32: FDIPT_IFACE_* bits                                                               */
   void* workspace;
   size_t workspace_bytes;
+  int32_t* n_interface_covered;      /* [P,I] i32: fdipt_sample_interface_mapped only (below); fdipt_sample_interface does not read it */
 } FdiptInterfaceArgs;
 /* per pair and row: the atoms that take part, and the row's reach in both structures */
 size_t fdipt_sample_interface_workspace(int P, int N);
@@ -1091,6 +1092,43 @@ size_t fdipt_sample_interface_workspace(int P, int N);
  * BACKBONE with a CA trace, a cutoff that is not positive, unknown flags.  FDIPT_ESIZE: N > FDIPT_IFACE_MAX_ROWS, I >
  * FDIPT_IFACE_MAX_INTERFACES, workspace too small, more blocks than a grid holds.  All before any launch. */
 int fdipt_sample_interface(const FdiptInterfaceArgs* args, fdipt_stream_t stream);
+
+/* ---------------------------------------------------------------- interface accuracy through a row map (opt-in) */
+/* The entry above for a model whose rows do NOT correspond to the reference's: pair p is (model ia of prot [S,N_a,atoms,3], reference ib
+ * of prot_b [S_b,N_b,atoms_b,3]) with the row map m = row_map->map[p,:] of "accuracy through a row map" above (m[j]: the model row of
+ * reference row j, or -1; it need not be monotone - the model may store its chains in another order - and must be injective on its
+ * entries >= 0).  The contract is DESIGN.md section 7.19.  As with the DockQ program's alignment step, no parity with that program is
+ * claimed: the contract is this project's own.
+ * args->N is N_b; args->prot_b is required; what args says about the model (prot, res_mask, atom_mask_a) has row_map->N_a rows; sides is
+ * [I,N_b] - the reference owns the rows and the sides - and every per-row output is [P,I,N_b].  N_a and N_b are independent, each at
+ * most FDIPT_IFACE_MAX_ROWS.  The reference's existing rows are read from args->res_mask_b ([S_b,N_b], required);
+ * row_map->res_mask_b and row_map->score_mask_b are NOT read.
+ * Reference row j EXISTS where res_mask_b[ib,j] != 0.  It is COVERED where it exists, 0 <= m[j] < N_a and res_mask[ia,m[j]] != 0.
+ * The gathered model G(p): row j is model row m[j] where covered and is masked off by res_mask elsewhere.
+ * Coverage FDIPT_MAP_IGNORE: a row takes part where it is covered, an atom where it exists in the reference row and in model row m[j];
+ * every output is bit for bit fdipt_sample_interface's on G, and n_interface_covered = n_interface_rows.
+ * Coverage FDIPT_MAP_PENALISE (a docking score when residues are missing): a row takes part where it EXISTS.  What is evaluated in the
+ * reference alone - the native contacts, res_native, interface_rows, n_interface_rows - runs over every existing row: an uncovered row
+ * with the atoms of the set that exist in the reference (CB set: CB where the reference has it, else CA), a covered row with the atoms
+ * both structures have.  A contact of the model, and so a shared one, needs both rows covered: an uncovered row costs fnat every native
+ * contact it is part of.  irmsd runs over the RMSD atoms of the interface rows that are covered - n_interface_covered [P,I] counts
+ * them - and lrmsd over the covered ligand rows under the superposition of the covered receptor rows, both in ascending reference rows
+ * (fd_block_sum's order).  dockq, fnonnat and the status bits follow the un-mapped rules on these numbers; FDIPT_IFACE_EMPTY_SIDE looks
+ * at the rows that take part.  The counts equal fdipt_sample_interface's on G with every uncovered existing row given the reference row's
+ * atom pattern at a far, distinct point (beyond both cutoffs from every atom and from each other, marked present): the test oracle.
+ * Verdict on the pair's map: FDIPT_MAP_OUT_OF_RANGE and FDIPT_MAP_DUPLICATE (8, 16) are FDIPT_IFACE_EMPTY_SIDE and
+ * FDIPT_IFACE_NOT_FINITE in this entry's status word, so the entry reports them under two values of its own (64, 128: defined behind the prototypes).  Either treats the
+ * pair's outputs on every interface as FDIPT_IFACE_SKIPPED does (n_interface_covered 0) with n_covered = n_reference = 0, and changes
+ * no bit of another pair; an entry of the map is range-checked at every read whatever the verdict was. */
+/* fdipt_sample_interface_workspace(P, N_b) plus the model row of every reference row and the verdicts on the maps */
+size_t fdipt_sample_interface_mapped_workspace(int P, int N_b);
+/* Four launches on one stream: the verdicts on the maps (with n_covered, n_reference), then fdipt_sample_interface's three reading the
+ * model through the map.  FDIPT_EINVAL: as fdipt_sample_interface, a null row_map, map, n_covered, n_reference, n_interface_covered or
+ * args->res_mask_b, N_a < 1, a coverage outside the two, no prot_b.  FDIPT_ESIZE: as fdipt_sample_interface, N_a >
+ * FDIPT_IFACE_MAX_ROWS.  All before any launch. */
+int fdipt_sample_interface_mapped(const FdiptInterfaceArgs* args, const FdiptRowMap* row_map, fdipt_stream_t stream);
+#define FDIPT_IFACE_MAP_OUT_OF_RANGE 64 /* status: an entry of the pair's map is < -1 or >= N_a (FDIPT_MAP_OUT_OF_RANGE of this entry) */
+#define FDIPT_IFACE_MAP_DUPLICATE 128   /* status: two reference rows of the pair map to the same model row                           */
 
 /* ---------------------------------------------------------------- inverse folding (opt-in) */
 /* The vanilla full-backbone ProteinMPNN (ProteinMPNN/protein_mpnn_utils.py: ProteinFeatures, EncLayer, DecLayer, ProteinMPNN.forward

@@ -8,6 +8,14 @@ checked against the device's.  ``sclk_mhz``: the shader clock the driver reports
 every 20 ms by a host thread during 40 further pruned calls; null where the file cannot be read).
 
     python tools/interface_wall.py [out.json]
+
+``--mapped`` times the entry through a row map instead (``interface_accuracy(..., alignment=, coverage="penalise")``; DESIGN.md section
+7.19) on the same load, for "cb" and "all", four variants in turn: the un-mapped call; an identity map; a map with a deleted window (rows
+300 .. 339 of the reference have no model row); and what a caller without the mapped entry would do for that window - a torch gather of
+the models into reference rows on the device, then the un-mapped call (its device time runs from in front of the gather to the end of
+the launches).  Also says whether the identity map gave the un-mapped call's bits and the window map under "ignore" the gather's.
+
+    python tools/interface_wall.py --mapped [out.json]
 """
 import json
 import os
@@ -170,5 +178,66 @@ def main():
             json.dump(out, f, indent=1)
 
 
+def main_mapped(path=None):
+    lib = _lib.load()
+    events = []
+
+    def timed(launch):
+        def call(*args):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            rc = launch(*args)
+            stop.record()
+            events.append((start, stop))
+            return rc
+        return call
+
+    lib.fdipt_sample_interface, lib.fdipt_sample_interface_mapped = timed(lib.fdipt_sample_interface), timed(lib.fdipt_sample_interface_mapped)
+    pos, models, sides = load()
+    n = int(pos.shape[0])
+    d_models, d_truth, d_sides = torch.from_numpy(models).cuda(), torch.from_numpy(pos[None]).cuda(), torch.from_numpy(sides).cuda()
+    identity = torch.arange(n, dtype=torch.int32, device="cuda")
+    window = identity.clone()
+    window[300:340] = -1
+    keys = ir.INT_OUTPUTS + ir.ROW_OUTPUTS + ir.FLOAT_OUTPUTS
+    out = {"load": {"samples": SAMPLES, "rows": n, "interfaces": int(len(sides)), "repeats": REPEATS, "window": [300, 339]}}
+
+    def gather_then_unmapped(mode):
+        start = torch.cuda.Event(enable_timing=True)
+        start.record()
+        rows = (window >= 0).float()
+        gathered = d_models[:, window.clamp(min=0).long()] * rows[None, :, None, None]
+        res = interface.interface_accuracy(gathered, d_truth, d_sides, atoms=mode, res_mask=rows[None].expand(SAMPLES, n))
+        events.append((start, events[-1][1]))
+        return res
+
+    for mode in ("cb", "all"):
+        variants = {"unmapped": lambda: interface.interface_accuracy(d_models, d_truth, d_sides, atoms=mode),
+                    "identity_map": lambda: interface.interface_accuracy(d_models, d_truth, d_sides, atoms=mode, alignment=identity, coverage="penalise"),
+                    "window_map": lambda: interface.interface_accuracy(d_models, d_truth, d_sides, atoms=mode, alignment=window, coverage="penalise"),
+                    "gather_then_unmapped": lambda: gather_then_unmapped(mode)}
+        walls, device_ms, res = {k: [] for k in variants}, {k: [] for k in variants}, {}
+        for _ in range(1 + REPEATS):  # (the first round is the warm-up of all four)
+            for name, run in variants.items():
+                t0 = time.perf_counter()
+                res[name] = run()
+                walls[name].append(time.perf_counter() - t0)
+                torch.cuda.synchronize()
+                device_ms[name].append(events[-1][0].elapsed_time(events[-1][1]))
+        ignore = interface.interface_accuracy(d_models, d_truth, d_sides, atoms=mode, alignment=window, coverage="ignore")
+        sclk = sclk_while(lambda: [variants["window_map"]() for _ in range(40)])
+        out[mode] = {name: {"call_wall_s": walls[name][1:], "launches_device_ms": device_ms[name][1:]} for name in variants}
+        out[mode].update(identity_equals_unmapped=bool(all(np.array_equal(res["identity_map"][k], res["unmapped"][k], equal_nan=True) for k in keys)),
+                         window_ignore_equals_gather=bool(all(np.array_equal(ignore[k], res["gather_then_unmapped"][k], equal_nan=True) for k in keys)),
+                         mean_fnat={name: float(res[name]["fnat"].mean()) for name in variants}, sclk_mhz=sclk)
+        print(mode, json.dumps(out[mode]), flush=True)
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
-    main()
+    if "--mapped" in sys.argv[1:]:
+        main_mapped(*[a for a in sys.argv[1:] if a != "--mapped"][:1])
+    else:
+        main()
