@@ -1,7 +1,7 @@
 """The one call path of the sample-analysis entries (selection, evaluation, violations, secondary_structure, sasa, tm_score, tm_align,
 inverse_folding, seq_align): shape checks, device choice and upload, optional per-row inputs, output buffers, the C call and the read-back.
 
-``structure_shape``, ``per_row`` on the host (``dev`` None), ``plan_pairs`` and ``square_matrix`` need neither torch nor the built
+``structure_shape``, ``check_shapes``, ``per_row`` on the host (``dev`` None), ``plan_pairs``, ``check_map``, ``add_coverage`` and ``square_matrix`` need neither torch nor the built
 library: an entry raises its shape errors before either is touched.
 """
 from __future__ import annotations
@@ -76,6 +76,32 @@ def per_row(x, shape, what: str, kind: str = "raw", default=None, dev=None):
     elif kind == "int" and x.is_floating_point():
         x = torch.round(x)
     return (x if dtype is None else x.to(getattr(torch, dtype))).contiguous()
+
+
+def check_shapes(checks, mapped: bool = False):
+    """The shapes of the optional inputs of a call, before torch or the library is touched: ``checks`` holds (name, the input or None,
+    the shape it should have).  ValueError, naming the input: it "does not match prot", or - ``mapped``: the two structures of an
+    entry with a row map have rows of their own - "does not match its structure"."""
+    for what, x, shape in checks:
+        got = None if x is None else tuple(x.shape if hasattr(x, "shape") else np.shape(x))
+        if x is not None and got != tuple(shape):
+            raise ValueError(f"{what} {got} does not match {'its structure' if mapped else 'prot'}: expected {tuple(shape)}")
+
+
+def atom_mask(x, shape, what: str, dev):
+    """An optional atom mask as the entries read it: contiguous uint8 on ``dev`` (non-zero: the atom exists), or None."""
+    import torch
+    m = per_row(x, shape, what, "mask", dev=dev)
+    return None if m is None else m.to(torch.uint8).contiguous()
+
+
+def add_coverage(out: dict, n_pairs: int) -> dict:
+    """The result of a mapped entry with ``coverage`` [P] = n_covered / n_reference (0 for no reference row); a result without a call
+    (``empty_outputs``: P = 0) gains the two zero-length counts first."""
+    if n_pairs == 0:
+        out.update(n_covered=np.zeros(0, dtype=np.int64), n_reference=np.zeros(0, dtype=np.int64))
+    out["coverage"] = np.divide(out["n_covered"], out["n_reference"], out=np.zeros(n_pairs), where=out["n_reference"] > 0)
+    return out
 
 
 def zeros_on(dev, spec: dict) -> dict:

@@ -2,75 +2,14 @@
 // contacts across an interface in the reference and in the model, fnat, fnonnat, interface RMSD, ligand RMSD and DockQ of P pairs
 // (model a, reference b) in row correspondence on I interfaces, all in float64.
 //
-// Three launches on one stream, nothing between them on the host:
-//   prep kernel     a block per pair: per row the atoms of the set that take part (they exist in both structures), the RMSD atoms, and
-//                   the row's reach in both structures (largest CA-to-atom distance) go to the workspace; the per-row outputs of the
-//                   pair are zeroed.
-//   contact kernel  a block per (pair, interface, tile of FDIPT_IFACE_ROWS rows).  The ligand rows pass through LDS in tiles of TILE rows
-//                   (256 at <= 5 atoms per row, 64 at 37: a block's LDS stays below 64 KB); a tile without a ligand row is skipped before
-//                   a coordinate is read.  A wave serves the block's receptor rows wave, wave + 4, ...: lane u holds atom u of the row in
-//                   both structures (the loop over u reads it with v_readlane), lane l takes the ligand rows l, l + 64, ... of the tile.
-//                   One residue pair yields its three bits together: contact of the reference, contact of the model, interface.  A
-//                   receptor row's counts belong to its block (plain stores); a ligand row's are summed in LDS per tile and flushed with
-//                   integer atomics.
-//   rmsd kernel     a block per (pair, interface): the integers of the pair (the receptor rows' counts summed), then two superpositions
-//                   as evaluate.hip forms them (centroids, covariance, fd_horn_rotation on one thread, deviations; fd_block_sum's order).
-// Integers only leave the contact kernel, so no order of anything changes a bit of them; pruning skips a residue pair of a structure
-// only where the triangle inequality proves that no atom pair of it can be within the cutoff.
-#include "interface_common.hpp"
+// The prep and rmsd kernels are interface_body.hpp's, in their instantiations without a row map; that header also describes the three
+// launches.  The contact kernel is this unit's own.
+#include "interface_body.hpp"
 
-// the pair's two structures; false where an index is out of range
-__device__ __forceinline__ bool if_pair(const FdiptInterfaceArgs& a, int p, IfStructure& sa, IfStructure& sb) {
-  const int ia = a.pairs[2 * p], ib = a.pairs[2 * p + 1], s_b = a.prot_b ? a.S_b : a.S;
-  if (ia < 0 || ia >= a.S || ib < 0 || ib >= s_b) return false;
-  const int atoms_b = a.prot_b ? a.atoms_b : a.atoms;
-  sa = {a.prot + (long)ia * a.N * a.atoms * 3, a.atom_mask_a ? a.atom_mask_a + (long)ia * a.N * a.atoms : nullptr, a.res_mask + (long)ia * a.N, a.atoms};
-  sb = {(a.prot_b ? a.prot_b : a.prot) + (long)ib * a.N * atoms_b * 3, a.atom_mask_b ? a.atom_mask_b + (long)ib * a.N * atoms_b : nullptr,
-        (a.prot_b ? a.res_mask_b : a.res_mask) + (long)ib * a.N, atoms_b};
-  return true;
-}
+__global__ __launch_bounds__(FD_THREADS) void iface_prep_kernel(FdiptInterfaceArgs a, int K) { if_prep_body<false>(a, FdiptRowMap{}, K); }
 
-__global__ __launch_bounds__(FD_THREADS) void iface_prep_kernel(FdiptInterfaceArgs a, int K) {
-  const int p = blockIdx.x, N = a.N, tid = threadIdx.x;
-  IfStructure sa, sb;
-  const bool ok = if_pair(a, p, sa, sb);
-  unsigned long long* bits = if_bits(a) + (long)p * N;
-  double* reach = if_reach(a) + (long)p * N * 2;
-  for (int i = tid; i < N; i += FD_THREADS) {
-    for (int k = 0; k < a.I; ++k) {
-      const long at = ((long)p * a.I + k) * N + i;
-      a.res_native[at] = a.res_model[at] = a.res_shared[at] = a.interface_rows[at] = 0;
-    }
-    unsigned long long b = 0ull;
-    double ra = 0.0, rb = 0.0;
-    if (ok && sa.rm[i] != 0.f && sb.rm[i] != 0.f) {
-      b = IF_PRESENT;
-      float caa[3], cab[3], va[3], vb[3];
-      const bool ca_ok = if_atom(sa, i, if_column(1, sa.atoms, 0), caa) & if_atom(sb, i, if_column(1, sb.atoms, 0), cab);
-      if (ca_ok) b |= IF_CA_OK;
-      for (int k = 0; k < K; ++k)
-        if (if_atom(sa, i, if_column(K, sa.atoms, k), va) & if_atom(sb, i, if_column(K, sb.atoms, k), vb)) b |= 1ull << k;
-      if (a.mode == FDIPT_IFACE_CB) b &= (b & 2ull) ? ~1ull : ~0ull;  // CB where both structures have it, else CA
-      for (int k = 0; k < K; ++k) {
-        if (!((b >> k) & 1ull) || !ca_ok) continue;
-        if_atom(sa, i, if_column(K, sa.atoms, k), va);
-        if_atom(sb, i, if_column(K, sb.atoms, k), vb);
-        ra = fmax(ra, if_sum_sq((double)va[0] - (double)caa[0], (double)va[1] - (double)caa[1], (double)va[2] - (double)caa[2]));
-        rb = fmax(rb, if_sum_sq((double)vb[0] - (double)cab[0], (double)vb[1] - (double)cab[1], (double)vb[2] - (double)cab[2]));
-      }
-      if (a.mode != FDIPT_IFACE_CA && sa.atoms > 1 && sb.atoms > 1) {
-        for (int r = 0; r < 4; ++r)
-          if (if_atom(sa, i, if_rmsd_column(sa.atoms, r), va) & if_atom(sb, i, if_rmsd_column(sb.atoms, r), vb)) b |= 1ull << (IF_RMSD_SHIFT + r);
-      } else if (ca_ok) {
-        b |= 1ull << (IF_RMSD_SHIFT + 1);
-      }
-    }
-    bits[i] = b;
-    reach[2 * i] = sqrt(ra);
-    reach[2 * i + 1] = sqrt(rb);
-  }
-}
-
+// The contact kernel stands here in full and again, with the model read at the resolved rows, in interface_mapped.hip: as an instantiation
+// of a shared body the unpruned all-atom pass measured 1.2 % slower.  A change to one is a change to both.
 template <int K, int TILE>
 __global__ __launch_bounds__(FD_THREADS) void iface_contact_kernel(FdiptInterfaceArgs a, int rtiles) {
   static_assert(K <= FD_WAVE && TILE % FD_WAVE == 0 && FDIPT_IFACE_ROWS <= 255 && FDIPT_IFACE_ROWS <= FD_THREADS, "a lane per atom; 8-bit counts per ligand row and tile");
@@ -223,75 +162,7 @@ __global__ __launch_bounds__(FD_THREADS) void iface_contact_kernel(FdiptInterfac
   }
 }
 
-__global__ __launch_bounds__(FD_THREADS) void iface_rmsd_kernel(FdiptInterfaceArgs a) {
-  __shared__ unsigned char cls[FDIPT_IFACE_MAX_ROWS];
-  __shared__ double red[FD_WAVES * 9];
-  __shared__ long long red_i[FD_WAVES * 6];
-  __shared__ double rot_sh[12];
-  __shared__ int flag_sh;
-  const int tid = threadIdx.x, N = a.N, p = blockIdx.x / a.I, k = blockIdx.x % a.I;
-  const long pk = (long)p * a.I + k;
-  IfStructure sa, sb;
-  if (!if_pair(a, p, sa, sb)) {
-    if (tid == 0) {
-      a.n_native[pk] = a.n_model[pk] = a.n_shared[pk] = a.n_interface_rows[pk] = 0;
-      a.fnat[pk] = a.fnonnat[pk] = 0.0;
-      a.irmsd[pk] = a.lrmsd[pk] = a.dockq[pk] = __builtin_nan("");
-      for (int c = 0; c < 9; ++c) a.interface_rotation[pk * 9 + c] = a.receptor_rotation[pk * 9 + c] = 0.0;
-      for (int c = 0; c < 3; ++c) a.interface_translation[pk * 3 + c] = a.receptor_translation[pk * 3 + c] = 0.0;
-      a.status[pk] = FDIPT_IFACE_SKIPPED;
-    }
-    return;
-  }
-  const int* side = a.sides + (long)k * N;
-  const unsigned long long* wb = if_bits(a) + (long)p * N;
-  // 0 .. 2: contacts of the reference, of the model, of both; 3: interface rows; 4, 5: receptor and ligand rows that take part
-  long long is[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = tid; i < N; i += FD_THREADS) {
-    const long at = pk * N + i;
-    int c = 0;
-    if (wb[i] & IF_PRESENT) c = side[i] == FDIPT_IFACE_RECEPTOR ? IF_CLS_RECEPTOR : side[i] == FDIPT_IFACE_LIGAND ? IF_CLS_LIGAND : 0;
-    if (c && a.interface_rows[at]) c |= IF_CLS_INTERFACE;
-    cls[i] = (unsigned char)c;
-    if (c & IF_CLS_RECEPTOR) {
-      is[0] += a.res_native[at];
-      is[1] += a.res_model[at];
-      is[2] += a.res_shared[at];
-    }
-    is[3] += (c & IF_CLS_INTERFACE) != 0;
-    is[4] += (c & IF_CLS_RECEPTOR) != 0;
-    is[5] += (c & IF_CLS_LIGAND) != 0;
-  }
-  fd_block_sum(is, red_i);  // (its barriers publish cls)
-  double ti[12], tl[12], irmsd, lrmsd;
-  int st_i, st_l;
-  if_superpose<false>(sa, sb, wb, nullptr, cls, N, IF_CLS_INTERFACE, IF_CLS_INTERFACE, red, rot_sh, &flag_sh, ti, irmsd, st_i);
-  if_superpose<false>(sa, sb, wb, nullptr, cls, N, IF_CLS_RECEPTOR, IF_CLS_LIGAND, red, rot_sh, &flag_sh, tl, lrmsd, st_l);
-  if (tid != 0) return;
-  int status = st_i | st_l | (is[0] == 0 ? FDIPT_IFACE_NO_NATIVE_CONTACT : 0) | (is[4] == 0 || is[5] == 0 ? FDIPT_IFACE_EMPTY_SIDE : 0);
-  const double fnat = is[0] > 0 ? (double)is[2] / (double)is[0] : 0.0;
-  const double fnonnat = is[1] > 0 ? (double)(is[1] - is[2]) / (double)is[1] : 0.0;
-  if (is[0] == 0) irmsd = __builtin_nan("");
-  const double si = irmsd / 1.5, sl = lrmsd / 8.5;
-  a.n_native[pk] = (int)is[0];
-  a.n_model[pk] = (int)is[1];
-  a.n_shared[pk] = (int)is[2];
-  a.n_interface_rows[pk] = (int)is[3];
-  a.fnat[pk] = fnat;
-  a.fnonnat[pk] = fnonnat;
-  a.irmsd[pk] = irmsd;
-  a.lrmsd[pk] = lrmsd;
-  a.dockq[pk] = (fnat + 1.0 / (1.0 + si * si) + 1.0 / (1.0 + sl * sl)) / 3.0;  // (NaN where an RMSD is)
-  for (int c = 0; c < 9; ++c) {
-    a.interface_rotation[pk * 9 + c] = ti[c];
-    a.receptor_rotation[pk * 9 + c] = tl[c];
-  }
-  for (int c = 0; c < 3; ++c) {
-    a.interface_translation[pk * 3 + c] = ti[9 + c];
-    a.receptor_translation[pk * 3 + c] = tl[9 + c];
-  }
-  a.status[pk] = status;
-}
+__global__ __launch_bounds__(FD_THREADS) void iface_rmsd_kernel(FdiptInterfaceArgs a) { if_rmsd_body<false>(a, FdiptRowMap{}); }
 
 extern "C" size_t fdipt_sample_interface_workspace(int P, int N) {
   if (P < 1 || N < 1) return 0;
@@ -299,35 +170,17 @@ extern "C" size_t fdipt_sample_interface_workspace(int P, int N) {
 }
 
 extern "C" int fdipt_sample_interface(const FdiptInterfaceArgs* a, fdipt_stream_t stream) {
-  if (!a || a->S < 1 || a->N < 1 || a->P < 1 || a->I < 1 || a->mode < FDIPT_IFACE_CA || a->mode > FDIPT_IFACE_ALL || !(a->contact_cutoff > 0.0) ||
-      !(a->interface_cutoff > 0.0) || (a->flags & ~FDIPT_IFACE_NO_PRUNE))
-    return FDIPT_EINVAL;
-  const int atoms_b = a->prot_b ? a->atoms_b : a->atoms;
-  for (int atoms : {a->atoms, atoms_b}) {
-    if (atoms != 37 && atoms != 5 && atoms != 1) return FDIPT_EINVAL;
-    if ((a->mode == FDIPT_IFACE_ALL && atoms != 37) || (a->mode != FDIPT_IFACE_CA && atoms == 1)) return FDIPT_EINVAL;
-  }
-  if (a->prot_b && (a->S_b < 1 || !a->res_mask_b)) return FDIPT_EINVAL;
-  if (!a->prot || !a->res_mask || !a->pairs || !a->sides || !a->n_native || !a->n_model || !a->n_shared || !a->n_interface_rows || !a->res_native ||
-      !a->res_model || !a->res_shared || !a->interface_rows || !a->fnat || !a->fnonnat || !a->irmsd || !a->lrmsd || !a->dockq || !a->interface_rotation ||
-      !a->interface_translation || !a->receptor_rotation || !a->receptor_translation || !a->status || !a->workspace)
-    return FDIPT_EINVAL;
-  if (a->N > FDIPT_IFACE_MAX_ROWS || a->I > FDIPT_IFACE_MAX_INTERFACES) return FDIPT_ESIZE;
+  const int rc = if_check_args(a, nullptr);
+  if (rc != FDIPT_OK) return rc;
   if (a->workspace_bytes < fdipt_sample_interface_workspace(a->P, a->N)) return FDIPT_ESIZE;
-  const long rtiles = cdiv(a->N, FDIPT_IFACE_ROWS);
-  if (rtiles * a->I * a->P > 0x7fffffffL) return FDIPT_ESIZE;
-  const dim3 grid((unsigned)(rtiles * a->I * a->P)), block(FD_THREADS);
-  const int K = if_set_atoms(a->mode);
-  hipLaunchKernelGGL(iface_prep_kernel, dim3(a->P), block, 0, (hipStream_t)stream, *a, K);
+  static void (*const contact[])(FdiptInterfaceArgs, int) = {  // by FDIPT_IFACE_CA .. FDIPT_IFACE_ALL
+      iface_contact_kernel<1, FDIPT_IFACE_TILE>, iface_contact_kernel<2, FDIPT_IFACE_TILE>, iface_contact_kernel<5, FDIPT_IFACE_TILE>,
+      iface_contact_kernel<37, FDIPT_IFACE_TILE_ALL>};
+  const int rtiles = cdiv(a->N, FDIPT_IFACE_ROWS);
+  const dim3 grid((unsigned)rtiles * a->I * a->P), block(FD_THREADS);
+  hipLaunchKernelGGL(iface_prep_kernel, dim3(a->P), block, 0, (hipStream_t)stream, *a, if_set_atoms(a->mode));
   FD_CHECK_LAUNCH();
-  if (a->mode == FDIPT_IFACE_CA)
-    hipLaunchKernelGGL((iface_contact_kernel<1, FDIPT_IFACE_TILE>), grid, block, 0, (hipStream_t)stream, *a, (int)rtiles);
-  else if (a->mode == FDIPT_IFACE_CB)
-    hipLaunchKernelGGL((iface_contact_kernel<2, FDIPT_IFACE_TILE>), grid, block, 0, (hipStream_t)stream, *a, (int)rtiles);
-  else if (a->mode == FDIPT_IFACE_BACKBONE)
-    hipLaunchKernelGGL((iface_contact_kernel<5, FDIPT_IFACE_TILE>), grid, block, 0, (hipStream_t)stream, *a, (int)rtiles);
-  else
-    hipLaunchKernelGGL((iface_contact_kernel<37, FDIPT_IFACE_TILE_ALL>), grid, block, 0, (hipStream_t)stream, *a, (int)rtiles);
+  hipLaunchKernelGGL(contact[a->mode - FDIPT_IFACE_CA], grid, block, 0, (hipStream_t)stream, *a, rtiles);
   FD_CHECK_LAUNCH();
   hipLaunchKernelGGL(iface_rmsd_kernel, dim3(a->P * a->I), block, 0, (hipStream_t)stream, *a);
   FD_CHECK_LAUNCH();

@@ -5,34 +5,13 @@
 #include "lddt_body.hpp"
 
 __global__ __launch_bounds__(FD_THREADS) void lddt_map_kernel(FdiptLddtArgs a, FdiptRowMap m) {
-  __shared__ unsigned bits_sh[FD_MAP_WORDS];
-  __shared__ int flag_sh, count_sh[2];
-  const int tid = threadIdx.x, lane = tid & (FD_WAVE - 1), N = a.N, p = blockIdx.x;
+  __shared__ FdMapLds lds;
+  const int N = a.N, p = blockIdx.x;
   const int ia = a.pairs[2 * p], ib = a.pairs[2 * p + 1];
-  if (ia < 0 || ia >= a.S || ib < 0 || ib >= a.S_b) {
-    if (tid == 0) ld_verdicts(a)[p] = FDIPT_LDDT_SKIPPED, m.n_covered[p] = 0, m.n_reference[p] = 0;
-    return;
-  }
-  const int* mp = m.map + (long)p * N;
-  const float *rmb = m.res_mask_b + (long)ib * N, *rma = a.res_mask + (long)ia * m.N_a;
-  if (tid < 2) count_sh[tid] = 0;
-  const int verdict = fd_map_check(mp, N, m.N_a, bits_sh, &flag_sh);  // (with barriers: count_sh is zero for everyone behind it)
-  for (int j0 = 0; j0 < N; j0 += FD_THREADS) {
-    const int j = j0 + tid;
-    const bool ex = j < N && rmb[j < N ? j : 0] != 0.f;
-    const bool cov = ex && fd_map_row(mp, rma, m.N_a, j) >= 0;
-    const unsigned long long be = __ballot(ex), bc = __ballot(cov);
-    if (lane == 0) {  // integer adds: the order changes nothing
-      if (be) atomicAdd(&count_sh[1], __popcll(be));
-      if (bc) atomicAdd(&count_sh[0], __popcll(bc));
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    ld_verdicts(a)[p] = verdict;
-    m.n_covered[p] = verdict ? 0 : count_sh[0];
-    m.n_reference[p] = verdict ? 0 : count_sh[1];
-  }
+  int verdict = FDIPT_LDDT_SKIPPED, n_covered = 0, n_reference = 0;
+  if (ia >= 0 && ia < a.S && ib >= 0 && ib < a.S_b)  // (block-uniform)
+    verdict = fd_map_judge(m.map + (long)p * N, a.res_mask + (long)ia * m.N_a, m.res_mask_b + (long)ib * N, N, m.N_a, lds, n_covered, n_reference);
+  if (threadIdx.x == 0) ld_verdicts(a)[p] = verdict, m.n_covered[p] = n_covered, m.n_reference[p] = n_reference;
 }
 
 template <int K, int TILE>

@@ -1,5 +1,7 @@
 // rowmap.hpp — the row map of the mapped accuracy entries (include/fdipt.h, "accuracy through a row map"): what
-// lddt_mapped.hip and gdt_mapped.hip share.  map[j] is the model row that corresponds to reference row j, or -1.
+// lddt_mapped.hip, gdt_mapped.hip and interface_mapped.hip share - the range-checked read of an entry, the verdict on a map, and the
+// pre-pass of the two entries that judge a pair's map in a launch of its own.  map[j] is the model row that corresponds to reference
+// row j, or -1.
 #pragma once
 #include "common.hpp"
 
@@ -38,4 +40,35 @@ __device__ __forceinline__ int fd_map_check(const int* mp, int n, int n_a, unsig
   if (flags) atomicOr(flag_sh, flags);
   __syncthreads();
   return *flag_sh;
+}
+
+// The LDS of fd_map_judge.
+struct FdMapLds {
+  unsigned bits[FD_MAP_WORDS];
+  int flag, count[2];
+};
+
+// The pre-pass of the entries that judge a pair's map in a launch of its own (lddt_mapped.hip, interface_mapped.hip), called by every
+// thread of the pair's block: fd_map_check's verdict on mp[0 .. n), then the reference rows that exist (mask_b: n_reference) and those
+// of them with a model row that exists (fd_map_row with mask_a: n_covered), both 0 under a verdict.  Every thread gets the same three
+// numbers.  The counts are ballots summed with integer atomics on LDS: no order changes them.
+__device__ __forceinline__ int fd_map_judge(const int* mp, const float* mask_a, const float* mask_b, int n, int n_a, FdMapLds& lds, int& n_covered,
+                                            int& n_reference) {
+  const int tid = threadIdx.x;
+  if (tid < 2) lds.count[tid] = 0;
+  const int verdict = fd_map_check(mp, n, n_a, lds.bits, &lds.flag);  // (with barriers: count is zero for everyone behind it)
+  for (int j0 = 0; j0 < n; j0 += FD_THREADS) {
+    const int j = j0 + tid;
+    const bool ex = j < n && mask_b[j < n ? j : 0] != 0.f;
+    const bool cov = ex && fd_map_row(mp, mask_a, n_a, j) >= 0;
+    const unsigned long long be = __ballot(ex), bc = __ballot(cov);
+    if ((tid & (FD_WAVE - 1)) == 0) {
+      if (be) atomicAdd(&lds.count[1], __popcll(be));
+      if (bc) atomicAdd(&lds.count[0], __popcll(bc));
+    }
+  }
+  __syncthreads();
+  n_covered = verdict ? 0 : lds.count[0];
+  n_reference = verdict ? 0 : lds.count[1];
+  return verdict;
 }

@@ -113,9 +113,7 @@ def _mapped_scores(prot_a, prot_b, mask_a, mask_b, pairs, norm_length, ref_index
     by_reference = isinstance(norm_length, str)
     if by_reference and norm_length != "reference":
         raise ValueError(f"norm_length should be numbers, None or 'reference', got {norm_length!r}")
-    for what, x, shape in (("mask_a", mask_a, (s_a, n_a)), ("mask_b", mask_b, (s_b, n_b))):
-        if x is not None and tuple(x.shape if hasattr(x, "shape") else np.shape(x)) != shape:
-            raise ValueError(f"{what} {tuple(x.shape if hasattr(x, 'shape') else np.shape(x))} does not match its structure: expected {shape}")
+    _call.check_shapes((("mask_a", mask_a, (s_a, n_a)), ("mask_b", mask_b, (s_b, n_b))), mapped=True)
     if by_reference:  # (the masked reference rows of every pair, on the host: a device mask is read back)
         rows = np.full(s_b, n_b, dtype=np.int64) if mask_b is None else np.count_nonzero(_call.host(mask_b), axis=1)
         norm_length = rows[np.clip(pair_list[:, 1], 0, s_b - 1)].astype(np.int32)
@@ -127,7 +125,6 @@ def _mapped_scores(prot_a, prot_b, mask_a, mask_b, pairs, norm_length, ref_index
     outputs = {key: ("float64" if key in ("gdt_ts", "gdt_ha", "rotation", "translation") else "int32", (n_pairs,) + shapes.get(key, ())) for key in OUTPUTS}
     if n_pairs == 0:
         out = _call.empty_outputs(outputs, _INTS)
-        out.update(n_covered=np.zeros(0, dtype=np.int64), n_reference=np.zeros(0, dtype=np.int64))
     else:
         import torch
         dev, (xa, xb) = _call.upload("gdt_scores", prot_a=prot_a, prot_b=prot_b)
@@ -138,9 +135,8 @@ def _mapped_scores(prot_a, prot_b, mask_a, mask_b, pairs, norm_length, ref_index
                                     norm_length=None if norm_length is None else torch.from_numpy(norm_length).to(dev)),
                                outputs, dict(N_a=n_a, coverage=0, map=_call.upload_map(alignment, n_pairs, n_b, dev), res_mask_b=None, score_mask_b=None),
                                widen=_INTS)
-    out["coverage"] = np.divide(out["n_covered"], out["n_reference"], out=np.zeros(n_pairs), where=out["n_reference"] > 0)
     out["pairs"] = pair_list.astype(np.int64)
-    return out
+    return _call.add_coverage(out, n_pairs)
 
 
 def gdt_metrics(result: dict, p: int) -> dict:

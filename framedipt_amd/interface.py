@@ -129,15 +129,17 @@ def interface_accuracy(prot_a, prot_b=None, sides=None, atoms: str = "cb", res_m
         raise ValueError(f"atoms should be 'ca', 'cb', 'backbone' or 'all', got {atoms!r}")
     if sides is None:
         raise ValueError("sides is required: chain_sides(chain_idx) or loop_sides(diffuse_mask, chain_idx) build it")
-    if alignment is not None:
-        return _mapped_interface(prot_a, prot_b, sides, atoms, res_mask, res_mask_b, atom_mask_a, atom_mask_b, pairs, ref_index, contact_cutoff,
-                                 interface_cutoff, prune, alignment, coverage)
-    if coverage != "ignore":
+    mapped = alignment is not None
+    if mapped and coverage not in COVERAGE:
+        raise ValueError(f"coverage should be 'ignore' or 'penalise', got {coverage!r}")
+    if not mapped and coverage != "ignore":
         raise ValueError(f"coverage={coverage!r} belongs to a call with an alignment")
-    s_a, n, atoms_a = _shape(prot_a, "prot_a")
-    s_b, n_b, atoms_b = (s_a, n, atoms_a) if prot_b is None else _shape(prot_b, "prot_b")
-    if n_b != n:
-        raise ValueError(f"prot_b {tuple(prot_b.shape)} does not have the {n} rows of prot_a")
+    if mapped and prot_b is None:
+        raise ValueError("alignment maps the rows of prot_b to those of prot_a: prot_b is required")
+    s_a, n_a, atoms_a = _shape(prot_a, "prot_a")
+    s_b, n, atoms_b = (s_a, n_a, atoms_a) if prot_b is None else _shape(prot_b, "prot_b")  # n: the rows of every per-row output, the reference's
+    if not mapped and n != n_a:
+        raise ValueError(f"prot_b {tuple(prot_b.shape)} does not have the {n_a} rows of prot_a")
     for what, layout in (("prot_a", atoms_a), ("prot_b", atoms_b)):
         if (atoms == "all" and layout != 37) or (atoms in ("cb", "backbone") and layout == 1):
             raise ValueError(f"atoms={atoms!r} needs {'atom37' if atoms == 'all' else 'the backbone atoms'}: {what} holds {layout} atom(s) per row")
@@ -151,20 +153,22 @@ def interface_accuracy(prot_a, prot_b=None, sides=None, atoms: str = "cb", res_m
     if len(sides_shape) == 1:
         sides_shape = (1,) + sides_shape
     if len(sides_shape) != 2 or sides_shape[1] != n or sides_shape[0] < 1:
-        raise ValueError(f"sides should be [I, {n}] (or [{n}]) with I >= 1, got {tuple(sides_host.shape)}")
+        raise ValueError(f"sides should be [I, {n}] (or [{n}]) with I >= 1{' - with an alignment the rows of prot_b, the reference -' if mapped else ''}, got "
+                         f"{tuple(sides_host.shape)}")
     n_if = sides_shape[0]
     if prot_b is None and pairs is None and ref_index is None:
         pair_list, square = ordered_pairs(s_a), True
     else:
         pair_list, square = _call.plan_pairs(s_a, s_b, prot_b is not None, pairs, ref_index)
     n_pairs = len(pair_list)
-    checks = (("res_mask", res_mask, (s_a, n)), ("res_mask_b", res_mask_b, (s_b, n)), ("atom_mask_a", atom_mask_a, (s_a, n) + (() if atoms_a == 1 else (atoms_a,))),
-              ("atom_mask_b", atom_mask_b, (s_b, n) + (() if atoms_b == 1 else (atoms_b,))))
-    for what, x, shape in checks:
-        if x is not None and tuple(x.shape if hasattr(x, "shape") else np.shape(x)) != shape:
-            raise ValueError(f"{what} {tuple(x.shape if hasattr(x, 'shape') else np.shape(x))} does not match prot: expected {shape}")
-    ints = PER_INTERFACE_INTS + PER_ROW[:3]
-    outputs = {key: ("int32", (n_pairs, n_if)) for key in PER_INTERFACE_INTS}
+    shape_a, shape_b = (s_a, n_a) + (() if atoms_a == 1 else (atoms_a,)), (s_b, n) + (() if atoms_b == 1 else (atoms_b,))
+    _call.check_shapes((("res_mask", res_mask, (s_a, n_a)), ("res_mask_b", res_mask_b, (s_b, n)), ("atom_mask_a", atom_mask_a, shape_a),
+                        ("atom_mask_b", atom_mask_b, shape_b)), mapped)
+    if mapped:
+        alignment = _call.check_map(alignment, n_pairs, n, n_a)
+    per_interface_ints = PER_INTERFACE_INTS + (("n_interface_covered",) if mapped else ())
+    ints = per_interface_ints + PER_ROW[:3]
+    outputs = {key: ("int32", (n_pairs, n_if)) for key in per_interface_ints}
     outputs.update({key: ("float64", (n_pairs, n_if)) for key in PER_INTERFACE})
     outputs.update({key: ("int32", (n_pairs, n_if, n)) for key in PER_ROW})
     outputs.update({key: ("float64", (n_pairs, n_if) + shape) for key, shape in TRANSFORMS.items()})
@@ -173,90 +177,31 @@ def interface_accuracy(prot_a, prot_b=None, sides=None, atoms: str = "cb", res_m
     else:
         import torch
         dev, (xa, xb) = _call.upload("interface_accuracy", prot_a=prot_a, prot_b=prot_b)
-
-        def atom_mask(x, shape, what):
-            m = _call.per_row(x, shape, what, "mask", dev=dev)
-            return None if m is None else m.to(torch.uint8).contiguous()
-
-        mask_a = atom_mask(atom_mask_a, checks[2][2], "atom_mask_a")
-        mask_b = mask_a if prot_b is None else atom_mask(atom_mask_b, checks[3][2], "atom_mask_b")
-        sides_dev = _call.per_row(sides_host.reshape(n_if, n), (n_if, n), "sides", "int", dev=dev)
-        out = _call.run("fdipt_sample_interface", _lib.InterfaceArgs, dev,
-                        dict(S=s_a, N=n, atoms=atoms_a, S_b=s_b, atoms_b=atoms_b, P=n_pairs, I=n_if, mode=MODES[atoms], flags=0 if prune else _lib.IFACE_NO_PRUNE,
-                             contact_cutoff=contact_cutoff, interface_cutoff=float(interface_cutoff)),
-                        dict(prot=xa, prot_b=xb, res_mask=_call.per_row(res_mask, (s_a, n), "res_mask", "mask", default=1, dev=dev),
-                             res_mask_b=None if prot_b is None else _call.per_row(res_mask_b, (s_b, n), "res_mask_b", "mask", default=1, dev=dev),
-                             atom_mask_a=mask_a, atom_mask_b=mask_b, pairs=torch.from_numpy(pair_list).to(dev), sides=sides_dev),
-                        outputs, widen=ints, workspace=("fdipt_sample_interface_workspace", n_pairs, n))
+        mask_a = _call.atom_mask(atom_mask_a, shape_a, "atom_mask_a", dev)
+        mask_b = mask_a if prot_b is None else _call.atom_mask(atom_mask_b, shape_b, "atom_mask_b", dev)
+        rows_b = None if prot_b is None else _call.per_row(res_mask_b, (s_b, n), "res_mask_b", "mask", default=1, dev=dev)
+        entry = "fdipt_sample_interface_mapped" if mapped else "fdipt_sample_interface"
+        call = (entry, _lib.InterfaceArgs, dev,
+                dict(S=s_a, N=n, atoms=atoms_a, S_b=s_b, atoms_b=atoms_b, P=n_pairs, I=n_if, mode=MODES[atoms], flags=0 if prune else _lib.IFACE_NO_PRUNE,
+                     contact_cutoff=contact_cutoff, interface_cutoff=float(interface_cutoff)),
+                dict(prot=xa, prot_b=xb, res_mask=_call.per_row(res_mask, (s_a, n_a), "res_mask", "mask", default=1, dev=dev), res_mask_b=rows_b,
+                     atom_mask_a=mask_a, atom_mask_b=mask_b, pairs=torch.from_numpy(pair_list).to(dev),
+                     sides=_call.per_row(sides_host.reshape(n_if, n), (n_if, n), "sides", "int", dev=dev)),
+                outputs)
+        if mapped:
+            out = _call.run_mapped(*call, dict(N_a=n_a, coverage=COVERAGE[coverage], map=_call.upload_map(alignment, n_pairs, n, dev), res_mask_b=rows_b,
+                                               score_mask_b=None), widen=ints, workspace=(entry + "_workspace", n_pairs, n))
+        else:
+            out = _call.run(*call, widen=ints, workspace=(entry + "_workspace", n_pairs, n))
     out["interface_rows"] = out["interface_rows"] != 0
     out.update(pairs=pair_list.astype(np.int64), atoms=atoms, contact_cutoff=contact_cutoff, interface_cutoff=float(interface_cutoff))
+    if mapped:
+        _call.add_coverage(out, n_pairs)
+        out["coverage_mode"] = coverage
     if square:
         for key, name in (("dockq", "matrix_dockq"), ("fnat", "matrix_fnat")):
             out[name] = np.tile(np.eye(s_a), (n_if, 1, 1))
             out[name][:, pair_list[:, 0], pair_list[:, 1]] = out[key].T
-    return out
-
-
-def _mapped_interface(prot_a, prot_b, sides, atoms, res_mask, res_mask_b, atom_mask_a, atom_mask_b, pairs, ref_index, contact_cutoff, interface_cutoff, prune,
-                      alignment, coverage) -> dict:
-    """``interface_accuracy`` with an alignment: one call of ``fdipt_sample_interface_mapped``."""
-    if coverage not in COVERAGE:
-        raise ValueError(f"coverage should be 'ignore' or 'penalise', got {coverage!r}")
-    if prot_b is None:
-        raise ValueError("alignment maps the rows of prot_b to those of prot_a: prot_b is required")
-    s_a, n_a, atoms_a = _shape(prot_a, "prot_a")
-    s_b, n_b, atoms_b = _shape(prot_b, "prot_b")
-    for what, layout in (("prot_a", atoms_a), ("prot_b", atoms_b)):
-        if (atoms == "all" and layout != 37) or (atoms in ("cb", "backbone") and layout == 1):
-            raise ValueError(f"atoms={atoms!r} needs {'atom37' if atoms == 'all' else 'the backbone atoms'}: {what} holds {layout} atom(s) per row")
-    contact_cutoff = CONTACT_CUTOFF[atoms] if contact_cutoff is None else float(contact_cutoff)
-    if not contact_cutoff > 0 or not interface_cutoff > 0:
-        raise ValueError(f"the cutoffs should be positive, got contact_cutoff={contact_cutoff}, interface_cutoff={interface_cutoff}")
-    sides_host = sides if hasattr(sides, "detach") else np.asarray(sides)
-    sides_shape = tuple(sides_host.shape)
-    if len(sides_shape) == 1:
-        sides_shape = (1,) + sides_shape
-    if len(sides_shape) != 2 or sides_shape[1] != n_b or sides_shape[0] < 1:
-        raise ValueError(f"sides should be [I, {n_b}] (or [{n_b}]) with I >= 1 - with an alignment the rows of prot_b, the reference -, got "
-                         f"{tuple(sides_host.shape)}")
-    n_if = sides_shape[0]
-    pair_list, _ = _call.plan_pairs(s_a, s_b, True, pairs, ref_index)
-    n_pairs = len(pair_list)
-    checks = (("res_mask", res_mask, (s_a, n_a)), ("res_mask_b", res_mask_b, (s_b, n_b)), ("atom_mask_a", atom_mask_a, (s_a, n_a) + (() if atoms_a == 1 else (atoms_a,))),
-              ("atom_mask_b", atom_mask_b, (s_b, n_b) + (() if atoms_b == 1 else (atoms_b,))))
-    for what, x, shape in checks:
-        if x is not None and tuple(x.shape if hasattr(x, "shape") else np.shape(x)) != shape:
-            raise ValueError(f"{what} {tuple(x.shape if hasattr(x, 'shape') else np.shape(x))} does not match its structure: expected {shape}")
-    alignment = _call.check_map(alignment, n_pairs, n_b, n_a)
-    ints = PER_INTERFACE_INTS + PER_ROW[:3] + ("n_interface_covered",)
-    outputs = {key: ("int32", (n_pairs, n_if)) for key in PER_INTERFACE_INTS + ("n_interface_covered",)}
-    outputs.update({key: ("float64", (n_pairs, n_if)) for key in PER_INTERFACE})
-    outputs.update({key: ("int32", (n_pairs, n_if, n_b)) for key in PER_ROW})
-    outputs.update({key: ("float64", (n_pairs, n_if) + shape) for key, shape in TRANSFORMS.items()})
-    if n_pairs == 0:
-        out = _call.empty_outputs(outputs, ints)
-        out.update(n_covered=np.zeros(0, dtype=np.int64), n_reference=np.zeros(0, dtype=np.int64))
-    else:
-        import torch
-        dev, (xa, xb) = _call.upload("interface_accuracy", prot_a=prot_a, prot_b=prot_b)
-
-        def atom_mask(x, shape, what):
-            m = _call.per_row(x, shape, what, "mask", dev=dev)
-            return None if m is None else m.to(torch.uint8).contiguous()
-
-        mask_b = _call.per_row(res_mask_b, (s_b, n_b), "res_mask_b", "mask", default=1, dev=dev)
-        out = _call.run_mapped("fdipt_sample_interface_mapped", _lib.InterfaceArgs, dev,
-                               dict(S=s_a, N=n_b, atoms=atoms_a, S_b=s_b, atoms_b=atoms_b, P=n_pairs, I=n_if, mode=MODES[atoms],
-                                    flags=0 if prune else _lib.IFACE_NO_PRUNE, contact_cutoff=contact_cutoff, interface_cutoff=float(interface_cutoff)),
-                               dict(prot=xa, prot_b=xb, res_mask=_call.per_row(res_mask, (s_a, n_a), "res_mask", "mask", default=1, dev=dev), res_mask_b=mask_b,
-                                    atom_mask_a=atom_mask(atom_mask_a, checks[2][2], "atom_mask_a"), atom_mask_b=atom_mask(atom_mask_b, checks[3][2], "atom_mask_b"),
-                                    pairs=torch.from_numpy(pair_list).to(dev), sides=_call.per_row(sides_host.reshape(n_if, n_b), (n_if, n_b), "sides", "int", dev=dev)),
-                               outputs,
-                               dict(N_a=n_a, coverage=COVERAGE[coverage], map=_call.upload_map(alignment, n_pairs, n_b, dev), res_mask_b=mask_b, score_mask_b=None),
-                               widen=ints, workspace=("fdipt_sample_interface_mapped_workspace", n_pairs, n_b))
-    out["interface_rows"] = out["interface_rows"] != 0
-    out["coverage"] = np.divide(out["n_covered"], out["n_reference"], out=np.zeros(n_pairs), where=out["n_reference"] > 0)
-    out.update(pairs=pair_list.astype(np.int64), atoms=atoms, contact_cutoff=contact_cutoff, interface_cutoff=float(interface_cutoff), coverage_mode=coverage)
     return out
 
 

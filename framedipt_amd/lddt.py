@@ -85,15 +85,17 @@ def local_accuracy(prot_a, prot_b=None, atoms: str = "ca", res_mask=None, score_
     ``status`` carries ``MAP_OUT_OF_RANGE`` / ``MAP_DUPLICATE`` and its outputs are zero."""
     if atoms not in MODES:
         raise ValueError(f"atoms should be 'ca', 'backbone' or 'all', got {atoms!r}")
-    if alignment is not None:
-        return _mapped_accuracy(prot_a, prot_b, atoms, res_mask, score_mask, atom_mask_a, atom_mask_b, pairs, ref_index, cutoff, same_residue, per_atom,
-                                alignment, coverage, res_mask_b)
-    if coverage != "ignore" or res_mask_b is not None:
+    mapped = alignment is not None
+    if mapped and coverage not in COVERAGE:
+        raise ValueError(f"coverage should be 'ignore' or 'penalise', got {coverage!r}")
+    if not mapped and (coverage != "ignore" or res_mask_b is not None):
         raise ValueError("coverage and res_mask_b belong to a call with an alignment")
-    s_a, n, atoms_a = _shape(prot_a, "prot_a")
-    s_b, n_b, atoms_b = (s_a, n, atoms_a) if prot_b is None else _shape(prot_b, "prot_b")
-    if n_b != n:
-        raise ValueError(f"prot_b {tuple(prot_b.shape)} does not have the {n} rows of prot_a")
+    if mapped and prot_b is None:
+        raise ValueError("an alignment maps the rows of prot_b to those of prot_a: prot_b is required")
+    s_a, n_a, atoms_a = _shape(prot_a, "prot_a")
+    s_b, n, atoms_b = (s_a, n_a, atoms_a) if prot_b is None else _shape(prot_b, "prot_b")  # n: the rows of every per-row output, the reference's
+    if not mapped and n != n_a:
+        raise ValueError(f"prot_b {tuple(prot_b.shape)} does not have the {n_a} rows of prot_a")
     for what, layout in (("prot_a", atoms_a), ("prot_b", atoms_b)):
         if (atoms == "all" and layout != 37) or (atoms == "backbone" and layout == 1):
             raise ValueError(f"atoms={atoms!r} needs {'atom37' if atoms == 'all' else 'the backbone atoms'}: {what} holds {layout} atom(s) per row")
@@ -106,12 +108,12 @@ def local_accuracy(prot_a, prot_b=None, atoms: str = "ca", res_mask=None, score_
     else:
         pair_list, square = _call.plan_pairs(s_a, s_b, prot_b is not None, pairs, ref_index)
     n_pairs, k = len(pair_list), SET_ATOMS[atoms]
+    score_rows = (s_b, n) if mapped else (s_a, n)  # (the rows that are reported are the reference's)
     # (shape errors of the optional inputs before torch or the library is touched)
-    checks = (("res_mask", res_mask, (s_a, n)), ("score_mask", score_mask, (s_a, n)), ("atom_mask_a", atom_mask_a, (s_a, n, atoms_a)),
-              ("atom_mask_b", atom_mask_b, (s_b, n, atoms_b)))
-    for what, x, shape in checks:
-        if x is not None and tuple(x.shape if hasattr(x, "shape") else np.shape(x)) != shape:
-            raise ValueError(f"{what} {tuple(x.shape if hasattr(x, 'shape') else np.shape(x))} does not match prot: expected {shape}")
+    _call.check_shapes((("res_mask", res_mask, (s_a, n_a)), ("res_mask_b", res_mask_b, (s_b, n)), ("score_mask", score_mask, score_rows),
+                        ("atom_mask_a", atom_mask_a, (s_a, n_a, atoms_a)), ("atom_mask_b", atom_mask_b, (s_b, n, atoms_b))), mapped)
+    if mapped:
+        alignment = _call.check_map(alignment, n_pairs, n, n_a)
     ints = ("n_scored", "n_passed", "status")
     outputs = {key: ("float64", (n_pairs,)) for key in PER_PAIR}
     outputs.update({key: ("float64", (n_pairs, n)) for key in PER_ROW})
@@ -123,84 +125,32 @@ def local_accuracy(prot_a, prot_b=None, atoms: str = "ca", res_mask=None, score_
     else:
         import torch
         dev, (xa, xb) = _call.upload("local_accuracy", prot_a=prot_a, prot_b=prot_b)
-
-        def atom_mask(x, shape, what):
-            m = _call.per_row(x, shape, what, "mask", dev=dev)
-            return None if m is None else m.to(torch.uint8).contiguous()
-
-        mask_a = atom_mask(atom_mask_a, (s_a, n, atoms_a), "atom_mask_a")
-        mask_b = mask_a if prot_b is None else atom_mask(atom_mask_b, (s_b, n, atoms_b), "atom_mask_b")
-        out = _call.run("fdipt_sample_lddt", _lib.LddtArgs, dev,
-                        dict(S=s_a, N=n, atoms=atoms_a, S_b=s_b, atoms_b=atoms_b, P=n_pairs, mode=MODES[atoms], same_residue=int(bool(same_residue)),
-                             cutoff=float(cutoff)),
-                        dict(prot=xa, prot_b=xb, res_mask=_call.per_row(res_mask, (s_a, n), "res_mask", "mask", default=1, dev=dev),
-                             score_mask=_call.per_row(score_mask, (s_a, n), "score_mask", "mask", default=1, dev=dev), atom_mask_a=mask_a,
-                             atom_mask_b=mask_b, pairs=torch.from_numpy(pair_list).to(dev)),
-                        outputs, widen=ints, workspace=("fdipt_sample_lddt_workspace", n_pairs, n))
+        mask_a = _call.atom_mask(atom_mask_a, (s_a, n_a, atoms_a), "atom_mask_a", dev)
+        mask_b = mask_a if prot_b is None else _call.atom_mask(atom_mask_b, (s_b, n, atoms_b), "atom_mask_b", dev)
+        scored = _call.per_row(score_mask, score_rows, "score_mask", "mask", default=1, dev=dev)
+        entry = "fdipt_sample_lddt_mapped" if mapped else "fdipt_sample_lddt"
+        call = (entry, _lib.LddtArgs, dev,
+                dict(S=s_a, N=n, atoms=atoms_a, S_b=s_b, atoms_b=atoms_b, P=n_pairs, mode=MODES[atoms], same_residue=int(bool(same_residue)),
+                     cutoff=float(cutoff)),
+                dict(prot=xa, prot_b=xb, res_mask=_call.per_row(res_mask, (s_a, n_a), "res_mask", "mask", default=1, dev=dev),
+                     score_mask=None if mapped else scored, atom_mask_a=mask_a, atom_mask_b=mask_b, pairs=torch.from_numpy(pair_list).to(dev)),
+                outputs)
+        if mapped:
+            out = _call.run_mapped(*call, dict(N_a=n_a, coverage=COVERAGE[coverage], map=_call.upload_map(alignment, n_pairs, n, dev),
+                                               res_mask_b=_call.per_row(res_mask_b, (s_b, n), "res_mask_b", "mask", default=1, dev=dev), score_mask_b=scored),
+                                   widen=ints, workspace=(entry + "_workspace", n_pairs, n))
+        else:
+            out = _call.run(*call, widen=ints, workspace=(entry + "_workspace", n_pairs, n))
     out["pairs"] = pair_list.astype(np.int64)
     out["atoms"] = atoms
+    if mapped:
+        _call.add_coverage(out, n_pairs)
     if square:
         out["matrix"] = np.ones((s_a, s_a), dtype=np.float64)
         out["drmsd_matrix"] = np.zeros((s_a, s_a), dtype=np.float64)
         out["matrix"][pair_list[:, 0], pair_list[:, 1]] = out["lddt"]
         out["drmsd_matrix"][pair_list[:, 0], pair_list[:, 1]] = out["drmsd"]
         out["consensus"] = consensus(out["res_lddt"], pair_list, s_a)
-    return out
-
-
-def _mapped_accuracy(prot_a, prot_b, atoms, res_mask, score_mask, atom_mask_a, atom_mask_b, pairs, ref_index, cutoff, same_residue, per_atom, alignment,
-                     coverage, res_mask_b) -> dict:
-    """``local_accuracy`` with an alignment: one call of ``fdipt_sample_lddt_mapped``."""
-    if coverage not in COVERAGE:
-        raise ValueError(f"coverage should be 'ignore' or 'penalise', got {coverage!r}")
-    if prot_b is None:
-        raise ValueError("an alignment maps the rows of prot_b to those of prot_a: prot_b is required")
-    s_a, n_a, atoms_a = _shape(prot_a, "prot_a")
-    s_b, n_b, atoms_b = _shape(prot_b, "prot_b")
-    for what, layout in (("prot_a", atoms_a), ("prot_b", atoms_b)):
-        if (atoms == "all" and layout != 37) or (atoms == "backbone" and layout == 1):
-            raise ValueError(f"atoms={atoms!r} needs {'atom37' if atoms == 'all' else 'the backbone atoms'}: {what} holds {layout} atom(s) per row")
-    if not cutoff > 0:
-        raise ValueError(f"cutoff should be positive, got {cutoff}")
-    pair_list, _ = _call.plan_pairs(s_a, s_b, True, pairs, ref_index)
-    n_pairs, k = len(pair_list), SET_ATOMS[atoms]
-    checks = (("res_mask", res_mask, (s_a, n_a)), ("res_mask_b", res_mask_b, (s_b, n_b)), ("score_mask", score_mask, (s_b, n_b)),
-              ("atom_mask_a", atom_mask_a, (s_a, n_a, atoms_a)), ("atom_mask_b", atom_mask_b, (s_b, n_b, atoms_b)))
-    for what, x, shape in checks:
-        if x is not None and tuple(x.shape if hasattr(x, "shape") else np.shape(x)) != shape:
-            raise ValueError(f"{what} {tuple(x.shape if hasattr(x, 'shape') else np.shape(x))} does not match its structure: expected {shape}")
-    alignment = _call.check_map(alignment, n_pairs, n_b, n_a)
-    ints = ("n_scored", "n_passed", "status")
-    outputs = {key: ("float64", (n_pairs,)) for key in PER_PAIR}
-    outputs.update({key: ("float64", (n_pairs, n_b)) for key in PER_ROW})
-    outputs.update(n_scored=("int32", (n_pairs, n_b)), n_passed=("int32", (n_pairs, n_b, 4)), status=("int32", (n_pairs,)))
-    if per_atom:
-        outputs["atom_lddt"] = ("float64", (n_pairs, n_b, k))
-    if n_pairs == 0:
-        out = _call.empty_outputs(outputs, ints)
-        out.update(n_covered=np.zeros(0, dtype=np.int64), n_reference=np.zeros(0, dtype=np.int64))
-    else:
-        import torch
-        dev, (xa, xb) = _call.upload("local_accuracy", prot_a=prot_a, prot_b=prot_b)
-
-        def atom_mask(x, shape, what):
-            m = _call.per_row(x, shape, what, "mask", dev=dev)
-            return None if m is None else m.to(torch.uint8).contiguous()
-
-        out = _call.run_mapped("fdipt_sample_lddt_mapped", _lib.LddtArgs, dev,
-                               dict(S=s_a, N=n_b, atoms=atoms_a, S_b=s_b, atoms_b=atoms_b, P=n_pairs, mode=MODES[atoms], same_residue=int(bool(same_residue)),
-                                    cutoff=float(cutoff)),
-                               dict(prot=xa, prot_b=xb, res_mask=_call.per_row(res_mask, (s_a, n_a), "res_mask", "mask", default=1, dev=dev),
-                                    atom_mask_a=atom_mask(atom_mask_a, (s_a, n_a, atoms_a), "atom_mask_a"),
-                                    atom_mask_b=atom_mask(atom_mask_b, (s_b, n_b, atoms_b), "atom_mask_b"), pairs=torch.from_numpy(pair_list).to(dev)),
-                               outputs,
-                               dict(N_a=n_a, coverage=COVERAGE[coverage], map=_call.upload_map(alignment, n_pairs, n_b, dev),
-                                    res_mask_b=_call.per_row(res_mask_b, (s_b, n_b), "res_mask_b", "mask", default=1, dev=dev),
-                                    score_mask_b=_call.per_row(score_mask, (s_b, n_b), "score_mask", "mask", default=1, dev=dev)),
-                               widen=ints, workspace=("fdipt_sample_lddt_mapped_workspace", n_pairs, n_b))
-    out["coverage"] = np.divide(out["n_covered"], out["n_reference"], out=np.zeros(n_pairs), where=out["n_reference"] > 0)
-    out["pairs"] = pair_list.astype(np.int64)
-    out["atoms"] = atoms
     return out
 
 

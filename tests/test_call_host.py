@@ -118,6 +118,40 @@ def test_per_row_mismatch_names_the_input_and_both_shapes(kind):
         _call.per_row(np.zeros((2, 3)), (2, 3, 5), "atom_mask", kind)
 
 
+def test_check_shapes_keeps_both_message_tails_and_needs_no_torch(monkeypatch):
+    import sys
+    monkeypatch.setitem(sys.modules, "torch", None)  # (an import of torch would raise)
+    wrong = np.ones((2, 9))
+    checks = (("res_mask", None, (1, 7)), ("res_mask_b", wrong, (1, 9)), ("atom_mask_b", np.ones((3, 3)), (1, 9, 5)))  # (the first mismatch is named)
+    with pytest.raises(ValueError, match=r"res_mask_b \(2, 9\) does not match prot: expected \(1, 9\)"):
+        _call.check_shapes(checks)
+    with pytest.raises(ValueError, match=r"res_mask_b \(2, 9\) does not match its structure: expected \(1, 9\)"):
+        _call.check_shapes(checks, mapped=True)
+    with pytest.raises(ValueError, match=r"res_mask_b \(2, 9\) does not match"):
+        _call.check_shapes((("res_mask_b", wrong.tolist(), [1, 9]),))          # a nested list has a shape too; the expected shape may be a list
+    _call.check_shapes((("res_mask", None, (1, 7)), ("res_mask_b", wrong, (2, 9))))
+    _call.check_shapes(())
+
+
+def test_the_folded_entries_keep_each_message_tail_where_it_was(monkeypatch):
+    import sys
+    monkeypatch.setitem(sys.modules, "torch", None)  # (an import of torch would raise)
+    from framedipt_amd import interface, lddt
+    wrong = np.ones((2, 9))
+    a, b, side = np.ones((1, 7, 3), np.float32), np.ones((1, 9, 3), np.float32), np.array([1] * 4 + [2] * 5)
+    for call in (lambda **kw: interface.interface_accuracy(a, b, side, atoms="ca", **kw), lambda **kw: lddt.local_accuracy(a, b, **kw)):
+        with pytest.raises(ValueError, match=r"res_mask_b \(2, 9\) does not match its structure: expected \(1, 9\)"):
+            call(alignment=np.full(9, -1), res_mask_b=wrong)
+    with pytest.raises(ValueError, match=r"res_mask_b \(2, 9\) does not match prot: expected \(1, 9\)"):
+        interface.interface_accuracy(b, b, side, atoms="ca", res_mask_b=wrong)
+
+
+def test_add_coverage_and_its_result_without_a_call():
+    assert _call.add_coverage({"n_covered": np.array([2, 0]), "n_reference": np.array([4, 0])}, 2)["coverage"].tolist() == [0.5, 0.0]
+    empty = _call.add_coverage({}, 0)
+    assert {k: (v.dtype, v.shape) for k, v in empty.items()} == {k: (np.dtype(t), (0,)) for k, t in (("n_covered", "int64"), ("n_reference", "int64"), ("coverage", "float64"))}
+
+
 def test_outputs_without_a_call():
     spec = {"tm": ("float64", (0,)), "rotation": ("float64", (0, 3, 3)), "status": ("int32", (0,))}
     out = _call.empty_outputs(spec, widen=("status",))

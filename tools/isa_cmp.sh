@@ -9,7 +9,7 @@ set -u
 [ $# -ge 2 ] || { sed -n 2,7p "$0"; exit 2; }
 A=$(cd "$1" && pwd); B=$(cd "$2" && pwd); shift 2
 CSRC=framedipt_amd/csrc
-if [ $# -gt 0 ]; then UNITS="$*"; else UNITS=$(sed -n 's/^for f in \(.*\); do$/\1/p' "$B/$CSRC/build.sh"); fi
+if [ $# -gt 0 ]; then UNITS="$*"; else UNITS=$(sed -n 's/^UNITS="\(.*\)"$/\1/p' "$B/$CSRC/build.sh"); fi
 FLAGS=$(sed -n 's/^FLAGS="\(.*\) \$EXTRA"$/\1/p' "$B/$CSRC/build.sh")
 [ -n "$UNITS" ] && [ -n "$FLAGS" ] || { echo "cannot read the unit list / FLAGS from $B/$CSRC/build.sh" >&2; exit 2; }
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}; OUT=${ISA_CMP_OUT:-/tmp/isa_cmp}; JOBS=${ISA_CMP_JOBS:-8}
