@@ -32,15 +32,15 @@ _H = _read_header()
 # every FDIPT_<NAME> integer macro as <NAME>: PREC_*, KF_* (FdiptDims.kernel_flags), SELECT_* and EVAL_* (limits and status bits),
 # VIOLATION_CONSTANTS, DSSP_* (class codes, the bridge slots of a row, status bits), TM_* and TMA_* (the row limits, status bits), SEARCH_* (the
 # largest top_k, status bits, the ranking), MPNN_* (limits,
-# status bits), LDDT_* (atom sets, tile sizes, status bits), GDT_* (modes, the number of cutoffs, status bits), MAP_* (the coverage switch and the status bits of a row map), SEQ_* (sequence alignment: limits, status bits), IFACE_* (interface accuracy: atom sets, sides, limits, tile sizes, flags, status bits), the E* return codes
+# status bits), LDDT_* (atom sets, tile sizes, status bits), GDT_* (modes, the number of cutoffs, status bits), MAP_* (the coverage switch and the status bits of a row map), SEQ_* (sequence alignment: limits, status bits, modes, free-end bits), IFACE_* (interface accuracy: atom sets, sides, limits, tile sizes, flags, status bits), the E* return codes
 globals().update(_H.macros)
 _ERR = {_H.macros["EINVAL"]: "FDIPT_EINVAL (bad argument)", _H.macros["ELAUNCH"]: "FDIPT_ELAUNCH (HIP launch error)",
         _H.macros["ESIZE"]: "FDIPT_ESIZE (workspace too small or N beyond the compiled tiling: N <= 1024, N <= 2048 with KF_STREAM_ATTN in the fp16 mode; "
                             "sample selection: a group of more than 64 samples; inverse folding: N > 2048 or more than 64 sequences; sequence alignment: a length > 2048; interface accuracy: N > 2048 or more than 64 interfaces)"}
 
-Dims, ForwardArgs, ReverseIndexed, SelectArgs, EvalArgs, ViolationArgs, DsspArgs, SasaArgs, TmArgs, TmAlignArgs, SearchArgs, MpnnDims, MpnnArgs, LddtArgs, GdtArgs, RowMap, SeqAlignArgs, InterfaceArgs = (
+Dims, ForwardArgs, ReverseIndexed, SelectArgs, EvalArgs, ViolationArgs, DsspArgs, SasaArgs, TmArgs, TmAlignArgs, SearchArgs, MpnnDims, MpnnArgs, LddtArgs, GdtArgs, RowMap, SeqAlignArgs, SeqAlignModeArgs, InterfaceArgs = (
     _H.structs["Fdipt" + n] for n in ("Dims", "ForwardArgs", "ReverseIndexed", "SelectArgs", "EvalArgs", "ViolationArgs", "DsspArgs", "SasaArgs", "TmArgs",
-                                      "TmAlignArgs", "SearchArgs", "MpnnDims", "MpnnArgs", "LddtArgs", "GdtArgs", "RowMap", "SeqAlignArgs", "InterfaceArgs"))
+                                      "TmAlignArgs", "SearchArgs", "MpnnDims", "MpnnArgs", "LddtArgs", "GdtArgs", "RowMap", "SeqAlignArgs", "SeqAlignModeArgs", "InterfaceArgs"))
 for _cls, _doc in ((ReverseIndexed, "one reverse step addressed through a device-side step cursor."),
                    (SelectArgs, "sample selection over G groups of the B samples of one atom37 array."),
                    (EvalArgs, "evaluation of B samples against R ground-truth structures."),
@@ -56,6 +56,7 @@ for _cls, _doc in ((ReverseIndexed, "one reverse step addressed through a device
                    (GdtArgs, "GDT-TS / GDT-HA of P pairs of structures: no, one global or a searched superposition per cutoff."),
                    (RowMap, "the row map of the mapped accuracy entries: the model row of every reference row, per pair."),
                    (SeqAlignArgs, "global sequence alignment with affine gaps (Gotoh) of P pairs of sequences."),
+                   (SeqAlignModeArgs, "sequence alignment with a mode (global, semi-global with free end gaps, local) of P pairs of sequences."),
                    (InterfaceArgs, "interface accuracy (contacts, fnat, iRMSD, LRMSD, DockQ) of P pairs of structures on I interfaces.")):
     _cls.__doc__ = f"Fdipt{_cls.__name__} (include/fdipt.h): {_doc}"
 

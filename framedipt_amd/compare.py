@@ -48,7 +48,8 @@ def sequence_aligned_accuracy(prot_a, aatype_a, prot_b, aatype_b, chain_a=None, 
                               pairs=None, ref_index=None, atoms: str = "ca", coverage: str = "penalise", superpose: str = "search", **scoring) -> dict:
     """prot_a [S,N_a,37 or 5,3]: the models, which share the residue types aatype_a [N_a] and the chain labels chain_a [N_a]; prot_b
     [S_b,N_b,37 or 5,3]: the references with aatype_b [N_b], chain_b [N_b].  The rows are matched by ``seq_align.chain_row_map`` (chains
-    with equal labels, or ``chain_pairs``; ``scoring``: its ``matrix``, ``open_gap``, ``extend_gap``), and the one map serves every pair of
+    with equal labels, or ``chain_pairs``; ``scoring``: its ``matrix``, ``open_gap``, ``extend_gap``, ``mode``, ``free_ends``, ``exclude_a``,
+    ``exclude_b`` - ``mode="semiglobal", free_ends="a"`` for a reference that lacks termini), and the one map serves every pair of
     ``local_accuracy(..., alignment=, coverage=)`` and ``gdt_scores(..., alignment=, norm_length="reference")``.
 
     Returns ``alignment`` [N_b], ``chains`` and per chain pair ``score``, ``identity``, ``identity_b``, ``n_identical``, ``n_aligned``,
@@ -78,7 +79,8 @@ def sequence_aligned_interface(prot_a, aatype_a, prot_b, aatype_b, chain_a, chai
     """The docking question for a model from another tool, or a ground truth read from its own file: prot_a [S,N_a,...] are the models
     with residue types aatype_a [N_a] and chain labels chain_a [N_a]; prot_b [S_b,N_b,...] the references with aatype_b, chain_b [N_b].
     The rows are matched by ``seq_align.chain_row_map`` (chains with equal labels, or ``chain_pairs`` [(label_a, label_b)]; ``scoring``:
-    its ``matrix``, ``open_gap``, ``extend_gap``) - the model may store its chains in another order, the map is then not monotone -, the
+    its ``matrix``, ``open_gap``, ``extend_gap``, ``mode``, ``free_ends``, ``exclude_a``, ``exclude_b``) - the model may store its chains in
+    another order, the map is then not monotone -, the
     interfaces are ``interface.chain_sides(chain_b, interfaces)`` (``interfaces``: pairs of the REFERENCE's chain labels; default: every
     pair), and ``interface.interface_accuracy(..., alignment=, coverage=)`` scores every pair of structures in one call.  The sibling of
     ``sequence_aligned_accuracy``; no parity with the DockQ program is claimed.

@@ -14,7 +14,7 @@ if [ -n "${FDIPT_CLEAN:-}" ]; then rm -f "$BUILD"/*.o "$OUT/$LIBNAME"; fi
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 # -Wno-inline-asm: the LDS-DMA helpers name m0 (a reserved register hipcc re-materialises before each of its own uses) as clobbered
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result -Wno-inline-asm $EXTRA"
-UNITS="gemm ipa_proj2 pair_mlp edge_embed2 edge_transition3 edge_transition4 attention attention3 pair_bias attention_seq chain rowblock frames select evaluate violations dssp sasa tmscore tmalign structsearch mpnn lddt lddt_mapped gdt gdt_mapped seqalign interface interface_mapped model"
+UNITS="gemm ipa_proj2 pair_mlp edge_embed2 edge_transition3 edge_transition4 attention attention3 pair_bias attention_seq chain rowblock frames select evaluate violations dssp sasa tmscore tmalign structsearch mpnn lddt lddt_mapped gdt gdt_mapped seqalign seqalign_modes interface interface_mapped model"
 pids=()
 T0=$SECONDS
 NCOMP=0

@@ -11,42 +11,9 @@
 // traceback: a byte per cell (2 bits each: the predecessor state of M, of X, of Y) goes to the wave's slab in the workspace, diagonal by
 // diagonal and packed, so a chunk's 64 bytes are contiguous; lane 0 walks the path back, counts it and writes the map.
 // score only: the path's counts (identical | aligned in one word, gap runs in 16 bits) ride with every state under the same choices.
-#include "common.hpp"
+#include "seqalign_common.hpp"
 
-#define SQ_NEG (-(1 << 30))  // unreachable; |reachable| < 2^27 and |every sum with it| < 2^31 under FDIPT_SEQ_MAX_HALF_UNITS
-#define SQ_TABLE_BYTES 1792  // 21 * 21 int32, padded to a multiple of 16
-#define SQ_LDS_MAX (160 * 1024)
-
-struct SqLayout {
-  int L1;          // indices i = 0 .. max_len_a, rounded up to a multiple of 4
-  int LA, LB;      // letters of a and of b, rounded likewise
-  int wave_bytes;  // of one wave's region, a multiple of 16
-};
-static inline __host__ __device__ SqLayout sq_layout(int max_a, int max_b, bool trace) {
-  SqLayout l;
-  l.L1 = (max_a + 1 + 3) & ~3, l.LA = (max_a + 3) & ~3, l.LB = (max_b + 3) & ~3;
-  // scores of M, X, Y, G; then (trace) G's state byte, or (score only) a count word and a run count per state
-  const int bytes = 4 * l.L1 * 4 + (trace ? l.L1 : 4 * l.L1 * 4 + 4 * l.L1 * 2) + l.LA + l.LB;
-  l.wave_bytes = (bytes + 15) & ~15;
-  return l;
-}
-
-// LDS writes of one step become visible to the other lanes' reads of the next: the wave runs in lockstep and its LDS operations complete
-// in order, so what is needed is that the compiler keeps the order
-__device__ __forceinline__ void sq_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// cells (i >= 1, j >= 1) of the diagonals before d = i + j, of a la x lb pair: where the direction bytes of diagonal d start in the slab
-__device__ __forceinline__ int sq_diag_offset(int d, int la, int lb) {
-  const int t = d - 2, mn = la < lb ? la : lb, mx = la < lb ? lb : la;
-  if (t <= mn) return t * (t + 1) / 2;
-  if (t <= mx) return mn * (mn + 1) / 2 + (t - mn) * mn;
-  const int r = la + lb - 1 - t;
-  return la * lb - r * (r + 1) / 2;
-}
+#define SQ_EXTRA 24  // score only, per index: a count word and a 16-bit run count for each of M, X, Y, G
 
 template <bool TRACE>
 __global__ __launch_bounds__(FD_THREADS) void seq_align_kernel(FdiptSeqAlignArgs a, int W, int wpb) {
@@ -56,7 +23,7 @@ __global__ __launch_bounds__(FD_THREADS) void seq_align_kernel(FdiptSeqAlignArgs
   for (int k = tid; k < FDIPT_SEQ_LETTERS * FDIPT_SEQ_LETTERS; k += blockDim.x) T[k] = a.table[k];
   __syncthreads();  // the only block barrier: from here on a wave is on its own
 
-  const SqLayout lay = sq_layout(a.max_len_a, a.max_len_b, TRACE);
+  const SqLayout lay = sq_layout(a.max_len_a, a.max_len_b, TRACE, SQ_EXTRA);
   const int L1 = lay.L1;
   char* base = sq_smem + SQ_TABLE_BYTES + (size_t)wave * lay.wave_bytes;
   int *Ms = (int*)base, *Xs = Ms + L1, *Ys = Xs + L1, *Gs = Ys + L1;
@@ -201,27 +168,8 @@ __global__ __launch_bounds__(FD_THREADS) void seq_align_kernel(FdiptSeqAlignArgs
   }
 }
 
-// waves of a block, its dynamic LDS, and the persistent waves of a launch over P pairs
-static int sq_plan(int P, int max_a, int max_b, bool trace, int& wpb, size_t& lds) {
-  const SqLayout lay = sq_layout(max_a, max_b, trace);
-  wpb = FD_THREADS / FD_WAVE;
-  while (wpb > 1 && SQ_TABLE_BYTES + (size_t)wpb * lay.wave_bytes > 64 * 1024) wpb >>= 1;
-  lds = SQ_TABLE_BYTES + (size_t)wpb * lay.wave_bytes;
-  if (lds > SQ_LDS_MAX) return 0;
-  const int blocks = (int)(SQ_LDS_MAX / lds) < 8 ? (int)(SQ_LDS_MAX / lds) : 8;
-  const int per_cu = blocks * wpb < 16 ? blocks * wpb : 16;
-  const long waves = (long)fd_cu_count() * per_cu;
-  return (int)(waves < P ? waves : P);
-}
-
 extern "C" size_t fdipt_seq_align_workspace_bytes(int P, int max_len_a, int max_len_b, int traceback, size_t max_workspace_bytes) {
-  if (!traceback || P < 1 || max_len_a < 1 || max_len_b < 1 || max_len_a > FDIPT_SEQ_MAX_ROWS || max_len_b > FDIPT_SEQ_MAX_ROWS) return 0;
-  int wpb;
-  size_t lds;
-  const size_t slab = (size_t)max_len_a * max_len_b;
-  size_t waves = (size_t)sq_plan(P, max_len_a, max_len_b, true, wpb, lds);
-  if (waves > max_workspace_bytes / slab) waves = max_workspace_bytes / slab;
-  return (waves < 1 ? 1 : waves) * slab;
+  return sq_workspace_bytes(P, max_len_a, max_len_b, traceback, max_workspace_bytes, SQ_EXTRA);
 }
 
 template <bool TRACE>
@@ -248,7 +196,7 @@ extern "C" int fdipt_seq_align(const FdiptSeqAlignArgs* a, fdipt_stream_t stream
   if (a->max_len_a > a->N_a || a->max_len_b > (a->seq_b ? a->N_b : a->N_a)) return FDIPT_EINVAL;
   int wpb;
   size_t lds;
-  int W = sq_plan(a->P, a->max_len_a, a->max_len_b, a->traceback != 0, wpb, lds);
+  int W = sq_plan(a->P, a->max_len_a, a->max_len_b, a->traceback != 0, SQ_EXTRA, wpb, lds);
   if (W < 1) return FDIPT_ESIZE;
   const size_t slab = (size_t)a->max_len_a * a->max_len_b;
   if (a->traceback && slab) {

@@ -869,11 +869,12 @@ def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, 
     return summary
 
 
-def write_seq_diversity(out_dir: str, owners, matrix, scoring: dict):
+def write_seq_diversity(out_dir: str, owners, matrix, scoring: dict, matrix_file: str = "pairwise_seq_identity.npy"):
     """``pairwise_seq_identity.npy`` (``matrix`` [Q,Q]: ``identity_short`` of every pair of designed sequences, unit diagonal) and
     ``seq_diversity.json``: ``owners`` [(sample stem, index among the sample's sequences)] in the matrix's order, the mean off-diagonal
     identity, per sample the largest identity of one of its sequences to a sequence of ANOTHER sample (None for a lone sample), and the
-    scoring parameters.  Returns the summary written."""
+    scoring parameters.  ``matrix_file``: the matrix file's name (``run_seq_diversity`` names the mode in it unless it is global).  Returns
+    the summary written."""
     matrix = np.asarray(matrix, dtype=np.float64)
     q = len(owners)
     stems = [o[0] for o in owners]
@@ -888,17 +889,19 @@ def write_seq_diversity(out_dir: str, owners, matrix, scoring: dict):
                "mean_identity": float(matrix[off].mean()) if q > 1 else None,
                "mean_identity_between_samples": float(matrix[other].mean()) if other.any() else None,
                "max_identity_to_other_sample": nearest, "identity": "n_identical / min(len_a, len_b)", "scoring": scoring,
-               "matrix": "pairwise_seq_identity.npy"}
-    np.save(os.path.join(out_dir, "pairwise_seq_identity.npy"), matrix)
+               "matrix": matrix_file}
+    np.save(os.path.join(out_dir, matrix_file), matrix)
     with open(os.path.join(out_dir, "seq_diversity.json"), "w") as f:
         json.dump(summary, f, indent=1)
     return summary
 
 
-def run_seq_diversity(out_dir: str, records, gathered: dict, matrix="blosum62", open_gap: float = -10.0, extend_gap: float = -0.5):
+def run_seq_diversity(out_dir: str, records, gathered: dict, matrix="blosum62", open_gap: float = -10.0, extend_gap: float = -0.5, mode: str = "global"):
     """Rank 0, after ``run_design`` (``--design --seq-diversity``, de novo runs; framedipt_amd/seq_align.py): every designed sequence of
     every sample (``designed_sequences`` of the gathered entries, which ``run_design`` leaves there) against every other in ONE
-    score-only launch of the global alignment - the lengths may differ - then ``write_seq_diversity``."""
+    score-only launch of the alignment - the lengths may differ - then ``write_seq_diversity``.  ``mode`` (``--seq-align-mode``): "global",
+    or "local" / "semiglobal" (every end gap free) for sequences that share a motif or overlap; these write
+    ``pairwise_seq_identity_<mode>.npy`` and leave the global file alone."""
     from . import seq_align
     owners, seqs = [], []
     for r in records:
@@ -908,9 +911,13 @@ def run_seq_diversity(out_dir: str, records, gathered: dict, matrix="blosum62", 
             seqs.append(seq)
     if not seqs:
         raise ValueError("--seq-diversity needs designed sequences: run_design has left none on the gathered entries")
-    found = seq_align.align_sequences(seqs, matrix=matrix, open_gap=open_gap, extend_gap=extend_gap, traceback=False)
-    scoring = {"matrix": matrix if isinstance(matrix, str) else "custom", "open_gap": float(open_gap), "extend_gap": float(extend_gap), "mode": "global"}
-    return write_seq_diversity(out_dir, owners, found["matrix"], scoring)
+    found = seq_align.align_sequences(seqs, matrix=matrix, open_gap=open_gap, extend_gap=extend_gap, traceback=False, mode=mode)
+    scoring = {"matrix": matrix if isinstance(matrix, str) else "custom", "open_gap": float(open_gap), "extend_gap": float(extend_gap), "mode": mode}
+    if mode == "global":
+        return write_seq_diversity(out_dir, owners, found["matrix"], scoring)
+    if mode == "semiglobal":
+        scoring["free_ends"] = "all"
+    return write_seq_diversity(out_dir, owners, found["matrix"], scoring, matrix_file=f"pairwise_seq_identity_{mode}.npy")
 
 
 def reference_layout_writer(out_dir: str, net, final_only: bool):
@@ -1054,6 +1061,8 @@ def main():
     ap.add_argument("--seq-diversity", action="store_true", help="--design, de novo runs: rank 0 then aligns all designed sequences of all samples all-against-all on "
                     "its GPU (framedipt_amd/seq_align.py: global alignment, BLOSUM62, open -10, extend -0.5, score only) and writes pairwise_seq_identity.npy "
                     "and seq_diversity.json")
+    ap.add_argument("--seq-align-mode", default="global", choices=("global", "local", "semiglobal"), help="--seq-diversity: the alignment mode; local (the best "
+                    "shared stretch) and semiglobal (every end gap free: overlaps) write pairwise_seq_identity_<mode>.npy and record the mode in seq_diversity.json")
     ap.add_argument("--novelty", default=None, metavar="SET.npz", help="de novo runs: after the run, rank 0 searches every final sample in the structure set "
                     "(framedipt_amd/structure_search.py: StructureSet.save) on its GPU and keeps the largest TM-score of the hits, the reference's pdbTM: "
                     "novelty.json, novelty.csv.  The query is the sample itself, not an ESMFold refold, and the search is this project's own: no parity "
@@ -1080,6 +1089,8 @@ def main():
         ap.error("--novelty-accuracy needs --novelty SET.npz")
     if a.seq_diversity and (not a.design or a.download_dir is not None):
         ap.error("--seq-diversity compares the designed sequences of a de novo run: it needs --design and no --download-dir")
+    if a.seq_align_mode != "global" and not a.seq_diversity:
+        ap.error("--seq-align-mode is the mode of --seq-diversity")
     if a.novelty and not 1 <= a.novelty_top_k <= 64:
         ap.error(f"--novelty-top-k {a.novelty_top_k}: expected 1 .. 64")
 
@@ -1256,9 +1267,9 @@ def main():
                   f"in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/seqs/<sample>.fa, design.json", flush=True)
             if a.seq_diversity:
                 t1 = time.perf_counter()
-                done = run_seq_diversity(a.out_dir, allrecs, gathered)
+                done = run_seq_diversity(a.out_dir, allrecs, gathered, mode=a.seq_align_mode)
                 print(f"sequence identity of {done['n_sequences']} designed sequence(s), all against all, in {time.perf_counter() - t1:.2f} s -> "
-                      f"{a.out_dir}/pairwise_seq_identity.npy, seq_diversity.json", flush=True)
+                      f"{a.out_dir}/{done['matrix']}, seq_diversity.json", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -12,8 +12,13 @@ Among equal candidates the first of M, X, Y wins (this project's own rule).  The
 maps are offset into whole-structure rows - the layout ``lddt.local_accuracy(..., alignment=)`` and ``gdt.gdt_scores(..., alignment=)``
 read (``compare.sequence_aligned_accuracy`` does the three calls).  ``row_map.from_residue_numbers`` is the counterpart by numbering.
 
-Not built: local and semi-global modes, free end gaps, other built-in tables, the reference's ``exclude_region`` (``row_map.push_mask``
-serves that purpose for the mapped entries).
+``mode="semiglobal"`` (chosen end gaps free: ``free_ends``) and ``mode="local"`` go through ``fdipt_seq_align_modes``
+(csrc/seqalign_modes.hip) and say where the charged path lies: ``begin_a``, ``end_a``, ``begin_b``, ``end_b``.  The
+same claim holds for them - the score only, against ``PairwiseAligner`` with ``mode = "local"`` or with its end-gap scores set to 0 on the
+matching sides; the rules that choose among equal end cells are this project's own.  ``chain_row_map(exclude_a=, exclude_b=)`` is the
+reference's ``exclude_region``, on the host.
+
+Not built: other built-in tables, per-pair modes in one launch, distinct end-gap penalties other than 0.
 """
 from __future__ import annotations
 
@@ -25,8 +30,12 @@ from .output import RESTYPES
 MAX_ROWS = _lib.SEQ_MAX_ROWS
 LETTERS = RESTYPES + "X"  # aatype 0 .. 20
 X = 20
-EMPTY, BAD_LETTER, SKIPPED = _lib.SEQ_EMPTY, _lib.SEQ_BAD_LETTER, _lib.SEQ_SKIPPED
+EMPTY, BAD_LETTER, SKIPPED, NO_ALIGNED = _lib.SEQ_EMPTY, _lib.SEQ_BAD_LETTER, _lib.SEQ_SKIPPED, _lib.SEQ_NO_ALIGNED
+MODES = {"global": _lib.SEQ_MODE_GLOBAL, "semiglobal": _lib.SEQ_MODE_SEMIGLOBAL, "local": _lib.SEQ_MODE_LOCAL}
+FREE_ENDS = {"a_left": _lib.SEQ_FREE_A_LEFT, "a_right": _lib.SEQ_FREE_A_RIGHT, "b_left": _lib.SEQ_FREE_B_LEFT, "b_right": _lib.SEQ_FREE_B_RIGHT}
+_FREE_SHORTHANDS = {"a": ("a_left", "a_right"), "b": ("b_left", "b_right"), "all": tuple(FREE_ENDS)}
 _COUNTS = ("n_aligned", "n_identical", "n_gaps_a", "n_gaps_b", "n_gap_runs")
+_SPAN = ("begin_a", "end_a", "begin_b", "end_b")
 _INTS = ("score",) + _COUNTS + ("alignment", "status")
 _MAX_WHOLE = _lib.SEQ_MAX_HALF_UNITS // 2
 
@@ -148,8 +157,31 @@ def _upload(dev, x):
     return (x.to(dev) if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).to(dev)).to(torch.int32).contiguous()
 
 
+def free_end_bits(mode: str, free_ends) -> int:
+    """The ``FDIPT_SEQ_FREE_*`` bits of ``free_ends`` under ``mode``: names out of ``FREE_ENDS`` (an iterable), or the shorthands "a"
+    (both ends of a free: b is fitted into a), "b" and "all" (an overlap alignment; the default of ``semiglobal``).  ValueError for an
+    unknown mode or name, and for ``free_ends`` with another mode than "semiglobal"."""
+    if not isinstance(mode, str) or mode not in MODES:
+        raise ValueError(f"mode should be one of {sorted(MODES)}, got {mode!r}")
+    if mode != "semiglobal":
+        if free_ends is not None:
+            raise ValueError(f"free_ends belongs to mode='semiglobal', got mode={mode!r}")
+        return 0
+    if free_ends is None:
+        free_ends = "all"
+    names = _FREE_SHORTHANDS.get(free_ends, (free_ends,)) if isinstance(free_ends, str) else tuple(free_ends)
+    unknown = [n for n in names if not isinstance(n, str) or n not in FREE_ENDS]
+    if unknown:
+        raise ValueError(f"free_ends should be 'a', 'b', 'all' or names out of {sorted(FREE_ENDS)}, got {unknown}")
+    bits = 0
+    for n in names:
+        bits |= FREE_ENDS[n]
+    return bits
+
+
 def align_sequences(seq_a, seq_b=None, len_a=None, len_b=None, pairs=None, ref_index=None, matrix="blosum62", open_gap: float = -10.0,
-                    extend_gap: float = -0.5, traceback: bool = True, max_workspace_bytes: int = 2 ** 30) -> dict:
+                    extend_gap: float = -0.5, traceback: bool = True, max_workspace_bytes: int = 2 ** 30, mode: str = "global",
+                    free_ends=None) -> dict:
     """seq_a: sequences as an integer array or device tensor [S,N_a] (aatype, 20 = X; ``len_a`` [S]: their lengths, default N_a), a list of
     one-letter strings (a letter outside the twenty becomes X) or a ragged list of integer rows (padded here).  seq_b, len_b: the second
     side likewise, or None.  Pairs as ``tm_align`` plans them: ``pairs`` [P,2]; no seq_b and no ref_index: all i < j of seq_a (the result
@@ -162,7 +194,16 @@ def align_sequences(seq_a, seq_b=None, len_a=None, len_b=None, pairs=None, ref_i
     Returns per pair ``score`` (float64, whole units), ``n_aligned``, ``n_identical`` (equal letters, X excluded), ``n_gaps_a`` /
     ``n_gaps_b`` (gap positions in a / in b), ``n_gap_runs``, ``alignment`` [P,N_b] (the row of a aligned with each row of b, or -1),
     ``status`` (EMPTY, BAD_LETTER, SKIPPED), ``identity`` = n_identical / n_aligned, ``identity_b`` = n_identical / len_b,
-    ``identity_short`` = n_identical / min(len_a, len_b) (0 where the divisor is 0), ``len_a``, ``len_b`` and ``pairs`` [P,2]."""
+    ``identity_short`` = n_identical / min(len_a, len_b) (0 where the divisor is 0), ``len_a``, ``len_b`` and ``pairs`` [P,2].
+
+    ``mode``: "global" (end gaps charged like inner gaps; ``fdipt_seq_align``), "semiglobal" or "local" (``fdipt_seq_align_modes``,
+    DESIGN.md section 7.20).  ``free_ends`` (semiglobal only; ``free_end_bits``): which end gaps cost nothing - names out of
+    ``FREE_ENDS``, "a" (b is fitted into a), "b", or "all" (the default: an overlap alignment).  Every mode adds the span of the charged
+    path, ``begin_a``, ``end_a``, ``begin_b``, ``end_b`` (global: 0, len_a, 0, len_b, formed here) - it aligns a[begin_a:end_a] with
+    b[begin_b:end_b] globally, the counts are those of the span and ``alignment`` is -1 outside it -, ``mode``, ``identity_span_b`` =
+    n_identical / (end_b - begin_b) and ``coverage_b`` = (end_b - begin_b) / len_b.  The two new modes set NO_ALIGNED in ``status`` where
+    the result has no aligned column (an empty local result, a semi-global optimum of free runs only)."""
+    bits = free_end_bits(mode, free_ends)
     table = table_half_units(matrix)
     o, e = half_units(open_gap, "open_gap"), half_units(extend_gap, "extend_gap")
     if int(max_workspace_bytes) < 0:
@@ -176,9 +217,10 @@ def align_sequences(seq_a, seq_b=None, len_a=None, len_b=None, pairs=None, ref_i
     n_pairs = len(pair_list)
     if n_pairs and (pair_list.min() < 0 or pair_list[:, 0].max() >= s_a or pair_list[:, 1].max() >= s_b):
         raise ValueError(f"pairs should index {s_a} and {s_b} sequences")
-    outputs = {k: ("int32", (n_pairs, n_b) if k == "alignment" else (n_pairs,)) for k in _INTS if traceback or k != "alignment"}
+    ints = _INTS if mode == "global" else _INTS + _SPAN
+    outputs = {k: ("int32", (n_pairs, n_b) if k == "alignment" else (n_pairs,)) for k in ints if traceback or k != "alignment"}
     if n_pairs == 0:
-        out = _call.empty_outputs(outputs, _INTS)
+        out = _call.empty_outputs(outputs, ints)
     else:
         import torch
         tensors = [x for x in (xa, xb) if torch.is_tensor(x)]
@@ -189,15 +231,26 @@ def align_sequences(seq_a, seq_b=None, len_a=None, len_b=None, pairs=None, ref_i
         dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
         max_a, max_b = int(la.max()), int(lb.max())
         da = _upload(dev, xa)
-        out = _call.run("fdipt_seq_align", _lib.SeqAlignArgs, dev,
-                        dict(S_a=s_a, N_a=n_a, S_b=s_b, N_b=n_b, P=n_pairs, max_len_a=max_a, max_len_b=max_b, open_gap=o, extend_gap=e, traceback=int(bool(traceback))),
+        scalars = dict(S_a=s_a, N_a=n_a, S_b=s_b, N_b=n_b, P=n_pairs, max_len_a=max_a, max_len_b=max_b, open_gap=o, extend_gap=e, traceback=int(bool(traceback)))
+        entry, struct = ("fdipt_seq_align", _lib.SeqAlignArgs) if mode == "global" else ("fdipt_seq_align_modes", _lib.SeqAlignModeArgs)
+        if mode != "global":
+            scalars.update(mode=MODES[mode], free_ends=bits)
+        out = _call.run(entry, struct, dev, scalars,
                         dict(seq_a=da, len_a=_upload(dev, la), seq_b=None if seq_b is None else _upload(dev, xb), len_b=None if seq_b is None else _upload(dev, lb),
                              pairs=torch.from_numpy(pair_list).to(dev), table=_upload(dev, table)),
-                        outputs, widen=_INTS,
-                        workspace=("fdipt_seq_align_workspace_bytes", n_pairs, max_a, max_b, int(bool(traceback)), int(max_workspace_bytes)))
+                        outputs, widen=ints,
+                        workspace=(entry + "_workspace_bytes", n_pairs, max_a, max_b, int(bool(traceback)), int(max_workspace_bytes)))
     out["score"] = out["score"].astype(np.float64) / 2.0
     out["len_a"], out["len_b"] = la[pair_list[:, 0]].astype(np.int64), lb[pair_list[:, 1]].astype(np.int64)
+    if mode == "global":  # the whole of both sequences, for every pair the device served
+        served = (out["status"] & (EMPTY | SKIPPED)) == 0
+        out.update(begin_a=np.zeros(n_pairs, dtype=np.int64), end_a=np.where(served, out["len_a"], 0), begin_b=np.zeros(n_pairs, dtype=np.int64),
+                   end_b=np.where(served, out["len_b"], 0))
+    out["mode"] = mode
     out.update(identities(out["n_identical"], out["n_aligned"], out["len_a"], out["len_b"]))
+    span_b = (out["end_b"] - out["begin_b"]).astype(np.float64)
+    out["identity_span_b"] = np.divide(out["n_identical"], span_b, out=np.zeros(n_pairs), where=span_b > 0)
+    out["coverage_b"] = np.divide(span_b, out["len_b"], out=np.zeros(n_pairs), where=out["len_b"] > 0)
     out["pairs"] = pair_list.astype(np.int64)
     if square:
         out["matrix"] = _call.square_matrix(s_a, pair_list, out["identity_short"])
@@ -260,22 +313,58 @@ def assemble_map(plan, alignments, n_b: int) -> np.ndarray:
     return out
 
 
-def chain_row_map(aatype_a, chain_a, aatype_b, chain_b, chain_pairs=None, **scoring) -> dict:
+def _regions(exclude, n: int, what: str):
+    """``exclude`` as one inclusive (start, end) per chain pair, (-1, -1) for None - the reference's default, which holds no row."""
+    if exclude is None:
+        return [(-1, -1)] * n
+    regions = [(-1, -1) if r is None else tuple(int(v) for v in r) for r in exclude]
+    if len(regions) != n or any(len(r) != 2 for r in regions):
+        raise ValueError(f"{what} should hold one inclusive (start, end) or None for each of the {n} chain pairs, got {exclude!r}")
+    return regions
+
+
+def drop_excluded(alignments, exclude_a, exclude_b):
+    """The reference's ``exclude_region`` on per-chain maps (rows relative to each chain): an aligned column whose row of a lies inside the
+    pair's region of a is dropped from the map; its row of b must then lie inside the region of b - ValueError otherwise, as
+    get_shared_residues_info raises.  The converse is not checked, as there.  Returns (maps, n_excluded [pairs])."""
+    maps, dropped = [], np.zeros(len(alignments), dtype=np.int64)
+    for k, (m, (sa, ea), (sb, eb)) in enumerate(zip(alignments, exclude_a, exclude_b)):
+        m = np.array(m, dtype=np.int64)
+        inside = (m >= 0) & (sa <= m) & (m <= ea)
+        rows_b = np.flatnonzero(inside)
+        if np.any((rows_b < sb) | (rows_b > eb)):
+            raise ValueError(f"chain pair {k}: a row of a inside its excluded region {(sa, ea)} is aligned with a row of b outside {(sb, eb)}; "
+                             "both chains should have the same excluded region")
+        m[inside] = -1
+        maps.append(m)
+        dropped[k] = int(inside.sum())
+    return maps, dropped
+
+
+def chain_row_map(aatype_a, chain_a, aatype_b, chain_b, chain_pairs=None, exclude_a=None, exclude_b=None, **scoring) -> dict:
     """The reference's per-chain procedure (framedipt/protein/align.py:get_shared_residues_info): aatype_a [N_a] and aatype_b [N_b] (integers,
     or one-letter strings) with chain labels chain_a [N_a], chain_b [N_b] (None: one chain).  The chains with equal labels, or the listed
     ``chain_pairs`` [(label_a, label_b)], are aligned in one launch; ``scoring``: ``matrix``, ``open_gap``, ``extend_gap``,
-    ``max_workspace_bytes`` of ``align_sequences``.
+    ``max_workspace_bytes``, ``mode`` and ``free_ends`` of ``align_sequences`` (``mode="semiglobal", free_ends="a"`` fits a reference chain
+    that lacks termini into the model's; a chain pair without an aligned column, NO_ALIGNED, leaves its rows at -1).
+    ``exclude_a``, ``exclude_b``: the reference's ``exclude_region`` - per chain pair one inclusive (start, end) in rows relative to the
+    chain, or None; ``drop_excluded`` applies them to the maps, the per-pair counts stay those of the alignment before.
 
     Returns ``alignment`` [N_b] (the row of a for each row of b, -1 for a gap and for every row of an unpaired chain), ``chains`` (the label
-    pairs) and per chain pair ``score``, ``identity``, ``identity_b``, ``identity_short``, ``n_aligned``, ``n_identical``, ``n_gaps_a``,
-    ``n_gaps_b``, ``n_gap_runs``, ``status``."""
+    pairs) and per chain pair ``score``, ``identity``, ``identity_b``, ``identity_short``, ``identity_span_b``, ``coverage_b``,
+    ``n_aligned``, ``n_identical``, ``n_gaps_a``, ``n_gaps_b``, ``n_gap_runs``, ``begin_a``, ``end_a``, ``begin_b``, ``end_b`` (relative to the
+    chains), ``n_excluded``, ``status``."""
     a = encode(aatype_a) if isinstance(aatype_a, str) else np.asarray(_call.host(aatype_a)).reshape(-1)
     b = encode(aatype_b) if isinstance(aatype_b, str) else np.asarray(_call.host(aatype_b)).reshape(-1)
+    free_end_bits(scoring.get("mode", "global"), scoring.get("free_ends"))
     plan = plan_chains(chain_a, len(a), chain_b, len(b), chain_pairs)
-    keys = ("score", "identity", "identity_b", "identity_short", "status") + _COUNTS
+    regions_a, regions_b = _regions(exclude_a, len(plan), "exclude_a"), _regions(exclude_b, len(plan), "exclude_b")
+    floats = ("score", "identity", "identity_b", "identity_short", "identity_span_b", "coverage_b")
+    keys = floats + ("status",) + _COUNTS + _SPAN
     if not plan:
-        out = {k: np.zeros(0, dtype=np.float64 if k in ("score",) or k.startswith("identity") else np.int64) for k in keys}
-        return dict(out, alignment=np.full(len(b), -1, dtype=np.int32), chains=[])
+        out = {k: np.zeros(0, dtype=np.float64 if k in floats else np.int64) for k in keys}
+        return dict(out, n_excluded=np.zeros(0, dtype=np.int64), alignment=np.full(len(b), -1, dtype=np.int32), chains=[])
     found = align_sequences([a[s:e] for _, _, (s, e), _ in plan], [b[s:e] for _, _, _, (s, e) in plan], traceback=True, **scoring)
     out = {k: found[k] for k in keys}
-    return dict(out, alignment=assemble_map(plan, found["alignment"], len(b)), chains=[(ca, cb) for ca, cb, _, _ in plan])
+    maps, out["n_excluded"] = drop_excluded([m[:e - s] for m, (_, _, _, (s, e)) in zip(found["alignment"], plan)], regions_a, regions_b)
+    return dict(out, alignment=assemble_map(plan, maps, len(b)), chains=[(ca, cb) for ca, cb, _, _ in plan])

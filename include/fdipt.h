@@ -1008,6 +1008,69 @@ size_t fdipt_seq_align_workspace_bytes(int P, int max_len_a, int max_len_b, int 
  * workspace below one slab. */
 int fdipt_seq_align(const FdiptSeqAlignArgs* args, fdipt_stream_t stream);
 
+/* ---------------------------------------------------------------- sequence alignment: modes (opt-in) */
+/* The alignment above with a mode: global, semi-global (chosen end gaps free) or local (Smith-Waterman with the same three states).
+ * Units, table, penalties, states and the tie rule inside a cell are those above; the contract is DESIGN.md section 7.20.  A path is
+ * a sequence of M / X / Y steps, a run a maximal stretch of one state; X is a letter of a against a gap, Y a letter of b.
+ * SEMIGLOBAL, free_ends a set of FDIPT_SEQ_FREE_* bits: the global score, except that the first run costs 0 if it is X with A_LEFT or Y
+ * with B_LEFT and the last run costs 0 if it is X with A_RIGHT or Y with B_RIGHT (only the first and the last run can be free).  The
+ * cells [i,0] are corners (M = 0, X and Y unreachable) with A_LEFT, the cells [0,j] with B_LEFT; the end cell is chosen among [la,lb],
+ * every [i,lb] with i < la (A_RIGHT) and every [la,j] with j < lb (B_RIGHT), each over its three states: score descending, then i + j
+ * descending, then i descending, then the first of M, X, Y.  The charged path runs from the end cell back to the first corner it
+ * reaches, or to [0,0]; a leading gap that is not free is walked and counted.  free_ends = 0 is GLOBAL.
+ * LOCAL: M[i,j] = T[a_i,b_j] + max(0, max(M, X, Y)[i-1,j-1]), the fresh start taken where that maximum is <= 0; X and Y as above; no
+ * boundary scores.  The end cell is the inner cell with the largest M: score descending, then i + j ascending, then i ascending; the
+ * path runs back to its fresh start.  No cell with M > 0: the empty result (zeros, a map of -1, a span of zeros).
+ * The charged path aligns a[begin_a:end_a] with b[begin_b:end_b] globally; the counts are those of the charged path (n_gaps_b = end_a -
+ * begin_a - n_aligned, n_gaps_a = end_b - begin_b - n_aligned), alignment is -1 outside the span.  status: the bits above (a length of 0
+ * stays FDIPT_SEQ_EMPTY alone), and FDIPT_SEQ_NO_ALIGNED on every other pair whose result has no aligned column, in every mode.
+ * traceback == 0: the counts and the origin (12 + 12 bits per state) ride through the recurrence; every output but alignment is the
+ * same number. */
+#define FDIPT_SEQ_NO_ALIGNED 8       /* status: the result has no aligned column (an empty local result, free runs only, gaps only)  */
+#define FDIPT_SEQ_MODE_GLOBAL 0
+#define FDIPT_SEQ_MODE_SEMIGLOBAL 1
+#define FDIPT_SEQ_MODE_LOCAL 2
+#define FDIPT_SEQ_FREE_A_LEFT 1      /* free_ends: a leading run of letters of a against gaps costs nothing                           */
+#define FDIPT_SEQ_FREE_A_RIGHT 2     /* a trailing run of letters of a                                                               */
+#define FDIPT_SEQ_FREE_B_LEFT 4      /* a leading run of letters of b                                                                */
+#define FDIPT_SEQ_FREE_B_RIGHT 8     /* a trailing run of letters of b                                                               */
+typedef struct FdiptSeqAlignModeArgs {
+  int32_t S_a, N_a;                  /* as FdiptSeqAlignArgs, field by field                                                        */
+  int32_t S_b, N_b;
+  int32_t P;
+  int32_t max_len_a, max_len_b;
+  int32_t open_gap, extend_gap;
+  int32_t traceback;
+  int32_t mode;                      /* FDIPT_SEQ_MODE_*                                                                            */
+  int32_t free_ends;                 /* FDIPT_SEQ_FREE_* bits; 0 unless mode is FDIPT_SEQ_MODE_SEMIGLOBAL                           */
+  const int32_t* seq_a;
+  const int32_t* len_a;
+  const int32_t* seq_b;
+  const int32_t* len_b;
+  const int32_t* pairs;
+  const int32_t* table;
+  /* outputs: [P] i32 */
+  int32_t* score;
+  int32_t* n_aligned;
+  int32_t* n_identical;
+  int32_t* n_gaps_a;                 /* charged Y steps                                                                             */
+  int32_t* n_gaps_b;                 /* charged X steps                                                                             */
+  int32_t* n_gap_runs;               /* charged runs                                                                                */
+  int32_t* begin_a;                  /* the origin [begin_a, begin_b] and the end cell [end_a, end_b] of the charged path           */
+  int32_t* end_a;
+  int32_t* begin_b;
+  int32_t* end_b;
+  int32_t* alignment;                /* [P,N_b] i32 (traceback)                                                                     */
+  int32_t* status;
+  void* workspace;
+  size_t workspace_bytes;
+} FdiptSeqAlignModeArgs;
+/* the slab rule of fdipt_seq_align_workspace_bytes */
+size_t fdipt_seq_align_modes_workspace_bytes(int P, int max_len_a, int max_len_b, int traceback, size_t max_workspace_bytes);
+/* One launch.  FDIPT_EINVAL: what fdipt_seq_align refuses, a null span output, an unknown mode, free_ends outside 0 .. 15, free_ends
+ * != 0 with another mode than FDIPT_SEQ_MODE_SEMIGLOBAL.  FDIPT_ESIZE: as fdipt_seq_align. */
+int fdipt_seq_align_modes(const FdiptSeqAlignModeArgs* args, fdipt_stream_t stream);
+
 /* ---------------------------------------------------------------- interface accuracy (opt-in) */
 /* Contacts across an interface, fnat, fnonnat, interface RMSD, ligand RMSD and DockQ (Basu & Wallner 2016: the formula, not the
  * program) of P pairs (model structure a, reference structure b) in row correspondence, each on the I interfaces of the call; float32

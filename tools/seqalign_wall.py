@@ -6,9 +6,13 @@
 
 Prints per load the wall time of the calls (device tensors in, NumPy results out; the first call on its own), the time of the launch
 between device-side events, the persistent waves the workspace cap produced (traceback), and beside it - as a yardstick, not a claim - the
-wall time of the NumPy restatement (tests/seqalign_ref.py) on a sample of the same pairs, scaled to the load.
+wall time of the NumPy restatement (tests/seqalign_ref.py) on a sample of the same pairs, scaled to the load.  ``sclk_mhz``: the shader
+clock the driver reports during further calls of the load (tools/interface_wall.py: ``sclk_while``; null where it cannot be read).
 
-    python tools/seqalign_wall.py [out.json]
+``--mode local`` / ``--mode semiglobal`` (every end gap free) time the same four loads through fdipt_seq_align_modes (DESIGN.md section
+7.20; the restatement beside them is tests/seqalign_modes_ref.py); the default is the global entry.
+
+    python tools/seqalign_wall.py [--mode {global,local,semiglobal}] [out.json]
 """
 import json
 import os
@@ -21,13 +25,25 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import seqalign_modes_ref  # noqa: E402
 import seqalign_ref  # noqa: E402
 from framedipt_amd import _lib, seq_align  # noqa: E402
+from interface_wall import sclk_while  # noqa: E402  (tools/: the shader clock the driver reports while a load runs)
+
+MODE = "global"
+if "--mode" in sys.argv:
+    k = sys.argv.index("--mode")
+    MODE = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
+if MODE not in seq_align.MODES:
+    sys.exit(f"--mode should be one of {sorted(seq_align.MODES)}")
+ENTRY = "fdipt_seq_align" if MODE == "global" else "fdipt_seq_align_modes"
 
 lib = _lib.load()
 events = []
-launch = lib.fdipt_seq_align
+launch = getattr(lib, ENTRY)
 
 
 def timed(*args):
@@ -39,7 +55,7 @@ def timed(*args):
     return rc
 
 
-lib.fdipt_seq_align = timed
+setattr(lib, ENTRY, timed)
 
 
 def measure(fn, repeats):
@@ -60,20 +76,24 @@ def restatement_wall(seqs_a, seqs_b, pairs, sample):
     rows = pairs[np.linspace(0, len(pairs) - 1, sample).astype(int)]
     t0 = time.perf_counter()
     for i, j in rows:
-        seqalign_ref.align(seqs_a[i], seqs_b[j], table, -20, -1)
+        if MODE == "global":
+            seqalign_ref.align(seqs_a[i], seqs_b[j], table, -20, -1)
+        else:
+            seqalign_modes_ref.align(seqs_a[i], seqs_b[j], table, -20, -1, seq_align.MODES[MODE], 15 if MODE == "semiglobal" else 0)
     return (time.perf_counter() - t0) / len(rows)
 
 
 def load(name, xa, xb, repeats, sample, **kw):
     dev = torch.device("cuda", torch.cuda.current_device())
     da, db = torch.from_numpy(xa).to(dev), None if xb is None else torch.from_numpy(xb).to(dev)
-    res, walls, device_ms = measure(lambda: seq_align.align_sequences(da, db, **kw), repeats)
+    res, walls, device_ms = measure(lambda: seq_align.align_sequences(da, db, mode=MODE, **kw), repeats)
     n_pairs = len(res["pairs"])
     traceback = kw.get("traceback", True)
     slab = xa.shape[1] * (xa if xb is None else xb).shape[1]
-    waves = int(lib.fdipt_seq_align_workspace_bytes(n_pairs, xa.shape[1], (xa if xb is None else xb).shape[1], 1, 2 ** 30)) // slab if traceback else None
+    waves = int(getattr(lib, ENTRY + "_workspace_bytes")(n_pairs, xa.shape[1], (xa if xb is None else xb).shape[1], 1, 2 ** 30)) // slab if traceback else None
+    sclk = sclk_while(lambda: [seq_align.align_sequences(da, db, mode=MODE, **kw) for _ in range(repeats)])
     per_pair = restatement_wall(xa, xa if xb is None else xb, res["pairs"], sample)
-    out = {"pairs": n_pairs, "traceback": traceback, "first_call_wall_s": walls[0], "call_wall_s": walls[1:], "device_ms": device_ms,
+    out = {"mode": MODE, "pairs": n_pairs, "traceback": traceback, "first_call_wall_s": walls[0], "call_wall_s": walls[1:], "device_ms": device_ms[:repeats], "sclk_mhz": sclk,
            "persistent_waves_of_the_slabs": waves, "mean_identity_short": float(res["identity_short"].mean()),
            "restatement_s_per_pair": per_pair, "restatement_s_scaled_to_load": per_pair * n_pairs}
     print(name, json.dumps(out), flush=True)
