@@ -1,299 +1,31 @@
 // seqalign_modes.hip — sequence alignment with a mode: global, semi-global (chosen end gaps free) and local, for P pairs of sequences:
-// fdipt_seq_align_modes (include/fdipt.h, "sequence alignment: modes").  int32 arithmetic in half units, exact.
+// fdipt_seq_align_modes (include/fdipt.h, "sequence alignment: modes").
 //
-// The design is seqalign.hip's, whose two kernels serve fdipt_seq_align with unchanged device code (the layout, the fence, the slab
-// offset and the launch plan are shared: seqalign_common.hpp): one persistent wave per pair,
-// the anti-diagonals IN PLACE in LDS indexed by i (before diagonal d, M/X/Y[i] hold cell (i, d-1-i) and G[i] holds max(M, X, Y) of cell
-// (i, d-2-i)), 2-bit directions in the wave's slab, lane 0 walks the path back.  What a mode adds:
-// * the boundary: a free left end makes the cells of column 0 (A_LEFT) or row 0 (B_LEFT) corners, M = 0; local has no boundary scores;
-// * local: M adds its table entry to max(0, G); the fresh start (G <= 0) is M's predecessor code 3;
-// * the end cell is a choice.  Every lane keeps a running best over the candidates it meets - the cells of the last row as it computes
-//   them (B_RIGHT), every inner cell's M (local) - and after the last diagonal over the last column, which survives in LDS because
-//   index i holds cell (i, lb) then (A_RIGHT; the cell (la, lb) is always a candidate).  A butterfly reduces the bests under the mode's
-//   key; a candidate is one cell, met by one lane, so the winner is unique and nothing depends on the order.  The bests are reset for
-//   every pair a wave serves;
-// * score only: beside the counts every state carries its origin (begin_a << 12 | begin_b), set at a corner or a fresh start and
-//   inherited under the same choices; a lane's best carries the counts and the origin of its candidate, and the winning lane writes.
-#include "seqalign_common.hpp"
-
-#define SQM_NONE (-2147483647 - 1)
-#define SQM_EXTRA 40  // score only, per index: a count word, an origin word and a 16-bit run count for each of M, X, Y, G
-
-// a candidate end cell: state st of cell (i, d - i) with score s; score only: its counts, gap runs and origin
-struct SqmBest {
-  int s, d, i, st;
-  unsigned c, r, o;
-};
-// the end-cell keys.  local: score descending, then i + j ascending, then i ascending; else: score, i + j and i descending, then M, X, Y
-template <int MODE>
-__device__ __forceinline__ bool sqm_better(int s, int d, int i, int st, const SqmBest& b) {
-  if (s != b.s) return s > b.s;
-  if (MODE == FDIPT_SEQ_MODE_LOCAL) return d != b.d ? d < b.d : i < b.i;
-  if (d != b.d) return d > b.d;
-  return i != b.i ? i > b.i : st < b.st;
-}
-template <int MODE>
-__device__ __forceinline__ void sqm_offer(SqmBest& b, int s, int d, int i, int st, unsigned c, unsigned r, unsigned o) {
-  if (sqm_better<MODE>(s, d, i, st, b)) b.s = s, b.d = d, b.i = i, b.st = st, b.c = c, b.r = r, b.o = o;
-}
+// The kernels are seqalign_body.hpp's, in its policies SQ_ENDS (semi-global; without a flag that is the global mode, so one
+// instantiation serves both) and SQ_LOCAL: the end cell is a choice, and the result carries the span of the charged path.
+#include "seqalign_body.hpp"
 
 template <int MODE, bool TRACE>
 __global__ __launch_bounds__(FD_THREADS) void seq_align_modes_kernel(FdiptSeqAlignModeArgs a, int W, int wpb) {
-  constexpr bool LOCAL = MODE == FDIPT_SEQ_MODE_LOCAL;
-  extern __shared__ __attribute__((aligned(16))) char sqm_smem[];
-  int* T = (int*)sqm_smem;
-  const int tid = threadIdx.x, lane = tid & (FD_WAVE - 1), wave = tid / FD_WAVE;
-  for (int k = tid; k < FDIPT_SEQ_LETTERS * FDIPT_SEQ_LETTERS; k += blockDim.x) T[k] = a.table[k];
-  __syncthreads();  // the only block barrier: from here on a wave is on its own
-
-  const SqLayout lay = sq_layout(a.max_len_a, a.max_len_b, TRACE, SQM_EXTRA);
-  const int L1 = lay.L1;
-  char* base = sqm_smem + SQ_TABLE_BYTES + (size_t)wave * lay.wave_bytes;
-  int *Ms = (int*)base, *Xs = Ms + L1, *Ys = Xs + L1, *Gs = Ys + L1;
-  char* more = (char*)(Gs + L1);
-  unsigned char* Gd = (unsigned char*)more;                                     // TRACE: the state G took
-  unsigned *Mc = (unsigned*)more, *Xc = Mc + L1, *Yc = Xc + L1, *Gc = Yc + L1;  // score only: identical << 16 | aligned
-  unsigned *Mo = Gc + L1, *Xo = Mo + L1, *Yo = Xo + L1, *Go = Yo + L1;          // score only: begin_a << 12 | begin_b
-  unsigned short *Mr = (unsigned short*)(Go + L1), *Xr = Mr + L1, *Yr = Xr + L1, *Gr = Yr + L1;  // score only: gap runs
-  unsigned char* sa = (unsigned char*)more + (TRACE ? L1 : L1 * SQM_EXTRA);
-  unsigned char* sb = sa + lay.LA;
-
-  const int w = blockIdx.x * wpb + wave;
-  if (w >= W) return;  // (the last block's spare waves: a slab belongs to one wave)
-  const int Sb = a.seq_b ? a.S_b : a.S_a, Nb = a.seq_b ? a.N_b : a.N_a;
-  const int32_t* seq_b = a.seq_b ? a.seq_b : a.seq_a;
-  const int32_t* len_b = a.seq_b ? a.len_b : a.len_a;
-  unsigned char* slab = TRACE ? (unsigned char*)a.workspace + (size_t)w * a.max_len_a * a.max_len_b : nullptr;
-  const int o = a.open_gap, e = a.extend_gap;
-  const int fe = MODE == FDIPT_SEQ_MODE_SEMIGLOBAL ? a.free_ends : 0;
-  const bool a_left = fe & FDIPT_SEQ_FREE_A_LEFT, a_right = fe & FDIPT_SEQ_FREE_A_RIGHT;
-  const bool b_left = fe & FDIPT_SEQ_FREE_B_LEFT, b_right = fe & FDIPT_SEQ_FREE_B_RIGHT;
-
-  for (long p = w; p < a.P; p += W) {
-    sq_wave_sync();  // (the walk of the last pair has read its letters)
-    const int ia = a.pairs[2 * p], ib = a.pairs[2 * p + 1];
-    const bool found = ia >= 0 && ia < a.S_a && ib >= 0 && ib < Sb;
-    int la = found ? a.len_a[ia] : -1, lb = found ? len_b[ib] : -1;
-    int status = 0;
-    if (la < 0 || lb < 0 || la > a.max_len_a || lb > a.max_len_b || la > a.N_a || lb > Nb) status = FDIPT_SEQ_SKIPPED;
-    else if (la == 0 || lb == 0) status = FDIPT_SEQ_EMPTY;
-    bool bad = false;
-    if (!status) {
-      for (int i = lane; i < la; i += FD_WAVE) {
-        int c = a.seq_a[(long)ia * a.N_a + i];
-        if (c < 0 || c >= FDIPT_SEQ_LETTERS) c = FDIPT_SEQ_LETTERS - 1, bad = true;
-        sa[i] = (unsigned char)c;
-      }
-      for (int j = lane; j < lb; j += FD_WAVE) {
-        int c = seq_b[(long)ib * Nb + j];
-        if (c < 0 || c >= FDIPT_SEQ_LETTERS) c = FDIPT_SEQ_LETTERS - 1, bad = true;
-        sb[j] = (unsigned char)c;
-      }
-      if (__ballot(bad) != 0ull) status |= FDIPT_SEQ_BAD_LETTER;
-    }
-
-    SqmBest best = {SQM_NONE, -1, -1, 0, 0u, 0u, 0u};  // reset for every pair
-    if (!(status & (FDIPT_SEQ_SKIPPED | FDIPT_SEQ_EMPTY))) {
-      for (int d = 0; d <= la + lb; ++d) {
-        const int lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
-        const int off = TRACE && d >= 2 ? sq_diag_offset(d, la, lb) - (d - lb > 1 ? d - lb : 1) : 0;  // + i: the cell's byte
-        for (int k = (hi - lo) / FD_WAVE; k >= 0; --k) {
-          const int i = lo + k * FD_WAVE + lane, j = d - i;
-          const bool on = i <= hi, inner = on && i >= 1 && j >= 1;
-          sq_wave_sync();
-          int m = SQ_NEG, x = SQ_NEG, y = SQ_NEG, g = SQ_NEG, gs = 0;
-          unsigned mc = 0, xc = 0, yc = 0, gc = 0, mr = 0, xr = 1, yr = 1, gr = 0, mo = 0, xo = 0, yo = 0, go = 0;
-          unsigned dir = 0;
-          if (inner) {
-            const int m1 = Ms[i - 1], x1 = Xs[i - 1], y1 = Ys[i - 1], m0 = Ms[i], x0 = Xs[i], y0 = Ys[i];
-            const int ca = sa[i - 1], cb = sb[j - 1];
-            // G of cell (i, j-1), for M[i+1, j] two diagonals on
-            g = m0, gs = 0;
-            if (x0 > g) g = x0, gs = 1;
-            if (y0 > g) g = y0, gs = 2;
-            const int g1 = Gs[i - 1];
-            const bool fresh = LOCAL && g1 <= 0;  // the fresh start wins the tie
-            const int dm = fresh ? 3 : TRACE ? Gd[i - 1] : 0;
-            m = (fresh ? 0 : g1) + T[ca * FDIPT_SEQ_LETTERS + cb];
-            int dx = 0, dy = 0;
-            x = m1 + o;
-            if (x1 + e > x) x = x1 + e, dx = 1;
-            if (y1 + o > x) x = y1 + o, dx = 2;
-            y = m0 + o;
-            if (x0 + o > y) y = x0 + o, dy = 1;
-            if (y0 + e > y) y = y0 + e, dy = 2;
-            dir = (unsigned)(dm | dx << 2 | dy << 4);
-            if (!TRACE) {
-              const unsigned c0[3] = {Mc[i], Xc[i], Yc[i]}, r0[3] = {Mr[i], Xr[i], Yr[i]}, o0[3] = {Mo[i], Xo[i], Yo[i]};
-              const unsigned c1[3] = {Mc[i - 1], Xc[i - 1], Yc[i - 1]}, r1[3] = {Mr[i - 1], Xr[i - 1], Yr[i - 1]}, o1[3] = {Mo[i - 1], Xo[i - 1], Yo[i - 1]};
-              gc = gs == 0 ? c0[0] : gs == 1 ? c0[1] : c0[2], gr = gs == 0 ? r0[0] : gs == 1 ? r0[1] : r0[2];
-              go = gs == 0 ? o0[0] : gs == 1 ? o0[1] : o0[2];
-              mc = (fresh ? 0u : Gc[i - 1]) + 1u + (ca == cb && ca != FDIPT_SEQ_LETTERS - 1 ? 0x10000u : 0u);
-              mr = fresh ? 0u : Gr[i - 1], mo = fresh ? (unsigned)((i - 1) << 12 | (j - 1)) : Go[i - 1];
-              xc = dx == 0 ? c1[0] : dx == 1 ? c1[1] : c1[2], xr = (dx == 0 ? r1[0] : dx == 1 ? r1[1] : r1[2]) + (dx != 1);
-              xo = dx == 0 ? o1[0] : dx == 1 ? o1[1] : o1[2];
-              yc = dy == 0 ? c0[0] : dy == 1 ? c0[1] : c0[2], yr = (dy == 0 ? r0[0] : dy == 1 ? r0[1] : r0[2]) + (dy != 2);
-              yo = dy == 0 ? o0[0] : dy == 1 ? o0[1] : o0[2];
-            }
-            if (LOCAL) sqm_offer<MODE>(best, m, d, i, 0, mc, mr, mo);
-          } else if (on && !LOCAL) {  // row 0 and column 0
-            if (d == 0) {
-              m = 0;
-            } else if (j == 0) {
-              if (a_left) m = 0, mo = (unsigned)(i << 12);  // a corner
-              else x = o + (i - 1) * e;
-            } else if (b_left) {  // i == 0: the corners (0, j) and (0, j-1)
-              m = 0, mo = (unsigned)j, g = 0, gs = 0, go = (unsigned)(j - 1);
-            } else {
-              y = o + (j - 1) * e;
-              // G of cell (0, j-1): M at the corner, Y beyond it
-              g = j == 1 ? 0 : o + (j - 2) * e, gs = j == 1 ? 0 : 2, gr = j == 1 ? 0 : 1;
-            }
-          }
-          if (!LOCAL && b_right && on && i == la && j < lb) {  // a candidate of the last row
-            int s = m, st = 0;
-            if (x > s) s = x, st = 1;
-            if (y > s) s = y, st = 2;
-            sqm_offer<MODE>(best, s, d, i, st, st == 0 ? mc : st == 1 ? xc : yc, st == 0 ? mr : st == 1 ? xr : yr, st == 0 ? mo : st == 1 ? xo : yo);
-          }
-          sq_wave_sync();  // every read of the chunk is done
-          if (on) {
-            Ms[i] = m, Xs[i] = x, Ys[i] = y, Gs[i] = g;
-            if (TRACE) {
-              Gd[i] = (unsigned char)gs;
-              if (inner) slab[off + i] = (unsigned char)dir;
-            } else {
-              Mc[i] = mc, Xc[i] = xc, Yc[i] = yc, Gc[i] = gc;
-              Mo[i] = mo, Xo[i] = xo, Yo[i] = yo, Go[i] = go;
-              Mr[i] = (unsigned short)mr, Xr[i] = (unsigned short)xr, Yr[i] = (unsigned short)yr, Gr[i] = (unsigned short)gr;
-            }
-          }
-        }
-      }
-      sq_wave_sync();
-      if (!LOCAL)  // the last column: index i holds cell (i, lb); the cell (la, lb) always, the others with A_RIGHT
-        for (int i = lane; i <= la; i += FD_WAVE) {
-          if (i < la && !a_right) continue;
-          int s = Ms[i], st = 0;
-          if (Xs[i] > s) s = Xs[i], st = 1;
-          if (Ys[i] > s) s = Ys[i], st = 2;
-          unsigned c = 0, r = 0, og = 0;
-          if (!TRACE) c = st == 0 ? Mc[i] : st == 1 ? Xc[i] : Yc[i], r = st == 0 ? Mr[i] : st == 1 ? Xr[i] : Yr[i], og = st == 0 ? Mo[i] : st == 1 ? Xo[i] : Yo[i];
-          sqm_offer<MODE>(best, s, i + lb, i, st, c, r, og);
-        }
-    }
-    // the wave's best: afterwards every lane holds the winner's key, and the lane that met it also its counts
-    SqmBest win = best;
-#pragma unroll
-    for (int mask = 1; mask < FD_WAVE; mask <<= 1) {
-      const int s = __shfl_xor(win.s, mask, FD_WAVE), d = __shfl_xor(win.d, mask, FD_WAVE), i = __shfl_xor(win.i, mask, FD_WAVE), st = __shfl_xor(win.st, mask, FD_WAVE);
-      if (sqm_better<MODE>(s, d, i, st, win)) win.s = s, win.d = d, win.i = i, win.st = st;
-    }
-    if (win.d < 0 || (LOCAL && win.s <= 0)) {  // (wave-uniform) SKIPPED, EMPTY, or the empty local result
-      if (TRACE)
-        for (int j = lane; j < Nb; j += FD_WAVE) a.alignment[p * Nb + j] = -1;
-      if (lane == 0) {
-        a.score[p] = 0, a.n_aligned[p] = 0, a.n_identical[p] = 0, a.n_gaps_a[p] = 0, a.n_gaps_b[p] = 0, a.n_gap_runs[p] = 0;
-        a.begin_a[p] = 0, a.end_a[p] = 0, a.begin_b[p] = 0, a.end_b[p] = 0;
-        a.status[p] = win.d < 0 ? status : status | FDIPT_SEQ_NO_ALIGNED;
-      }
-      continue;
-    }
-    const int ei = win.i, ej = win.d - win.i;
-    if (TRACE) {
-      for (int j = ej + lane; j < Nb; j += FD_WAVE) a.alignment[p * Nb + j] = -1;  // (rows begin_b .. end_b-1 are the walk's)
-      __threadfence();  // the slab's bytes, written by every lane, are lane 0's to read
-      int bi = 0, bj = 0, aligned = 0, identical = 0, runs = 0;
-      if (lane == 0) {
-        int32_t* map = a.alignment + p * Nb;
-        int i = ei, j = ej, cur = win.st;
-        while (i > 0 && j > 0) {
-          const int d = i + j;
-          const int byte = slab[sq_diag_offset(d, la, lb) - (d - lb > 1 ? d - lb : 1) + i];
-          const int prev = (byte >> (2 * cur)) & 3;
-          if (cur == 0) {
-            const int ca = sa[i - 1], cb = sb[j - 1];
-            ++aligned, identical += ca == cb && ca != FDIPT_SEQ_LETTERS - 1;
-            map[j - 1] = i - 1, --i, --j;
-            if (LOCAL && prev == 3) break;  // the fresh start: the origin
-          } else if (cur == 1) {
-            runs += prev != 1, --i;
-          } else {
-            runs += prev != 2, map[j - 1] = -1, --j;
-          }
-          cur = prev;
-        }
-        if (!LOCAL) {  // on the boundary: a corner is the origin; a leading gap that is not free is walked and counted
-          if (j == 0 && i > 0 && !a_left) ++runs, i = 0;
-          else if (i == 0 && j > 0 && !b_left) {
-            ++runs;
-            for (; j > 0; --j) map[j - 1] = -1;
-          }
-        }
-        bi = i, bj = j;
-      }
-      bj = __shfl(bj, 0, FD_WAVE);
-      for (int j = lane; j < bj; j += FD_WAVE) a.alignment[p * Nb + j] = -1;
-      if (lane == 0) {
-        a.score[p] = win.s, a.n_aligned[p] = aligned, a.n_identical[p] = identical;
-        a.n_gaps_a[p] = ej - bj - aligned, a.n_gaps_b[p] = ei - bi - aligned, a.n_gap_runs[p] = runs;
-        a.begin_a[p] = bi, a.end_a[p] = ei, a.begin_b[p] = bj, a.end_b[p] = ej;
-        a.status[p] = aligned ? status : status | FDIPT_SEQ_NO_ALIGNED;
-      }
-    } else if (best.d == win.d && best.i == win.i) {  // the one lane that met the winning cell
-      const int aligned = (int)(best.c & 0xffffu), bi = (int)(best.o >> 12), bj = (int)(best.o & 0xfffu);
-      a.score[p] = win.s, a.n_aligned[p] = aligned, a.n_identical[p] = (int)(best.c >> 16);
-      a.n_gaps_a[p] = ej - bj - aligned, a.n_gaps_b[p] = ei - bi - aligned, a.n_gap_runs[p] = (int)best.r;
-      a.begin_a[p] = bi, a.end_a[p] = ei, a.begin_b[p] = bj, a.end_b[p] = ej;
-      a.status[p] = aligned ? status : status | FDIPT_SEQ_NO_ALIGNED;
-    }
-  }
+  seq_align_body<MODE == FDIPT_SEQ_MODE_LOCAL ? SQ_LOCAL : SQ_ENDS, TRACE>(a, W, wpb);
 }
 
 extern "C" size_t fdipt_seq_align_modes_workspace_bytes(int P, int max_len_a, int max_len_b, int traceback, size_t max_workspace_bytes) {
-  return sq_workspace_bytes(P, max_len_a, max_len_b, traceback, max_workspace_bytes, SQM_EXTRA);
-}
-
-template <int MODE, bool TRACE>
-static int sqm_launch(const FdiptSeqAlignModeArgs* a, int W, int wpb, size_t lds, hipStream_t stream) {
-  static FdPerDevice attr_dev;
-  const int dev_ = fd_device();
-  if (lds > 64 * 1024 && !attr_dev.get(dev_)) {
-    if (hipFuncSetAttribute((const void*)seq_align_modes_kernel<MODE, TRACE>, hipFuncAttributeMaxDynamicSharedMemorySize, SQ_LDS_MAX) != hipSuccess) return FDIPT_ELAUNCH;
-    attr_dev.set(dev_, 1);
-  }
-  hipLaunchKernelGGL((seq_align_modes_kernel<MODE, TRACE>), dim3((unsigned)cdiv(W, wpb)), dim3((unsigned)(wpb * FD_WAVE)), lds, stream, *a, W, wpb);
-  FD_CHECK_LAUNCH();
-  return FDIPT_OK;
-}
-
-template <int MODE>
-static int sqm_launch_mode(const FdiptSeqAlignModeArgs* a, int W, int wpb, size_t lds, hipStream_t stream) {
-  return a->traceback ? sqm_launch<MODE, true>(a, W, wpb, lds, stream) : sqm_launch<MODE, false>(a, W, wpb, lds, stream);
+  return sq_workspace_bytes(P, max_len_a, max_len_b, traceback, max_workspace_bytes, sq_extra(SQ_ENDS));
 }
 
 extern "C" int fdipt_seq_align_modes(const FdiptSeqAlignModeArgs* a, fdipt_stream_t stream) {
-  if (!a || a->S_a < 1 || a->N_a < 1 || a->P < 1 || !a->seq_a || !a->len_a || !a->pairs || !a->table) return FDIPT_EINVAL;
-  if (a->seq_b && (a->S_b < 1 || a->N_b < 1 || !a->len_b)) return FDIPT_EINVAL;
-  if (!a->score || !a->n_aligned || !a->n_identical || !a->n_gaps_a || !a->n_gaps_b || !a->n_gap_runs || !a->status) return FDIPT_EINVAL;
-  if (!a->begin_a || !a->end_a || !a->begin_b || !a->end_b) return FDIPT_EINVAL;
-  if (a->traceback && !a->alignment) return FDIPT_EINVAL;
+  // (this entry's own checks come first; every refusal up to the size check is FDIPT_EINVAL, so their order decides nothing)
+  if (!a || !a->begin_a || !a->end_a || !a->begin_b || !a->end_b) return FDIPT_EINVAL;
   if (a->mode != FDIPT_SEQ_MODE_GLOBAL && a->mode != FDIPT_SEQ_MODE_SEMIGLOBAL && a->mode != FDIPT_SEQ_MODE_LOCAL) return FDIPT_EINVAL;
   if (a->free_ends < 0 || a->free_ends > 15 || (a->free_ends && a->mode != FDIPT_SEQ_MODE_SEMIGLOBAL)) return FDIPT_EINVAL;
-  if (a->open_gap > 0 || a->extend_gap > 0 || a->open_gap < -FDIPT_SEQ_MAX_HALF_UNITS || a->extend_gap < -FDIPT_SEQ_MAX_HALF_UNITS) return FDIPT_EINVAL;
-  if (a->max_len_a < 0 || a->max_len_b < 0) return FDIPT_EINVAL;
-  if (a->max_len_a > FDIPT_SEQ_MAX_ROWS || a->max_len_b > FDIPT_SEQ_MAX_ROWS) return FDIPT_ESIZE;
-  if (a->max_len_a > a->N_a || a->max_len_b > (a->seq_b ? a->N_b : a->N_a)) return FDIPT_EINVAL;
-  int wpb;
+  int rc = sq_check_args(a), W, wpb;
   size_t lds;
-  int W = sq_plan(a->P, a->max_len_a, a->max_len_b, a->traceback != 0, SQM_EXTRA, wpb, lds);
-  if (W < 1) return FDIPT_ESIZE;
-  const size_t slab = (size_t)a->max_len_a * a->max_len_b;
-  if (a->traceback && slab) {
-    if (!a->workspace || a->workspace_bytes < slab) return FDIPT_ESIZE;
-    if ((size_t)W > a->workspace_bytes / slab) W = (int)(a->workspace_bytes / slab);
-  }
-  // (free_ends = 0 is the global mode: one instantiation serves both)
-  if (a->mode == FDIPT_SEQ_MODE_LOCAL) return sqm_launch_mode<FDIPT_SEQ_MODE_LOCAL>(a, W, wpb, lds, (hipStream_t)stream);
-  return sqm_launch_mode<FDIPT_SEQ_MODE_SEMIGLOBAL>(a, W, wpb, lds, (hipStream_t)stream);
+  if (rc != FDIPT_OK || (rc = sq_plan_launch(a, sq_extra(SQ_ENDS), W, wpb, lds)) != FDIPT_OK) return rc;
+  static FdPerDevice attr_dev[2][2];  // per kernel
+  static void (*const kernels[2][2])(FdiptSeqAlignModeArgs, int, int) = {
+      {seq_align_modes_kernel<FDIPT_SEQ_MODE_SEMIGLOBAL, false>, seq_align_modes_kernel<FDIPT_SEQ_MODE_SEMIGLOBAL, true>},
+      {seq_align_modes_kernel<FDIPT_SEQ_MODE_LOCAL, false>, seq_align_modes_kernel<FDIPT_SEQ_MODE_LOCAL, true>}};
+  const int local = a->mode == FDIPT_SEQ_MODE_LOCAL, trace = a->traceback != 0;
+  return sq_launch(kernels[local][trace], attr_dev[local][trace], a, W, wpb, lds, (hipStream_t)stream);
 }
