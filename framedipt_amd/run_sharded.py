@@ -22,6 +22,7 @@ of the world size (framedipt_amd/sharding.py).
 from __future__ import annotations
 
 import argparse
+import collections
 import json
 import os
 import time
@@ -146,6 +147,101 @@ def group_records_by_name(records):
     return {name: sorted(rs, key=lambda x: (x["sample_i"], x["item"])) for name, rs in groups.items()}
 
 
+# ---- what the rank-0 stages below share: batches of gathered entries (NumPy only) and the two file writers -------------------------
+
+def rows_that_exist(it):
+    """[n] float32: the gathered entry's res_mask, ones where it has none."""
+    return np.ones(it["prot"].shape[0], dtype=np.float32) if it.get("res_mask") is None else np.asarray(it["res_mask"], dtype=np.float32)
+
+
+def diffused_rows_that_exist(it):
+    """[n] float32: the entry's diffused rows among those that exist."""
+    return np.asarray(it["diffused"], dtype=np.float32) * rows_that_exist(it)
+
+
+def padded_batch(entries, **dtypes):
+    """``entries``: [(atom37 [n,37,3], gathered entry)] -> (prot [B,n_max,37,3] float32, then one [B,n_max] array of the given dtype per
+    keyword in their order), every sample zero-padded to the longest.  ``diffused``: the entry's value; ``res_mask``: 1 where the entry has
+    none; ``chain_idx`` and ``aatype``: rounded, 0 where the entry has none."""
+    n_max = max(pos.shape[0] for pos, _ in entries)
+    prot = np.zeros((len(entries), n_max, 37, 3), dtype=np.float32)
+    out = {k: np.zeros((len(entries), n_max), dtype=dt) for k, dt in dtypes.items()}
+    for b, (pos, it) in enumerate(entries):
+        n = pos.shape[0]
+        prot[b, :n] = pos
+        for k, rows in out.items():
+            if k == "diffused":
+                rows[b, :n] = it[k]
+            elif k == "res_mask":
+                rows[b, :n] = 1 if it.get(k) is None else it[k]
+            else:
+                rows[b, :n] = 0 if it.get(k) is None else np.rint(it[k])
+    return (prot, *out.values())
+
+
+def records_by_length(records, gathered: dict):
+    """{sample length: its records}, lengths and records in the order the records come in."""
+    by_length = {}
+    for r in records:
+        by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+    return by_length
+
+
+def stack_group(rs, gathered: dict):
+    """Records of one length -> (prot [S,L,37,3] float32, the rows that exist [S,L] float32)."""
+    items = [gathered[r["item"]] for r in rs]
+    return np.stack([it["prot"] for it in items]).astype(np.float32), np.stack([rows_that_exist(it) for it in items])
+
+
+Structure = collections.namedtuple("Structure", "g name records items truth labels structures sources")
+
+
+def structures_by_name(records, gathered: dict, selected=None):
+    """One ``Structure`` per name of ``group_records_by_name``: its index ``g``, its records and their gathered entries ``items``, the ground
+    truth (``gt`` of the first entry that has one, else None) and, row for row, ``labels`` (the sample indices as strings), ``structures``
+    (atom37 [n,37,3]) and ``sources`` (the gathered entry whose masks a row takes).  With ``selected`` (what ``run_selection`` kept) the five
+    selected structures follow the samples, each with the first sample's entry as its source."""
+    from . import selection
+    for g, (name, rs) in enumerate(group_records_by_name(records).items()):
+        items = [gathered[r["item"]] for r in rs]
+        labels, structures, sources = [str(r["sample_i"]) for r in rs], [it["prot"] for it in items], list(items)
+        if selected is not None:
+            n = items[0]["prot"].shape[0]
+            labels += list(selection.STRATEGIES)
+            structures += [selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n] for strategy in selection.STRATEGIES]
+            sources += [items[0]] * len(selection.STRATEGIES)
+        yield Structure(g, str(name), rs, items, next((it["gt"] for it in items if "gt" in it), None), labels, structures, sources)
+
+
+def number(v):
+    """A JSON value of a Python number: None for NaN."""
+    return None if v != v else v
+
+
+def numbers(values):
+    """The JSON list of an array of floats (NumPy scalars become Python's): None for NaN."""
+    return [number(v) for v in np.asarray(values).tolist()]
+
+
+def cell(v):
+    """A CSV cell: a float through ``repr``, nothing for None."""
+    return "" if v is None else repr(v) if isinstance(v, float) else v
+
+
+def write_json(out_dir: str, name: str, summary):
+    with open(os.path.join(out_dir, name), "w") as f:
+        json.dump(summary, f, indent=1)
+    return summary
+
+
+def write_csv(out_dir: str, name: str, fieldnames, rows, restval="", extrasaction="raise"):
+    import csv
+    with open(os.path.join(out_dir, name), "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=list(fieldnames), restval=restval, extrasaction=extrasaction)
+        w.writeheader()
+        w.writerows(rows)
+
+
 def run_selection(out_dir: str, records, gathered: dict, reference_layout: bool, sigma: float = 30.0, max_iterations: int = 10000, keep=None):
     """Rank 0, after the gather (``--select``): one ``selection.select_samples`` launch for every structure of the run - the samples of
     a name form a group, shorter structures are padded with undiffused rows - then ``selection.json`` (indices, weights, status per
@@ -157,15 +253,8 @@ def run_selection(out_dir: str, records, gathered: dict, reference_layout: bool,
     from . import output, selection
     by_name = group_records_by_name(records)
     order = [r for rs in by_name.values() for r in rs]
-    n_max = max(gathered[r["item"]]["prot"].shape[0] for r in order)
-    prot = np.zeros((len(order), n_max, 37, 3), dtype=np.float32)
-    mask = np.zeros((len(order), n_max), dtype=np.float32)
-    groups = np.zeros(len(order), dtype=np.int64)
-    for b, r in enumerate(order):
-        it = gathered[r["item"]]
-        n = it["prot"].shape[0]
-        prot[b, :n], mask[b, :n] = it["prot"], it["diffused"]
-        groups[b] = list(by_name).index(str(r["name"]))
+    prot, mask = padded_batch([(gathered[r["item"]]["prot"], gathered[r["item"]]) for r in order], diffused=np.float32)
+    groups = np.array([list(by_name).index(str(r["name"])) for r in order], dtype=np.int64)
     sel = selection.select_samples(prot, mask, groups, sigma=sigma, max_iterations=max_iterations)
     if keep is not None:
         keep.update(selection=sel, prot=prot)
@@ -188,9 +277,7 @@ def run_selection(out_dir: str, records, gathered: dict, reference_layout: bool,
                 chosen["file"] = os.path.relpath(str(path), out_dir)
             entry["strategies"][strategy] = chosen
         summary["structures"][name] = entry
-    with open(os.path.join(out_dir, "selection.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    return summary
+    return write_json(out_dir, "selection.json", summary)
 
 
 def run_evaluation(out_dir: str, records, gathered: dict, tcr: bool = False, selected=None):
@@ -201,31 +288,16 @@ def run_evaluation(out_dir: str, records, gathered: dict, tcr: bool = False, sel
     sample or strategy: pdb_name, sample, the scalars, then the reference's flattened per-residue columns; a structure with a region
     shorter than 4 residues has the scalars only).  Without ground truth (de novo runs) only the CA geometry checks are reported.
     Returns the summary written to ``evaluation.json``."""
-    import csv
-
-    from . import evaluation, selection
-    by_name = group_records_by_name(records)
-    rows = []  # (structure, label, atom37 [n,37,3], gathered entry)
-    for g, (name, rs) in enumerate(by_name.items()):
-        rows += [(name, str(r["sample_i"]), gathered[r["item"]]["prot"], gathered[r["item"]]) for r in rs]
-        if selected is not None:
-            first = gathered[rs[0]["item"]]
-            n = first["prot"].shape[0]
-            rows += [(name, strategy, selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n], first)
-                     for strategy in selection.STRATEGIES]
-    names = list(by_name)
-    truth = {name: next((gathered[r["item"]]["gt"] for r in rs if "gt" in gathered[r["item"]]), None) for name, rs in by_name.items()}
+    from . import evaluation
+    rows, truth = [], {}  # (structure, label, atom37 [n,37,3], gathered entry); structure -> ground truth
+    for st in structures_by_name(records, gathered, selected):
+        rows += [(st.name, label, pos, it) for label, pos, it in zip(st.labels, st.structures, st.sources)]
+        truth[st.name] = st.truth
+    names = list(truth)
     with_truth = all(t is not None for t in truth.values())
-    n_max = max(row[2].shape[0] for row in rows)
-    prot = np.zeros((len(rows), n_max, 37, 3), dtype=np.float32)
-    diffuse, res_mask, chain = (np.zeros((len(rows), n_max), dtype=dt) for dt in (np.float32, np.float32, np.int32))
-    for b, (_, _, pos, it) in enumerate(rows):
-        n = pos.shape[0]
-        prot[b, :n], diffuse[b, :n] = pos, it["diffused"]
-        res_mask[b, :n] = 1 if it.get("res_mask") is None else it["res_mask"]
-        chain[b, :n] = 0 if it.get("chain_idx") is None else np.rint(it["chain_idx"])
+    prot, diffuse, res_mask, chain = padded_batch([row[2:] for row in rows], diffused=np.float32, res_mask=np.float32, chain_idx=np.int32)
     if with_truth:
-        reference = np.zeros((len(names), n_max, 37, 3), dtype=np.float32)
+        reference = np.zeros((len(names),) + prot.shape[1:], dtype=np.float32)
         for r, name in enumerate(names):
             reference[r, :truth[name].shape[0]] = truth[name]
         res = evaluation.evaluate_samples(prot, reference, diffuse, chain, [names.index(row[0]) for row in rows], res_mask)
@@ -233,14 +305,13 @@ def run_evaluation(out_dir: str, records, gathered: dict, tcr: bool = False, sel
     else:  # (no ground truth: every sample against itself, only the geometry of the sample is reported)
         res = evaluation.evaluate_samples(prot, prot, diffuse, chain, None, res_mask)
         scalars = evaluation.GEOMETRY_SCALARS
-    number = lambda v: None if isinstance(v, float) and v != v else v  # noqa: E731  (NaN: no bond / no pair)
     summary = {"ground_truth": with_truth, "structures": {}}
     table, columns = [], ["pdb_name", "sample"] + list(scalars)
     for b, (name, label, _, _) in enumerate(rows):
         entry = summary["structures"].setdefault(name, {"regions": [list(r) for r in res["regions"][b]], "region_rows": [list(r) for r in res["region_rows"][b]],
                                                         "region_names": evaluation.default_region_names(len(res["regions"][b]), tcr), "samples": {}})
         values = {k: res[k][b].item() for k in scalars}
-        entry["samples"][label] = {k: number(v) for k, v in values.items()}
+        entry["samples"][label] = {k: number(v) for k, v in values.items()}  # (NaN: no bond / no pair)
         row = {"pdb_name": name, "sample": label, **values}
         if with_truth:
             entry["samples"][label]["region_bb_rmsd"] = res["region_bb_rmsd"][b].tolist()
@@ -250,13 +321,8 @@ def run_evaluation(out_dir: str, records, gathered: dict, tcr: bool = False, sel
                 pass
         columns += [k for k in row if k not in columns]
         table.append(row)
-    with open(os.path.join(out_dir, "evaluation.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "metrics.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=columns, restval="")
-        w.writeheader()
-        w.writerows({k: repr(v) if isinstance(v, float) else v for k, v in row.items()} for row in table)
-    return summary
+    write_csv(out_dir, "metrics.csv", columns, ({k: cell(v) for k, v in row.items()} for row in table), restval="")
+    return write_json(out_dir, "evaluation.json", summary)
 
 
 def run_violations(out_dir: str, records, gathered: dict):
@@ -265,34 +331,19 @@ def run_violations(out_dir: str, records, gathered: dict):
     rows, residue_index is the position within the sample.  Writes ``violations.json`` (per sample the scalars, the counts and the
     indices of the violating residues) and ``violations.csv`` (one row per sample: pdb_name, sample, the scalars and counts).  Returns
     the summary written to ``violations.json``."""
-    import csv
-
     from . import violations
     order = [r for rs in group_records_by_name(records).values() for r in rs]
-    n_max = max(gathered[r["item"]]["prot"].shape[0] for r in order)
-    prot = np.zeros((len(order), n_max, 37, 3), dtype=np.float32)
-    diffuse, res_mask = np.zeros((len(order), n_max), dtype=np.float32), np.zeros((len(order), n_max), dtype=np.float32)
-    for b, r in enumerate(order):
-        it = gathered[r["item"]]
-        n = it["prot"].shape[0]
-        prot[b, :n], diffuse[b, :n] = it["prot"], it["diffused"]
-        res_mask[b, :n] = 1 if it.get("res_mask") is None else it["res_mask"]
+    prot, diffuse, res_mask = padded_batch([(gathered[r["item"]]["prot"], gathered[r["item"]]) for r in order], diffused=np.float32, res_mask=np.float32)
     res = violations.structural_violations(prot, diffuse, res_mask, atoms="diffused")
-    number = lambda v: None if isinstance(v, float) and v != v else v  # noqa: E731  (NaN: no kept row)
     columns = violations.SCALARS + violations.COUNTS
     summary, table = {"atoms": "diffused", "samples": []}, []
     for b, r in enumerate(order):
         values = {k: res[k][b].item() for k in columns}
         summary["samples"].append({"pdb_name": r["name"], "sample": r["sample_i"], "n_res": int(gathered[r["item"]]["prot"].shape[0]),
-                                   **{k: number(v) for k, v in values.items()}, "residue_violations": violations.residue_violations(res, b)})
-        table.append({"pdb_name": r["name"], "sample": r["sample_i"], **{k: repr(v) if isinstance(v, float) else v for k, v in values.items()}})
-    with open(os.path.join(out_dir, "violations.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "violations.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample"] + list(columns))
-        w.writeheader()
-        w.writerows(table)
-    return summary
+                                   **{k: number(v) for k, v in values.items()}, "residue_violations": violations.residue_violations(res, b)})  # (NaN: no kept row)
+        table.append({"pdb_name": r["name"], "sample": r["sample_i"], **{k: cell(v) for k, v in values.items()}})
+    write_csv(out_dir, "violations.csv", ["pdb_name", "sample"] + list(columns), table)
+    return write_json(out_dir, "violations.json", summary)
 
 
 def run_lddt(out_dir: str, records, gathered: dict, inpainting: bool = False, selected=None):
@@ -303,60 +354,40 @@ def run_lddt(out_dir: str, records, gathered: dict, inpainting: bool = False, se
     lddt_ca, lddt_bb, drmsd, fape, region_fape); a structure without ground truth is listed as skipped.  De novo runs: per sample length
     one all-against-all call on the CA atoms: ``pairwise_lddt_ca_length_<L>.npy`` (row = model, column = reference) and
     ``consistency.json`` with every sample's mean off-diagonal lDDT and its ``consensus`` profile.  Returns the summary written."""
-    import csv
-
-    from . import lddt, selection
+    from . import lddt
     if not inpainting:
-        by_length = {}
-        for r in sorted(records, key=lambda x: x["item"]):
-            by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+        by_length = records_by_length(sorted(records, key=lambda x: x["item"]), gathered)
         summary = {"atoms": "ca", "lengths": []}
         for length in sorted(by_length):
             rs = by_length[length]
-            prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
-            mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+            prot, mask = stack_group(rs, gathered)
             res = lddt.local_accuracy(prot, atoms="ca", res_mask=mask)
             np.save(os.path.join(out_dir, f"pairwise_lddt_ca_length_{length}.npy"), res["matrix"])
             summary["lengths"].append({"length": length, "samples": [
                 {"pdb_name": r["name"], "sample": r["sample_i"], "mean_lddt": float(np.delete(res["matrix"][s], s).mean()) if len(rs) > 1 else None,
                  "consensus": res["consensus"][s].tolist()} for s, r in enumerate(rs)]})
-        with open(os.path.join(out_dir, "consistency.json"), "w") as f:
-            json.dump(summary, f, indent=1)
-        return summary
+        return write_json(out_dir, "consistency.json", summary)
     columns = ["lddt_ca", "lddt_bb", "drmsd", "fape", "region_fape"]
     summary, table = {"atoms": ["ca", "backbone"], "score_mask": "diffused rows", "samples": [], "skipped": []}, []
-    for g, (name, rs) in enumerate(group_records_by_name(records).items()):
-        items = [gathered[r["item"]] for r in rs]
-        truth = next((it["gt"] for it in items if "gt" in it), None)
-        if truth is None:
-            summary["skipped"].append(str(name))
+    for st in structures_by_name(records, gathered, selected):
+        if st.truth is None:
+            summary["skipped"].append(st.name)
             continue
-        n = items[0]["prot"].shape[0]
-        labels, structures, sources = [str(r["sample_i"]) for r in rs], [it["prot"] for it in items], list(items)
-        if selected is not None:
-            labels += list(selection.STRATEGIES)
-            structures += [selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n] for strategy in selection.STRATEGIES]
-            sources += [items[0]] * len(selection.STRATEGIES)
-        prot = np.stack(structures).astype(np.float32)
-        res_mask = np.stack([np.ones(n, dtype=np.float32) if it.get("res_mask") is None else it["res_mask"] for it in sources]).astype(np.float32)
-        score = np.stack([it["diffused"] for it in sources]).astype(np.float32) * res_mask
-        reference = np.asarray(truth, dtype=np.float32)[None]
+        prot = np.stack(st.structures).astype(np.float32)
+        res_mask = np.stack([rows_that_exist(it) for it in st.sources])
+        score = np.stack([diffused_rows_that_exist(it) for it in st.sources])
+        reference = np.asarray(st.truth, dtype=np.float32)[None]
         ca = lddt.local_accuracy(prot, reference, atoms="ca", res_mask=res_mask, score_mask=score)
         bb = lddt.local_accuracy(prot, reference, atoms="backbone", res_mask=res_mask, score_mask=score)
-        for s, label in enumerate(labels):
+        for s, label in enumerate(st.labels):
             rows = np.flatnonzero(score[s])
             values = {**lddt.lddt_metrics(ca, s), "lddt_bb": lddt.lddt_metrics(bb, s)["lddt_bb"]}
-            summary["samples"].append({"pdb_name": str(name), "sample": label, **{k: values[k] for k in columns}, "status": int(ca["status"][s] | bb["status"][s]),
+            summary["samples"].append({"pdb_name": st.name, "sample": label, **{k: values[k] for k in columns}, "status": int(ca["status"][s] | bb["status"][s]),
                                        "rows": rows.tolist(), "res_lddt_ca": ca["res_lddt"][s][rows].tolist(), "res_lddt_bb": bb["res_lddt"][s][rows].tolist(),
                                        "res_fape": ca["res_fape"][s][rows].tolist()})
-            table.append({"pdb_name": str(name), "sample": label, **{k: repr(values[k]) for k in columns}})
-    with open(os.path.join(out_dir, "lddt.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "lddt.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample"] + columns)
-        w.writeheader()
-        w.writerows(table)
-    return summary
+            table.append({"pdb_name": st.name, "sample": label, **{k: repr(values[k]) for k in columns}})
+    write_csv(out_dir, "lddt.csv", ["pdb_name", "sample"] + columns, table)
+    return write_json(out_dir, "lddt.json", summary)
 
 
 def run_interface(out_dir: str, records, gathered: dict, inpainting: bool = False, selected=None, atoms: str = "cb"):
@@ -367,45 +398,31 @@ def run_interface(out_dir: str, records, gathered: dict, inpainting: bool = Fals
     chain the flat metrics of ``interface_metrics`` and the per-row contact counts of the ligand rows) and ``interface.csv`` (one row per
     sample and chain); a structure without ground truth, without a second chain or without diffused rows is listed as skipped.  De novo
     runs have no reference complex: the flag is refused.  Returns the summary written."""
-    import csv
-
-    from . import interface, selection
+    from . import interface
     if not inpainting:
         raise SystemExit("--interface scores the samples of an inpainting run against their ground-truth complex; a de novo run has none")
     columns = ["n_native", "n_model", "n_shared", "n_interface_rows", "fnat", "fnonnat", "irmsd", "lrmsd", "dockq", "capri_class", "status"]
     summary = {"atoms": atoms, "contact_cutoff": interface.CONTACT_CUTOFF[atoms], "interface_cutoff": 10.0, "sides": "ligand: the diffused rows of a chain; receptor: the other chains",
                "contract": "DESIGN.md section 7.18 (no parity with the DockQ program is claimed)", "samples": [], "skipped": []}
     table = []
-    for g, (name, rs) in enumerate(group_records_by_name(records).items()):
-        items = [gathered[r["item"]] for r in rs]
-        truth = next((it["gt"] for it in items if "gt" in it), None)
-        n = items[0]["prot"].shape[0]
-        chain = np.zeros(n) if items[0].get("chain_idx") is None else np.rint(np.asarray(items[0]["chain_idx"]))
-        sides, chains = interface.loop_sides(np.asarray(items[0]["diffused"]) != 0, chain)
-        if truth is None or len(sides) == 0 or not (sides == interface.RECEPTOR).any():
-            summary["skipped"].append(str(name))
+    for st in structures_by_name(records, gathered, selected):
+        first = st.items[0]
+        chain = np.zeros(first["prot"].shape[0]) if first.get("chain_idx") is None else np.rint(np.asarray(first["chain_idx"]))
+        sides, chains = interface.loop_sides(np.asarray(first["diffused"]) != 0, chain)
+        if st.truth is None or len(sides) == 0 or not (sides == interface.RECEPTOR).any():
+            summary["skipped"].append(st.name)
             continue
-        labels, structures, sources = [str(r["sample_i"]) for r in rs], [it["prot"] for it in items], list(items)
-        if selected is not None:
-            labels += list(selection.STRATEGIES)
-            structures += [selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n] for strategy in selection.STRATEGIES]
-            sources += [items[0]] * len(selection.STRATEGIES)
-        res_mask = np.stack([np.ones(n, dtype=np.float32) if it.get("res_mask") is None else it["res_mask"] for it in sources]).astype(np.float32)
-        res = interface.interface_accuracy(np.stack(structures).astype(np.float32), np.asarray(truth, dtype=np.float32)[None], sides, atoms=atoms, res_mask=res_mask)
-        for s, label in enumerate(labels):
+        res_mask = np.stack([rows_that_exist(it) for it in st.sources])
+        res = interface.interface_accuracy(np.stack(st.structures).astype(np.float32), np.asarray(st.truth, dtype=np.float32)[None], sides, atoms=atoms, res_mask=res_mask)
+        for s, label in enumerate(st.labels):
             for k, c in enumerate(chains):
                 rows = np.flatnonzero(sides[k] == interface.LIGAND)
                 values = interface.interface_metrics(res, s, k)
-                summary["samples"].append({"pdb_name": str(name), "sample": label, "chain": int(c), **values, "ligand_rows": rows.tolist(),
+                summary["samples"].append({"pdb_name": st.name, "sample": label, "chain": int(c), **values, "ligand_rows": rows.tolist(),
                                            **{key: res[key][s, k][rows].tolist() for key in ("res_native", "res_model", "res_shared")}})
-                table.append({"pdb_name": str(name), "sample": label, "chain": int(c), **{key: "" if values[key] is None else repr(values[key]) for key in columns}})
-    with open(os.path.join(out_dir, "interface.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "interface.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "chain"] + columns)
-        w.writeheader()
-        w.writerows(table)
-    return summary
+                table.append({"pdb_name": st.name, "sample": label, "chain": int(c), **{key: cell(values[key]) for key in columns}})
+    write_csv(out_dir, "interface.csv", ["pdb_name", "sample", "chain"] + columns, table)
+    return write_json(out_dir, "interface.json", summary)
 
 
 def write_gdt(out_dir: str, structures: dict, skipped=()):
@@ -413,29 +430,21 @@ def write_gdt(out_dir: str, structures: dict, skipped=()):
     superposition: the frame of the fixed context; the searched superposition per cutoff), "counts_fixed" and "counts": [S,5], "status":
     [S]}.  Writes ``gdt.json`` (all of it, with the names in ``skipped``) and ``gdt.csv`` (one row per sample: pdb_name, sample,
     n_scored, gdt_ts_fixed, gdt_ha_fixed, gdt_ts, gdt_ha).  Returns the summary written to ``gdt.json``."""
-    import csv
-
     from . import gdt
-    number = lambda v: None if v != v else float(v)  # noqa: E731  (NaN: a status bit)
     summary = {"cutoffs": list(gdt.CUTOFFS), "rows": "diffused rows that exist", "superposition": "search: DESIGN.md section 7.14 (no parity with LGA is claimed)",
                "structures": {}, "skipped": [str(n) for n in skipped]}
     table = []
     for name, e in structures.items():
         summary["structures"][name] = {"samples": list(e["samples"]), "n_scored": [int(v) for v in e["n_scored"]],
-                                       "gdt_ts_fixed": [number(v) for v in e["fixed"]["gdt_ts"]], "gdt_ha_fixed": [number(v) for v in e["fixed"]["gdt_ha"]],
-                                       "gdt_ts": [number(v) for v in e["search"]["gdt_ts"]], "gdt_ha": [number(v) for v in e["search"]["gdt_ha"]],
+                                       "gdt_ts_fixed": numbers(e["fixed"]["gdt_ts"]), "gdt_ha_fixed": numbers(e["fixed"]["gdt_ha"]),
+                                       "gdt_ts": numbers(e["search"]["gdt_ts"]), "gdt_ha": numbers(e["search"]["gdt_ha"]),
                                        "counts_fixed": np.asarray(e["counts_fixed"]).tolist(), "counts": np.asarray(e["counts"]).tolist(),
                                        "status": [int(v) for v in e["status"]]}
-        table += [{"pdb_name": name, "sample": label, "n_scored": int(e["n_scored"][s]), "gdt_ts_fixed": repr(float(e["fixed"]["gdt_ts"][s])),
-                   "gdt_ha_fixed": repr(float(e["fixed"]["gdt_ha"][s])), "gdt_ts": repr(float(e["search"]["gdt_ts"][s])), "gdt_ha": repr(float(e["search"]["gdt_ha"][s]))}
+        table += [{"pdb_name": name, "sample": label, "n_scored": int(e["n_scored"][s]), "gdt_ts_fixed": cell(float(e["fixed"]["gdt_ts"][s])),
+                   "gdt_ha_fixed": cell(float(e["fixed"]["gdt_ha"][s])), "gdt_ts": cell(float(e["search"]["gdt_ts"][s])), "gdt_ha": cell(float(e["search"]["gdt_ha"][s]))}
                   for s, label in enumerate(e["samples"])]
-    with open(os.path.join(out_dir, "gdt.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "gdt.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "n_scored", "gdt_ts_fixed", "gdt_ha_fixed", "gdt_ts", "gdt_ha"])
-        w.writeheader()
-        w.writerows(table)
-    return summary
+    write_csv(out_dir, "gdt.csv", ["pdb_name", "sample", "n_scored", "gdt_ts_fixed", "gdt_ha_fixed", "gdt_ts", "gdt_ha"], table)
+    return write_json(out_dir, "gdt.json", summary)
 
 
 def run_gdt(out_dir: str, records, gathered: dict, inpainting: bool = False, selected=None):
@@ -444,37 +453,25 @@ def run_gdt(out_dir: str, records, gathered: dict, inpainting: bool = False, sel
     the diffused rows that exist, without a superposition and with the searched one, then ``write_gdt``; a structure without ground
     truth is listed as skipped.  De novo runs: per sample length one all-against-all searched call:
     ``pairwise_gdt_ts_length_<L>.npy``.  Returns the summary written (de novo: {"lengths": [...]})."""
-    from . import gdt, selection
+    from . import gdt
     if not inpainting:
-        by_length = {}
-        for r in sorted(records, key=lambda x: x["item"]):
-            by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
+        by_length = records_by_length(sorted(records, key=lambda x: x["item"]), gathered)
         for length in sorted(by_length):
-            rs = by_length[length]
-            prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
-            mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+            prot, mask = stack_group(by_length[length], gathered)
             np.save(os.path.join(out_dir, f"pairwise_gdt_ts_length_{length}.npy"), gdt.gdt_scores(prot, mask_a=mask)["matrix_ts"])
         return {"lengths": sorted(by_length)}
     structures, skipped = {}, []
-    for g, (name, rs) in enumerate(group_records_by_name(records).items()):
-        items = [gathered[r["item"]] for r in rs]
-        truth = next((it["gt"] for it in items if "gt" in it), None)
-        if truth is None:
-            skipped.append(str(name))
+    for st in structures_by_name(records, gathered, selected):
+        if st.truth is None:
+            skipped.append(st.name)
             continue
-        n = items[0]["prot"].shape[0]
-        labels, models, sources = [str(r["sample_i"]) for r in rs], [it["prot"] for it in items], list(items)
-        if selected is not None:
-            labels += list(selection.STRATEGIES)
-            models += [selection.selected_structure(selected["selection"], g, strategy, selected["prot"])[:n] for strategy in selection.STRATEGIES]
-            sources += [items[0]] * len(selection.STRATEGIES)
-        prot = np.stack(models).astype(np.float32)
-        mask = np.stack([it["diffused"] * (1 if it.get("res_mask") is None else it["res_mask"]) for it in sources]).astype(np.float32)
-        reference = np.asarray(truth, dtype=np.float32)[None]
+        prot = np.stack(st.structures).astype(np.float32)
+        mask = np.stack([diffused_rows_that_exist(it) for it in st.sources])
+        reference = np.asarray(st.truth, dtype=np.float32)[None]
         fixed = gdt.gdt_scores(prot, reference, mask_a=mask, superpose="none")
         search = gdt.gdt_scores(prot, reference, mask_a=mask, superpose="search")
-        structures[str(name)] = {"samples": labels, "n_scored": search["n_scored"], "fixed": fixed, "search": search, "counts_fixed": fixed["counts"],
-                                 "counts": search["counts"], "status": fixed["status"] | search["status"]}
+        structures[st.name] = {"samples": st.labels, "n_scored": search["n_scored"], "fixed": fixed, "search": search, "counts_fixed": fixed["counts"],
+                               "counts": search["counts"], "status": fixed["status"] | search["status"]}
     return write_gdt(out_dir, structures, skipped)
 
 
@@ -484,36 +481,19 @@ def run_secondary_structure(out_dir: str, records, gathered: dict):
     rows.  Writes ``secondary_structure.json`` (per sample the C / H / E string over the rows that exist and the four fractions of the
     reference's ``calc_mdtraj_metrics``) and ``secondary_structure.csv`` (one row per sample: pdb_name, sample, n_res, the fractions, the
     string).  Returns the summary written to ``secondary_structure.json``."""
-    import csv
-
     from . import secondary_structure as sec
     order = [r for rs in group_records_by_name(records).values() for r in rs]
-    n_max = max(gathered[r["item"]]["prot"].shape[0] for r in order)
-    prot = np.zeros((len(order), n_max, 37, 3), dtype=np.float32)
-    res_mask = np.zeros((len(order), n_max), dtype=np.float32)
-    chain, aatype = np.zeros((len(order), n_max), dtype=np.int32), np.zeros((len(order), n_max), dtype=np.int32)
-    for b, r in enumerate(order):
-        it = gathered[r["item"]]
-        n = it["prot"].shape[0]
-        prot[b, :n] = it["prot"]
-        res_mask[b, :n] = 1 if it.get("res_mask") is None else it["res_mask"]
-        chain[b, :n] = 0 if it.get("chain_idx") is None else np.rint(it["chain_idx"])
-        aatype[b, :n] = 0 if it.get("aatype") is None else np.rint(it["aatype"])
+    prot, res_mask, chain, aatype = padded_batch([(gathered[r["item"]]["prot"], gathered[r["item"]]) for r in order],
+                                                 res_mask=np.float32, chain_idx=np.int32, aatype=np.int32)
     res = sec.secondary_structure(prot, res_mask, chain, aatype)
-    number = lambda v: None if v != v else v  # noqa: E731  (NaN: no row exists)
     summary, table = {"alphabet": "C coil, H helix (alpha, 3-10, pi), E strand", "samples": []}, []
     for b, r in enumerate(order):
         values = {k: res[k][b].item() for k in sec.FRACTIONS}
         head = {"pdb_name": r["name"], "sample": r["sample_i"], "n_res": int(gathered[r["item"]]["prot"].shape[0])}
-        summary["samples"].append({**head, **{k: number(v) for k, v in values.items()}, "ss": res["ss_string"][b], "status": int(res["status"][b])})
-        table.append({**head, **{k: repr(v) for k, v in values.items()}, "ss": res["ss_string"][b]})
-    with open(os.path.join(out_dir, "secondary_structure.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "secondary_structure.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "n_res"] + list(sec.FRACTIONS) + ["ss"])
-        w.writeheader()
-        w.writerows(table)
-    return summary
+        summary["samples"].append({**head, **{k: number(v) for k, v in values.items()}, "ss": res["ss_string"][b], "status": int(res["status"][b])})  # (NaN: no row exists)
+        table.append({**head, **{k: cell(v) for k, v in values.items()}, "ss": res["ss_string"][b]})
+    write_csv(out_dir, "secondary_structure.csv", ["pdb_name", "sample", "n_res"] + list(sec.FRACTIONS) + ["ss"], table)
+    return write_json(out_dir, "secondary_structure.json", summary)
 
 
 def run_sasa(out_dir: str, records, gathered: dict, inpainting: bool = False):
@@ -524,29 +504,19 @@ def run_sasa(out_dir: str, records, gathered: dict, inpainting: bool = False):
     carries the reference's eight ASA / RSA keys against it.  Writes ``sasa.json`` (per sample the diffused rows, their ASA and RSA
     and the total) and ``sasa.csv`` (one row per sample: pdb_name, sample, n_res, total, mean ASA and mean RSA over the diffused rows).
     Returns the summary written to ``sasa.json``."""
-    import csv
-
     from . import sasa
     by_name = group_records_by_name(records)
     order = [r for rs in by_name.values() for r in rs]
 
     def batch(entries):  # [(atom37 [n,37,3], gathered entry)] -> one padded call
-        n_max = max(pos.shape[0] for pos, _ in entries)
-        prot = np.zeros((len(entries), n_max, 37, 3), dtype=np.float32)
-        res_mask, aatype = np.zeros((len(entries), n_max), dtype=np.float32), np.zeros((len(entries), n_max), dtype=np.int64)
-        for b, (pos, it) in enumerate(entries):
-            n = pos.shape[0]
-            prot[b, :n] = pos
-            res_mask[b, :n] = 1 if it.get("res_mask") is None else it["res_mask"]
-            aatype[b, :n] = 0 if not inpainting or it.get("aatype") is None else np.rint(it["aatype"])
-        return sasa.solvent_accessibility(prot, None, res_mask, aatype)
+        prot, res_mask, aatype = padded_batch(entries, res_mask=np.float32, aatype=np.int64)
+        return sasa.solvent_accessibility(prot, None, res_mask, aatype if inpainting else np.zeros_like(aatype))
 
     res = batch([(gathered[r["item"]]["prot"], gathered[r["item"]]) for r in order])
     names = list(by_name)
     truth = {name: next((gathered[r["item"]] for r in rs if "gt" in gathered[r["item"]]), None) for name, rs in by_name.items()}
     with_truth = inpainting and all(t is not None for t in truth.values())
     gt = batch([(truth[name]["gt"], truth[name]) for name in names]) if with_truth else None
-    numbers = lambda v: [None if x != x else x for x in np.asarray(v).tolist()]  # noqa: E731  (NaN: a residue type without a maximal ASA)
     summary, table = {"unit": "square Angstrom", "probe_radius": 1.40, "n_points": 100, "ground_truth": with_truth, "samples": []}, []
     for b, r in enumerate(order):
         it = gathered[r["item"]]
@@ -555,20 +525,15 @@ def run_sasa(out_dir: str, records, gathered: dict, inpainting: bool = False):
         asa, rsa = res["residue_sasa"][b, rows], res["rsa"][b, rows]
         head = {"pdb_name": r["name"], "sample": r["sample_i"], "n_res": int(n)}
         total = float(res["residue_sasa"][b, :n].sum())
-        entry = {**head, "n_atoms": int(res["n_atoms"][b]), "total": total, "rows": rows.tolist(), "asa": numbers(asa), "rsa": numbers(rsa)}
+        entry = {**head, "n_atoms": int(res["n_atoms"][b]), "total": total, "rows": rows.tolist(), "asa": numbers(asa), "rsa": numbers(rsa)}  # (NaN: a residue type without a maximal ASA)
         if with_truth:  # (the diffused rows as single-row regions: the reference's keys per residue of the diffused regions)
             metrics = sasa.sasa_metrics(gt, names.index(str(r["name"])), res, b, [(k, k) for k in rows])
             entry["metrics"] = {k: numbers(v) for k, v in metrics.items()}
         summary["samples"].append(entry)
-        mean = lambda v: repr(float(np.mean(v))) if len(v) else ""  # noqa: E731
-        table.append({**head, "total": repr(total), "mean_asa": mean(asa), "mean_rsa": mean(rsa)})
-    with open(os.path.join(out_dir, "sasa.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "sasa.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "n_res", "total", "mean_asa", "mean_rsa"])
-        w.writeheader()
-        w.writerows(table)
-    return summary
+        mean = lambda v: cell(float(np.mean(v)) if len(v) else None)  # noqa: E731
+        table.append({**head, "total": cell(total), "mean_asa": mean(asa), "mean_rsa": mean(rsa)})
+    write_csv(out_dir, "sasa.csv", ["pdb_name", "sample", "n_res", "total", "mean_asa", "mean_rsa"], table)
+    return write_json(out_dir, "sasa.json", summary)
 
 
 def write_diversity(out_dir: str, matrices: dict, tm_score_th: float = 0.5):
@@ -576,8 +541,6 @@ def write_diversity(out_dir: str, matrices: dict, tm_score_th: float = 0.5):
     per length - deliberately not the reference's cache name ``pairwise_tm_score_length_<L>.npy``: the numbers are those of the row-by-row
     correspondence, not TM-align's, and must not be picked up as such - and ``diversity.json`` / ``diversity.csv`` (length, samples,
     clusters, diversity at the threshold).  Returns the summary written to ``diversity.json``."""
-    import csv
-
     from . import tm_score
     summary = {"tm_score_th": tm_score_th, "alignment": "fixed: row i with row i (a lower bound of TM-align's score)", "lengths": []}
     for length in sorted(matrices):
@@ -586,36 +549,25 @@ def write_diversity(out_dir: str, matrices: dict, tm_score_th: float = 0.5):
         d = tm_score.diversity(matrix, tm_score_th)
         summary["lengths"].append({"length": int(length), "samples": d["samples"], "clusters": d["clusters"], "diversity": d["diversity"],
                                    "labels": d["labels"].tolist()})
-    with open(os.path.join(out_dir, "diversity.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "diversity.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["length", "samples", "clusters", "diversity"], extrasaction="ignore")
-        w.writeheader()
-        w.writerows({**e, "diversity": repr(e["diversity"])} for e in summary["lengths"])
-    return summary
+    write_csv(out_dir, "diversity.csv", ["length", "samples", "clusters", "diversity"], ({**e, "diversity": cell(e["diversity"])} for e in summary["lengths"]),
+              extrasaction="ignore")
+    return write_json(out_dir, "diversity.json", summary)
 
 
 def write_tm_table(out_dir: str, structures: dict):
     """``structures``: name -> {"samples": [labels], "tm_score": [S] against the ground truth over the diffused rows, "n_aligned": [S],
     "matrix": [S,S] among the structure's samples}.  Writes ``tm_score.json`` (all of it) and ``tm_score.csv`` (one row per sample:
     pdb_name, sample, n_aligned, tm_score).  Returns the summary written to ``tm_score.json``."""
-    import csv
-    number = lambda v: None if v != v else float(v)  # noqa: E731  (NaN: fewer than 3 rows)
     summary = {"alignment": "fixed: row i with row i over the diffused rows", "structures": {}}
     table = []
     for name, e in structures.items():
-        summary["structures"][name] = {"samples": list(e["samples"]), "tm_score": [number(v) for v in e["tm_score"]],
+        summary["structures"][name] = {"samples": list(e["samples"]), "tm_score": numbers(e["tm_score"]),  # (NaN: fewer than 3 rows)
                                        "n_aligned": [int(v) for v in e["n_aligned"]],
-                                       "matrix": [[number(v) for v in row] for row in np.asarray(e["matrix"], dtype=np.float64)]}
-        table += [{"pdb_name": name, "sample": label, "n_aligned": int(n), "tm_score": repr(float(v))}
+                                       "matrix": [numbers(row) for row in np.asarray(e["matrix"], dtype=np.float64)]}
+        table += [{"pdb_name": name, "sample": label, "n_aligned": int(n), "tm_score": cell(float(v))}
                   for label, n, v in zip(e["samples"], e["n_aligned"], e["tm_score"])]
-    with open(os.path.join(out_dir, "tm_score.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "tm_score.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["pdb_name", "sample", "n_aligned", "tm_score"])
-        w.writeheader()
-        w.writerows(table)
-    return summary
+    write_csv(out_dir, "tm_score.csv", ["pdb_name", "sample", "n_aligned", "tm_score"], table)
+    return write_json(out_dir, "tm_score.json", summary)
 
 
 def run_tm_score(out_dir: str, records, gathered: dict, inpainting: bool = False, tm_score_th: float = 0.5):
@@ -625,28 +577,22 @@ def run_tm_score(out_dir: str, records, gathered: dict, inpainting: bool = False
     all-against-all call among the structure's samples over the same rows, then ``write_tm_table``.  Returns the summary written."""
     from . import tm_score
     if not inpainting:
-        by_length = {}
-        for r in records:
-            by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
         matrices = {}
-        for length, rs in by_length.items():
-            prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
-            mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+        for length, rs in records_by_length(records, gathered).items():
+            prot, mask = stack_group(rs, gathered)
             matrices[length] = tm_score.tm_scores(prot, mask_a=mask)["matrix"]
         return write_diversity(out_dir, matrices, tm_score_th)
     structures = {}
-    for name, rs in group_records_by_name(records).items():
-        items = [gathered[r["item"]] for r in rs]
-        prot = np.stack([it["prot"] for it in items]).astype(np.float32)
-        mask = np.stack([it["diffused"] * (1 if it.get("res_mask") is None else it["res_mask"]) for it in items]).astype(np.float32)
-        truth = next((it["gt"] for it in items if "gt" in it), None)
-        entry = {"samples": [str(r["sample_i"]) for r in rs], "matrix": tm_score.tm_scores(prot, mask_a=mask)["matrix"]}
-        if truth is not None:
-            against = tm_score.tm_scores(prot, np.asarray(truth, dtype=np.float32)[None], mask_a=mask)
+    for st in structures_by_name(records, gathered):
+        prot = np.stack(st.structures).astype(np.float32)
+        mask = np.stack([diffused_rows_that_exist(it) for it in st.items])
+        entry = {"samples": st.labels, "matrix": tm_score.tm_scores(prot, mask_a=mask)["matrix"]}
+        if st.truth is not None:
+            against = tm_score.tm_scores(prot, np.asarray(st.truth, dtype=np.float32)[None], mask_a=mask)
             entry.update(tm_score=against["tm"], n_aligned=against["n_aligned"])
         else:
-            entry.update(tm_score=np.full(len(rs), np.nan), n_aligned=mask.sum(1).astype(np.int64))
-        structures[str(name)] = entry
+            entry.update(tm_score=np.full(len(st.records), np.nan), n_aligned=mask.sum(1).astype(np.int64))
+        structures[st.name] = entry
     return write_tm_table(out_dir, structures)
 
 
@@ -660,8 +606,6 @@ def write_diversity_aligned(out_dir: str, aligned: dict, fixed: dict, tm_score_t
     score: a length with such pairs is written but not clustered (``clusters`` and ``diversity`` null).  ``skipped``: lengths beyond the
     row limit of the search; ``inits``: the search's mode (``--tm-inits``), recorded.  Returns the summary written to
     ``diversity_aligned.json``."""
-    import csv
-
     from . import tm_score
     summary = {"tm_score_th": tm_score_th, "alignment": "searched (DESIGN.md section 7.9; no parity with tmtools.tm_align is claimed), "
                "the fixed row-by-row score where it is larger", "inits": str(inits), "lengths": [], "skipped_lengths": [int(v) for v in skipped]}
@@ -676,27 +620,19 @@ def write_diversity_aligned(out_dir: str, aligned: dict, fixed: dict, tm_score_t
             d = tm_score.diversity(matrix, tm_score_th)
             entry.update(clusters=d["clusters"], diversity=d["diversity"], labels=d["labels"].tolist())
         summary["lengths"].append(entry)
-    with open(os.path.join(out_dir, "diversity_aligned.json"), "w") as fh:
-        json.dump(summary, fh, indent=1)
-    with open(os.path.join(out_dir, "diversity_aligned.csv"), "w", newline="") as fh:
-        w = csv.DictWriter(fh, fieldnames=["length", "samples", "clusters", "diversity", "fixed_won", "nan_pairs"], extrasaction="ignore")
-        w.writeheader()
-        w.writerows({**e, "diversity": "" if e["diversity"] is None else repr(e["diversity"]), "clusters": "" if e["clusters"] is None else e["clusters"]}
-                    for e in summary["lengths"])
-    return summary
+    write_csv(out_dir, "diversity_aligned.csv", ["length", "samples", "clusters", "diversity", "fixed_won", "nan_pairs"],
+              ({**e, "diversity": cell(e["diversity"]), "clusters": cell(e["clusters"])} for e in summary["lengths"]), extrasaction="ignore")
+    return write_json(out_dir, "diversity_aligned.json", summary)
 
 
 def write_tm_align_table(out_dir: str, structures: dict, skipped=None, inits: str = "default"):
     """``structures``: name -> {"samples": [labels], "rows": the most rows any sample of the structure was aligned over, "matrix": [S,S] of
     ``tm_align`` among the structure's samples over the diffused rows}; ``skipped``: name -> rows, the structures with more diffused rows
     than the search takes; ``inits``: the search's mode, recorded.  Writes ``tm_align.json``.  Returns the summary written."""
-    number = lambda v: None if v != v else float(v)  # noqa: E731  (NaN: a status bit)
     summary = {"alignment": "searched over the diffused rows (DESIGN.md section 7.9)", "inits": str(inits), "structures": {
-        name: {"samples": list(e["samples"]), "rows": int(e["rows"]), "matrix": [[number(v) for v in row] for row in np.asarray(e["matrix"], dtype=np.float64)]}
+        name: {"samples": list(e["samples"]), "rows": int(e["rows"]), "matrix": [numbers(row) for row in np.asarray(e["matrix"], dtype=np.float64)]}  # (NaN: a status bit)
         for name, e in structures.items()}, "skipped_structures": {str(k): int(v) for k, v in (skipped or {}).items()}}
-    with open(os.path.join(out_dir, "tm_align.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    return summary
+    return write_json(out_dir, "tm_align.json", summary)
 
 
 def compact_rows(prot, mask):
@@ -723,13 +659,9 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
     from . import tm_align, tm_score
     tm_align.check_inits(inits)
     if not inpainting:
-        by_length = {}
-        for r in records:
-            by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
         aligned, fixed, skipped = {}, {}, []
-        for length, rs in by_length.items():
-            prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
-            mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
+        for length, rs in records_by_length(records, gathered).items():
+            prot, mask = stack_group(rs, gathered)
             rows, rows_mask = compact_rows(prot, mask)
             if rows.shape[1] > tm_align.MAX_ROWS:
                 skipped.append(length)
@@ -738,15 +670,12 @@ def run_tm_align(out_dir: str, records, gathered: dict, inpainting: bool = False
             fixed[length] = tm_score.tm_scores(prot, mask_a=mask)["matrix"]
         return write_diversity_aligned(out_dir, aligned, fixed, tm_score_th, skipped, inits)
     structures, skipped = {}, {}
-    for name, rs in group_records_by_name(records).items():
-        items = [gathered[r["item"]] for r in rs]
-        prot = np.stack([it["prot"] for it in items]).astype(np.float32)
-        mask = np.stack([it["diffused"] * (1 if it.get("res_mask") is None else it["res_mask"]) for it in items]).astype(np.float32)
-        rows, rows_mask = compact_rows(prot, mask)
+    for st in structures_by_name(records, gathered):
+        rows, rows_mask = compact_rows(np.stack(st.structures), np.stack([diffused_rows_that_exist(it) for it in st.items]))
         if rows.shape[1] > tm_align.MAX_ROWS:
-            skipped[str(name)] = rows.shape[1]
+            skipped[st.name] = rows.shape[1]
             continue
-        structures[str(name)] = {"samples": [str(r["sample_i"]) for r in rs], "rows": rows.shape[1], "matrix": tm_align.tm_align(rows, mask_a=rows_mask, inits=inits)["matrix"]}
+        structures[st.name] = {"samples": st.labels, "rows": rows.shape[1], "matrix": tm_align.tm_align(rows, mask_a=rows_mask, inits=inits)["matrix"]}
     return write_tm_align_table(out_dir, structures, skipped, inits)
 
 
@@ -764,18 +693,11 @@ def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1,
     written."""
     if inpainting:
         raise ValueError("--novelty is for de novo runs: a redesigned region inside a fixed context is not novel by construction")
-    import csv
-
     from . import structure_search
     db = structure_search.StructureSet.load(set_path)
-    by_length = {}
-    for r in records:
-        by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
     samples, skipped, accurate = [], [], []
-    for length, rs in by_length.items():
-        prot = np.stack([gathered[r["item"]]["prot"] for r in rs]).astype(np.float32)
-        mask = np.stack([np.ones(length, dtype=np.float32) if gathered[r["item"]].get("res_mask") is None else gathered[r["item"]]["res_mask"] for r in rs])
-        rows, rows_mask = compact_rows(prot, mask)
+    for length, rs in records_by_length(records, gathered).items():
+        rows, rows_mask = compact_rows(*stack_group(rs, gathered))
         if rows.shape[1] > structure_search.MAX_ROWS:
             skipped.append(length)
             continue
@@ -795,22 +717,15 @@ def run_novelty(out_dir: str, records, gathered: dict, set_path, top_k: int = 1,
                "query": "the sample itself (the reference searches the ESMFold refold of a sample)",
                "search": "the alignment search of DESIGN.md sections 7.9 and 7.15, pdbTM normalised by the sample's rows; no parity with foldseek is claimed",
                "samples": samples, "skipped_lengths": sorted(skipped)}
-    with open(os.path.join(out_dir, "novelty.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    with open(os.path.join(out_dir, "novelty.csv"), "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=["length", "sample", "pdbTM", "hit"])
-        w.writeheader()
-        w.writerows({"length": e["length"], "sample": e["sample"], "pdbTM": repr(e["pdbTM"]), "hit": e["hit"]} for e in samples)
+    write_csv(out_dir, "novelty.csv", ["length", "sample", "pdbTM", "hit"],
+              ({"length": e["length"], "sample": e["sample"], "pdbTM": repr(e["pdbTM"]), "hit": e["hit"]} for e in samples))
     if accuracy:
-        with open(os.path.join(out_dir, "novelty_accuracy.json"), "w") as f:
-            json.dump({"set": str(set_path), "top_k": int(top_k), "atoms": "ca", "coverage": "penalise", "superpose": "search",
-                       "reference": "the hit: lDDT charges the hit's rows the sample has no partner for, GDT is divided by the hit's rows",
-                       "hits": accurate}, f, indent=1)
-        with open(os.path.join(out_dir, "novelty_accuracy.csv"), "w", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=["length", "sample", "rank", "hit", "lddt_ca", "gdt_ts", "gdt_ha", "n_covered", "n_reference"], extrasaction="ignore")
-            w.writeheader()
-            w.writerows({**e, **{k: repr(e[k]) for k in ("lddt_ca", "gdt_ts", "gdt_ha")}} for e in accurate)
-    return summary
+        write_json(out_dir, "novelty_accuracy.json", {"set": str(set_path), "top_k": int(top_k), "atoms": "ca", "coverage": "penalise", "superpose": "search",
+                                                      "reference": "the hit: lDDT charges the hit's rows the sample has no partner for, GDT is divided by the hit's rows",
+                                                      "hits": accurate})
+        write_csv(out_dir, "novelty_accuracy.csv", ["length", "sample", "rank", "hit", "lddt_ca", "gdt_ts", "gdt_ha", "n_covered", "n_reference"],
+                  ({**e, **{k: repr(e[k]) for k in ("lddt_ca", "gdt_ts", "gdt_ha")}} for e in accurate), extrasaction="ignore")
+    return write_json(out_dir, "novelty.json", summary)
 
 
 def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, seq_per_sample: int = 8, weights=None, temperature: float = 0.1,
@@ -829,11 +744,8 @@ def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, 
     model = inverse_folding.ProteinMPNN(ca_only=ca_only)
     model = model.load_checkpoint(weights) if weights else model.load_synthetic(0)
     os.makedirs(os.path.join(out_dir, "seqs"), exist_ok=True)
-    by_length = {}
-    for r in records:
-        by_length.setdefault(int(gathered[r["item"]]["prot"].shape[0]), []).append(r)
     samples = {}
-    for length, rs in by_length.items():
+    for length, rs in records_by_length(records, gathered).items():
         for start in range(0, len(rs), max_batch):
             chunk = rs[start:start + max_batch]
             items = [gathered[r["item"]] for r in chunk]
@@ -857,16 +769,14 @@ def run_design(out_dir: str, records, gathered: dict, inpainting: bool = False, 
                 samples[stem] = {"item": r["item"], "name": r["name"], "sample_i": r["sample_i"], "n_res": length,
                                  "designed_rows": int((res["chain_mask"][b] * res["res_mask"][b]).sum()), "sequences": res["sequences"][b],
                                  "score": [float(v) for v in res["score"][b]], "global_score": [float(v) for v in res["global_score"][b]],
-                                 "seq_recovery": [None if np.isnan(v) else float(v) for v in res["seq_recovery"][b]], "status": int(res["status"][b]),
+                                 "seq_recovery": numbers(res["seq_recovery"][b]), "status": int(res["status"][b]),
                                  "fasta": fasta}
                 if native is not None:
                     samples[stem]["native_conditional_score"] = float(native[b])
                 gathered[r["item"]]["designed_sequences"] = list(res["sequences"][b])  # what --seq-diversity compares
     summary = {"weights": model.source, "synthetic": not weights, "ca_only": model.ca_only, "k_neighbors": model.k_neighbors, "temperature": temperature, "seed": seed,
                "seq_per_sample": seq_per_sample, "omit": omit_aas, "samples": samples}
-    with open(os.path.join(out_dir, "design.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    return summary
+    return write_json(out_dir, "design.json", summary)
 
 
 def write_seq_diversity(out_dir: str, owners, matrix, scoring: dict, matrix_file: str = "pairwise_seq_identity.npy"):
@@ -891,9 +801,7 @@ def write_seq_diversity(out_dir: str, owners, matrix, scoring: dict, matrix_file
                "max_identity_to_other_sample": nearest, "identity": "n_identical / min(len_a, len_b)", "scoring": scoring,
                "matrix": matrix_file}
     np.save(os.path.join(out_dir, matrix_file), matrix)
-    with open(os.path.join(out_dir, "seq_diversity.json"), "w") as f:
-        json.dump(summary, f, indent=1)
-    return summary
+    return write_json(out_dir, "seq_diversity.json", summary)
 
 
 def run_seq_diversity(out_dir: str, records, gathered: dict, matrix="blosum62", open_gap: float = -10.0, extend_gap: float = -0.5, mode: str = "global"):
@@ -979,7 +887,9 @@ def reference_layout_writer(out_dir: str, net, final_only: bool):
     return write_item
 
 
-def main():
+def parse_args(argv=None):
+    """The command line (``argv``: the arguments, default ``sys.argv[1:]``) -> the namespace ``main()`` runs on; what the flags exclude among
+    each other is refused here, before anything is loaded."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--min-length", type=int, default=300)
@@ -1075,7 +985,7 @@ def main():
                     "through the hit's alignment -> novelty_accuracy.json, novelty_accuracy.csv (novelty.json and novelty.csv do not change)")
     ap.add_argument("--tm-score-th", type=float, default=0.5, help="--tm-score, --tm-align: the TM-score threshold of the clusters (reference default)")
     ap.add_argument("--verify", type=int, default=0, help="inference_fn(verify=k): the forward of every k-th step runs twice and must reproduce its bits")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.keep not in ("all", "last"):
         try:
             a.keep = int(a.keep)
@@ -1093,6 +1003,76 @@ def main():
         ap.error("--seq-align-mode is the mode of --seq-diversity")
     if a.novelty and not 1 <= a.novelty_top_k <= 64:
         ap.error(f"--novelty-top-k {a.novelty_top_k}: expected 1 .. 64")
+    return a
+
+
+# The rank-0 stages that follow a run, in the order they run; ``main()`` knows a stage by its row alone.  ``flag``: the namespace attribute
+# that switches it on.  ``run(a, records, gathered, inp, selected)``: the call of its ``run_*`` (``inp``: an inpainting run; ``selected``: what
+# ``run_selection`` keeps for the stages that score the selected structures, None where nothing is kept) -> its summary.  ``ground_truth``:
+# in inpainting runs it needs the ground-truth atom37 of every structure (``gt`` of the gathered entries).  ``selected``: it scores the
+# selected structures.  ``report(a, done, inp, s)``: the line printed after it, ``s`` its seconds.
+Stage = collections.namedtuple("Stage", "flag run ground_truth selected report")
+STAGES = (
+    Stage("select", lambda a, recs, g, inp, sel: run_selection(a.out_dir, recs, g, reference_layout=inp, sigma=a.select_sigma, max_iterations=a.select_iterations, keep=sel),
+          False, False, lambda a, done, inp, s: f"selected structures of {len(done['structures'])} structure(s) in {s:.2f} s -> {a.out_dir}/selection.json"),
+    Stage("evaluate", lambda a, recs, g, inp, sel: run_evaluation(a.out_dir, recs, g, tcr=a.tcr, selected=sel if inp else None),
+          True, True, lambda a, done, inp, s: f"evaluated {sum(len(e['samples']) for e in done['structures'].values())} structure(s) in {s:.2f} s -> "
+                                              f"{a.out_dir}/evaluation.json, metrics.csv"),
+    Stage("violations", lambda a, recs, g, inp, sel: run_violations(a.out_dir, recs, g),
+          False, False, lambda a, done, inp, s: f"structural violations of {len(done['samples'])} sample(s) in {s:.2f} s -> {a.out_dir}/violations.json, violations.csv"),
+    Stage("secondary_structure", lambda a, recs, g, inp, sel: run_secondary_structure(a.out_dir, recs, g),
+          False, False, lambda a, done, inp, s: f"secondary structure of {len(done['samples'])} sample(s) in {s:.2f} s -> "
+                                                f"{a.out_dir}/secondary_structure.json, secondary_structure.csv"),
+    Stage("sasa", lambda a, recs, g, inp, sel: run_sasa(a.out_dir, recs, g, inpainting=inp),
+          True, False, lambda a, done, inp, s: f"solvent accessibility of {len(done['samples'])} sample(s) in {s:.2f} s -> {a.out_dir}/sasa.json, sasa.csv"),
+    Stage("tm_score", lambda a, recs, g, inp, sel: run_tm_score(a.out_dir, recs, g, inpainting=inp, tm_score_th=a.tm_score_th),
+          True, False, lambda a, done, inp, s: "TM-scores of " + (
+              f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_score.json, tm_score.csv" if inp else
+              f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity.json, diversity.csv, pairwise_tm_score_fixed_length_<L>.npy") + f" in {s:.2f} s"),
+    Stage("tm_align", lambda a, recs, g, inp, sel: run_tm_align(a.out_dir, recs, g, inpainting=inp, tm_score_th=a.tm_score_th, inits=a.tm_inits),
+          False, False, lambda a, done, inp, s: "structural alignments of " + (
+              f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_align.json" if inp else
+              f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity_aligned.json, diversity_aligned.csv, pairwise_tm_score_aligned_length_<L>.npy") + f" in {s:.2f} s"),
+    Stage("lddt", lambda a, recs, g, inp, sel: run_lddt(a.out_dir, recs, g, inpainting=inp, selected=sel if inp else None),
+          True, True, lambda a, done, inp, s: "lDDT, dRMSD and FAPE of " + (
+              f"{len(done['samples'])} structure(s) -> {a.out_dir}/lddt.json, lddt.csv" if inp else
+              f"{len(done['lengths'])} length(s) -> {a.out_dir}/consistency.json, pairwise_lddt_ca_length_<L>.npy") + f" in {s:.2f} s"),
+    Stage("gdt", lambda a, recs, g, inp, sel: run_gdt(a.out_dir, recs, g, inpainting=inp, selected=sel if inp else None),
+          True, True, lambda a, done, inp, s: "GDT-TS and GDT-HA of " + (
+              f"{len(done['structures'])} structure(s) -> {a.out_dir}/gdt.json, gdt.csv" if inp else
+              f"{len(done['lengths'])} length(s) -> {a.out_dir}/pairwise_gdt_ts_length_<L>.npy") + f" in {s:.2f} s"),
+    Stage("interface", lambda a, recs, g, inp, sel: run_interface(a.out_dir, recs, g, inpainting=inp, selected=sel, atoms=a.interface_atoms),
+          True, True, lambda a, done, inp, s: f"interface accuracy of {len(done['samples'])} (structure, chain) entr(ies) in {s:.2f} s -> "
+                                              f"{a.out_dir}/interface.json, interface.csv"),
+    Stage("novelty", lambda a, recs, g, inp, sel: run_novelty(a.out_dir, recs, g, a.novelty, top_k=a.novelty_top_k, inpainting=inp, inits=a.tm_inits,
+                                                              accuracy=a.novelty_accuracy),
+          False, False, lambda a, done, inp, s: f"novelty of {len(done['samples'])} sample(s) against {done['entries']} structure(s) in {s:.2f} s -> "
+                                                f"{a.out_dir}/novelty.json, novelty.csv"),
+    Stage("design", lambda a, recs, g, inp, sel: run_design(a.out_dir, recs, g, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights,
+                                                             omit_aas=a.omit_aas, ca_only=a.ca_only),
+          False, False, lambda a, done, inp, s: f"{a.seq_per_sample} sequence(s) for each of {len(done['samples'])} sample(s) with {'SYNTHETIC ' if done['synthetic'] else ''}"
+                                                f"{'CA-only ' if done['ca_only'] else ''}ProteinMPNN parameters{'' if done['synthetic'] else ' of ' + str(done['weights'])} "
+                                                f"in {s:.2f} s -> {a.out_dir}/seqs/<sample>.fa, design.json"),
+    # (after the design, whose sequences it compares: parse_args refuses the flag without --design)
+    Stage("seq_diversity", lambda a, recs, g, inp, sel: run_seq_diversity(a.out_dir, recs, g, mode=a.seq_align_mode),
+          False, False, lambda a, done, inp, s: f"sequence identity of {done['n_sequences']} designed sequence(s), all against all, in {s:.2f} s -> "
+                                                f"{a.out_dir}/{done['matrix']}, seq_diversity.json"),
+)
+
+Plan = collections.namedtuple("Plan", "stages collect ground_truth keep_selection")
+
+
+def stage_plan(a, inp: bool) -> Plan:
+    """What ``main()`` does after the sampling, from the namespace alone: the stages that are switched on, in their order; ``collect``: the
+    ranks keep their samples on the host and gather them on rank 0 (a stage runs); ``ground_truth``: run_rank builds the ground-truth
+    atom37 of every structure (an inpainting run with a stage that scores against it); ``keep_selection``: ``run_selection`` keeps its result
+    (``--select`` with a stage that scores the selected structures)."""
+    stages = tuple(s for s in STAGES if getattr(a, s.flag))
+    return Plan(stages, bool(stages), bool(inp) and any(s.ground_truth for s in stages), bool(a.select) and any(s.selected for s in stages))
+
+
+def main():
+    a = parse_args()
 
     import torch
     import torch.distributed as dist
@@ -1179,9 +1159,10 @@ def main():
         write_item = lambda *args, **kw: one_gpu_turn(lambda: plain_write(*args, **kw))  # noqa: E731
 
     t0 = time.perf_counter()
-    collected = {} if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt or a.interface or a.novelty else None
+    plan = stage_plan(a, inp)
+    collected = {} if plan.collect else None
     ground_truth = None
-    if (a.evaluate or a.sasa or a.tm_score or a.lddt or a.gdt or a.interface) and inp:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
+    if plan.ground_truth:  # (the ground-truth atom37 the writer builds for <pdb>_1.pdb)
         def ground_truth(feats):
             build = lambda: inference.get_atom_positions_from_rigids(net, feats["rigids_0"], feats["torsion_angles_sin_cos"][..., 2, :], feats["aatype"])[0]  # noqa: E731
             return one_gpu_turn(build) if one_gpu and world > 1 else build()
@@ -1192,7 +1173,7 @@ def main():
     if world > 1:
         dist.barrier()
     gathered = None
-    if a.select or a.evaluate or a.violations or a.secondary_structure or a.sasa or a.tm_score or a.tm_align or a.design or a.lddt or a.gdt or a.interface or a.novelty:  # (every rank takes part in the gather; rank 0 receives)
+    if plan.collect:  # (every rank takes part in the gather; rank 0 receives)
         from . import sharding
         gathered = sharding.gather_results(collected, len(ds), rank, world)
     if rank == 0:
@@ -1201,75 +1182,11 @@ def main():
                                                                 **({} if a.keep == "all" else {"keep": a.keep})})
         print(f"{sum(r['n_res'] for r in allrecs) * a.num_t / el:.0f} residue*steps/s (incl. model set-up and file output)")
         print(f"{len(ds)} samples on {world} GPU(s) in {el:.1f} s -> {a.out_dir}/manifest.json", flush=True)
-        selected = {} if a.select and (a.evaluate or a.lddt or a.gdt or a.interface) else None
-        if a.select:
+        selected = {} if plan.keep_selection else None
+        for stage in plan.stages:
             t1 = time.perf_counter()
-            done = run_selection(a.out_dir, allrecs, gathered, reference_layout=inp, sigma=a.select_sigma, max_iterations=a.select_iterations, keep=selected)
-            print(f"selected structures of {len(done['structures'])} structure(s) in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/selection.json", flush=True)
-        if a.evaluate:
-            t1 = time.perf_counter()
-            done = run_evaluation(a.out_dir, allrecs, gathered, tcr=a.tcr, selected=selected if inp else None)
-            print(f"evaluated {sum(len(e['samples']) for e in done['structures'].values())} structure(s) in {time.perf_counter() - t1:.2f} s -> "
-                  f"{a.out_dir}/evaluation.json, metrics.csv", flush=True)
-        if a.violations:
-            t1 = time.perf_counter()
-            done = run_violations(a.out_dir, allrecs, gathered)
-            print(f"structural violations of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
-                  f"{a.out_dir}/violations.json, violations.csv", flush=True)
-        if a.secondary_structure:
-            t1 = time.perf_counter()
-            done = run_secondary_structure(a.out_dir, allrecs, gathered)
-            print(f"secondary structure of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
-                  f"{a.out_dir}/secondary_structure.json, secondary_structure.csv", flush=True)
-        if a.sasa:
-            t1 = time.perf_counter()
-            done = run_sasa(a.out_dir, allrecs, gathered, inpainting=inp)
-            print(f"solvent accessibility of {len(done['samples'])} sample(s) in {time.perf_counter() - t1:.2f} s -> "
-                  f"{a.out_dir}/sasa.json, sasa.csv", flush=True)
-        if a.tm_score:
-            t1 = time.perf_counter()
-            done = run_tm_score(a.out_dir, allrecs, gathered, inpainting=inp, tm_score_th=a.tm_score_th)
-            what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_score.json, tm_score.csv" if inp else \
-                f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity.json, diversity.csv, pairwise_tm_score_fixed_length_<L>.npy"
-            print(f"TM-scores of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
-        if a.tm_align:
-            t1 = time.perf_counter()
-            done = run_tm_align(a.out_dir, allrecs, gathered, inpainting=inp, tm_score_th=a.tm_score_th, inits=a.tm_inits)
-            what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/tm_align.json" if inp else \
-                f"{len(done['lengths'])} length(s) -> {a.out_dir}/diversity_aligned.json, diversity_aligned.csv, pairwise_tm_score_aligned_length_<L>.npy"
-            print(f"structural alignments of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
-        if a.lddt:
-            t1 = time.perf_counter()
-            done = run_lddt(a.out_dir, allrecs, gathered, inpainting=inp, selected=selected if inp else None)
-            what = f"{len(done['samples'])} structure(s) -> {a.out_dir}/lddt.json, lddt.csv" if inp else \
-                f"{len(done['lengths'])} length(s) -> {a.out_dir}/consistency.json, pairwise_lddt_ca_length_<L>.npy"
-            print(f"lDDT, dRMSD and FAPE of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
-        if a.gdt:
-            t1 = time.perf_counter()
-            done = run_gdt(a.out_dir, allrecs, gathered, inpainting=inp, selected=selected if inp else None)
-            what = f"{len(done['structures'])} structure(s) -> {a.out_dir}/gdt.json, gdt.csv" if inp else \
-                f"{len(done['lengths'])} length(s) -> {a.out_dir}/pairwise_gdt_ts_length_<L>.npy"
-            print(f"GDT-TS and GDT-HA of {what} in {time.perf_counter() - t1:.2f} s", flush=True)
-        if a.interface:
-            t1 = time.perf_counter()
-            done = run_interface(a.out_dir, allrecs, gathered, inpainting=inp, selected=selected, atoms=a.interface_atoms)
-            print(f"interface accuracy of {len(done['samples'])} (structure, chain) entr(ies) in {time.perf_counter() - t1:.2f} s -> "
-                  f"{a.out_dir}/interface.json, interface.csv", flush=True)
-        if a.novelty:
-            t1 = time.perf_counter()
-            done = run_novelty(a.out_dir, allrecs, gathered, a.novelty, top_k=a.novelty_top_k, inpainting=inp, inits=a.tm_inits, accuracy=a.novelty_accuracy)
-            print(f"novelty of {len(done['samples'])} sample(s) against {done['entries']} structure(s) in {time.perf_counter() - t1:.2f} s -> "
-                  f"{a.out_dir}/novelty.json, novelty.csv", flush=True)
-        if a.design:
-            t1 = time.perf_counter()
-            done = run_design(a.out_dir, allrecs, gathered, inpainting=inp, seq_per_sample=a.seq_per_sample, weights=a.mpnn_weights, omit_aas=a.omit_aas, ca_only=a.ca_only)
-            print(f"{a.seq_per_sample} sequence(s) for each of {len(done['samples'])} sample(s) with {'SYNTHETIC ' if done['synthetic'] else ''}{'CA-only ' if done['ca_only'] else ''}ProteinMPNN parameters{'' if done['synthetic'] else ' of ' + str(done['weights'])} "
-                  f"in {time.perf_counter() - t1:.2f} s -> {a.out_dir}/seqs/<sample>.fa, design.json", flush=True)
-            if a.seq_diversity:
-                t1 = time.perf_counter()
-                done = run_seq_diversity(a.out_dir, allrecs, gathered, mode=a.seq_align_mode)
-                print(f"sequence identity of {done['n_sequences']} designed sequence(s), all against all, in {time.perf_counter() - t1:.2f} s -> "
-                      f"{a.out_dir}/{done['matrix']}, seq_diversity.json", flush=True)
+            done = stage.run(a, allrecs, gathered, inp, selected)
+            print(stage.report(a, done, inp, time.perf_counter() - t1), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -124,5 +124,9 @@ def test_run_sharded_takes_the_noise_flag():
 
     from framedipt_amd import run_sharded
     assert inspect.signature(run_sharded.run_rank).parameters["noise"].default == "host"
-    src = inspect.getsource(run_sharded.main)
-    assert '"--noise"' in src and '"noise": a.noise' in src
+    assert run_sharded.parse_args(["--out-dir", "x"]).noise == "host"
+    assert run_sharded.parse_args(["--out-dir", "x", "--noise", "device"]).noise == "device"
+    with pytest.raises(SystemExit) as done:  # (a choice of host / device)
+        run_sharded.parse_args(["--out-dir", "x", "--noise", "both"])
+    assert done.value.code == 2
+    assert '"noise": a.noise' in inspect.getsource(run_sharded.main)  # (the manifest's meta)

@@ -1,7 +1,6 @@
 """CPU tests of the interface accuracy: the NumPy restatement (tests/interface_ref.py) against closed forms, the side helpers of
 framedipt_amd/interface.py on the chain labels of the 1fyt complex, the fixture's own records, and the errors ``interface_accuracy``
 raises before torch or the library is touched."""
-import inspect
 import sys
 
 import numpy as np
@@ -184,7 +183,9 @@ def test_run_sharded_names_the_flag(monkeypatch, capsys):
     with pytest.raises(SystemExit) as done:
         run_sharded.main()
     assert done.value.code == 2 and "de novo run has none" in " ".join(capsys.readouterr().err.split())
-    src = inspect.getsource(run_sharded.main)
-    assert src.count("a.interface") >= 5 and "run_interface(" in src
+    a = run_sharded.parse_args(["--out-dir", "x", "--download-dir", "d", "--interface"])
+    for inp in (False, True):  # the samples are gathered, the stage alone runs, the ground truth is built in inpainting runs only
+        plan = run_sharded.stage_plan(a, inp)
+        assert plan.collect and [s.flag for s in plan.stages] == ["interface"] and plan.ground_truth == inp and not plan.keep_selection
     with pytest.raises(SystemExit, match="inpainting"):
         run_sharded.run_interface("x", [], {}, inpainting=False)

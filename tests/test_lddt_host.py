@@ -189,7 +189,6 @@ def test_lddt_metrics_and_consensus():
 
 def test_run_sharded_parses_the_lddt_flag(monkeypatch, capsys):
     """The flag is an option of the command line (its help names the files) and main() gathers and scores when it is set."""
-    import inspect
     import sys
 
     from framedipt_amd import run_sharded
@@ -202,5 +201,7 @@ def test_run_sharded_parses_the_lddt_flag(monkeypatch, capsys):
     with pytest.raises(SystemExit) as done:  # (a switch: it takes no value)
         run_sharded.main()
     assert done.value.code == 2
-    src = inspect.getsource(run_sharded.main)
-    assert src.count("a.lddt") >= 4 and "run_lddt(" in src
+    a = run_sharded.parse_args(["--out-dir", "x", "--lddt"])
+    for inp in (False, True):  # the samples are gathered, the stage alone runs, the ground truth is built in inpainting runs only
+        plan = run_sharded.stage_plan(a, inp)
+        assert plan.collect and [s.flag for s in plan.stages] == ["lddt"] and plan.ground_truth == inp and not plan.keep_selection

@@ -120,7 +120,6 @@ def test_violation_metrics_names_and_argument_checks():
 
 def test_run_sharded_parses_the_violations_flag(monkeypatch, capsys):
     """The flag is an option of the command line (its help names the two files) and main() gathers and scores when it is set."""
-    import inspect
     import sys
 
     from framedipt_amd import run_sharded
@@ -133,5 +132,7 @@ def test_run_sharded_parses_the_violations_flag(monkeypatch, capsys):
     with pytest.raises(SystemExit) as done:  # (a switch: it takes no value)
         run_sharded.main()
     assert done.value.code == 2
-    src = inspect.getsource(run_sharded.main)
-    assert "a.select or a.evaluate or a.violations" in src and "run_violations(a.out_dir, allrecs, gathered)" in src
+    a = run_sharded.parse_args(["--out-dir", "x", "--violations"])
+    for inp in (False, True):  # the samples are gathered, the stage alone runs, and it needs no ground truth
+        plan = run_sharded.stage_plan(a, inp)
+        assert plan.collect and [s.flag for s in plan.stages] == ["violations"] and not plan.ground_truth and not plan.keep_selection
